@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- images/sec of the Light-Head R-CNN forward path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload lighthead|resnet50]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--workload lighthead|resnet50] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+result line.  --full adds everything else: the sustained leg, the instrumented roofline repeat (and --ops), the live
+f16x3-vs-f32 parity check and the CPU baseline.
 
 One "step" = one pass of the whole hot path (backbone + RPN + proposals + PsRoiAlign + light
 head + per-class NMS) over one batch of B synthetic 480x480 images per GPU, inputs already
@@ -54,6 +58,7 @@ PEAK_HBM_GBS = 8000.0
 # SURVEY.md 8d "Bytes (minimum, each tensor once)": activations sum(in+out) per layer (136.4 + 1.7 + 5.9) M elements x 4 B,
 # PSROIAlign 1.76 + 1.2 MB, detections 80 KB; weights (44.7 M x 4 B) are amortised over the batch
 HBM_MIN_BYTES_PER_IMAGE = (136.4e6 + 1.7e6 + 5.9e6) * 4 + 1.76e6 + 1.2e6 + 80e3
+DUMP_BYTES = 60 * 10 ** 6        # --dump-outputs: all arrays together stay below 64 MB (npy headers included)
 
 
 def parse():
@@ -95,9 +100,9 @@ def parse():
     ap.add_argument('--pool', default='split', choices=['split', 'whole', 'split_all'],
                     help='entry-flow pools: horizontal half in the producing block (default, 237x237 block) or one kernel')
     ap.add_argument('--sustain-seconds', type=float, default=10.0,
-                    help='after the K timed steps: an UN-timed-for-value leg of back-to-back steps of about this many '
-                         'seconds (reported as sustained_images_per_sec), so that a utilisation sampler with a period of '
-                         'seconds sees the GPU busy whatever --steps is; 0 = off')
+                    help='with --full, after the K timed steps: an UN-timed-for-value leg of back-to-back steps of about '
+                         'this many seconds (reported as sustained_images_per_sec), so that a utilisation sampler with a '
+                         'period of seconds sees the GPU busy whatever --steps is; 0 = off')
     ap.add_argument('--ksplit', default='on', choices=['on', 'off', 'all'],
                     help='fixed split-K: narrow head GEMM (on, default), nothing (off), RPN conv as well (all) -- A/B runs')
     ap.add_argument('--cross', default='f16', choices=['f16', 'fp8'],
@@ -119,10 +124,37 @@ def parse():
                          'step (it first runs a forward over that fraction of its images, inside the timed region), so that '
                          'its bandwidth-bound entry flow meets the first stream\'s GEMM-bound middle flow; compare '
                          'median_ms_per_step')
-    ap.add_argument('--ops', action='store_true', help='also print the per-op table to stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the sustained leg, the instrumented roofline repeat, the live '
+                         'parity check and the CPU baseline (each still subject to its own --no-* / --sustain-seconds '
+                         'option); a plain run does only what the headline figure needs')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float32; a fixed '
+                         'seeded sample of the images when the whole would exceed %d MB)' % (DUMP_BYTES // 10 ** 6))
+    ap.add_argument('--ops', action='store_true', help='also print the per-op table to stderr (needs --full)')
     ap.add_argument('--no-parity', action='store_true', help='skip the live f16x3-vs-f32 GPU cross-check')
     ap.add_argument('--no-roofline', action='store_true', help='skip the instrumented eager repeat')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.ops and not args.full:
+        ap.error('--ops reads the instrumented roofline leg, which runs with --full only')
+    if not args.full:
+        args.sustain_seconds = 0
+        args.no_roofline = args.no_parity = args.no_cpu_baseline = True
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: {name: host array whose leading axis is the image} -> out_dir/<name>.npy as float32.  Above DUMP_BYTES
+    the same fixed, seeded sample of images is kept from every array."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_image = sum(a[:1].astype(np.float32).nbytes for a in arrays.values())
+    keep = max(1, DUMP_BYTES // per_image)
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, np.float32))
 
 
 def _code_only(src):
@@ -379,7 +411,7 @@ def main():
     from xdet import weights as W
     from xdet import dist as xdist
     from xdet._lib import lib, check
-    from xdet.runtime import Event, DeviceBuffer, set_precision
+    from xdet.runtime import Event, DeviceBuffer, set_precision, to_host
     ndev = ctypes.c_int()
     check(lib().xdet_device_count(ctypes.byref(ndev)))
     device = local_rank
@@ -486,6 +518,15 @@ def main():
                 # asynchronous: waits for the nets' streams on the device, overlaps the next step
                 comm.allgather_detections(ds.ptr, db.ptr, B, nc, topk, streams=[nt.stream for nt in nets],
                                           double_buffered=True)
+
+        def outputs():
+            # what the step hands its caller: every image's per-class detections (all ranks' after the all-gather)
+            if comm is not None:
+                g = comm.gathered()
+                return {'det_scores': g[..., 0], 'det_boxes': g[..., 1:]}
+            return {'det_scores': np.concatenate([to_host(nt._det_scores.ptr, (sb, nc, topk), np.float32) for nt in nets]),
+                    'det_boxes': np.concatenate([to_host(nt._det_boxes.ptr, (sb, nc, topk, 4), np.float32)
+                                                 for nt in nets])}
     else:
         from xdet.resnet import ResNet50Trunk
         weights = W.make_resnet50_weights(4321)
@@ -512,6 +553,9 @@ def main():
             g = use_graph if graph is None else graph
             for nt in (nets[:1] if only_first else nets):
                 nt.forward_device(sb, use_graph=g)
+
+        def outputs():
+            return {'features': np.concatenate([to_host(nt._out.ptr, (sb,) + nt.out_shape, np.float32) for nt in nets])}
 
     def sync_all():
         for nt in nets:
@@ -543,6 +587,8 @@ def main():
     dev_ms = evs[0].elapsed_ms(evs[K])
     if comm is not None and args.workload == 'lighthead':
         gathered = comm.gathered()                   # [world*B, C, K, 5]: proves every rank's shard arrived
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())   # before any later leg overwrites the last timed step's outputs
     dt_local = dt
     if comm is not None:
         dt = comm.max_over_ranks(dt)                 # the slowest rank's wall clock: what `value` is computed from

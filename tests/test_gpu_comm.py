@@ -178,7 +178,7 @@ def test_bench_through_the_rank_launcher(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ('import sys; sys.path.insert(0, %r); from xdet.launch import launch_ranks; '
             'sys.exit(launch_ranks([sys.executable, %r, "--gpus", "1", "--comm", "--steps", "2", "--warmup", "1", '
-            '"--batch", "16", "--no-cpu-baseline", "--no-parity"], 1, timeout=900))'
+            '"--batch", "16", "--full", "--no-cpu-baseline", "--no-parity"], 1, timeout=900))'
             % (os.path.join(root, 'x-detector_amd'), os.path.join(root, 'bench.py')))
     p = subprocess.run([sys.executable, '-c', code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1000)
     assert p.returncode == 0, p.stderr.decode()[-2000:]

@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
 bash tools/collect_profile.sh ${TAG} --ways 1 --batch 128 > /dev/null 2>&1
 bash tools/bench_lines.sh ${TAG}
-python bench.py > $O/profiles/${TAG}_bench_default_full.json 2> /dev/null
-python bench.py --no-cpu-baseline --no-parity --comm --voc-stream > $O/profiles/${TAG}_bench_comm_voc_world1.json 2>/dev/null
+python bench.py --full > $O/profiles/${TAG}_bench_default_full.json 2> /dev/null
+python bench.py --full --no-cpu-baseline --no-parity --comm --voc-stream > $O/profiles/${TAG}_bench_comm_voc_world1.json 2>/dev/null
 # single image: kernel stats + the dispatch list of one step (RPN branch on the main stream: durations without sharing)
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_b1 -- python $GRAFT_REPO_ROOT/bench.py --batch 1 --serial-rpn --steps 50 --warmup 10 --no-cpu-baseline --no-roofline --no-parity --sustain-seconds 0 > $O/${TAG}_b1.log 2>&1)
 cp "$(find $O/${TAG}_b1 -name '*kernel_stats.csv' | head -1)" $O/profiles/${TAG}_batch1_kernel_stats.csv
