@@ -93,6 +93,43 @@ int xdet_psroialign_grad(const float* rois, const float* grad_pooled, const int3
                          int N, int C, int H, int W, int R, int grid_w, int grid_h, int use_max, int feat_layout,
                          int ldc, void* stream);
 
+/* ---- RotatedPsRoiAlign forward (oriented boxes; the rotated op of libps_roi_align.so) -----
+ * Replaces op_module.rotated_ps_roi_align(inputs, rois, orders, grid_dim_width, grid_dim_height, pool_method)
+ * (REGISTER_OP cpp/PSROIPooling/rotated_ps_roi_align_op.cc:38-77; CPU functor :82-301; argument checks
+ * :320-343; CUDA kernel rotated_ps_roi_align_op.cu).  The forward is bit-exact against the CPU functor.
+ *   feat    f32 [N,C,H,W] (feat_layout 0) or [N,H,W,ldc] (feat_layout 1, first C channels used), C = gh*gw*bank
+ *   rois    f32 [N,R,8]: four vertices (y0,x0,y1,x1,y2,x2,y3,x3) in [0,1], clockwise
+ *   orders  i32 [N,R]: the first vertex.  order < 0: vertex 0, moved on by one when side0 + side2 > side1 + side3
+ *           (squared lengths, :185-203).  order >= 0: vertex (order mod 4) -- a superset of the documented [-1, 4)
+ *           (the reference indexes (2*order + k) % 8).
+ *   pooled  f32 [N,R,C] (= [N,R,gh*gw,bank]); index i32 same shape, may be NULL ('max': n_w*pool_h + pool_w of the
+ *           first maximum; 'mean': 0).  Same element order and channel mapping as xdet_psroialign_fwd.
+ * Degenerate quad (a squared side below FLT_MIN; no convexity test -- concave and self-intersecting quads pool like
+ * any other): pooled 0 and index 0, both written as the reference does (:205-211).
+ * Out-of-bounds samples (superset): where the reference reads outside the plane -- a sample coordinate <= -1, or an
+ * integer part >= the map size -- the integer cell is clamped into [0, size-1] (its +1 neighbour clamped to size-1)
+ * and the reference's fractional weights are kept.  Everywhere else, including -1 < coordinate < 0 (extrapolation
+ * with in-bounds reads), values are the reference's bit for bit.  Sample counts per bin axis are capped at H + W
+ * (never reached by a quad inside [0,1]; bounds the work of a NaN / far-out quad).
+ * Errors: the op's checks plus grid > 0 and C divisible by gh*gw (the reference divides by zero there) ->
+ * XDET_ERR_INVALID_ARG before any GPU work; HIP failures -> XDET_ERR_HIP. */
+int xdet_rotated_psroialign_fwd(const float* feat, const float* rois, const int32_t* orders, float* pooled,
+                                int32_t* index, int N, int C, int H, int W, int R, int grid_w, int grid_h, int use_max,
+                                int feat_layout, int ldc, void* stream);
+
+/* ---- RotatedPsRoiAlignGrad (training backward of the rotated op) ---------------------------
+ * Replaces op_module.rotated_ps_roi_align_grad(inputs, rois, orders, pooled_features_grad, pooled_index,
+ * grid_dim_width, grid_dim_height, pool_method) (REGISTER_OP rotated_ps_roi_align_grad_op.cc:39-60; CPU functor
+ * :221-390; checks :408-436; CUDA scatter rotated_ps_roi_align_grad_op.cu:37-170).
+ *   rois, orders as the forward; grad_pooled f32 [N,R,C]; pooled_index i32 [N,R,C] (the forward's; may be NULL for
+ *   'mean'); grad_feat f32 [N,C,H,W] (feat_layout 0) or [N,H,W,ldc] (feat_layout 1): zero-filled, then the same
+ *   bilinear weights times the upstream gradient accumulated with float atomics ('max': the sample pooled_index
+ *   names; 'mean': every sample, grad / (n_h*n_w) as the CUDA kernel scales it).  Summation order is therefore
+ *   unspecified; results agree with the reference to rounding.  Geometry and clamping as the forward. */
+int xdet_rotated_psroialign_grad(const float* rois, const int32_t* orders, const float* grad_pooled,
+                                 const int32_t* pooled_index, float* grad_feat, int N, int C, int H, int W, int R,
+                                 int grid_w, int grid_h, int use_max, int feat_layout, int ldc, void* stream);
+
 /* ---- layer objects: the tf.layers.* kernels the graph builders call ---------------------
  * xdet_conv_create: tf.layers.conv2d / dense (+ folded inference BN / bias, + ReLU)
  * (net/xception_body.py:243-265,381-400,450-475,540-558; net/resnet_v2.py:89-100).

@@ -168,6 +168,17 @@ int launch_psroialign(const float* feat, const float* rois, float* pooled, int32
 int launch_psroialign_grad(const float* rois, const float* grad_pooled, const int32_t* pooled_index, float* grad_out,
                            int N, int C, int H, int W, int R, int gw, int gh, int use_max, int layout, int ldc,
                            hipStream_t s);
+// NCHW map -> stream-ordered NHWC scratch copy (hipFreeAsync it after use); *scratch stays NULL where the direct form
+// is kept (a stream being captured, a failed allocation)
+int psroi_nhwc_scratch(const float* feat, int N, int C, int H, int W, hipStream_t s, float** scratch);
+
+// ---- RotatedPsRoiAlign (rotated_psroialign.hip) ---------------------------------------------
+int launch_rotated_psroialign(const float* feat, const float* rois, const int32_t* orders, float* pooled,
+                              int32_t* index, int N, int C, int H, int W, int R, int gw, int gh, int use_max,
+                              int layout, int ldc, hipStream_t s);
+int launch_rotated_psroialign_grad(const float* rois, const int32_t* orders, const float* grad_pooled,
+                                   const int32_t* pooled_index, float* grad_out, int N, int C, int H, int W, int R,
+                                   int gw, int gh, int use_max, int layout, int ldc, hipStream_t s);
 
 // ---- RPN tail / proposals (proposals.hip) ----------------------------------------------
 struct ProposalWorkspace {

@@ -2292,6 +2292,20 @@ int xdet_psroialign_grad(const float* rois, const float* grad_pooled, const int3
                                 feat_layout, feat_layout == 0 ? C : ldc, S(stream));
 }
 
+int xdet_rotated_psroialign_fwd(const float* feat, const float* rois, const int32_t* orders, float* pooled,
+                                int32_t* index, int N, int C, int H, int W, int R, int grid_w, int grid_h, int use_max,
+                                int feat_layout, int ldc, void* stream) {
+  return launch_rotated_psroialign(feat, rois, orders, pooled, index, N, C, H, W, R, grid_w, grid_h, use_max,
+                                   feat_layout, feat_layout == 0 ? C : ldc, S(stream));
+}
+
+int xdet_rotated_psroialign_grad(const float* rois, const int32_t* orders, const float* grad_pooled,
+                                 const int32_t* pooled_index, float* grad_feat, int N, int C, int H, int W, int R,
+                                 int grid_w, int grid_h, int use_max, int feat_layout, int ldc, void* stream) {
+  return launch_rotated_psroialign_grad(rois, orders, grad_pooled, pooled_index, grad_feat, N, C, H, W, R, grid_w,
+                                        grid_h, use_max, feat_layout, feat_layout == 0 ? C : ldc, S(stream));
+}
+
 int xdet_conv_create(void** layer, int kh, int kw, int cin, int cout, int stride, int dilation, int pad_mode,
                      int pad_t, int pad_l, const float* k, const float* scale, const float* shift, int relu_out) {
   XDET_REQUIRE(layer, "layer is NULL");

@@ -399,6 +399,30 @@ __global__ __launch_bounds__(256) void psroi_nchw_to_nhwc_kernel(const float* __
   }
 }
 
+int psroi_nhwc_scratch(const float* feat, int N, int C, int H, int W, hipStream_t s, float** scratch) {
+  *scratch = nullptr;
+  // (a stream that is being captured keeps the direct form: an allocation there would become a graph node, and a
+  // failed runtime call would invalidate the capture)
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+  if (cap != hipStreamCaptureStatusNone) return XDET_OK;
+  float* p = nullptr;
+  const size_t bytes = (size_t)N * H * W * C * sizeof(float);
+  if (hipMallocAsync(reinterpret_cast<void**>(&p), bytes, s) != hipSuccess || !p) {
+    (void)hipGetLastError();                             // no scratch: the direct form
+    return XDET_OK;
+  }
+  hipLaunchKernelGGL(psroi_nchw_to_nhwc_kernel, dim3((unsigned)cdiv(H * W, 32), (unsigned)cdiv(C, 32), (unsigned)N), dim3(256), 0, s,
+                     feat, p, C, H * W);
+  const hipError_t te = hipGetLastError();             // the transpose's own launch error, before anything else is issued
+  if (te != hipSuccess) {
+    (void)hipFreeAsync(p, s);
+    return hip_fail(te, "psroi_nchw_to_nhwc_kernel launch", __FILE__, __LINE__);
+  }
+  *scratch = p;
+  return XDET_OK;
+}
+
 int launch_psroialign(const float* feat, const float* rois, float* pooled, int32_t* index, int N, int C, int H,
                       int W, int R, int gw, int gh, int use_max, int layout, int ldc, int out_ld,
                       int rois_are_corners, hipStream_t s) {
@@ -412,26 +436,17 @@ int launch_psroialign(const float* feat, const float* rois, float* pooled, int32
   // NCHW (the reference op's layout, light_head_rfcn_eval.py:85): neighbouring channels are H * W floats apart, so every
   // lane of a gather touches its own cache line (553 us for 64 x 300 ROIs of the mixed set against 120 us for the NHWC
   // form).  With enough ROIs it pays to transpose the map once into a stream-ordered scratch allocation and run the NHWC
-  // two-channel kernel on it: same values, same arithmetic.  (An odd bank, a stream that is being
-  // captured -- an allocation there would become a graph node, and a failed runtime call would invalidate the capture --
-  // or a failed allocation keep the direct form.)
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
-  if (layout == 0 && cap == hipStreamCaptureStatusNone && (C / (gw * gh)) % 2 == 0 && C % 2 == 0 &&
-      (int64_t)R * C >= (int64_t)4 * H * W) {
+  // two-channel kernel on it: same values, same arithmetic.  (An odd bank, a stream that is being captured or a failed
+  // allocation keep the direct form: psroi_nhwc_scratch.)
+  if (layout == 0 && (C / (gw * gh)) % 2 == 0 && C % 2 == 0 && (int64_t)R * C >= (int64_t)4 * H * W) {
     float* scratch = nullptr;
-    const size_t bytes = (size_t)N * H * W * C * sizeof(float);
-    if (hipMallocAsync(reinterpret_cast<void**>(&scratch), bytes, s) == hipSuccess && scratch) {
-      hipLaunchKernelGGL(psroi_nchw_to_nhwc_kernel, dim3((unsigned)cdiv(H * W, 32), (unsigned)cdiv(C, 32), (unsigned)N), dim3(256), 0, s,
-                         feat, scratch, C, H * W);
-      const hipError_t te = hipGetLastError();           // the transpose's own launch error, before anything else is issued
-      int rc = te == hipSuccess ? XDET_OK : hip_fail(te, "psroi_nchw_to_nhwc_kernel launch", __FILE__, __LINE__);
-      if (rc == XDET_OK)
-        rc = launch_psroialign(scratch, rois, pooled, index, N, C, H, W, R, gw, gh, use_max, 1, C, out_ld, rois_are_corners, s);
+    XDET_TRY(psroi_nhwc_scratch(feat, N, C, H, W, s, &scratch));
+    if (scratch) {
+      const int rc = launch_psroialign(scratch, rois, pooled, index, N, C, H, W, R, gw, gh, use_max, 1, C, out_ld,
+                                       rois_are_corners, s);
       (void)hipFreeAsync(scratch, s);
       return rc;
     }
-    (void)hipGetLastError();                             // no scratch: the direct form below
   }
   // image n on XCD n & 7; fewer than 8 images: each image on 8 / N XCDs (see the kernel)
   const int split = (int64_t)N * R <= 2048 ? 1 : 0;      // one ROI per workgroup (see the kernel)

@@ -73,6 +73,8 @@ SIGNATURES = {
     'xdet_event_elapsed_ms': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float)]),
     'xdet_psroialign_fwd': (c_int, [PF, PF, PF, PI] + [c_int] * 12 + [c_void_p]),
     'xdet_psroialign_grad': (c_int, [PF, PF, PI, PF] + [c_int] * 10 + [c_void_p]),
+    'xdet_rotated_psroialign_fwd': (c_int, [PF, PF, PI, PF, PI] + [c_int] * 10 + [c_void_p]),
+    'xdet_rotated_psroialign_grad': (c_int, [PF, PI, PF, PI, PF] + [c_int] * 10 + [c_void_p]),
     'xdet_conv_create': (c_int, [ctypes.POINTER(c_void_p)] + [c_int] * 9 + [PF, PF, PF, c_int]),
     'xdet_conv_forward': (c_int, [c_void_p, PF, c_int, c_int, c_int, c_int, PF, c_int, PF, c_int, c_void_p]),
     'xdet_conv_out_shape': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),

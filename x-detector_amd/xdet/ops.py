@@ -82,6 +82,82 @@ def ps_roi_align_grad(inputs, rois, pooled_features_grad, pooled_index, grid_dim
     return to_host(d_out.ptr, shape, np.float32, stream)
 
 
+def _rotated_checks(inputs_shape, rois, orders, grid_dim_width, grid_dim_height, pool_method):
+    """RotatedPSROIAlignOp / RotatedPSROIAlignGradOp's OP_REQUIRES (rotated_ps_roi_align_op.cc:308-343,
+    rotated_ps_roi_align_grad_op.cc:397-436), plus a zero grid and C not divisible by gh*gw (the reference divides by
+    zero there) -> (N, C, H, W, R, grid_size)"""
+    if not isinstance(pool_method, str) or ('mean' not in pool_method and 'max' not in pool_method):
+        raise InvalidArgumentError(-1, "Need Attr pool_method to be either 'mean' or 'max', got %r" % (pool_method,))
+    if grid_dim_width < 0 or grid_dim_height < 0:
+        raise InvalidArgumentError(-1, 'Need Attr grid_dim_width/grid_dim_height >= 0')
+    if len(inputs_shape) != 4:
+        raise InvalidArgumentError(-1, "inputs must be in 'NCHW' format.")
+    if rois.ndim != 3 or rois.shape[2] != 8:
+        raise InvalidArgumentError(-1, "rois must be in 'batch_size x num_rois x 8' format.")
+    if orders.ndim != 2:
+        raise InvalidArgumentError(-1, "orders must be in 'batch_size x num_rois' format.")
+    if inputs_shape[0] != rois.shape[0]:
+        raise InvalidArgumentError(-1, "'batch_size' in inputs and rois don't match.")
+    if orders.shape != rois.shape[:2]:
+        raise InvalidArgumentError(-1, "'batch_size' or 'num_rois' in orders and rois don't match.")
+    N, C, H, W = (int(d) for d in inputs_shape)
+    gs = int(grid_dim_width) * int(grid_dim_height)
+    if gs == 0 or C % gs != 0:
+        raise InvalidArgumentError(-1, 'channels must be divisible by grid_dim_width * grid_dim_height (> 0)')
+    return N, C, H, W, rois.shape[1], gs
+
+
+def rotated_ps_roi_align(inputs, rois, orders, grid_dim_width, grid_dim_height, pool_method, stream=None):
+    """op_module.rotated_ps_roi_align (REGISTER_OP cpp/PSROIPooling/rotated_ps_roi_align_op.cc:38-77).
+
+    inputs [N,C,H,W] f32 NCHW, rois [N,R,8] four vertices (y0,x0,...,y3,x3) in [0,1] clockwise, orders [N,R] i32
+    (first vertex; -1: the one starting the shorter side pair) -> (pooled_features [N,R,gh*gw,C/(gh*gw)] f32,
+    pooled_index same shape i32).  Bit-exact against the reference's CPU functor; out-of-bounds samples and orders
+    outside [-1, 4) as include/xdet.h states.  Raises InvalidArgumentError for the cases the reference's OP_REQUIRES
+    reject (and for a zero grid or C not divisible by gh*gw)."""
+    inputs = np.asarray(inputs, np.float32)
+    rois = np.asarray(rois, np.float32)
+    orders = np.asarray(orders)
+    N, C, H, W, R, gs = _rotated_checks(inputs.shape, rois, orders, grid_dim_width, grid_dim_height, pool_method)
+    orders = np.ascontiguousarray(orders, np.int32)
+    d_in, d_roi, d_ord = to_device(inputs), to_device(rois), to_device(orders)
+    n_out = N * R * C
+    d_pool, d_idx = DeviceBuffer(max(n_out * 4, 16)), DeviceBuffer(max(n_out * 4, 16))
+    check(lib().xdet_rotated_psroialign_fwd(d_in.ptr, d_roi.ptr, d_ord.ptr, d_pool.ptr, d_idx.ptr, N, C, H, W, R,
+                                            grid_dim_width, grid_dim_height, 1 if 'max' in pool_method else 0, 0, C,
+                                            stream.handle if stream else None))
+    shape = (N, R, gs, C // gs)
+    return to_host(d_pool.ptr, shape, np.float32, stream), to_host(d_idx.ptr, shape, np.int32, stream)
+
+
+def rotated_ps_roi_align_grad(inputs, rois, orders, pooled_features_grad, pooled_index, grid_dim_width,
+                              grid_dim_height, pool_method, stream=None):
+    """op_module.rotated_ps_roi_align_grad (REGISTER_OP cpp/PSROIPooling/rotated_ps_roi_align_grad_op.cc:39-60; the
+    gradient of RotatedPsRoiAlign, cpp/PSROIPooling/test_op.py:150-162).
+
+    inputs [N,C,H,W] (only its shape is used, as in the reference), rois [N,R,8], orders [N,R],
+    pooled_features_grad / pooled_index [N,R,gh*gw,C/(gh*gw)] -> grad_output [N,C,H,W] f32 (float atomics:
+    agreement with a sequential evaluation to rounding)."""
+    shape = tuple(inputs.shape)
+    rois = np.asarray(rois, np.float32)
+    orders = np.asarray(orders)
+    grad = np.ascontiguousarray(pooled_features_grad, np.float32)
+    index = np.ascontiguousarray(pooled_index, np.int32)
+    N, C, H, W, R, gs = _rotated_checks(shape, rois, orders, grid_dim_width, grid_dim_height, pool_method)
+    if grad.shape != index.shape:
+        raise InvalidArgumentError(-1, 'pooled_index and pooled_features_grad must have the same shape')
+    if grad.shape != (N, R, gs, C // gs):
+        raise InvalidArgumentError(-1, "both pooled_index and pooled_features_grad must have the shape "
+                                       "'batch_size x num_rois x grid_size x bank_size'")
+    orders = np.ascontiguousarray(orders, np.int32)
+    d_roi, d_ord, d_grad, d_idx = to_device(rois), to_device(orders), to_device(grad), to_device(index)
+    d_out = DeviceBuffer(max(N * C * H * W * 4, 16))
+    check(lib().xdet_rotated_psroialign_grad(d_roi.ptr, d_ord.ptr, d_grad.ptr, d_idx.ptr, d_out.ptr, N, C, H, W, R,
+                                             grid_dim_width, grid_dim_height, 1 if 'max' in pool_method else 0, 0, C,
+                                             stream.handle if stream else None))
+    return to_host(d_out.ptr, shape, np.float32, stream)
+
+
 PAD_VALID, PAD_SAME, PAD_EXPLICIT = 0, 1, 2
 
 
