@@ -115,3 +115,25 @@ def test_handles_are_checked():
         check(lib().xdet_net_calibrate(net.handle, net._images.ptr, 1, ctypes.byref(k), net.stream.handle))
     with pytest.raises(InvalidArgumentError):
         check(lib().xdet_net_forward(net.handle, net._images.ptr, 1, None, None, net._out.ptr, net._out.ptr, 0, net.stream.handle))
+
+
+def test_profile_entry_points_check_the_handle_kind():
+    """xdet_profile_* name the net type in an argument: a trunk handle passed as a light-head net (kind 0) is an
+    InvalidArgumentError, not a cast to the wrong type."""
+    import ctypes
+    from xdet import weights as W
+    from xdet._lib import lib, check, InvalidArgumentError
+    from xdet.resnet import ResNet50Trunk
+    net = ResNet50Trunk(W.make_resnet50_weights(4321), image_size=96, max_batch=1)
+    n = ctypes.c_int()
+    d = (ctypes.c_double * 4096)()
+    c = (ctypes.c_int * 4096)()
+    buf = ctypes.create_string_buffer(256)
+    for call in (lambda kind: lib().xdet_profile_enable(net.handle, kind, 0),
+                 lambda kind: lib().xdet_profile_read(net.handle, kind, 4096, ctypes.byref(n), d, c, d),
+                 lambda kind: lib().xdet_profile_mfma_flops(net.handle, kind, 4096, ctypes.byref(n), d),
+                 lambda kind: lib().xdet_profile_op_name(net.handle, kind, 0, buf, 256)):
+        with pytest.raises(InvalidArgumentError):
+            check(call(0))
+        check(call(1))                                   # its own kind
+    assert n.value > 0 and buf.value

@@ -123,6 +123,21 @@ struct LayerBase {
   int device = 0; // the HIP device the weights live on (current device at creation)
 };
 
+// what one ConvLayer::forward reads and writes, everything but the geometry (unset members: absent)
+struct ConvIO {
+  const float* in = nullptr;                               // f32 input (split in registers) ...
+  const unsigned short *in_hi = nullptr, *in_lo = nullptr; // ... or the input as f16 planes (LDS-DMA kernel)
+  const unsigned short* zeros = nullptr;                   // 256 B of zeros: the planes' out-of-image taps
+  float* out = nullptr;                                    // NULL: planes only
+  const float* res = nullptr;                              // residual added in the epilogue
+  int relu_in = 0;
+  unsigned short *out_hi = nullptr, *out_lo = nullptr;     // planes copy of the output: relu?(out * pl_scale + pl_shift)
+  int planes_relu = 0;
+  const float *pl_scale = nullptr, *pl_shift = nullptr;    // (NULL: no affine)
+  int group_rows = 0, group_live_rows = 0;                 // grouped GEMM (groups > 1): rows per group, live rows of each
+  int x8 = 0, x8_exp = 0;                                  // in_lo holds x8 records (conv_params.h)
+};
+
 struct ConvLayer : LayerBase {
   int kh, kw, cin, cout, stride, dil, pad_mode, pad_t, pad_l, relu_out;
   int groups = 1;     // > 1: grouped GEMM (1x1 only): weight matrix g serves rows [g*group_rows, (g+1)*group_rows)
@@ -351,40 +366,36 @@ struct ConvLayer : LayerBase {
     return 2.0 * Ho * Wo * (double)cin * cout * kh * kw;
   }
 
-  int forward(const float* in, int N, int H, int W, int ldi, float* out, int ldo, const float* res, int relu_in,
-              hipStream_t s, const unsigned short* in_hi = nullptr, const unsigned short* in_lo = nullptr,
-              const unsigned short* zeros = nullptr, unsigned short* out_hi = nullptr,
-              unsigned short* out_lo = nullptr, int planes_relu = 0, const float* pl_scale = nullptr,
-              const float* pl_shift = nullptr, int group_rows = 0, int x8 = 0, int x8_exp = 0, int group_live_rows = 0) const {
+  int forward(const ConvIO& io, int N, int H, int W, int ldi, int ldo, hipStream_t s) const {
     XDET_REQUIRE(ldi == ld_in(), "conv: ld_in must be round_up(cin,32) (4 for cin<=4)");
     XDET_REQUIRE(ldo == ld_out(), "conv: ld_out must be round_up(cout,32)");
     ConvParams p;
-    p.in = in; p.wt = d_wt; p.wt_hi = d_wt_hi; p.wt_lo = d_wt_lo; p.out = out; p.scale = d_scale; p.shift = d_shift; p.res = res;
+    p.in = io.in; p.wt = d_wt; p.wt_hi = d_wt_hi; p.wt_lo = d_wt_lo; p.out = io.out; p.scale = d_scale; p.shift = d_shift; p.res = io.res;
     p.N = N; p.H = H; p.W = W; p.ldi = ldi; p.ldo = ldo; p.ldr = ldo;
     out_shape(H, W, &p.Ho, &p.Wo, &p.pad_t, &p.pad_l);
     XDET_REQUIRE(p.Ho > 0 && p.Wo > 0, "conv: empty output");
     p.Cin_p = cin_p; p.Kp = kp; p.Cout_pad = cout_pad;
     p.KH = kh; p.KW = kw; p.stride = stride; p.dil = dil;
     p.M = N * p.Ho * p.Wo;
-    p.relu_in = relu_in; p.relu_out = relu_out;
-    p.in_hi = in_hi; p.in_lo = in_lo; p.zeros = zeros;
-    p.out_hi = precision == PREC_F32 ? nullptr : out_hi; p.out_lo = out_lo; p.planes_relu = planes_relu;
-    p.pl_scale = pl_scale; p.pl_shift = pl_shift; p.pl_c32 = pl_c32;
+    p.relu_in = io.relu_in; p.relu_out = relu_out;
+    p.in_hi = io.in_hi; p.in_lo = io.in_lo; p.zeros = io.zeros;
+    p.out_hi = precision == PREC_F32 ? nullptr : io.out_hi; p.out_lo = io.out_lo; p.planes_relu = io.planes_relu;
+    p.pl_scale = io.pl_scale; p.pl_shift = io.pl_shift; p.pl_c32 = pl_c32;
     p.group_rows = 0; p.group_wt_stride = 0;
     if (groups > 1) {
-      XDET_REQUIRE(in_hi && group_rows > 0 && group_rows % 128 == 0 && (int64_t)group_rows * groups == p.M,
+      XDET_REQUIRE(io.in_hi && io.group_rows > 0 && io.group_rows % 128 == 0 && (int64_t)io.group_rows * groups == p.M,
                    "conv(grouped): M must be groups * group_rows, group_rows a multiple of 128, input as planes");
-      p.group_rows = group_rows;
+      p.group_rows = io.group_rows;
       p.group_wt_stride = (long long)cout_pad * kp;
-      p.group_live_rows = group_live_rows;
+      p.group_live_rows = io.group_live_rows;
     }
     if (precision == PREC_F32) return launch_conv_mfma_f32(p, small_cin, n_tile, s);
-    if (in_hi) {   // A operand already split into f16 planes by its producer: LDS-DMA kernel
-      XDET_REQUIRE(!small_cin && relu_in == 0, "conv(dma): needs >= 32 input channels and no ReLU-on-load");
+    if (io.in_hi) {   // A operand already split into f16 planes by its producer: LDS-DMA kernel
+      XDET_REQUIRE(!small_cin && io.relu_in == 0, "conv(dma): needs >= 32 input channels and no ReLU-on-load");
       p.wt_hi = d_wt_hi_b; p.wt_lo = d_wt_lo_b;   // K-blocked copies
-      if (x8) {                                   // `in_lo` holds [hi8 | lo8] records: the cross terms run on the fp8 MFMA
+      if (io.x8) {                                // `in_lo` holds [hi8 | lo8] records: the cross terms run on the fp8 MFMA
         XDET_REQUIRE(d_wt_x8_b && precision == PREC_F16X3 && ksplit < 1, "conv: x8 planes need a pointwise f16x3 layer without a split-K");
-        p.wt_lo = d_wt_x8_b; p.x8 = 1; p.x8_exp = x8_exp;
+        p.wt_lo = d_wt_x8_b; p.x8 = 1; p.x8_exp = io.x8_exp;
       }
       if (ksplit >= 1 && groups == 1) {
         // a split-K layer's summation tree is part of its definition: a batch whose planes leave the kernel's 4 GiB
@@ -450,6 +461,70 @@ struct Buf {
   size_t per_image() const { return (size_t)H * W * ld; }
 };
 
+// How Plan::add_conv writes its output besides the f32 tensor (the default: f32 only).  Builders set it when they know the
+// output's consumers.
+struct ConvEmit {
+  // 1 = the conv also writes its output as split planes (a consumer on the LDS-DMA path then needs no split pass), 2 = the
+  // planes hold relu(output) (for a consumer that applies ReLU on load), 3 = planes ONLY: every consumer is on the LDS-DMA
+  // path, the f32 tensor is never written
+  int planes = 0;
+  // planes == 3: the planes go into channel blocks [0, ld_out/32) of THIS wider planes tensor (same pixels) instead of a
+  // tensor of their own -- the left part of a concatenated operand [this conv's output | what another op wrote]
+  const Buf* into = nullptr;
+  // host, ld floats each: the planes copy is relu(out * scale + shift), a following BN+ReLU pre-activation folded into this
+  // conv's epilogue
+  const std::vector<float>* bn_scale = nullptr;
+  const std::vector<float>* bn_shift = nullptr;
+  // non-NULL: the planes copy is only read by the three-launch form of the next block -- a forward in which planes_dropped()
+  // says that block runs fused (resnet_bneck.hip makes its own pre-activation from the f32 tensor) does not write it.
+  // add_conv stores the planes_drop_ok entry it registered here (-1: none).
+  int* optional = nullptr;
+  bool ksplit = false;         // a split-K candidate (plans that split only some layers)
+};
+
+// Captured forwards of a plan.  A graph bakes in every pointer it was recorded with (and the per-forward decisions), so the
+// key holds all of them; the cache is bounded, oldest-first eviction.
+struct GraphCache {
+  typedef std::array<uintptr_t, 6> Key;
+  static constexpr size_t kMax = 8;
+  std::map<Key, hipGraphExec_t> execs;
+  std::vector<Key> order;      // capture order, for eviction
+  void clear() {
+    for (auto& g : execs) (void)hipGraphExecDestroy(g.second);
+    execs.clear();
+    order.clear();
+  }
+  // replay the graph of `key` on s; without one, capture `forward` on s first
+  int launch(const Key& key, hipStream_t s, const std::function<int()>& forward) {
+    auto it = execs.find(key);
+    if (it == execs.end()) {
+      if (execs.size() >= kMax) {
+        const Key old = order.front();
+        order.erase(order.begin());
+        (void)hipGraphExecDestroy(execs[old]);
+        execs.erase(old);
+      }
+      hipGraph_t g = nullptr;
+      XDET_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+      const int rc = forward();
+      const hipError_t e = hipStreamEndCapture(s, &g);
+      if (rc != XDET_OK || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
+        if (rc != XDET_OK) return rc;
+        XDET_HIP(e);
+      }
+      hipGraphExec_t ge = nullptr;
+      const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(g);
+      XDET_HIP(ei);
+      it = execs.emplace(key, ge).first;
+      order.push_back(key);
+    }
+    XDET_HIP(hipGraphLaunch(it->second, s));
+    return XDET_OK;
+  }
+};
+
 struct Op {
   std::string name;
   int stage;
@@ -475,8 +550,10 @@ struct Plan {
   std::vector<std::unique_ptr<LayerBase>> layers;
   std::vector<Op> ops;
   WeightMap w;
+  GraphCache graphs;
 
   virtual ~Plan() {
+    graphs.clear();
     for (void* p : allocs) (void)hipFree(p);
   }
   size_t allocated_bytes = 0;
@@ -485,6 +562,13 @@ struct Plan {
     allocated_bytes += std::max<size_t>(bytes, 256);
     if (zero) XDET_HIP(hipMemset(*out, 0, std::max<size_t>(bytes, 256)));
     allocs.push_back(*out);
+    return XDET_OK;
+  }
+  // a plan-owned device copy of a host vector
+  template <class T>
+  int upload(const std::vector<T>& h, T** d) {
+    XDET_TRY(alloc_bytes(h.size() * sizeof(T), reinterpret_cast<void**>(d), false));
+    XDET_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return XDET_OK;
   }
   // ---- workspace ----
@@ -585,6 +669,15 @@ struct Plan {
       (*shift)[c] = b->v[c] - m->v[c] * sc + (bias ? bias[c] * sc : 0.f);
     }
     return XDET_OK;
+  }
+  // fold_bn zero-padded to `ld` channels and uploaded (the host copies stay in *scale / *shift)
+  int upload_bn(const std::string& bn, int C, int ld, float eps, std::vector<float>* scale, std::vector<float>* shift,
+                float** d_scale, float** d_shift) {
+    XDET_TRY(fold_bn(bn, C, eps, nullptr, scale, shift));
+    scale->resize(ld, 0.f);
+    shift->resize(ld, 0.f);
+    XDET_TRY(upload(*scale, d_scale));
+    return upload(*shift, d_shift);
   }
 
   // ---- activation pre-scale of the split-precision operands ----
@@ -786,35 +879,17 @@ struct Plan {
   }
 
   // ---- op builders ----
-  // Set by a builder right before add_conv / conv_bn when it knows the output feeds a conv on the
-  // LDS-DMA path: 1 = the conv also writes its output as split planes (the consumer then needs no
-  // split pass), 2 = the planes hold relu(output) (for a consumer that applies ReLU on load),
-  // 3 = planes ONLY: every consumer is on the LDS-DMA path, the f32 tensor is never written.
-  // With emit_bn_scale/shift set (device arrays, ld floats) the planes copy is relu(out*scale+shift):
-  // a following BN+ReLU pre-activation folded into this conv's epilogue.
-  int emit_planes_next = 0;
-  // With emit_planes_next = 3: the planes go into channel blocks [0, ld_out/32) of THIS wider planes tensor (same pixels) instead
-  // of a tensor of their own -- the left part of a concatenated operand [this conv's output | what another op wrote]
-  const Buf* emit_planes_into = nullptr;
-  std::vector<float> emit_bn_scale, emit_bn_shift;   // host, ld floats each (empty: no folded BN)
-  // Set by a builder right before add_conv: the planes copy of this conv's output is only read by the three-launch form of
-  // the next block -- a forward in which planes_dropped() says that block runs fused (resnet_bneck.hip makes its own
-  // pre-activation from the f32 tensor) does not write it
-  bool planes_optional_next = false;
   std::vector<char> planes_drop_ok;      // per registered conv: its one planes reader turned out to be a kernel that does not read them
-  int last_optional_idx = -1;            // index the last add_conv registered (-1: it registered nothing)
   virtual bool planes_dropped() const { return false; }
   // Split-K policy (conv_mfma_ksplit.hip).  ksplit_design_batch > 0: a conv whose grid at THAT batch size (a constant
   // of the plan: 8 for the ResNet trunk = BASELINE config 2, 1 for the detector's single-image latency path) leaves
   // most of the 256 CUs idle gets its K steps cut into S ranges, S = what fills the chip at the design batch, at
   // least 8 steps per range.  S depends on the layer and the plan constant only -- never on the batch of a call.
   int ksplit_design_batch = 0;
-  bool ksplit_next = false;            // builders of plans that split only some layers set this before add_conv
-  bool ksplit_all = false;
+  bool ksplit_all = false;             // false: only the layers a builder marks (ConvEmit::ksplit) are candidates
   static int pow2_floor(int64_t v) { int r = 1; while ((int64_t)r * 2 <= v) r *= 2; return r; }
-  int maybe_ksplit(ConvLayer* L, int Hi, int Wi, int Ho, int Wo) {
-    const bool want = ksplit_design_batch > 0 && (ksplit_all || ksplit_next);
-    ksplit_next = false;
+  int maybe_ksplit(ConvLayer* L, int Hi, int Wi, int Ho, int Wo, bool marked) {
+    const bool want = ksplit_design_batch > 0 && (ksplit_all || marked);
     if (!want || !L->dma_capable() || L->groups != 1 || L->cout_pad % 64 != 0) return XDET_OK;
     if (!conv_ksplit_supported(L->kh, L->kw, (int64_t)max_batch * Hi * Wi, L->ld_in(), L->cin_p, L->cout_pad)) return XDET_OK;
     const int bn = L->cout_pad % 128 == 0 ? 128 : 64, nk = L->kp / 32;
@@ -844,12 +919,11 @@ struct Plan {
     // scratch: borrowed from the plan -- bound in finish_ksplit() once every layer's need is known
     XDET_TRY(L->enable_ksplit(1, 448 / S));
     L->ksplit = S;
-    ks_layers.push_back({L, ks_on_aux_stream});
+    ks_layers.push_back({L, ws_pool == 1});        // (a layer of the side stream borrows that stream's slab)
     return XDET_OK;
   }
   struct KsLayer { ConvLayer* L; bool aux; };
   std::vector<KsLayer> ks_layers;
-  bool ks_on_aux_stream = false;       // builders set this around layers that run on the side stream (the RPN branch)
   float* ks_slab[2] = {nullptr, nullptr};
   int* ks_ticket[2] = {nullptr, nullptr};
   // one slab per stream (main / side), sized for the largest split-K layer on it (a slab per layer was
@@ -872,17 +946,14 @@ struct Plan {
   bool patch_conv3x3 = true;     // option "conv3x3" = "patch" | "gemm"
   bool fuse_hpool = true;        // option "pool" = "split" | "whole": horizontal half of an entry-flow pool in the producer
   int pool_fuse_min_pixels = 100 * 100;   // ... for the 237 x 237 block (+0.8 %) and the 119 x 119 one (time-neutral, -0.9 GB)
-  int add_conv(const std::string& name, int stage, const Buf& in_, ConvLayer* L, const Buf* res, int relu_in, Buf* out) {
+  int add_conv(const std::string& name, int stage, const Buf& in_, ConvLayer* L, const Buf* res, int relu_in, Buf* out,
+               const ConvEmit& em = {}) {
     Buf in = in_;
     bool own_split = false;
-    const int emit = L->precision == PREC_F32 ? 0 : emit_planes_next;
-    const bool folded_bn = emit && !emit_bn_scale.empty();
-    if (folded_bn) XDET_TRY(L->set_planes_bn(emit_bn_scale, emit_bn_shift));
-    emit_planes_next = 0;
-    const Buf* planes_into = emit_planes_into;
-    emit_planes_into = nullptr;
-    emit_bn_scale.clear();
-    emit_bn_shift.clear();
+    const int emit = L->precision == PREC_F32 ? 0 : em.planes;
+    const bool folded_bn = emit && em.bn_scale;
+    if (folded_bn) XDET_TRY(L->set_planes_bn(*em.bn_scale, *em.bn_shift));
+    const Buf* planes_into = em.into;
     // split path: big stride-1 contractions take their A operand as f16 planes through the LDS DMA;
     // if the producer did not emit planes, one cheap element-wise pass makes them (ReLU folded in)
     // (a strided conv takes planes too if its producer wrote them: the DMA gathers any pixel per row; it is not worth
@@ -910,7 +981,7 @@ struct Plan {
     L->out_shape(in.H, in.W, &Ho, &Wo, &a, &b);
     XDET_TRY(new_buf(Ho, Wo, L->cout, out));
     XDET_REQUIRE(in.ld == L->ld_in() && out->ld == L->ld_out(), "plan: conv channel strides do not match");
-    if (in.hi) XDET_TRY(maybe_ksplit(L, in.H, in.W, Ho, Wo)); else ksplit_next = false;
+    if (in.hi) XDET_TRY(maybe_ksplit(L, in.H, in.W, Ho, Wo, em.ksplit));
     XDET_REQUIRE(!planes_into || emit == 3, "plan: a concatenated planes destination needs a planes-only output");
     if (emit) {
       if (planes_into) {
@@ -942,27 +1013,24 @@ struct Plan {
       pscales[in.pidx].x8_ok = false;                // a second consumer: keep the f16 form
     }
     const int x8_pidx = in.hi ? in.pidx : -1;
-    const bool planes_optional = planes_optional_next && emit != 0 && emit != 3;
-    planes_optional_next = false;
-    last_optional_idx = -1;
-    if (planes_optional) {
-      last_optional_idx = (int)planes_drop_ok.size();
-      planes_drop_ok.push_back(0);
-    }
-    const int drop_idx = last_optional_idx;
+    const bool planes_optional = em.optional && emit != 0 && emit != 3;
+    const int drop_idx = planes_optional ? (int)planes_drop_ok.size() : -1;
+    if (planes_optional) planes_drop_ok.push_back(0);
+    if (em.optional) *em.optional = drop_idx;
     const Buf i = in, o = *out;
     const float* rp = res ? res->p : nullptr;
     const unsigned short* z = zeros;
     if (res) XDET_REQUIRE(res->H == Ho && res->W == Wo && res->ld == o.ld, "plan: residual shape mismatch");
     ops.push_back({name, stage, L->flops(in.H, in.W), [=](int N, hipStream_t s) {
+                     ConvIO io;
+                     io.in = i.p; io.in_hi = i.hi; io.in_lo = i.lo; io.zeros = z; io.relu_in = relu_in;
+                     io.x8 = plane_x8(x8_pidx, &io.x8_exp) ? 1 : 0;
+                     io.out = o.no_f32 ? nullptr : o.p; io.res = rp;
+                     if (!(planes_optional && planes_drop_ok[drop_idx] && planes_dropped())) { io.out_hi = o.hi; io.out_lo = o.lo; }
                      // the planes copy: relu(out * bn_scale + bn_shift) * 2^-out_exp for a folded BN, else (relu?)(out) * 2^-out_exp
-                     const bool aff = folded_bn || L->out_exp != 0;
-                     int x8_exp = 0;
-                     const int x8 = plane_x8(x8_pidx, &x8_exp) ? 1 : 0;
-                     const bool drop = planes_optional && planes_drop_ok[drop_idx] && planes_dropped();
-                     return L->forward(i.p, N, i.H, i.W, i.ld, o.no_f32 ? nullptr : o.p, o.ld, rp, relu_in, s, i.hi, i.lo,
-                                       z, drop ? nullptr : o.hi, drop ? nullptr : o.lo, (o.planes_relu || folded_bn) ? 1 : 0, aff ? L->d_pl_scale : nullptr,
-                                       aff ? L->d_pl_shift : nullptr, 0, x8, x8_exp);
+                     io.planes_relu = (o.planes_relu || folded_bn) ? 1 : 0;
+                     if (folded_bn || L->out_exp != 0) { io.pl_scale = L->d_pl_scale; io.pl_shift = L->d_pl_shift; }
+                     return L->forward(io, N, i.H, i.W, i.ld, o.ld, s);
                    }});
     if (own_split) release_planes(in);
     return XDET_OK;
@@ -1017,7 +1085,8 @@ struct Plan {
   // relu(in * pre_sc + pre_sh) -- the pre-activation BN of a ResNet v2 block, applied in the subsample pass
   int conv_bn(const std::string& name, const std::string& bn, float eps, int stage, const Buf& in, int k, int cout,
               int stride, int pad_mode, int relu_out, const Buf* res, int relu_in, Buf* out, int pad_expl = 0,
-              const float* pre_sc = nullptr, const float* pre_sh = nullptr, const Buf* presub = nullptr) {
+              const float* pre_sc = nullptr, const float* pre_sh = nullptr, const Buf* presub = nullptr,
+              const ConvEmit& emit = {}) {
     const HostTensor* kt;
     XDET_TRY(need(name + "/kernel", &kt, {k, k, in.C, cout}));
     std::vector<float> sc, sh;
@@ -1041,7 +1110,7 @@ struct Plan {
         // the producer of `in` (the pool pass in front of this block) already wrote the raw subsampled planes
         XDET_REQUIRE(!pre_sc && presub->H == (in.H + 1) / 2 && presub->W == (in.W + 1) / 2 && presub->ld == in.ld,
                      "plan: pre-made subsampled planes do not match the projection's input");
-        XDET_TRY(add_conv(name, stage, *presub, L, res, 0, out));
+        XDET_TRY(add_conv(name, stage, *presub, L, res, 0, out, emit));
         release_planes(*presub);
         return XDET_OK;
       }
@@ -1053,7 +1122,7 @@ struct Plan {
       ops.push_back({name + "/subsample_split", stage, 0.0, [=](int N, hipStream_t s) {
                        return launch_split_f32_subsample2(i.p, o.hi, o.lo, N, i.H, i.W, i.ld, s, pre_sc, pre_sh, pmul(o.pidx));
                      }});
-      XDET_TRY(add_conv(name, stage, sub, L, res, 0, out));
+      XDET_TRY(add_conv(name, stage, sub, L, res, 0, out, emit));
       release_planes(sub);                         // read by this projection only
       return XDET_OK;
     }
@@ -1061,7 +1130,7 @@ struct Plan {
     XDET_TRY(L->init(k, k, in.C, cout, stride, 1, pad_mode, pad_expl, pad_expl, kt->v.data(), scp, shp, relu_out));
     // 3x3 VALID over 32 channels (block1_conv2): the input tile is staged in LDS once and the nine taps are shifted
     // fragment reads of it (conv3x3_patch.hip) instead of nine DMA'd K steps; same products, same order
-    if (patch_conv3x3 && L->dma_capable() && in.hi && !in.planes_relu && !relu_in && !res && emit_planes_next == 0 &&
+    if (patch_conv3x3 && L->dma_capable() && in.hi && !in.planes_relu && !relu_in && !res && emit.planes == 0 &&
         in.ld == 32 && conv3x3_patch_supported(k, k, in.C, L->cout_pad, stride, 1, pad_mode) && L->cout_pad == L->ld_out()) {
       XDET_TRY(new_buf(in.H - 2, in.W - 2, cout, out));
       if (in.pidx >= 0) pscales[in.pidx].apply.push_back([L](int e) { return L->set_in_exp(e); });
@@ -1072,7 +1141,7 @@ struct Plan {
                      }});
       return XDET_OK;
     }
-    return add_conv(name, stage, in, L, res, relu_in, out);
+    return add_conv(name, stage, in, L, res, relu_in, out, emit);
   }
   // (ReLU ->) separable_conv2d -> BN (-> +residual) (-> ReLU)   net/xception_body.py:220-234
   // pool_res != NULL: the block is followed by max_pooling2d(3, 2, 'same') + tf.add(pool_res) (entry flow,
@@ -1083,7 +1152,8 @@ struct Plan {
   // subsampled planes into *next_sub (what the NEXT block's 1x1 / stride-2 projection reads) and stores relu(sum) as *out
   // (what its first separable conv reads): maxpool_v3s2_add_kernel<SUB>.  next_sub->hi stays NULL where that form is not taken.
   int sep_bn(const std::string& name, float eps, int stage, const Buf& in, int cout, int pre_relu, int dilation,
-             int relu_out, const Buf* res, Buf* out, const Buf* pool_res = nullptr, Buf* next_sub = nullptr) {
+             int relu_out, const Buf* res, Buf* out, const Buf* pool_res = nullptr, Buf* next_sub = nullptr,
+             const ConvEmit& emit = {}) {
     const HostTensor *dk, *pk;
     XDET_TRY(need(name + "/depthwise_kernel", &dk, {3, 3, in.C, 1}));
     XDET_TRY(need(name + "/pointwise_kernel", &pk, {1, 1, in.C, cout}));
@@ -1096,7 +1166,7 @@ struct Plan {
     // Entry-flow shapes (<= 256 input channels, 128 / 256 outputs, dilation 1, no residual, f32 consumers only):
     // ONE fused kernel, the depthwise result never leaves the CU (sepconv_fused.hip); bit-identical to the
     // two-kernel form below, which the wide 30x30 layers keep (their GEMM needs the big MFMA tiles).
-    if (fuse_sepconv && L->dma_capable() && !res && emit_planes_next == 0 && !in.no_f32 &&
+    if (fuse_sepconv && L->dma_capable() && !res && emit.planes == 0 && !in.no_f32 &&
         sepconv_fused_supported(in.ld, L->cout_pad, dilation) && L->ld_out() <= L->cout_pad) {
       {
         // the depthwise result is split on the CU and never reaches HBM: its range is bounded from the block input,
@@ -1161,18 +1231,12 @@ struct Plan {
       release_f32(full);
       return XDET_OK;
     }
-    Buf t;
+    Buf t, full;
     XDET_TRY(add_dw(name + "/depthwise", stage, in, D, pre_relu, &t, /*planes_only=*/L->dma_capable()));
-    if (!pool_res) {
-      XDET_TRY(add_conv(name + "/pointwise", stage, t, L, res, 0, out));
-      release_planes(t);                           // the depthwise result: read by its pointwise conv only
-      release_f32(t);
-      return XDET_OK;
-    }
-    Buf full;
-    XDET_TRY(add_conv(name + "/pointwise", stage, t, L, res, 0, &full));
-    release_planes(t);
+    XDET_TRY(add_conv(name + "/pointwise", stage, t, L, res, 0, pool_res ? &full : out, emit));
+    release_planes(t);                             // the depthwise result: read by its pointwise conv only
     release_f32(t);
+    if (!pool_res) return XDET_OK;
     XDET_TRY(add_pool(name + "/pool_add", stage, full, pool_res, out));
     release_f32(full);
     return XDET_OK;
@@ -1236,8 +1300,6 @@ enum { ST_BODY = 0, ST_RPN = 1, ST_LSEP = 2, ST_HEAD = 3, ST_EXIT = 4 };
 
 static inline double nsplit_of(const ConvLayer* L) { return L->precision == PREC_F16X3 ? 3.0 : 1.0; }
 
-typedef std::array<uintptr_t, 6> GraphKey;
-
 struct LightHeadNet : Plan {
   xdet_lighthead_config cfg;
   bool built = false;
@@ -1262,12 +1324,9 @@ struct LightHeadNet : Plan {
   const float* cur_images = nullptr;
   hipStream_t aux = nullptr;            // side stream of the RPN/proposal branch
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  static constexpr size_t kMaxGraphs = 8;
-  std::map<GraphKey, hipGraphExec_t> graphs;   // keyed by (N, images, image_shapes, bbox_img, det_scores, det_boxes)
-  std::vector<GraphKey> graph_order;           // capture order, for eviction
 
   ~LightHeadNet() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+    graphs.clear();              // (before the streams they were captured on)
     // the side stream and its fork / join events (created on the first forward): a net that leaves them behind leaks a
     // hardware queue per instance -- a long test session (~150 nets) ran the runtime out of them and died inside a capture
     if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -1287,14 +1346,9 @@ struct LightHeadNet : Plan {
       const HostTensor* kt;
       XDET_TRY(need("block1_conv1/kernel", &kt, {3, 3, 3, 32}));
       std::vector<float> sc, sh;
-      XDET_TRY(fold_bn("block1_conv1_bn", 32, eps, nullptr, &sc, &sh));
       float *d_w, *d_sc, *d_sh;
-      XDET_TRY(alloc_bytes(kt->v.size() * 4, reinterpret_cast<void**>(&d_w), false));
-      XDET_TRY(alloc_bytes(32 * 4, reinterpret_cast<void**>(&d_sc), false));
-      XDET_TRY(alloc_bytes(32 * 4, reinterpret_cast<void**>(&d_sh), false));
-      XDET_HIP(hipMemcpy(d_w, kt->v.data(), kt->v.size() * 4, hipMemcpyHostToDevice));
-      XDET_HIP(hipMemcpy(d_sc, sc.data(), 32 * 4, hipMemcpyHostToDevice));
-      XDET_HIP(hipMemcpy(d_sh, sh.data(), 32 * 4, hipMemcpyHostToDevice));
+      XDET_TRY(upload(kt->v, &d_w));
+      XDET_TRY(upload_bn("block1_conv1_bn", 32, 32, eps, &sc, &sh, &d_sc, &d_sh));
       x = Buf();
       x.H = x.W = (S - 3) / 2 + 1; x.C = 32; x.ld = 32; x.no_f32 = true;
       XDET_TRY(new_planes(&x));
@@ -1314,7 +1368,6 @@ struct LightHeadNet : Plan {
                      }});
       ops.back().mfma_flops = 0.0;      // VALU kernel
     } else {
-      emit_planes_next = 3;   // feeds block1_conv2 (LDS-DMA path) only
       XDET_TRY(conv_bn("block1_conv1", "block1_conv1_bn", eps, ST_BODY, in4, 3, 32, 2, 0, 1, nullptr, 0, &x));
     }
     XDET_TRY(conv_bn("block1_conv2", "block1_conv2_bn", eps, ST_BODY, x, 3, 64, 1, 0, 1, nullptr, 0, &t));
@@ -1354,8 +1407,8 @@ struct LightHeadNet : Plan {
       const std::string pre = "block" + std::to_string(blk);
       XDET_TRY(sep_bn(pre + "_sepconv1", eps, ST_BODY, x, 728, 1, 1, 0, nullptr, &a));
       XDET_TRY(sep_bn(pre + "_sepconv2", eps, ST_BODY, a, 728, 1, 1, 0, nullptr, &b2));
-      if (blk == 12) emit_planes_next = 2;   // mid_outputs = ReLU(this) feeds the RPN 3x3 conv
-      XDET_TRY(sep_bn(pre + "_sepconv3", eps, ST_BODY, b2, 728, 1, 1, 0, &res, &c3));
+      // block 12: mid_outputs = ReLU(this) feeds the RPN 3x3 conv (relu planes)
+      XDET_TRY(sep_bn(pre + "_sepconv3", eps, ST_BODY, b2, 728, 1, 1, 0, &res, &c3, nullptr, nullptr, ConvEmit{blk == 12 ? 2 : 0}));
       release_f32(a);                              // a block's three tensors die with it: the middle flow lives in four
       release_f32(b2);                             // f32 blocks and one planes pair instead of 24 + 24
       release_f32(res);
@@ -1375,8 +1428,9 @@ struct LightHeadNet : Plan {
     // does not depend on the batch it arrives in.
     large_sep_spectral = g_default_precision != PREC_F32 && spectral_supported(c3.H) && c3.H == c3.W && large_sep_mode != 1;
     if (large_sep_mode == 2) XDET_REQUIRE(large_sep_spectral, "large_sep=spectral needs a split-precision mode and a 16/30/50 feature map");
-    emit_planes_next = large_sep_spectral ? 0 : 1;   // the direct (15,1) conv takes planes; the DFT pass reads f32
-    XDET_TRY(sep_bn("block14_sepconv2", eps, ST_EXIT, c3, 2048, 0, 2, 1, nullptr, &d4));   // :366-376
+    // :366-376; the direct (15,1) conv takes planes, the DFT pass reads f32
+    XDET_TRY(sep_bn("block14_sepconv2", eps, ST_EXIT, c3, 2048, 0, 2, 1, nullptr, &d4, nullptr, nullptr,
+                    ConvEmit{large_sep_spectral ? 0 : 1}));
     release_f32(a);
     release_f32(r);
     release_f32(b2);
@@ -1400,14 +1454,13 @@ struct LightHeadNet : Plan {
     ConvLayer* L0 = keep(new ConvLayer());
     XDET_TRY(L0->init(3, 3, 728, 512, 1, 1, 1, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
     Buf hid;
-    emit_planes_next = 3;   // only the fused 1x1 heads read it
+    ConvEmit hid_emit;
+    hid_emit.planes = 3;    // only the fused 1x1 heads read it
     // (a single image is 8 x 4 tiles against 207 K steps.  Fixed split-K -- option "ksplit" = "all" -- takes it from 116 to
     //  37 us, but costs the 256 x 256 tile at bench-size batches: 1.92 -> 2.36 ms per 128 images, -0.9 % end to end.
     //  With the fork in front of the exit flow the conv is off the critical path of a single image anyway.)
-    ksplit_next = latency_ksplit && rpn_ksplit;
-    ks_on_aux_stream = rpn_side_stream;     // the RPN branch runs beside the exit flow: its own scratch slab
-    XDET_TRY(add_conv("rpn_head/conv2d", ST_RPN, mid_x, L0, nullptr, /*relu_in=*/1, &hid));
-    ks_on_aux_stream = false;
+    hid_emit.ksplit = latency_ksplit && rpn_ksplit;
+    XDET_TRY(add_conv("rpn_head/conv2d", ST_RPN, mid_x, L0, nullptr, /*relu_in=*/1, &hid, hid_emit));
     // cls (2A) and box (4A) 1x1 heads share their input: one GEMM over the concatenated filters
     const int co = 6 * A;
     std::vector<float> kc((size_t)512 * co), bc(co);
@@ -1423,39 +1476,48 @@ struct LightHeadNet : Plan {
     return XDET_OK;
   }
 
-  int build_large_sep() {
-    const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid;
+  // The large-separable block's weights (net/xception_body.py:450-475) with its two branches fused: both (15,1) convs read
+  // the same input -> ONE conv with the filters concatenated (2*mid outputs: ka, ba); branch_0b + branch_1b = ONE (1,15) conv
+  // over the 2*mid stacked channels (kb), whose bias sum is folded into the BN(1e-5) + ReLU behind it (sc, sh)
+  int large_sep_weights(int cin, int mid, int co, std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb,
+                        std::vector<float>* sc, std::vector<float>* sh) const {
     const HostTensor *a0, *a0b, *a1, *a1b, *c0, *c0b, *c1, *c1b;
-    XDET_TRY(need("large_sep_feature/Branch_0/conv2d/kernel", &a0, {15, 1, 2048, mid}));
+    XDET_TRY(need("large_sep_feature/Branch_0/conv2d/kernel", &a0, {15, 1, cin, mid}));
     XDET_TRY(need("large_sep_feature/Branch_0/conv2d/bias", &a0b, {mid}));
-    XDET_TRY(need("large_sep_feature/Branch_1/conv2d/kernel", &a1, {15, 1, 2048, mid}));
+    XDET_TRY(need("large_sep_feature/Branch_1/conv2d/kernel", &a1, {15, 1, cin, mid}));
     XDET_TRY(need("large_sep_feature/Branch_1/conv2d/bias", &a1b, {mid}));
     XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/kernel", &c0, {1, 15, mid, co}));
     XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/bias", &c0b, {co}));
     XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/kernel", &c1, {1, 15, mid, co}));
     XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/bias", &c1b, {co}));
-    // both (15,1) convs read the same input: one conv with the filters concatenated (2*mid outputs)
-    std::vector<float> ka((size_t)15 * 2048 * 2 * mid), ba(2 * mid);
-    for (size_t tc = 0; tc < (size_t)15 * 2048; ++tc) {
-      memcpy(&ka[tc * 2 * mid], &a0->v[tc * mid], mid * sizeof(float));
-      memcpy(&ka[tc * 2 * mid + mid], &a1->v[tc * mid], mid * sizeof(float));
+    const int mid2 = 2 * mid;
+    ka->resize((size_t)15 * cin * mid2);
+    ba->resize(mid2);
+    kb->resize((size_t)15 * mid2 * co);
+    for (size_t tc = 0; tc < (size_t)15 * cin; ++tc) {
+      memcpy(&(*ka)[tc * mid2], &a0->v[tc * mid], mid * sizeof(float));
+      memcpy(&(*ka)[tc * mid2 + mid], &a1->v[tc * mid], mid * sizeof(float));
     }
-    for (int j = 0; j < mid; ++j) { ba[j] = a0b->v[j]; ba[mid + j] = a1b->v[j]; }
-    ConvLayer* LA = keep(new ConvLayer());
-    XDET_TRY(LA->init(15, 1, 2048, 2 * mid, 1, 1, 1, 0, 0, ka.data(), nullptr, ba.data(), 0));
-    Buf t;
-    emit_planes_next = 3;   // only the (1,15) conv reads it
-    XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d", ST_LSEP, out, LA, nullptr, 0, &t));
-    // branch_0b + branch_1b = one (1,15) conv over the 2*mid stacked channels; then BN(1e-5)+ReLU
-    std::vector<float> kb((size_t)15 * 2 * mid * co);
+    for (int j = 0; j < mid; ++j) { (*ba)[j] = a0b->v[j]; (*ba)[mid + j] = a1b->v[j]; }
     for (int tap = 0; tap < 15; ++tap)
       for (int ci = 0; ci < mid; ++ci) {
-        memcpy(&kb[((size_t)tap * 2 * mid + ci) * co], &c0->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
-        memcpy(&kb[((size_t)tap * 2 * mid + mid + ci) * co], &c1->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
+        memcpy(&(*kb)[((size_t)tap * mid2 + ci) * co], &c0->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
+        memcpy(&(*kb)[((size_t)tap * mid2 + mid + ci) * co], &c1->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
       }
-    std::vector<float> bsum(co), sc, sh;
+    std::vector<float> bsum(co);
     for (int j = 0; j < co; ++j) bsum[j] = c0b->v[j] + c1b->v[j];
-    XDET_TRY(fold_bn("large_sep_feature/batch_normalization", co, 1e-5f, bsum.data(), &sc, &sh));
+    return fold_bn("large_sep_feature/batch_normalization", co, 1e-5f, bsum.data(), sc, sh);
+  }
+
+  int build_large_sep() {
+    const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid;
+    std::vector<float> ka, ba, kb, sc, sh;
+    XDET_TRY(large_sep_weights(out.C, mid, co, &ka, &ba, &kb, &sc, &sh));
+    ConvLayer* LA = keep(new ConvLayer());
+    XDET_TRY(LA->init(15, 1, out.C, 2 * mid, 1, 1, 1, 0, 0, ka.data(), nullptr, ba.data(), 0));
+    Buf t;
+    // only the (1,15) conv reads it: planes only
+    XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d", ST_LSEP, out, LA, nullptr, 0, &t, ConvEmit{3}));
     ConvLayer* LB = keep(new ConvLayer());
     XDET_TRY(LB->init(1, 15, 2 * mid, co, 1, 1, 1, 0, 0, kb.data(), sc.data(), sh.data(), 1));
     XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d_1", ST_LSEP, t, LB, nullptr, 0, &feat));
@@ -1468,30 +1530,9 @@ struct LightHeadNet : Plan {
   int build_large_sep_spectral() {
     const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid, F = out.H, NB = spectral_points(F) / 2;
     const int cin = out.C, cin_ld = out.ld, mid2 = 2 * mid, co_ld = round_up(co, 32);
-    const HostTensor *a0, *a0b, *a1, *a1b, *c0, *c0b, *c1, *c1b;
-    XDET_TRY(need("large_sep_feature/Branch_0/conv2d/kernel", &a0, {15, 1, cin, mid}));
-    XDET_TRY(need("large_sep_feature/Branch_0/conv2d/bias", &a0b, {mid}));
-    XDET_TRY(need("large_sep_feature/Branch_1/conv2d/kernel", &a1, {15, 1, cin, mid}));
-    XDET_TRY(need("large_sep_feature/Branch_1/conv2d/bias", &a1b, {mid}));
-    XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/kernel", &c0, {1, 15, mid, co}));
-    XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/bias", &c0b, {co}));
-    XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/kernel", &c1, {1, 15, mid, co}));
-    XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/bias", &c1b, {co}));
     // the same branch fusion as the direct form: (15,1) with 2*mid outputs, (1,15) over the stacked channels
-    std::vector<float> ka((size_t)15 * cin * mid2), kb((size_t)15 * mid2 * co), ba(mid2), ones(std::max(mid2, co_ld), 1.f);
-    for (size_t tc = 0; tc < (size_t)15 * cin; ++tc) {
-      memcpy(&ka[tc * mid2], &a0->v[tc * mid], mid * sizeof(float));
-      memcpy(&ka[tc * mid2 + mid], &a1->v[tc * mid], mid * sizeof(float));
-    }
-    for (int j = 0; j < mid; ++j) { ba[j] = a0b->v[j]; ba[mid + j] = a1b->v[j]; }
-    for (int tap = 0; tap < 15; ++tap)
-      for (int ci = 0; ci < mid; ++ci) {
-        memcpy(&kb[((size_t)tap * mid2 + ci) * co], &c0->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
-        memcpy(&kb[((size_t)tap * mid2 + mid + ci) * co], &c1->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
-      }
-    std::vector<float> bsum(co), sc, sh;
-    for (int j = 0; j < co; ++j) bsum[j] = c0b->v[j] + c1b->v[j];
-    XDET_TRY(fold_bn("large_sep_feature/batch_normalization", co, 1e-5f, bsum.data(), &sc, &sh));
+    std::vector<float> ka, kb, ba, sc, sh, ones(std::max(mid2, co_ld), 1.f);
+    XDET_TRY(large_sep_weights(cin, mid, co, &ka, &ba, &kb, &sc, &sh));
     sc.resize(co_ld, 0.f);
     sh.resize(co_ld, 0.f);
     ConvLayer* LA = keep(new ConvLayer());
@@ -1509,15 +1550,12 @@ struct LightHeadNet : Plan {
     std::vector<float> tf, ti;
     spectral_tables(F, &tf, &ti);
     float *d_tf, *d_tf_b, *d_ti, *d_ones, *d_ba, *d_sc, *d_sh;
-    auto up = [&](const std::vector<float>& h, float** d) {
-      XDET_TRY(alloc_bytes(h.size() * 4, reinterpret_cast<void**>(d), false));
-      XDET_HIP(hipMemcpy(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-      return (int)XDET_OK;
-    };
-    XDET_TRY(up(tf, &d_tf)); XDET_TRY(up(tf, &d_tf_b)); XDET_TRY(up(ti, &d_ti)); XDET_TRY(up(ones, &d_ones)); XDET_TRY(up(ba, &d_ba));
-    XDET_TRY(up(sc, &d_sc)); XDET_TRY(up(sh, &d_sh));
+    XDET_TRY(upload(tf, &d_tf)); XDET_TRY(upload(tf, &d_tf_b)); XDET_TRY(upload(ti, &d_ti)); XDET_TRY(upload(ones, &d_ones));
+    XDET_TRY(upload(ba, &d_ba)); XDET_TRY(upload(sc, &d_sc)); XDET_TRY(upload(sh, &d_sh));
     // workspace, sized for max_batch: rows of every bin are padded to a whole number of 256-row GEMM tiles
     const size_t mp_max = (size_t)round_up(max_batch * F, 256), rows = (size_t)NB * mp_max;
+    // rows per bin at a batch of N: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
+    auto mpad = [F](int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); };
     unsigned short *xa_hi, *xa_lo, *xb_hi, *xb_lo;
     float *y1, *tmid, *y2;
     XDET_TRY(alloc_bytes(rows * 2 * cin_ld * 2 + 512, reinterpret_cast<void**>(&xa_hi)));
@@ -1533,29 +1571,25 @@ struct LightHeadNet : Plan {
     // range of the planes is reached at activations of ~65504 / F, and tmid is an un-normalised 15-tap conv output:
     // this is where a checkpoint with large activations would overflow first.
     f32_bufs.emplace_back(tmid, (size_t)F * F * mid2);
-    {
-      // (prop_ws.bad is carved later, in build(): the lambda reads it through `this` at call time)
-      auto mpad_rc = [F](int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); };
-      extra_range_checks.push_back([=](int N, hipStream_t s) {
-        const int mp = mpad_rc(N);
-        XDET_TRY(launch_range_check_planes(xa_hi, N, F, 2 * cin_ld, prop_ws.bad, s, NB, mp));
-        XDET_TRY(launch_range_check_planes(xb_hi, N, F, 2 * mid2, prop_ws.bad, s, NB, mp));
-        // the per-bin products are f32 and never split: NaN / inf only
-        XDET_TRY(launch_range_check(y1, N, (size_t)F * 2 * mid2, 3.4028235e38f, prop_ws.bad, s, NB, (size_t)mp * 2 * mid2));
-        return launch_range_check(y2, N, (size_t)F * 2 * co_ld, 3.4028235e38f, prop_ws.bad, s, NB, (size_t)mp * 2 * co_ld);
-      });
-    }
+    // (prop_ws.bad is carved later, in build(): the lambda reads it through `this` at call time)
+    extra_range_checks.push_back([=](int N, hipStream_t s) {
+      const int mp = mpad(N);
+      XDET_TRY(launch_range_check_planes(xa_hi, N, F, 2 * cin_ld, prop_ws.bad, s, NB, mp));
+      XDET_TRY(launch_range_check_planes(xb_hi, N, F, 2 * mid2, prop_ws.bad, s, NB, mp));
+      // the per-bin products are f32 and never split: NaN / inf only
+      XDET_TRY(launch_range_check(y1, N, (size_t)F * 2 * mid2, 3.4028235e38f, prop_ws.bad, s, NB, (size_t)mp * 2 * mid2));
+      return launch_range_check(y2, N, (size_t)F * 2 * co_ld, 3.4028235e38f, prop_ws.bad, s, NB, (size_t)mp * 2 * co_ld);
+    });
     const std::string pre = "large_sep_feature/Branch_0+1/";
     {
       // activation pre-scale of the DFT-domain operands: the forward transform is linear, so 2^-e rides in its table
       // (one copy per transform) and 2^e in the per-bin GEMM's epilogue scale.  These are the tensors with the least
       // headroom: a bin sums up to F samples, and the second one transforms an un-normalised 15-tap conv output.
-      auto mpad_ps = [F](int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); };
       const std::vector<float> tf_host = tf;
       PlaneScale pa, pb;
       pa.name = pre + "conv2d/dft_y (DFT-domain planes)";
       pa.hi = xa_hi;
-      pa.halves = [=](int N) { return (int64_t)NB * mpad_ps(N) * 2 * cin_ld; };
+      pa.halves = [=](int N) { return (int64_t)NB * mpad(N) * 2 * cin_ld; };
       pa.apply.push_back([=](int e) {
         std::vector<float> t(tf_host);
         for (float& v : t) v = ldexpf(v, -e);
@@ -1564,7 +1598,7 @@ struct LightHeadNet : Plan {
       });
       pb.name = pre + "conv2d_1/dft_x (DFT-domain planes)";
       pb.hi = xb_hi;
-      pb.halves = [=](int N) { return (int64_t)NB * mpad_ps(N) * 2 * mid2; };
+      pb.halves = [=](int N) { return (int64_t)NB * mpad(N) * 2 * mid2; };
       pb.apply.push_back([=](int e) {
         std::vector<float> t(tf_host);
         for (float& v : t) v = ldexpf(v, -e);
@@ -1580,15 +1614,15 @@ struct LightHeadNet : Plan {
       pscales.push_back(pb);
     }
     const double fl_a = 2.0 * F * F * (double)cin * mid2 * 15, fl_b = 2.0 * F * F * (double)mid2 * co * 15;
-    // rows per bin: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
-    auto mpad = [F](int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); };
     // flops < 0 marks an auxiliary pass of a contraction: its time counts with the conv kernels, it has no FLOPs of its own
     ops.push_back({pre + "conv2d/dft_y", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
                      return launch_dft_fwd(o.p, F, o.ld, 0, N, mpad(N), d_tf, xa_hi, xa_lo, s);
                    }});
     ops.push_back({pre + "conv2d [spectral]", ST_LSEP, fl_a, [=](int N, hipStream_t s) {
-                     return LA->forward(nullptr, 1, 1, NB * mpad(N), 2 * cin_ld, y1, 2 * mid2, nullptr, 0, s, xa_hi, xa_lo,
-                                        LA->d_zeros, nullptr, nullptr, 0, nullptr, nullptr, mpad(N), 0, 0, N * F);
+                     ConvIO io;                   // NB groups of mpad(N) rows, N * F of them live
+                     io.in_hi = xa_hi; io.in_lo = xa_lo; io.zeros = LA->d_zeros; io.out = y1;
+                     io.group_rows = mpad(N); io.group_live_rows = N * F;
+                     return LA->forward(io, 1, 1, NB * mpad(N), 2 * cin_ld, 2 * mid2, s);
                    }});
     ops.back().mfma_flops = 2.0 * nsplit_of(LA) * NB * (double)F * (2.0 * cin_ld) * (2.0 * mid2);
     ops.push_back({pre + "conv2d/idft_y+bias", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
@@ -1598,8 +1632,10 @@ struct LightHeadNet : Plan {
                      return launch_dft_fwd(tmid, F, mid2, 1, N, mpad(N), d_tf_b, xb_hi, xb_lo, s);
                    }});
     ops.push_back({pre + "conv2d_1 [spectral]", ST_LSEP, fl_b, [=](int N, hipStream_t s) {
-                     return LB->forward(nullptr, 1, 1, NB * mpad(N), 2 * mid2, y2, 2 * co_ld, nullptr, 0, s, xb_hi, xb_lo,
-                                        LB->d_zeros, nullptr, nullptr, 0, nullptr, nullptr, mpad(N), 0, 0, N * F);
+                     ConvIO io;
+                     io.in_hi = xb_hi; io.in_lo = xb_lo; io.zeros = LB->d_zeros; io.out = y2;
+                     io.group_rows = mpad(N); io.group_live_rows = N * F;
+                     return LB->forward(io, 1, 1, NB * mpad(N), 2 * mid2, 2 * co_ld, s);
                    }});
     ops.back().mfma_flops = 2.0 * nsplit_of(LB) * NB * (double)F * (2.0 * mid2) * (2.0 * co_ld);
     ops.push_back({pre + "conv2d_1/idft_x+bn+relu", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
@@ -1621,8 +1657,7 @@ struct LightHeadNet : Plan {
     XDET_TRY(new_buf(R, 1, C, &pooled));
     ConvLayer* L0 = keep(new ConvLayer());
     XDET_TRY(L0->init(1, 1, C, 2048, 1, 1, 0, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
-    emit_planes_next = 1;
-    XDET_TRY(add_conv("final_head/subnet_fc", ST_HEAD, pooled, L0, nullptr, 0, &fc));
+    XDET_TRY(add_conv("final_head/subnet_fc", ST_HEAD, pooled, L0, nullptr, 0, &fc, ConvEmit{1}));
     const int co = nc + 4;
     std::vector<float> kc((size_t)2048 * co), bc(co);
     for (int ci = 0; ci < 2048; ++ci) {
@@ -1633,8 +1668,9 @@ struct LightHeadNet : Plan {
     for (int j = 0; j < 4; ++j) bc[nc + j] = b2->v[j];
     ConvLayer* L1 = keep(new ConvLayer());
     XDET_TRY(L1->init(1, 1, 2048, co, 1, 1, 0, 0, 0, kc.data(), nullptr, bc.data(), 0));
-    ksplit_next = latency_ksplit;     // 300 rows x 25 outputs: 3 tiles against 64 K steps
-    XDET_TRY(add_conv("final_head/fc_cls+fc_loc", ST_HEAD, fc, L1, nullptr, 0, &cls_reg));
+    ConvEmit cls_emit;
+    cls_emit.ksplit = latency_ksplit;     // 300 rows x 25 outputs: 3 tiles against 64 K steps
+    XDET_TRY(add_conv("final_head/fc_cls+fc_loc", ST_HEAD, fc, L1, nullptr, 0, &cls_reg, cls_emit));
     return XDET_OK;
   }
 
@@ -1645,7 +1681,7 @@ struct LightHeadNet : Plan {
     max_batch = cfg.max_batch;
     net_precision = g_default_precision;
     ksplit_design_batch = 1;            // the reference evaluates single images (light_head_rfcn_eval.py:212); only layers a
-    ksplit_all = false;                 // builder marks (ksplit_next) are split
+    ksplit_all = false;                 // builder marks (ConvEmit::ksplit) are split
     XDET_TRY(build_body());
     XDET_TRY(build_rpn());
     XDET_TRY(large_sep_spectral ? build_large_sep_spectral() : build_large_sep());
@@ -1671,10 +1707,8 @@ struct LightHeadNet : Plan {
           ++a;
         }
     }
-    XDET_TRY(alloc_bytes(yx.size() * 4, reinterpret_cast<void**>(&anc_yx)));
-    XDET_TRY(alloc_bytes(hw.size() * 4, reinterpret_cast<void**>(&anc_hw)));
-    XDET_HIP(hipMemcpy(anc_yx, yx.data(), yx.size() * 4, hipMemcpyHostToDevice));
-    XDET_HIP(hipMemcpy(anc_hw, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
+    XDET_TRY(upload(yx, &anc_yx));
+    XDET_TRY(upload(hw, &anc_hw));
     XDET_TRY(alloc_bytes((size_t)B * n_anchor * 4, reinterpret_cast<void**>(&objectness)));
     XDET_TRY(alloc_bytes((size_t)B * n_anchor * 16, reinterpret_cast<void**>(&rpn_boxes)));
     XDET_TRY(alloc_bytes((size_t)B * R * 16, reinterpret_cast<void**>(&proposals)));
@@ -1686,10 +1720,8 @@ struct LightHeadNet : Plan {
     std::vector<int> shp((size_t)B * 2, cfg.image_size);
     std::vector<float> bb((size_t)B * 4);
     for (int i = 0; i < B; ++i) { bb[i * 4] = 0.f; bb[i * 4 + 1] = 0.f; bb[i * 4 + 2] = 1.f; bb[i * 4 + 3] = 1.f; }
-    XDET_TRY(alloc_bytes(shp.size() * 4, reinterpret_cast<void**>(&def_shapes)));
-    XDET_TRY(alloc_bytes(bb.size() * 4, reinterpret_cast<void**>(&def_bbox)));
-    XDET_HIP(hipMemcpy(def_shapes, shp.data(), shp.size() * 4, hipMemcpyHostToDevice));
-    XDET_HIP(hipMemcpy(def_bbox, bb.data(), bb.size() * 4, hipMemcpyHostToDevice));
+    XDET_TRY(upload(shp, &def_shapes));
+    XDET_TRY(upload(bb, &def_bbox));
     w.clear();   // host copies are no longer needed
     built = true;
     return XDET_OK;
@@ -1704,17 +1736,13 @@ struct LightHeadNet : Plan {
     return XDET_OK;
   }
   int xception_body(const float* images, int N, hipStream_t s) {
-    XDET_TRY(check(N));
-    XDET_REQUIRE(images != nullptr, "images is NULL");
-    cur_images = images;         // the stem op reads the NCHW input directly (graphs are keyed on this pointer)
-    if (!stem_direct) XDET_TRY(launch_nchw_to_nhwc4(images, in4.p, N, 3, cfg.image_size, cfg.image_size, 4, s));
-    XDET_TRY(run_stage(ST_BODY, N, s));
+    XDET_TRY(entry_and_middle_flow(images, N, s));
     return run_stage(ST_EXIT, N, s);
   }
   int entry_and_middle_flow(const float* images, int N, hipStream_t s) {      // up to mid_outputs
     XDET_TRY(check(N));
     XDET_REQUIRE(images != nullptr, "images is NULL");
-    cur_images = images;
+    cur_images = images;         // the stem op reads the NCHW input directly (graphs are keyed on this pointer)
     if (!stem_direct) XDET_TRY(launch_nchw_to_nhwc4(images, in4.p, N, 3, cfg.image_size, cfg.image_size, 4, s));
     return run_stage(ST_BODY, N, s);
   }
@@ -1759,17 +1787,12 @@ struct LightHeadNet : Plan {
                               shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
                               cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
   }
-  void drop_graphs() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
-    graph_order.clear();
-  }
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled) {
     XDET_TRY(check(N));
     XDET_REQUIRE(images != nullptr, "calibrate: images is NULL");
     if (n_scaled) *n_scaled = 0;
     if (net_precision == PREC_F32 || pscales.empty()) return XDET_OK;
-    drop_graphs();                                   // graphs bake kernel arguments (the split passes' multipliers)
+    graphs.clear();                                  // graphs bake kernel arguments (the split passes' multipliers)
     const size_t slots = (size_t)N * (cfg.num_classes - 1) * cfg.nms_topk;
     float *ds = nullptr, *db = nullptr;
     XDET_HIP(hipMalloc(reinterpret_cast<void**>(&ds), slots * 4));
@@ -1873,12 +1896,6 @@ struct ResNetTrunk : Plan {
       if (g.Lprev->out_exp != 0 || g.La->in_exp != 0 || g.La->out_exp != 0) return false;
     return true;
   }
-  typedef std::array<uintptr_t, 4> Key;            // (N, images, out, fused forms or not): everything a captured graph bakes in
-  std::map<Key, hipGraphExec_t> graphs;
-  std::vector<Key> graph_order;
-  ~ResNetTrunk() {
-    for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-  }
 
   // Pre-activation bottlenecks (net/resnet_v2.py:142-184).  The BN+ReLU that follows the two inner
   // convs is folded into their epilogues; the one that opens a block cannot be (the raw block input
@@ -1921,14 +1938,8 @@ __global__ void bn_relu_kernel(const float* __restrict__ in, const float* __rest
 
 int ResNetTrunk::add_bn_relu(const std::string& bn, const Buf& in, Buf* out) {
   std::vector<float> sc, sh;
-  XDET_TRY(fold_bn(bn, in.C, 1e-5f, nullptr, &sc, &sh));
-  sc.resize(in.ld, 0.f);
-  sh.resize(in.ld, 0.f);
   float *dsc, *dsh;
-  XDET_TRY(alloc_bytes(sc.size() * 4, reinterpret_cast<void**>(&dsc)));
-  XDET_TRY(alloc_bytes(sh.size() * 4, reinterpret_cast<void**>(&dsh)));
-  XDET_HIP(hipMemcpy(dsc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
-  XDET_HIP(hipMemcpy(dsh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+  XDET_TRY(upload_bn(bn, in.C, in.ld, 1e-5f, &sc, &sh, &dsc, &dsh));
   XDET_TRY(new_buf(in.H, in.W, in.C, out));
   if (g_default_precision != PREC_F32 && in.ld % 32 == 0) {
     XDET_TRY(new_planes(out));
@@ -1981,14 +1992,8 @@ int ResNetTrunk::build() {
     same_pad(x.W, 3, 2, 1, &pl, &Wo);
     const std::string bn0 = "batch_normalization";
     std::vector<float> sc, sh;
-    XDET_TRY(fold_bn(bn0, x.C, 1e-5f, nullptr, &sc, &sh));
-    sc.resize(x.ld, 0.f);
-    sh.resize(x.ld, 0.f);
     float *dsc, *dsh;
-    XDET_TRY(alloc_bytes(sc.size() * 4, reinterpret_cast<void**>(&dsc)));
-    XDET_TRY(alloc_bytes(sh.size() * 4, reinterpret_cast<void**>(&dsh)));
-    XDET_HIP(hipMemcpy(dsc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
-    XDET_HIP(hipMemcpy(dsh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+    XDET_TRY(upload_bn(bn0, x.C, x.ld, 1e-5f, &sc, &sh, &dsc, &dsh));
     stem_pre = Buf();
     stem_pre.H = Ho; stem_pre.W = Wo; stem_pre.C = x.C; stem_pre.ld = x.ld; stem_pre.no_f32 = true;
     XDET_TRY(new_planes(&stem_pre));
@@ -2096,8 +2101,8 @@ int ResNetTrunk::build() {
       const size_t op_first = ops.size();
       const int my_prev_group = prev_group;       // the bneck group of the block before, if it runs fused
       prev_group = -1;
-      emit_planes_next = 3;                       // the 3x3 (stride 1 or 2) takes its input as planes (only)
-      XDET_TRY(conv_bn(c1, b1, 1e-5f, 0, pre, 1, f, 1, 1, 1, nullptr, 0, &y1));
+      // (the 3x3, stride 1 or 2, takes its input as planes only)
+      XDET_TRY(conv_bn(c1, b1, 1e-5f, 0, pre, 1, f, 1, 1, 1, nullptr, 0, &y1, 0, nullptr, nullptr, nullptr, ConvEmit{3}));
       ConvLayer* La = static_cast<ConvLayer*>(layers.back().get());
       // The opening 1x1 of a stage-2 block on resnet_preconv.hip: it makes relu(bn(x)) from the raw block input itself, so
       // the producer of x does not write the planes copy (decided per forward with the fused blocks: bneck_all_ok()).
@@ -2120,9 +2125,10 @@ int ResNetTrunk::build() {
         };
         ops[op_first].name += " [pre-activation on the CU]";
       }
-      emit_planes_next = 3;                       // the closing 1x1 always does
-      if (cat_on) emit_planes_into = &cat;
-      XDET_TRY(conv_bn(c2, b2, 1e-5f, 0, y1, 3, f, s, s > 1 ? 2 : 1, 1, nullptr, 0, &y2, 1));
+      ConvEmit e2;
+      e2.planes = 3;                              // the closing 1x1 always does
+      if (cat_on) e2.into = &cat;
+      XDET_TRY(conv_bn(c2, b2, 1e-5f, 0, y1, 3, f, s, s > 1 ? 2 : 1, 1, nullptr, 0, &y2, 1, nullptr, nullptr, nullptr, e2));
       XDET_REQUIRE(!cat_on || (y2.hi == cat.hi && y2.H == cat.H && y2.W == cat.W), "plan: the 3x3 conv did not take the concatenated operand");
       ConvLayer* Lb = static_cast<ConvLayer*>(layers.back().get());
       // The next block opens with BN+ReLU of this block's output.  Fold it in: the closing conv writes its f32
@@ -2130,25 +2136,19 @@ int ResNetTrunk::build() {
       // disappears.  (A stage opener's strided projection cannot read those full-resolution planes: see above.)
       const bool last = st == 3 && b == blocks[st] - 1;
       float *nsc = nullptr, *nsh = nullptr;
+      std::vector<float> nsc_host, nsh_host;
+      ConvEmit e3;
+      int my_drop_idx = -1;                       // this block's closing conv, if its planes copy is optional
       if (!last && g_default_precision != PREC_F32) {
         const std::string nbn = bi == 0 ? "batch_normalization" : "batch_normalization_" + std::to_string(bi);
-        std::vector<float> sc, sh;
-        XDET_TRY(fold_bn(nbn, 4 * f, 1e-5f, nullptr, &sc, &sh));
-        const int ldn = round_up(4 * f, 32);
-        sc.resize(ldn, 0.f);
-        sh.resize(ldn, 0.f);
-        XDET_TRY(alloc_bytes(sc.size() * 4, reinterpret_cast<void**>(&nsc)));
-        XDET_TRY(alloc_bytes(sh.size() * 4, reinterpret_cast<void**>(&nsh)));
-        XDET_HIP(hipMemcpy(nsc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
-        XDET_HIP(hipMemcpy(nsh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
-        emit_planes_next = 1;
-        emit_bn_scale = sc;                         // (host copies: the conv keeps its own device arrays, which carry the
-        emit_bn_shift = sh;                         //  planes' pre-scale; nsc / nsh below stay as they are for the projection)
+        XDET_TRY(upload_bn(nbn, 4 * f, round_up(4 * f, 32), 1e-5f, &nsc_host, &nsh_host, &nsc, &nsh));
+        e3.planes = 1;
+        e3.bn_scale = &nsc_host;                    // (host copies: the conv keeps its own device arrays, which carry the
+        e3.bn_shift = &nsh_host;                    //  planes' pre-scale; nsc / nsh stay as they are for the projection)
+        // (the planes copy of this block's output has one reader, the next block's opening conv: if that block turns out to
+        //  run on a kernel that makes its own pre-activation, it marks this conv's planes as droppable)
+        if (g_default_precision == PREC_F16X3) e3.optional = &my_drop_idx;
       }
-      // (a stage's opening block in front of an identity block that can run fused: its planes copy is optional)
-      // (the planes copy of this block's output has one reader, the next block's opening conv: if that block turns out to run on
-      //  a kernel that makes its own pre-activation, it marks this conv's planes as droppable)
-      planes_optional_next = g_default_precision == PREC_F16X3 && nsc != nullptr;
       if (cat_on) {
         const HostTensor *kc, *kp;
         XDET_TRY(need(c3 + "/kernel", &kc, {1, 1, f, 4 * f}));
@@ -2157,12 +2157,11 @@ int ResNetTrunk::build() {
         for (float v : kp->v) kcat.push_back(ldexpf(v, cat_d));             // (the block-input part is stored * 2^-cat_d)
         ConvLayer* L = keep(new ConvLayer());
         XDET_TRY(L->init(1, 1, f + pre.C, 4 * f, 1, 1, 1, 0, 0, kcat.data(), nullptr, nullptr, 0));
-        XDET_TRY(add_conv(c3 + " + " + cproj + " [shortcut projection folded into the reduction]", 0, cat, L, nullptr, 0, &y3));
+        XDET_TRY(add_conv(c3 + " + " + cproj + " [shortcut projection folded into the reduction]", 0, cat, L, nullptr, 0, &y3, e3));
       } else {
-        XDET_TRY(conv_bn(c3, "", 0.f, 0, y2, 1, 4 * f, 1, 1, 0, &shortcut, 0, &y3));
+        XDET_TRY(conv_bn(c3, "", 0.f, 0, y2, 1, 4 * f, 1, 1, 0, &shortcut, 0, &y3, 0, nullptr, nullptr, nullptr, e3));
       }
       ConvLayer* Lc = static_cast<ConvLayer*>(layers.back().get());
-      const int my_drop_idx = last_optional_idx;  // this block's closing conv, if its planes copy is optional
       // An identity block as ONE kernel (resnet_bneck.hip), reading the raw block input (it applies the pre-activation BN +
       // ReLU itself, with the arithmetic of the planes copy the previous block's closing conv writes) and writing the
       // pre-activation planes of the next block only if that one runs as three launches.  The three ops stay in the plan:
@@ -2319,7 +2318,9 @@ int xdet_conv_forward(void* layer, const float* in, int N, int H, int W, int ld_
   LayerBase* b = static_cast<LayerBase*>(layer);
   XDET_REQUIRE(b && b->kind == 1, "not a conv layer");
   DeviceGuard guard(b->device);
-  return static_cast<ConvLayer*>(b)->forward(in, N, H, W, ld_in, out, ld_out, residual, relu_in, S(stream));
+  ConvIO io;
+  io.in = in; io.out = out; io.res = residual; io.relu_in = relu_in;
+  return static_cast<ConvLayer*>(b)->forward(io, N, H, W, ld_in, ld_out, S(stream));
 }
 int xdet_split_f32(const float* in, uint16_t* hi, uint16_t* lo, int64_t n_pix, int ld, int relu, void* stream) {
   XDET_REQUIRE(in && hi && lo, "split: NULL argument");
@@ -2333,7 +2334,9 @@ int xdet_conv_forward_planes(void* layer, const uint16_t* in_hi, const uint16_t*
   XDET_REQUIRE(L->dma_capable(), "layer was not created in a split-precision mode (or has < 32 input channels)");
   XDET_REQUIRE(in_hi && (in_lo || L->precision == PREC_F16), "conv(planes): NULL planes");
   DeviceGuard guard(L->device);
-  return L->forward(nullptr, N, H, W, ld_in, out, ld_out, residual, 0, S(stream), in_hi, in_lo, L->d_zeros);
+  ConvIO io;
+  io.in_hi = in_hi; io.in_lo = in_lo; io.zeros = L->d_zeros; io.out = out; io.res = residual;
+  return L->forward(io, N, H, W, ld_in, ld_out, S(stream));
 }
 int xdet_split_f32_x8(const float* in, uint16_t* hi, uint16_t* lo8, int64_t n_pix, int ld, int relu, int x8_exp, void* stream) {
   XDET_REQUIRE(in && hi && lo8, "split: NULL argument");
@@ -2349,8 +2352,10 @@ int xdet_conv_forward_planes_x8(void* layer, const uint16_t* in_hi, const uint16
   XDET_REQUIRE(in_hi && in_lo8, "conv(planes): NULL planes");
   XDET_REQUIRE(x8_exp > -100 && x8_exp < 100, "conv(x8): exponent out of range");
   DeviceGuard guard(L->device);
-  return L->forward(nullptr, N, H, W, ld_in, out, ld_out, residual, 0, S(stream), in_hi, in_lo8, L->d_zeros, nullptr, nullptr, 0,
-                    nullptr, nullptr, 0, 1, x8_exp);
+  ConvIO io;
+  io.in_hi = in_hi; io.in_lo = in_lo8; io.zeros = L->d_zeros; io.out = out; io.res = residual;
+  io.x8 = 1; io.x8_exp = x8_exp;
+  return L->forward(io, N, H, W, ld_in, ld_out, S(stream));
 }
 int xdet_conv_set_ksplit(void* layer, int ksplit, int mode, int max_parallel_tiles) {
   LayerBase* b = static_cast<LayerBase*>(layer);
@@ -2608,7 +2613,6 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
 }
 int xdet_net_build(void* net) {
   XDET_NET_KIND(net, 0, "net_build");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<LightHeadNet*>(net)->device);
   return static_cast<LightHeadNet*>(net)->build();
 }
@@ -2652,7 +2656,6 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
 int xdet_net_xception_body(void* net, const float* images, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_xception_body");
   LightHeadNet* n = static_cast<LightHeadNet*>(net);
-  XDET_REQUIRE(n, "net is NULL");
   DeviceGuard guard(n->device);
   XDET_TRY(n->xception_body(images, N, S(stream)));
   // materialise mid_outputs = ReLU(x) for API users (the fused forward applies it on load instead)
@@ -2661,7 +2664,6 @@ int xdet_net_xception_body(void* net, const float* images, int N, void* stream) 
 int xdet_net_get_rpn(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_get_rpn");
   LightHeadNet* n = static_cast<LightHeadNet*>(net);
-  XDET_REQUIRE(n, "net is NULL");
   DeviceGuard guard(n->device);
   XDET_TRY(n->check(N));
   return n->run_stage(ST_RPN, N, S(stream));
@@ -2669,32 +2671,27 @@ int xdet_net_get_rpn(void* net, int N, void* stream) {
 int xdet_net_large_sep(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_large_sep");
   LightHeadNet* n = static_cast<LightHeadNet*>(net);
-  XDET_REQUIRE(n, "net is NULL");
   DeviceGuard guard(n->device);
   XDET_TRY(n->check(N));
   return n->run_stage(ST_LSEP, N, S(stream));
 }
 int xdet_net_rpn_decode(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_rpn_decode");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<LightHeadNet*>(net)->device);
   return static_cast<LightHeadNet*>(net)->rpn_decode(N, S(stream));
 }
 int xdet_net_get_proposals(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_get_proposals");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<LightHeadNet*>(net)->device);
   return static_cast<LightHeadNet*>(net)->get_proposals(N, S(stream));
 }
 int xdet_net_get_head(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_get_head");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<LightHeadNet*>(net)->device);
   return static_cast<LightHeadNet*>(net)->get_head(N, S(stream));
 }
 int xdet_net_head_decode(void* net, int N, void* stream) {
   XDET_NET_KIND(net, 0, "net_head_decode");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<LightHeadNet*>(net)->device);
   return static_cast<LightHeadNet*>(net)->head_decode(N, S(stream));
 }
@@ -2716,38 +2713,11 @@ int xdet_net_forward(void* net, const float* images, int N, const int* image_sha
   hipStream_t s = S(stream);
   if (!use_graph) return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s);
   XDET_REQUIRE(s != nullptr, "graph replay needs an explicit (non-default) stream");
-  // A captured graph bakes in every pointer it was recorded with, so the cache key is the whole
-  // argument tuple: a call with another input, shape, bbox or output buffer captures its own graph
-  // (double-buffered outputs keep one graph each; the cache is bounded, oldest-first eviction).
-  const GraphKey key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)image_shapes, (uintptr_t)bbox_img,
-                         (uintptr_t)det_scores, (uintptr_t)det_boxes}};
-  auto it = n->graphs.find(key);
-  if (it == n->graphs.end()) {
-    if (n->graphs.size() >= LightHeadNet::kMaxGraphs) {
-      const GraphKey old = n->graph_order.front();
-      n->graph_order.erase(n->graph_order.begin());
-      (void)hipGraphExecDestroy(n->graphs[old]);
-      n->graphs.erase(old);
-    }
-    hipGraph_t g = nullptr;
-    XDET_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s);
-    const hipError_t e = hipStreamEndCapture(s, &g);
-    if (rc != XDET_OK || e != hipSuccess) {
-      if (g) (void)hipGraphDestroy(g);
-      if (rc != XDET_OK) return rc;
-      XDET_HIP(e);
-    }
-    hipGraphExec_t ge = nullptr;
-    const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    XDET_HIP(ei);
-    n->graphs[key] = ge;
-    n->graph_order.push_back(key);
-    it = n->graphs.find(key);
-  }
-  XDET_HIP(hipGraphLaunch(it->second, s));
-  return XDET_OK;
+  // the cache key is the whole argument tuple: a call with another input, shape, bbox or output buffer captures its own
+  // graph (double-buffered outputs keep one graph each)
+  const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)image_shapes, (uintptr_t)bbox_img,
+                                (uintptr_t)det_scores, (uintptr_t)det_boxes}};
+  return n->graphs.launch(key, s, [&]() { return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s); });
 }
 
 int xdet_net_calibrate(void* net, const float* images, int N, int* n_scaled, void* stream) {
@@ -2783,7 +2753,7 @@ int xdet_net_graph_count(void* net, int* count) {
   XDET_NET_KIND(net, 0, "net_graph_count");
   LightHeadNet* n = static_cast<LightHeadNet*>(net);
   XDET_REQUIRE(n && count, "graph_count: NULL argument");
-  *count = (int)n->graphs.size();
+  *count = (int)n->graphs.execs.size();
   return XDET_OK;
 }
 
@@ -2806,22 +2776,28 @@ int xdet_net_flops_per_image(void* net, double* backbone, double* rpn, double* l
   return XDET_OK;
 }
 
-// mode 0 = light-head net, 1 = resnet trunk
-static Plan* as_plan(void* net, int kind) {
-  return kind == 0 ? static_cast<Plan*>(static_cast<LightHeadNet*>(net)) : static_cast<Plan*>(static_cast<ResNetTrunk*>(net));
+// kind 0 = light-head net, 1 = resnet trunk: the handle must be one
+static int as_plan(void* net, int kind, Plan** p) {
+  XDET_NET_KIND(net, kind, "profile");
+  *p = plan_of(net);
+  return XDET_OK;
 }
 int xdet_profile_enable(void* net, int kind, int enable) {
-  XDET_REQUIRE(net, "net is NULL");
-  as_plan(net, kind)->profiling = enable != 0;
+  Plan* p;
+  XDET_TRY(as_plan(net, kind, &p));
+  p->profiling = enable != 0;
   return XDET_OK;
 }
 int xdet_profile_read(void* net, int kind, int max_ops, int* n_ops, double* ms, int* launches, double* flops) {
   XDET_REQUIRE(net && n_ops && ms && launches && flops, "profile_read: NULL argument");
-  return as_plan(net, kind)->profile_read(max_ops, n_ops, ms, launches, flops);
+  Plan* p;
+  XDET_TRY(as_plan(net, kind, &p));
+  return p->profile_read(max_ops, n_ops, ms, launches, flops);
 }
 int xdet_profile_mfma_flops(void* net, int kind, int max_ops, int* n_ops, double* issued) {
   XDET_REQUIRE(net && n_ops && issued, "profile_mfma_flops: NULL argument");
-  Plan* p = as_plan(net, kind);
+  Plan* p;
+  XDET_TRY(as_plan(net, kind, &p));
   *n_ops = (int)std::min<size_t>(p->ops.size(), (size_t)max_ops);
   const double per_term = g_default_precision == PREC_F16X3 ? 3.0 : 1.0;
   for (int i = 0; i < *n_ops; ++i) {
@@ -2832,7 +2808,8 @@ int xdet_profile_mfma_flops(void* net, int kind, int max_ops, int* n_ops, double
 }
 int xdet_profile_op_name(void* net, int kind, int op, char* buf, int buflen) {
   XDET_REQUIRE(net && buf && buflen > 0, "profile_op_name: bad arguments");
-  Plan* p = as_plan(net, kind);
+  Plan* p;
+  XDET_TRY(as_plan(net, kind, &p));
   XDET_REQUIRE(op >= 0 && op < (int)p->ops.size(), "profile_op_name: op out of range");
   snprintf(buf, buflen, "%s", p->ops[op].name.c_str());
   return XDET_OK;
@@ -2875,7 +2852,6 @@ int xdet_resnet_set_option(void* net, const char* key, const char* value) {
 }
 int xdet_resnet_build(void* net) {
   XDET_NET_KIND(net, 1, "resnet_build");
-  XDET_REQUIRE(net, "net is NULL");
   DeviceGuard guard(static_cast<ResNetTrunk*>(net)->device);
   return static_cast<ResNetTrunk*>(net)->build();
 }
@@ -2903,34 +2879,9 @@ int xdet_resnet_forward_graph(void* net, const float* images, int N, float* out_
   hipStream_t s = S(stream);
   XDET_REQUIRE(s != nullptr, "graph replay needs an explicit (non-default) stream");
   DeviceGuard guard(r->device);
-  const ResNetTrunk::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)out_nhwc, (uintptr_t)r->bneck_all_ok()}};
-  auto it = r->graphs.find(key);
-  if (it == r->graphs.end()) {
-    if (r->graphs.size() >= 8) {
-      const ResNetTrunk::Key old = r->graph_order.front();
-      r->graph_order.erase(r->graph_order.begin());
-      (void)hipGraphExecDestroy(r->graphs[old]);
-      r->graphs.erase(old);
-    }
-    hipGraph_t g = nullptr;
-    XDET_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = xdet_resnet_forward(net, images, N, out_nhwc, stream);
-    const hipError_t e = hipStreamEndCapture(s, &g);
-    if (rc != XDET_OK || e != hipSuccess) {
-      if (g) (void)hipGraphDestroy(g);
-      if (rc != XDET_OK) return rc;
-      XDET_HIP(e);
-    }
-    hipGraphExec_t ge = nullptr;
-    const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    XDET_HIP(ei);
-    r->graphs[key] = ge;
-    r->graph_order.push_back(key);
-    it = r->graphs.find(key);
-  }
-  XDET_HIP(hipGraphLaunch(it->second, s));
-  return XDET_OK;
+  // (N, images, out, fused forms or not): everything a captured graph bakes in
+  const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)out_nhwc, (uintptr_t)r->bneck_all_ok(), 0, 0}};
+  return r->graphs.launch(key, s, [&]() { return xdet_resnet_forward(net, images, N, out_nhwc, stream); });
 }
 // activation pre-scale of the trunk's split-precision operands (as xdet_net_calibrate): pre-activation planes
 // (bn_relu pass / the previous block's epilogue, whose folded BN carries 2^-e), the inner convs' planes, the strided
@@ -2942,9 +2893,7 @@ int xdet_resnet_calibrate(void* net, const float* images, int N, int* n_scaled, 
   DeviceGuard guard(r->device);
   if (n_scaled) *n_scaled = 0;
   if (r->net_precision == PREC_F32) return XDET_OK;
-  for (auto& g : r->graphs) (void)hipGraphExecDestroy(g.second);      // graphs bake kernel arguments
-  r->graphs.clear();
-  r->graph_order.clear();
+  r->graphs.clear();                                                  // graphs bake kernel arguments
   return r->calibrate_planes(N, S(stream), n_scaled, [&](hipStream_t st) { return xdet_resnet_forward(net, images, N, nullptr, st); });
 }
 int xdet_resnet_out_shape(void* net, int* Ho, int* Wo, int* C) {

@@ -9,7 +9,7 @@
 // resnet_bneck.hip: 16-byte loads of x three K steps ahead in registers -> bn_a -> ReLU -> hi / lo (the arithmetic of the
 // planes copy a conv epilogue writes, so the bits agree) -> one of two LDS A tiles under the previous step's MFMAs; the
 // weights come through a four-stage LDS-DMA ring three steps ahead; one barrier per 32-deep K step.  The producer of x then
-// does not write the planes copy at all (ResNetTrunk: planes_optional_next / BneckGroup::next_fused).
+// does not write the planes copy at all (ResNetTrunk: ConvEmit::optional / BneckGroup::next_fused).
 //
 // Tile = 128 (or 64) consecutive pixels x all CMID output channels (8 waves: 4 row blocks x 2 column halves, or 2 x 4),
 // persistent workgroups.
