@@ -228,6 +228,25 @@ int xdet_nchw_to_nhwc4(const float* in_nchw, float* out_nhwc4, int N, int C, int
  * uint8 [H,W,3] (device) -> whitened f32, TF-legacy bilinear warp to out_size x out_size, CHW
  * (one image of the [N,3,S,S] network input); bbox_img is the constant [0,0,1,1]. */
 int xdet_preprocess_eval(const uint8_t* image_hwc, int H, int W, float* out_chw, int out_size, void* stream);
+/* F1, ragged batch: light_head_preprocess_for_eval with its `resize` argument (common_preprocessing.py:383-440) for N
+ * images in one launch.  packed: the uint8 HWC images back to back (packed_bytes in all); offsets i64 [N]: byte offset
+ * of image n; image_shapes i32 [N][2]: its original (H, W) -- the buffer xdet_net_forward reads as image_shapes.  All
+ * three are device memory and are read by the kernel, never taken as launch arguments, so a captured graph serves any
+ * mix of sizes.  -> out_nchw f32 [N,3,S,S] (S = out_size), bbox_img f32 [N,4] (16-byte aligned).
+ * Values of `resize` = the reference's IntEnum Resize (common_preprocessing.py:29-32):
+ *   WARP_RESIZE     TF-legacy bilinear warp to S x S (:435-439), bit-identical to xdet_preprocess_eval.
+ *   PAD_AND_RESIZE  factor = min(1, S/H, S/W) in f64, (rh, rw) = floor(factor * (H, W)) (:405-410), warp to rh x rw, then
+ *                   centred zero pad (zeros in whitened space: whitening comes first, :392-393).
+ *   CENTRAL_CROP    no resize: per axis crop max((H-S)//2, 0), pad max((S-H)//2, 0) (tf_image.py:207-305).
+ *   NONE            whitening only; H = W = S required (:400-402).
+ * bbox_img: [0,0,1,1] through bboxes_crop_or_pad (tf_image.py:179-203) for the crop and then the pad step, each in f32 as
+ * b*[h,w,h,w] + offset, / [th,tw,th,tw]; WARP and NONE give [0,0,1,1].  An invalid descriptor (H or W <= 0, an image
+ * that does not lie inside packed, rh or rw = 0, NONE with a size other than S x S) reads nothing: its planes and its
+ * bbox_img are NaN, and xdet_bboxes_eval reports a NaN bbox_img as NaN scores for that image only. */
+enum { XDET_RESIZE_NONE = 1, XDET_RESIZE_CENTRAL_CROP = 2, XDET_RESIZE_PAD_AND_RESIZE = 3, XDET_RESIZE_WARP = 4 };
+int xdet_preprocess_eval_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                               const int32_t* image_shapes, int N, int out_size, int resize, float* out_nchw,
+                               float* bbox_img, void* stream);
 
 /* ---- A4+A6: RPN glue + AnchorEncoder.decode_all_anchors ----------------------------------
  * (light_head_rfcn_eval.py:389-397; preprocessing/anchor_manipulator.py:641-669,698-757)
@@ -255,7 +274,8 @@ int xdet_ext_decode_rois(const float* rois, const float* reg, int ld_reg, int64_
 
 /* ---- A12: bboxes_eval detection part (light_head_rfcn_eval.py:263-287) -------------------
  *   cls logits [N,R,ld_cls], boxes [N,R,4], image_shapes i32 [N,2] (H,W of the raw image),
- *   bbox_img f32 [N,4] -> det_scores [N,num_classes-1,nms_topk], det_boxes [..,4], zero padded. */
+ *   bbox_img f32 [N,4] -> det_scores [N,num_classes-1,nms_topk], det_boxes [..,4], zero padded.  An image with a
+ *   non-finite head logit or a non-finite bbox_img gets NaN in slot 0 of every class. */
 int xdet_bboxes_eval(const float* cls, int ld_cls, const float* boxes, int N, int R, int num_classes,
                      const int* image_shapes, const float* bbox_img, int net_h, int net_w, float select_thr,
                      float nms_thr, int nms_topk, float* det_scores, float* det_boxes, void* stream);
@@ -331,6 +351,15 @@ int xdet_net_bboxes_eval(void* net, int N, const int* image_shapes, const float*
  * xdet_net_graph_count: number of graphs currently cached (tests). */
 int xdet_net_forward(void* net, const float* images_nchw, int N, const int* image_shapes, const float* bbox_img,
                      float* det_scores, float* det_boxes, int use_graph, void* stream);
+/* uint8 ingest + whole forward: xdet_preprocess_eval_batch (out_size = the net's S) into images_nchw / bbox_img, then
+ * xdet_net_forward with image_shapes and bbox_img, so detections are filtered with each image's original shape
+ * (light_head_rfcn_eval.py:277,369,412) and come back relative to the original image (bboxes_resize).  All buffers are
+ * the caller's.  use_graph != 0: ingest and forward are ONE graph, cached per argument tuple (N, packed, packed_bytes,
+ * offsets, image_shapes, resize, images_nchw, bbox_img, det_scores, det_boxes); the image sizes and offsets are buffer
+ * contents, so a replay may carry a batch of other sizes as long as it fits in packed_bytes. */
+int xdet_net_forward_u8(void* net, const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                        const int32_t* image_shapes, int N, int resize, float* images_nchw, float* bbox_img,
+                        float* det_scores, float* det_boxes, int use_graph, void* stream);
 /* Activation pre-scale of the split-precision operands (modes 1 / 2).  An f16 hi part overflows beyond 65504 while the
  * reference computes in f32 everywhere and has BN-less edges (net/xception_body.py:381-400,450-475).  Every tensor that
  * is split into f16 planes carries a power-of-two exponent e: the planes hold x * 2^-e and the consuming contraction

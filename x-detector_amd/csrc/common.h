@@ -160,6 +160,9 @@ int launch_resnet_bneck(const BneckLaunch& a, int N, hipStream_t s);
 
 // ---- F1 pre-processing (preprocess.hip) ----------------------------------------------
 int launch_preprocess_eval(const unsigned char* img, int H, int W, float* out_chw, int S, hipStream_t s);
+int launch_preprocess_batch(const unsigned char* packed, int64_t packed_bytes, const int64_t* offsets,
+                            const int* image_shapes, int N, int S, int mode, float* out_nchw, float* bbox_img,
+                            hipStream_t s);
 
 // ---- PsRoiAlign (psroialign.hip) -------------------------------------------------------
 int launch_psroialign(const float* feat, const float* rois, float* pooled, int32_t* index, int N, int C, int H,

@@ -203,6 +203,9 @@ __global__ __launch_bounds__(EV_T) void bboxes_eval_kernel(const float* __restri
   const float sx = ref.z - ref.x, sy = ref.w - ref.y;   // bboxes_resize scale (h, w)
 
   int local_bad = bad_per_image ? bad_per_image[n] : 0;     // (proposal stage: non-finite RPN outputs)
+  // a non-finite bbox_img is reported the same way: xdet_preprocess_eval_batch writes NaN for an invalid image
+  // descriptor, whose NaN planes alone would not reach the scores (the first ReLU maps NaN to 0)
+  if (!(isfinite(ref.x) && isfinite(ref.y) && isfinite(ref.z) && isfinite(ref.w))) local_bad = 1;
   for (int r0 = 0; r0 < R; r0 += EV_T) {
     const int r = r0 + tid;
     bool valid = false;

@@ -485,7 +485,7 @@ struct ConvEmit {
 // Captured forwards of a plan.  A graph bakes in every pointer it was recorded with (and the per-forward decisions), so the
 // key holds all of them; the cache is bounded, oldest-first eviction.
 struct GraphCache {
-  typedef std::array<uintptr_t, 6> Key;
+  typedef std::array<uintptr_t, 10> Key;
   static constexpr size_t kMax = 8;
   std::map<Key, hipGraphExec_t> execs;
   std::vector<Key> order;      // capture order, for eviction
@@ -2485,6 +2485,12 @@ int xdet_maxpool3x3s2_add(const float* in, const float* residual, float* out, in
 int xdet_preprocess_eval(const uint8_t* image_hwc, int H, int W, float* out_chw, int out_size, void* stream) {
   return launch_preprocess_eval(image_hwc, H, W, out_chw, out_size, S(stream));
 }
+int xdet_preprocess_eval_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                               const int32_t* image_shapes, int N, int out_size, int resize, float* out_nchw,
+                               float* bbox_img, void* stream) {
+  return launch_preprocess_batch(packed, packed_bytes, offsets, image_shapes, N, out_size, resize, out_nchw, bbox_img,
+                                 S(stream));
+}
 int xdet_nchw_to_nhwc4(const float* in, float* out, int N, int C, int H, int W, void* stream) {
   return launch_nchw_to_nhwc4(in, out, N, C, H, W, 4, S(stream));
 }
@@ -2716,8 +2722,34 @@ int xdet_net_forward(void* net, const float* images, int N, const int* image_sha
   // the cache key is the whole argument tuple: a call with another input, shape, bbox or output buffer captures its own
   // graph (double-buffered outputs keep one graph each)
   const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)image_shapes, (uintptr_t)bbox_img,
-                                (uintptr_t)det_scores, (uintptr_t)det_boxes}};
+                                (uintptr_t)det_scores, (uintptr_t)det_boxes, 0, 0, 0, 0}};
   return n->graphs.launch(key, s, [&]() { return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s); });
+}
+
+int xdet_net_forward_u8(void* net, const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                        const int32_t* image_shapes, int N, int resize, float* images, float* bbox_img,
+                        float* det_scores, float* det_boxes, int use_graph, void* stream) {
+  XDET_NET_KIND(net, 0, "net_forward_u8");
+  LightHeadNet* n = static_cast<LightHeadNet*>(net);
+  XDET_REQUIRE(n && packed && offsets && image_shapes && images && bbox_img && det_scores && det_boxes,
+               "forward_u8: NULL argument");
+  XDET_TRY(n->check(N));
+  XDET_REQUIRE(resize >= XDET_RESIZE_NONE && resize <= XDET_RESIZE_WARP, "forward_u8: unknown resize mode");
+  XDET_REQUIRE(packed_bytes >= 0, "forward_u8: packed_bytes < 0");
+  DeviceGuard guard(n->device);
+  hipStream_t s = S(stream);
+  auto run = [&]() {
+    XDET_TRY(launch_preprocess_batch(packed, packed_bytes, offsets, image_shapes, N, n->cfg.image_size, resize, images,
+                                     bbox_img, s));
+    return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s);
+  };
+  if (!use_graph) return run();
+  XDET_REQUIRE(s != nullptr, "graph replay needs an explicit (non-default) stream");
+  // xdet_net_forward's keys carry 0 in the last four slots; resize >= 1 keeps the two apart
+  const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)image_shapes, (uintptr_t)bbox_img,
+                                (uintptr_t)det_scores, (uintptr_t)det_boxes, (uintptr_t)packed, (uintptr_t)packed_bytes,
+                                (uintptr_t)offsets, (uintptr_t)resize}};
+  return n->graphs.launch(key, s, run);
 }
 
 int xdet_net_calibrate(void* net, const float* images, int N, int* n_scaled, void* stream) {
@@ -2880,7 +2912,7 @@ int xdet_resnet_forward_graph(void* net, const float* images, int N, float* out_
   XDET_REQUIRE(s != nullptr, "graph replay needs an explicit (non-default) stream");
   DeviceGuard guard(r->device);
   // (N, images, out, fused forms or not): everything a captured graph bakes in
-  const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)out_nhwc, (uintptr_t)r->bneck_all_ok(), 0, 0}};
+  const GraphCache::Key key = {{(uintptr_t)N, (uintptr_t)images, (uintptr_t)out_nhwc, (uintptr_t)r->bneck_all_ok(), 0, 0, 0, 0, 0, 0}};
   return r->graphs.launch(key, s, [&]() { return xdet_resnet_forward(net, images, N, out_nhwc, stream); });
 }
 // activation pre-scale of the trunk's split-precision operands (as xdet_net_calibrate): pre-activation planes

@@ -97,6 +97,7 @@ SIGNATURES = {
     'xdet_maxpool_v3s2_add': (c_int, [PF, PF, PF, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_maxpool3x3s2_add': (c_int, [PF, PF, PF, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_preprocess_eval': (c_int, [c_void_p, c_int, c_int, PF, c_int, c_void_p]),
+    'xdet_preprocess_eval_batch': (c_int, [c_void_p, c_int64, c_void_p, PI, c_int, c_int, c_int, PF, PF, c_void_p]),
     'xdet_nchw_to_nhwc4': (c_int, [PF, PF, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_rpn_decode': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, c_int, c_int, PF, PF, PF, PF, c_void_p]),
     'xdet_proposals_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
@@ -120,6 +121,8 @@ SIGNATURES = {
     'xdet_net_head_decode': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_bboxes_eval': (c_int, [c_void_p, c_int, PI, PF, PF, PF, c_void_p]),
     'xdet_net_forward': (c_int, [c_void_p, PF, c_int, PI, PF, PF, PF, c_int, c_void_p]),
+    'xdet_net_forward_u8': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, PI, c_int, c_int, PF, PF, PF, PF, c_int,
+                                    c_void_p]),
     'xdet_net_calibrate': (c_int, [c_void_p, PF, c_int, ctypes.POINTER(c_int), c_void_p]),
     'xdet_net_plane_scales': (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'xdet_net_x8_planes': (c_int, [c_void_p, ctypes.POINTER(c_int)]),

@@ -175,6 +175,47 @@ class LightHeadDetector(object):
         s, b = self.detections(n)
         return [{c + 1: (s[i, c], b[i, c]) for c in range(self.num_classes - 1)} for i in range(n)]
 
+    def detect_images(self, images, resize=None, use_graph=True):
+        """A list of at most max_batch decoded uint8 [H,W,3] images of any sizes -> the list forward() returns, one
+        {class: (scores, boxes)} per image, boxes relative to each ORIGINAL image (light_head_rfcn_eval.py:263-287 with
+        labels['targets'][-1] = the image's shape, and bbox_img from the resize step).  Ingest (xdet_net_forward_u8:
+        light_head_preprocess_for_eval with `resize`, ops.Resize) and the forward run as one launch sequence, or one
+        graph (use_graph): image sizes live in device buffers, so batches of other sizes replay the same graph as
+        long as the packed bytes fit."""
+        from . import ops
+        imgs, S, mode = ops._check_batch(images, self.image_size, ops.Resize.WARP_RESIZE if resize is None else resize,
+                                         self.max_batch)
+        packed, offsets, shapes = ops.pack_images(imgs)
+        n = len(imgs)
+        B = self.max_batch
+        if not hasattr(self, '_ingest'):
+            # offsets / image_shapes / bbox_img: max_batch entries, allocated once.  packed grows only: a regrown buffer
+            # has another pointer and size, so the next call captures a new graph instead of replaying one that
+            # reads the old buffer.
+            self._ingest = {'offsets': DeviceBuffer(B * 8), 'shapes': DeviceBuffer(B * 8),
+                            'bbox_img': DeviceBuffer(B * 16), 'packed': None}
+        bufs = self._ingest
+        if bufs['packed'] is None or bufs['packed'].nbytes < packed.nbytes:
+            cap = max(packed.nbytes, 2 * bufs['packed'].nbytes if bufs['packed'] is not None else 0)
+            bufs['packed'] = DeviceBuffer(cap)
+        h = self.stream.handle
+        check(lib().xdet_memcpy_h2d(bufs['packed'].ptr, _host(packed), packed.nbytes, h))
+        check(lib().xdet_memcpy_h2d(bufs['offsets'].ptr, _host(offsets), offsets.nbytes, h))
+        check(lib().xdet_memcpy_h2d(bufs['shapes'].ptr, _host(shapes), shapes.nbytes, h))
+        # packed_bytes = the buffer's capacity: the graph key stays the same for every batch that fits
+        check(lib().xdet_net_forward_u8(self.handle, bufs['packed'].ptr, bufs['packed'].nbytes, bufs['offsets'].ptr,
+                                        bufs['shapes'].ptr, n, int(mode), self._images.ptr, bufs['bbox_img'].ptr,
+                                        self._det_scores.ptr, self._det_boxes.ptr, 1 if use_graph else 0, h))
+        self._N = n
+        s, b = self.detections(n)
+        return [{c + 1: (s[i, c], b[i, c]) for c in range(self.num_classes - 1)} for i in range(n)]
+
+    def graph_count(self):
+        """graphs cached by this detector's net (xdet_net_graph_count)"""
+        k = ctypes.c_int()
+        check(lib().xdet_net_graph_count(self.handle, ctypes.byref(k)))
+        return k.value
+
     def predictions(self, n=None):
         """the `predictions` dict of the EstimatorSpec (light_head_rfcn_eval.py:429-433)."""
         n = n or self._N

@@ -5,6 +5,7 @@ Inputs may be numpy arrays (copied to the GPU, results copied back -- convenient
 tests) or DeviceTensor / DeviceBuffer objects (stay on the GPU).
 """
 import ctypes
+import enum
 
 import numpy as np
 
@@ -404,24 +405,138 @@ def bboxes_eval(cls_pred_logits, bboxes_pred, image_shape=(480, 480), bbox_img=(
     return out[0] if single else out
 
 
+class Resize(enum.IntEnum):
+    """The reference's resizing strategies (preprocessing/common_preprocessing.py:29-32), same names and values."""
+    NONE = 1
+    CENTRAL_CROP = 2
+    PAD_AND_RESIZE = 3
+    WARP_RESIZE = 4
+
+
+def _resize_mode(resize):
+    try:
+        return Resize(int(resize))
+    except (TypeError, ValueError):
+        raise InvalidArgumentError(-1, 'resize must be one of %s, got %r' % ([m.name for m in Resize], resize))
+
+
+def _check_image(img, what='image'):
+    """uint8 [H,W,3] with H, W > 0 -- the host-side checks, before any GPU work"""
+    a = np.asarray(img)
+    if a.ndim != 3:
+        raise InvalidArgumentError(-1, '%s: Input must be of size [height, width, C>0], got shape %r' % (what, a.shape))
+    if a.shape[2] != 3:
+        raise InvalidArgumentError(-1, '%s: 3 channels (RGB) expected, got %d' % (what, a.shape[2]))
+    if a.shape[0] == 0 or a.shape[1] == 0:
+        raise InvalidArgumentError(-1, '%s: empty image %r' % (what, a.shape))
+    if a.dtype != np.uint8:
+        raise InvalidArgumentError(-1, '%s: uint8 image expected, got %s' % (what, a.dtype))
+    return np.ascontiguousarray(a)
+
+
+def _check_batch(images, out_size, resize, max_images=None):
+    mode = _resize_mode(resize)
+    S = int(out_size)
+    if S <= 0:
+        raise InvalidArgumentError(-1, 'out_size must be > 0, got %d' % S)
+    if isinstance(images, np.ndarray) and images.ndim == 3:
+        raise InvalidArgumentError(-1, 'a list of [H,W,3] images is expected, got one image')
+    imgs = [_check_image(im, 'images[%d]' % i) for i, im in enumerate(images)]
+    if not imgs:
+        raise InvalidArgumentError(-1, 'no images')
+    if max_images is not None and len(imgs) > max_images:
+        raise InvalidArgumentError(-1, '%d images but at most %d per call' % (len(imgs), max_images))
+    if mode == Resize.NONE:
+        for i, im in enumerate(imgs):
+            if im.shape[:2] != (S, S):
+                raise InvalidArgumentError(-1, 'images[%d]: Resize.NONE needs %dx%d images, got %dx%d'
+                                           % (i, S, S, im.shape[0], im.shape[1]))
+    return imgs, S, mode
+
+
+def pack_images(images):
+    """list of uint8 [H,W,3] -> (packed uint8 bytes, offsets i64 [N], image_shapes i32 [N,2]): the layout of
+    xdet_preprocess_eval_batch (include/xdet.h)"""
+    sizes = [im.size for im in images]
+    offsets = np.zeros(len(images), np.int64)
+    offsets[1:] = np.cumsum(sizes)[:-1]
+    packed = np.concatenate([im.reshape(-1) for im in images])
+    shapes = np.array([im.shape[:2] for im in images], np.int32).reshape(-1, 2)
+    return packed, offsets, shapes
+
+
+def resize_geometry(H, W, S, resize):
+    """host side of the resize step: (h, w) entering resize_image_bboxes_with_crop_or_pad and its (crop_y, crop_x,
+    pad_y, pad_x, kept_h, kept_w) (common_preprocessing.py:403-418, tf_image.py:261-274); None for WARP / NONE"""
+    mode = _resize_mode(resize)
+    if mode in (Resize.NONE, Resize.WARP_RESIZE):
+        return None
+    h, w = H, W
+    if mode == Resize.PAD_AND_RESIZE:
+        factor = min(np.float64(1.0), min(np.float64(S) / np.float64(H), np.float64(S) / np.float64(W)))
+        h, w = int(np.floor(factor * np.float64(H))), int(np.floor(factor * np.float64(W)))
+    return (h, w), (max((h - S) // 2, 0), max((w - S) // 2, 0), max((S - h) // 2, 0), max((S - w) // 2, 0),
+                    min(S, h), min(S, w))
+
+
+def bboxes_crop_or_pad(bboxes, height, width, offset_y, offset_x, target_height, target_width):
+    """tf_image.bboxes_crop_or_pad (tf_image.py:179-203): f32, b * [h,w,h,w] + offset, / [th,tw,th,tw]"""
+    f32 = np.float32
+    b = np.asarray(bboxes, f32).reshape(-1, 4)
+    b = (b * np.array([height, width, height, width], f32)).astype(f32)
+    b = (b + np.array([offset_y, offset_x, offset_y, offset_x], f32)).astype(f32)
+    return (b / np.array([target_height, target_width, target_height, target_width], f32)).astype(f32)
+
+
+def _map_gt_boxes(bboxes, H, W, S, mode):
+    b = np.asarray(bboxes, np.float32).reshape(-1, 4)
+    geom = resize_geometry(H, W, S, mode)
+    if geom is None:
+        return b.copy()
+    (h, w), (cy, cx, py, px, kh, kw) = geom
+    return bboxes_crop_or_pad(bboxes_crop_or_pad(b, h, w, -cy, -cx, kh, kw), kh, kw, py, px, S, S)
+
+
+def light_head_preprocess_batch(images, out_size, resize=Resize.WARP_RESIZE, stream=None):
+    """light_head_preprocess_for_eval's image side for a list of uint8 [H,W,3] images of any sizes, one launch
+    (xdet_preprocess_eval_batch) -> (planes f32 [N,3,S,S], bbox_img f32 [N,4], image_shapes i32 [N,2])."""
+    imgs, S, mode = _check_batch(images, out_size, resize)
+    packed, offsets, shapes = pack_images(imgs)
+    N = len(imgs)
+    d_p, d_o, d_s = to_device(packed), to_device(offsets), to_device(shapes)
+    d_out, d_b = DeviceBuffer(N * 3 * S * S * 4), DeviceBuffer(N * 16)
+    check(lib().xdet_preprocess_eval_batch(d_p.ptr, packed.nbytes, d_o.ptr, d_s.ptr, N, S, int(mode), d_out.ptr,
+                                           d_b.ptr, stream.handle if stream else None))
+    return (to_host(d_out.ptr, (N, 3, S, S), np.float32, stream), to_host(d_b.ptr, (N, 4), np.float32, stream),
+            shapes)
+
+
 def light_head_preprocess_for_eval(image, labels=None, bboxes=None, out_shape=(480, 480), data_format='NHWC',
-                                   difficults=None, stream=None):
-    """preprocessing/common_preprocessing.py:383-440 (Resize.WARP_RESIZE, the eval default):
-    uint8 [H,W,3] -> (image f32 [S,S,3] or [3,S,S], labels, bboxes, bbox_img=[0,0,1,1])."""
-    img = np.ascontiguousarray(image, np.uint8)
-    if img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError('Input must be of size [height, width, C>0]')
-    assert out_shape[0] == out_shape[1], 'square network input'
+                                   difficults=None, resize=Resize.WARP_RESIZE, stream=None):
+    """preprocessing/common_preprocessing.py:383-440:
+    uint8 [H,W,3] -> (image f32 [S,S,3] or [3,S,S], labels, bboxes, bbox_img f32 [4]).
+    The image goes through xdet_preprocess_eval_batch; the ground-truth `bboxes` through the same crop / pad as
+    bbox_img (on the host, f32 in TF's order), and the boxes and labels flagged in `difficults` are removed (:427-431).
+    Resize.NONE needs an S x S image (the network input is S x S)."""
+    img = _check_image(np.asarray(image, np.uint8))
+    if out_shape[0] != out_shape[1]:
+        raise InvalidArgumentError(-1, 'square network input expected, got %r' % (tuple(out_shape),))
     S = int(out_shape[0])
-    d_in = to_device(img)
-    d_out = DeviceBuffer(3 * S * S * 4)
-    check(lib().xdet_preprocess_eval(d_in.ptr, img.shape[0], img.shape[1], d_out.ptr, S,
-                                     stream.handle if stream else None))
-    chw = to_host(d_out.ptr, (3, S, S), np.float32, stream)
+    planes, bbox_img, _ = light_head_preprocess_batch([img], S, resize, stream)
+    chw = planes[0]
     out = chw if data_format == 'NCHW' else np.ascontiguousarray(chw.transpose(1, 2, 0))
-    return out, labels, bboxes, np.array([0., 0., 1., 1.], np.float32)
+    if bboxes is not None:
+        bboxes = _map_gt_boxes(bboxes, img.shape[0], img.shape[1], S, resize)
+    if difficults is not None:
+        keep = np.logical_not(np.asarray(difficults).astype(bool)).reshape(-1)
+        if labels is not None:
+            labels = np.asarray(labels)[keep]
+        if bboxes is not None:
+            bboxes = bboxes[keep]
+    return out, labels, bboxes, bbox_img[0]
 
 
-def light_head_preprocess_for_test(image, out_shape, data_format='NHWC', stream=None):
-    """preprocessing/common_preprocessing.py:442-458."""
-    return light_head_preprocess_for_eval(image, None, None, out_shape, data_format, stream=stream)[0]
+def light_head_preprocess_for_test(image, out_shape, data_format='NHWC', resize=Resize.WARP_RESIZE, stream=None):
+    """preprocessing/common_preprocessing.py:442-458.  (The reference accepts `resize` here but always warps; this
+    applies it -- the default is the same.)"""
+    return light_head_preprocess_for_eval(image, None, None, out_shape, data_format, resize=resize, stream=stream)[0]
