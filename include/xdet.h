@@ -280,6 +280,42 @@ int xdet_bboxes_eval(const float* cls, int ld_cls, const float* boxes, int N, in
                      const int* image_shapes, const float* bbox_img, int net_h, int net_w, float select_thr,
                      float nms_thr, int nms_topk, float* det_scores, float* det_boxes, void* stream);
 
+/* ---- bboxes_eval, scoring part: eval_helper.bboxes_matching_batch (utility/eval_helper.py:700-830) -----------------
+ * The TP / FP flags of every detection slot against the image's ground truth, per (image, class), as the greedy walk of
+ * bboxes_matching (:722-781) gives them: IoU in f32 in its operation order, times the 0/1 class mask, FIRST maximum over
+ * the boxes, strictly greater than the threshold; a detection whose best box is `difficult` is neither; with no box of
+ * the class the best box is box 0 and ITS difficult flag decides.  Every one of the K slots is matched, padding too.
+ *   det_scores f32 [N,C,K], det_boxes f32 [N,C,K,4]: what xdet_net_forward / xdet_bboxes_eval write (class label c + 1)
+ *   glabels i32 [N,G], gbboxes f32 [N,G,4] (ymin,xmin,ymax,xmax in the detections' frame), gdifficults u8 [N,G],
+ *   n_gt i32 [N]: image n has its first n_gt[n] entries (clamped to [0, G]; the rest is never read); G <= 512
+ *   -> tp u8 [N,C,K], fp u8 [N,C,K], n_gbboxes i32 [N,C] (boxes of the class that are not difficult)
+ * An image the forward marked bad (NaN in slot 0 of a class's scores) is not scored: flags and n_gbboxes 0.
+ * det_boxes and gbboxes must be 16-byte aligned.  Errors (N, C, K, G <= 0, G > 512, NULL, threshold not finite) ->
+ * XDET_ERR_INVALID_ARG before any GPU work. */
+int xdet_bboxes_matching(const float* det_scores, const float* det_boxes, int N, int C, int K, const int32_t* glabels,
+                         const float* gbboxes, const uint8_t* gdifficults, const int32_t* n_gt, int G,
+                         float matching_threshold, uint8_t* tp, uint8_t* fp, int32_t* n_gbboxes, void* stream);
+/* metrics.streaming_tp_fp_arrays (utility/metrics.py:102-170) on the device: per class the object count and one record
+ * (score, TP-or-FP, image id, slot) for every slot with (tp | fp) and score > 1e-4.  xdet_tpfp_update = the matcher above
+ * + the append, enqueued on `stream`; neither synchronises nor reads anything on the host (the call that first sees a larger
+ * N than any before allocates the flag scratch, which the handle owns).  Records of a call land behind the class's cursor
+ * in (image index within the call, slot) order whatever the scheduling.  image_ids i32 [N] (device) names the images so
+ * that shards can be merged.  A call whose records do not fit the class's capacity appends nothing for that class (no
+ * objects either) and sets `overflow`; a bad image adds nothing and is counted in `bad_images`.
+ * xdet_tpfp_read is the one host-synchronous call: counts i32 [C], nobjects i64 [C], bad_images, overflow; then, when the
+ * four record arrays are given (each records_capacity entries, sized by the caller from an earlier call's counts), the
+ * records of class 0, 1, ... back to back.  xdet_tpfp_reset clears counts, objects and both flags.
+ * The handle is typed like the net handles: another handle type -> XDET_ERR_INVALID_ARG. */
+int xdet_tpfp_create(void** acc, int C, int K, int capacity_per_class);
+int xdet_tpfp_destroy(void* acc);
+int xdet_tpfp_reset(void* acc, void* stream);
+int xdet_tpfp_update(void* acc, const float* det_scores, const float* det_boxes, int N, const int32_t* image_ids,
+                     const int32_t* glabels, const float* gbboxes, const uint8_t* gdifficults, const int32_t* n_gt, int G,
+                     float matching_threshold, void* stream);
+int xdet_tpfp_read(void* acc, int32_t* counts_host, int64_t* nobjects_host, int32_t* bad_images_host, int32_t* overflow_host,
+                   int64_t records_capacity, float* scores_host, uint8_t* is_tp_host, int32_t* image_id_host,
+                   int32_t* slot_host, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

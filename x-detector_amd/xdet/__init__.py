@@ -12,6 +12,9 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   AnchorCreator, ext_decode_rois
                           <- preprocessing/anchor_manipulator.py:686-757, 671-683
   bboxes_eval             <- light_head_rfcn_eval.py:263-287
+  bboxes_matching_batch, GpuStreamingTpFp (xdet.evaluation; LightHeadDetector.evaluate_images / evaluate)
+                          <- eval_helper.bboxes_matching_batch, metrics.streaming_tp_fp_arrays
+                                                             (light_head_rfcn_eval.py:288-338)
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """
@@ -21,7 +24,7 @@ from . import weights                                                         # 
 
 def __getattr__(name):
     import importlib
-    for mod in ('ops', 'model', 'resnet', 'runtime'):
+    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation'):
         m = importlib.import_module('.' + mod, __name__)
         if hasattr(m, name):
             return getattr(m, name)

@@ -105,6 +105,14 @@ SIGNATURES = {
     'xdet_ext_decode_rois': (c_int, [PF, PF, c_int, c_int64, PF, c_void_p]),
     'xdet_bboxes_eval': (c_int, [PF, c_int, PF, c_int, c_int, c_int, PI, PF, c_int, c_int, c_float, c_float, c_int,
                                  PF, PF, c_void_p]),
+    'xdet_bboxes_matching': (c_int, [PF, PF, c_int, c_int, c_int, PI, PF, c_void_p, PI, c_int, c_float, c_void_p, c_void_p, PI,
+                                     c_void_p]),
+    'xdet_tpfp_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
+    'xdet_tpfp_destroy': (c_int, [c_void_p]),
+    'xdet_tpfp_reset': (c_int, [c_void_p, c_void_p]),
+    'xdet_tpfp_update': (c_int, [c_void_p, PF, PF, c_int, PI, PI, PF, c_void_p, PI, c_int, c_float, c_void_p]),
+    'xdet_tpfp_read': (c_int, [c_void_p, PI, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int64, PF, c_void_p,
+                               PI, PI, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),

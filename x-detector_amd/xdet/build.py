@@ -25,6 +25,7 @@ SOURCES = [
     ('rotated_psroialign.hip', ['-ffp-contract=off']),
     ('proposals.hip', ['-ffp-contract=off']),
     ('detect.hip', ['-ffp-contract=off']),
+    ('evalmatch.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('net.hip', []),
     ('comm.hip', []),

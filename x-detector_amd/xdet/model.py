@@ -182,11 +182,20 @@ class LightHeadDetector(object):
         light_head_preprocess_for_eval with `resize`, ops.Resize) and the forward run as one launch sequence, or one
         graph (use_graph): image sizes live in device buffers, so batches of other sizes replay the same graph as
         long as the packed bytes fit."""
+        n = self._ingest_forward(images, resize, use_graph)
+        s, b = self.detections(n)
+        return [{c + 1: (s[i, c], b[i, c]) for c in range(self.num_classes - 1)} for i in range(n)]
+
+    def _ingest_forward(self, images, resize, use_graph, before_upload=None):
+        """detect_images' asynchronous part: pack, copy, xdet_net_forward_u8 on self.stream -> the number of images.
+        before_upload(n): called once the batch is checked, in front of the first copy."""
         from . import ops
         imgs, S, mode = ops._check_batch(images, self.image_size, ops.Resize.WARP_RESIZE if resize is None else resize,
                                          self.max_batch)
         packed, offsets, shapes = ops.pack_images(imgs)
         n = len(imgs)
+        if before_upload is not None:
+            before_upload(n)
         B = self.max_batch
         if not hasattr(self, '_ingest'):
             # offsets / image_shapes / bbox_img: max_batch entries, allocated once.  packed grows only: a regrown buffer
@@ -207,8 +216,55 @@ class LightHeadDetector(object):
                                         bufs['shapes'].ptr, n, int(mode), self._images.ptr, bufs['bbox_img'].ptr,
                                         self._det_scores.ptr, self._det_boxes.ptr, 1 if use_graph else 0, h))
         self._N = n
-        s, b = self.detections(n)
-        return [{c + 1: (s[i, c], b[i, c]) for c in range(self.num_classes - 1)} for i in range(n)]
+        self._host_keep = (packed, offsets, shapes)      # (referenced until the next call: nothing waits for the copies here)
+        return n
+
+    def evaluate_images(self, images, ground_truths, image_ids=None, resize=None, accumulator=None, matching_threshold=0.5,
+                        use_graph=True):
+        """detect_images' ingest and forward, then the scoring of the detections against the ground truth
+        (evaluation.GpuStreamingTpFp: xdet_tpfp_update) on the same stream, with the ground truth copied to the device in
+        front of the forward -- light_head_rfcn_eval.py:263-296 for a batch.  Nothing is copied back and the stream is not
+        synchronised: the call returns with the work enqueued, the accumulator is read later (records(),
+        average_precisions()).  ground_truths: per image (glabels, gbboxes, gdifficults) with boxes (ymin, xmin, ymax,
+        xmax) relative to the original image, as glabels_raw / gbboxes_raw / isdifficult; image_ids: one integer per image
+        (default: a running count per detector), the order of the dataset.  Returns the accumulator (the detector's own
+        unless one is given)."""
+        from .evaluation import GpuStreamingTpFp
+        if accumulator is None:
+            if not hasattr(self, '_accumulator'):
+                self._accumulator = GpuStreamingTpFp(self.num_classes, self.nms_topk)
+            accumulator = self._accumulator
+        if len(ground_truths) != len(images):
+            raise InvalidArgumentError(-1, 'evaluate_images: %d images but ground truth of %d' % (len(images), len(ground_truths)))
+        if image_ids is None:
+            first = getattr(self, '_next_image_id', 0)
+            image_ids = np.arange(first, first + len(images), dtype=np.int32)
+
+        def stage(n):
+            accumulator.stage(image_ids, ground_truths, self.stream)
+        n = self._ingest_forward(images, resize, use_graph, before_upload=stage)
+        accumulator.enqueue(self._det_scores.ptr, self._det_boxes.ptr, n, matching_threshold, self.stream)
+        self._next_image_id = int(np.max(image_ids)) + 1
+        return accumulator
+
+    def evaluate(self, dataset, batch=None, resize=None, accumulator=None, matching_threshold=0.5):
+        """dataset: an iterable of (image uint8 [H,W,3], (glabels, gbboxes, gdifficults)) -> {'AP_VOC07': {class: AP},
+        'AP_VOC12': {...}, 'mAP_VOC07': ., 'mAP_VOC12': .} as the reference's eval reports them
+        (light_head_rfcn_eval.py:304-338); images are numbered in the order they arrive."""
+        from .evaluation import GpuStreamingTpFp
+        acc = accumulator if accumulator is not None else GpuStreamingTpFp(self.num_classes, self.nms_topk)
+        batch = batch or self.max_batch
+        images, gts, seen = [], [], 0
+        for image, gt in dataset:
+            images.append(image)
+            gts.append(gt)
+            if len(images) == batch:
+                self.evaluate_images(images, gts, np.arange(seen, seen + len(images)), resize, acc, matching_threshold)
+                seen += len(images)
+                images, gts = [], []
+        if images:
+            self.evaluate_images(images, gts, np.arange(seen, seen + len(images)), resize, acc, matching_threshold)
+        return acc.summary()
 
     def graph_count(self):
         """graphs cached by this detector's net (xdet_net_graph_count)"""
