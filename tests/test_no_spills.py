@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'x-detector_amd', 'csrc')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 EXEMPT = {'conv_mfma.hip'}
+HOST_UNITS = ('plan.hip', 'lighthead.hip', 'resnet_trunk.hip', 'cabi.hip')   # plans, nets, C ABI: host code only
 
 
 def _usage(src, extra):
@@ -42,7 +43,12 @@ def test_no_kernel_spills_to_scratch():
     spec = importlib.util.spec_from_file_location('xdet_build', os.path.join(ROOT, 'x-detector_amd', 'xdet', 'build.py'))
     B = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(B)
-    todo = [(s, e) for s, e in B.SOURCES if s not in EXEMPT and s not in ('net.hip', 'comm.hip')]
+    # a unit skipped by name must not hide a kernel (the headers the host units share included)
+    for src in HOST_UNITS + ('layers.h', 'plan.h', 'lighthead.h', 'resnet_trunk.h'):
+        assert src.endswith('.h') or src in [s for s, _ in B.SOURCES], src
+        with open(os.path.join(CSRC, src)) as f:
+            assert '__global__' not in f.read(), src + ' is skipped as host code but holds a kernel'
+    todo = [(s, e) for s, e in B.SOURCES if s not in EXEMPT and s not in HOST_UNITS + ('comm.hip',)]
     with ThreadPoolExecutor(max_workers=6) as ex:
         res = list(ex.map(lambda a: _usage(*a), todo))
     n = 0

@@ -79,6 +79,9 @@ int launch_maxpool3x3s2_bn_planes(const float* in, const float* scale, const flo
                                   int N, int H, int W, int C, int ld, int Ho, int Wo, int pad_t, int pad_l, float mul,
                                   hipStream_t s, unsigned short* hi2 = nullptr, unsigned short* lo2 = nullptr, int c32_2 = 0,
                                   float mul2 = 1.f);
+// bn + ReLU of an f32 tensor; hi != NULL: also as split planes scaled by mul
+int launch_bn_relu(const float* in, const float* scale, const float* shift, float* out, unsigned short* hi, unsigned short* lo,
+                   int64_t npix, int ld, float mul, hipStream_t s);
 // vertical half only, over rows the producer already pooled horizontally (sepconv_fused.hip HPOOL)
 int launch_maxpool_v3s2_add(const float* in_hpooled, const float* res, float* out, int N, int H, int Wo, int C, int ld,
                             int Ho, int pad_t, hipStream_t s, unsigned short* sub_hi = nullptr, unsigned short* sub_lo = nullptr,

@@ -647,7 +647,7 @@ int launch_planes_copy_blocks(const unsigned short* shi, const unsigned short* s
 // ResNet v2 stem tail (net/resnet_v2.py:311-330 initial_max_pool, then the first block's batch_norm_relu :142-156): the pooled
 // tensor has ONE reader, the first block's pre-activation, and that one is read as split planes only (its shortcut is a
 // projection of the pre-activation).  Same window walk as maxpool3x3s2_add_kernel; the result goes through bn + ReLU and
-// out as planes [pix/16][ld/32][16][32] (the arithmetic of bn_relu_kernel in net.hip: fma, NaN-keeping ReLU, * mul, hi / lo)
+// out as planes [pix/16][ld/32][16][32] (the arithmetic of bn_relu_kernel below: fma, NaN-keeping ReLU, * mul, hi / lo)
 // -- the pooled f32 tensor (29.5 MB per batch of 8) is neither written nor read back.
 __global__ __launch_bounds__(256) void maxpool3x3s2_bn_planes_kernel(const float* __restrict__ in, const float* __restrict__ scale,
                                                                      const float* __restrict__ shift,
@@ -730,6 +730,46 @@ int launch_maxpool3x3s2_bn_planes(const float* in, const float* scale, const flo
   const dim3 grid((unsigned)(cdiv(nbands, 8) * 8), (unsigned)cdiv((int64_t)Wo * (ld / 4), 256));
   hipLaunchKernelGGL(maxpool3x3s2_bn_planes_kernel, grid, dim3(256), 0, s, in, scale, shift, hi, lo, H, W, ld, Ho, Wo, pad_t, pad_l,
                      nbands, bpi, mul, hi2, lo2, c32_2, mul2);
+  XDET_LAUNCH_CHECK();
+  return XDET_OK;
+}
+
+// A block's opening BN + ReLU as its own pass (pre-activation bottlenecks, net/resnet_v2.py:142-156); also writes the result
+// as split planes [pix/16][ld/32][16][32] when hi != NULL (its consumers are 1x1 convs on the LDS-DMA path)
+__global__ void bn_relu_kernel(const float* __restrict__ in, const float* __restrict__ scale,
+                               const float* __restrict__ shift, float* __restrict__ out,
+                               unsigned short* __restrict__ hi, unsigned short* __restrict__ lo, int64_t npix, int ld,
+                               float mul) {
+  // mul = 2^-e, the planes' activation pre-scale (1 by default): hi + lo = relu(bn(x)) * mul; the f32 copy is unscaled
+  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+  const int c4n = ld >> 2;
+  const int64_t total = npix * c4n;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % c4n) * 4;
+    float4 v = reinterpret_cast<const float4*>(in)[i];
+    const float4 sc = *reinterpret_cast<const float4*>(scale + c), sh = *reinterpret_cast<const float4*>(shift + c);
+    // (a ReLU that keeps NaN, as the conv epilogue's: an overflowed split operand upstream must reach the caller, not turn into 0)
+    v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y); v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
+    v.x = !(v.x <= 0.f) ? v.x : 0.f; v.y = !(v.y <= 0.f) ? v.y : 0.f; v.z = !(v.z <= 0.f) ? v.z : 0.f; v.w = !(v.w <= 0.f) ? v.w : 0.f;
+    reinterpret_cast<float4*>(out)[i] = v;
+    if (hi) {
+      const int64_t pix = i / c4n;
+      v.x *= mul; v.y *= mul; v.z *= mul; v.w *= mul;
+      const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
+      h4 hv = {h0, h1, h2, h3};
+      h4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
+               (_Float16)(v.w - (float)h3)};
+      const int64_t o = (((pix >> 4) * (ld >> 5) + (c >> 5)) << 9) + ((pix & 15) << 5) + (c & 31);
+      *reinterpret_cast<uint2*>(hi + o) = *reinterpret_cast<uint2*>(&hv);
+      *reinterpret_cast<uint2*>(lo + o) = *reinterpret_cast<uint2*>(&lv);
+    }
+  }
+}
+
+int launch_bn_relu(const float* in, const float* scale, const float* shift, float* out, unsigned short* hi, unsigned short* lo,
+                   int64_t npix, int ld, float mul, hipStream_t s) {
+  const int blocks = (int)std::min<int64_t>(cdiv(npix * (ld / 4), 256), 256 * 32);
+  hipLaunchKernelGGL(bn_relu_kernel, dim3(blocks), dim3(256), 0, s, in, scale, shift, out, hi, lo, npix, ld, mul);
   XDET_LAUNCH_CHECK();
   return XDET_OK;
 }
@@ -887,7 +927,7 @@ int launch_range_check(const float* x, int N, size_t per_image, float limit, int
   return XDET_OK;
 }
 
-// ---- range calibration (activation pre-scale of the split-precision planes, net.hip calibrate()) ----
+// ---- range calibration (activation pre-scale of the split-precision planes, Plan::calibrate_planes in plan.hip) ----
 // largest |hi| of a split plane as f16 bits (inf / NaN sort above every finite value: bits >= 0x7c00)
 __global__ __launch_bounds__(256) void absmax_planes_kernel(const uint4* __restrict__ hi, int64_t n8, unsigned* __restrict__ out) {
   unsigned m = 0;

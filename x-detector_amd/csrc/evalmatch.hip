@@ -286,7 +286,7 @@ static int launch_bboxes_matching(const float* det_scores, const float* det_boxe
   return XDET_OK;
 }
 
-// The accumulator handle.  Laid out like the net handles (csrc/net.hip struct Plan: a virtual destructor, then the kind tag), so
+// The accumulator handle.  Laid out like the net handles (csrc/plan.h struct Plan: a virtual destructor, then the kind tag), so
 // that an entry point given a handle of another type sees a tag that is not its own and returns XDET_ERR_INVALID_ARG.
 struct TpfpAccumulator {
   virtual ~TpfpAccumulator() {

@@ -1,0 +1,125 @@
+// The Light-Head R-CNN eval graph (lighr_head_model_fn, light_head_rfcn_eval.py:364-433) as a static launch plan.
+#pragma once
+#include "plan.h"
+
+namespace xdet {
+
+// ST_EXIT: the exit flow (conv2d_4, blocks 13-14, net/xception_body.py:340-376) -- part of the backbone, its own stage so that
+// the RPN branch, which only needs mid_outputs (:339), can fork in front of it
+enum { ST_BODY = 0, ST_RPN = 1, ST_LSEP = 2, ST_HEAD = 3, ST_EXIT = 4 };
+
+struct LightHeadNet : Plan {
+  xdet_lighthead_config cfg;
+  bool built = false;
+  Buf in4, mid_x, out, rpn_out, feat, pooled, fc, cls_reg;
+  float *objectness = nullptr, *rpn_boxes = nullptr, *proposals = nullptr, *head_boxes = nullptr;
+  float* class_probs = nullptr;   // [B][num_classes][R] softmax of the head's logits, class-major (head_decode_probs_kernel)
+  float *anc_yx = nullptr, *anc_hw = nullptr;
+  float* mid_relu = nullptr;   // materialised ReLU(x) ("mid_outputs", xception_body.py:339) for API users
+  void* prop_ws_mem = nullptr;
+  ProposalWorkspace prop_ws;
+  int* def_shapes = nullptr;
+  float* def_bbox = nullptr;
+  int fmap = 0, n_anchor = 0;
+  int large_sep_mode = 0;               // 0 = auto, 1 = direct (15,1)/(1,15) convs, 2 = spectral (DFT-domain GEMMs)
+  bool large_sep_spectral = false;      // decided at build
+  bool rpn_side_stream = true;          // option "rpn_stream" = "side" | "main"
+  bool check_range = false;             // option "check_range" = "off" | "on": validate every activation against the f16 range
+  bool latency_ksplit = true;           // option "ksplit" = "on" | "off" | "all": fixed split-K for the narrow head GEMM (on),
+  bool rpn_ksplit = false;              // ... and the RPN conv as well (all)
+  std::vector<std::function<int(int, hipStream_t)>> extra_range_checks;   // tensors that are not plain [N][pixels][ld] (DFT bins)
+  bool stem_direct = false;             // block1_conv1 as the dedicated NCHW -> planes kernel
+  const float* cur_images = nullptr;
+  hipStream_t aux = nullptr;            // side stream of the RPN/proposal branch
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+
+  ~LightHeadNet() {
+    graphs.clear();              // (before the streams they were captured on)
+    // the side stream and its fork / join events (created on the first forward): a net that leaves them behind leaks a
+    // hardware queue per instance -- a long test session (~150 nets) ran the runtime out of them and died inside a capture
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (aux) (void)hipStreamDestroy(aux);
+  }
+
+  int build_body();
+
+  int build_rpn();
+
+  int large_sep_weights(int cin, int mid, int co, std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb,
+                        std::vector<float>* sc, std::vector<float>* sh) const;
+
+  int build_large_sep();
+
+  int build_large_sep_spectral();
+
+  int build_head();
+
+  int build();
+
+  int check(int N) const {
+    if (!built) {
+      set_last_error("net not built");
+      return XDET_ERR_STATE;
+    }
+    XDET_REQUIRE(N > 0 && N <= max_batch, "batch must be in 1..max_batch");
+    return XDET_OK;
+  }
+  int xception_body(const float* images, int N, hipStream_t s) {
+    XDET_TRY(entry_and_middle_flow(images, N, s));
+    return run_stage(ST_EXIT, N, s);
+  }
+  int entry_and_middle_flow(const float* images, int N, hipStream_t s) {      // up to mid_outputs
+    XDET_TRY(check(N));
+    XDET_REQUIRE(images != nullptr, "images is NULL");
+    cur_images = images;         // the stem op reads the NCHW input directly (graphs are keyed on this pointer)
+    if (!stem_direct) XDET_TRY(launch_nchw_to_nhwc4(images, in4.p, N, 3, cfg.image_size, cfg.image_size, 4, s));
+    return run_stage(ST_BODY, N, s);
+  }
+  int rpn_decode(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_rpn_decode(rpn_out.p, rpn_out.ld, 0, 2 * cfg.num_anchors, N, fmap, fmap, cfg.num_anchors, anc_yx,
+                             anc_hw, objectness, rpn_boxes, s);
+  }
+  int get_proposals(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_get_proposals(objectness, rpn_boxes, N, n_anchor, cfg.rpn_pre_nms_top_n, cfg.rpn_post_nms_top_n,
+                                cfg.rpn_nms_thres, cfg.rpn_min_size, prop_ws, proposals, s);
+  }
+  int get_head(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    const int C = cfg.bank * cfg.grid * cfg.grid;
+    XDET_TRY(launch_psroialign(feat.p, proposals, pooled.p, nullptr, N, C, feat.H, feat.W, cfg.rpn_post_nms_top_n,
+                               cfg.grid, cfg.grid, 1, 1, feat.ld, pooled.ld, /*corners=*/1, s));
+    return run_stage(ST_HEAD, N, s);
+  }
+  int head_decode(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_ext_decode_rois(proposals, cls_reg.p + cfg.num_classes, cls_reg.ld,
+                                  (int64_t)N * cfg.rpn_post_nms_top_n, head_boxes, s);
+  }
+  // the whole forward: A11 and the softmax A12 starts from in one pass over the ROIs, then A12 from the probabilities
+  int head_decode_probs(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_head_decode_probs(proposals, cls_reg.p, cls_reg.ld, cfg.num_classes, cfg.rpn_post_nms_top_n,
+                                    (int64_t)N * cfg.rpn_post_nms_top_n, head_boxes, class_probs, prop_ws.bad, s);
+  }
+  int bboxes_eval_probs(int N, const int* shapes, const float* bbox, float* ds, float* db, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_bboxes_eval_probs(class_probs, head_boxes, N, cfg.rpn_post_nms_top_n, cfg.num_classes,
+                                    shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
+                                    cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
+  }
+  // the stage entry points (xdet_net_head_decode / xdet_net_bboxes_eval): each complete on its own, from "cls_reg" / "head_boxes"
+  int bboxes_eval(int N, const int* shapes, const float* bbox, float* ds, float* db, hipStream_t s) {
+    XDET_TRY(check(N));
+    return launch_bboxes_eval(cls_reg.p, cls_reg.ld, head_boxes, N, cfg.rpn_post_nms_top_n, cfg.num_classes,
+                              shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
+                              cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
+  }
+  int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);
+  int forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
+                    hipStream_t s);
+};
+
+}  // namespace xdet

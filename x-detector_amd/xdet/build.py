@@ -27,7 +27,10 @@ SOURCES = [
     ('detect.hip', ['-ffp-contract=off']),
     ('evalmatch.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
-    ('net.hip', []),
+    ('plan.hip', []),
+    ('lighthead.hip', []),
+    ('resnet_trunk.hip', []),
+    ('cabi.hip', []),
     ('comm.hip', []),
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-result']
