@@ -316,6 +316,55 @@ int xdet_tpfp_read(void* acc, int32_t* counts_host, int64_t* nobjects_host, int3
                    int64_t records_capacity, float* scores_host, uint8_t* is_tp_host, int32_t* image_id_host,
                    int32_t* slot_host, void* stream);
 
+/* ---- training targets: AnchorEncoder.encode_all_anchors / ext_encode_rois (preprocessing/anchor_manipulator.py:118-171,
+ * 319-445) ---------------------------------------------------------------------------------------------------------
+ * What the training script does with the ground truth before any loss, on the device (csrc/targets.hip).  All arithmetic
+ * in f32, every operation rounded on its own, in the reference's order.  Ground truth as xdet_bboxes_matching takes it:
+ * glabels i32 [N,G], gbboxes f32 [N,G,4] (ymin,xmin,ymax,xmax), n_gt i32 [N] (clamped to [0, G]; nothing behind it is
+ * read), G <= 512.  Coordinates are expected finite.
+ *   overlap O[g,a]: inter = max(min(ymax) - max(ymin), 0) * max(min(xmax) - max(xmin), 0), union = (area_g + area_a) - inter,
+ *     O = union == 0 ? 0 : inter / union, times the 0/1 inside mask of candidate a:
+ *     ymin >= -b && xmin >= -b && ymax < f32(1 + b) && xmax < f32(1 + b)   (1 + b formed in double from the float argument)
+ *   dual-max match (high, low): best_g[a] = FIRST maximum of column a, mv its value; m = -1 if mv < low, -2 if
+ *     low <= mv < high, else best_g.  best_a[g] = FIRST maximum of row g (an all-zero row points at candidate 0).  A
+ *     candidate named by some best_a[g] takes the FIRST maximum over g of O[g,a] * [best_a[g] == a] -- box 0 when all of
+ *     these are zero -- and score O[that box, a]; every other candidate scores mv.
+ *   label = glabels[max(m,0)] * [m > -1] - [m < -1];  target = [m > -1] * (((gcy - yref) / href) / s0, ((gcx - xref) / wref) / s1,
+ *     log(gh / href) / s2, log(gw / wref) / s3) of box max(m,0), the multiplication by the mask performed.
+ *   An image without participating ground truth: labels 0, targets and scores 0 (the reference fails there).
+ * xdet_encode_anchors: candidates are the Hh * Ww * A anchors (anchors_yx [Hh*Ww,2], anchors_hw [A,2], index
+ *   (y * Ww + x) * A + k as in xdet_rpn_decode; corners yref -+ href / 2, xref -+ wref / 2), all of the image's boxes take part.
+ *   -> labels i32 [N,HWA], targets f32 [N,HWA,4], scores f32 [N,HWA].
+ * xdet_encode_rois: boxes with label <= 0 are dropped (order kept, G' left); candidates are the image's R ROIs followed by
+ *   those G' boxes (M = R + G' <= 8192 with R + G as the bound), reference point yref = ymin + h / 2, h = ymax - ymin.  Then the
+ *   sample: exp_fg = round_half_even(f32(rois_per_image) * fg_fraction); pos = {label > 0}, neg = {label == 0 and score >
+ *   bg_low_thr} in index order; fg = pos if |pos| < exp_fg else the first exp_fg of shuffle(pos); exp_bg = rois_per_image -
+ *   min(|pos|, exp_fg); bg likewise from neg; keep = fg ++ bg; with n_keep < rois_per_image and left = rois_per_image -
+ *   n_keep the output rows are keep[tile(range(n_keep), left / n_keep + 1) ++ shuffle(range(n_keep))[: left % n_keep]].
+ *   shuffle(S) = S ordered by (key, element) ascending, key = mix(mix(mix(seed ^ 0x9E3779B9) + image) ^ (2 * element + stream))
+ *   in 32-bit unsigned arithmetic, mix(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16;
+ *   stream 0 for candidates, 1 for the positions of the tail; image = image_ids[n] (device i32 [N]; NULL: n).
+ *   -> out_rois f32 [N,rois_per_image,4], out_targets likewise, out_labels i32, out_scores f32 [N,rois_per_image];
+ *   out_index (may be NULL) the candidate index, >= R for a ground-truth box; counts (may be NULL) i32 [N,4]: M, |pos|,
+ *   |neg|, n_keep; all_labels / all_targets / all_scores (each may be NULL) the unsampled results [N,R+G], entries behind M:
+ *   label -1, zeros.  n_keep == 0 (the reference divides by zero): rows zero, label -1, index -1.
+ * workspace: xdet_targets_workspace_bytes(N, n_candidates, G) bytes, 16-byte aligned, n_candidates = R + G for
+ *   xdet_encode_rois and 0 for xdet_encode_anchors; it needs no initialisation: every control word is cleared by the call.
+ *   Box and target arrays must be 16-byte aligned; prior_scaling4 is four floats on the host.  Neither call synchronises or reads anything on the host.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: sizes <= 0, G > 512, R + G > 8192, rois_per_image outside [1, 8192],
+ *   fg_fraction outside [0, 1], a NULL required pointer, a border or threshold that is not finite, a prior scaling that is
+ *   zero or not finite. */
+size_t xdet_targets_workspace_bytes(int N, int n_candidates, int G);
+int xdet_encode_anchors(const float* anchors_yx, const float* anchors_hw, int Hh, int Ww, int A, float allowed_border,
+                        const int32_t* glabels, const float* gbboxes, const int32_t* n_gt, int N, int G, float high_thr,
+                        float low_thr, const float* prior_scaling4, void* workspace, int32_t* labels, float* targets,
+                        float* scores, void* stream);
+int xdet_encode_rois(const float* rois, int R, const int32_t* glabels, const float* gbboxes, const int32_t* n_gt, int N, int G,
+                     float allowed_border, float fg_thr, float bg_high_thr, float bg_low_thr, const float* prior_scaling4,
+                     int rois_per_image, float fg_fraction, uint32_t seed, const int32_t* image_ids, void* workspace,
+                     float* out_rois, float* out_targets, int32_t* out_labels, float* out_scores, int32_t* out_index,
+                     int32_t* counts, int32_t* all_labels, float* all_targets, float* all_scores, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

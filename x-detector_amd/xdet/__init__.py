@@ -15,16 +15,19 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   bboxes_matching_batch, GpuStreamingTpFp (xdet.evaluation; LightHeadDetector.evaluate_images / evaluate)
                           <- eval_helper.bboxes_matching_batch, metrics.streaming_tp_fp_arrays
                                                              (light_head_rfcn_eval.py:288-338)
+  AnchorEncoder (encode_all_anchors, ext_encode_rois), encode_anchors, encode_rois, host_encode_anchors, host_encode_rois
+  (xdet.targets)          <- preprocessing/anchor_manipulator.py:96-445: the training targets, on the GPU and in NumPy
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """
 from ._lib import XdetError, InvalidArgumentError, LightHeadConfig, lib      # noqa: F401
 from . import weights                                                         # noqa: F401
+from . import targets                                                         # noqa: F401
 
 
 def __getattr__(name):
     import importlib
-    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation'):
+    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets'):
         m = importlib.import_module('.' + mod, __name__)
         if hasattr(m, name):
             return getattr(m, name)

@@ -26,6 +26,7 @@ SOURCES = [
     ('proposals.hip', ['-ffp-contract=off']),
     ('detect.hip', ['-ffp-contract=off']),
     ('evalmatch.hip', ['-ffp-contract=off']),
+    ('targets.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('plan.hip', []),
     ('lighthead.hip', []),

@@ -369,7 +369,8 @@ def _same(t, view):
 
 
 def XceptionBody(input_image, num_classes, is_training=False, data_format='channels_last'):
-    """net/xception_body.py:236-379 -> (mid_outputs, outputs) as DeviceTensors (NHWC)."""
+    """net/xception_body.py:236-379 -> (mid_outputs, outputs) as DeviceTensors (NHWC).  Forward only: of the training
+    graph this package has the target assignment (get_proposals with is_training=True), not the batch-norm updates."""
     assert not is_training, 'forward-only path'
     d = _det()
     a = np.asarray(input_image, np.float32)
@@ -418,8 +419,11 @@ def rpn_decode(rpn_cls_score, rpn_bbox_pred):
 
 def get_proposals(object_score, bboxes_pred, encode_fn, rpn_pre_nms_top_n, rpn_post_nms_top_n, nms_threshold,
                   rpn_min_size, is_training, data_format):
-    """net/xception_body.py:402-448 (eval branch) -> proposals [N,post_n,4] numpy."""
-    assert not is_training, 'forward-only path'
+    """net/xception_body.py:402-448 -> proposals [N,post_n,4] numpy.  is_training=True (:446-448): the same proposal
+    stage, then encode_fn(proposals) with the net's `proposals` buffer handed over on the device -> its (rois, targets,
+    labels, scores) (targets.AnchorEncoder.ext_encode_rois).  Nothing else of the training graph exists here."""
+    if is_training and encode_fn is None:
+        raise InvalidArgumentError(-1, 'get_proposals: is_training=True needs an encode_fn')
     d = _det()
     # the native net bakes these in at build time (xdet_lighthead_config): a caller porting reference code
     # with other values must build the detector with them, not get silently different proposals
@@ -433,13 +437,16 @@ def get_proposals(object_score, bboxes_pred, encode_fn, rpn_pre_nms_top_n, rpn_p
     d.write('rpn_boxes', np.asarray(bboxes_pred, np.float32))
     check(lib().xdet_net_get_proposals(d.handle, n, d.stream.handle))
     _sync(d)
+    if is_training:
+        return encode_fn(d.buffer('proposals', n))
     return d.flat('proposals', (n, d.R, 4))
 
 
 def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposals_bboxes, num_classes, is_training,
              using_ohem, ohem_roi_one_image, data_format, var_scope):
     """net/xception_body.py:477-560 (eval, no OHEM) -> (cls_score [N,R,nc], bboxes_reg [N,R,4]) numpy.
-    `pooling_op` is accepted for signature parity; the fused HIP PsRoiAlign is always used."""
+    `pooling_op` is accepted for signature parity; the fused HIP PsRoiAlign is always used.  Forward only: the head's
+    losses and OHEM are not part of this package."""
     assert not is_training and not using_ohem, 'forward-only path'
     d = _det()
     if (grid_width, grid_height) != (d.cfg.grid, d.cfg.grid) or num_classes != d.cfg.num_classes:

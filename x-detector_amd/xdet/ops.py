@@ -350,10 +350,12 @@ def rpn_decode(rpn_cls, rpn_box, anchors, stream=None):
 def get_proposals(object_score, bboxes_pred, encode_fn=None, rpn_pre_nms_top_n=5000, rpn_post_nms_top_n=1000,
                   nms_threshold=0.7, rpn_min_size=16. / 480, is_training=False, data_format='channels_first',
                   return_counts=False, stream=None):
-    """net/xception_body.py:402-448, eval branch (is_training must be False).
-    object_score [N,n], bboxes_pred [N,n,4] -> proposals [N,post_n,4]."""
-    if is_training:
-        raise NotImplementedError('forward-only path: is_training=True is out of scope')
+    """net/xception_body.py:402-448.  object_score [N,n], bboxes_pred [N,n,4] -> proposals [N,post_n,4].
+    is_training=True (:446-448): the same proposal stage, then encode_fn(proposals) with the proposals handed over on the
+    device (a DeviceTensor [N,post_n,1,4]) -> its (rois, targets, labels, scores), e.g. of
+    targets.AnchorEncoder.ext_encode_rois."""
+    if is_training and encode_fn is None:
+        raise InvalidArgumentError(-1, 'get_proposals: is_training=True needs an encode_fn')
     s = np.ascontiguousarray(object_score, np.float32)
     b = np.ascontiguousarray(bboxes_pred, np.float32)
     N, n = s.shape
@@ -363,6 +365,9 @@ def get_proposals(object_score, bboxes_pred, encode_fn=None, rpn_pre_nms_top_n=5
     d_c = DeviceBuffer(N * 16)
     check(lib().xdet_get_proposals(d_s.ptr, d_b.ptr, N, n, rpn_pre_nms_top_n, rpn_post_nms_top_n, nms_threshold,
                                    rpn_min_size, ws.ptr, d_r.ptr, d_c.ptr, stream.handle if stream else None))
+    if is_training:
+        synchronize(stream)
+        return encode_fn(DeviceTensor(d_r.ptr, (N, rpn_post_nms_top_n, 1, 4), 4, owner=d_r))
     rois = to_host(d_r.ptr, (N, rpn_post_nms_top_n, 4), np.float32, stream)
     if return_counts:
         return rois, to_host(d_c.ptr, (N, 4), np.int32, stream)
