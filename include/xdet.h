@@ -365,6 +365,58 @@ int xdet_encode_rois(const float* rois, int R, const int32_t* glabels, const flo
                      float* out_rois, float* out_targets, int32_t* out_labels, float* out_scores, int32_t* out_index,
                      int32_t* counts, int32_t* all_labels, float* all_targets, float* all_scores, void* stream);
 
+/* ---- training losses: everything of lighr_head_model_fn between the logits and the scalar loss
+ * (light_head_rfcn_train.py:257-275, 312-413; net/xception_body.py:502-533, 560), with the gradients with respect to the
+ * logits (csrc/losses.hip; the NumPy statement of the same contract is xdet/losses.py) ----------------------------------
+ * All arithmetic in f32, every operation rounded on its own, in the reference's order.
+ *   modified_smooth_l1(d = pred - target; sigma): sigma2 = sigma * sigma; |d| < 1 / sigma2 ? (d * d) * (0.5 * sigma2)
+ *     : |d| - 0.5 / sigma2;  derivative d * sigma2, else sign(d).  Over a box: ((s(d0) + s(d1)) + s(d2)) + s(d3).
+ *   cross entropy of a row x with class y: m = max x, s = sum_j exp(x_j - m) in index order, ce = log(s) - (x_y - m);
+ *     derivative exp(x_j - m) / s - [j == y].
+ * xdet_rpn_loss (:312-380).  rpn_out, ld, cls_off, box_off, Hh, Ww, A and the anchor index (y * Ww + x) * A + k as
+ *   xdet_rpn_decode takes them (the detector's "rpn_out" buffer goes in as it is); labels i32 [N * n_a] and targets f32
+ *   [N * n_a, 4] as xdet_encode_anchors writes them, n_a = Hh * Ww * A.  S = N * anchors_per_image rows are selected from
+ *   the batch flattened, by the sampler of xdet_encode_rois above run once over all N * n_a anchors: rois_per_image = S,
+ *   fg_fraction = fg_ratio, pos = {label > 0}, neg = {label == 0} (no score condition), element = flat anchor index,
+ *   image = 0 -- in NumPy, targets.sample_rois(labels_flat, ones, S, fg_ratio, 0., seed, image=0).
+ *   -> sel_index i32 [S] (-1 everywhere when n_keep == 0), counts i32 [4]: |pos|, |neg|, n_keep, the number of selected
+ *   rows (with multiplicity) whose label > 0 (n_sel_pos), losses f32 [3]:
+ *     ce = (sum over the S selected rows of ce(cls row, label > 0)) / S
+ *     loc = ((sum over the selected rows with label > 0 of smooth_l1(box row - target)) / n_sel_pos) / fg_ratio
+ *     total = ce + loc.
+ *   Where the reference yields NaN or fails: n_sel_pos == 0 -> loc = 0; n_keep == 0 -> all three 0, all gradients 0.
+ *   grad_rpn_out (may be NULL): d total / d rpn_out in rpn_out's own layout, same ld: EVERY cls / box channel of every anchor
+ *   is written (zeros where not selected; channels outside the two ranges are not touched).  A row selected m times
+ *   (m = left / n_keep + 1, plus one inside the tail; 1 when n_keep == S) gets (d ce) * (f32(m) / f32(S)) on its two cls
+ *   channels and, with label > 0, (d smooth_l1) * ((f32(m) / f32(n_sel_pos)) / fg_ratio) on its four box channels.
+ * xdet_head_loss (:384-413, xception_body.py:502-533, 560).  cls [N,P,C] at cls_reg + cls_off, reg [N,P,4] at cls_reg +
+ *   reg_off, row stride ld (the detector's "cls_reg" buffer: cls_off 0, reg_off C); labels i32 [N,P], targets f32 [N,P,4]
+ *   as xdet_encode_rois writes them.
+ *     per_roi[n,p] = ce(cls row, label) + [label > 0] * (smooth_l1(reg row - target) / fg_ratio); a row whose label is
+ *     outside [0, C) (the -1 rows of xdet_encode_rois) has 0 and gradient 0.
+ *   ohem_k > 0: K = min(ohem_k, P), select[n,:] = the rows of the K largest per_roi[n,:], descending, equal values in
+ *   ascending row order (tf.nn.top_k); the per-ROI value is computed by one instruction sequence for every row, so rows with
+ *   equal inputs tie bit for bit.  ohem_k == 0 (using_ohem=False): K = P, select[n,:] = 0 .. P-1.
+ *   -> losses f32 [3]: the means over the N * K selected rows of per_roi (head_loss), of its ce term, of its smooth-L1 term
+ *   (the reference's two summaries); per_roi f32 [N,P]; select i32 [N,K].
+ *   grad_cls_reg (may be NULL): d head_loss / d cls_reg in the buffer's layout: the C + 4 channels of all N * P rows are
+ *   written, zero for rows not selected: (d ce) * w and ((d smooth_l1) / fg_ratio) * w, w = 1 / f32(N * K).
+ * Every float sum is a tree of a fixed shape: the same call twice gives the same bits.  Neither call synchronises or reads
+ * anything on the host.  workspace: xdet_losses_workspace_bytes(N, anchors_per_image) bytes (anchors_per_image 0: enough
+ * for xdet_head_loss only; 0 is returned for sizes outside the limits), 16-byte aligned; it needs no initialisation and a
+ * workspace sized for a larger N serves a smaller one.
+ * Limits: N * n_a <= 2^27, S <= 32768 (N = 128 at 256 anchors per image); N <= 1024, P <= 8192, 2 <= C <= 128.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: sizes outside the limits, ld not a multiple of 4 / cls_off odd /
+ *   box_off not a multiple of 4 (RPN), channel ranges outside ld or overlapping, fg_ratio outside (0, 1], sigma not positive
+ *   and finite, ohem_k < 0, a NULL required pointer, rpn_out / targets / workspace / gradient not 16-byte aligned (RPN). */
+size_t xdet_losses_workspace_bytes(int N, int anchors_per_image);
+int xdet_rpn_loss(const float* rpn_out, int ld, int cls_off, int box_off, int N, int Hh, int Ww, int A, const int32_t* labels,
+                  const float* targets, int anchors_per_image, float fg_ratio, uint32_t seed, float sigma, void* workspace,
+                  int32_t* sel_index, int32_t* counts, float* losses, float* grad_rpn_out, void* stream);
+int xdet_head_loss(const float* cls_reg, int ld, int cls_off, int reg_off, int N, int P, int C, const int32_t* labels,
+                   const float* targets, float fg_ratio, int ohem_k, float sigma, void* workspace, float* losses, float* per_roi,
+                   int32_t* select, float* grad_cls_reg, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

@@ -14,6 +14,7 @@
 //   tg_sample_kernel    ROIs only, one workgroup per image: foreground / background lists, the shuffle as a sort by
 //                       (hash key, element), the up-sampling tail, the gather
 #include "common.h"
+#include "shuffle.h"
 
 #include <algorithm>
 #include <climits>
@@ -250,15 +251,7 @@ __global__ __launch_bounds__(TG_T) void tg_assign_kernel(TgCand c, int G, TgWork
 // ---- the sampler -------------------------------------------------------------------------------------------------
 
 // shuffle(S) = S ordered by (key, element): key = mix(mix(mix(seed ^ 0x9E3779B9) + image) ^ (2 * element + stream)), mix the
-// 32-bit finaliser below -- integers only, the same on the host (xdet/targets.py shuffle_keys)
-__host__ __device__ __forceinline__ unsigned tg_mix(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
+// 32-bit finaliser of shuffle.h -- integers only, the same on the host (xdet/targets.py shuffle_keys)
 __device__ __forceinline__ unsigned long long tg_key(unsigned image_word, unsigned element, unsigned stream) {
   return ((unsigned long long)tg_mix(image_word ^ (2u * element + stream)) << 32) | element;
 }

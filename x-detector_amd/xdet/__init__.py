@@ -17,17 +17,21 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                                                              (light_head_rfcn_eval.py:288-338)
   AnchorEncoder (encode_all_anchors, ext_encode_rois), encode_anchors, encode_rois, host_encode_anchors, host_encode_rois
   (xdet.targets)          <- preprocessing/anchor_manipulator.py:96-445: the training targets, on the GPU and in NumPy
+  rpn_loss, head_loss, HeadLoss, host_rpn_loss, host_head_loss, modified_smooth_l1
+  (xdet.losses)           <- light_head_rfcn_train.py:257-275, 312-413; net/xception_body.py:502-533, 560: the training
+                             losses (RPN sampling, OHEM) and their gradients with respect to the logits
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """
 from ._lib import XdetError, InvalidArgumentError, LightHeadConfig, lib      # noqa: F401
 from . import weights                                                         # noqa: F401
 from . import targets                                                         # noqa: F401
+from . import losses                                                          # noqa: F401
 
 
 def __getattr__(name):
     import importlib
-    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets'):
+    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets', 'losses'):
         m = importlib.import_module('.' + mod, __name__)
         if hasattr(m, name):
             return getattr(m, name)

@@ -27,6 +27,7 @@ SOURCES = [
     ('detect.hip', ['-ffp-contract=off']),
     ('evalmatch.hip', ['-ffp-contract=off']),
     ('targets.hip', ['-ffp-contract=off']),
+    ('losses.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('plan.hip', []),
     ('lighthead.hip', []),

@@ -370,7 +370,8 @@ def _same(t, view):
 
 def XceptionBody(input_image, num_classes, is_training=False, data_format='channels_last'):
     """net/xception_body.py:236-379 -> (mid_outputs, outputs) as DeviceTensors (NHWC).  Forward only: of the training
-    graph this package has the target assignment (get_proposals with is_training=True), not the batch-norm updates."""
+    graph this package has the target assignment (get_proposals with is_training=True) and the losses (xdet.losses,
+    get_head with is_training=True), not the batch-norm updates."""
     assert not is_training, 'forward-only path'
     d = _det()
     a = np.asarray(input_image, np.float32)
@@ -421,7 +422,7 @@ def get_proposals(object_score, bboxes_pred, encode_fn, rpn_pre_nms_top_n, rpn_p
                   rpn_min_size, is_training, data_format):
     """net/xception_body.py:402-448 -> proposals [N,post_n,4] numpy.  is_training=True (:446-448): the same proposal
     stage, then encode_fn(proposals) with the net's `proposals` buffer handed over on the device -> its (rois, targets,
-    labels, scores) (targets.AnchorEncoder.ext_encode_rois).  Nothing else of the training graph exists here."""
+    labels, scores) (targets.AnchorEncoder.ext_encode_rois)."""
     if is_training and encode_fn is None:
         raise InvalidArgumentError(-1, 'get_proposals: is_training=True needs an encode_fn')
     d = _det()
@@ -444,20 +445,37 @@ def get_proposals(object_score, bboxes_pred, encode_fn, rpn_pre_nms_top_n, rpn_p
 
 def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposals_bboxes, num_classes, is_training,
              using_ohem, ohem_roi_one_image, data_format, var_scope):
-    """net/xception_body.py:477-560 (eval, no OHEM) -> (cls_score [N,R,nc], bboxes_reg [N,R,4]) numpy.
-    `pooling_op` is accepted for signature parity; the fused HIP PsRoiAlign is always used.  Forward only: the head's
-    losses and OHEM are not part of this package."""
-    assert not is_training and not using_ohem, 'forward-only path'
+    """net/xception_body.py:477-560.  is_training=False -> (cls_score [N,R,nc], bboxes_reg [N,R,4]) numpy.
+    is_training=True (:502-533, 560): `proposals_bboxes` are the sampled ROIs of get_proposals' training branch and `loss_func`
+    a losses.HeadLoss carrying their labels, targets and fg_ratio; PsRoiAlign and the head run on them, then xdet_head_loss
+    on the net's `cls_reg` buffer in place (OHEM keeps the ohem_roi_one_image hardest ROIs per image; the reference's second
+    run of the dense layers on the gathered rows has the same weights, so the selected rows' logits are the gathered ones)
+    -> the scalar head loss; losses, per-ROI values, the selection and d loss / d cls_reg are in loss_func.result.  The head's
+    row count is fixed when the detector is built: proposals_bboxes.shape[1] must equal its rpn_post_nms_top_n (a head detector
+    built with rpn_post_nms_top_n = the ROIs sampled per image).  `pooling_op` is accepted for signature parity; the fused HIP
+    PsRoiAlign is always used.  The backward of the dense layers is not part of this package."""
     d = _det()
     if (grid_width, grid_height) != (d.cfg.grid, d.cfg.grid) or num_classes != d.cfg.num_classes:
         raise InvalidArgumentError(-1, 'get_head: grid %dx%d / %d classes but the detector was built with %dx%d / %d'
                                    % (grid_width, grid_height, num_classes, d.cfg.grid, d.cfg.grid, d.cfg.num_classes))
     n = proposals_bboxes.shape[0]
+    if is_training:
+        from .losses import HeadLoss
+        if not isinstance(loss_func, HeadLoss):
+            raise InvalidArgumentError(-1, 'get_head: is_training=True needs a losses.HeadLoss as loss_func')
+        if proposals_bboxes.shape[1] != d.R:
+            raise InvalidArgumentError(-1, 'get_head: %d ROIs per image but the detector was built with rpn_post_nms_top_n = %d'
+                                       % (proposals_bboxes.shape[1], d.R))
+    elif using_ohem:
+        raise InvalidArgumentError(-1, 'get_head: OHEM belongs to the training branch (is_training=True)')
     view = d.buffer('feat', n)
     if not _same(net_input, view):
         d.write('feat', net_input.numpy() if isinstance(net_input, DeviceTensor) else net_input)
     d.write('proposals', np.asarray(proposals_bboxes, np.float32))
     check(lib().xdet_net_get_head(d.handle, n, d.stream.handle))
     _sync(d)
+    if is_training:
+        res = loss_func(d.buffer('cls_reg', n), None, int(ohem_roi_one_image) if using_ohem else 0, num_classes)
+        return float(res.losses[0])
     cr = d.buffer('cls_reg', n).numpy().reshape(n, d.R, -1)
     return cr[..., :num_classes], cr[..., num_classes:num_classes + 4]
