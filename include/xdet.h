@@ -247,6 +247,40 @@ enum { XDET_RESIZE_NONE = 1, XDET_RESIZE_CENTRAL_CROP = 2, XDET_RESIZE_PAD_AND_R
 int xdet_preprocess_eval_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
                                const int32_t* image_shapes, int N, int out_size, int resize, float* out_nchw,
                                float* bbox_img, void* stream);
+/* Training ingest: light_head_preprocess_for_train (preprocessing/common_preprocessing.py:328-381) for N decoded images
+ * of any sizes and their ground truth, in one call: random colour distortion (distort_color, fast_mode=False, :212-262),
+ * SSD expand and patch sampling (tf_image.py:602-630, 547-571, 393-545), random horizontal flip (tf_image.py:322-346),
+ * TF-legacy bilinear warp to S x S (as above), * 2 - [R,G,B mean]/127.5, CHW.  packed / offsets / image_shapes as in
+ * xdet_preprocess_eval_batch; glabels i32 [N,G], gbboxes f32 [N,G,4] (ymin, xmin, ymax, xmax in [0,1]), n_gt i32 [N]
+ * (clamped to [0,G]); image_ids i32 [N] or NULL (then 0 .. N-1).  All of them device memory, read by the kernels.
+ * -> out_nchw f32 [N,3,S,S]; out_glabels / out_gbboxes / out_n_gt in the same layout, boxes in the frame of the network
+ * input, in input order, zeros behind out_n_gt -- what xdet_encode_anchors reads.  The statement the kernels are equal to,
+ * bit for bit, is xdet/augment.py host_preprocess_train; its module docstring gives every step.  In short:
+ *   draws     draw(seed, image_id, k) = mix(word ^ (0x80000000 | k)), word = mix(mix(seed ^ 0x9E3779B9) + image_id), mix the
+ *             32-bit finaliser of the shuffle keys below; bit 31 is the stream no shuffle uses.  k counts the draws of one
+ *             image in the reference's program order.  float in [lo,hi): lo + ((u >> 8) * 2^-24) * (hi - lo); int in
+ *             [lo,hi): lo + u % (hi - lo), lo for an empty range (TF raises); the 7-way multinomial: u % 7.
+ *   contrast  the mean is taken over the whole source image after the ops in front of contrast in the drawn ordering and
+ *             is DEFINED as f32(sum over pixels of int64(rint(v * 65536)) / (H * W * 65536)): an exact integer sum and one
+ *             f64 division, independent of reduction order, grid and batch.
+ *   patches   the reference's loops with their bounds (3 attempts x 50 x 20 x 10 rounds); the `no box kept` term of
+ *             check_roi_overlap, unbounded in the reference, is bounded by the 50 as well.
+ * records (may be NULL): one 128-byte record per image, 32 little-endian words:
+ *   0 valid | 1-2 canvas h, w | 3-4 offset y, x of the image in the canvas | 5-8 crop y, x, h, w | 9 flip | 10 colour
+ *   ordering | 11-14 f32 brightness delta, saturation factor, hue delta, contrast factor | 15-17 f32 contrast means |
+ *   18 attempts used | 19 fallback to the originals | 20 draws consumed | 21 last attempt expanded | 22 last attempt's
+ *   min_iou index | 23 a patch below one pixel was met | 24 mask of min_iou indices drawn | 25 mask of attempts that
+ *   expanded | 26 boxes read | 27 boxes written | 28-31 zero.
+ * An invalid descriptor (H or W <= 0, an image that does not lie inside packed) reads nothing: NaN planes for that image
+ * only, out_n_gt = 0, a zero record.  workspace: xdet_preprocess_train_workspace_bytes(N, G) bytes, 16-byte aligned.
+ * N <= 0, G <= 0, G > 512, out_size <= 0, packed_bytes < 0 or a NULL required pointer: XDET_ERR_INVALID_ARG before any
+ * GPU work. */
+size_t xdet_preprocess_train_workspace_bytes(int N, int G);
+int xdet_preprocess_train_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                                const int32_t* image_shapes, const int32_t* glabels, const float* gbboxes,
+                                const int32_t* n_gt, const int32_t* image_ids /* may be NULL: 0..N-1 */, int N, int G,
+                                int out_size, uint32_t seed, float* out_nchw, int32_t* out_glabels, float* out_gbboxes,
+                                int32_t* out_n_gt, void* records /* may be NULL */, void* workspace, void* stream);
 
 /* ---- A4+A6: RPN glue + AnchorEncoder.decode_all_anchors ----------------------------------
  * (light_head_rfcn_eval.py:389-397; preprocessing/anchor_manipulator.py:641-669,698-757)

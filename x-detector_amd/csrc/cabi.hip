@@ -295,6 +295,18 @@ int xdet_preprocess_eval_batch(const uint8_t* packed, int64_t packed_bytes, cons
   return launch_preprocess_batch(packed, packed_bytes, offsets, image_shapes, N, out_size, resize, out_nchw, bbox_img,
                                  S(stream));
 }
+size_t xdet_preprocess_train_workspace_bytes(int N, int G) {
+  if (N <= 0 || G <= 0) return 0;
+  return preprocess_train_workspace_bytes(N, G);
+}
+int xdet_preprocess_train_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
+                                const int32_t* image_shapes, const int32_t* glabels, const float* gbboxes,
+                                const int32_t* n_gt, const int32_t* image_ids, int N, int G, int out_size, uint32_t seed,
+                                float* out_nchw, int32_t* out_glabels, float* out_gbboxes, int32_t* out_n_gt, void* records,
+                                void* workspace, void* stream) {
+  return launch_preprocess_train(packed, packed_bytes, offsets, image_shapes, glabels, gbboxes, n_gt, image_ids, N, G,
+                                 out_size, seed, out_nchw, out_glabels, out_gbboxes, out_n_gt, records, workspace, S(stream));
+}
 int xdet_nchw_to_nhwc4(const float* in, float* out, int N, int C, int H, int W, void* stream) {
   return launch_nchw_to_nhwc4(in, out, N, C, H, W, 4, S(stream));
 }

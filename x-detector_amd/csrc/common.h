@@ -167,6 +167,13 @@ int launch_preprocess_batch(const unsigned char* packed, int64_t packed_bytes, c
                             const int* image_shapes, int N, int S, int mode, float* out_nchw, float* bbox_img,
                             hipStream_t s);
 
+// ---- training ingest: colour distortion, expand / patch sampling, flip, warp (augment.hip) ----
+size_t preprocess_train_workspace_bytes(int N, int G);
+int launch_preprocess_train(const unsigned char* packed, int64_t packed_bytes, const int64_t* offsets,
+                            const int* image_shapes, const int* glabels, const float* gbboxes, const int* n_gt,
+                            const int* image_ids, int N, int G, int S, unsigned seed, float* out_nchw, int* out_glabels,
+                            float* out_gbboxes, int* out_n_gt, void* records, void* workspace, hipStream_t s);
+
 // ---- PsRoiAlign (psroialign.hip) -------------------------------------------------------
 int launch_psroialign(const float* feat, const float* rois, float* pooled, int32_t* index, int N, int C, int H,
                       int W, int R, int gw, int gh, int use_max, int layout, int ldc, int out_ld,

@@ -20,6 +20,9 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   rpn_loss, head_loss, HeadLoss, host_rpn_loss, host_head_loss, modified_smooth_l1
   (xdet.losses)           <- light_head_rfcn_train.py:257-275, 312-413; net/xception_body.py:502-533, 560: the training
                              losses (RPN sampling, OHEM) and their gradients with respect to the logits
+  augment (preprocess_train, host_preprocess_train, draw)
+  (xdet.augment)          <- preprocessing/common_preprocessing.py:212-262, 328-381; preprocessing/tf_image.py:322-346,
+                             393-630: the training ingest (colour distortion, expand / patch sampling, flip, warp)
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """
@@ -27,6 +30,7 @@ from ._lib import XdetError, InvalidArgumentError, LightHeadConfig, lib      # n
 from . import weights                                                         # noqa: F401
 from . import targets                                                         # noqa: F401
 from . import losses                                                          # noqa: F401
+from . import augment                                                         # noqa: F401
 
 
 def __getattr__(name):

@@ -98,6 +98,9 @@ SIGNATURES = {
     'xdet_maxpool3x3s2_add': (c_int, [PF, PF, PF, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_preprocess_eval': (c_int, [c_void_p, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_preprocess_eval_batch': (c_int, [c_void_p, c_int64, c_void_p, PI, c_int, c_int, c_int, PF, PF, c_void_p]),
+    'xdet_preprocess_train_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'xdet_preprocess_train_batch': (c_int, [c_void_p, c_int64, c_void_p, PI, PI, PF, PI, PI, c_int, c_int, c_int, ctypes.c_uint32,
+                                            PF, PI, PF, PI, c_void_p, c_void_p, c_void_p]),
     'xdet_nchw_to_nhwc4': (c_int, [PF, PF, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_rpn_decode': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, c_int, c_int, PF, PF, PF, PF, c_void_p]),
     'xdet_proposals_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -29,6 +29,7 @@ SOURCES = [
     ('targets.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
+    ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),
     ('lighthead.hip', []),
     ('resnet_trunk.hip', []),

@@ -247,17 +247,35 @@ def _scaling(prior_scaling):
     return (ctypes.c_float * 4)(*s)
 
 
+def _device_ground_truth(labels, bboxes, n_gt):
+    """True when the ground truth is already in device memory (all three DeviceTensors, shapes agreeing)"""
+    from .runtime import DeviceTensor
+    from ._lib import InvalidArgumentError
+    dev = [isinstance(v, DeviceTensor) for v in (labels, bboxes, n_gt)]
+    if not any(dev):
+        return False
+    if not all(dev) or bboxes.shape != (labels.shape[0], labels.shape[3], 1, 4) or n_gt.shape[3] != labels.shape[0]:
+        raise InvalidArgumentError(-1, 'device ground truth: labels [N,1,1,G], bboxes [N,G,1,4] and n_gt [1,1,1,N] expected')
+    return True
+
+
 def _h(stream):
     return stream.handle if stream is not None else None
 
 
 def encode_anchors(anchor, labels, bboxes, n_gt=None, allowed_border=0., high_thr=0.7, low_thr=0.3,
                    prior_scaling=(1., 1., 1., 1.), stream=None):
-    """host_encode_anchors on the GPU (xdet_encode_anchors) -> (labels i32 [N,HWA], targets f32 [N,HWA,4], scores f32 [N,HWA])"""
+    """host_encode_anchors on the GPU (xdet_encode_anchors) -> (labels i32 [N,HWA], targets f32 [N,HWA,4], scores f32 [N,HWA]).
+    labels / bboxes / n_gt may be the DeviceTensors of augment.preprocess_train ([N,1,1,G] i32, [N,G,1,4] f32, [1,1,1,N]
+    i32): they are read where they are, nothing is copied to the host."""
     from ._lib import lib, check
     from .runtime import to_device, to_host, DeviceBuffer, synchronize
-    gl, gb, ng = ground_truth(labels, bboxes, n_gt)
-    N, G = gl.shape
+    on_device = _device_ground_truth(labels, bboxes, n_gt)
+    if on_device:
+        N, G = labels.shape[0], labels.shape[3]
+    else:
+        gl, gb, ng = ground_truth(labels, bboxes, n_gt)
+        N, G = gl.shape
     yref, xref, href, wref = (np.asarray(v, f32) for v in anchor)
     Hh, Ww = yref.shape if yref.ndim == 2 else (yref.size, 1)
     A = int(href.size)
@@ -271,7 +289,7 @@ def encode_anchors(anchor, labels, bboxes, n_gt=None, allowed_border=0., high_th
     n_a = Hh * Ww * A
     yx = to_device(np.stack([yref.reshape(-1), xref.reshape(-1)], 1).astype(f32))
     hw = to_device(np.stack([href.reshape(-1), wref.reshape(-1)], 1).astype(f32))
-    d_gl, d_gb, d_ng = to_device(gl), to_device(gb), to_device(ng)
+    d_gl, d_gb, d_ng = (labels, bboxes, n_gt) if on_device else (to_device(gl), to_device(gb), to_device(ng))
     ws = DeviceBuffer(max(lib().xdet_targets_workspace_bytes(N, 0, G), 16))
     d_l, d_t, d_s = DeviceBuffer(N * n_a * 4), DeviceBuffer(N * n_a * 16), DeviceBuffer(N * n_a * 4)
     check(lib().xdet_encode_anchors(yx.ptr, hw.ptr, Hh, Ww, A, args[0], d_gl.ptr, d_gb.ptr, d_ng.ptr, N, G, thr[0], thr[1], sc4,
@@ -362,10 +380,13 @@ class AnchorEncoder(object):
         """labels / bboxes: one image ([g] / [g,4], as in the reference's input pipeline), a list of per-image arrays, or
         padded [N,G] / [N,G,4] with n_gt -> (labels, targets, scores, anchor_boxes, n_layers), lists per layer; labels int64.
         A single image gives arrays without the batch axis."""
-        single = not isinstance(labels, (list, tuple)) and np.asarray(labels).ndim == 1
-        if single:
-            labels, bboxes = [np.asarray(labels)], [np.asarray(bboxes, f32).reshape(-1, 4)]
-        gl, gb, ng = ground_truth(labels, bboxes, n_gt)
+        if _device_ground_truth(labels, bboxes, n_gt):      # augment.preprocess_train's outputs, as they are
+            single, (gl, gb, ng) = False, (labels, bboxes, n_gt)
+        else:
+            single = not isinstance(labels, (list, tuple)) and np.asarray(labels).ndim == 1
+            if single:
+                labels, bboxes = [np.asarray(labels)], [np.asarray(bboxes, f32).reshape(-1, 4)]
+            gl, gb, ng = ground_truth(labels, bboxes, n_gt)
         out_l, out_t, out_s, out_b = [], [], [], []
         for layer, anchor in enumerate(self._anchors):
             l, t, s = encode_anchors(anchor, gl, gb, ng, self._allowed_borders[layer], self._positive_threshold,
