@@ -210,6 +210,49 @@ int xdet_conv3x3_patch_forward(void* layer, const uint16_t* in_hi, const uint16_
 int xdet_resnet_bneck_forward(void* conv_a, void* conv_b, void* conv_c, const float* pre_scale, const float* pre_shift,
                               const float* x, int N, int H, int W, float* out, const float* next_scale,
                               const float* next_shift, uint16_t* out_hi, uint16_t* out_lo, void* stream);
+/* A (taps,1) [axis 0] or (1,taps) [axis 1] SAME convolution in the DFT domain of the convolved axis (csrc/spectral.hip;
+ * the large-separable convs, net/xception_body.py:450-475): forward DFT of every line of the F x F map -> one real GEMM
+ * [N*F, 2 Cin] x [2 Cin, 2 Cout] per frequency bin (grouped split-precision GEMM) -> inverse DFT with
+ * out = relu?(y * scale + shift).  kernel_host f32 [taps][cin][cout] (taps odd, <= 15); scale_host / shift_host [cout] or NULL;
+ * F must be 16, 30 or 50 and the layer must be created in a split-precision mode (anything else: XDET_ERR_INVALID_ARG, nothing
+ * is launched).  in: NHWC f32 [N][F][F][ld_in], ld_in = round_up(cin, 32); out: NHWC f32 [N][F][F][ld_out], ld_out a multiple
+ * of 4 and >= round_up(cout, 32) (channels [0, round_up(cout, 32)) are written).  workspace: device memory of
+ * xdet_spectral_conv_workspace_bytes(layer, N) bytes, 256-byte aligned, any contents (every row that is read back is written
+ * first).  An image's result does not depend on the batch it arrives in: how the launchers deal bins and output positions to
+ * workgroups changes with N, the arithmetic per element does not.  Inside a net: option "large_sep" = "spectral" | "auto".
+ * Destroy with xdet_layer_destroy. */
+int xdet_spectral_conv_create(void** layer, const float* kernel_host, int taps, int cin, int cout, int axis, int F,
+                              const float* scale_host, const float* shift_host, int relu_out);
+size_t xdet_spectral_conv_workspace_bytes(void* layer, int N);
+int xdet_spectral_conv_forward(void* layer, const float* in, int N, int ld_in, void* workspace, float* out, int ld_out,
+                               void* stream);
+/* block1_conv1 of the Xception entry (net/xception_body.py:243-250): 3x3 / stride 2 / VALID, 3 -> 32 channels, folded BN +
+ * ReLU, from the NCHW input [N][3][S][S] straight to split planes (xdet_split_f32 layout, ld 32) of the
+ * [N][Ho][Ho][32] output, Ho = (S - 3) / 2 + 1.  w27x32 (device): [ky][kx][ci][32]; scale / shift (device): [32].  The planes
+ * hold ceil(N*Ho*Ho / 16) * 16 * 32 halves each; pixels past N*Ho*Ho of the last group are not written. */
+int xdet_stem_conv3x3s2_forward(const float* in_nchw, const float* w27x32, const float* scale, const float* shift,
+                                uint16_t* out_hi, uint16_t* out_lo, int N, int S, void* stream);
+/* conv2d_fixed_padding(7 x 7, 64 filters, stride 2) of the ResNet v2 stem (net/resnet_v2.py:311-320) from the NCHW input
+ * [N][3][S][S] with the input patch staged in LDS (csrc/resnet_stem.hip).  `layer`: xdet_conv_create(7, 7, 3, 64, stride 2,
+ * pad_mode 2, pad 3 / 3) in mode 1 (f16x3); its scale / shift are applied, its relu_out must be 0.  out: NHWC f32
+ * [N][Ho][Ho][64], Ho = (S - 1) / 2 + 1.  Bit-identical to xdet_nchw_to_nhwc4 + xdet_conv_forward on the same layer. */
+int xdet_resnet_stem7x7_forward(void* layer, const float* in_nchw, int N, int S, float* out, void* stream);
+/* initial_max_pool (3 x 3, stride 2, SAME; net/resnet_v2.py:311-330) + the first block's batch_norm_relu (:142-156) in one pass:
+ * in NHWC f32 [N][H][W][ld] (ld % 32 == 0) -> split planes (xdet_split_f32 layout, ld) of relu(pool(in) * scale + shift) * mul
+ * over the [N][(H+1)/2][(W+1)/2] pixels; scale / shift (device): [ld].  out_hi2 / out_lo2 (optional, both or neither): a second
+ * copy scaled by mul2 into the channel blocks of a wider planes tensor [pix/16][c32_2][16][32], c32_2 >= ld / 32 -- the
+ * pointers address this tensor's first channel block in it; its other blocks are not touched. */
+int xdet_maxpool3x3s2_bn_planes(const float* in, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo,
+                                int N, int H, int W, int C, int ld, float mul, uint16_t* out_hi2, uint16_t* out_lo2,
+                                int c32_2, float mul2, void* stream);
+/* The opening 1x1 conv of a ResNet v2 bottleneck with the pre-activation made on the CU (csrc/resnet_preconv.hip;
+ * net/resnet_v2.py:142-166): planes of relu(bn_b(conv1x1(relu(x * pre_scale + pre_shift)))).  `layer`: a 1x1 stride-1 layer
+ * from xdet_conv_create in mode 1 with the folded bn_b and relu_out 1, Cin 256 or 512 -> 128 outputs (stage 2 of ResNet-50;
+ * anything else: XDET_ERR_INVALID_ARG).  x: NHWC f32 [N][H][W][Cin]; pre_scale / pre_shift (device): [Cin]; out planes in the
+ * xdet_split_f32 layout, ld 128.  Bit-identical to xdet_split_f32 of relu(x * pre_scale + pre_shift) + xdet_conv_forward_planes
+ * + xdet_split_f32 of its output. */
+int xdet_resnet_preconv_forward(void* layer, const float* pre_scale, const float* pre_shift, const float* x, int N, int H,
+                                int W, uint16_t* out_hi, uint16_t* out_lo, void* stream);
 /* The entry-flow tail "separable block -> max_pooling2d(3, 2, 'same') -> tf.add(residual)" (net/xception_body.py:268-286)
  * with the pool split between the two kernels: xdet_sepconv_fused_hpool_forward is xdet_sepconv_fused_forward whose
  * epilogue writes the 3-column / stride-2 maximum of every output row (out_hpooled: NHWC f32 [N][H][(W+1)/2][ld_out]),

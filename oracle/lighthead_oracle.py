@@ -48,8 +48,10 @@ def same_pad(n, k, s, d=1):
     return total // 2, total - total // 2, out
 
 
-def conv2d(x, w, stride=1, padding='SAME', dilation=1, bias=None):
-    """x [N,H,W,Cin] f32, w [kh,kw,Cin,Cout] (HWIO). im2col + sgemm."""
+def conv2d(x, w, stride=1, padding='SAME', dilation=1, bias=None, dtype=F32):
+    """x [N,H,W,Cin] f32, w [kh,kw,Cin,Cout] (HWIO). im2col + sgemm (dtype=np.float64: + dgemm, the high-precision
+    reference of the op-level kernel tests)."""
+    F32 = dtype
     x = np.asarray(x, F32)
     N, H, W, Cin = x.shape
     kh, kw, _, Cout = w.shape

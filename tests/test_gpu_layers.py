@@ -334,6 +334,29 @@ def test_specialised_conv_entry_points_reject_what_they_cannot_run():
     assert sep_wide(x64, fused=False).numpy().shape == (1, 9, 9, 384)
 
 
+def test_resnet_preconv_entry_point_rejects_layers_outside_its_class():
+    """xdet_resnet_preconv_forward runs 256 | 512 -> 128 channels (stage 2 of ResNet-50) in f16x3 only"""
+    from xdet import ops
+    from xdet._lib import InvalidArgumentError
+    from xdet.ops import Conv2D
+    from xdet.runtime import DeviceTensor, set_precision
+    rng = np.random.default_rng(1)
+    k = lambda *s: (rng.standard_normal(s) / 8).astype(np.float32)
+    set_precision('f16x3')
+    try:
+        layers = [Conv2D(k(1, 1, 128, 128), relu=True),        # cin outside the class
+                  Conv2D(k(1, 1, 256, 64), relu=True),         # cmid outside the class
+                  Conv2D(k(1, 1, 256, 128)),                   # no ReLU behind the folded BN
+                  Conv2D(k(3, 3, 256, 128), relu=True)]        # not a 1x1
+    finally:
+        set_precision('f32')
+    layers.append(Conv2D(k(1, 1, 256, 128), relu=True))        # created in f32 mode: no split-precision weights
+    for L in layers:
+        x = DeviceTensor.from_numpy(rng.standard_normal((1, 3, 5, L.cin)).astype(np.float32))
+        with pytest.raises(InvalidArgumentError):
+            ops.resnet_preconv(L, np.ones(L.cin, np.float32), np.zeros(L.cin, np.float32), x)
+
+
 def test_fused_block_and_split_pool_random_shapes():
     """60 random (N, H, W, Cin, Cout, ReLU) draws -- single rows / columns, widths around the 28- and 30-column tile
     steps, every output-width class of the fused kernel (one 128-wide pass, 256-wide passes, masked channels): the

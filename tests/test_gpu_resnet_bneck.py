@@ -7,6 +7,8 @@ tail -- and, through tests/test_gpu_resnet.py, within 1e-4 of the oracle."""
 import numpy as np
 import pytest
 
+from planes_util import planes_to_f32 as _planes_to_f32
+
 pytestmark = pytest.mark.gpu
 
 
@@ -72,15 +74,6 @@ def test_projection_folded_into_the_closing_conv(size, batch, n):
     scale = float(np.abs(b).max())
     assert float(np.abs(a - b).max()) <= 2e-5 * scale, (float(np.abs(a - b).max()), scale)
     assert not np.array_equal(a, b)      # (the two forms do differ in the last bits: the switch is live)
-
-
-def _planes_to_f32(hi_buf, lo_buf, n_pix, ld):
-    """[pix/16][ld/32][16][32] f16 hi / lo planes -> f32 [n_pix][ld] of hi + lo"""
-    from xdet.runtime import to_host
-    g = -(-n_pix // 16)
-    hi = to_host(hi_buf.ptr, (g, ld // 32, 16, 32), np.float16).astype(np.float32)
-    lo = to_host(lo_buf.ptr, (g, ld // 32, 16, 32), np.float16).astype(np.float32)
-    return (hi + lo).transpose(0, 2, 1, 3).reshape(g * 16, ld)[:n_pix]
 
 
 @pytest.mark.parametrize('N,H,W', [(2, 8, 30), (1, 12, 60), (3, 10, 37), (1, 5, 7), (2, 120, 120)])

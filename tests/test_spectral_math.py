@@ -2,8 +2,8 @@
 convolution: a (15,1) SAME convolution == per-bin complex products in the L = F+14 point DFT domain of
 the convolved axis, with the two real bins (DC, Nyquist) packed into bin 0 and every bin evaluated as ONE
 real GEMM [Xr Xi] x [[Gr, Gi], [-Gi, Gr]].  Same tables, same packing, same block matrices as the C++ host
-code (spectral_tables / spectral_weights); the HIP kernels themselves are checked on the GPU
-(tests/test_gpu_e2e.py, '+spectral' cases)."""
+code (spectral_tables / spectral_weights); the HIP kernels themselves are checked on the GPU, on their own
+(tests/test_gpu_spectral.py) and inside the net (tests/test_gpu_e2e.py, '+spectral' cases)."""
 import numpy as np
 import pytest
 

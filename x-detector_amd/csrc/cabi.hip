@@ -255,6 +255,79 @@ int xdet_resnet_bneck_forward(void* conv_a, void* conv_b, void* conv_c, const fl
   DeviceGuard guard(A->device);
   return launch_resnet_bneck(a, N, S(stream));
 }
+int xdet_spectral_conv_create(void** layer, const float* kernel_host, int taps, int cin, int cout, int axis, int F,
+                              const float* scale_host, const float* shift_host, int relu_out) {
+  XDET_REQUIRE(layer, "layer is NULL");
+  std::unique_ptr<SpectralConv> L(new SpectralConv());
+  XDET_TRY(L->init(kernel_host, taps, cin, cout, axis, F, scale_host, shift_host, relu_out));
+  *layer = static_cast<LayerBase*>(L.release());
+  return XDET_OK;
+}
+// workspace of a batch of N: [x_hi | x_lo | y], each with 512 bytes of slack, each starting 256-byte aligned
+static size_t spectral_part(size_t bytes) { return (bytes + 512 + 255) / 256 * 256; }
+size_t xdet_spectral_conv_workspace_bytes(void* layer, int N) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  if (!b || b->kind != 3 || N <= 0) return 0;
+  const SpectralConv* L = static_cast<SpectralConv*>(b);
+  return 2 * spectral_part(L->planes_halves(N) * 2) + spectral_part(L->y_floats(N) * 4);
+}
+int xdet_spectral_conv_forward(void* layer, const float* in, int N, int ld_in, void* workspace, float* out, int ld_out,
+                               void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 3, "not a spectral conv layer");
+  SpectralConv* L = static_cast<SpectralConv*>(b);
+  XDET_REQUIRE(in && workspace && out && N > 0 && (int64_t)N * L->F <= (1 << 24), "spectral conv: NULL argument / bad batch");
+  XDET_REQUIRE(ld_in == L->cin_ld && ld_out >= L->cout_ld && ld_out % 4 == 0 && (uintptr_t)workspace % 256 == 0,
+               "spectral conv: ld_in must be round_up(cin,32), ld_out a multiple of 4 and >= round_up(cout,32), the workspace 256-byte aligned");
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  const size_t pl = spectral_part(L->planes_halves(N) * 2);
+  DeviceGuard guard(L->device);
+  return L->forward(in, N, reinterpret_cast<unsigned short*>(ws), reinterpret_cast<unsigned short*>(ws + pl),
+                    reinterpret_cast<float*>(ws + 2 * pl), out, ld_out, S(stream));
+}
+int xdet_stem_conv3x3s2_forward(const float* in_nchw, const float* w27x32, const float* scale, const float* shift,
+                                uint16_t* out_hi, uint16_t* out_lo, int N, int S_, void* stream) {
+  XDET_REQUIRE(in_nchw && w27x32 && scale && shift && out_hi && out_lo, "stem_conv3x3s2: NULL argument");
+  XDET_REQUIRE(N > 0 && S_ >= 3 && (int64_t)N * S_ * S_ < ((int64_t)1 << 31), "stem_conv3x3s2: bad batch / image side");
+  return launch_stem_conv3x3s2(in_nchw, w27x32, scale, shift, out_hi, out_lo, N, S_, S(stream));
+}
+int xdet_resnet_stem7x7_forward(void* layer, const float* in_nchw, int N, int S_, float* out, void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 1, "not a conv layer");
+  ConvLayer* L = static_cast<ConvLayer*>(b);
+  XDET_REQUIRE(L->precision == PREC_F16X3 && L->groups == 1 && L->d_wt_hi && L->d_wt_lo && L->relu_out == 0 && L->pad_t == L->pad_l &&
+                   L->kp == 224 && resnet_stem7x7_supported(L->kh, L->kw, L->cin, L->cout, L->stride, L->pad_mode, L->pad_t, S_),
+               "resnet_stem7x7: needs a 7x7 / stride 2 / explicit pad 3 conv 3 -> 64 without ReLU, created in mode 1 (f16x3), S >= 16");
+  XDET_REQUIRE(in_nchw && out && N > 0 && (int64_t)N * S_ * S_ * 16 < ((int64_t)1 << 31), "resnet_stem7x7: NULL argument / bad batch");
+  DeviceGuard guard(L->device);
+  return launch_resnet_stem7x7(in_nchw, L->d_wt_hi, L->d_wt_lo, L->d_scale, L->d_shift, out, N, S_, S(stream));
+}
+int xdet_maxpool3x3s2_bn_planes(const float* in, const float* scale, const float* shift, uint16_t* out_hi, uint16_t* out_lo,
+                                int N, int H, int W, int C, int ld, float mul, uint16_t* out_hi2, uint16_t* out_lo2,
+                                int c32_2, float mul2, void* stream) {
+  XDET_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && ld > 0, "maxpool + bn planes: bad shape");
+  XDET_REQUIRE((out_hi2 == nullptr) == (out_lo2 == nullptr), "maxpool + bn planes: the second destination needs both planes");
+  int Ho, Wo, pt, pl;
+  same_pad(H, 3, 2, 1, &pt, &Ho);
+  same_pad(W, 3, 2, 1, &pl, &Wo);
+  return launch_maxpool3x3s2_bn_planes(in, scale, shift, out_hi, out_lo, N, H, W, C, ld, Ho, Wo, pt, pl, mul, S(stream), out_hi2,
+                                       out_lo2, c32_2, mul2);
+}
+int xdet_resnet_preconv_forward(void* layer, const float* pre_scale, const float* pre_shift, const float* x, int N, int H,
+                                int W, uint16_t* out_hi, uint16_t* out_lo, void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 1, "not a conv layer");
+  ConvLayer* L = static_cast<ConvLayer*>(b);
+  XDET_REQUIRE(L->precision == PREC_F16X3 && L->dma_capable() && L->groups == 1 && L->kh == 1 && L->kw == 1 && L->stride == 1 &&
+                   L->relu_out == 1 && L->cout_pad == L->cout && L->cin_p == L->cin && L->ksplit <= 1,
+               "resnet_preconv: needs a 1x1 stride-1 conv with ReLU created in mode 1 (f16x3)");
+  XDET_REQUIRE(N > 0 && H > 0 && W > 0 && resnet_preconv_supported(L->cin, L->cout, (int64_t)N * H * W),
+               "resnet_preconv: unsupported channel counts (256 | 512 -> 128) / tensor size");
+  XDET_REQUIRE(pre_scale && pre_shift && x && out_hi && out_lo, "resnet_preconv: NULL argument");
+  DeviceGuard guard(L->device);
+  return launch_resnet_preconv(x, pre_scale, pre_shift, L->d_wt_hi_b, L->d_wt_lo_b, L->d_scale, L->d_shift, out_hi, out_lo,
+                               (int64_t)N * H * W, L->cin, L->cout, S(stream));
+}
 int xdet_sepconv_fused_hpool_forward(void* dw_layer, void* pw_layer, const float* in, int N, int H, int W, int ld_in,
                                      float* out_hpooled, int ld_out, int relu_in, void* stream) {
   LayerBase* a = static_cast<LayerBase*>(dw_layer);

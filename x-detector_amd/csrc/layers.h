@@ -88,7 +88,7 @@ static inline void same_pad(int n, int k, int s, int d, int* before, int* out) {
 
 struct LayerBase {
   virtual ~LayerBase() {}
-  int kind = 0;   // 1 conv, 2 depthwise
+  int kind = 0;   // 1 conv, 2 depthwise, 3 spectral conv
   int device = 0; // the HIP device the weights live on (current device at creation)
 };
 
@@ -380,6 +380,77 @@ struct ConvLayer : LayerBase {
   }
   // can this layer consume pre-split f16 planes (conv_mfma_dma.hip)?
   bool dma_capable() const { return precision != PREC_F32 && !small_cin; }
+};
+
+// One T-tap SAME convolution along one image axis in the DFT domain of that axis (spectral.hip): forward DFT of every
+// line -> one real GEMM per frequency bin (a grouped ConvLayer) -> inverse DFT with out = relu?(y * scale + shift).
+// The layer owns its tables, block matrices and epilogue arrays; the DFT-domain tensors live in a workspace of the
+// caller: split planes x_hi / x_lo of planes_halves(N) halves each and the f32 products y of y_floats(N) floats
+// (+ 512 bytes of slack each).  The three passes are separate members so that a plan can time them as three ops.
+struct SpectralConv : LayerBase {
+  int F = 0, NB = 0, axis = 0, cin = 0, cin_ld = 0, cout = 0, cout_ld = 0, relu = 0;
+  ConvLayer G;                           // [NB] groups of [2 cin_ld x 2 cout_ld] real block matrices
+  Pow2Scaled tab_fwd;                    // the forward table carries the operand planes' activation pre-scale 2^-e
+  float *d_tf = nullptr, *d_ti = nullptr, *d_scale = nullptr, *d_shift = nullptr;
+  ~SpectralConv() override {
+    if (d_tf) (void)hipFree(d_tf);
+    if (d_ti) (void)hipFree(d_ti);
+    if (d_scale) (void)hipFree(d_scale);
+    if (d_shift) (void)hipFree(d_shift);
+  }
+  // rows per bin at a batch of N: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
+  static int m_pad(int F, int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); }
+  int m_pad(int N) const { return m_pad(F, N); }
+  size_t planes_halves(int N) const { return (size_t)NB * m_pad(N) * 2 * cin_ld; }
+  size_t y_floats(int N) const { return (size_t)NB * m_pad(N) * 2 * cout_ld; }
+  // w: [T][cin][cout] (the taps along `axis`: 0 = y, 1 = x); scale / shift: [cout] or NULL (ones / zeros)
+  int init(const float* w, int T, int cin_, int cout_, int axis_, int F_, const float* scale, const float* shift, int relu_) {
+    XDET_REQUIRE(w && T > 0 && T % 2 == 1 && T <= 15 && cin_ > 0 && cout_ > 0 && (axis_ == 0 || axis_ == 1),
+                 "spectral conv: an odd number of taps (<= 15) along axis 0 | 1");
+    XDET_REQUIRE(spectral_supported(F_), "spectral conv: the feature-map side must be 16, 30 or 50");
+    XDET_REQUIRE(g_default_precision != PREC_F32, "spectral conv: needs a split-precision mode");
+    kind = 3;
+    F = F_; NB = spectral_points(F) / 2; axis = axis_; relu = relu_;
+    cin = cin_; cin_ld = round_up(cin, 32); cout = cout_; cout_ld = round_up(cout, 32);
+    {
+      std::vector<float> wb;
+      spectral_weights(w, T, cin, cout, cin_ld, cout_ld, F, &wb);
+      XDET_TRY(G.init(1, 1, 2 * cin_ld, 2 * cout_ld, 1, 1, 0, 0, 0, wb.data(), nullptr, nullptr, 0, NB));
+    }
+    device = G.device;
+    std::vector<float> ti, sc(cout_ld, 0.f), sh(cout_ld, 0.f);
+    spectral_tables(F, &tab_fwd.host, &ti);
+    for (int c = 0; c < cout; ++c) { sc[c] = scale ? scale[c] : 1.f; sh[c] = shift ? shift[c] : 0.f; }
+    XDET_TRY(upload(tab_fwd.host, &d_tf));
+    XDET_TRY(upload(ti, &d_ti));
+    XDET_TRY(upload(sc, &d_scale));
+    XDET_TRY(upload(sh, &d_shift));
+    tab_fwd.dev = d_tf;
+    return XDET_OK;
+  }
+  // the forward transform is linear: 2^-e rides in its table and 2^e in the per-bin GEMM's epilogue scale
+  int set_in_exp(int e) {
+    XDET_TRY(tab_fwd.upload(-e));
+    return G.set_in_exp(e);
+  }
+  int dft_fwd(const float* in, int N, unsigned short* x_hi, unsigned short* x_lo, hipStream_t s) const {
+    return launch_dft_fwd(in, F, cin_ld, axis, N, m_pad(N), d_tf, x_hi, x_lo, s);
+  }
+  int gemm(int N, const unsigned short* x_hi, const unsigned short* x_lo, float* y, hipStream_t s) const {
+    ConvIO io;                   // NB groups of m_pad(N) rows, N * F of them live
+    io.in_hi = x_hi; io.in_lo = x_lo; io.zeros = G.d_zeros; io.out = y;
+    io.group_rows = m_pad(N); io.group_live_rows = N * F;
+    return G.forward(io, 1, 1, NB * m_pad(N), 2 * cin_ld, 2 * cout_ld, s);
+  }
+  int dft_inv(int N, const float* y, float* out, int ldo, hipStream_t s) const {
+    return launch_dft_inv(y, F, 2 * cout_ld, cout_ld, N, m_pad(N), d_ti, d_scale, d_shift, relu, out, ldo, axis, s);
+  }
+  int forward(const float* in, int N, unsigned short* x_hi, unsigned short* x_lo, float* y, float* out, int ldo,
+              hipStream_t s) const {
+    XDET_TRY(dft_fwd(in, N, x_hi, x_lo, s));
+    XDET_TRY(gemm(N, x_hi, x_lo, y, s));
+    return dft_inv(N, y, out, ldo, s);
+  }
 };
 
 struct DepthwiseLayer : LayerBase {

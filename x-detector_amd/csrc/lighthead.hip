@@ -218,34 +218,21 @@ int LightHeadNet::build_large_sep() {
 // real GEMM [N*F, 2*Cin] x [2*Cin, 2*Cout] on the split-precision MFMA kernel (grouped launch), a forward
 // DFT pass in front and an inverse pass (+bias / +BN+ReLU) behind each of the two convolutions
 int LightHeadNet::build_large_sep_spectral() {
-  const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid, F = out.H, NB = spectral_points(F) / 2;
-  const int cin = out.C, cin_ld = out.ld, mid2 = 2 * mid, co_ld = round_up(co, 32);
+  const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid, F = out.H;
+  const int cin = out.C, mid2 = 2 * mid;
   // the same branch fusion as the direct form: (15,1) with 2*mid outputs, (1,15) over the stacked channels
-  std::vector<float> ka, kb, ba, sc, sh, ones(std::max(mid2, co_ld), 1.f);
+  std::vector<float> ka, kb, ba, sc, sh;
   XDET_TRY(large_sep_weights(cin, mid, co, &ka, &ba, &kb, &sc, &sh));
-  sc.resize(co_ld, 0.f);
-  sh.resize(co_ld, 0.f);
-  ConvLayer* LA = keep(new ConvLayer());
-  ConvLayer* LB = keep(new ConvLayer());
-  {
-    std::vector<float> wa;
-    spectral_weights(ka.data(), 15, cin, mid2, cin_ld, mid2, F, &wa);
-    XDET_TRY(LA->init(1, 1, 2 * cin_ld, 2 * mid2, 1, 1, 0, 0, 0, wa.data(), nullptr, nullptr, 0, NB));
-  }
-  {
-    std::vector<float> wb;
-    spectral_weights(kb.data(), 15, mid2, co, mid2, co_ld, F, &wb);
-    XDET_TRY(LB->init(1, 1, 2 * mid2, 2 * co_ld, 1, 1, 0, 0, 0, wb.data(), nullptr, nullptr, 0, NB));
-  }
-  std::vector<float> tf, ti;
-  spectral_tables(F, &tf, &ti);
-  float *d_tf, *d_tf_b, *d_ti, *d_ones, *d_ba, *d_sc, *d_sh;
-  XDET_TRY(upload(tf, &d_tf)); XDET_TRY(upload(tf, &d_tf_b)); XDET_TRY(upload(ti, &d_ti)); XDET_TRY(upload(ones, &d_ones));
-  XDET_TRY(upload(ba, &d_ba)); XDET_TRY(upload(sc, &d_sc)); XDET_TRY(upload(sh, &d_sh));
+  // (15,1) + bias along y, then (1,15) + BN + ReLU along x: the layer the C ABI exposes as xdet_spectral_conv_*
+  SpectralConv* SA = keep(new SpectralConv());
+  SpectralConv* SB = keep(new SpectralConv());
+  XDET_TRY(SA->init(ka.data(), 15, cin, mid2, 0, F, nullptr, ba.data(), 0));
+  XDET_TRY(SB->init(kb.data(), 15, mid2, co, 1, F, sc.data(), sh.data(), 1));
+  XDET_REQUIRE(SA->cin_ld == out.ld && SA->cout_ld == mid2, "plan: the spectral convs' channel strides");
+  const int NB = SA->NB, cin_ld = SA->cin_ld, co_ld = SB->cout_ld;
   // workspace, sized for max_batch: rows of every bin are padded to a whole number of 256-row GEMM tiles
   const size_t mp_max = (size_t)round_up(max_batch * F, 256), rows = (size_t)NB * mp_max;
-  // rows per bin at a batch of N: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
-  auto mpad = [F](int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); };
+  auto mpad = [F](int N) { return SpectralConv::m_pad(F, N); };
   unsigned short *xa_hi, *xa_lo, *xb_hi, *xb_lo;
   float *y1, *tmid, *y2;
   XDET_TRY(alloc_bytes(rows * 2 * cin_ld * 2 + 512, reinterpret_cast<void**>(&xa_hi)));
@@ -272,25 +259,17 @@ int LightHeadNet::build_large_sep_spectral() {
   });
   const std::string pre = "large_sep_feature/Branch_0+1/";
   {
-    // activation pre-scale of the DFT-domain operands: the forward transform is linear, so 2^-e rides in its table
-    // (one copy per transform) and 2^e in the per-bin GEMM's epilogue scale.  These are the tensors with the least
+    // activation pre-scale of the DFT-domain operands (SpectralConv::set_in_exp).  These are the tensors with the least
     // headroom: a bin sums up to F samples, and the second one transforms an un-normalised 15-tap conv output.
-    const Pow2Scaled tab_a{tf, d_tf}, tab_b{tf, d_tf_b};
     PlaneScale pa, pb;
     pa.name = pre + "conv2d/dft_y (DFT-domain planes)";
     pa.hi = xa_hi;
-    pa.halves = [=](int N) { return (int64_t)NB * mpad(N) * 2 * cin_ld; };
-    pa.apply.push_back([=](int e) {
-      XDET_TRY(tab_a.upload(-e));
-      return LA->set_in_exp(e);
-    });
+    pa.halves = [=](int N) { return (int64_t)SA->planes_halves(N); };
+    pa.apply.push_back([=](int e) { return SA->set_in_exp(e); });
     pb.name = pre + "conv2d_1/dft_x (DFT-domain planes)";
     pb.hi = xb_hi;
-    pb.halves = [=](int N) { return (int64_t)NB * mpad(N) * 2 * mid2; };
-    pb.apply.push_back([=](int e) {
-      XDET_TRY(tab_b.upload(-e));
-      return LB->set_in_exp(e);
-    });
+    pb.halves = [=](int N) { return (int64_t)SB->planes_halves(N); };
+    pb.apply.push_back([=](int e) { return SB->set_in_exp(e); });
     // rows [N*F, m_pad) of a bin are padding that only an earlier, larger batch ever wrote: a measurement over
     // whole bins must not see that batch's (possibly overflowed) values
     const size_t bytes_a = rows * 2 * cin_ld * 2, bytes_b = rows * 2 * mid2 * 2;
@@ -301,32 +280,14 @@ int LightHeadNet::build_large_sep_spectral() {
   }
   const double fl_a = 2.0 * F * F * (double)cin * mid2 * 15, fl_b = 2.0 * F * F * (double)mid2 * co * 15;
   // flops < 0 marks an auxiliary pass of a contraction: its time counts with the conv kernels, it has no FLOPs of its own
-  ops.push_back({pre + "conv2d/dft_y", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
-                   return launch_dft_fwd(o.p, F, o.ld, 0, N, mpad(N), d_tf, xa_hi, xa_lo, s);
-                 }});
-  ops.push_back({pre + "conv2d [spectral]", ST_LSEP, fl_a, [=](int N, hipStream_t s) {
-                   ConvIO io;                   // NB groups of mpad(N) rows, N * F of them live
-                   io.in_hi = xa_hi; io.in_lo = xa_lo; io.zeros = LA->d_zeros; io.out = y1;
-                   io.group_rows = mpad(N); io.group_live_rows = N * F;
-                   return LA->forward(io, 1, 1, NB * mpad(N), 2 * cin_ld, 2 * mid2, s);
-                 }});
-  ops.back().mfma_flops = 2.0 * nsplit_of(LA) * NB * (double)F * (2.0 * cin_ld) * (2.0 * mid2);
-  ops.push_back({pre + "conv2d/idft_y+bias", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
-                   return launch_dft_inv(y1, F, 2 * mid2, mid2, N, mpad(N), d_ti, d_ones, d_ba, 0, tmid, mid2, 0, s);
-                 }});
-  ops.push_back({pre + "conv2d_1/dft_x", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
-                   return launch_dft_fwd(tmid, F, mid2, 1, N, mpad(N), d_tf_b, xb_hi, xb_lo, s);
-                 }});
-  ops.push_back({pre + "conv2d_1 [spectral]", ST_LSEP, fl_b, [=](int N, hipStream_t s) {
-                   ConvIO io;
-                   io.in_hi = xb_hi; io.in_lo = xb_lo; io.zeros = LB->d_zeros; io.out = y2;
-                   io.group_rows = mpad(N); io.group_live_rows = N * F;
-                   return LB->forward(io, 1, 1, NB * mpad(N), 2 * mid2, 2 * co_ld, s);
-                 }});
-  ops.back().mfma_flops = 2.0 * nsplit_of(LB) * NB * (double)F * (2.0 * mid2) * (2.0 * co_ld);
-  ops.push_back({pre + "conv2d_1/idft_x+bn+relu", ST_LSEP, -1.0, [=](int N, hipStream_t s) {
-                   return launch_dft_inv(y2, F, 2 * co_ld, co_ld, N, mpad(N), d_ti, d_sc, d_sh, 1, ft.p, ft.ld, 1, s);
-                 }});
+  ops.push_back({pre + "conv2d/dft_y", ST_LSEP, -1.0, [=](int N, hipStream_t s) { return SA->dft_fwd(o.p, N, xa_hi, xa_lo, s); }});
+  ops.push_back({pre + "conv2d [spectral]", ST_LSEP, fl_a, [=](int N, hipStream_t s) { return SA->gemm(N, xa_hi, xa_lo, y1, s); }});
+  ops.back().mfma_flops = 2.0 * nsplit_of(&SA->G) * NB * (double)F * (2.0 * cin_ld) * (2.0 * mid2);
+  ops.push_back({pre + "conv2d/idft_y+bias", ST_LSEP, -1.0, [=](int N, hipStream_t s) { return SA->dft_inv(N, y1, tmid, mid2, s); }});
+  ops.push_back({pre + "conv2d_1/dft_x", ST_LSEP, -1.0, [=](int N, hipStream_t s) { return SB->dft_fwd(tmid, N, xb_hi, xb_lo, s); }});
+  ops.push_back({pre + "conv2d_1 [spectral]", ST_LSEP, fl_b, [=](int N, hipStream_t s) { return SB->gemm(N, xb_hi, xb_lo, y2, s); }});
+  ops.back().mfma_flops = 2.0 * nsplit_of(&SB->G) * NB * (double)F * (2.0 * mid2) * (2.0 * co_ld);
+  ops.push_back({pre + "conv2d_1/idft_x+bn+relu", ST_LSEP, -1.0, [=](int N, hipStream_t s) { return SB->dft_inv(N, y2, ft.p, ft.ld, s); }});
   return XDET_OK;
 }
 

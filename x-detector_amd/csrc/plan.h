@@ -316,6 +316,7 @@ struct Plan {
   int add_pool(const std::string& name, int stage, const Buf& in, const Buf* res, Buf* out);
   ConvLayer* keep(ConvLayer* L) { layers.emplace_back(L); return L; }
   DepthwiseLayer* keep(DepthwiseLayer* L) { layers.emplace_back(L); return L; }
+  SpectralConv* keep(SpectralConv* L) { layers.emplace_back(L); return L; }
 
   // tf.layers.conv2d(use_bias=False) + BN (+ReLU); *layer (optional): the conv layer it made
   int conv_bn(const std::string& name, const std::string& bn, float eps, int stage, const Buf& in, const ConvArgs& args, Buf* out,

@@ -92,6 +92,14 @@ SIGNATURES = {
     'xdet_conv3x3_patch_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_resnet_bneck_forward': (c_int, [c_void_p, c_void_p, c_void_p, PF, PF, PF, c_int, c_int, c_int, PF, PF, PF,
                                           c_void_p, c_void_p, c_void_p]),
+    'xdet_spectral_conv_create': (c_int, [ctypes.POINTER(c_void_p), PF, c_int, c_int, c_int, c_int, c_int, PF, PF, c_int]),
+    'xdet_spectral_conv_workspace_bytes': (c_size_t, [c_void_p, c_int]),
+    'xdet_spectral_conv_forward': (c_int, [c_void_p, PF, c_int, c_int, c_void_p, PF, c_int, c_void_p]),
+    'xdet_stem_conv3x3s2_forward': (c_int, [PF, PF, PF, PF, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'xdet_resnet_stem7x7_forward': (c_int, [c_void_p, PF, c_int, c_int, PF, c_void_p]),
+    'xdet_maxpool3x3s2_bn_planes': (c_int, [PF, PF, PF, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                            c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    'xdet_resnet_preconv_forward': (c_int, [c_void_p, PF, PF, PF, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'xdet_sepconv_fused_hpool_forward': (c_int, [c_void_p, c_void_p, PF, c_int, c_int, c_int, c_int, PF, c_int, c_int,
                                                  c_void_p]),
     'xdet_maxpool_v3s2_add': (c_int, [PF, PF, PF, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -297,6 +297,118 @@ def max_pool_3x3_s2_same_add(x, residual=None, stream=None):
     return out
 
 
+def planes_bytes(n_pix, ld):
+    """bytes of one f16 plane of the xdet_split_f32 layout [ceil(n_pix/16)][ld/32][16][32]"""
+    return -(-n_pix // 16) * 16 * ld * 2
+
+
+def _planes_pair(out, n_pix, ld):
+    if out is not None:
+        return out
+    return DeviceBuffer(planes_bytes(n_pix, ld), zero=True), DeviceBuffer(planes_bytes(n_pix, ld), zero=True)
+
+
+class SpectralConv(object):
+    """A (T,1) [axis 0] or (1,T) [axis 1] SAME convolution (T <= 15 taps, stride 1) over an F x F map in the DFT domain of the
+    convolved axis (xdet_spectral_conv_*; the large-separable convs, net/xception_body.py:450-475), with folded
+    scale / shift (+ReLU).  kernel [T, cin, cout]; F in (16, 30, 50); split-precision modes only."""
+    def __init__(self, kernel, axis, F, scale=None, shift=None, relu=False):
+        k = np.ascontiguousarray(kernel, np.float32)
+        self.taps, self.cin, self.cout = k.shape
+        self.axis, self.F = int(axis), int(F)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        sh = None if shift is None else np.ascontiguousarray(shift, np.float32)
+        h = c_void_p()
+        check(lib().xdet_spectral_conv_create(ctypes.byref(h), _host(k), self.taps, self.cin, self.cout, self.axis, self.F,
+                                              _host(sc) if sc is not None else None, _host(sh) if sh is not None else None,
+                                              1 if relu else 0))
+        self.handle = h
+
+    def workspace_bytes(self, N):
+        return int(lib().xdet_spectral_conv_workspace_bytes(self.handle, int(N)))
+
+    def __call__(self, x, out=None, workspace=None, stream=None):
+        """x: DeviceTensor [N,F,F,cin]; out (optional): a DeviceTensor to write into (its ld may exceed round_up(cout,32));
+        workspace (optional): a DeviceBuffer of workspace_bytes(N) bytes, any contents"""
+        N, H, W, C = x.shape
+        assert (H, W, C) == (self.F, self.F, self.cin), (x.shape, self.F, self.cin)
+        if out is None:
+            out = DeviceTensor.empty((N, H, W, self.cout))
+        ws = workspace if workspace is not None else DeviceBuffer(self.workspace_bytes(N))
+        check(lib().xdet_spectral_conv_forward(self.handle, x.ptr, N, x.ld, ws.ptr, out.ptr, out.ld,
+                                               stream.handle if stream else None))
+        synchronize(stream)
+        return out
+
+    def __del__(self):
+        try:
+            lib().xdet_layer_destroy(self.handle)
+        except Exception:
+            pass
+
+
+def stem_conv3x3s2(images_nchw, kernel_hwio, scale, shift, out=None, stream=None):
+    """block1_conv1 (net/xception_body.py:243-250; xdet_stem_conv3x3s2_forward): images f32 [N,3,S,S], kernel [3,3,3,32],
+    scale / shift [32] (folded BN; ReLU follows) -> (hi, lo) planes (ld 32) of the [N,Ho,Ho,32] output, Ho = (S-3)//2 + 1.
+    out: a (hi, lo) pair of DeviceBuffers to write into."""
+    x = np.ascontiguousarray(images_nchw, np.float32)
+    N, C, S, S2 = x.shape
+    assert C == 3 and S == S2 and tuple(np.shape(kernel_hwio)) == (3, 3, 3, 32)
+    Ho = (S - 3) // 2 + 1
+    d_x, d_w = to_device(x), to_device(np.ascontiguousarray(kernel_hwio, np.float32))
+    d_sc, d_sh = to_device(np.ascontiguousarray(scale, np.float32)), to_device(np.ascontiguousarray(shift, np.float32))
+    hi, lo = _planes_pair(out, N * Ho * Ho, 32)
+    check(lib().xdet_stem_conv3x3s2_forward(d_x.ptr, d_w.ptr, d_sc.ptr, d_sh.ptr, hi.ptr, lo.ptr, N, S,
+                                            stream.handle if stream else None))
+    synchronize(stream)
+    return hi, lo
+
+
+def resnet_stem7x7(conv, images_nchw, stream=None):
+    """conv2d_fixed_padding(7, 64, stride 2) of the ResNet v2 stem on its own kernel (xdet_resnet_stem7x7_forward): `conv` a
+    Conv2D(7x7x3x64, stride 2, 'EXPLICIT', explicit_pad=3) created in the f16x3 mode, images f32 [N,3,S,S] -> DeviceTensor
+    [N,Ho,Ho,64]; the same bits as conv(NHWC images)."""
+    x = np.ascontiguousarray(images_nchw, np.float32)
+    N, C, S, S2 = x.shape
+    assert C == 3 and S == S2
+    Ho = (S - 1) // 2 + 1
+    d_x = to_device(x)
+    out = DeviceTensor.empty((N, Ho, Ho, 64))
+    check(lib().xdet_resnet_stem7x7_forward(conv.handle, d_x.ptr, N, S, out.ptr, stream.handle if stream else None))
+    synchronize(stream)
+    return out
+
+
+def max_pool_3x3_s2_bn_planes(x, scale, shift, mul=1.0, out=None, second=None, stream=None):
+    """max_pooling2d(3, 2, 'same') -> relu(. * scale + shift) * mul as split planes (xdet_maxpool3x3s2_bn_planes; the ResNet
+    stem tail, net/resnet_v2.py:311-330 + :142-156).  x: DeviceTensor [N,H,W,C] (ld % 32 == 0); scale / shift [ld].
+    second = (hi2_ptr, lo2_ptr, c32_2, mul2): a second copy * mul2 into the channel blocks of a wider planes tensor.
+    -> (hi, lo) DeviceBuffers over the N * ceil(H/2) * ceil(W/2) pixels."""
+    N, H, W, C = x.shape
+    n_pix = N * -(-H // 2) * -(-W // 2)
+    d_sc, d_sh = to_device(np.ascontiguousarray(scale, np.float32)), to_device(np.ascontiguousarray(shift, np.float32))
+    hi, lo = _planes_pair(out, n_pix, x.ld)
+    hi2, lo2, c32_2, mul2 = second if second is not None else (None, None, 0, 1.0)
+    check(lib().xdet_maxpool3x3s2_bn_planes(x.ptr, d_sc.ptr, d_sh.ptr, hi.ptr, lo.ptr, N, H, W, C, x.ld, float(mul),
+                                            _ptr(hi2), _ptr(lo2), int(c32_2), float(mul2), stream.handle if stream else None))
+    synchronize(stream)
+    return hi, lo
+
+
+def resnet_preconv(conv, pre_scale, pre_shift, x, out=None, stream=None):
+    """The opening 1x1 conv of a ResNet v2 bottleneck with the pre-activation made on the CU (xdet_resnet_preconv_forward):
+    planes of conv(relu(x * pre_scale + pre_shift)); `conv` a 1x1 Conv2D with ReLU, 256 | 512 -> 128 channels, created in the
+    f16x3 mode.  x: DeviceTensor [N,H,W,cin] -> (hi, lo) DeviceBuffers (ld 128)."""
+    N, H, W, C = x.shape
+    assert C == conv.cin and x.ld == C, (C, x.ld, conv.cin)
+    d_sc, d_sh = to_device(np.ascontiguousarray(pre_scale, np.float32)), to_device(np.ascontiguousarray(pre_shift, np.float32))
+    hi, lo = _planes_pair(out, N * H * W, channel_ld(conv.cout))
+    check(lib().xdet_resnet_preconv_forward(conv.handle, d_sc.ptr, d_sh.ptr, x.ptr, N, H, W, hi.ptr, lo.ptr,
+                                            stream.handle if stream else None))
+    synchronize(stream)
+    return hi, lo
+
+
 class AnchorCreator(object):
     """preprocessing/anchor_manipulator.py:686-757 (single feature layer)."""
     def __init__(self, img_shape, layers_shapes, anchor_scales, extra_anchor_scales, anchor_ratios, layer_steps):
