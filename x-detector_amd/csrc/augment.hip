@@ -13,6 +13,7 @@
 // Sizes and ground truth come from device memory, as in preprocess_batch_kernel; nothing of the canvas or of the
 // distorted full-size image is ever materialised.
 #include "common.h"
+#include "shuffle.h"
 
 #include <algorithm>
 
@@ -42,11 +43,6 @@ struct AugWorkspace {
   AugRecord* rec;              // [N]
   unsigned long long* sums;    // [N][4] two's-complement fixed-point sums (R, G, B, unused)
 };
-
-__host__ __device__ __forceinline__ unsigned aug_mix(unsigned x) {
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return x;
-}
 
 // the select forms of the contract: max(a, b) = a < b ? b : a, min(a, b) = b < a ? b : a
 __device__ __forceinline__ float smax(float a, float b) { return a < b ? b : a; }
@@ -145,7 +141,7 @@ __device__ __forceinline__ Rgb load_rgb(const unsigned char* __restrict__ img, i
 struct Draws {
   unsigned word;
   int k;
-  __device__ __forceinline__ unsigned next() { return aug_mix(word ^ (0x80000000u | (unsigned)k++)); }
+  __device__ __forceinline__ unsigned next() { return tg_mix(word ^ (0x80000000u | (unsigned)k++)); }
   __device__ __forceinline__ float uf(float lo, float hi) {
     const float t = (float)(next() >> 8) * 0x1p-24f;
     return lo + t * (hi - lo);
@@ -204,7 +200,7 @@ __global__ __launch_bounds__(AUG_WAVE) void augment_geometry_kernel(
   const int n_in = min(max(n_gt[n], 0), G);
   const int n_pad = (n_in + AUG_WAVE - 1) / AUG_WAVE * AUG_WAVE;
   Draws D;
-  D.word = aug_mix(seed_word + (unsigned)(image_ids ? image_ids[n] : n));
+  D.word = tg_mix(seed_word + (unsigned)(image_ids ? image_ids[n] : n));
   D.k = 0;
 
   // colour parameters, each drawn when its op is reached
@@ -618,7 +614,7 @@ int launch_preprocess_train(const unsigned char* packed, int64_t packed_bytes, c
   ws.rec = static_cast<AugRecord*>(workspace);
   ws.sums = reinterpret_cast<unsigned long long*>(ws.rec + N);
   hipLaunchKernelGGL(augment_geometry_kernel, dim3((unsigned)N), dim3(AUG_WAVE), 0, s, packed_bytes, offsets, image_shapes,
-                     glabels, gbboxes, n_gt, image_ids, G, aug_mix(seed ^ 0x9E3779B9u), ws, out_glabels, out_gbboxes, out_n_gt);
+                     glabels, gbboxes, n_gt, image_ids, G, tg_mix(seed ^ 0x9E3779B9u), ws, out_glabels, out_gbboxes, out_n_gt);
   XDET_LAUNCH_CHECK();
   hipLaunchKernelGGL(augment_mean_kernel, dim3(AUG_MEAN_BLOCKS, (unsigned)N), dim3(AUG_T), 0, s, packed, offsets, image_shapes,
                      ws);

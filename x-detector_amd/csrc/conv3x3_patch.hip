@@ -14,15 +14,12 @@
 //
 // Tile = 4 output rows x 30 pixels (a 128-row GEMM tile; 30 + 2 = 32 patch columns = two 1 KB DMA pieces per row
 // and plane), 4 waves as 2 x 2 over 128 pixels x 64 channels, two patch buffers (the next tile's patch is in flight
-// during the MFMAs; fragment reads behind the DMA are inline asm, see sepconv_fused.hip), XCD-band interleaved tile
+// during the MFMAs; fragment reads behind the DMA are inline asm, see cu_prims.h), XCD-band interleaved tile
 // order.  K order (tap ascending, two halves) and product order are conv_dma_f16_kernel's: bit-identical.
 #include "common.h"
+#include "cu_prims.h"
 
 namespace xdet {
-
-typedef float cp_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 cp_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int CP_R = 4, CP_X = 30, CP_P = 32, CP_ROWS = CP_R + 2;
 constexpr int CP_PLANE_H = CP_ROWS * CP_P * 32 + 3 * 32;     // halves per plane per buffer (+3 pixels of slack: px 30, 31 + kx)
@@ -35,16 +32,6 @@ struct Conv3x3PatchParams {
   float* out;                            // NHWC f32 [N][Ho][Wo][ldo]
   int N, H, W, Ho, Wo, ldo, relu, TY, TX, ntiles;
 };
-
-__device__ __forceinline__ unsigned cp_lds_addr(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) void*)(p);
-}
-template <int OFF>
-__device__ __forceinline__ cp_f16x8 cp_ds_read_b128(unsigned addr) {
-  cp_f16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
 
 template <bool SPLIT3>
 __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(Conv3x3PatchParams p) {
@@ -98,14 +85,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(Conv3x3PatchParam
   const int wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves: 64 pixels (two tile rows) x 32 channels each
 
   // the whole filter of this wave's 32 output channels, both halves of all nine taps, in registers
-  cp_f16x8 bh[9][2], bl[9][2];
+  f16x8 bh[9][2], bl[9][2];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const size_t o = ((size_t)t * 64 + (wn * 32 + frow)) * 32 + (ks * 2 + fh) * 8;
-      bh[t][ks] = *reinterpret_cast<const cp_f16x8*>(p.wt_hi + o);
-      if (SPLIT3) bl[t][ks] = *reinterpret_cast<const cp_f16x8*>(p.wt_lo + o);
+      bh[t][ks] = *reinterpret_cast<const f16x8*>(p.wt_hi + o);
+      if (SPLIT3) bl[t][ks] = *reinterpret_cast<const f16x8*>(p.wt_lo + o);
     }
   const float esc = p.scale[wn * 32 + frow], esh = p.shift[wn * 32 + frow];
 
@@ -118,24 +105,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(Conv3x3PatchParam
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     issue(nxt, buf ^ 1, t + G < t_end);
     __builtin_amdgcn_sched_barrier(0);
-    cp_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    const unsigned pbase = cp_lds_addr(&s_patch[buf][0][0]);
+    const unsigned pbase = lds_addr(&s_patch[buf][0][0]);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int ky = tap / 3, kx = tap % 3;
-      cp_f16x8 ah[2][2], al[2][2];
+      f16x8 ah[2][2], al[2][2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int q = (wm * 2 + i + ky) * CP_P + frow + kx;                 // patch pixel feeding output pixel frow
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const unsigned a = pbase + (unsigned)(q * 32 + (((ks * 2 + fh) ^ ((q >> 2) & 3)) << 3)) * 2u;
-          ah[i][ks] = cp_ds_read_b128<0>(a);
-          if (SPLIT3) al[i][ks] = cp_ds_read_b128<CP_PLANE_H * 2>(a);
+          ah[i][ks] = ds_read_h8<0>(a);
+          if (SPLIT3) al[i][ks] = ds_read_h8<CP_PLANE_H * 2>(a);
         }
       }
       if (SPLIT3)

@@ -14,10 +14,10 @@
 // Epilogue: y = acc*scale[co] + shift[co] (+ residual) (ReLU): folded inference BN
 // (net/xception_body.py:232, net/resnet_v2.py:41-50) or bias.
 #include "common.h"
+#include "cu_prims.h"
 
 namespace xdet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
 constexpr int LDS_LD = 36;   // floats per LDS row: 32 + 4 pad (144 B, keeps b128 reads conflict-free)

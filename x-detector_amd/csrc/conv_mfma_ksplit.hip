@@ -18,41 +18,15 @@
 //
 // Tile 128 x 128 (2 x 2 waves of 64 x 64) or 128 x 64 (4 x 1 waves of 32 x 64) with a FOUR-stage operand ring: the stage
 // being read plus two in flight plus the one being refilled; one barrier per 32-deep step, which waits with
-// vmcnt(two stages' worth) for the oldest stage only.  LDS reads are inline asm (the compiler would drain vmcnt(0) in
-// front of every LDS read while LDS-DMA writes are outstanding); every step issues the same number of DMA instructions
-// (past the end from the zero page) so that the vmcnt arithmetic is static.
+// vmcnt(two stages' worth) for the oldest stage only.  LDS reads are the inline-asm accessors of cu_prims.h; every step
+// issues the same number of DMA instructions (past the end from the zero page) so that the vmcnt arithmetic is static.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "cu_prims.h"
 #include <cstdlib>
 #include <cstring>
 
 namespace xdet {
-
-typedef float ks_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 ks_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef float ks_f4 __attribute__((ext_vector_type(4)));
-
-#define XDET_KS_GLDS16(gptr, lptr)                                                                     \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),              \
-                                   (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-
-template <int OFF>
-__device__ __forceinline__ ks_f16x8 ks_ds_read_b128(unsigned addr) {
-  ks_f16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-
-template <int V>
-struct ks_int { static constexpr int value = V; };
-template <int N, typename F, int I = 0>
-__device__ __forceinline__ void ks_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ks_int<I>{});
-    ks_static_for<N, F, I + 1>(static_cast<F&&>(f));
-  }
-}
 
 // PARALLEL: gridDim covers (tile, range) pairs; else one workgroup per tile walks every range.
 // NT = KH * KW (1 or 9), a compile-time constant: the tap loop is unrolled, so the per-lane source offset of every
@@ -74,12 +48,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int NSTAGE = 4;
-  constexpr bool HALFB_ = WAVES_M * WAVES_N == 8 && BN == 64;
-  constexpr int A_IT = BM / (16 * NW), B_IT = HALFB_ ? 1 : BN / (16 * NW);
+  constexpr int A_IT = BM / (16 * NW), B_IT = HALFB ? 1 : BN / (16 * NW);
   constexpr int ROWB = 32;
   constexpr int STAGE = (2 * BM + 2 * BN) * ROWB;          // halves per stage
-  constexpr int PIECES = HALFB_ ? 3 : (A_IT + B_IT) * (NSPLIT > 1 ? 2 : 1);
-  static_assert(!HALFB_ || NSPLIT == 3, "eight waves on the 64-wide tile: the f16x3 form");
+  constexpr int PIECES = HALFB ? 3 : (A_IT + B_IT) * (NSPLIT > 1 ? 2 : 1);
+  static_assert(!HALFB || NSPLIT == 3, "eight waves on the 64-wide tile: the f16x3 form");
   extern __shared__ __attribute__((aligned(16))) u16 smem16[];
 
   const int tid = threadIdx.x;
@@ -176,7 +149,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
     }
   };
 
-  ks_f32x16 acc[TM][TN], tot[TM][TN];
+  f32x16 acc[TM][TN], tot[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -204,9 +177,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
   }
 
   // prologue: the first NSTAGE - 1 stages of the span
-  ks_static_for<NSTAGE - 1>([&](auto J) {
+  static_for<NSTAGE - 1>([&](auto J) {
     constexpr int j = decltype(J)::value;
-    issue(cc_lo + j / NT, ks_int<j % NT>{}, j);
+    issue(cc_lo + j / NT, int_c<j % NT>{}, j);
   });
   int ring = 0;
   int next_fold = PARALLEL ? (1 << 30) : cs;               // sequential mode: fold at every range boundary
@@ -225,26 +198,26 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
       first = false;
       next_fold += cs;
     }
-    ks_static_for<NT>([&](auto TAP) {
+    static_for<NT>([&](auto TAP) {
       constexpr int tap = decltype(TAP)::value;
       // this stage has landed (two younger stages may still be in flight) and every wave is done reading the stage
       // before it, whose ring slot the new DMA overwrites
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NSTAGE - 2) * PIECES) : "memory");
-      issue(cc + (tap + NSTAGE - 1) / NT, ks_int<(tap + NSTAGE - 1) % NT>{}, (ring + NSTAGE - 1) & (NSTAGE - 1));
+      issue(cc + (tap + NSTAGE - 1) / NT, int_c<(tap + NSTAGE - 1) % NT>{}, (ring + NSTAGE - 1) & (NSTAGE - 1));
       __builtin_amdgcn_sched_barrier(0);
       const unsigned sb = lds0 + (unsigned)(ring * STAGE * 2);
-      ks_f16x8 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
+      f16x8 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-          ah[h][i] = ks_ds_read_b128<0>(sb + a_off[h][i]);
-          if (NSPLIT > 1) al[h][i] = ks_ds_read_b128<BM * ROWB * 2>(sb + a_off[h][i]);
+          ah[h][i] = ds_read_h8<0>(sb + a_off[h][i]);
+          if (NSPLIT > 1) al[h][i] = ds_read_h8<BM * ROWB * 2>(sb + a_off[h][i]);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          bh[h][j] = ks_ds_read_b128<0>(sb + b_off[h][j]);
-          if (NSPLIT > 1) bl[h][j] = ks_ds_read_b128<BN * ROWB * 2>(sb + b_off[h][j]);
+          bh[h][j] = ds_read_h8<0>(sb + b_off[h][j]);
+          if (NSPLIT > 1) bl[h][j] = ds_read_h8<BN * ROWB * 2>(sb + b_off[h][j]);
         }
       }
 #pragma unroll
@@ -299,7 +272,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
   } else if (S > 1 && !p.ks_ticket) {
     // park the raw accumulators: slab [tile][range][v][tid] of float4 (every store instruction one contiguous 4 / 8 KB)
     constexpr int V = TM * TN * 4;
-    ks_f4* slab = reinterpret_cast<ks_f4*>(p.ks_partial) + ((size_t)tile * S + range) * V * (64 * NW);
+    f32x4* slab = reinterpret_cast<f32x4*>(p.ks_partial) + ((size_t)tile * S + range) * V * (64 * NW);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -307,7 +280,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           slab[((i * TN + j) * 4 + q) * (64 * NW) + tid] =
-              ks_f4{acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
+              f32x4{acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
     return;                                                // the fold + epilogue: conv_ksplit_fold_kernel, next launch
   }
   if (PARALLEL && S > 1 && p.ks_ticket) {
@@ -322,15 +295,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.ks_partial + (size_t)tile * S * V * (NW * 256), 0,
                                                                         S * V * (NW * 1024), 0x00020000);
     const int vo = tid * 16;
-    typedef unsigned ks_u4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const ks_f4 x = {acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ks_u4, x), rs, vo, (range * V + (i * TN + j) * 4 + q) * (NW * 1024), 16);
+          const f32x4 x = {acc[i][j][q * 4], acc[i][j][q * 4 + 1], acc[i][j][q * 4 + 2], acc[i][j][q * 4 + 3]};
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), rs, vo, (range * V + (i * TN + j) * 4 + q) * (NW * 1024), 16);
         }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -343,15 +315,15 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
     __syncthreads();
     if (!*s_last) return;
     __syncthreads();                                       // (s_last is read before the epilogue reuses the LDS)
-    ks_f4 t[V];
+    f32x4 t[V];
 #pragma unroll 1
     for (int r0 = 0; r0 < S; r0 += 2) {
-      ks_f4 u0[V], u1[V];
+      f32x4 u0[V], u1[V];
       const bool two = r0 + 1 < S;
 #pragma unroll
       for (int v = 0; v < V; ++v) {
-        u0[v] = __builtin_bit_cast(ks_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (r0 * V + v) * (NW * 1024), 16));
-        u1[v] = __builtin_bit_cast(ks_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (two ? (r0 + 1) * V + v : r0 * V + v) * (NW * 1024), 16));
+        u0[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (r0 * V + v) * (NW * 1024), 16));
+        u1[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (two ? (r0 + 1) * V + v : r0 * V + v) * (NW * 1024), 16));
       }
 #pragma unroll
       for (int v = 0; v < V; ++v) {
@@ -365,7 +337,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_ksplit_kernel
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const ks_f4 x = t[(i * TN + j) * 4 + q];
+          const f32x4 x = t[(i * TN + j) * 4 + q];
           acc[i][j][q * 4] = x.x; acc[i][j][q * 4 + 1] = x.y; acc[i][j][q * 4 + 2] = x.z; acc[i][j][q * 4 + 3] = x.w;
         }
   }
@@ -407,15 +379,15 @@ __global__ __launch_bounds__(64) void conv_ksplit_fold_kernel(ConvParams p) {
   const int vo = tid * 16;
   // two ranges per pass of a real loop (2 x V loads in flight, then their additions in range order): unrolled over all S
   // ranges the compiler put every load up front and spilled; one range per pass is a chain of S memory round trips
-  ks_f4 t[V];
+  f32x4 t[V];
 #pragma unroll 1
   for (int r0 = 0; r0 < S; r0 += 2) {
-    ks_f4 u0[V], u1[V];
+    f32x4 u0[V], u1[V];
     const bool two = r0 + 1 < S;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      u0[v] = __builtin_bit_cast(ks_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (r0 * V + v) * (NW * 1024), 0));
-      u1[v] = __builtin_bit_cast(ks_f4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (two ? (r0 + 1) * V + v : r0 * V + v) * (NW * 1024), 0));
+      u0[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (r0 * V + v) * (NW * 1024), 0));
+      u1[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo, (two ? (r0 + 1) * V + v : r0 * V + v) * (NW * 1024), 0));
     }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -423,14 +395,14 @@ __global__ __launch_bounds__(64) void conv_ksplit_fold_kernel(ConvParams p) {
       if (two) t[v] = t[v] + u1[v];
     }
   }
-  ks_f32x16 acc[TM][TN];
+  f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const ks_f4 x = t[(i * TN + j) * 4 + q];
+        const f32x4 x = t[(i * TN + j) * 4 + q];
         acc[i][j][q * 4] = x.x; acc[i][j][q * 4 + 1] = x.y; acc[i][j][q * 4 + 2] = x.z; acc[i][j][q * 4 + 3] = x.w;
       }
   if (m0 + BM <= p.M) conv_epilogue_full<WM, WN, TM, TN, 1, LDS_BYTES>(p, acc, smem16, 0, lane, wm, wn, m0, n0);

@@ -21,25 +21,12 @@
 // latency on its own), LDS is double-buffered: one barrier per K-step.
 #include "common.h"
 #include "conv_epilogue.h"
+#include "cu_prims.h"
 
 namespace xdet {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 constexpr int BKH = 32;      // K step (16-bit elements)
 constexpr int LDH = 40;      // u16 per LDS row: 32 + 8 pad = 80 B
-
-__device__ __forceinline__ void split4(const float4 v, uint2* hi, uint2* lo) {
-  const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-  f16x4 hv = {h0, h1, h2, h3};
-  f16x4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
-              (_Float16)(v.w - (float)h3)};
-  *hi = *reinterpret_cast<uint2*>(&hv);
-  *lo = *reinterpret_cast<uint2*>(&lv);
-}
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool SMALL_CIN, int NSPLIT>
 __global__ __launch_bounds__(256) void conv_mfma_f16_kernel(ConvParams p) {

@@ -4,6 +4,7 @@
 //     tf.layers.separable_conv2d (net/xception_body.py:220-234,268,354,366)
 //   * max-pool 3x3/2 SAME + residual add (net/xception_body.py:281-286,302-307,321-326)
 #include "common.h"
+#include "cu_prims.h"
 #include <cstdlib>
 
 namespace xdet {
@@ -37,8 +38,6 @@ int launch_nchw_to_nhwc4(const float* in, float* out, int N, int C, int H, int W
 // split-precision path) instead of f32.
 constexpr int DW_SX = 4;
 
-typedef _Float16 f16x4e __attribute__((ext_vector_type(4)));
-
 // offset (in halves) of channel c of pixel `pix` in a split plane.  Layout: [pix/16][ld/32][16][32]:
 // 16 pixels x 32 channels form one contiguous 1 KB block (what one LDS-DMA instruction of the conv
 // kernel moves), and all channel blocks of a 16-pixel group are adjacent, so a producer that walks
@@ -71,7 +70,7 @@ __device__ __forceinline__ void dw_store_strip(const float4* acc, float* __restr
     for (int k = 0; k < 4; ++k) {
       const float4 v = acc[k];
       const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-      f16x4e hv = {h0, h1, h2, h3};
+      f16x4 hv = {h0, h1, h2, h3};
       h[k] = *reinterpret_cast<uint2*>(&hv);
       h8[k] = pack_e4m3x4((float)h0, (float)h1, (float)h2, (float)h3, x8_hi);
       l8[k] = pack_e4m3x4(v.x - (float)h0, v.y - (float)h1, v.z - (float)h2, v.w - (float)h3, x8_lo);
@@ -107,8 +106,8 @@ __device__ __forceinline__ void dw_store_strip(const float4* acc, float* __restr
     for (int k = 0; k < 4; ++k) {
       const float4 v = acc[k];
       const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-      f16x4e hv = {h0, h1, h2, h3};
-      f16x4e lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
+      f16x4 hv = {h0, h1, h2, h3};
+      f16x4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
                    (_Float16)(v.w - (float)h3)};
       h[k] = *reinterpret_cast<uint2*>(&hv);
       l[k] = *reinterpret_cast<uint2*>(&lv);
@@ -410,9 +409,7 @@ int launch_depthwise3x3_split(const float* in, const float* w9c, unsigned short*
 // walk the OUTPUT order, so a wave writes one 1 KB block (16 pixels x 32 channels) and reads whole
 // 128-B lines (one pixel's 32-channel chunk per 4 lanes); consecutive waves take the next channel
 // block of the same 16 pixels.
-typedef _Float16 f16x8e __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void split8(const float4 a, const float4 b, f16x8e* h, f16x8e* l) {
+__device__ __forceinline__ void split8(const float4 a, const float4 b, f16x8* h, f16x8* l) {
   const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -443,9 +440,9 @@ __global__ __launch_bounds__(256) void split_f32_kernel(const float* __restrict_
     }
     a.x *= mul; a.y *= mul; a.z *= mul; a.w *= mul;
     b.x *= mul; b.y *= mul; b.z *= mul; b.w *= mul;
-    f16x8e h, l;
+    f16x8 h, l;
     split8(a, b, &h, &l);
-    *reinterpret_cast<f16x8e*>(hi + i * 8) = h;
+    *reinterpret_cast<f16x8*>(hi + i * 8) = h;
     if (X8) {   // 8 channels of the (pixel, block) record: 8 bytes of hi8 at +c, 8 bytes of lo8 at +32 + c
       const float hf[8] = {(float)h[0], (float)h[1], (float)h[2], (float)h[3], (float)h[4], (float)h[5], (float)h[6], (float)h[7]};
       const float vf[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -456,7 +453,7 @@ __global__ __launch_bounds__(256) void split_f32_kernel(const float* __restrict_
           make_uint2(pack_e4m3x4(vf[0] - hf[0], vf[1] - hf[1], vf[2] - hf[2], vf[3] - hf[3], x8_lo),
                      pack_e4m3x4(vf[4] - hf[4], vf[5] - hf[5], vf[6] - hf[6], vf[7] - hf[7], x8_lo));
     } else {
-      *reinterpret_cast<f16x8e*>(lo + i * 8) = l;
+      *reinterpret_cast<f16x8*>(lo + i * 8) = l;
     }
   }
 }
@@ -510,11 +507,11 @@ __global__ __launch_bounds__(256) void split_f32_subsample2_kernel(const float* 
     }
     a.x *= mul; a.y *= mul; a.z *= mul; a.w *= mul;
     b.x *= mul; b.y *= mul; b.z *= mul; b.w *= mul;
-    f16x8e h, l;
+    f16x8 h, l;
     split8(a, b, &h, &l);
     const int64_t o = ((grp * c32_dst + cc) << 6) + (i & 63);
-    *reinterpret_cast<f16x8e*>(hi + o * 8) = h;
-    *reinterpret_cast<f16x8e*>(lo + o * 8) = l;
+    *reinterpret_cast<f16x8*>(hi + o * 8) = h;
+    *reinterpret_cast<f16x8*>(lo + o * 8) = l;
   }
 }
 
@@ -616,20 +613,19 @@ int launch_maxpool3x3s2_add(const float* in, const float* res, float* out, int N
 __global__ __launch_bounds__(256) void planes_copy_blocks_kernel(const unsigned short* __restrict__ shi, const unsigned short* __restrict__ slo,
                                                                  unsigned short* __restrict__ dhi, unsigned short* __restrict__ dlo,
                                                                  int64_t groups, int c32_src, int c32_dst, float r) {
-  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
   const int64_t n = groups * c32_src * 64;             // 16-byte pieces per plane
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t blk = i >> 6;
     const int64_t grp = blk / c32_src;
     const int cc = (int)(blk - grp * c32_src);
     const int64_t o = ((grp * c32_dst + cc) << 6) + (i & 63);
-    h8 h = *reinterpret_cast<const h8*>(shi + i * 8), l = *reinterpret_cast<const h8*>(slo + i * 8);
+    f16x8 h = *reinterpret_cast<const f16x8*>(shi + i * 8), l = *reinterpret_cast<const f16x8*>(slo + i * 8);
     if (r != 1.f) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) { h[k] = (_Float16)((float)h[k] * r); l[k] = (_Float16)((float)l[k] * r); }
     }
-    *reinterpret_cast<h8*>(dhi + o * 8) = h;
-    *reinterpret_cast<h8*>(dlo + o * 8) = l;
+    *reinterpret_cast<f16x8*>(dhi + o * 8) = h;
+    *reinterpret_cast<f16x8*>(dlo + o * 8) = l;
   }
 }
 
@@ -741,7 +737,6 @@ __global__ void bn_relu_kernel(const float* __restrict__ in, const float* __rest
                                unsigned short* __restrict__ hi, unsigned short* __restrict__ lo, int64_t npix, int ld,
                                float mul) {
   // mul = 2^-e, the planes' activation pre-scale (1 by default): hi + lo = relu(bn(x)) * mul; the f32 copy is unscaled
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
   const int c4n = ld >> 2;
   const int64_t total = npix * c4n;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -756,8 +751,8 @@ __global__ void bn_relu_kernel(const float* __restrict__ in, const float* __rest
       const int64_t pix = i / c4n;
       v.x *= mul; v.y *= mul; v.z *= mul; v.w *= mul;
       const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-      h4 hv = {h0, h1, h2, h3};
-      h4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
+      f16x4 hv = {h0, h1, h2, h3};
+      f16x4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
                (_Float16)(v.w - (float)h3)};
       const int64_t o = (((pix >> 4) * (ld >> 5) + (c >> 5)) << 9) + ((pix & 15) << 5) + (c & 31);
       *reinterpret_cast<uint2*>(hi + o) = *reinterpret_cast<uint2*>(&hv);

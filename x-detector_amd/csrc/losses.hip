@@ -332,7 +332,8 @@ __global__ __launch_bounds__(LS_T) void ls_compact_kernel(const int* __restrict_
   if (any_sel) flush();
 }
 
-// ascending bitonic sort of P (a power of two) 32-bit words in LDS, all LS_OT threads
+// ascending bitonic sort of P (a power of two) 32-bit words in LDS, all LS_OT threads (one pair per thread and pass:
+// another loop than lds_bitonic_sort_u64 of shuffle.h)
 __device__ void ls_sort(unsigned* s, int P) {
   for (int k = 2; k <= P; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -514,21 +515,6 @@ struct HeadArgs {
   float* partial;          // [N][4]
 };
 
-// ascending bitonic sort of P (a power of two) distinct 64-bit words in LDS, all HL_T threads
-__device__ void hl_sort(unsigned long long* s, int P) {
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P; i += HL_T) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long x = s[i], y = s[p];
-          if ((x > y) == ((i & k) == 0)) { s[i] = y; s[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 // row max and sum of exp(x - max) in index order
 __device__ __forceinline__ void hl_softmax_terms(const float* x, int C, float* mx, float* s) {
   float m = x[0];
@@ -576,7 +562,7 @@ __global__ __launch_bounds__(HL_T) void hl_image_kernel(HeadArgs a) {
     s_sort[p] = ((unsigned long long)(~__float_as_uint(l)) << 32) | (unsigned)p;
   }
   __syncthreads();
-  if (a.ohem) hl_sort(s_sort, a.P2);
+  if (a.ohem) lds_bitonic_sort_u64<HL_T>(s_sort, a.P2);
   float sl = 0.f, sc = 0.f, so = 0.f;
   for (int r = tid; r < a.K; r += HL_T) {
     const int e = a.ohem ? min((int)(s_sort[r] & 0xFFFFFFFFull), a.P - 1) : r;

@@ -24,19 +24,12 @@
 // on which operand a factor comes from (profiles/NOTES_r05.md 7), so the block's output is bit-identical to the
 // three-launch path (tests/test_gpu_resnet.py).
 #include "common.h"
+#include "cu_prims.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 namespace xdet {
-
-typedef float bk_f32x16 __attribute__((ext_vector_type(16)));
-typedef float bk_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 bk_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 bk_f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bk_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned bk_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 
 struct BneckParams {
   const float* x;                          // the block input, NHWC f32, channel stride COUT (= Cin): conv1x1_a's operand is made
@@ -55,49 +48,6 @@ struct BneckParams {
   int TY, TX, ntiles;
   int dbg;   // XDET_BNECK_DEBUG=1|2 (diagnosis only): channels 0..CMID-1 of `out` receive mid1 / mid2 (hi + lo) instead of the result
 };
-
-__device__ __forceinline__ unsigned bk_lds_addr(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) void*)(p);
-}
-// LDS accesses next to in-flight LDS-DMA writes are inline asm: the compiler would put s_waitcnt vmcnt(0) in front of each
-template <int OFF>
-__device__ __forceinline__ bk_f16x8 bk_ds_read_h8(unsigned addr) {
-  bk_f16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ bk_f32x4 bk_ds_read_f4(unsigned addr) {
-  bk_f32x4 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ void bk_ds_write_b64(unsigned addr, bk_u2 v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-// ReLU that keeps NaN (conv_epilogue.h ep_relu)
-__device__ __forceinline__ float bk_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
-
-// hi = f16(v), lo = f16(v - float(hi)) of four values (the conv epilogue's planes copy, conv_epilogue.h)
-__device__ __forceinline__ void bk_split4(const float (&t)[4], bk_u2* h, bk_u2* l) {
-  const _Float16 h0 = (_Float16)t[0], h1 = (_Float16)t[1], h2 = (_Float16)t[2], h3 = (_Float16)t[3];
-  const bk_f16x4 hv = {h0, h1, h2, h3};
-  const bk_f16x4 lv = {(_Float16)(t[0] - (float)h0), (_Float16)(t[1] - (float)h1), (_Float16)(t[2] - (float)h2),
-                       (_Float16)(t[3] - (float)h3)};
-  *h = __builtin_bit_cast(bk_u2, hv);
-  *l = __builtin_bit_cast(bk_u2, lv);
-}
-
-template <int V>
-struct bk_int { static constexpr int value = V; };
-template <int N, typename F, int I = 0>
-__device__ __forceinline__ void bk_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(bk_int<I>{});
-    bk_static_for<N, F, I + 1>(static_cast<F&&>(f));
-  }
-}
 
 template <int CMID, int R, int COUT>
 struct BneckGeom {
@@ -157,7 +107,7 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
   const int t_begin = xcd * per_xcd + wg;
   const int t_end = min(p.ntiles, (xcd + 1) * per_xcd);
   if (t_begin >= t_end) return;
-  const unsigned lds0 = bk_lds_addr(smem);
+  const unsigned lds0 = lds_addr(smem);
 
   // ---- tables: the folded BNs of the pre-activation and of the three epilogues ----
   {
@@ -243,34 +193,34 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       x_vo[q] = ok ? (pix * COUT + (unsigned)(g4 * 4)) * 4u : 0xffffffffu;     // (outside: any finite value -- epilogue 1 zeroes those pixels)
     }
   };
-  bk_f32x4 xr[3][XQ];                              // the loads of three K steps in flight
+  f32x4 xr[3][XQ];                              // the loads of three K steps in flight
   auto load_x = [&](int kt, auto SET) {
     constexpr int set = decltype(SET)::value;
 #pragma unroll
     for (int q = 0; q < XQ; ++q)
-      xr[set][q] = __builtin_bit_cast(bk_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)x_vo[q], kt * 128, 0));
+      xr[set][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)x_vo[q], kt * 128, 0));
   };
   auto transform = [&](int kt, auto SET) {         // x of step kt (in registers) -> A tile kt & 1
     constexpr int set = decltype(SET)::value;
-    bk_f32x4 sc = bk_ds_read_f4<0>(t_p + (kt * 32 + g4 * 4) * 4), sh = bk_ds_read_f4<COUT * 4>(t_p + (kt * 32 + g4 * 4) * 4);
+    f32x4 sc = ds_read_f4<0>(t_p + (kt * 32 + g4 * 4) * 4), sh = ds_read_f4<COUT * 4>(t_p + (kt * 32 + g4 * 4) * 4);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc), "+v"(sh)::"memory");
     const unsigned base = lds0 + G::OFF_A + (kt & 1) * A_STAGE;
 #pragma unroll
     for (int q = 0; q < XQ; ++q) {
       float t[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) t[k] = bk_relu(fmaf(xr[set][q][k], sc[k], sh[k]));
-      bk_u2 h, l;
-      bk_split4(t, &h, &l);
-      bk_ds_write_b64<0>(base + aw_off[q], h);
-      bk_ds_write_b64<A_PLANE>(base + aw_off[q], l);
+      for (int k = 0; k < 4; ++k) t[k] = relu_keep_nan(fmaf(xr[set][q][k], sc[k], sh[k]));
+      u32x2 h, l;
+      split4(t, &h, &l);
+      ds_write_b64<0>(base + aw_off[q], h);
+      ds_write_b64<A_PLANE>(base + aw_off[q], l);
     }
   };
 
   // ---- conv1x1_c's weights of this wave's output channels: straight from L2 into registers, requested at the start of a
   //      tile's phase 2 (a phase later they are there; held across the whole kernel they cost the other phases 32 registers
   //      and the compiler spilled -- every scratch reload waits with vmcnt(0), i.e. for the whole weight stream) ----
-  bk_f16x8 wch[NB3][NCC2][2], wcl[NB3][NCC2][2];
+  f16x8 wch[NB3][NCC2][2], wcl[NB3][NCC2][2];
   // (raw buffer loads: one 32-bit per-lane offset, the K block / half in the scalar offset -- as plain pointer loads the eight
   //  64-bit addresses were loop invariants the compiler kept across the whole tile loop, and spilled)
   const __amdgpu_buffer_rsrc_t r_wch = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.wc_hi), 0, NCC2 * COUT * 64, 0x00020000);
@@ -284,8 +234,8 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
           const int so = (kb * COUT + (wave * NB3 + j) * 32) * 64 + ks * 32;
-          wch[j][kb][ks] = __builtin_bit_cast(bk_f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_wch, vo, so, 0));
-          wcl[j][kb][ks] = __builtin_bit_cast(bk_f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_wcl, vo, so, 0));
+          wch[j][kb][ks] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_wch, vo, so, 0));
+          wcl[j][kb][ks] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(r_wcl, vo, so, 0));
         }
   };
 
@@ -323,9 +273,9 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       reinterpret_cast<unsigned long long*>(smem + G::OFF_STAMP)[n_stamp++] = __builtin_amdgcn_s_memtime();
   };
   auto prologue = [&]() {                          // groups -3, -2, -1 of the tile's VMEM queue
-    load_x(0, bk_int<0>{}); issue_b(0);
-    load_x(1, bk_int<1>{}); issue_b(1);
-    load_x(2, bk_int<2>{}); issue_b(2);
+    load_x(0, int_c<0>{}); issue_b(0);
+    load_x(1, int_c<1>{}); issue_b(1);
+    load_x(2, int_c<2>{}); issue_b(2);
   };
   prologue();
 
@@ -349,45 +299,45 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
     // end of step `wave`'s group: the counted waits of the following three steps see NRES more entries.
     constexpr int NRES = R * 4;
     static_assert(NB3 == 1, "one channel block per wave (the shortcut loads ride on one K step)");
-    bk_f32x4 res[R][NB3][4];
+    f32x4 res[R][NB3][4];
     // =============================== phase 1: conv1x1_a on the halo patch ===============================
     // (the prologue's loads are older than the previous tile's epilogue stores: everything has landed after this wait, and
     //  the counted waits of the steps below are upper bounds)
     stamp();                                       // 0: tile start
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stamp();                                       // 1: everything of the prologue (and the last epilogue) has landed
-    transform(0, bk_int<0>{});
-    bk_f32x16 acc1[2];
+    transform(0, int_c<0>{});
+    f32x16 acc1[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc1[b][r] = 0.f;
-    bk_static_for<NK1>([&](auto KT) {
+    static_for<NK1>([&](auto KT) {
       constexpr int kt = decltype(KT)::value;
       // A tile kt & 1 is complete (own writes retired, then the barrier), W(kt) has landed, every wave is done with step kt - 1
       if ((unsigned)(kt - wave - 1) < 3u) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(G::younger_b(kt) + NRES) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(G::younger_b(kt)) : "memory");
-      if constexpr (kt + 3 < NK1) load_x(kt + 3, bk_int<kt % 3>{});
+      if constexpr (kt + 3 < NK1) load_x(kt + 3, int_c<kt % 3>{});
       issue_b(kt + 3);
       if (kt == wave) {
 #pragma unroll
         for (int i = 0; i < R; ++i)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            res[i][0][q] = __builtin_bit_cast(bk_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)o_vo[i], 8 * q * 4, 0));
+            res[i][0][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)o_vo[i], 8 * q * 4, 0));
       }
       const unsigned sa = lds0 + G::OFF_A + (kt & 1) * A_STAGE, sb = lds0 + G::OFF_B + (kt % G::NRING) * B_STAGE;
-      bk_f16x8 bh[2], bl[2], ah0[2], al0[2], ah1[2], al1[2];
+      f16x8 bh[2], bl[2], ah0[2], al0[2], ah1[2], al1[2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bh[ks] = bk_ds_read_h8<0>(sb + b_off[ks]);
-        bl[ks] = bk_ds_read_h8<B_PLANE>(sb + b_off[ks]);
-        ah0[ks] = bk_ds_read_h8<0>(sa + a1_off[0][ks]);
-        al0[ks] = bk_ds_read_h8<A_PLANE>(sa + a1_off[0][ks]);
+        bh[ks] = ds_read_h8<0>(sb + b_off[ks]);
+        bl[ks] = ds_read_h8<B_PLANE>(sb + b_off[ks]);
+        ah0[ks] = ds_read_h8<0>(sa + a1_off[0][ks]);
+        al0[ks] = ds_read_h8<A_PLANE>(sa + a1_off[0][ks]);
         ah1[ks] = ah0[ks]; al1[ks] = al0[ks];
         if (two1) {
-          ah1[ks] = bk_ds_read_h8<0>(sa + a1_off[1][ks]);
-          al1[ks] = bk_ds_read_h8<A_PLANE>(sa + a1_off[1][ks]);
+          ah1[ks] = ds_read_h8<0>(sa + a1_off[1][ks]);
+          al1[ks] = ds_read_h8<A_PLANE>(sa + a1_off[1][ks]);
         }
       }
 #pragma unroll
@@ -406,18 +356,18 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       if constexpr (kt + 1 < NK1) {
         if ((unsigned)(kt - wave) < 3u) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::younger_x(kt) + NRES) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::younger_x(kt)) : "memory");
-        transform(kt + 1, bk_int<(kt + 1) % 3>{});
+        transform(kt + 1, int_c<(kt + 1) % 3>{});
       }
     });
     stamp();                                       // 2: phase 1 done
     // ---- epilogue 1: bn_b + ReLU, zero outside the image, split -> mid1 ----
     {
-      bk_f32x4 sc[4], sh[4];                       // this lane's 16 channels of the block column (the same for both blocks)
+      f32x4 sc[4], sh[4];                       // this lane's 16 channels of the block column (the same for both blocks)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c = nj1 * 32 + 8 * q + 4 * fh_t;
-        sc[q] = bk_ds_read_f4<0>(t_a + c * 4);
-        sh[q] = bk_ds_read_f4<CMID * 4>(t_a + c * 4);
+        sc[q] = ds_read_f4<0>(t_a + c * 4);
+        sh[q] = ds_read_f4<CMID * 4>(t_a + c * 4);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc[q]), "+v"(sh[q])::"memory");   // (tied: the FMAs stay below)
@@ -432,15 +382,15 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
           float v[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            v[k] = bk_relu(fmaf(acc1[b][4 * q + k], sc[q][k], sh[q][k]));
+            v[k] = relu_keep_nan(fmaf(acc1[b][4 * q + k], sc[q][k], sh[q][k]));
             v[k] = ok ? v[k] : 0.f;
           }
-          bk_u2 h, l;
-          bk_split4(v, &h, &l);
-          if (q == 0) { bk_ds_write_b64<0>(row, h); bk_ds_write_b64<CMID * 2>(row, l); }
-          if (q == 1) { bk_ds_write_b64<16>(row, h); bk_ds_write_b64<CMID * 2 + 16>(row, l); }
-          if (q == 2) { bk_ds_write_b64<32>(row, h); bk_ds_write_b64<CMID * 2 + 32>(row, l); }
-          if (q == 3) { bk_ds_write_b64<48>(row, h); bk_ds_write_b64<CMID * 2 + 48>(row, l); }
+          u32x2 h, l;
+          split4(v, &h, &l);
+          if (q == 0) { ds_write_b64<0>(row, h); ds_write_b64<CMID * 2>(row, l); }
+          if (q == 1) { ds_write_b64<16>(row, h); ds_write_b64<CMID * 2 + 16>(row, l); }
+          if (q == 2) { ds_write_b64<32>(row, h); ds_write_b64<CMID * 2 + 32>(row, l); }
+          if (q == 3) { ds_write_b64<48>(row, h); ds_write_b64<CMID * 2 + 48>(row, l); }
         }
       }
     }
@@ -449,7 +399,7 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
     //      front of W(NK1 + 3): the first three steps of phase 2 count them as younger ----
     load_wc(frow_t, fh_t);
     // =============================== phase 2: conv3x3_b out of mid1 ===============================
-    bk_f32x16 acc2;
+    f32x16 acc2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
     // One barrier per TRIPLE of taps (a row of the 3 x 3 window of one 32-channel chunk): its three weight stages were requested
@@ -475,14 +425,14 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       for (int kx = 0; kx < 3; ++kx) {
         const unsigned sb = lds0 + G::OFF_B + (unsigned)((j0 + kx) % G::NRING) * B_STAGE;
         const unsigned ar = m1_base + (unsigned)(((mi2 + ky) * 32 + frow_t + kx) * MP + cc * 64 + fh_t * 16);
-        bk_f16x8 bh[2], bl[2], ah[2], al[2];
+        f16x8 bh[2], bl[2], ah[2], al[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          bh[ks] = bk_ds_read_h8<0>(sb + b_off[ks]);
-          bl[ks] = bk_ds_read_h8<B_PLANE>(sb + b_off[ks]);
+          bh[ks] = ds_read_h8<0>(sb + b_off[ks]);
+          bl[ks] = ds_read_h8<B_PLANE>(sb + b_off[ks]);
         }
-        ah[0] = bk_ds_read_h8<0>(ar); al[0] = bk_ds_read_h8<CMID * 2>(ar);
-        ah[1] = bk_ds_read_h8<32>(ar); al[1] = bk_ds_read_h8<CMID * 2 + 32>(ar);
+        ah[0] = ds_read_h8<0>(ar); al[0] = ds_read_h8<CMID * 2>(ar);
+        ah[1] = ds_read_h8<32>(ar); al[1] = ds_read_h8<CMID * 2 + 32>(ar);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(ah[0]), "+v"(al[0]), "+v"(ah[1]), "+v"(al[1])::"memory");
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -495,12 +445,12 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
     stamp();                                       // 4: phase 2 done
     // ---- epilogue 2: bn_c + ReLU, split -> mid2 (over the A tiles: nobody reads them any more) ----
     {
-      bk_f32x4 sc[4], sh[4];
+      f32x4 sc[4], sh[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c = nj2 * 32 + 8 * q + 4 * fh_t;
-        sc[q] = bk_ds_read_f4<0>(t_b + c * 4);
-        sh[q] = bk_ds_read_f4<CMID * 4>(t_b + c * 4);
+        sc[q] = ds_read_f4<0>(t_b + c * 4);
+        sh[q] = ds_read_f4<CMID * 4>(t_b + c * 4);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc[q]), "+v"(sh[q])::"memory");
@@ -509,13 +459,13 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       for (int q = 0; q < 4; ++q) {
         float v[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = bk_relu(fmaf(acc2[4 * q + k], sc[q][k], sh[q][k]));
-        bk_u2 h, l;
-        bk_split4(v, &h, &l);
-        if (q == 0) { bk_ds_write_b64<0>(row, h); bk_ds_write_b64<CMID * 2>(row, l); }
-        if (q == 1) { bk_ds_write_b64<16>(row, h); bk_ds_write_b64<CMID * 2 + 16>(row, l); }
-        if (q == 2) { bk_ds_write_b64<32>(row, h); bk_ds_write_b64<CMID * 2 + 32>(row, l); }
-        if (q == 3) { bk_ds_write_b64<48>(row, h); bk_ds_write_b64<CMID * 2 + 48>(row, l); }
+        for (int k = 0; k < 4; ++k) v[k] = relu_keep_nan(fmaf(acc2[4 * q + k], sc[q][k], sh[q][k]));
+        u32x2 h, l;
+        split4(v, &h, &l);
+        if (q == 0) { ds_write_b64<0>(row, h); ds_write_b64<CMID * 2>(row, l); }
+        if (q == 1) { ds_write_b64<16>(row, h); ds_write_b64<CMID * 2 + 16>(row, l); }
+        if (q == 2) { ds_write_b64<32>(row, h); ds_write_b64<CMID * 2 + 32>(row, l); }
+        if (q == 3) { ds_write_b64<48>(row, h); ds_write_b64<CMID * 2 + 48>(row, l); }
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");       // mid2 complete
@@ -537,7 +487,7 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
     }
     auto half = [&](auto HALF) {
       constexpr int i0 = decltype(HALF)::value * RH;
-      bk_f32x16 acc3[RH][NB3];
+      f32x16 acc3[RH][NB3];
 #pragma unroll
       for (int i = 0; i < RH; ++i)
 #pragma unroll
@@ -548,12 +498,12 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
       for (int kb = 0; kb < NCC2; ++kb)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          bk_f16x8 ah[RH], al[RH];
+          f16x8 ah[RH], al[RH];
 #pragma unroll
           for (int i = 0; i < RH; ++i) {
             const unsigned ar = m2_base + (unsigned)(((i0 + i) * 32 + frow_t) * MP + kb * 64 + (ks * 2 + fh_t) * 16);
-            ah[i] = bk_ds_read_h8<0>(ar);
-            al[i] = bk_ds_read_h8<CMID * 2>(ar);
+            ah[i] = ds_read_h8<0>(ar);
+            al[i] = ds_read_h8<CMID * 2>(ar);
           }
 #pragma unroll
           for (int i = 0; i < RH; ++i) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ah[i]), "+v"(al[i])::"memory");
@@ -587,43 +537,43 @@ __global__ __launch_bounds__(512) void resnet_bneck_kernel(BneckParams p) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c = (wave * NB3 + j) * 32 + 8 * q + 4 * fh_t;
-          bk_f32x4 sc = bk_ds_read_f4<0>(t_c + c * 4), sh = bk_ds_read_f4<COUT * 4>(t_c + c * 4);
-          bk_f32x4 psc = bk_ds_read_f4<2 * COUT * 4>(t_c + c * 4), psh = bk_ds_read_f4<3 * COUT * 4>(t_c + c * 4);
+          f32x4 sc = ds_read_f4<0>(t_c + c * 4), sh = ds_read_f4<COUT * 4>(t_c + c * 4);
+          f32x4 psc = ds_read_f4<2 * COUT * 4>(t_c + c * 4), psh = ds_read_f4<3 * COUT * 4>(t_c + c * 4);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc), "+v"(sh), "+v"(psc), "+v"(psh)::"memory");
 #pragma unroll
           for (int i = 0; i < RH; ++i) {
-            bk_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
               v[k] = fmaf(acc3[i][j][4 * q + k], sc[k], sh[k]);
               v[k] += res[i0 + i][j][q][k];
             }
             if (p.dbg == 1 || p.dbg == 2) {
-              bk_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+              f32x4 z = {0.f, 0.f, 0.f, 0.f};
               if ((wave * NB3 + j) * 32 < CMID) {
                 const unsigned base = p.dbg == 1 ? m1_base + (unsigned)(((i0 + i + 1) * 32 + frow_t + 1) * MP) : m2_base + (unsigned)(((i0 + i) * 32 + frow_t) * MP);
-                const bk_f16x4 hh = *reinterpret_cast<const bk_f16x4*>(smem + (base - lds0) + c * 2);
-                const bk_f16x4 ll = *reinterpret_cast<const bk_f16x4*>(smem + (base - lds0) + CMID * 2 + c * 2);
+                const f16x4 hh = *reinterpret_cast<const f16x4*>(smem + (base - lds0) + c * 2);
+                const f16x4 ll = *reinterpret_cast<const f16x4*>(smem + (base - lds0) + CMID * 2 + c * 2);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) z[k] = (float)hh[k] + (float)ll[k];
               }
               v = z;
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bk_u4, v), r_out, (int)o_vo[i0 + i], (j * 32 + 8 * q) * 4, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r_out, (int)o_vo[i0 + i], (j * 32 + 8 * q) * 4, 0);
             if (p.out_hi) {
               float tt[4];
 #pragma unroll
-              for (int k = 0; k < 4; ++k) tt[k] = bk_relu(fmaf(v[k], psc[k], psh[k]));
-              bk_u2 h, l;
-              bk_split4(tt, &h, &l);
+              for (int k = 0; k < 4; ++k) tt[k] = relu_keep_nan(fmaf(v[k], psc[k], psh[k]));
+              u32x2 h, l;
+              split4(tt, &h, &l);
               __builtin_amdgcn_raw_buffer_store_b64(h, r_ohi, (int)p_vo[i0 + i], j * 1024 + q * 16, 0);
               __builtin_amdgcn_raw_buffer_store_b64(l, r_olo, (int)p_vo[i0 + i], j * 1024 + q * 16, 0);
             }
           }
         }
     };
-    half(bk_int<0>{});
-    half(bk_int<1>{});
+    half(int_c<0>{});
+    half(int_c<1>{});
     stamp();                                       // 7: epilogue 3 issued
     if (p.dbg) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (mid2 was read above)
   }

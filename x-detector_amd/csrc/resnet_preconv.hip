@@ -17,16 +17,10 @@
 // group, the epilogue (bn_b + ReLU, split) stores 8 bytes per plane straight into the [pix/16][C/32][16][32] layout.
 // K order, product order and epilogue arithmetic are conv_dma_f16_kernel's: bit-identical (tests/test_gpu_resnet_bneck.py).
 #include "common.h"
+#include "cu_prims.h"
 #include <algorithm>
 
 namespace xdet {
-
-typedef float pc_f32x16 __attribute__((ext_vector_type(16)));
-typedef float pc_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 pc_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pc_f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned pc_u2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
 
 struct PreconvParams {
   const float* x;                           // [M][CIN] f32
@@ -36,41 +30,6 @@ struct PreconvParams {
   u16* out_hi; u16* out_lo;                 // planes [M/16][CMID/32][16][32]
   int M, ntiles;
 };
-
-template <int OFF>
-__device__ __forceinline__ pc_f16x8 pc_ds_read_h8(unsigned addr) {
-  pc_f16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ pc_f32x4 pc_ds_read_f4(unsigned addr) {
-  pc_f32x4 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ void pc_ds_write_b64(unsigned addr, pc_u2 v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ float pc_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }   // keeps NaN (conv_epilogue.h)
-__device__ __forceinline__ void pc_split4(const float (&t)[4], pc_u2* h, pc_u2* l) {
-  const _Float16 h0 = (_Float16)t[0], h1 = (_Float16)t[1], h2 = (_Float16)t[2], h3 = (_Float16)t[3];
-  const pc_f16x4 hv = {h0, h1, h2, h3};
-  const pc_f16x4 lv = {(_Float16)(t[0] - (float)h0), (_Float16)(t[1] - (float)h1), (_Float16)(t[2] - (float)h2),
-                       (_Float16)(t[3] - (float)h3)};
-  *h = __builtin_bit_cast(pc_u2, hv);
-  *l = __builtin_bit_cast(pc_u2, lv);
-}
-template <int V>
-struct pc_int { static constexpr int value = V; };
-template <int N, typename F, int I = 0>
-__device__ __forceinline__ void pc_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(pc_int<I>{});
-    pc_static_for<N, F, I + 1>(static_cast<F&&>(f));
-  }
-}
 
 template <int CMID, int CIN, int BM_>
 struct PreconvGeom {
@@ -155,27 +114,27 @@ __global__ __launch_bounds__(512) void resnet_preconv_kernel(PreconvParams p) {
       x_vo[q] = m < p.M ? ((unsigned)m * CIN + (unsigned)(g4 * 4)) * 4u : 0xffffffffu;
     }
   };
-  pc_f32x4 xr[3][XQ];
+  f32x4 xr[3][XQ];
   auto load_x = [&](int kt, auto SET) {
     constexpr int set = decltype(SET)::value;
 #pragma unroll
     for (int q = 0; q < XQ; ++q)
-      xr[set][q] = __builtin_bit_cast(pc_f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)x_vo[q], kt * 128, 0));
+      xr[set][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_x, (int)x_vo[q], kt * 128, 0));
   };
   auto transform = [&](int kt, auto SET) {
     constexpr int set = decltype(SET)::value;
-    pc_f32x4 sc = pc_ds_read_f4<0>(t_p + (kt * 32 + g4 * 4) * 4), sh = pc_ds_read_f4<CIN * 4>(t_p + (kt * 32 + g4 * 4) * 4);
+    f32x4 sc = ds_read_f4<0>(t_p + (kt * 32 + g4 * 4) * 4), sh = ds_read_f4<CIN * 4>(t_p + (kt * 32 + g4 * 4) * 4);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc), "+v"(sh)::"memory");
     const unsigned base = lds0 + G::OFF_A + (kt & 1) * A_STAGE;
 #pragma unroll
     for (int q = 0; q < XQ; ++q) {
       float t[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) t[k] = pc_relu(fmaf(xr[set][q][k], sc[k], sh[k]));
-      pc_u2 h, l;
-      pc_split4(t, &h, &l);
-      pc_ds_write_b64<0>(base + aw_off[q], h);
-      pc_ds_write_b64<A_PLANE>(base + aw_off[q], l);
+      for (int k = 0; k < 4; ++k) t[k] = relu_keep_nan(fmaf(xr[set][q][k], sc[k], sh[k]));
+      u32x2 h, l;
+      split4(t, &h, &l);
+      ds_write_b64<0>(base + aw_off[q], h);
+      ds_write_b64<A_PLANE>(base + aw_off[q], l);
     }
   };
   // fragments: this wave's row block mi = wave / WPM, column blocks (wave % WPM) * NBW + j
@@ -196,9 +155,9 @@ __global__ __launch_bounds__(512) void resnet_preconv_kernel(PreconvParams p) {
   tile_offsets(t_begin * BM);
   __syncthreads();
   auto prologue = [&]() {
-    load_x(0, pc_int<0>{}); issue_b(0);
-    load_x(1, pc_int<1>{}); issue_b(1);
-    load_x(2, pc_int<2>{}); issue_b(2);
+    load_x(0, int_c<0>{}); issue_b(0);
+    load_x(1, int_c<1>{}); issue_b(1);
+    load_x(2, int_c<2>{}); issue_b(2);
   };
   prologue();
 
@@ -207,29 +166,29 @@ __global__ __launch_bounds__(512) void resnet_preconv_kernel(PreconvParams p) {
     int frow_t = frow, fh_t = fh;
     asm volatile("" : "+v"(frow_t), "+v"(fh_t));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the prologue (older than the last tile's stores) has landed
-    transform(0, pc_int<0>{});
-    pc_f32x16 acc[NBW];
+    transform(0, int_c<0>{});
+    f32x16 acc[NBW];
 #pragma unroll
     for (int j = 0; j < NBW; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-    pc_static_for<NK>([&](auto KT) {
+    static_for<NK>([&](auto KT) {
       constexpr int kt = decltype(KT)::value;
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(G::younger_b(kt)) : "memory");
       if constexpr (kt + 3 < NK) {
-        load_x(kt + 3, pc_int<kt % 3>{});
+        load_x(kt + 3, int_c<kt % 3>{});
         issue_b(kt + 3);
       }
       const unsigned sa = lds0 + G::OFF_A + (kt & 1) * A_STAGE, sb = lds0 + G::OFF_B + (kt & 3) * B_STAGE;
-      pc_f16x8 ah[2], al[2], bh[2][NBW], bl[2][NBW];
+      f16x8 ah[2], al[2], bh[2][NBW], bl[2][NBW];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        ah[ks] = pc_ds_read_h8<0>(sa + a_off[ks]);
-        al[ks] = pc_ds_read_h8<A_PLANE>(sa + a_off[ks]);
+        ah[ks] = ds_read_h8<0>(sa + a_off[ks]);
+        al[ks] = ds_read_h8<A_PLANE>(sa + a_off[ks]);
 #pragma unroll
         for (int j = 0; j < NBW; ++j) {
-          bh[ks][j] = pc_ds_read_h8<0>(sb + b_off[ks][j]);
-          bl[ks][j] = pc_ds_read_h8<B_PLANE>(sb + b_off[ks][j]);
+          bh[ks][j] = ds_read_h8<0>(sb + b_off[ks][j]);
+          bl[ks][j] = ds_read_h8<B_PLANE>(sb + b_off[ks][j]);
         }
       }
 #pragma unroll
@@ -249,7 +208,7 @@ __global__ __launch_bounds__(512) void resnet_preconv_kernel(PreconvParams p) {
       }
       if constexpr (kt + 1 < NK) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::younger_x(kt)) : "memory");
-        transform(kt + 1, pc_int<(kt + 1) % 3>{});
+        transform(kt + 1, int_c<(kt + 1) % 3>{});
       }
     });
     // every wave is done with the ring and the A tiles: the next tile's first loads travel under this tile's epilogue
@@ -267,13 +226,13 @@ __global__ __launch_bounds__(512) void resnet_preconv_kernel(PreconvParams p) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c = (nh * NBW + j) * 32 + 8 * q + 4 * fh_t;
-          pc_f32x4 sc = pc_ds_read_f4<0>(t_e + c * 4), sh = pc_ds_read_f4<CMID * 4>(t_e + c * 4);
+          f32x4 sc = ds_read_f4<0>(t_e + c * 4), sh = ds_read_f4<CMID * 4>(t_e + c * 4);
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sc), "+v"(sh)::"memory");
           float v[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) v[k] = pc_relu(fmaf(acc[j][4 * q + k], sc[k], sh[k]));
-          pc_u2 h, l;
-          pc_split4(v, &h, &l);
+          for (int k = 0; k < 4; ++k) v[k] = relu_keep_nan(fmaf(acc[j][4 * q + k], sc[k], sh[k]));
+          u32x2 h, l;
+          split4(v, &h, &l);
           __builtin_amdgcn_raw_buffer_store_b64(h, r_ohi, (int)pbase, ((nh * NBW + j) << 10) + q * 16, 0);
           __builtin_amdgcn_raw_buffer_store_b64(l, r_olo, (int)pbase, ((nh * NBW + j) << 10) + q * 16, 0);
         }

@@ -18,14 +18,10 @@
 // K order (tap * 4 + channel, ascending, taps 49..55 zero weights), product order (lo*hi, hi*lo, hi*hi per 16-deep half)
 // and the epilogue's fma are those of conv_mfma_f16_kernel<128, 64, 4, 1, true, 3>: bit-identical (tests/test_gpu_resnet_bneck.py).
 #include "common.h"
+#include "cu_prims.h"
 #include <algorithm>
 
 namespace xdet {
-
-typedef float rs_f32x16 __attribute__((ext_vector_type(16)));
-typedef float rs_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 rs_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 
 constexpr int RS_TR = 8, RS_TC = 32;                 // output rows x columns of a tile
 constexpr int RS_PR = 2 * RS_TR + 5, RS_PC = 2 * RS_TC + 5;   // patch rows x columns (21 x 69)
@@ -36,8 +32,7 @@ constexpr int RS_W_B = 64 * RS_WP;                   // bytes per filter plane
 constexpr int RS_NPIX = (RS_PR * RS_PC + 511) / 512; // patch pixels per thread (3)
 constexpr int RS_LDS = 2 * RS_PATCH_B + 2 * RS_W_B;
 
-typedef unsigned rs_u4 __attribute__((ext_vector_type(4)));
-
+// Not split4 (cu_prims.h): the v_fma_mix form, sf_split4 of sepconv_fused.hip on a float4 -- the same bits.
 // (one asm block: gfx950 wants a wait state between a half-register write and a VALU read of the register, and inline asm is
 //  opaque to the hazard recogniser -- see sf_split4)
 __device__ __forceinline__ void rs_split4(const float4 a, uint2* h, uint2* l) {
@@ -130,7 +125,7 @@ __global__ __launch_bounds__(512) void resnet_stem7x7_kernel(ResnetStemParams p)
     const bool more = t + GW < t_end;
     const Coord nxt = decode(min(t + GW, p.ntiles - 1));
     if (more) load_patch(nxt);                     // the next tile's pixels travel under this tile's MFMAs
-    rs_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -153,13 +148,13 @@ __global__ __launch_bounds__(512) void resnet_stem7x7_kernel(ResnetStemParams p)
       uint2 h0, l0, h1, l1;
       rs_split4(v0, &h0, &l0);
       rs_split4(v1, &h1, &l1);
-      const rs_u4 hq = {h0.x, h0.y, h1.x, h1.y}, lq = {l0.x, l0.y, l1.x, l1.y};
-      const rs_f16x8 ah = __builtin_bit_cast(rs_f16x8, hq), al = __builtin_bit_cast(rs_f16x8, lq);
-      rs_f16x8 bh[2], bl[2];
+      const u32x4 hq = {h0.x, h0.y, h1.x, h1.y}, lq = {l0.x, l0.y, l1.x, l1.y};
+      const f16x8 ah = __builtin_bit_cast(f16x8, hq), al = __builtin_bit_cast(f16x8, lq);
+      f16x8 bh[2], bl[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        bh[j] = *reinterpret_cast<const rs_f16x8*>(w_base + j * 32 * RS_WP + kk * 32);
-        bl[j] = *reinterpret_cast<const rs_f16x8*>(w_base + RS_W_B + j * 32 * RS_WP + kk * 32);
+        bh[j] = *reinterpret_cast<const f16x8*>(w_base + j * 32 * RS_WP + kk * 32);
+        bl[j] = *reinterpret_cast<const f16x8*>(w_base + RS_W_B + j * 32 * RS_WP + kk * 32);
       }
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[j], acc[j], 0, 0, 0);

@@ -16,6 +16,7 @@
 // Rounds 2-4 ran the phases back to back on four waves, two workgroups per CU (git history; the same-box A/B against
 // that library is in profiles/r05_ab_lines.txt); round 5: sepconv_pc_kernel below.
 #include "common.h"
+#include "cu_prims.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -42,12 +43,6 @@ constexpr bool SF_DO_STORE = SF_PROBE_LEVEL == 0 || SF_PROBE_LEVEL == 4 || SF_PR
 #else
 #define SF_STAMP(slot) do {} while (0)
 #endif
-
-typedef float sf_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 sf_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sf_f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-typedef unsigned sf_u2 __attribute__((ext_vector_type(2)));
 
 constexpr int SF_R = 4, SF_X = 30, SF_P = 32;       // tile rows, tile width, patch pitch (pixels)
 constexpr int SF_ROWS = SF_R + 2;                   // patch rows
@@ -80,34 +75,9 @@ struct SepFusedParams {
 #endif
 };
 
-// LDS accesses issued while the patch prefetch (an LDS-writing DMA) is in flight.  The compiler cannot tell
-// that they never alias the DMA's target buffer and would drain vmcnt(0) in front of every one of them
-// (stalling on the prefetch each chunk), so they are issued as inline asm with explicit lgkmcnt waits.
-typedef __attribute__((address_space(3))) void* sf_lds_ptr;
-__device__ __forceinline__ unsigned sf_lds_addr(const void* p) {
-  return (unsigned)(size_t)(sf_lds_ptr)(p);
-}
-template <int OFF>
-__device__ __forceinline__ void sf_ds_write_b64(unsigned addr, uint2 v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-typedef float sf_f32x4 __attribute__((ext_vector_type(4)));
-typedef float sf_f32x2 __attribute__((ext_vector_type(2)));
-template <int OFF>
-__device__ __forceinline__ sf_f32x4 sf_ds_read_f4(unsigned addr) {
-  sf_f32x4 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ sf_f16x8 sf_ds_read_b128(unsigned addr) {
-  sf_f16x8 r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-  return r;
-}
-
-// ReLU of a value that came out of an asm LDS read.  fmaxf() would first canonicalise it (a second v_max_f32 per
-// element: the compiler cannot know it is not a signalling NaN) -- 72 extra VALU instructions per 32-channel chunk.
+// Not relu_keep_nan (cu_prims.h): one asm v_max_f32, for a value that came out of an asm LDS read.  fmaxf() and the
+// builtin maximum would first canonicalise it (a second v_max_f32 per element: the compiler cannot know it is not a
+// signalling NaN) -- 72 extra VALU instructions per 32-channel chunk.
 __device__ __forceinline__ float sf_relu(float x) {
   float r;
   asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
@@ -118,10 +88,11 @@ __device__ __forceinline__ float sf_relu(float x) {
 // computes then hold every window of its 14 pooled columns (window k = local columns 2k .. 2k+2).
 constexpr int SF_XP = 28;
 
+// Not split4 (cu_prims.h): the same bits from other instructions.
 // hi = f16(a), lo = f16(a - float(hi)) of four values, as two packed pairs each.  v_fma_mixlo/hi_f16 take the f16 hi half
 // straight as an fma operand and round the f32 difference (exact: it has at most 13 significant bits) to f16 into one
 // half of the destination: one instruction per value where convert-back + subtract + convert were two -- the same bits.
-__device__ __forceinline__ void sf_split4(sf_f32x4 a, uint2* h, uint2* l) {
+__device__ __forceinline__ void sf_split4(f32x4 a, uint2* h, uint2* l) {
   // ONE asm block: inline asm is opaque to the hazard recogniser, and gfx950 wants a wait state between a half-register
   // write (v_fma_mixlo / mixhi) and a VALU that reads the register -- the order below keeps another instruction between
   // the two halves of each lo word, the trailing s_nop covers whatever the compiler places behind the block
@@ -266,12 +237,12 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
     unsigned wa_k[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      wa_k[k] = sf_lds_addr(&s_a[0][0]) +
+      wa_k[k] = lds_addr(&s_a[0][0]) +
                 (unsigned)((wave * 32 + (strip & 4) * 4 + k * 4 + (strip & 3)) * 32 + (((c4 >> 1) ^ k) << 3) + (c4 & 1) * 4) * 2u;
     const unsigned t_rel = (unsigned)((wave * SF_ROW_F + pxb * 32 + (pxb >> 3) * 32 + c4 * 4) * 4);
     const unsigned hi_rel = 512u + ((pxb & 7) == 4 ? 128u : 0u);
-    const unsigned patch0 = sf_lds_addr(&s_patch[0][0]);
-    const unsigned w_base = sf_lds_addr(s_w) + (unsigned)(c4 * 4 * 4);
+    const unsigned patch0 = lds_addr(&s_patch[0][0]);
+    const unsigned w_base = lds_addr(s_w) + (unsigned)(c4 * 4 * 4);
 
     int rslot = 0, abuf = 0, pchunk = 0;
     for (int s = 0; s < total; ++s) {
@@ -290,20 +261,20 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
       const unsigned t_hi = t_addr + hi_rel;
       const unsigned w_addr = w_base + (unsigned)(pchunk * 32 * 4);
       const unsigned wa_off = (unsigned)abuf * 16384u;
-      sf_f32x4 a[4];
+      f32x4 a[4];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) a[k] = (sf_f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int k = 0; k < 4; ++k) a[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
       // the reads of a patch row (six pixels, three taps) are issued one row ahead of the row being filtered and
       // consumed behind counted lgkmcnt waits (LDS returns in order; the counter has four bits: <= 15 in flight)
-      sf_f32x4 col[3][6], ww[3][3];
+      f32x4 col[3][6], ww[3][3];
       auto read_row = [&](auto KY) {
         constexpr int ky = decltype(KY)::value;
         const unsigned ra = t_addr + ky * (SF_ROW_F * 4), rb = t_hi + ky * (SF_ROW_F * 4);
-        col[ky][0] = sf_ds_read_f4<0>(ra);   col[ky][1] = sf_ds_read_f4<128>(ra); col[ky][2] = sf_ds_read_f4<256>(ra);
-        col[ky][3] = sf_ds_read_f4<384>(ra); col[ky][4] = sf_ds_read_f4<0>(rb);   col[ky][5] = sf_ds_read_f4<128>(rb);
-        ww[ky][0] = sf_ds_read_f4<(ky * 3 + 0) * SF_KMAX * 4>(w_addr);
-        ww[ky][1] = sf_ds_read_f4<(ky * 3 + 1) * SF_KMAX * 4>(w_addr);
-        ww[ky][2] = sf_ds_read_f4<(ky * 3 + 2) * SF_KMAX * 4>(w_addr);
+        col[ky][0] = ds_read_f4<0>(ra);   col[ky][1] = ds_read_f4<128>(ra); col[ky][2] = ds_read_f4<256>(ra);
+        col[ky][3] = ds_read_f4<384>(ra); col[ky][4] = ds_read_f4<0>(rb);   col[ky][5] = ds_read_f4<128>(rb);
+        ww[ky][0] = ds_read_f4<(ky * 3 + 0) * SF_KMAX * 4>(w_addr);
+        ww[ky][1] = ds_read_f4<(ky * 3 + 1) * SF_KMAX * 4>(w_addr);
+        ww[ky][2] = ds_read_f4<(ky * 3 + 2) * SF_KMAX * 4>(w_addr);
       };
       auto fma_row = [&](auto KY, auto PENDING) {
         constexpr int ky = decltype(KY)::value;
@@ -325,11 +296,11 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const sf_f32x2 c_lo = __builtin_shufflevector(col[ky][k + kx], col[ky][k + kx], 0, 1);
-            const sf_f32x2 c_hi = __builtin_shufflevector(col[ky][k + kx], col[ky][k + kx], 2, 3);
-            const sf_f32x2 w_lo = __builtin_shufflevector(ww[ky][kx], ww[ky][kx], 0, 1);
-            const sf_f32x2 w_hi = __builtin_shufflevector(ww[ky][kx], ww[ky][kx], 2, 3);
-            sf_f32x2 a_lo = __builtin_shufflevector(a[k], a[k], 0, 1), a_hi = __builtin_shufflevector(a[k], a[k], 2, 3);
+            const f32x2 c_lo = __builtin_shufflevector(col[ky][k + kx], col[ky][k + kx], 0, 1);
+            const f32x2 c_hi = __builtin_shufflevector(col[ky][k + kx], col[ky][k + kx], 2, 3);
+            const f32x2 w_lo = __builtin_shufflevector(ww[ky][kx], ww[ky][kx], 0, 1);
+            const f32x2 w_hi = __builtin_shufflevector(ww[ky][kx], ww[ky][kx], 2, 3);
+            f32x2 a_lo = __builtin_shufflevector(a[k], a[k], 0, 1), a_hi = __builtin_shufflevector(a[k], a[k], 2, 3);
             a_lo = __builtin_elementwise_fma(c_lo, w_lo, a_lo);
             a_hi = __builtin_elementwise_fma(c_hi, w_hi, a_hi);
             a[k] = __builtin_shufflevector(a_lo, a_hi, 0, 1, 2, 3);
@@ -348,8 +319,8 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
       for (int k = 0; k < 4; ++k) {
         uint2 h, l;
         sf_split4(a[k], &h, &l);
-        sf_ds_write_b64<0>(wa_k[k] + wa_off, h);
-        if (SPLIT3) sf_ds_write_b64<8192>(wa_k[k] + wa_off, l);
+        ds_write_b64<0>(wa_k[k] + wa_off, h);
+        if (SPLIT3) ds_write_b64<8192>(wa_k[k] + wa_off, l);
       }
       SF_STAMP(3);                                   // stencil + A-tile writes issued
       rslot = rslot == NSLOT - 1 ? 0 : rslot + 1;
@@ -372,9 +343,9 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const int slot = wm * TM * 32 + ((frow & 16) | ((frow & 3) << 2) | ((frow >> 2) & 3));
-    a_rd[ks] = sf_lds_addr(&s_a[0][0]) + (unsigned)(slot * 32 + (((ks * 2 + fh) ^ (frow & 3)) << 3)) * 2u;
+    a_rd[ks] = lds_addr(&s_a[0][0]) + (unsigned)(slot * 32 + (((ks * 2 + fh) ^ (frow & 3)) << 3)) * 2u;
   }
-  sf_f32x16 acc[TM][2];
+  f32x16 acc[TM][2];
   // Pointwise weights: L2 -> registers, one 16-deep half at a time, requested as soon as the half's registers are free
   // (right behind its MFMAs) for the NEXT step -- half a step + the barrier ahead of their use.  Loads and waits are
   // inline asm: left to the compiler, the first MFMA of a step sat behind `s_waitcnt vmcnt(0)` (loop-carried loads
@@ -382,7 +353,7 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
   // and every step paid an L2 round trip.  vmcnt retires in order: with NB loads per half, `vmcnt(NB)` in front of a
   // half's MFMAs leaves exactly the other half's loads in flight (a tile's last step also waits for its stores).
   constexpr int NB = SPLIT3 ? 4 : 2;
-  sf_f16x8 bh[2][2], bl[2][2];
+  f16x8 bh[2][2], bl[2][2];
   const unsigned bvoff = (unsigned)(((wn * 64 + frow) * 32 + fh * 8) * 2);                // bytes; j: + 2048, ks: + 32
 #define SF_LOAD_B(dst, base, imm) \
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(bvoff), "s"(base), "n"(imm) : "memory")
@@ -433,11 +404,11 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
     const int nn0 = nxt.nt * BN;
     const unsigned aoff = (unsigned)((s - 1) & 1) * 16384u;
     auto half = [&](const int ks) {
-      sf_f16x8 ah[TM], al[TM];
+      f16x8 ah[TM], al[TM];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        ah[i] = sf_ds_read_b128<0>(a_rd[ks] + aoff + i * 2048);
-        if (SPLIT3) al[i] = sf_ds_read_b128<128 * 64>(a_rd[ks] + aoff + i * 2048);
+        ah[i] = ds_read_h8<0>(a_rd[ks] + aoff + i * 2048);
+        if (SPLIT3) al[i] = ds_read_h8<128 * 64>(a_rd[ks] + aoff + i * 2048);
       }
 #pragma unroll
       for (int i = 0; i < TM; i += 2) {

@@ -34,4 +34,21 @@ __host__ __device__ __forceinline__ unsigned tg_unmix(unsigned x) {
   return x;
 }
 
+// ascending bitonic sort of P (a power of two) distinct 64-bit words (keys carrying their elements) in LDS, by all THREADS
+// threads of the workgroup; ends with a barrier
+template <int THREADS>
+__device__ void lds_bitonic_sort_u64(unsigned long long* s, int P) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < P; i += THREADS) {
+        const int p = i ^ j;
+        if (p > i) {
+          const unsigned long long x = s[i], y = s[p];
+          if ((x > y) == ((i & k) == 0)) { s[i] = y; s[p] = x; }
+        }
+      }
+      __syncthreads();
+    }
+}
+
 }  // namespace xdet

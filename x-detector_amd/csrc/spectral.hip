@@ -23,24 +23,24 @@
 // come through the scalar cache.  One thread owns 4 channels of one line; a wave covers 8 lines x 32
 // channels, so every load/store instruction moves 8 x 128 B (f32) or one contiguous 512 B (planes).
 #include "common.h"
+#include "cu_prims.h"
 
 #include <cmath>
 #include <vector>
 
 namespace xdet {
 
-typedef _Float16 sp_f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
-
 __device__ __forceinline__ size_t sp_blocked_off(size_t pix, int c, int c32n) {
   return (((pix >> 4) * (size_t)c32n + (size_t)(c >> 5)) << 9) + ((pix & 15) << 5) + (size_t)(c & 31);
 }
 
+// Not split4 (cu_prims.h): the same expression, stored through the __restrict__ plane pointers (through split4's plain
+// uint2* arguments the compiler schedules dft_fwd_kernel differently)
 __device__ __forceinline__ void sp_store_split(u16* __restrict__ hi, u16* __restrict__ lo, size_t off, const float4 v) {
   const _Float16 h0 = (_Float16)v.x, h1 = (_Float16)v.y, h2 = (_Float16)v.z, h3 = (_Float16)v.w;
-  sp_f16x4 hv = {h0, h1, h2, h3};
-  sp_f16x4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
-                 (_Float16)(v.w - (float)h3)};
+  f16x4 hv = {h0, h1, h2, h3};
+  f16x4 lv = {(_Float16)(v.x - (float)h0), (_Float16)(v.y - (float)h1), (_Float16)(v.z - (float)h2),
+              (_Float16)(v.w - (float)h3)};
   *reinterpret_cast<uint2*>(hi + off) = *reinterpret_cast<uint2*>(&hv);
   *reinterpret_cast<uint2*>(lo + off) = *reinterpret_cast<uint2*>(&lv);
 }

@@ -256,21 +256,6 @@ __device__ __forceinline__ unsigned long long tg_key(unsigned image_word, unsign
   return ((unsigned long long)tg_mix(image_word ^ (2u * element + stream)) << 32) | element;
 }
 
-// ascending bitonic sort of P (a power of two) distinct 64-bit words in LDS, all TG_ST threads
-__device__ void tg_sort(unsigned long long* s, int P) {
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < P; i += TG_ST) {
-        const int p = i ^ j;
-        if (p > i) {
-          const unsigned long long x = s[i], y = s[p];
-          if ((x > y) == ((i & k) == 0)) { s[i] = y; s[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 // the members of class `cls` among seq[0 .. len) in sequence order, the first `take` of them, to keep[base ...]
 // (seq == NULL: the identity sequence).  All TG_ST threads; s_wave: TG_ST / 64 + 1 ints.
 __device__ void tg_take(const unsigned long long* seq, int len, const unsigned char* s_cls, int cls, int take, int* keep, int base,
@@ -353,7 +338,7 @@ __global__ __launch_bounds__(TG_ST) void tg_sample_kernel(TgSample p, TgWorkspac
   const bool bg_all = n_neg < exp_bg;
   const int n_bg = bg_all ? n_neg : exp_bg;
   const int n_keep = n_fg + n_bg;
-  if (!fg_all || !bg_all) tg_sort(s_sort, p.P);            // (block-uniform; the padding words sort behind the Mn real ones)
+  if (!fg_all || !bg_all) lds_bitonic_sort_u64<TG_ST>(s_sort, p.P);            // (block-uniform; the padding words sort behind the Mn real ones)
   tg_take(fg_all ? nullptr : s_sort, Mn, s_cls, 1, n_fg, s_keep, 0, s_wave);
   tg_take(bg_all ? nullptr : s_sort, Mn, s_cls, 2, n_bg, s_keep, n_fg, s_wave);
   __syncthreads();
@@ -372,7 +357,7 @@ __global__ __launch_bounds__(TG_ST) void tg_sample_kernel(TgSample p, TgWorkspac
       while (P2 < n_keep) P2 <<= 1;
       for (int i = tid; i < P2; i += TG_ST) s_sort[i] = i < n_keep ? tg_key(word, (unsigned)i, 1u) : ~0ull;
       __syncthreads();
-      tg_sort(s_sort, P2);
+      lds_bitonic_sort_u64<TG_ST>(s_sort, P2);
     }
   }
   for (int j = tid; j < p.rpi; j += TG_ST) {
