@@ -494,6 +494,40 @@ int xdet_head_loss(const float* cls_reg, int ld, int cls_off, int reg_off, int N
                    const float* targets, float fg_ratio, int ohem_k, float sigma, void* workspace, float* losses, float* per_roi,
                    int32_t* select, float* grad_cls_reg, void* stream);
 
+/* ---- the backward of a dense layer y = act(x W + b), act = identity or ReLU (csrc/dense_backward.hip; the NumPy statement
+ * of the same contract is xdet.ops.host_dense_backward) -----------------------------------------------------------------
+ *   x  f32 [M,K], row stride ld_x          the layer's input
+ *   w  f32 [K,J] dense, row-major          the kernel as the checkpoint stores it ([in, out]), on the device
+ *   y  f32 [M,J], row stride ld_y, or NULL the forward's output AFTER its ReLU; NULL for a layer without one
+ *   dy f32 [M,J], row stride ld_dy         d loss / d y
+ *     g  = dy                  if y is NULL
+ *        = y > 0 ? dy : 0      otherwise: exact zeros of y mask, and so does a NaN in y (NaN > 0 is false: the gradient
+ *                              behind a NaN activation is 0, whatever dy holds there)
+ *   -> dx f32 [M,K], row stride ld_dx = g W^T (NULL: skipped);  dw f32 [K,J] dense = x^T g;  db f32 [J] = column sums of g.
+ * Columns at or beyond a matrix's width (K for x and dx, J for y and dy) are never read -- padding may hold NaN -- and
+ * nothing is written to dx beyond column K - 1.  The detector's buffers go in as they are: dy = the gradient xdet_head_loss
+ * wrote (ld of "cls_reg", J = C + 4), x = "fc"; then dy = that call's dx, y = "fc", x = "pooled".
+ * Arithmetic: both products on the matrix pipe in split precision: every operand value v is hi = f16(v), lo = f16(v - hi),
+ *   a product is hi*hi + hi*lo + lo*hi accumulated in f32 (lo*lo, below 2^-22 of the product, is dropped).  Before the split
+ *   each of x, w and g is multiplied by a power of two of its own, 2^(11 - floor(log2(max |v|))) over the operand (columns
+ *   inside the width only; 2^0 for an all-zero operand), which a pre-pass finds on the device; the results are multiplied
+ *   by the inverse powers.  Both steps are exact, so gradients far below the f16 range keep f32-class accuracy, and scaling
+ *   dy by a power of two scales dx, dw and db by exactly that power (bit for bit, short of f32 underflow).  An operand holding
+ *   an inf or a NaN makes the outputs it reaches NaN.  db is summed in f32.
+ * Order of the sums: dw's sum over the M rows is cut into ranges of
+ *     rows_per_range = round_up(ceil(M / max(1, 512 / tiles)), 128),  tiles = ceil(K / 128) * ceil(J / (J <= 32 ? 32 : 128))
+ *   rows (integer divisions), each summed on its own and the ranges then added in index order; db is summed over chunks of
+ *   max(64, ceil(M / 1024)) rows in row order, the chunks then added in index order.  No float atomics: the same call gives
+ *   the same bits; rows computed from batches of different M are not required to agree bit for bit.
+ * workspace: xdet_dense_backward_workspace_bytes(M, K, J) bytes (never 0 for sizes inside the limits, 0 outside them); it
+ *   needs no initialisation and may be larger.  The call does not synchronise and reads nothing on the host.
+ * Limits: K, J <= 4096, M * max(K, J) < 2^31.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, ld_x < K, ld_dy < J, ld_y < J with
+ *   a y, ld_dx < K with a dx, a NULL x, w, dy, dw, db or workspace. */
+size_t xdet_dense_backward_workspace_bytes(int M, int K, int J);
+int xdet_dense_backward(const float* x, int ld_x, const float* w, const float* y, int ld_y, const float* dy, int ld_dy, int M,
+                        int K, int J, float* dx, int ld_dx, float* dw, float* db, void* workspace, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

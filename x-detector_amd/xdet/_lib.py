@@ -135,6 +135,9 @@ SIGNATURES = {
                               c_float, c_void_p, PI, PI, PF, PF, c_void_p]),
     'xdet_head_loss': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, c_int, PI, PF, c_float, c_int, c_float, c_void_p, PF, PF,
                                PI, PF, c_void_p]),
+    'xdet_dense_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'xdet_dense_backward': (c_int, [PF, c_int, PF, PF, c_int, PF, c_int, c_int, c_int, c_int, PF, c_int, PF, PF, c_void_p,
+                                    c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),

@@ -28,6 +28,7 @@ SOURCES = [
     ('evalmatch.hip', ['-ffp-contract=off']),
     ('targets.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
+    ('dense_backward.hip', []),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

@@ -221,7 +221,8 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
                          g_cls, g_loc)
 
 
-def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=1., num_classes=None, with_grad=True, stream=None):
+def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=1., num_classes=None, with_grad=True, stream=None,
+              device_grad=None):
     """host_head_loss on the GPU (xdet_head_loss), the same results.  cls_score [N,P,C] / bboxes_reg [N,P,4] as NumPy arrays;
     or cls_score = the detector's `cls_reg` DeviceTensor ([N,P,1,C+4]: C class logits, then the 4 regression outputs) with
     bboxes_reg None -- read in place.  labels [N,P] / targets [N,P,4]: NumPy or device buffers (as xdet_encode_rois wrote
@@ -268,6 +269,8 @@ def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=
     if with_grad:
         g = to_host(d_grad.ptr, (N, P, ld), f32)
         g_cls, g_reg = np.ascontiguousarray(g[..., :C]), np.ascontiguousarray(g[..., C:C + 4])
+        if device_grad is not None:
+            device_grad.append(DeviceTensor(d_grad.ptr, (N, P, 1, C + 4), ld, owner=d_grad))
     return HeadLossResult(to_host(d_loss.ptr, (3,), f32), to_host(d_per.ptr, (N, P), f32), to_host(d_sel.ptr, (N, K), np.int32),
                           g_cls, g_reg)
 
@@ -276,14 +279,18 @@ class HeadLoss(object):
     """The `loss_func` of model.get_head(..., is_training=True): the sampled ROIs' labels [N,P] and targets [N,P,4]
     (what the encode_fn of get_proposals returned) and fg_ratio, as the reference's lambda closes over them
     (light_head_rfcn_train.py:407).  Calling it with the head's outputs gives the HeadLossResult; get_head leaves the last
-    one in `.result` (losses, per_roi, select and the gradients) and returns the scalar."""
+    one in `.result` (losses, per_roi, select and the gradients) and returns the scalar; `.grad_device` is d loss / d cls_reg
+    on the GPU, in the `cls_reg` buffer's layout (model.head_backward reads it)."""
 
     def __init__(self, labels, targets, fg_ratio, sigma=1.):
         self.labels, self.targets, self.fg_ratio, self.sigma = labels, targets, fg_ratio, sigma
         self.result = None
+        self.grad_device = None
 
     def __call__(self, cls_score, bboxes_reg=None, ohem_k=0, num_classes=None, stream=None):
         labels = self.labels if hasattr(self.labels, 'ptr') else np.asarray(self.labels).astype(np.int32)
+        kept = []
         self.result = head_loss(cls_score, bboxes_reg, labels, self.targets, self.fg_ratio, ohem_k, self.sigma, num_classes,
-                                stream=stream)
+                                stream=stream, device_grad=kept)
+        self.grad_device = kept[0] if kept else None
         return self.result

@@ -40,8 +40,11 @@ class LightHeadDetector(object):
         h = c_void_p()
         check(lib().xdet_net_create(ctypes.byref(h), ctypes.byref(self.cfg)))
         self.handle = h
+        self._head_kernels = {}            # the dense layers' kernels as the checkpoint stores them (head_backward)
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, np.float32)
+            if name in ('final_head/subnet_fc/kernel', 'final_head/fc_cls/kernel', 'final_head/fc_loc/kernel'):
+                self._head_kernels[name] = a
             dims = (ctypes.c_int64 * a.ndim)(*a.shape)
             check(lib().xdet_net_set_weight(self.handle, name.encode(), _host(a), a.ndim, dims))
         check(lib().xdet_net_set_option(self.handle, b'large_sep', large_sep.encode()))
@@ -453,7 +456,7 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
     -> the scalar head loss; losses, per-ROI values, the selection and d loss / d cls_reg are in loss_func.result.  The head's
     row count is fixed when the detector is built: proposals_bboxes.shape[1] must equal its rpn_post_nms_top_n (a head detector
     built with rpn_post_nms_top_n = the ROIs sampled per image).  `pooling_op` is accepted for signature parity; the fused HIP
-    PsRoiAlign is always used.  The backward of the dense layers is not part of this package."""
+    PsRoiAlign is always used.  head_backward(loss_func) takes the gradient from there through the two dense layers."""
     d = _det()
     if (grid_width, grid_height) != (d.cfg.grid, d.cfg.grid) or num_classes != d.cfg.num_classes:
         raise InvalidArgumentError(-1, 'get_head: grid %dx%d / %d classes but the detector was built with %dx%d / %d'
@@ -479,3 +482,43 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
         return float(res.losses[0])
     cr = d.buffer('cls_reg', n).numpy().reshape(n, d.R, -1)
     return cr[..., :num_classes], cr[..., num_classes:num_classes + 4]
+
+
+def head_backward(loss_func):
+    """The backward of the head's dense layers, called after get_head(..., is_training=True, ...) on the same detector:
+    d loss / d cls_reg (loss_func.grad_device, what xdet_head_loss wrote) goes through `fc_cls+fc_loc` (x = the net's `fc`
+    buffer, the concatenated [2048, nc + 4] kernel) and then, masked by fc's ReLU, through `subnet_fc` (x = `pooled`) -- two
+    calls of xdet_dense_backward on the net's buffers with their own ld.  -> a dict with the six gradients under the
+    checkpoint's variable names (final_head/{subnet_fc,fc_cls,fc_loc}/{kernel,bias}, NumPy) and 'pooled': d loss / d pooled
+    as a DeviceTensor [N,R,1,C] ([N * R, C] rows, ld C) and 'fc': d loss / d fc (in front of fc's ReLU mask) likewise.  Where it goes from there (PsRoiAlignGrad) is the caller's."""
+    from . import ops
+    d = _det()
+    g = getattr(loss_func, 'grad_device', None)
+    if getattr(loss_func, 'result', None) is None or g is None:
+        raise InvalidArgumentError(-1, 'head_backward: the losses ran without a gradient (call get_head(..., is_training=True, '
+                                       '...) with this loss_func first)')
+    n, nc = g.shape[0], d.cfg.num_classes
+    if (g.shape[1], g.shape[3]) != (d.R, nc + 4) or n > d.max_batch:
+        raise InvalidArgumentError(-1, 'head_backward: gradient of shape %r but the detector has %d ROIs per image, %d classes, '
+                                       'max_batch %d' % (g.shape, d.R, nc, d.max_batch))
+    if len(d._head_kernels) != 3:
+        raise InvalidArgumentError(-1, 'head_backward: the detector was built without the final_head kernels')
+    if not hasattr(d, '_head_kernels_dev'):
+        k0 = d._head_kernels['final_head/subnet_fc/kernel']
+        k1 = np.concatenate([d._head_kernels['final_head/fc_cls/kernel'], d._head_kernels['final_head/fc_loc/kernel']], axis=1)
+        d._head_kernels_dev = []
+        for k in (k0, np.ascontiguousarray(k1)):
+            b = to_device(k)
+            d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
+    w0, w1 = d._head_kernels_dev
+    fc, pooled = d.buffer('fc', n), d.buffer('pooled', n)
+    dx1, dw1, db1 = ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
+    dx0, dw0, db0 = ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
+    _sync(d)
+    K0, K1 = w0.shape[0], w1.shape[0]
+    kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
+    return {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
+            'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
+            'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy(),
+            'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
+            'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)}

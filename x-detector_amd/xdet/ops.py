@@ -657,3 +657,80 @@ def light_head_preprocess_for_test(image, out_shape, data_format='NHWC', resize=
     """preprocessing/common_preprocessing.py:442-458.  (The reference accepts `resize` here but always warps; this
     applies it -- the default is the same.)"""
     return light_head_preprocess_for_eval(image, None, None, out_shape, data_format, resize=resize, stream=stream)[0]
+
+
+# ---- the backward of a dense layer (xdet_dense_backward, csrc/dense_backward.hip) -------------------------------------
+
+def host_dense_backward(x, w, dy, y=None, dtype=np.float32, with_dx=True):
+    """The NumPy statement of xdet_dense_backward (include/xdet.h) for a layer y = act(x w + b): x [M,K], w [K,J], dy [M,J],
+    y [M,J] the forward's output after its ReLU (None: no ReLU) -> (dx [M,K] = g w^T, dw [K,J] = x^T g, db [J] = column
+    sums of g) with g = dy, or dy where y > 0 and 0 elsewhere (an exact zero and a NaN in y both give 0).  dtype float32,
+    or float64: the accuracy yardstick.  with_dx=False: dx is None."""
+    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
+    g = dy
+    if y is not None:
+        with np.errstate(invalid='ignore'):
+            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
+    dx = np.matmul(g, w.T).astype(dtype) if with_dx else None
+    return dx, np.matmul(x.T, g).astype(dtype), g.sum(axis=0, dtype=dtype)
+
+
+def _matrix(a, what):
+    """a DeviceTensor ([N,H,W,C] with its ld: N*H*W rows of C) or a 2-D array -> (rows, width, DeviceTensor or f32 array)"""
+    if isinstance(a, DeviceTensor):
+        return int(np.prod(a.shape[:-1])), int(a.shape[-1]), a
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2:
+        raise InvalidArgumentError(-1, 'dense_backward: %s must be a matrix, got shape %r' % (what, a.shape))
+    return a.shape[0], a.shape[1], a
+
+
+def dense_backward_device(x, w, dy, y=None, with_dx=True, stream=None):
+    """dense_backward with the results left on the GPU: (dx DeviceTensor [M,1,1,K] or None, dw DeviceBuffer [K,J],
+    db DeviceBuffer [J]); nothing is synchronised."""
+    M, K, dx_in = _matrix(x, 'x')
+    Kw, J, dw_in = _matrix(w, 'w')
+    Md, Jd, dy_in = _matrix(dy, 'dy')
+    bad = (Kw, Md, Jd) != (K, M, J)
+    if y is not None:
+        My, Jy, y_in = _matrix(y, 'y')
+        bad = bad or (My, Jy) != (M, J)
+    if bad:
+        raise InvalidArgumentError(-1, 'dense_backward: x [M,K], w [K,J], dy [M,J] and y [M,J] expected, got %r'
+                                   % ([(M, K), (Kw, J), (Md, Jd)] + ([(My, Jy)] if y is not None else []),))
+    if min(M, K, J) <= 0 or max(K, J) > 4096 or M * max(K, J) >= 2 ** 31:
+        raise InvalidArgumentError(-1, 'dense_backward: M = %d, K = %d, J = %d (positive, K and J at most 4096, '
+                                       'M * max(K, J) below 2^31)' % (M, K, J))
+    if isinstance(dw_in, DeviceTensor) and dw_in.ld != J:
+        raise InvalidArgumentError(-1, 'dense_backward: w must be dense on the device (ld %d, J = %d)' % (dw_in.ld, J))
+
+    def dev(a, width):
+        if isinstance(a, DeviceTensor):
+            return a, a.ptr, a.ld
+        b = to_device(a)
+        return b, b.ptr, width
+    kx, px, ldx = dev(dx_in, K)
+    kw, pw, _ = dev(dw_in, J)
+    kd, pd, ldd = dev(dy_in, J)
+    ky, py, ldy = dev(y_in, J) if y is not None else (None, None, 0)
+    d_dx = DeviceTensor.empty((M, 1, 1, K), ld=K) if with_dx else None
+    d_dw, d_db = DeviceBuffer(K * J * 4), DeviceBuffer(max(J * 4, 16))
+    ws = DeviceBuffer(lib().xdet_dense_backward_workspace_bytes(M, K, J))
+    check(lib().xdet_dense_backward(px, ldx, pw, py, ldy, pd, ldd, M, K, J, d_dx.ptr if with_dx else None, K, d_dw.ptr,
+                                    d_db.ptr, ws.ptr, stream.handle if stream else None))
+    if d_dx is not None:
+        d_dx._keep = (kx, kw, kd, ky, ws)      # operands and workspace live until the stream has run the call
+    d_dw._keep = (kx, kw, kd, ky, ws)
+    return d_dx, d_dw, d_db
+
+
+def dense_backward(x, w, dy, y=None, with_dx=True, stream=None):
+    """host_dense_backward on the GPU (xdet_dense_backward): x [M,K], w [K,J], dy [M,J], y [M,J] or None as NumPy arrays or
+    DeviceTensors (read in place with their ld; [N,H,W,C] counts as N*H*W rows of C) -> (dx [M,K] or None, dw [K,J],
+    db [J]) as NumPy arrays."""
+    d_dx, d_dw, d_db = dense_backward_device(x, w, dy, y, with_dx, stream)
+    synchronize(stream)
+    J = int((w.shape if isinstance(w, DeviceTensor) else np.shape(w))[-1])
+    K = d_dw.nbytes // (4 * J)
+    dx = to_host(d_dx.ptr, (d_dx.shape[0], K), np.float32, stream) if d_dx is not None else None
+    return dx, to_host(d_dw.ptr, (K, J), np.float32, stream), to_host(d_db.ptr, (J,), np.float32, stream)
