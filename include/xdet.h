@@ -173,6 +173,29 @@ int xdet_conv_forward_planes(void* layer, const uint16_t* in_hi, const uint16_t*
 int xdet_split_f32_x8(const float* in, uint16_t* hi, uint16_t* lo8, int64_t n_pix, int ld, int relu, int x8_exp, void* stream);
 int xdet_conv_forward_planes_x8(void* layer, const uint16_t* in_hi, const uint16_t* in_lo8, int N, int H, int W, int ld_in,
                                 float* out, int ld_out, const float* residual, int x8_exp, void* stream);
+/* One conv layer with everything its epilogue can write (csrc/conv_epilogue.h), as Plan::add_conv asks for it inside a net:
+ * the f32 output and / or a second copy of it as split planes (xdet_split_f32 layout) for the next layer's LDS-DMA operand.
+ * The same ConvLayer::forward as the nets: kernel family and tile follow from the shapes and xdet_conv_set_ksplit.
+ *   input    either `in` (f32 NHWC, with relu_in) or `in_hi` / `in_lo` planes (x8 != 0: the x8 form with x8_exp), the other NULL
+ *   out      f32 NHWC [N][Ho][Wo][ld_out], or NULL: planes only
+ *   out_hi / out_lo   both or neither: planes of relu?(out * s + h), hi = f16(t), lo = f16(t - hi);
+ *            ceil(N*Ho*Wo/16)*16 * max(planes_ld, ld_out) halves each.  Channels [cout, ld_out) are +0; the pad rows beyond N*Ho*Wo
+ *            are not written.
+ *   planes_ld   channel stride of the planes destination: 0 or ld_out = the layer's own planes tensor; a larger multiple of 32 =
+ *            a wider (concatenated) operand of which this conv fills blocks [0, ld_out/32) of every 16-pixel group
+ *   planes_relu   the planes hold max(., 0) (NaN stays NaN, unlike xdet_split_f32's ReLU-on-load)
+ *   bn_scale / bn_shift   host [cout] or NULL: a following inference BN folded into the planes copy, s = bn_scale * 2^-out_exp,
+ *            h = bn_shift * 2^-out_exp; implies planes_relu.  Without one s = 2^-out_exp, h = 0 (out_exp = 0: no affine at all).
+ *            They REPLACE the layer's planes affine and out_exp and stay set until the next call, so the door is for layers
+ *            created with xdet_conv_create, not for a layer that belongs to a net: there it would overwrite the exponent the
+ *            calibration chose, without a word.
+ * XDET_ERR_INVALID_ARG (never a fall-back) for: planes from a layer created in the f32 mode; no output at all; one plane of the
+ * two; planes_ld not a multiple of 32 or below ld_out; a wider destination together with a BN.  A door for tests: the nets
+ * reach the same code through their plans. */
+int xdet_conv_forward_emit(void* layer, const float* in, const uint16_t* in_hi, const uint16_t* in_lo, int x8, int x8_exp, int relu_in,
+                           int N, int H, int W, int ld_in, float* out, int ld_out, const float* residual, uint16_t* out_hi,
+                           uint16_t* out_lo, int planes_ld, int planes_relu, const float* bn_scale_host, const float* bn_shift_host,
+                           int out_exp, void* stream);
 int xdet_layer_destroy(void* layer);
 /* depthwise 3x3 SAME stride 1 (the depthwise half of tf.layers.separable_conv2d,
  * net/xception_body.py:224-231); dw_kernel_host f32 [3,3,C,1]; in/out NHWC with stride ld. */

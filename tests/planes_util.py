@@ -2,11 +2,17 @@
 import numpy as np
 
 
+def planes_rows(flat, n_pix, ld):
+    """the halves of one plane [ceil(n_pix/16)][ld/32][16][32], already on the host, as [ceil(n_pix/16)*16][ld] (pixel-major;
+    a view where `flat` allows it; whatever lies behind the plane is left out)"""
+    g = -(-n_pix // 16)
+    return np.asarray(flat)[:g * 16 * ld].reshape(g, ld // 32, 16, 32).transpose(0, 2, 1, 3).reshape(g * 16, ld)
+
+
 def planes_raw(buf, n_pix, ld):
     """one f16 plane [ceil(n_pix/16)][ld/32][16][32] -> its raw halves as uint16 [ceil(n_pix/16)*16][ld] (pixel-major)"""
     from xdet.runtime import to_host
-    g = -(-n_pix // 16)
-    return to_host(buf.ptr, (g, ld // 32, 16, 32), np.uint16).transpose(0, 2, 1, 3).reshape(g * 16, ld)
+    return planes_rows(to_host(buf.ptr, (-(-n_pix // 16) * 16 * ld,), np.uint16), n_pix, ld)
 
 
 def planes_to_f32(hi_buf, lo_buf, n_pix, ld):

@@ -161,6 +161,62 @@ int xdet_conv_forward_planes_x8(void* layer, const uint16_t* in_hi, const uint16
   io.x8 = 1; io.x8_exp = x8_exp;
   return L->forward(io, N, H, W, ld_in, ld_out, S(stream));
 }
+// A door for tests over stand-alone layers (xdet_conv_create).  Not for a layer that belongs to a net: the planes affine and
+// out_exp given here replace the layer's own (a plan's calibration) and stay set.
+int xdet_conv_forward_emit(void* layer, const float* in, const uint16_t* in_hi, const uint16_t* in_lo, int x8, int x8_exp, int relu_in,
+                           int N, int H, int W, int ld_in, float* out, int ld_out, const float* residual, uint16_t* out_hi,
+                           uint16_t* out_lo, int planes_ld, int planes_relu, const float* bn_scale, const float* bn_shift,
+                           int out_exp, void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 1, "not a conv layer");
+  ConvLayer* L = static_cast<ConvLayer*>(b);
+  XDET_REQUIRE(L->groups == 1, "conv(emit): grouped GEMMs write no planes");
+  XDET_REQUIRE((in != nullptr) != (in_hi != nullptr), "conv(emit): the input is either f32 or planes");
+  XDET_REQUIRE(!in_hi || L->dma_capable(), "layer was not created in a split-precision mode (or has < 32 input channels)");
+  XDET_REQUIRE(!in_hi || in_lo || L->precision == PREC_F16, "conv(emit): NULL planes");
+  XDET_REQUIRE(!in_hi || !relu_in, "conv(emit): planes carry their ReLU already");
+  XDET_REQUIRE(!x8 || (in_hi && in_lo && L->d_wt_x8_b && x8_exp > -100 && x8_exp < 100),
+               "conv(emit): x8 planes need a pointwise (1x1, stride 1) f16x3 layer and an exponent in (-100, 100)");
+  XDET_REQUIRE(out || out_hi || out_lo, "conv(emit): no output at all");
+  XDET_REQUIRE((out_hi != nullptr) == (out_lo != nullptr), "conv(emit): the planes copy is a pair of planes");
+  const bool emit = out_hi != nullptr;
+  XDET_REQUIRE(!emit || L->precision != PREC_F32, "conv(emit): a layer created in the f32 mode writes no planes");
+  XDET_REQUIRE(emit || (planes_ld == 0 && !planes_relu && !bn_scale && !bn_shift && out_exp == 0),
+               "conv(emit): planes options without planes");
+  XDET_REQUIRE((bn_scale != nullptr) == (bn_shift != nullptr), "conv(emit): a planes BN is a scale and a shift");
+  XDET_REQUIRE(out_exp > -100 && out_exp < 100, "conv(emit): out_exp out of range");
+  XDET_REQUIRE(ld_out == L->ld_out(), "conv: ld_out must be round_up(cout,32)");
+  XDET_REQUIRE(planes_ld == 0 || (planes_ld % 32 == 0 && planes_ld >= ld_out),
+               "conv(emit): planes_ld must be 0, ld_out or a larger multiple of 32");
+  const bool wide = planes_ld > ld_out, folded_bn = bn_scale != nullptr;
+  XDET_REQUIRE(!wide || !folded_bn, "conv(emit): a concatenated planes destination takes no folded BN");
+  DeviceGuard guard(L->device);
+  if (emit && (folded_bn || out_exp != 0 || L->out_exp != 0 || !L->pl_shift.host.empty())) {
+    XDET_HIP(hipStreamSynchronize(S(stream)));          // (an earlier call may still read the arrays rewritten below)
+    if (folded_bn) {
+      XDET_TRY(L->set_planes_bn(std::vector<float>(bn_scale, bn_scale + L->cout), std::vector<float>(bn_shift, bn_shift + L->cout)));
+    } else {
+      L->pl_scale.host.clear();                         // (set_out_exp fills in the ones)
+      L->pl_shift.host.clear();
+    }
+    XDET_TRY(L->set_out_exp(out_exp));
+  }
+  ConvIO io;
+  io.in = in; io.in_hi = in_hi; io.in_lo = in_lo; io.zeros = in_hi ? L->d_zeros : nullptr; io.relu_in = relu_in;
+  io.x8 = x8 ? 1 : 0; io.x8_exp = x8 ? x8_exp : 0;
+  io.out = out; io.res = residual;
+  if (emit) {
+    // as Plan::add_conv fills it: a folded BN implies the planes ReLU; the affine goes in exactly when there is one
+    io.out_hi = out_hi; io.out_lo = out_lo;
+    io.planes_relu = (planes_relu || folded_bn) ? 1 : 0;
+    if (folded_bn || L->out_exp != 0) { io.pl_scale = L->d_pl_scale; io.pl_shift = L->d_pl_shift; }
+  }
+  const int saved_c32 = L->pl_c32;
+  L->pl_c32 = wide ? planes_ld >> 5 : 0;
+  const int rc = L->forward(io, N, H, W, ld_in, ld_out, S(stream));
+  L->pl_c32 = saved_c32;
+  return rc;
+}
 int xdet_conv_set_ksplit(void* layer, int ksplit, int mode, int max_parallel_tiles) {
   LayerBase* b = static_cast<LayerBase*>(layer);
   XDET_REQUIRE(b && b->kind == 1, "not a conv layer");

@@ -184,6 +184,11 @@ class Conv2D(object):
             max_parallel_tiles = 448 // max(int(ksplit), 1)
         check(lib().xdet_conv_set_ksplit(self.handle, int(ksplit), int(mode), int(max_parallel_tiles)))
 
+    def out_shape(self, H, W):
+        ho, wo = ctypes.c_int(), ctypes.c_int()
+        check(lib().xdet_conv_out_shape(self.handle, H, W, ctypes.byref(ho), ctypes.byref(wo)))
+        return ho.value, wo.value
+
     def __call__(self, x, residual=None, relu_in=False, stream=None, planes=False, staged_tile=False, x8_exp=None):
         """planes=True (split-precision modes only): split x into f16 hi/lo planes first and run the
         LDS-DMA kernel -- the path every big contraction takes inside a net.  staged_tile=True (with planes; 3x3 VALID
@@ -193,9 +198,8 @@ class Conv2D(object):
         exponent e with max|x| * 2^-e in (128, 256]."""
         N, H, W, C = x.shape
         assert C == self.cin, (C, self.cin)
-        ho, wo = ctypes.c_int(), ctypes.c_int()
-        check(lib().xdet_conv_out_shape(self.handle, H, W, ctypes.byref(ho), ctypes.byref(wo)))
-        out = DeviceTensor.empty((N, ho.value, wo.value, self.cout))
+        ho, wo = self.out_shape(H, W)
+        out = DeviceTensor.empty((N, ho, wo, self.cout))
         if planes:
             n = -(-N * H * W // 16) * 16 * x.ld
             hi, lo = DeviceBuffer(n * 2 + 512, zero=True), DeviceBuffer(n * 2 + 512, zero=True)
@@ -220,6 +224,35 @@ class Conv2D(object):
         check(lib().xdet_conv_forward(self.handle, x.ptr, N, H, W, x.ld, out.ptr, out.ld,
                                       residual.ptr if residual is not None else None, 1 if relu_in else 0,
                                       stream.handle if stream else None))
+        return out
+
+    def emit(self, x=None, in_planes=None, shape=None, x8_exp=None, relu_in=False, residual=None, out=None, out_planes=None,
+             planes_ld=0, planes_relu=False, bn=None, out_exp=0, stream=None):
+        """The layer with everything its epilogue can write (xdet_conv_forward_emit), as a net's plan asks for it.
+        Input: x (f32 DeviceTensor) or in_planes = (hi, lo) buffers with shape = (N, H, W) (x8_exp: the x8 form).
+        out: a DeviceTensor or None (planes only); out_planes: (hi, lo) buffers or None; planes_ld: channel stride of a wider
+        planes destination; bn = (scale, shift) host arrays [cout]: a BN folded into the planes copy; out_exp: planes * 2^-out_exp.
+        The caller owns every buffer (the tests poison them)."""
+        if x is not None:
+            N, H, W, C = x.shape
+            assert C == self.cin, (C, self.cin)
+            ld_in = x.ld
+        else:
+            N, H, W = shape
+            ld_in = channel_ld(self.cin)
+        sc = sh = None
+        if bn is not None:
+            sc, sh = (np.ascontiguousarray(a, np.float32) for a in bn)
+            assert sc.shape == sh.shape == (self.cout,)
+        ih, il = in_planes if in_planes is not None else (None, None)
+        oh, ol = out_planes if out_planes is not None else (None, None)
+        p = lambda b: b.ptr if b is not None else None
+        check(lib().xdet_conv_forward_emit(self.handle, p(x), p(ih), p(il), 0 if x8_exp is None else 1, int(x8_exp or 0),
+                                           1 if relu_in else 0, N, H, W, ld_in, p(out), -(-self.cout // 32) * 32, p(residual), p(oh),
+                                           p(ol), int(planes_ld), 1 if planes_relu else 0, _host(sc) if sc is not None else None,
+                                           _host(sh) if sh is not None else None, int(out_exp),
+                                           stream.handle if stream else None))
+        synchronize(stream)
         return out
 
     def __del__(self):
