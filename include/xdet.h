@@ -93,6 +93,27 @@ int xdet_psroialign_grad(const float* rois, const float* grad_pooled, const int3
                          int N, int C, int H, int W, int R, int grid_w, int grid_h, int use_max, int feat_layout,
                          int ldc, void* stream);
 
+/* ---- F2 with a fixed summation order (csrc/psroialign_grad_ordered.hip) -------
+ * The same gradient as a pure function of its inputs: no float atomics.  Per output element the contributions are added
+ * in the order ROI index, sample row i, sample column j, then the corners (iy,ix), (iy1,ix), (iy,ix1), (iy1,ix1), each a
+ * separately rounded f32 add -- the order of a sequential evaluation, so the result is bit-identical to one and two calls
+ * give the same bits.  (An ROI whose gradient row is all zero may be skipped: at most the sign of a zero differs.)
+ *   rois         f32 [N,R,4] (cy,cx,h,w) -- or corner boxes when rois_are_corners != 0 (_point2center on the fly, as
+ *                xdet_psroialign_fwd does)
+ *   grad_pooled  f32 [N*R, ld_grad], first C entries of a row used (ld_grad >= C)
+ *   pooled_index i32 [N*R, ld_index] likewise ('max'; may be NULL for 'mean', which never reads it).  An index outside
+ *                [0, n_h*n_w) contributes nothing for that element; no access ever leaves the map.
+ *   grad_feat    f32 [N,C,H,W] (feat_layout 0) or [N,H,W,ldc] (feat_layout 1).  EVERY element is written, the padding
+ *                channels [C, ldc) as zeros; N*R == 0 gives all zeros.  Nothing needs to be cleared beforehand.
+ * One lane owns the H x W plane of one (n, c) in LDS, so H*W is limited: beyond
+ * XDET_PSROIALIGN_GRAD_ORDERED_MAX_PIXELS the call returns XDET_ERR_INVALID_ARG (xdet_psroialign_grad takes such maps).
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: the checks of xdet_psroialign_grad, ld_grad < C, ld_index < C,
+ * ldc < C (feat_layout 1), 'max' with a NULL index, H*W above the limit. */
+#define XDET_PSROIALIGN_GRAD_ORDERED_MAX_PIXELS 40448 /* (160 KB of LDS - a 2 KB geometry table) / 4 bytes */
+int xdet_psroialign_grad_ordered(const float* rois, const float* grad_pooled, int ld_grad, const int32_t* pooled_index,
+                                 int ld_index, float* grad_feat, int N, int C, int H, int W, int R, int grid_w, int grid_h,
+                                 int use_max, int feat_layout, int ldc, int rois_are_corners, void* stream);
+
 /* ---- RotatedPsRoiAlign forward (oriented boxes; the rotated op of libps_roi_align.so) -----
  * Replaces op_module.rotated_ps_roi_align(inputs, rois, orders, grid_dim_width, grid_dim_height, pool_method)
  * (REGISTER_OP cpp/PSROIPooling/rotated_ps_roi_align_op.cc:38-77; CPU functor :82-301; argument checks
@@ -595,12 +616,16 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   of a register-split conv (|x| <= 65504) and of a fused separable block (relu?(x) * sum|taps| * 2^-e <= 65504) -- and
  *   every other activation tensor for NaN / inf; a violation marks the image's detection scores NaN (slot 0 of every
  *   class), as a non-finite RPN score or head logit always does.  A diagnostic for new checkpoints: the pass re-reads
- *   all activations. */
+ *   all activations.
+ *   "pool_index" = "off" | "keep": the head's PsRoiAlign also writes its argmax sample ids into an i32 buffer
+ *   [max_batch * R, C] (ld of "pooled"; xdet_net_buffer "pool_index"), which xdet_net_head_pool_backward needs.  off
+ *   (default): the forward is the same call as ever and the buffer does not exist. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
 /* named workspace buffers (views, owned by the net): "mid","out","rpn_out","feat","objectness",
- * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts" */
+ * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts"; "pool_index" (i32, dims / ld of "pooled")
+ * with option "pool_index" = "keep" only, otherwise XDET_ERR_INVALID_ARG */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */
@@ -610,6 +635,11 @@ int xdet_net_rpn_decode(void* net, int N, void* stream);                        
 int xdet_net_get_proposals(void* net, int N, void* stream);                            /* :402 -> "proposals" */
 int xdet_net_get_head(void* net, int N, void* stream);                                 /* :477 -> "cls_reg" */
 int xdet_net_head_decode(void* net, int N, void* stream);                              /* -> "head_boxes" */
+/* The head's pooling backward: d loss / d pooled (device, [N*R, ld], first C = grid*grid*bank entries of a row) ->
+ * d loss / d feat, by xdet_psroialign_grad_ordered on the net's own "proposals" (corner boxes), the "pool_index" the last
+ * xdet_net_get_head kept, cfg.grid and 'max'.  d_feat: [N, feat.H, feat.W, feat.ld], the layout of the "feat" buffer,
+ * every element written (padding channels zero).  XDET_ERR_STATE for a net built with "pool_index" = "off". */
+int xdet_net_head_pool_backward(void* net, int N, const float* d_pooled, int ld, float* d_feat, void* stream);
 int xdet_net_bboxes_eval(void* net, int N, const int* image_shapes, const float* bbox_img, float* det_scores,
                          float* det_boxes, void* stream);
 /* whole forward: images f32 [N,3,S,S] -> det_scores [N,20,topk], det_boxes [N,20,topk,4].

@@ -95,6 +95,13 @@ int xdet_psroialign_grad(const float* rois, const float* grad_pooled, const int3
                                 feat_layout, feat_layout == 0 ? C : ldc, S(stream));
 }
 
+int xdet_psroialign_grad_ordered(const float* rois, const float* grad_pooled, int ld_grad, const int32_t* pooled_index,
+                                 int ld_index, float* grad_feat, int N, int C, int H, int W, int R, int grid_w, int grid_h,
+                                 int use_max, int feat_layout, int ldc, int rois_are_corners, void* stream) {
+  return launch_psroialign_grad_ordered(rois, grad_pooled, ld_grad, pooled_index, ld_index, grad_feat, N, C, H, W, R, grid_w,
+                                        grid_h, use_max, feat_layout, feat_layout == 0 ? C : ldc, rois_are_corners, S(stream));
+}
+
 int xdet_rotated_psroialign_fwd(const float* feat, const float* rois, const int32_t* orders, float* pooled,
                                 int32_t* index, int N, int C, int H, int W, int R, int grid_w, int grid_h, int use_max,
                                 int feat_layout, int ldc, void* stream) {
@@ -568,6 +575,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->patch_conv3x3 = v == "patch";
     return XDET_OK;
   }
+  if (k == "pool_index") {
+    XDET_REQUIRE(v == "keep" || v == "off", "pool_index must be keep | off");
+    n->keep_pool_index = v == "keep";
+    return XDET_OK;
+  }
   set_last_error("unknown option: " + k);
   return XDET_ERR_INVALID_ARG;
 }
@@ -594,6 +606,11 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
   else if (s == "rpn_out") from_buf(n->rpn_out);
   else if (s == "feat") from_buf(n->feat);
   else if (s == "pooled") from_buf(n->pooled);
+  else if (s == "pool_index") {
+    XDET_REQUIRE(n->pool_index != nullptr, "net_buffer: pool_index needs a net built with the option pool_index=keep");
+    from_buf(n->pooled);
+    *dptr = n->pool_index;
+  }
   else if (s == "fc") from_buf(n->fc);
   else if (s == "cls_reg") from_buf(n->cls_reg);
   else if (s == "objectness") { *dptr = n->objectness; dims[0] = B; dims[1] = n->n_anchor; dims[2] = 1; dims[3] = 1; *ld = 1; }
@@ -637,6 +654,10 @@ int xdet_net_get_proposals(void* net, int N, void* stream) {
 int xdet_net_get_head(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_get_head");
   return n->get_head(N, S(stream));
+}
+int xdet_net_head_pool_backward(void* net, int N, const float* d_pooled, int ld, float* d_feat, void* stream) {
+  XDET_LIGHTHEAD(n, net, "net_head_pool_backward");
+  return n->head_pool_backward(N, d_pooled, ld, d_feat, S(stream));
 }
 int xdet_net_head_decode(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_head_decode");

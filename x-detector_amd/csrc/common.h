@@ -181,6 +181,10 @@ int launch_psroialign(const float* feat, const float* rois, float* pooled, int32
 int launch_psroialign_grad(const float* rois, const float* grad_pooled, const int32_t* pooled_index, float* grad_out,
                            int N, int C, int H, int W, int R, int gw, int gh, int use_max, int layout, int ldc,
                            hipStream_t s);
+// the same gradient with a fixed summation order (psroialign_grad_ordered.hip): bit-identical to a sequential evaluation
+int launch_psroialign_grad_ordered(const float* rois, const float* grad_pooled, int ld_grad, const int32_t* pooled_index,
+                                   int ld_index, float* grad_out, int N, int C, int H, int W, int R, int gw, int gh,
+                                   int use_max, int layout, int ldc, int corners, hipStream_t s);
 // NCHW map -> stream-ordered NHWC scratch copy (hipFreeAsync it after use); *scratch stays NULL where the direct form
 // is kept (a stream being captured, a failed allocation)
 int psroi_nhwc_scratch(const float* feat, int N, int C, int H, int W, hipStream_t s, float** scratch);

@@ -13,6 +13,8 @@ struct LightHeadNet : Plan {
   bool built = false;
   Buf in4, mid_x, out, rpn_out, feat, pooled, fc, cls_reg;
   float *objectness = nullptr, *rpn_boxes = nullptr, *proposals = nullptr, *head_boxes = nullptr;
+  int32_t* pool_index = nullptr;  // [B * R][pooled.ld] argmax sample ids of the head's PsRoiAlign (option "pool_index" = "keep")
+  bool keep_pool_index = false;
   float* class_probs = nullptr;   // [B][num_classes][R] softmax of the head's logits, class-major (head_decode_probs_kernel)
   float *anc_yx = nullptr, *anc_hw = nullptr;
   float* mid_relu = nullptr;   // materialised ReLU(x) ("mid_outputs", xception_body.py:339) for API users
@@ -89,9 +91,22 @@ struct LightHeadNet : Plan {
   int get_head(int N, hipStream_t s) {
     XDET_TRY(check(N));
     const int C = cfg.bank * cfg.grid * cfg.grid;
-    XDET_TRY(launch_psroialign(feat.p, proposals, pooled.p, nullptr, N, C, feat.H, feat.W, cfg.rpn_post_nms_top_n,
+    XDET_TRY(launch_psroialign(feat.p, proposals, pooled.p, pool_index, N, C, feat.H, feat.W, cfg.rpn_post_nms_top_n,
                                cfg.grid, cfg.grid, 1, 1, feat.ld, pooled.ld, /*corners=*/1, s));
     return run_stage(ST_HEAD, N, s);
+  }
+  // d loss / d pooled -> d loss / d feat in the layout of `feat`: the order-exact PsRoiAlign gradient on the net's own
+  // corner proposals and the argmax the last get_head kept
+  int head_pool_backward(int N, const float* d_pooled, int ld, float* d_feat, hipStream_t s) {
+    XDET_TRY(check(N));
+    if (!pool_index) {
+      set_last_error("net_head_pool_backward: the net was built with pool_index=off (no argmax to go back through)");
+      return XDET_ERR_STATE;
+    }
+    XDET_REQUIRE(d_pooled && d_feat, "net_head_pool_backward: NULL argument");
+    const int C = cfg.bank * cfg.grid * cfg.grid;
+    return launch_psroialign_grad_ordered(proposals, d_pooled, ld, pool_index, pooled.ld, d_feat, N, C, feat.H, feat.W,
+                                          cfg.rpn_post_nms_top_n, cfg.grid, cfg.grid, 1, 1, feat.ld, /*corners=*/1, s);
   }
   int head_decode(int N, hipStream_t s) {
     XDET_TRY(check(N));

@@ -302,6 +302,7 @@ int LightHeadNet::build_head() {
   XDET_TRY(need("final_head/fc_loc/bias", &b2, {4}));
   // ROI rows are the GEMM M dimension: treat [N*R, C] as an NHWC tensor with H = R, W = 1
   XDET_TRY(new_buf(R, 1, C, &pooled));
+  if (keep_pool_index) XDET_TRY(alloc_bytes((size_t)max_batch * R * pooled.ld * sizeof(int32_t), reinterpret_cast<void**>(&pool_index)));
   ConvLayer* L0 = keep(new ConvLayer());
   XDET_TRY(L0->init(1, 1, C, 2048, 1, 1, 0, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
   XDET_TRY(add_conv("final_head/subnet_fc", ST_HEAD, pooled, L0, nullptr, 0, &fc, ConvEmit{1}));

@@ -73,6 +73,7 @@ SIGNATURES = {
     'xdet_event_elapsed_ms': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float)]),
     'xdet_psroialign_fwd': (c_int, [PF, PF, PF, PI] + [c_int] * 12 + [c_void_p]),
     'xdet_psroialign_grad': (c_int, [PF, PF, PI, PF] + [c_int] * 10 + [c_void_p]),
+    'xdet_psroialign_grad_ordered': (c_int, [PF, PF, c_int, PI, c_int, PF] + [c_int] * 11 + [c_void_p]),
     'xdet_rotated_psroialign_fwd': (c_int, [PF, PF, PI, PF, PI] + [c_int] * 10 + [c_void_p]),
     'xdet_rotated_psroialign_grad': (c_int, [PF, PI, PF, PI, PF] + [c_int] * 10 + [c_void_p]),
     'xdet_conv_create': (c_int, [ctypes.POINTER(c_void_p)] + [c_int] * 9 + [PF, PF, PF, c_int]),
@@ -154,6 +155,7 @@ SIGNATURES = {
     'xdet_net_get_proposals': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_get_head': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_head_decode': (c_int, [c_void_p, c_int, c_void_p]),
+    'xdet_net_head_pool_backward': (c_int, [c_void_p, c_int, PF, c_int, PF, c_void_p]),
     'xdet_net_bboxes_eval': (c_int, [c_void_p, c_int, PI, PF, PF, PF, c_void_p]),
     'xdet_net_forward': (c_int, [c_void_p, PF, c_int, PI, PF, PF, PF, c_int, c_void_p]),
     'xdet_net_forward_u8': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, PI, c_int, c_int, PF, PF, PF, PF, c_int,

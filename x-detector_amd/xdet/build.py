@@ -22,6 +22,7 @@ SOURCES = [
     ('resnet_stem.hip', []),
     ('resnet_preconv.hip', []),
     ('psroialign.hip', ['-ffp-contract=off']),
+    ('psroialign_grad_ordered.hip', ['-ffp-contract=off']),
     ('rotated_psroialign.hip', ['-ffp-contract=off']),
     ('proposals.hip', ['-ffp-contract=off']),
     ('detect.hip', ['-ffp-contract=off']),

@@ -21,7 +21,8 @@ class LightHeadDetector(object):
     def __init__(self, weights, image_size=480, max_batch=1, num_classes=21, rpn_pre_nms_top_n=5000,
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
-                 conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None):
+                 conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
+                 pool_index=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -29,7 +30,9 @@ class LightHeadDetector(object):
         every tensor keeps its own block (check_range=True selects 'ssa' by itself); memory() reports both figures.
         cross='fp8': the cross terms of the split-precision products of the depthwise -> pointwise layers (28 of the 46
         contractions, the dominant ones) are computed from fp8 copies of the operands (the "x8" form, include/xdet.h) -- once
-        calibrate() has measured the tensors; until then, and with 'f16', everything is f16x3."""
+        calibrate() has measured the tensors; until then, and with 'f16', everything is f16x3.
+        pool_index=True: the head's PsRoiAlign keeps its argmax sample ids (buffer 'pool_index'), which
+        head_backward(..., to_feat=True) needs; the default forward writes none and allocates nothing for them."""
         if device is not None:
             check(lib().xdet_set_device(int(device)))
         self.cfg = LightHeadConfig(image_size=image_size, max_batch=max_batch, num_classes=num_classes,
@@ -59,6 +62,9 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'pool_sub', pool_sub.encode()))
         check(lib().xdet_net_set_option(self.handle, b'ksplit', ksplit.encode() if isinstance(ksplit, str) else (b'on' if ksplit else b'off')))
         check(lib().xdet_net_set_option(self.handle, b'cross', cross.encode()))
+        if pool_index:
+            check(lib().xdet_net_set_option(self.handle, b'pool_index', b'keep'))
+        self.pool_index = bool(pool_index)
         check(lib().xdet_net_build(self.handle))
         self.max_batch = max_batch
         self.image_size = image_size
@@ -484,15 +490,22 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
     return cr[..., :num_classes], cr[..., num_classes:num_classes + 4]
 
 
-def head_backward(loss_func):
+def head_backward(loss_func, to_feat=False):
     """The backward of the head's dense layers, called after get_head(..., is_training=True, ...) on the same detector:
     d loss / d cls_reg (loss_func.grad_device, what xdet_head_loss wrote) goes through `fc_cls+fc_loc` (x = the net's `fc`
     buffer, the concatenated [2048, nc + 4] kernel) and then, masked by fc's ReLU, through `subnet_fc` (x = `pooled`) -- two
     calls of xdet_dense_backward on the net's buffers with their own ld.  -> a dict with the six gradients under the
     checkpoint's variable names (final_head/{subnet_fc,fc_cls,fc_loc}/{kernel,bias}, NumPy) and 'pooled': d loss / d pooled
-    as a DeviceTensor [N,R,1,C] ([N * R, C] rows, ld C) and 'fc': d loss / d fc (in front of fc's ReLU mask) likewise.  Where it goes from there (PsRoiAlignGrad) is the caller's."""
+    as a DeviceTensor [N,R,1,C] ([N * R, C] rows, ld C) and 'fc': d loss / d fc (in front of fc's ReLU mask) likewise.
+    to_feat=True (a detector built with pool_index=True): d loss / d pooled goes on through xdet_net_head_pool_backward -- the
+    order-exact PsRoiAlign gradient on the net's `proposals` and the argmax get_head kept -- on the same stream, with no host
+    round trip in between, and the dict gains 'feat': d loss / d feat as a DeviceTensor [N,H,W,C] with the `feat` buffer's
+    ld (padding channels zero), what the large-separable backward will read."""
     from . import ops
     d = _det()
+    if to_feat and not d.pool_index:
+        raise InvalidArgumentError(-1, 'head_backward: to_feat=True needs a detector built with pool_index=True (the head '
+                                       'kept no argmax to go back through)')
     g = getattr(loss_func, 'grad_device', None)
     if getattr(loss_func, 'result', None) is None or g is None:
         raise InvalidArgumentError(-1, 'head_backward: the losses ran without a gradient (call get_head(..., is_training=True, '
@@ -512,13 +525,22 @@ def head_backward(loss_func):
             d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
     w0, w1 = d._head_kernels_dev
     fc, pooled = d.buffer('fc', n), d.buffer('pooled', n)
+    d_feat = None
+    if to_feat:                                    # (allocated ahead of the launches, not between the last two)
+        fb = d.buffer('feat', n)
+        d_feat = DeviceTensor.empty(fb.shape, ld=fb.ld)
     dx1, dw1, db1 = ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
     dx0, dw0, db0 = ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
+    if to_feat:
+        check(lib().xdet_net_head_pool_backward(d.handle, n, dx0.ptr, dx0.ld, d_feat.ptr, d.stream.handle))
     _sync(d)
     K0, K1 = w0.shape[0], w1.shape[0]
     kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
-    return {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
-            'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
-            'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy(),
-            'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
-            'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)}
+    out = {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
+           'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
+           'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy(),
+           'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
+           'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)}
+    if to_feat:
+        out['feat'] = d_feat
+    return out

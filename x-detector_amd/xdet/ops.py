@@ -49,12 +49,14 @@ def ps_roi_align(inputs, rois, grid_dim_width, grid_dim_height, pool_method, str
 
 
 def ps_roi_align_grad(inputs, rois, pooled_features_grad, pooled_index, grid_dim_width, grid_dim_height, pool_method,
-                      stream=None):
+                      ordered=False, stream=None):
     """op_module.ps_roi_align_grad (REGISTER_OP cpp/PSROIPooling/ps_roi_align_grad_op.cc:39-57; registered as
     the gradient of PsRoiAlign in cpp/PSROIPooling/test_op.py:93-104).
 
     inputs [N,C,H,W] (only its shape is used, as in the reference), rois [N,R,4],
-    pooled_features_grad / pooled_index [N,R,gh*gw,C/(gh*gw)] -> grad_output [N,C,H,W] f32."""
+    pooled_features_grad / pooled_index [N,R,gh*gw,C/(gh*gw)] -> grad_output [N,C,H,W] f32.
+    ordered=True: the same shapes and errors through xdet_psroialign_grad_ordered -- no float atomics, the sums in the
+    order of a sequential evaluation (bit-identical to one); H*W is limited (include/xdet.h)."""
     if not isinstance(pool_method, str) or ('mean' not in pool_method and 'max' not in pool_method):
         raise InvalidArgumentError(-1, "Need Attr pool_method to be either 'mean' or 'max', got %r" % (pool_method,))
     shape = tuple(inputs.shape)
@@ -77,10 +79,74 @@ def ps_roi_align_grad(inputs, rois, pooled_features_grad, pooled_index, grid_dim
                                        'elements')
     d_roi, d_grad, d_idx = to_device(rois), to_device(grad), to_device(index)
     d_out = DeviceBuffer(max(N * C * H * W * 4, 16))
+    if ordered:
+        check(lib().xdet_psroialign_grad_ordered(d_roi.ptr, d_grad.ptr, C, d_idx.ptr, C, d_out.ptr, N, C, H, W, R,
+                                                 grid_dim_width, grid_dim_height, 1 if 'max' in pool_method else 0, 0, C, 0,
+                                                 stream.handle if stream else None))
+        return to_host(d_out.ptr, shape, np.float32, stream)
     check(lib().xdet_psroialign_grad(d_roi.ptr, d_grad.ptr, d_idx.ptr, d_out.ptr, N, C, H, W, R, grid_dim_width,
                                      grid_dim_height, 1 if 'max' in pool_method else 0, 0, C,
                                      stream.handle if stream else None))
     return to_host(d_out.ptr, shape, np.float32, stream)
+
+
+def ps_roi_align_grad_device(rois, grad, index, shape, grid_dim_width, grid_dim_height, pool_method='max',
+                             rois_are_corners=False, ld=None, out=None, stream=None):
+    """xdet_psroialign_grad_ordered with everything left on the GPU; nothing is synchronised.
+    rois: [N,R,4] NumPy array, DeviceBuffer or DeviceTensor (packed rows of 4; corner boxes with rois_are_corners=True);
+    grad: DeviceTensor [N,R,1,C] (N*R rows of C with its ld) or a NumPy array of N*R*C elements; index: likewise as i32
+    (a DeviceTensor / DeviceBuffer is read as int32), None for 'mean'; shape = (N, H, W, C) of the feature map.
+    -> DeviceTensor [N,H,W,C] with channel stride `ld` (default: channel_ld(C)), every element written, padding zero.
+    out: a DeviceTensor of that shape to write into instead."""
+    if not isinstance(pool_method, str) or ('mean' not in pool_method and 'max' not in pool_method):
+        raise InvalidArgumentError(-1, "Need Attr pool_method to be either 'mean' or 'max', got %r" % (pool_method,))
+    use_max = 'max' in pool_method
+    if len(shape) != 4:
+        raise InvalidArgumentError(-1, 'ps_roi_align_grad_device: shape must be (N, H, W, C)')
+    N, H, W, C = (int(v) for v in shape)
+    gs = grid_dim_width * grid_dim_height
+    if gs <= 0 or C % gs != 0:
+        raise InvalidArgumentError(-1, 'channels must be divisible by grid_dim_width * grid_dim_height')
+    if use_max and index is None:
+        raise InvalidArgumentError(-1, "ps_roi_align_grad_device: 'max' needs the forward's pooled_index")
+    keep = []
+
+    def rows(a, dtype, what):
+        if isinstance(a, DeviceTensor):
+            if a.shape[-1] != C:
+                raise InvalidArgumentError(-1, 'ps_roi_align_grad_device: %s has %d channels, the map %d' % (what, a.shape[-1], C))
+            return a.ptr, a.ld, int(np.prod(a.shape[:-1]))
+        a = np.ascontiguousarray(a, dtype)
+        if a.size % C:
+            raise InvalidArgumentError(-1, 'ps_roi_align_grad_device: %s must hold rows of %d channels' % (what, C))
+        b = to_device(a)
+        keep.append(b)
+        return b.ptr, C, a.size // C
+    pg, ldg, ng = rows(grad, np.float32, 'grad')
+    pi, ldi, ni = rows(index, np.int32, 'index') if index is not None else (None, C, ng)
+    if isinstance(rois, (DeviceTensor, DeviceBuffer)):
+        pr = rois.ptr
+        nroi = (int(np.prod(rois.shape)) if isinstance(rois, DeviceTensor) else rois.nbytes // 4) // 4
+    else:
+        r = np.ascontiguousarray(rois, np.float32)
+        if r.ndim != 3 or r.shape[2] != 4 or r.shape[0] != N:
+            raise InvalidArgumentError(-1, "rois must be in 'batch_size x num_rois x 4' format.")
+        b = to_device(r)
+        keep.append(b)
+        pr, nroi = b.ptr, r.shape[0] * r.shape[1]
+    if N <= 0 or ng % N or ni != ng or nroi < ng:
+        raise InvalidArgumentError(-1, 'ps_roi_align_grad_device: %d gradient rows, %d index rows, %d ROIs for %d images'
+                                   % (ng, ni, nroi, N))
+    R = ng // N
+    if out is None:
+        out = DeviceTensor.empty((N, H, W, C), ld=ld)
+    elif tuple(out.shape) != (N, H, W, C):
+        raise InvalidArgumentError(-1, 'ps_roi_align_grad_device: out has shape %r, not %r' % (out.shape, (N, H, W, C)))
+    check(lib().xdet_psroialign_grad_ordered(pr, pg, ldg, pi, ldi, out.ptr, N, C, H, W, R, grid_dim_width, grid_dim_height,
+                                             1 if use_max else 0, 1, out.ld, 1 if rois_are_corners else 0,
+                                             stream.handle if stream else None))
+    out._keep = (keep, rois, grad, index)      # operands live until the stream has run the call
+    return out
 
 
 def _rotated_checks(inputs_shape, rois, orders, grid_dim_width, grid_dim_height, pool_method):
