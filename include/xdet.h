@@ -396,10 +396,29 @@ int xdet_ext_decode_rois(const float* rois, const float* reg, int ld_reg, int64_
 /* ---- A12: bboxes_eval detection part (light_head_rfcn_eval.py:263-287) -------------------
  *   cls logits [N,R,ld_cls], boxes [N,R,4], image_shapes i32 [N,2] (H,W of the raw image),
  *   bbox_img f32 [N,4] -> det_scores [N,num_classes-1,nms_topk], det_boxes [..,4], zero padded.  An image with a
- *   non-finite head logit or a non-finite bbox_img gets NaN in slot 0 of every class. */
+ *   non-finite head logit or a non-finite bbox_img gets NaN in slot 0 of every class.  A box with a NaN coordinate is
+ *   never a detection (the reference's clip keeps the NaN and its filter drops the box); every class whose threshold the
+ *   ROI's score passed gets NaN in slot 0. */
 int xdet_bboxes_eval(const float* cls, int ld_cls, const float* boxes, int N, int R, int num_classes,
                      const int* image_shapes, const float* bbox_img, int net_h, int net_w, float select_thr,
                      float nms_thr, int nms_topk, float* det_scores, float* det_boxes, void* stream);
+
+/* ---- A11 + A12 in the form xdet_net_forward runs them (a door for tests) -----------------
+ * xdet_head_decode_probs: one pass over the n = N*R rows of the head's output: cls_reg [n][ld], a row = num_classes logits
+ *   and 4 regression values (columns behind them are never read), rois [n][4] -> boxes [n][4] (xdet_ext_decode_rois),
+ *   probs [N][num_classes][R] (the softmax, class-major), bad i32 [N]: the caller zeroes it, an image with a non-finite
+ *   logit gets 1, nothing else is written.  form 0: the kernel the net gets (32 lanes per ROI when num_classes + 4 <= 32,
+ *   else one thread per ROI); form 1: one thread per ROI for any class count.
+ *   XDET_ERR_INVALID_ARG, nothing launched: NULL, num_classes < 2, R < 1, n < 0, n % R != 0, ld < num_classes + 4, rois or
+ *   boxes not 16-byte aligned, form outside {0, 1}.
+ * xdet_bboxes_eval_probs: xdet_bboxes_eval from those probabilities instead of the logits; bad_per_image (may be NULL):
+ *   i32 [N], an image with a non-zero entry gets NaN in slot 0 of every class.  Same limits as xdet_bboxes_eval
+ *   (R <= 1024, 1 <= nms_topk <= 256, num_classes >= 2, nms_thr >= 0). */
+int xdet_head_decode_probs(const float* rois, const float* cls_reg, int ld, int num_classes, int R, int64_t n, int form,
+                           float* boxes, float* probs, int32_t* bad, void* stream);
+int xdet_bboxes_eval_probs(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
+                           const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
+                           const int32_t* bad_per_image /* may be NULL */, float* det_scores, float* det_boxes, void* stream);
 
 /* ---- bboxes_eval, scoring part: eval_helper.bboxes_matching_batch (utility/eval_helper.py:700-830) -----------------
  * The TP / FP flags of every detection slot against the image's ground truth, per (image, class), as the greedy walk of

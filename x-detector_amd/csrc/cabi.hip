@@ -474,6 +474,25 @@ int xdet_bboxes_eval(const float* cls, int ld_cls, const float* boxes, int N, in
   return launch_bboxes_eval(cls, ld_cls, boxes, N, R, num_classes, image_shapes, bbox_img, net_h, net_w, select_thr,
                             nms_thr, nms_topk, det_scores, det_boxes, S(stream));
 }
+// The net's form of the same tail (LightHeadNet::forward_eager: launch_head_decode_probs, launch_bboxes_eval_probs) at op level
+int xdet_head_decode_probs(const float* rois, const float* cls_reg, int ld, int num_classes, int R, int64_t n, int form,
+                           float* boxes, float* probs, int32_t* bad, void* stream) {
+  XDET_REQUIRE(rois && cls_reg && boxes && probs && bad, "head_decode_probs: NULL argument");
+  XDET_REQUIRE(num_classes >= 2, "head_decode_probs: num_classes must be >= 2");
+  XDET_REQUIRE(R >= 1, "head_decode_probs: rois per image must be >= 1");
+  XDET_REQUIRE(n >= 0 && n % R == 0, "head_decode_probs: n must be a non-negative multiple of the rois per image");
+  XDET_REQUIRE(ld >= num_classes + 4, "head_decode_probs: ld must be >= num_classes + 4");
+  XDET_REQUIRE(((uintptr_t)rois & 15) == 0 && ((uintptr_t)boxes & 15) == 0, "head_decode_probs: rois and boxes must be 16-byte aligned");
+  XDET_REQUIRE(form == 0 || form == 1, "head_decode_probs: form must be 0 or 1");
+  return launch_head_decode_probs(rois, cls_reg, ld, num_classes, R, n, boxes, probs, bad, S(stream), form);
+}
+int xdet_bboxes_eval_probs(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
+                           const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
+                           const int32_t* bad_per_image, float* det_scores, float* det_boxes, void* stream) {
+  XDET_REQUIRE(probs && boxes && image_shapes && bbox_img && det_scores && det_boxes, "bboxes_eval_probs: NULL argument");
+  return launch_bboxes_eval_probs(probs, boxes, N, R, num_classes, image_shapes, bbox_img, net_h, net_w, select_thr, nms_thr,
+                                  nms_topk, det_scores, det_boxes, S(stream), bad_per_image);
+}
 
 // A handle is a void*: both plan types start with their Plan base, whose kind tag says what the pointer really is
 // (handing a resnet handle to a light-head entry point used to be undefined behaviour).

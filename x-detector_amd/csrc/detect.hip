@@ -50,7 +50,8 @@ __device__ __forceinline__ void class_probs_begin(const float* __restrict__ lg, 
 // A11 + the class probabilities A12 starts from, once per ROI (the whole forward): bboxes_eval runs one workgroup per
 // (image, class), and each of the 20 used to redo the 21-way softmax of every ROI from row-strided logits -- 430 of the
 // kernel's 580 us per 128 images at R = 1000.  probs is class-major [N][num_classes][R]: the class workgroup reads its
-// column coalesced.  A non-finite logit marks the image in `bad` (bboxes_eval makes it a NaN the host raises on).
+// column coalesced.  A non-finite logit marks the image in `bad` (bboxes_eval makes it a NaN the host raises on); a NaN box
+// is bboxes_eval's to report (where it loads the box: the logits form has no other place).
 __global__ void head_decode_probs_kernel(const float* __restrict__ rois, const float* __restrict__ cls_reg, int ld, int num_classes,
                                          int R, int64_t n, float* __restrict__ out, float* __restrict__ probs,
                                          int* __restrict__ bad) {
@@ -133,10 +134,13 @@ __global__ __launch_bounds__(256) void head_decode_probs_lanes_kernel(const floa
   }
 }
 
+// form 0: the launcher's choice (what the net gets); 1: one thread per ROI whatever the class count (xdet_head_decode_probs:
+// the two kernels on the same input)
 int launch_head_decode_probs(const float* rois, const float* cls_reg, int ld, int num_classes, int R, int64_t n, float* out,
-                             float* probs, int* bad, hipStream_t s) {
+                             float* probs, int* bad, hipStream_t s, int form) {
+  XDET_REQUIRE(form == 0 || form == 1, "head_decode_probs: form must be 0 or 1");
   if (n == 0) return XDET_OK;
-  if (num_classes + 4 <= 32 && ld >= num_classes + 4)
+  if (form == 0 && num_classes + 4 <= 32 && ld >= num_classes + 4)
     hipLaunchKernelGGL(head_decode_probs_lanes_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n * 32, 256), 16384)), dim3(256), 0, s,
                        rois, cls_reg, ld, num_classes, R, n, out, probs, bad);
   else
@@ -227,6 +231,11 @@ __global__ __launch_bounds__(EV_T) void bboxes_eval_kernel(const float* __restri
       const float fmask = s > select_thr ? 1.f : 0.f;          // tf_bboxes_select_layer :581-585
       s = s * fmask;
       float4 b = *reinterpret_cast<const float4*>(boxes + ((int64_t)n * R + r) * 4);
+      // A NaN coordinate (a NaN regression output, or exp(p) * href = inf * 0) would come out of fmaxf / fminf below as the
+      // frame's edge and the ROI as a full-frame detection at its class score; the reference's tf.maximum keeps the NaN and
+      // filter_boxes drops the box.  Dropped here too, and loud like a non-finite logit when the class selected the ROI.
+      const bool nan_box = b.x != b.x || b.y != b.y || b.z != b.z || b.w != b.w;
+      if (nan_box && fmask != 0.f) local_bad = 1;
       b.x *= fmask; b.y *= fmask; b.z *= fmask; b.w *= fmask;
       // bboxes_clip(bbox_img, .)
       float ymin = fmaxf(b.x, ref.x), xmin = fmaxf(b.y, ref.y);
@@ -237,7 +246,7 @@ __global__ __launch_bounds__(EV_T) void bboxes_eval_kernel(const float* __restri
       const float ws = xmax - xmin, hs = ymax - ymin;
       const float xc = xmin + ws / 2.f, yc = ymin + hs / 2.f;
       // zero-score survivors only ever act as zero padding downstream -> drop them here
-      valid = ws > min_size && hs > min_size && xc > 0.f && yc > 0.f && xc < 1.f && yc < 1.f && s > 0.f;
+      valid = ws > min_size && hs > min_size && xc > 0.f && yc > 0.f && xc < 1.f && yc < 1.f && s > 0.f && !nan_box;
       // bboxes_resize
       bx[r] = make_float4((ymin - ref.x) / sx, (xmin - ref.y) / sy, (ymax - ref.x) / sx, (xmax - ref.y) / sy);
     }

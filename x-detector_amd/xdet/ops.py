@@ -621,6 +621,54 @@ def bboxes_eval(cls_pred_logits, bboxes_pred, image_shape=(480, 480), bbox_img=(
     return out[0] if single else out
 
 
+def head_decode_probs(rois, cls_reg, num_classes, R, form=0, stream=None):
+    """xdet_head_decode_probs: the decode + softmax pass of the whole forward (csrc/detect.hip) on its own.
+    rois [n,4] (or [N,R,4]), cls_reg 2-D [n,ld]: a row = num_classes logits, 4 regression values and ld - num_classes - 4
+    columns that are never read; n = N * R.  -> (boxes [n,4], probs [N,num_classes,R] class-major, bad i32 [N]).
+    form 0: the kernel the net gets; 1: one thread per ROI."""
+    r = np.ascontiguousarray(rois, np.float32).reshape(-1, 4)
+    c = np.ascontiguousarray(cls_reg, np.float32)
+    if c.ndim != 2 or c.shape[0] != r.shape[0]:
+        raise InvalidArgumentError(-1, 'head_decode_probs: cls_reg must be [n, ld] with one row per ROI, got %r for %d ROIs'
+                                   % (c.shape, r.shape[0]))
+    n, ld = c.shape
+    N = n // R if R > 0 else 0
+    d_r, d_c = to_device(r), to_device(c)
+    d_b, d_p = DeviceBuffer(max(n * 16, 16)), DeviceBuffer(max(n * num_classes * 4, 16))
+    d_bad = DeviceBuffer(max(N * 4, 16), zero=True)
+    check(lib().xdet_head_decode_probs(d_r.ptr, d_c.ptr, ld, num_classes, R, n, form, d_b.ptr, d_p.ptr, d_bad.ptr,
+                                       stream.handle if stream else None))
+    return (to_host(d_b.ptr, (n, 4), np.float32, stream), to_host(d_p.ptr, (N, num_classes, R), np.float32, stream),
+            to_host(d_bad.ptr, (N,), np.int32, stream))
+
+
+def bboxes_eval_from_probs(probs, bboxes_pred, image_shape=(480, 480), bbox_img=(0., 0., 1., 1.), select_threshold=0.01,
+                           nms_threshold=0.3, nms_topk=200, train_image_size=480, bad=None, stream=None):
+    """xdet_bboxes_eval_probs: bboxes_eval from head_decode_probs' outputs, as the whole forward runs it.
+    probs [N,num_classes,R] (or [num_classes,R]), bboxes_pred [N*R,4] in any shape, bad: i32 [N] or None
+    -> what bboxes_eval returns."""
+    p = np.ascontiguousarray(probs, np.float32)
+    single = p.ndim == 2
+    if single:
+        p = p[None]
+    N, nc, R = p.shape
+    b = np.ascontiguousarray(bboxes_pred, np.float32).reshape(N, R, 4)
+    shapes = np.broadcast_to(np.asarray(image_shape, np.int32).reshape(-1, 2), (N, 2))
+    bimg = np.broadcast_to(np.asarray(bbox_img, np.float32).reshape(-1, 4), (N, 4))
+    d_p, d_b = to_device(p), to_device(b)
+    d_s, d_i = to_device(np.ascontiguousarray(shapes)), to_device(np.ascontiguousarray(bimg))
+    d_bad = None if bad is None else to_device(np.ascontiguousarray(bad, np.int32).reshape(N))
+    n_out = max(N * (nc - 1) * nms_topk, 1)
+    d_os, d_ob = DeviceBuffer(max(n_out * 4, 16)), DeviceBuffer(max(n_out * 16, 16))
+    check(lib().xdet_bboxes_eval_probs(d_p.ptr, d_b.ptr, N, R, nc, d_s.ptr, d_i.ptr, train_image_size, train_image_size,
+                                       select_threshold, nms_threshold, nms_topk, d_bad.ptr if d_bad else None, d_os.ptr,
+                                       d_ob.ptr, stream.handle if stream else None))
+    sc = to_host(d_os.ptr, (N, nc - 1, nms_topk), np.float32, stream)
+    bx = to_host(d_ob.ptr, (N, nc - 1, nms_topk, 4), np.float32, stream)
+    out = [{k + 1: (sc[n, k], bx[n, k]) for k in range(nc - 1)} for n in range(N)]
+    return out[0] if single else out
+
+
 class Resize(enum.IntEnum):
     """The reference's resizing strategies (preprocessing/common_preprocessing.py:29-32), same names and values."""
     NONE = 1
