@@ -228,6 +228,19 @@ def test_a_bad_image_is_counted_and_contributes_nothing():
     assert not nb[5].any() and not tp[5].any() and not fp[5].any() and np.array_equal(tp[4], wtp[4])
 
 
+def test_the_scratch_grows_with_the_batch_and_is_kept_for_a_smaller_one():
+    """one accumulator fed batches of 2, then 5 (its per-batch scratch is freed and re-made larger), then 3 (kept)"""
+    from xdet.evaluation import GpuStreamingTpFp
+    scores, boxes, gts = M.make_batch(45, 10, 4, 8, 7)
+    host = host_stream(scores, boxes, gts)
+    assert sum(len(v) for v in host.scores.values()) > 0
+    acc = GpuStreamingTpFp(4 + 1, 8, 256)
+    for sel in (np.arange(0, 2), np.arange(2, 7), np.arange(7, 10)):
+        acc.update(scores[sel], boxes[sel], image_ids=sel, ground_truths=[gts[j] for j in sel])
+    assert_equals_host(acc, host)
+    assert acc.bad_images == 0 and not acc.overflow
+
+
 # ---- 8, 9. through the detector -------------------------------------------------------------------------------------
 
 def rand_image(H, W, seed):

@@ -596,9 +596,12 @@ __global__ __launch_bounds__(AUG_T) void augment_pixels_kernel(const unsigned ch
   }
 }
 
+// the one description of the workspace: rec[N], sums[N][4], packed (walk it with an alignment of 8 bytes)
+static AugWorkspace aug_layout(WsWalk& w, int N) { return {w.take<AugRecord>(N), w.take<unsigned long long>((size_t)N * 4)}; }
+
 size_t preprocess_train_workspace_bytes(int N, int G) {
   (void)G;                     // the boxes of one image live in LDS
-  return (size_t)N * (sizeof(AugRecord) + 4 * sizeof(unsigned long long));
+  return ws_measure(8, aug_layout, N);
 }
 
 int launch_preprocess_train(const unsigned char* packed, int64_t packed_bytes, const int64_t* offsets,
@@ -610,9 +613,7 @@ int launch_preprocess_train(const unsigned char* packed, int64_t packed_bytes, c
   XDET_REQUIRE(N > 0 && N <= 65535 && S > 0 && packed_bytes >= 0, "preprocess_train: bad sizes");
   XDET_REQUIRE(G > 0 && G <= AUG_MAX_GT, "preprocess_train: G must be in 1 .. 512");
   XDET_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)records & 3) == 0, "preprocess_train: unaligned workspace or records");
-  AugWorkspace ws;
-  ws.rec = static_cast<AugRecord*>(workspace);
-  ws.sums = reinterpret_cast<unsigned long long*>(ws.rec + N);
+  const AugWorkspace ws = ws_carve(workspace, 8, aug_layout, N);
   hipLaunchKernelGGL(augment_geometry_kernel, dim3((unsigned)N), dim3(AUG_WAVE), 0, s, packed_bytes, offsets, image_shapes,
                      glabels, gbboxes, n_gt, image_ids, G, tg_mix(seed ^ 0x9E3779B9u), ws, out_glabels, out_gbboxes, out_n_gt);
   XDET_LAUNCH_CHECK();

@@ -15,20 +15,6 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Layers and nets live on the device that was current when they were created; every entry point that
-// launches on their behalf makes that device current for the call (and restores the caller's), so two
-// detectors on two GPUs can share one process / one host thread per device.
-struct DeviceGuard {
-  int prev = -1, want = -1;
-  explicit DeviceGuard(int dev) : want(dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-  }
-};
-
 int g_default_precision = PREC_F32;
 
 }  // namespace xdet
@@ -47,12 +33,10 @@ int xdet_device_pci_bus_id(int dev, char* buf, int buflen) {
   return XDET_OK;
 }
 int xdet_probe_ipc(void) {
-  void* p = nullptr;
-  XDET_HIP(hipMalloc(&p, 1 << 16));
+  DevMem<unsigned char> p;
+  XDET_TRY(p.alloc(1 << 16));
   hipIpcMemHandle_t h;
-  const hipError_t e = hipIpcGetMemHandle(&h, p);
-  (void)hipFree(p);
-  XDET_HIP(e);
+  XDET_HIP(hipIpcGetMemHandle(&h, p));
   return XDET_OK;
 }
 int xdet_set_default_precision(int mode) {
@@ -327,12 +311,15 @@ int xdet_spectral_conv_create(void** layer, const float* kernel_host, int taps, 
   return XDET_OK;
 }
 // workspace of a batch of N: [x_hi | x_lo | y], each with 512 bytes of slack, each starting 256-byte aligned
-static size_t spectral_part(size_t bytes) { return (bytes + 512 + 255) / 256 * 256; }
+struct SpectralWorkspace { unsigned short *x_hi, *x_lo; float* y; };
+static SpectralWorkspace spectral_layout(WsWalk& w, const SpectralConv* L, int N) {
+  const size_t pl = L->planes_halves(N) + 256;
+  return {w.take<unsigned short>(pl), w.take<unsigned short>(pl), w.take<float>(L->y_floats(N) + 128)};
+}
 size_t xdet_spectral_conv_workspace_bytes(void* layer, int N) {
   LayerBase* b = static_cast<LayerBase*>(layer);
   if (!b || b->kind != 3 || N <= 0) return 0;
-  const SpectralConv* L = static_cast<SpectralConv*>(b);
-  return 2 * spectral_part(L->planes_halves(N) * 2) + spectral_part(L->y_floats(N) * 4);
+  return ws_measure(256, spectral_layout, static_cast<const SpectralConv*>(b), N);
 }
 int xdet_spectral_conv_forward(void* layer, const float* in, int N, int ld_in, void* workspace, float* out, int ld_out,
                                void* stream) {
@@ -342,11 +329,9 @@ int xdet_spectral_conv_forward(void* layer, const float* in, int N, int ld_in, v
   XDET_REQUIRE(in && workspace && out && N > 0 && (int64_t)N * L->F <= (1 << 24), "spectral conv: NULL argument / bad batch");
   XDET_REQUIRE(ld_in == L->cin_ld && ld_out >= L->cout_ld && ld_out % 4 == 0 && (uintptr_t)workspace % 256 == 0,
                "spectral conv: ld_in must be round_up(cin,32), ld_out a multiple of 4 and >= round_up(cout,32), the workspace 256-byte aligned");
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const size_t pl = spectral_part(L->planes_halves(N) * 2);
+  const SpectralWorkspace ws = ws_carve(workspace, 256, spectral_layout, L, N);
   DeviceGuard guard(L->device);
-  return L->forward(in, N, reinterpret_cast<unsigned short*>(ws), reinterpret_cast<unsigned short*>(ws + pl),
-                    reinterpret_cast<float*>(ws + 2 * pl), out, ld_out, S(stream));
+  return L->forward(in, N, ws.x_hi, ws.x_lo, ws.y, out, ld_out, S(stream));
 }
 int xdet_stem_conv3x3s2_forward(const float* in_nchw, const float* w27x32, const float* scale, const float* shift,
                                 uint16_t* out_hi, uint16_t* out_lo, int N, int S_, void* stream) {
@@ -453,13 +438,12 @@ int xdet_rpn_decode(const float* rpn_out, int ld, int cls_off, int box_off, int 
                            S(stream));
 }
 size_t xdet_proposals_workspace_bytes(int N, int n_anchor, int pre_n, int post_n) {
-  return proposal_workspace_bytes(N, n_anchor, pre_n, post_n);
+  return ws_measure(256, proposal_workspace_layout, N, n_anchor, pre_n, post_n);
 }
 int xdet_get_proposals(const float* objectness, const float* boxes, int N, int n_anchor, int pre_n, int post_n,
                        float nms_thr, float min_size, void* workspace, float* rois, int* counts_out, void* stream) {
   XDET_REQUIRE(objectness && boxes && workspace && rois, "get_proposals: NULL argument");
-  ProposalWorkspace ws;
-  proposal_workspace_carve(workspace, N, n_anchor, pre_n, post_n, &ws);
+  const ProposalWorkspace ws = ws_carve(workspace, 256, proposal_workspace_layout, N, n_anchor, pre_n, post_n);
   XDET_TRY(launch_get_proposals(objectness, boxes, N, n_anchor, pre_n, post_n, nms_thr, min_size, ws, rois, S(stream)));
   if (counts_out) XDET_HIP(hipMemcpyAsync(counts_out, ws.counts, (size_t)N * 16, hipMemcpyDeviceToDevice, S(stream)));
   return XDET_OK;
@@ -523,11 +507,11 @@ static int set_weight(Plan* p, const char* name, const float* data, int ndim, co
 
 int xdet_net_create(void** net, const xdet_lighthead_config* cfg) {
   XDET_REQUIRE(net && cfg, "net/cfg is NULL");
-  LightHeadNet* n = new LightHeadNet();
+  std::unique_ptr<LightHeadNet> n(new LightHeadNet());
   n->plan_kind = 0;
   n->cfg = *cfg;
   XDET_HIP(hipGetDevice(&n->device));
-  *net = n;
+  *net = n.release();
   return XDET_OK;
 }
 int xdet_net_set_weight(void* net, const char* name, const float* data, int ndim, const int64_t* dims) {
@@ -822,12 +806,12 @@ int xdet_profile_op_name(void* net, int kind, int op, char* buf, int buflen) {
 // ---- resnet trunk ----
 int xdet_resnet_create(void** net, int image_size, int max_batch) {
   XDET_REQUIRE(net && image_size >= 64 && max_batch > 0, "resnet_create: bad arguments");
-  ResNetTrunk* r = new ResNetTrunk();
+  std::unique_ptr<ResNetTrunk> r(new ResNetTrunk());
   r->plan_kind = 1;
   r->image_size = image_size;
   r->max_batch = max_batch;
   XDET_HIP(hipGetDevice(&r->device));
-  *net = r;
+  *net = r.release();
   return XDET_OK;
 }
 int xdet_resnet_set_weight(void* net, const char* name, const float* data, int ndim, const int64_t* dims) {

@@ -22,6 +22,7 @@
 // step.  A caller that alternates between TWO pairs (det_double_buffered != 0: forward k+1 writes the
 // pair that call k-1 packed) waits for pack k-1 instead, which finished a step ago: no join at all.
 #include "common.h"
+#include "device_mem.h"
 
 #include <rccl/rccl.h>
 
@@ -145,29 +146,17 @@ __global__ void pack_detections_kernel(const float* __restrict__ scores, const f
   }
 }
 
-// make the communicator's device current for the call (the caller may have switched devices since init)
-struct CommDeviceGuard {
-  int prev = -1, want = -1;
-  explicit CommDeviceGuard(int dev) : want(dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want) (void)hipSetDevice(want);
-  }
-  ~CommDeviceGuard() {
-    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-  }
-};
-
 struct Comm {
   int rank = 0, world = 1, device = 0;
   double timeout_s = 300.0;       // watchdog: a host wait on the communicator's stream longer than this is a dead peer
   bool dead = false;              // set by the watchdog; every later call fails fast
-  char* d_bytes = nullptr;        // device staging of xdet_comm_allgather_bytes
+  DevMem<char> d_bytes;           // device staging of xdet_comm_allgather_bytes
   size_t d_bytes_cap = 0;
   ncclComm_t comm = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev_packed[2] = {nullptr, nullptr}, ev_done = nullptr;
   std::vector<hipEvent_t> ev_in;
-  double* d_scalar = nullptr;     // device scratch of the scalar collectives (barrier, max)
+  DevMem<double> d_scalar;        // device scratch of the scalar collectives (barrier, max)
   // pinned host staging of the host-buffer collectives: a D2H copy into PAGEABLE memory blocks the host until the
   // stream has drained, i.e. behind a dead peer it would hang inside hipMemcpyAsync before the watchdog is ever polled
   char* h_pinned = nullptr;
@@ -191,12 +180,10 @@ struct Comm {
       else if (g_rccl.CommAbort) (void)g_rccl.CommAbort(comm);
     }
     if (h_pinned) (void)hipHostFree(h_pinned);
-    if (d_bytes) (void)hipFree(d_bytes);
     for (hipEvent_t e : ev_in) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_packed)
       if (e) (void)hipEventDestroy(e);
     if (ev_done) (void)hipEventDestroy(ev_done);
-    if (d_scalar) (void)hipFree(d_scalar);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -316,7 +303,7 @@ int xdet_comm_init(void** comm_out, int rank, int world, const char* unique_id_p
     XDET_HIP(hipEventRecord(e, c->stream));
   }
   XDET_HIP(hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
-  XDET_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_scalar), 2 * sizeof(double)));
+  XDET_TRY(c->d_scalar.alloc(2));
   XDET_HIP(hipEventRecord(c->ev_done, c->stream));
   *comm_out = c.release();
   return XDET_OK;
@@ -325,7 +312,7 @@ int xdet_comm_init(void** comm_out, int rank, int world, const char* unique_id_p
 int xdet_comm_destroy(void* comm) {
   Comm* c = static_cast<Comm*>(comm);
   if (!c) return XDET_OK;
-  CommDeviceGuard guard(c->device);
+  DeviceGuard guard(c->device);
   if (c->stream && !c->dead) {
     // drain under the watchdog: a destroy behind a dead peer must not hang either
     if (hipEventRecord(c->ev_done, c->stream) == hipSuccess) (void)watchdog_wait(c, c->ev_done, "comm_destroy");
@@ -368,7 +355,7 @@ int xdet_comm_allgather_detections(void* comm, const float* det_scores, const fl
     set_last_error("allgather_detections: the communicator was aborted by the watchdog");
     return XDET_ERR_STATE;
   }
-  CommDeviceGuard dev_guard(c->device);
+  DeviceGuard dev_guard(c->device);
   while ((int)c->ev_in.size() < n_producers) {
     hipEvent_t e;
     XDET_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -398,7 +385,7 @@ int xdet_comm_allgather_detections(void* comm, const float* det_scores, const fl
 int xdet_comm_wait(void* comm, void* stream) {
   Comm* c = static_cast<Comm*>(comm);
   XDET_REQUIRE(c, "comm is NULL");
-  CommDeviceGuard guard(c->device);
+  DeviceGuard guard(c->device);
   if (stream) XDET_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), c->ev_done, 0));
   else return watchdog_wait(c, c->ev_done, "comm_wait");
   return XDET_OK;
@@ -411,7 +398,7 @@ int xdet_comm_allreduce_max(void* comm, double* value_host) {
     set_last_error("allreduce_max: the communicator was aborted by the watchdog");
     return XDET_ERR_STATE;
   }
-  CommDeviceGuard guard(c->device);
+  DeviceGuard guard(c->device);
   // drain first: the staging buffer may still be the target of an earlier call's copy
   XDET_HIP(hipEventRecord(c->ev_done, c->stream));
   XDET_TRY(watchdog_wait(c, c->ev_done, "allreduce_max"));
@@ -437,16 +424,14 @@ int xdet_comm_allgather_bytes(void* comm, const void* send_host, void* recv_host
     set_last_error("allgather_bytes: the communicator was aborted by the watchdog");
     return XDET_ERR_STATE;
   }
-  CommDeviceGuard guard(c->device);
+  DeviceGuard guard(c->device);
   const size_t need = bytes * (size_t)(c->world + 1);
   if (need > c->d_bytes_cap) {
     // (drain under the watchdog: an earlier collective behind a dead peer must not hang the reallocation either)
     XDET_HIP(hipEventRecord(c->ev_done, c->stream));
     XDET_TRY(watchdog_wait(c, c->ev_done, "allgather_bytes"));
-    if (c->d_bytes) (void)hipFree(c->d_bytes);
-    c->d_bytes = nullptr;
     c->d_bytes_cap = 0;
-    XDET_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_bytes), need));
+    XDET_TRY(c->d_bytes.alloc(need));
     c->d_bytes_cap = need;
   }
   // through pinned staging: both copies are then truly asynchronous and the host only ever waits in the watchdog

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/xdet.h"   // XDET_OK / XDET_ERR_* codes
 #include "conv_params.h"   // struct ConvParams: what every MFMA conv kernel is launched with
+#include "workspace.h"     // WsWalk, ws_measure / ws_carve: how a caller-owned workspace is sized and handed out
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -215,8 +216,7 @@ struct ProposalWorkspace {
   unsigned long long* nms_sup;  // [N][ceil(pre_n / 256)][8] per panel: candidates suppressed by the kept list (zeroed with hist)
   unsigned long long* nms_col;  // [min(N, 64)][3][36][64] a cluster's exchange of the panel's own IoU bits
 };
-size_t proposal_workspace_bytes(int N, int n_anchor, int pre_n, int post_n);
-void proposal_workspace_carve(void* base, int N, int n_anchor, int pre_n, int post_n, ProposalWorkspace* ws);
+ProposalWorkspace proposal_workspace_layout(WsWalk& w, int N, int n_anchor, int pre_n, int post_n);
 int launch_rpn_decode(const float* rpn_out, int ld, int cls_off, int box_off, int N, int Hh, int Ww, int A,
                       const float* anchors_yx, const float* anchors_hw, float* objectness, float* boxes,
                       hipStream_t s);

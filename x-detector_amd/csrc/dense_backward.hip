@@ -65,11 +65,15 @@ static DbPlan db_plan(int M, int K, int J) {
   return p;
 }
 
-static size_t db_workspace_bytes(int M, int K, int J) {
-  const DbPlan p = db_plan(M, K, J);
-  size_t n = DB_CTL_WORDS + (size_t)p.n_chunks * J;
-  if (p.n_ranges > 1) n += (size_t)p.n_ranges * K * J;
-  return n * 4;
+struct DbWorkspace {
+  unsigned* ctl;      // [DB_CTL_WORDS]
+  float* partial;     // [n_chunks][J] db's row-chunk sums
+  float* slabs;       // [n_ranges][K][J] dW's range sums (more than one range only)
+};
+// the one description of the workspace; its parts are whole words, packed (walk it with an alignment of 4 bytes)
+static DbWorkspace db_layout(WsWalk& w, const DbPlan& p, int K, int J) {
+  return {w.take<unsigned>(DB_CTL_WORDS), w.take<float>((size_t)p.n_chunks * J),
+          w.take<float>(p.n_ranges > 1 ? (size_t)p.n_ranges * K * J : 0)};
 }
 
 __device__ __forceinline__ unsigned db_abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
@@ -377,7 +381,7 @@ extern "C" {
 
 size_t xdet_dense_backward_workspace_bytes(int M, int K, int J) {
   if (M <= 0 || K <= 0 || J <= 0 || K > DB_MAX_DIM || J > DB_MAX_DIM || (int64_t)M * std::max(K, J) >= (1ll << 31)) return 0;
-  return db_workspace_bytes(M, K, J);
+  return ws_measure(4, db_layout, db_plan(M, K, J), K, J);
 }
 
 int xdet_dense_backward(const float* x, int ld_x, const float* w, const float* y, int ld_y, const float* dy, int ld_dy, int M,
@@ -391,9 +395,7 @@ int xdet_dense_backward(const float* x, int ld_x, const float* w, const float* y
   XDET_REQUIRE(workspace, "dense_backward: NULL workspace");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const DbPlan pl = db_plan(M, K, J);
-  unsigned* ctl = static_cast<unsigned*>(workspace);
-  float* partial = static_cast<float*>(workspace) + DB_CTL_WORDS;
-  float* slabs = partial + (size_t)pl.n_chunks * J;
+  const auto [ctl, partial, slabs] = ws_carve(workspace, 4, db_layout, pl, K, J);
 
   DbPre a{};
   a.x = x; a.w = w; a.y = y; a.dy = dy;

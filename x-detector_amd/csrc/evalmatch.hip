@@ -3,6 +3,7 @@
 // (utility/metrics.py:102-170) as tpfp_append_kernel.  The PR curve and the APs stay on the host (xdet/evaluation.py).
 // Compiled with -ffp-contract=off: the IoU must round like the separately rounded f32 operations of the host port.
 #include "common.h"
+#include "device_mem.h"
 
 #include <climits>
 #include <cmath>
@@ -286,36 +287,39 @@ static int launch_bboxes_matching(const float* det_scores, const float* det_boxe
   return XDET_OK;
 }
 
+struct TpfpScratch {     // per-batch results of the matcher, read by the append
+  unsigned char *tp, *fp;  // [batch][C][K]
+  int *n_gb, *rec;         // [batch][C]
+  int* bad;                // [batch]
+};
+
 // The accumulator handle.  Laid out like the net handles (csrc/plan.h struct Plan: a virtual destructor, then the kind tag), so
 // that an entry point given a handle of another type sees a tag that is not its own and returns XDET_ERR_INVALID_ARG.
 struct TpfpAccumulator {
-  virtual ~TpfpAccumulator() {
-    for (void* p : {(void*)st.cursor, (void*)st.nobjects, (void*)st.misc, (void*)st.scores, (void*)st.is_tp, (void*)st.image_id,
-                    (void*)st.slot, (void*)tp, (void*)fp, (void*)n_gb, (void*)rec, (void*)bad})
-      if (p) (void)hipFree(p);
-  }
+  virtual ~TpfpAccumulator() {}
   int plan_kind = 2;     // 0 / 1: the nets
   int C = 0, K = 0, cap = 0;
-  int batch = 0;         // images the scratch below is sized for
+  int batch = 0;         // images the scratch is sized for
+  DevMem<unsigned char> state_mem, scratch_mem;   // one block each: what `st` and `sc` point into
   TpfpState st{};
-  unsigned char *tp = nullptr, *fp = nullptr;   // [batch][C][K]
-  int *n_gb = nullptr, *rec = nullptr;          // [batch][C]
-  int* bad = nullptr;                           // [batch]
+  TpfpScratch sc{};
 
+  static TpfpState state_layout(WsWalk& w, int C, int cap) {
+    const size_t n = (size_t)C * cap;
+    return {w.take<int>(C), w.take<long long>(C), w.take<int>(4), w.take<float>(n), w.take<unsigned char>(n), w.take<int>(n),
+            w.take<int>(n)};
+  }
+  static TpfpScratch scratch_layout(WsWalk& w, int N, int C, int K) {
+    const size_t slots = (size_t)N * C * K, nc = (size_t)N * C;
+    return {w.take<unsigned char>(slots), w.take<unsigned char>(slots), w.take<int>(nc), w.take<int>(nc), w.take<int>(N)};
+  }
+  // grow only, never shrink
   int reserve(int N) {
     if (N <= batch) return XDET_OK;
-    // (hipFree waits for the device: a call that grows the scratch is the one that synchronises)
-    for (void** p : {(void**)&tp, (void**)&fp, (void**)&n_gb, (void**)&rec, (void**)&bad}) {
-      if (*p) XDET_HIP(hipFree(*p));
-      *p = nullptr;
-    }
     batch = 0;
-    const size_t slots = (size_t)N * C * K;
-    XDET_HIP(hipMalloc((void**)&tp, slots));
-    XDET_HIP(hipMalloc((void**)&fp, slots));
-    XDET_HIP(hipMalloc((void**)&n_gb, (size_t)N * C * 4));
-    XDET_HIP(hipMalloc((void**)&rec, (size_t)N * C * 4));
-    XDET_HIP(hipMalloc((void**)&bad, (size_t)N * 4));
+    // (freeing the smaller block waits for the device: a call that grows the scratch is the one that synchronises)
+    XDET_TRY(scratch_mem.alloc(ws_measure(256, scratch_layout, N, C, K)));
+    sc = ws_carve(scratch_mem.get(), 256, scratch_layout, N, C, K);
     batch = N;
     return XDET_OK;
   }
@@ -349,17 +353,9 @@ int xdet_tpfp_create(void** acc, int C, int K, int capacity_per_class) {
   a->C = C;
   a->K = K;
   a->cap = capacity_per_class;
-  const size_t n = (size_t)C * capacity_per_class;
-  XDET_HIP(hipMalloc((void**)&a->st.cursor, (size_t)C * 4));
-  XDET_HIP(hipMalloc((void**)&a->st.nobjects, (size_t)C * 8));
-  XDET_HIP(hipMalloc((void**)&a->st.misc, 16));
-  XDET_HIP(hipMalloc((void**)&a->st.scores, n * 4));
-  XDET_HIP(hipMalloc((void**)&a->st.is_tp, n));
-  XDET_HIP(hipMalloc((void**)&a->st.image_id, n * 4));
-  XDET_HIP(hipMalloc((void**)&a->st.slot, n * 4));
-  XDET_HIP(hipMemset(a->st.cursor, 0, (size_t)C * 4));
-  XDET_HIP(hipMemset(a->st.nobjects, 0, (size_t)C * 8));
-  XDET_HIP(hipMemset(a->st.misc, 0, 16));
+  XDET_TRY(a->state_mem.alloc(ws_measure(256, TpfpAccumulator::state_layout, C, a->cap)));
+  a->st = ws_carve(a->state_mem.get(), 256, TpfpAccumulator::state_layout, C, a->cap);
+  XDET_TRY(xdet_tpfp_reset(a.get(), nullptr));   // cursor, nobjects and misc start at 0
   XDET_HIP(hipStreamSynchronize(nullptr));   // (the accumulator is used from non-blocking streams, which do not wait for these)
   *acc = a.release();
   return XDET_OK;
@@ -389,9 +385,9 @@ int xdet_tpfp_update(void* acc, const float* det_scores, const float* det_boxes,
   XDET_REQUIRE(image_ids, "tpfp_update: image_ids is NULL");
   XDET_TRY(a->reserve(N));
   XDET_TRY(launch_bboxes_matching(det_scores, det_boxes, N, a->C, a->K, glabels, gbboxes, gdifficults, n_gt, G, matching_threshold,
-                                  a->tp, a->fp, a->n_gb, a->rec, a->bad, S(stream)));
-  hipLaunchKernelGGL(tpfp_append_kernel, dim3(a->C), dim3(AP_T), 0, S(stream), det_scores, a->tp, a->fp, a->n_gb, a->rec, a->bad,
-                     image_ids, N, a->C, a->K, a->cap, a->st);
+                                  a->sc.tp, a->sc.fp, a->sc.n_gb, a->sc.rec, a->sc.bad, S(stream)));
+  hipLaunchKernelGGL(tpfp_append_kernel, dim3(a->C), dim3(AP_T), 0, S(stream), det_scores, a->sc.tp, a->sc.fp, a->sc.n_gb, a->sc.rec,
+                     a->sc.bad, image_ids, N, a->C, a->K, a->cap, a->st);
   XDET_LAUNCH_CHECK();
   return XDET_OK;
 }

@@ -2,6 +2,7 @@
 // number-format helpers they share with the plans.
 #pragma once
 #include "common.h"
+#include "device_mem.h"
 
 #include <algorithm>
 #include <cmath>
@@ -9,12 +10,6 @@
 #include <vector>
 
 namespace xdet {
-
-static inline int upload(const std::vector<float>& h, float** d) {
-  XDET_HIP(hipMalloc(reinterpret_cast<void**>(d), std::max<size_t>(h.size(), 1) * sizeof(float)));
-  XDET_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-  return XDET_OK;
-}
 
 // A device parameter array that carries an exact power-of-two rescale: the host copy at exponent 0 and its device array
 // (not owned), re-uploaded as host * 2^e, zero-padded to n floats where the device array is longer than the host copy.
@@ -113,13 +108,13 @@ struct ConvLayer : LayerBase {
   int cin_p, kp, cout_pad, n_tile;
   bool small_cin;
   int precision = PREC_F32;
-  float *d_wt = nullptr, *d_scale = nullptr, *d_shift = nullptr;
-  unsigned short *d_wt_hi = nullptr, *d_wt_lo = nullptr;
+  DevMem<float> d_wt, d_scale, d_shift;
+  DevMem<unsigned short> d_wt_hi, d_wt_lo;
   // the same f16 weights K-blocked as [Kp/32][Cout_pad][32] for the LDS-DMA kernel: one K-step of a
   // tile's B operand is then one contiguous run
-  unsigned short *d_wt_hi_b = nullptr, *d_wt_lo_b = nullptr;
-  unsigned short* d_wt_x8_b = nullptr;   // x8 form of the K-blocked lo plane (conv_params.h): 32 B fp8(w_lo * 2^9) | 32 B fp8(w_hi * 2^-2) per (K block, row)
-  unsigned short* d_zeros = nullptr;   // 256 B of zeros on the layer's device: the source of out-of-image taps
+  DevMem<unsigned short> d_wt_hi_b, d_wt_lo_b;
+  DevMem<unsigned short> d_wt_x8_b;      // x8 form of the K-blocked lo plane (conv_params.h): 32 B fp8(w_lo * 2^9) | 32 B fp8(w_hi * 2^-2) per (K block, row)
+  DevMem<unsigned short> d_zeros;      // 256 B of zeros on the layer's device: the source of out-of-image taps
   // Activation pre-scale (split-precision range, Plan::calibrate): the A-operand planes hold x * 2^-in_exp and the
   // epilogue scale carries 2^in_exp (exact: powers of two); a planes copy of the output is written as out * 2^-out_exp
   // through the epilogue's pl_scale / pl_shift.  Both 0 unless a calibration found a tensor near the f16 range.
@@ -132,34 +127,33 @@ struct ConvLayer : LayerBase {
   int pl_c32 = 0;                      // planes destination wider than the output (conv_params.h pl_c32); 0: its own planes tensor
   bool ks_narrow = false;              // 128 x 64 tiles although the layer is a multiple of 128 wide (one range, twice the workgroups)
   int64_t ks_tiles = 0;                // tiles the scratch below was sized for
+  // what the launch reads: the layer's own pair below, or the plan's (Plan::finish_ksplit: one per stream, shared by its layers)
   float* d_ks_partial = nullptr;
   int* d_ks_ticket = nullptr;          // 4096 zeroed ints: arrival tickets of the in-kernel fold (conv_params.h ks_ticket)
-  bool ks_owns_scratch = false;        // false: the slab belongs to the plan (one per stream, shared by its layers)
+  DevMem<float> ks_own_partial;        // a stand-alone layer's own scratch (xdet_conv_set_ksplit)
+  DevMem<int> ks_own_ticket;
   size_t ks_scratch_bytes(int S, int64_t tiles) const {
     return S > 1 ? (size_t)std::max<int64_t>(tiles, 1) * S * 128 * (cout_pad % 128 == 0 ? 128 : 64) * sizeof(float) : 0;
   }
-  // shared == nullptr: the layer allocates its own slab (stand-alone layers behind xdet_conv_set_ksplit); inside a plan the
-  // ops of one stream run one after the other, so all its split-K layers borrow ONE slab sized for the largest of them
-  int enable_ksplit(int S, int64_t max_parallel_tiles, float* shared = nullptr) {
+  // S > 1: the layer allocates its own slab (stand-alone layers behind xdet_conv_set_ksplit); inside a plan the ops of one
+  // stream run one after the other, so all its split-K layers borrow ONE slab sized for the largest of them (finish_ksplit)
+  int enable_ksplit(int S, int64_t max_parallel_tiles) {
     XDET_REQUIRE(S >= 1 && S <= 16 && dma_capable() && groups == 1, "ksplit: 1..16 ranges, a split-precision non-grouped layer");
-    if (d_ks_partial && ks_owns_scratch) { (void)hipFree(d_ks_partial); (void)hipFree(d_ks_ticket); }
+    ks_own_partial.reset();
+    ks_own_ticket.reset();
     d_ks_partial = nullptr;
     d_ks_ticket = nullptr;
-    ks_owns_scratch = false;
     ks_tiles = std::max<int64_t>(max_parallel_tiles, 1);
     if (S > 1) {
-      if (shared) d_ks_partial = shared;
-      else {
-        XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_ks_partial), ks_scratch_bytes(S, ks_tiles)));
-        XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_ks_ticket), 4096 * sizeof(int)));
-        XDET_HIP(hipMemset(d_ks_ticket, 0, 4096 * sizeof(int)));
-        ks_owns_scratch = true;
-      }
+      XDET_TRY(ks_own_partial.alloc(ks_scratch_bytes(S, ks_tiles) / sizeof(float)));
+      XDET_TRY(ks_own_ticket.alloc_zeroed(4096));
+      d_ks_partial = ks_own_partial;
+      d_ks_ticket = ks_own_ticket;
     }
     ksplit = S;
     return XDET_OK;
   }
-  float *d_pl_scale = nullptr, *d_pl_shift = nullptr;
+  DevMem<float> d_pl_scale, d_pl_shift;
   int set_in_exp(int e) {
     XDET_TRY(in_scale.upload(e));
     in_exp = e;
@@ -177,8 +171,8 @@ struct ConvLayer : LayerBase {
   int set_out_exp(int e) {
     const size_t n = (size_t)std::max(cout_pad, ld_out());
     if (!d_pl_scale) {
-      XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_pl_scale), n * sizeof(float)));
-      XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_pl_shift), n * sizeof(float)));
+      XDET_TRY(d_pl_scale.alloc(n));
+      XDET_TRY(d_pl_shift.alloc(n));
       pl_scale.dev = d_pl_scale;
       pl_shift.dev = d_pl_shift;
     }
@@ -187,21 +181,6 @@ struct ConvLayer : LayerBase {
     XDET_TRY(pl_shift.upload(-e, n));
     out_exp = e;
     return XDET_OK;
-  }
-
-  ~ConvLayer() override {
-    if (d_ks_partial && ks_owns_scratch) { (void)hipFree(d_ks_partial); (void)hipFree(d_ks_ticket); }
-    if (d_pl_scale) (void)hipFree(d_pl_scale);
-    if (d_pl_shift) (void)hipFree(d_pl_shift);
-    if (d_zeros) (void)hipFree(d_zeros);
-    if (d_wt_hi_b) (void)hipFree(d_wt_hi_b);
-    if (d_wt_lo_b) (void)hipFree(d_wt_lo_b);
-    if (d_wt_x8_b) (void)hipFree(d_wt_x8_b);
-    if (d_wt_hi) (void)hipFree(d_wt_hi);
-    if (d_wt_lo) (void)hipFree(d_wt_lo);
-    if (d_wt) (void)hipFree(d_wt);
-    if (d_scale) (void)hipFree(d_scale);
-    if (d_shift) (void)hipFree(d_shift);
   }
 
   // groups_ > 1: w_hwio is [groups][cin][cout] (1x1), scale/shift are [groups][cout]
@@ -239,11 +218,10 @@ struct ConvLayer : LayerBase {
     XDET_REQUIRE(groups == 1 || precision != PREC_F32, "conv: grouped GEMMs need a split-precision mode");
     XDET_HIP(hipGetDevice(&device));
     if (precision != PREC_F32 && !small_cin) {
-      XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_zeros), 256));
-      XDET_HIP(hipMemset(d_zeros, 0, 256));
+      XDET_TRY(d_zeros.alloc_zeroed(128));
     }
     if (precision == PREC_F32) {
-      XDET_TRY(upload(wt, &d_wt));
+      XDET_TRY(d_wt.upload(wt.data(), wt.size()));
     } else {
       // per-output-channel power-of-two pre-scale so that max|w| lands in [512, 1024): w_hi cannot
       // overflow f16 and w_lo (~2^-11 |w|) stays a normal f16; undone exactly in the epilogue scale
@@ -265,12 +243,8 @@ struct ConvLayer : LayerBase {
       }
       std::vector<float>().swap(wt);
       if (groups == 1) {      // [Cout_pad][Kp] copies: the register-staged kernel (strided / small-cin convs)
-        XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_wt_hi), hi.size() * 2));
-        XDET_HIP(hipMemcpy(d_wt_hi, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-        if (precision == PREC_F16X3) {
-          XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_wt_lo), lo.size() * 2));
-          XDET_HIP(hipMemcpy(d_wt_lo, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-        }
+        XDET_TRY(d_wt_hi.upload(hi.data(), hi.size()));
+        if (precision == PREC_F16X3) XDET_TRY(d_wt_lo.upload(lo.data(), lo.size()));
       }
       if (!small_cin) {       // K-blocked [g][Kp/32][Cout_pad][32] copies: the LDS-DMA kernel
         std::vector<unsigned short> blk(hi.size());
@@ -282,12 +256,10 @@ struct ConvLayer : LayerBase {
             }
         };
         kblock(hi);
-        XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_wt_hi_b), blk.size() * 2));
-        XDET_HIP(hipMemcpy(d_wt_hi_b, blk.data(), blk.size() * 2, hipMemcpyHostToDevice));
+        XDET_TRY(d_wt_hi_b.upload(blk.data(), blk.size()));
         if (precision == PREC_F16X3) {
           kblock(lo);
-          XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_wt_lo_b), blk.size() * 2));
-          XDET_HIP(hipMemcpy(d_wt_lo_b, blk.data(), blk.size() * 2, hipMemcpyHostToDevice));
+          XDET_TRY(d_wt_lo_b.upload(blk.data(), blk.size()));
           if (kh == 1 && kw == 1 && stride == 1 && groups == 1) {   // a pointwise layer may be fed x8 planes
             unsigned char* b8 = reinterpret_cast<unsigned char*>(blk.data());
             for (int co = 0; co < cout_pad; ++co)
@@ -296,14 +268,13 @@ struct ConvLayer : LayerBase {
                 rec[k & 31] = f32_to_e4m3(std::ldexp(f16_to_f32(lo[(size_t)co * kp + k]), 9));
                 rec[32 + (k & 31)] = f32_to_e4m3(std::ldexp(f16_to_f32(hi[(size_t)co * kp + k]), -2));
               }
-            XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_wt_x8_b), blk.size() * 2));
-            XDET_HIP(hipMemcpy(d_wt_x8_b, blk.data(), blk.size() * 2, hipMemcpyHostToDevice));
+            XDET_TRY(d_wt_x8_b.upload(blk.data(), blk.size()));
           }
         }
       }
     }
-    XDET_TRY(upload(sc, &d_scale));
-    XDET_TRY(upload(sh, &d_shift));
+    XDET_TRY(d_scale.upload(sc.data(), sc.size()));
+    XDET_TRY(d_shift.upload(sh.data(), sh.size()));
     in_scale.host = sc;
     in_scale.dev = d_scale;
     return XDET_OK;
@@ -391,13 +362,7 @@ struct SpectralConv : LayerBase {
   int F = 0, NB = 0, axis = 0, cin = 0, cin_ld = 0, cout = 0, cout_ld = 0, relu = 0;
   ConvLayer G;                           // [NB] groups of [2 cin_ld x 2 cout_ld] real block matrices
   Pow2Scaled tab_fwd;                    // the forward table carries the operand planes' activation pre-scale 2^-e
-  float *d_tf = nullptr, *d_ti = nullptr, *d_scale = nullptr, *d_shift = nullptr;
-  ~SpectralConv() override {
-    if (d_tf) (void)hipFree(d_tf);
-    if (d_ti) (void)hipFree(d_ti);
-    if (d_scale) (void)hipFree(d_scale);
-    if (d_shift) (void)hipFree(d_shift);
-  }
+  DevMem<float> d_tf, d_ti, d_scale, d_shift;
   // rows per bin at a batch of N: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
   static int m_pad(int F, int N) { return N * F <= 128 ? 128 : round_up(N * F, 256); }
   int m_pad(int N) const { return m_pad(F, N); }
@@ -421,10 +386,10 @@ struct SpectralConv : LayerBase {
     std::vector<float> ti, sc(cout_ld, 0.f), sh(cout_ld, 0.f);
     spectral_tables(F, &tab_fwd.host, &ti);
     for (int c = 0; c < cout; ++c) { sc[c] = scale ? scale[c] : 1.f; sh[c] = shift ? shift[c] : 0.f; }
-    XDET_TRY(upload(tab_fwd.host, &d_tf));
-    XDET_TRY(upload(ti, &d_ti));
-    XDET_TRY(upload(sc, &d_scale));
-    XDET_TRY(upload(sh, &d_shift));
+    XDET_TRY(d_tf.upload(tab_fwd.host.data(), tab_fwd.host.size()));
+    XDET_TRY(d_ti.upload(ti.data(), ti.size()));
+    XDET_TRY(d_scale.upload(sc.data(), sc.size()));
+    XDET_TRY(d_shift.upload(sh.data(), sh.size()));
     tab_fwd.dev = d_tf;
     return XDET_OK;
   }
@@ -455,7 +420,7 @@ struct SpectralConv : LayerBase {
 
 struct DepthwiseLayer : LayerBase {
   int C, dil, ld;
-  float* d_w = nullptr;
+  DevMem<float> d_w;
   Pow2Scaled taps;               // d_w and its host copy: a planes-producing depthwise carries its activation pre-scale in them
   int out_exp = 0;
   int set_out_exp(int e) {       // every partial sum of the FMA chain scales exactly with a power of two
@@ -463,7 +428,6 @@ struct DepthwiseLayer : LayerBase {
     out_exp = e;
     return XDET_OK;
   }
-  ~DepthwiseLayer() override { if (d_w) (void)hipFree(d_w); }
   int init(int C_, int dil_, const float* w33c1) {
     XDET_REQUIRE(C_ > 0 && dil_ > 0 && w33c1, "depthwise: bad arguments");
     kind = 2;
@@ -472,7 +436,7 @@ struct DepthwiseLayer : LayerBase {
     std::vector<float> w((size_t)9 * ld, 0.f);
     for (int t = 0; t < 9; ++t)
       for (int c = 0; c < C; ++c) w[(size_t)t * ld + c] = w33c1[(size_t)t * C + c];
-    XDET_TRY(upload(w, &d_w));
+    XDET_TRY(d_w.upload(w.data(), w.size()));
     taps.host = w;
     taps.dev = d_w;
     return XDET_OK;

@@ -363,8 +363,8 @@ int LightHeadNet::build() {
   XDET_TRY(alloc_bytes((size_t)B * R * 16, reinterpret_cast<void**>(&head_boxes)));
   XDET_TRY(alloc_bytes((size_t)B * cfg.num_classes * R * 4, reinterpret_cast<void**>(&class_probs)));
   XDET_TRY(alloc_bytes((size_t)B * mid_x.per_image() * 4, reinterpret_cast<void**>(&mid_relu)));
-  XDET_TRY(alloc_bytes(proposal_workspace_bytes(B, n_anchor, cfg.rpn_pre_nms_top_n, R), &prop_ws_mem));
-  proposal_workspace_carve(prop_ws_mem, B, n_anchor, cfg.rpn_pre_nms_top_n, R, &prop_ws);
+  XDET_TRY(alloc_bytes(ws_measure(256, proposal_workspace_layout, B, n_anchor, cfg.rpn_pre_nms_top_n, R), &prop_ws_mem));
+  prop_ws = ws_carve(prop_ws_mem, 256, proposal_workspace_layout, B, n_anchor, cfg.rpn_pre_nms_top_n, R);
   std::vector<int> shp((size_t)B * 2, cfg.image_size);
   std::vector<float> bb((size_t)B * 4);
   for (int i = 0; i < B; ++i) { bb[i * 4] = 0.f; bb[i * 4 + 1] = 0.f; bb[i * 4 + 2] = 1.f; bb[i * 4 + 3] = 1.f; }
@@ -382,13 +382,10 @@ int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_sc
   if (net_precision == PREC_F32 || pscales.empty()) return XDET_OK;
   graphs.clear();                                  // graphs bake kernel arguments (the split passes' multipliers)
   const size_t slots = (size_t)N * (cfg.num_classes - 1) * cfg.nms_topk;
-  float *ds = nullptr, *db = nullptr;
-  XDET_HIP(hipMalloc(reinterpret_cast<void**>(&ds), slots * 4));
-  XDET_HIP(hipMalloc(reinterpret_cast<void**>(&db), slots * 16));
-  const int rc = calibrate_planes(N, s, n_scaled, [&](hipStream_t st) { return forward_eager(images, N, nullptr, nullptr, ds, db, st); });
-  (void)hipFree(ds);
-  (void)hipFree(db);
-  return rc;
+  DevMem<float> ds, db;                            // detections of the calibration forwards: nobody reads them
+  XDET_TRY(ds.alloc(slots));
+  XDET_TRY(db.alloc(slots * 4));
+  return calibrate_planes(N, s, n_scaled, [&](hipStream_t st) { return forward_eager(images, N, nullptr, nullptr, ds, db, st); });
 }
 
 int LightHeadNet::forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,

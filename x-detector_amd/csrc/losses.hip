@@ -73,27 +73,19 @@ struct LsWorkspace {
   float* partial;                  // [LS_NB][4] per-workgroup loss sums (RPN: rows kernel; head: per image)
 };
 
-static size_t ls_align(size_t b) { return (b + 255) / 256 * 256; }
-
-static size_t ls_workspace_bytes(int N, int S) {
-  const size_t s = (size_t)S, n = (size_t)std::max(N, LS_NB);
-  return ls_align(sizeof(LsCtl)) + ls_align(sizeof(LsState)) + 2 * ls_align(2 * LS_NB * 4) + ls_align(2 * s * 4) + 2 * ls_align(s * 4) +
-         ls_align(n * 16);
-}
-
-static LsWorkspace ls_carve(void* base, int S) {
+// the one description of the workspace (S = 0: the head loss, which uses `partial` alone)
+static LsWorkspace ls_layout(WsWalk& w, int S) {
   const size_t s = (size_t)S;
-  char* p = static_cast<char*>(base);
-  LsWorkspace w;
-  w.ctl = reinterpret_cast<LsCtl*>(p);          p += ls_align(sizeof(LsCtl));
-  w.st = reinterpret_cast<LsState*>(p);         p += ls_align(sizeof(LsState));
-  w.blockcnt = reinterpret_cast<int*>(p);       p += ls_align(2 * LS_NB * 4);
-  w.blockoff = reinterpret_cast<int*>(p);       p += ls_align(2 * LS_NB * 4);
-  w.ckeys = reinterpret_cast<unsigned*>(p);     p += ls_align(2 * s * 4);
-  w.keep = reinterpret_cast<int*>(p);           p += ls_align(s * 4);
-  w.mult = reinterpret_cast<int*>(p);           p += ls_align(s * 4);
-  w.partial = reinterpret_cast<float*>(p);
-  return w;
+  LsWorkspace ws;
+  ws.ctl = w.take<LsCtl>(1);
+  ws.st = w.take<LsState>(1);
+  ws.blockcnt = w.take<int>(2 * LS_NB);
+  ws.blockoff = w.take<int>(2 * LS_NB);
+  ws.ckeys = w.take<unsigned>(2 * s);
+  ws.keep = w.take<int>(s);
+  ws.mult = w.take<int>(s);
+  ws.partial = w.take<float>((size_t)LS_NB * 4);
+  return ws;
 }
 
 // ---- arithmetic shared by both losses ------------------------------------------------------------------------------
@@ -620,7 +612,7 @@ extern "C" {
 
 size_t xdet_losses_workspace_bytes(int N, int anchors_per_image) {
   if (N <= 0 || N > LS_NB || anchors_per_image < 0 || (int64_t)N * anchors_per_image > LS_MAXS) return 0;
-  return ls_workspace_bytes(N, N * anchors_per_image);
+  return ws_measure(256, ls_layout, N * anchors_per_image);
 }
 
 int xdet_rpn_loss(const float* rpn_out, int ld, int cls_off, int box_off, int N, int Hh, int Ww, int A, const int32_t* labels,
@@ -642,7 +634,7 @@ int xdet_rpn_loss(const float* rpn_out, int ld, int cls_off, int box_off, int N,
   const int M = (int)M64, Sn = N * anchors_per_image;
   const int exp_fg = (int)std::nearbyint((float)Sn * fg_ratio);             // tf.round: half to even
   const unsigned word = tg_mix(tg_mix(seed ^ 0x9E3779B9u) + 0u);            // image 0: the batch is one flat population
-  const LsWorkspace ws = ls_carve(workspace, Sn);
+  const LsWorkspace ws = ws_carve(workspace, 256, ls_layout, Sn);
   const int nb = (int)std::min<int64_t>(cdiv(M, 8 * LS_T), LS_NB);
   const int chunk = round_up((int)cdiv(M, nb), LS_T);
   hipStream_t s = S(stream);
@@ -723,7 +715,7 @@ int xdet_head_loss(const float* cls_reg, int ld, int cls_off, int reg_off, int N
   a.per_roi = per_roi;
   a.select = select;
   a.grad = grad_cls_reg;
-  a.partial = ls_carve(workspace, 0).partial;
+  a.partial = ws_carve(workspace, 256, ls_layout, 0).partial;
   XDET_TRY(ensure_dynamic_lds(g_head_once, reinterpret_cast<const void*>(hl_image_kernel), hl_lds_bytes(HL_MAXP, HL_MAXP)));
   hipLaunchKernelGGL(hl_image_kernel, dim3(N), dim3(HL_T), hl_lds_bytes(P, a.P2), S(stream), a);
   XDET_LAUNCH_CHECK();

@@ -135,7 +135,7 @@ struct Plan {
   int max_batch = 1;
   bool profiling = false;
   std::vector<ProfRec> prof;
-  std::vector<void*> allocs;
+  std::vector<DevMem<unsigned char>> allocs;               // the pool: every block of alloc_bytes(), freed with the plan
   std::vector<std::pair<const float*, size_t>> f32_bufs;   // every activation tensor of new_buf(): (pointer, floats per image)
   struct PlanesRec { const unsigned short* hi; int64_t pix_per_image; int ld; };
   std::vector<PlanesRec> planes_bufs;                      // ... and of new_planes()
@@ -145,16 +145,14 @@ struct Plan {
   WeightMap w;
   GraphCache graphs;
 
-  virtual ~Plan() {
-    graphs.clear();
-    for (void* p : allocs) (void)hipFree(p);
-  }
+  virtual ~Plan() { graphs.clear(); }
   size_t allocated_bytes = 0;
   int alloc_bytes(size_t bytes, void** out, bool zero = true) {
-    XDET_HIP(hipMalloc(out, std::max<size_t>(bytes, 256)));
+    DevMem<unsigned char> m;
+    XDET_TRY(zero ? m.alloc_zeroed(bytes, 256) : m.alloc(bytes, 256));
     allocated_bytes += std::max<size_t>(bytes, 256);
-    if (zero) XDET_HIP(hipMemset(*out, 0, std::max<size_t>(bytes, 256)));
-    allocs.push_back(*out);
+    *out = m.get();
+    allocs.push_back(std::move(m));
     return XDET_OK;
   }
   // a plan-owned device copy of a host vector

@@ -79,17 +79,16 @@ void Plan::f32_limit(const float* p, float* limit, int* relu) const {
 int Plan::calibrate_planes(int N, hipStream_t s, int* n_scaled, const std::function<int(hipStream_t)>& run) {
   if (n_scaled) *n_scaled = 0;
   if (pscales.empty()) return XDET_OK;
-  unsigned* d_max = nullptr;
-  XDET_HIP(hipMalloc(reinterpret_cast<void**>(&d_max), pscales.size() * sizeof(unsigned)));
+  DevMem<unsigned> d_max;
+  XDET_TRY(d_max.alloc(pscales.size()));
   std::vector<unsigned> h_max(pscales.size());
-  int rc = XDET_OK;
   for (const PlaneScale& p : pscales)
-    if (p.clear && rc == XDET_OK) rc = p.clear(s);
+    if (p.clear) XDET_TRY(p.clear(s));
   const int max_passes = (int)pscales.size() + 4;
   const bool verbose = getenv("XDET_CALIBRATE_VERBOSE") != nullptr;
   int pass = 0;
-  for (; pass < max_passes && rc == XDET_OK; ++pass) {
-    if ((rc = hipMemsetAsync(d_max, 0, pscales.size() * sizeof(unsigned), s) == hipSuccess ? XDET_OK : XDET_ERR_HIP) != XDET_OK) break;
+  for (; pass < max_passes; ++pass) {
+    XDET_HIP(hipMemsetAsync(d_max, 0, pscales.size() * sizeof(unsigned), s));
     // tensors with a producing op in the plan are measured right behind it, on the stream it ran on (their workspace
     // block may belong to another tensor by the end of the forward); the rest after the whole forward
     auto measure = [&](size_t i, hipStream_t st) {
@@ -102,16 +101,15 @@ int Plan::calibrate_planes(int N, hipStream_t s, int* n_scaled, const std::funct
         if (pscales[i].op_index == op) XDET_TRY(measure(i, st));
       return (int)XDET_OK;
     };
-    rc = run(s);
-    after_op = nullptr;
-    if (rc != XDET_OK) break;
-    for (size_t i = 0; i < pscales.size() && rc == XDET_OK; ++i)
-      if (pscales[i].op_index < 0) rc = measure(i, s);
-    if (rc != XDET_OK) break;
-    if (hipMemcpyAsync(h_max.data(), d_max, h_max.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) { rc = XDET_ERR_HIP; break; }
+    const int rc = run(s);
+    after_op = nullptr;                            // (it refers to this frame: reset before any return)
+    XDET_TRY(rc);
+    for (size_t i = 0; i < pscales.size(); ++i)
+      if (pscales[i].op_index < 0) XDET_TRY(measure(i, s));
+    XDET_HIP(hipMemcpyAsync(h_max.data(), d_max, h_max.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    XDET_HIP(hipStreamSynchronize(s));
     bool changed = false;
-    for (size_t i = 0; i < pscales.size() && rc == XDET_OK; ++i) {
+    for (size_t i = 0; i < pscales.size(); ++i) {
       const PlaneScale& p = pscales[i];
       float m;                                     // magnitude of the operand as the MFMAs would see it now
       bool broken;
@@ -130,21 +128,19 @@ int Plan::calibrate_planes(int N, hipStream_t s, int* n_scaled, const std::funct
         fprintf(stderr, "xdet calibrate: pass %d  %-70s exp %d  max %s%g\n", pass, p.name.c_str(), p.exp,
                 broken ? "inf/NaN " : "", (double)m);
       if (broken) {
-        rc = set_plane_exp((int)i, p.exp + 8);
+        XDET_TRY(set_plane_exp((int)i, p.exp + 8));
         changed = true;
         break;                                     // downstream tensors were computed from garbage: re-measure
       }
       if (m > kRangeTarget) {
         int e = 0;
         (void)frexpf(m / kRangeTarget, &e);        // m / target in [2^(e-1), 2^e)
-        rc = set_plane_exp((int)i, p.exp + e);
+        XDET_TRY(set_plane_exp((int)i, p.exp + e));
         changed = true;
       }
     }
     if (!changed) break;
   }
-  (void)hipFree(d_max);
-  XDET_TRY(rc);
   if (pass >= max_passes) {
     set_last_error("calibrate: the activation ranges did not settle (non-finite inputs or weights?)");
     return XDET_ERR_STATE;

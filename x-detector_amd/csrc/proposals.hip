@@ -42,46 +42,30 @@ template <int NBLK> struct NmsPanel {
   static constexpr int S = 64 * NBLK;                  // candidates per panel
   static constexpr int TRI = NBLK * (NBLK + 1) / 2;    // 64 x 64 blocks (I <= J) of the panel's triangle
 };
-// int words zeroed by prop_zero_kernel at the start of every forward: hist[N][HIST_BINS], bad[round_up(N,4)],
-// nms_ctl[N][4] (cluster barrier counter, give-up flag), nms_sup[N][panels][8] as 64-bit words
-static inline size_t prop_zeroed_words(int N, int pre_n) {
-  return (size_t)N * HIST_BINS + (size_t)round_up(N, 4) + (size_t)N * 4 + (size_t)N * cdiv(pre_n, NMS_SUP_PANEL) * 16;
-}
-
-size_t proposal_workspace_bytes(int N, int n_anchor, int pre_n, int post_n) {
-  size_t b = 0;
-  auto add = [&](size_t x) { b += (x + 255) / 256 * 256; };
-  add((size_t)N * n_anchor * 8);
-  add((size_t)N * n_anchor * 16);
-  add((size_t)N * n_anchor * 4);
-  add((size_t)N * 16);
-  add((size_t)N * pre_n * 16);
-  add((size_t)N * pre_n * 4);
-  add((size_t)N * n_anchor * 8);
-  add(prop_zeroed_words(N, pre_n) * 4);                        // hist + bad + the NMS cluster words (zeroed together)
-  add((size_t)N * 4);
-  add((size_t)N * post_n * 4);
-  add((size_t)std::min(N, NMS_CLUSTER_IMAGES) * 3 * NmsPanel<NMS_CLUSTER_NBLK>::TRI * 64 * 8);
-  return b;
-}
-
-void proposal_workspace_carve(void* base, int N, int n_anchor, int pre_n, int post_n, ProposalWorkspace* ws) {
-  char* p = static_cast<char*>(base);
-  auto take = [&](size_t x) { char* r = p; p += (x + 255) / 256 * 256; return r; };
-  ws->keys = reinterpret_cast<u64*>(take((size_t)N * n_anchor * 8));
-  ws->cboxes = reinterpret_cast<float*>(take((size_t)N * n_anchor * 16));
-  ws->ranks = reinterpret_cast<int*>(take((size_t)N * n_anchor * 4));
-  ws->counts = reinterpret_cast<int*>(take((size_t)N * 16));
-  ws->sboxes = reinterpret_cast<float*>(take((size_t)N * pre_n * 16));
-  ws->sscores = reinterpret_cast<float*>(take((size_t)N * pre_n * 4));
-  ws->cand = reinterpret_cast<u64*>(take((size_t)N * n_anchor * 8));
-  ws->hist = reinterpret_cast<int*>(take(prop_zeroed_words(N, pre_n) * 4));
-  ws->bad = ws->hist + (size_t)N * HIST_BINS;
-  ws->nms_ctl = reinterpret_cast<unsigned*>(ws->bad + round_up(N, 4));
-  ws->nms_sup = reinterpret_cast<u64*>(ws->nms_ctl + (size_t)N * 4);
-  ws->tbin = reinterpret_cast<int*>(take((size_t)N * 4));
-  ws->kept = reinterpret_cast<int*>(take((size_t)N * post_n * 4));
-  ws->nms_col = reinterpret_cast<u64*>(take((size_t)std::min(N, NMS_CLUSTER_IMAGES) * 3 * NmsPanel<NMS_CLUSTER_NBLK>::TRI * 64 * 8));
+// The one description of the workspace (ws_measure sizes it, ws_carve hands it out).
+// hist[N][HIST_BINS], bad[round_up(N,4)], nms_ctl[N][4] (cluster barrier counter, give-up flag) and nms_sup[N][panels][8]
+// (64-bit words) are ONE part: the int words prop_zero_kernel clears at the start of every forward.
+ProposalWorkspace proposal_workspace_layout(WsWalk& w, int N, int n_anchor, int pre_n, int post_n) {
+  const size_t n = (size_t)N, a = n * n_anchor, p = n * pre_n;
+  const size_t n_hist = n * HIST_BINS, n_bad = (size_t)round_up(N, 4), n_ctl = n * 4, n_sup = n * cdiv(pre_n, NMS_SUP_PANEL) * 16;
+  ProposalWorkspace ws{};
+  ws.keys = w.take<u64>(a);
+  ws.cboxes = w.take<float>(a * 4);
+  ws.ranks = w.take<int>(a);
+  ws.counts = w.take<int>(n * 4);
+  ws.sboxes = w.take<float>(p * 4);
+  ws.sscores = w.take<float>(p);
+  ws.cand = w.take<u64>(a);
+  ws.hist = w.take<int>(n_hist + n_bad + n_ctl + n_sup);
+  if (ws.hist) {                                 // (a measuring walk hands out NULL)
+    ws.bad = ws.hist + n_hist;
+    ws.nms_ctl = reinterpret_cast<unsigned*>(ws.bad + n_bad);
+    ws.nms_sup = reinterpret_cast<u64*>(ws.nms_ctl + n_ctl);
+  }
+  ws.tbin = w.take<int>(n);
+  ws.kept = w.take<int>(n * post_n);
+  ws.nms_col = w.take<u64>((size_t)std::min(N, NMS_CLUSTER_IMAGES) * 3 * NmsPanel<NMS_CLUSTER_NBLK>::TRI * 64);
+  return ws;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -38,26 +38,18 @@ struct TgWorkspace {
   float* tg;                    // [N][n_candidates][4]
 };
 
-static size_t tg_align(size_t b) { return (b + 255) / 256 * 256; }
-
-static size_t tg_workspace_bytes(int N, int n_cand, int G) {
+// the one description of the workspace (n_cand = 0: the anchor form, whose per-candidate results go to the caller's arrays)
+static TgWorkspace tg_layout(WsWalk& w, int N, int n_cand, int G) {
   const size_t n = (size_t)N, g = (size_t)G, m = (size_t)n_cand;
-  return tg_align(n * 4) + tg_align(n * g * 4) + tg_align(n * g * 16) + tg_align(n * g * 8) + tg_align(n * m * 4) +
-         tg_align(n * m * 4) + tg_align(n * m * 16);
-}
-
-static TgWorkspace tg_carve(void* base, int N, int n_cand, int G) {
-  const size_t n = (size_t)N, g = (size_t)G, m = (size_t)n_cand;
-  char* p = static_cast<char*>(base);
-  TgWorkspace w;
-  w.cn = reinterpret_cast<int*>(p);                      p += tg_align(n * 4);
-  w.clab = reinterpret_cast<int*>(p);                    p += tg_align(n * g * 4);
-  w.cbox = reinterpret_cast<float4*>(p);                 p += tg_align(n * g * 16);
-  w.rowmax = reinterpret_cast<unsigned long long*>(p);   p += tg_align(n * g * 8);
-  w.lab = reinterpret_cast<int*>(p);                     p += tg_align(n * m * 4);
-  w.sc = reinterpret_cast<float*>(p);                    p += tg_align(n * m * 4);
-  w.tg = reinterpret_cast<float*>(p);
-  return w;
+  TgWorkspace ws;
+  ws.cn = w.take<int>(n);
+  ws.clab = w.take<int>(n * g);
+  ws.cbox = w.take<float4>(n * g);
+  ws.rowmax = w.take<unsigned long long>(n * g);
+  ws.lab = w.take<int>(n * m);
+  ws.sc = w.take<float>(n * m);
+  ws.tg = w.take<float>(n * m * 4);
+  return ws;
 }
 
 // where the candidates come from: anchors (rois == NULL; index (y * W + x) * A + k as in rpn_decode_kernel) or the image's
@@ -428,7 +420,7 @@ extern "C" {
 
 size_t xdet_targets_workspace_bytes(int N, int n_candidates, int G) {
   if (N <= 0 || G <= 0 || n_candidates < 0) return 0;
-  return tg_workspace_bytes(N, n_candidates, G);
+  return ws_measure(256, tg_layout, N, n_candidates, G);
 }
 
 int xdet_encode_anchors(const float* anchors_yx, const float* anchors_hw, int Hh, int Ww, int A, float allowed_border,
@@ -443,7 +435,7 @@ int xdet_encode_anchors(const float* anchors_yx, const float* anchors_hw, int Hh
   XDET_TRY(check_ground_truth("encode_anchors", glabels, gbboxes, n_gt, workspace));
   XDET_REQUIRE(anchors_yx && anchors_hw && labels && targets && scores, "encode_anchors: NULL argument");
   XDET_REQUIRE(aligned16(targets), "encode_anchors: targets must be 16-byte aligned");
-  const TgWorkspace ws = tg_carve(workspace, N, 0, G);
+  const TgWorkspace ws = ws_carve(workspace, 256, tg_layout, N, 0, G);
   TgCand c{};
   c.anchors_yx = anchors_yx;
   c.anchors_hw = anchors_hw;
@@ -472,7 +464,7 @@ int xdet_encode_rois(const float* rois, int R, const int32_t* glabels, const flo
   XDET_REQUIRE(aligned16(rois) && aligned16(out_rois) && aligned16(out_targets) && aligned16(all_targets),
                "encode_rois: box and target arrays must be 16-byte aligned");
   const int M = R + G;
-  const TgWorkspace ws = tg_carve(workspace, N, M, G);
+  const TgWorkspace ws = ws_carve(workspace, 256, tg_layout, N, M, G);
   int* lab = all_labels ? all_labels : ws.lab;
   float* tg = all_targets ? all_targets : ws.tg;
   float* sc = all_scores ? all_scores : ws.sc;
