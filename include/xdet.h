@@ -591,6 +591,43 @@ size_t xdet_dense_backward_workspace_bytes(int M, int K, int J);
 int xdet_dense_backward(const float* x, int ld_x, const float* w, const float* y, int ld_y, const float* dy, int ld_dy, int M,
                         int K, int J, float* dx, int ld_dx, float* dw, float* db, void* workspace, void* stream);
 
+/* ---- the backward of a stride-1 'SAME' convolution y = act(conv(xe, w) + b), xe = x or max(x, 0), act = identity or ReLU
+ * (csrc/conv_backward.hip; the NumPy statement of the same contract is xdet.ops.host_conv_backward).  NHWC, dilation 1,
+ * zero padding of (kh - 1) / 2 rows and (kw - 1) / 2 columns on either side; M = N * H * W pixels -------------------------
+ *   x  f32 [N,H,W,C], pixel stride ld_x          the layer's input (relu_in != 0: the conv read max(x, 0))
+ *   w  f32 [kh,kw,C,J] dense                     the kernel as the checkpoint stores it (HWIO), on the device
+ *   y  f32 [N,H,W,J], pixel stride ld_y, or NULL the forward's output AFTER its ReLU; NULL for a layer without one
+ *   dy f32 [N,H,W,J], pixel stride ld_dy         d loss / d y
+ *     g  = dy, or y > 0 ? dy : 0 with a y (exact zeros of y mask, and so does a NaN in y, as in xdet_dense_backward)
+ *     xe = x,  or x > 0 ? x : 0 with relu_in (a NaN in x counts as 0 and gets the gradient 0)
+ *   -> dx f32 [N,H,W,C], pixel stride ld_dx (NULL: skipped): dx[n,h,w,c] = sum over taps (a,b) and j of
+ *        g[n, h - a + kh/2, w - b + kw/2, j] * w[a,b,c,j] (terms outside the image are absent), and with relu_in 0 wherever
+ *        x > 0 is false;
+ *      dw f32 [kh,kw,C,J] dense: dw[a,b,c,j] = sum over pixels of xe[n, h + a - kh/2, w + b - kw/2, c] * g[n,h,w,j];
+ *      db f32 [J] = column sums of g.
+ * A shift never leaves its image or its image row: what lies outside counts as zero and is not read.  Channels at or beyond
+ * a tensor's count (C for x and dx, J for y and dy) are never read -- padding may hold NaN -- and nothing is written to dx
+ * beyond channel C - 1.  The detector's buffers go in as they are: x = "mid_x" with relu_in, y = "rpn_hidden", dy = the dx of the
+ * xdet_dense_backward call over the RPN's two 1x1 heads.
+ * Arithmetic: as xdet_dense_backward -- both products on the matrix pipe in split precision (hi*hi + hi*lo + lo*hi, f32
+ *   accumulation), each of xe, w and g under a power of two of its own, 2^(11 - floor(log2(max |v|))) over the operand
+ *   (channels inside the count only; 2^0 for an all-zero operand), found by a pre-pass on the device and taken out again
+ *   exactly: scaling dy by a power of two scales dx, dw and db by exactly that power.  db is summed in f32.
+ * Order of the sums: dx reduces over (tap, j), taps in storage order, in one pipeline.  dw's sum over the M pixels is cut
+ *   into ranges by xdet_dense_backward's rule with tiles = ceil(kh * kw * C / 128) * ceil(J / (J <= 32 ? 32 : 128)), the
+ *   ranges added in index order; db in chunks of max(64, ceil(M / 1024)) pixels added in index order.  No float atomics:
+ *   the same call gives the same bits.
+ * workspace: xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw) bytes (never 0 inside the limits, 0 outside them); it
+ *   needs no initialisation and may be larger.  The call does not synchronise and reads nothing on the host.  No patch
+ *   matrix is written anywhere: both products fetch the shifted pixels as they go.
+ * Limits: kh, kw odd and <= 15; C, J <= 4096; M * max(C, J, every ld given) < 2^31.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, an even kh or kw, ld_x < C,
+ *   ld_dy < J, ld_y < J with a y, ld_dx < C with a dx, a NULL x, w, dy, dw, db or workspace. */
+size_t xdet_conv_backward_workspace_bytes(int N, int H, int W, int C, int J, int kh, int kw);
+int xdet_conv_backward(const float* x, int ld_x, const float* w, const float* y, int ld_y, const float* dy, int ld_dy, int N,
+                       int H, int W, int C, int J, int kh, int kw, int relu_in, float* dx, int ld_dx, float* dw, float* db,
+                       void* workspace, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {
@@ -638,13 +675,18 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   all activations.
  *   "pool_index" = "off" | "keep": the head's PsRoiAlign also writes its argmax sample ids into an i32 buffer
  *   [max_batch * R, C] (ld of "pooled"; xdet_net_buffer "pool_index"), which xdet_net_head_pool_backward needs.  off
- *   (default): the forward is the same call as ever and the buffer does not exist. */
+ *   (default): the forward is the same call as ever and the buffer does not exist.
+ *   "rpn_hidden" = "off" | "keep": rpn_head/conv2d (net/xception_body.py:384) also writes its output after the ReLU as an
+ *   f32 tensor [max_batch, h, w, 512] (xdet_net_buffer "rpn_hidden"), the ReLU mask and dense-layer input of the RPN head's
+ *   backward (xdet_dense_backward, then xdet_conv_backward).  off (default): the conv writes the split planes its 1x1
+ *   heads read and nothing else, and the name is refused.  "rpn_out" has the same bits either way. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
 /* named workspace buffers (views, owned by the net): "mid","out","rpn_out","feat","objectness",
  * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts"; "pool_index" (i32, dims / ld of "pooled")
- * with option "pool_index" = "keep" only, otherwise XDET_ERR_INVALID_ARG */
+ * with option "pool_index" = "keep" only, "rpn_hidden" (f32 [max_batch,h,w,512]) with option "rpn_hidden" = "keep" only,
+ * otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */

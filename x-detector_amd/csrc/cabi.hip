@@ -583,6 +583,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->keep_pool_index = v == "keep";
     return XDET_OK;
   }
+  if (k == "rpn_hidden") {
+    XDET_REQUIRE(v == "keep" || v == "off", "rpn_hidden must be keep | off");
+    n->keep_rpn_hidden = v == "keep";
+    return XDET_OK;
+  }
   set_last_error("unknown option: " + k);
   return XDET_ERR_INVALID_ARG;
 }
@@ -613,6 +618,10 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
     XDET_REQUIRE(n->pool_index != nullptr, "net_buffer: pool_index needs a net built with the option pool_index=keep");
     from_buf(n->pooled);
     *dptr = n->pool_index;
+  }
+  else if (s == "rpn_hidden") {
+    XDET_REQUIRE(n->rpn_hidden.p != nullptr, "net_buffer: rpn_hidden needs a net built with the option rpn_hidden=keep");
+    from_buf(n->rpn_hidden);
   }
   else if (s == "fc") from_buf(n->fc);
   else if (s == "cls_reg") from_buf(n->cls_reg);

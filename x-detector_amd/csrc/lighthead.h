@@ -15,6 +15,8 @@ struct LightHeadNet : Plan {
   float *objectness = nullptr, *rpn_boxes = nullptr, *proposals = nullptr, *head_boxes = nullptr;
   int32_t* pool_index = nullptr;  // [B * R][pooled.ld] argmax sample ids of the head's PsRoiAlign (option "pool_index" = "keep")
   bool keep_pool_index = false;
+  Buf rpn_hidden;                 // relu(rpn_head/conv2d) as f32 [B,h,w,512] (option "rpn_hidden" = "keep"; p stays NULL without)
+  bool keep_rpn_hidden = false;
   float* class_probs = nullptr;   // [B][num_classes][R] softmax of the head's logits, class-major (head_decode_probs_kernel)
   float *anc_yx = nullptr, *anc_hw = nullptr;
   float* mid_relu = nullptr;   // materialised ReLU(x) ("mid_outputs", xception_body.py:339) for API users

@@ -145,12 +145,14 @@ int LightHeadNet::build_rpn() {
   XDET_TRY(L0->init(3, 3, 728, 512, 1, 1, 1, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
   Buf hid;
   ConvEmit hid_emit;
-  hid_emit.planes = 3;    // only the fused 1x1 heads read it
+  // only the fused 1x1 heads read it: planes alone -- unless the RPN's backward wants the f32 tensor for its ReLU mask
+  hid_emit.planes = keep_rpn_hidden ? 1 : 3;
   // (a single image is 8 x 4 tiles against 207 K steps.  Fixed split-K -- option "ksplit" = "all" -- takes it from 116 to
   //  37 us, but costs the 256 x 256 tile at bench-size batches: 1.92 -> 2.36 ms per 128 images, -0.9 % end to end.
   //  With the fork in front of the exit flow the conv is off the critical path of a single image anyway.)
   hid_emit.ksplit = latency_ksplit && rpn_ksplit;
   XDET_TRY(add_conv("rpn_head/conv2d", ST_RPN, mid_x, L0, nullptr, /*relu_in=*/1, &hid, hid_emit));
+  if (keep_rpn_hidden) rpn_hidden = hid;      // a named buffer: never handed back to the pool
   // cls (2A) and box (4A) 1x1 heads share their input: one GEMM over the concatenated filters
   const int co = 6 * A;
   std::vector<float> kc((size_t)512 * co), bc(co);

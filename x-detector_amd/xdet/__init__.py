@@ -23,6 +23,9 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   augment (preprocess_train, host_preprocess_train, draw)
   (xdet.augment)          <- preprocessing/common_preprocessing.py:212-262, 328-381; preprocessing/tf_image.py:322-346,
                              393-630: the training ingest (colour distortion, expand / patch sampling, flip, warp)
+  dense_backward, conv_backward, host_dense_backward, host_conv_backward; rpn_backward, head_backward (xdet.model)
+  (xdet.ops)              <- what tf.gradients derives for the reference's dense layers and stride-1 'SAME' convs
+                             (net/xception_body.py:381-400, 536-557): the RPN head's and the detection head's backward
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

@@ -30,6 +30,7 @@ SOURCES = [
     ('targets.hip', ['-ffp-contract=off']),
     ('losses.hip', ['-ffp-contract=off']),
     ('dense_backward.hip', []),
+    ('conv_backward.hip', []),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

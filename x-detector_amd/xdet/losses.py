@@ -31,7 +31,14 @@ MAX_SELECTED = 32768      # N * anchors_per_image
 MAX_ROIS = 8192           # P
 MAX_CLASSES = 128         # C
 
-RpnLossResult = collections.namedtuple('RpnLossResult', 'losses sel_index counts grad_cls grad_loc')
+
+
+class RpnLossResult(collections.namedtuple('RpnLossResult', 'losses sel_index counts grad_cls grad_loc')):
+    """The five fields unpack as ever; `grad_device` (an attribute, not a field) is d loss / d rpn_out left on the GPU by
+    rpn_loss(..., keep_device=True): a DeviceTensor [N,h,w,6A] with the rpn_out buffer's ld, else None."""
+    grad_device = None
+
+
 HeadLossResult = collections.namedtuple('HeadLossResult', 'losses per_roi select grad_cls grad_reg')
 
 
@@ -160,12 +167,16 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
-def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio, seed=0, sigma=1., with_grad=True, stream=None):
+def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio, seed=0, sigma=1., with_grad=True, stream=None,
+             keep_device=False):
     """host_rpn_loss on the GPU (xdet_rpn_loss), the same results.  cls_score / bbox_pred: NumPy [N,Hh,Ww,2A] / [N,Hh,Ww,4A]
     (or [N,n,2A] / [N,n,4A]), or the two DeviceTensor views model.get_rpn returns -- then the detector's rpn_out buffer is
     read in place, nothing is copied.  labels [N,n_a] / targets [N,n_a,4]: NumPy or device buffers (DeviceBuffer /
     DeviceTensor, as xdet_encode_anchors wrote them).  The gradients come back in the layout of the inputs:
-    grad_cls [N,...,2A], grad_loc [N,...,4A] (None without with_grad)."""
+    grad_cls [N,...,2A], grad_loc [N,...,4A] (None without with_grad).
+    keep_device=True (the two views of get_rpn, cls_score [N,h,w,2A] followed by bbox_pred, and with_grad): the result's
+    `grad_device` also carries the gradient as the GPU wrote it, a DeviceTensor [N,h,w,6A] with rpn_out's ld -- what
+    model.rpn_backward reads."""
     from ._lib import lib, check, InvalidArgumentError
     from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
     if isinstance(cls_score, DeviceTensor) != isinstance(bbox_pred, DeviceTensor):
@@ -185,6 +196,9 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
             raise InvalidArgumentError(-1, 'rpn_loss: cls_score [N,..,2A] and bbox_pred [N,..,4A] expected, got %r and %r' % (c.shape, b.shape))
         cls_off, box_off = 0, _round_up(2 * A, 4)
         ld = box_off + 4 * A
+    if keep_device and not (on_device and with_grad and len(shp) == 4 and cls_off == 0 and box_off == 2 * A):
+        raise InvalidArgumentError(-1, 'rpn_loss: keep_device=True needs with_grad and the two DeviceTensor views model.get_rpn '
+                                       'returns ([N,h,w,2A] and, right behind it, [N,h,w,4A])')
     N, hw = int(shp[0]), int(np.prod(shp[1:-1]))
     S = N * int(anchors_per_image)
     fgr, sg = float(fg_ratio), float(sigma)
@@ -217,8 +231,11 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
         g = to_host(d_grad.ptr, (N, hw, ld), f32)
         g_cls = np.ascontiguousarray(g[..., cls_off:cls_off + 2 * A]).reshape(shp)
         g_loc = np.ascontiguousarray(g[..., box_off:box_off + 4 * A]).reshape(tuple(shp[:-1]) + (4 * A,))
-    return RpnLossResult(to_host(d_loss.ptr, (3,), f32), to_host(d_sel.ptr, (S,), np.int32), to_host(d_cnt.ptr, (4,), np.int32),
-                         g_cls, g_loc)
+    res = RpnLossResult(to_host(d_loss.ptr, (3,), f32), to_host(d_sel.ptr, (S,), np.int32), to_host(d_cnt.ptr, (4,), np.int32),
+                        g_cls, g_loc)
+    if keep_device:
+        res.grad_device = DeviceTensor(d_grad.ptr, tuple(shp[:3]) + (6 * A,), ld, owner=d_grad)
+    return res
 
 
 def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=1., num_classes=None, with_grad=True, stream=None,

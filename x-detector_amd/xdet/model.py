@@ -22,7 +22,7 @@ class LightHeadDetector(object):
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
-                 pool_index=False):
+                 pool_index=False, rpn_hidden=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -32,7 +32,9 @@ class LightHeadDetector(object):
         contractions, the dominant ones) are computed from fp8 copies of the operands (the "x8" form, include/xdet.h) -- once
         calibrate() has measured the tensors; until then, and with 'f16', everything is f16x3.
         pool_index=True: the head's PsRoiAlign keeps its argmax sample ids (buffer 'pool_index'), which
-        head_backward(..., to_feat=True) needs; the default forward writes none and allocates nothing for them."""
+        head_backward(..., to_feat=True) needs; the default forward writes none and allocates nothing for them.
+        rpn_hidden=True: rpn_head/conv2d keeps its f32 output (buffer 'rpn_hidden'), which rpn_backward needs; the default
+        forward writes only the split planes the 1x1 heads read."""
         if device is not None:
             check(lib().xdet_set_device(int(device)))
         self.cfg = LightHeadConfig(image_size=image_size, max_batch=max_batch, num_classes=num_classes,
@@ -44,10 +46,13 @@ class LightHeadDetector(object):
         check(lib().xdet_net_create(ctypes.byref(h), ctypes.byref(self.cfg)))
         self.handle = h
         self._head_kernels = {}            # the dense layers' kernels as the checkpoint stores them (head_backward)
+        self._rpn_kernels = {}             # ... and the RPN head's three (rpn_backward)
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, np.float32)
             if name in ('final_head/subnet_fc/kernel', 'final_head/fc_cls/kernel', 'final_head/fc_loc/kernel'):
                 self._head_kernels[name] = a
+            if rpn_hidden and name in ('rpn_head/conv2d/kernel', 'rpn_head/conv2d_1/kernel', 'rpn_head/conv2d_2/kernel'):
+                self._rpn_kernels[name] = a
             dims = (ctypes.c_int64 * a.ndim)(*a.shape)
             check(lib().xdet_net_set_weight(self.handle, name.encode(), _host(a), a.ndim, dims))
         check(lib().xdet_net_set_option(self.handle, b'large_sep', large_sep.encode()))
@@ -64,7 +69,9 @@ class LightHeadDetector(object):
         check(lib().xdet_net_set_option(self.handle, b'cross', cross.encode()))
         if pool_index:
             check(lib().xdet_net_set_option(self.handle, b'pool_index', b'keep'))
-        self.pool_index = bool(pool_index)
+        if rpn_hidden:
+            check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
+        self.pool_index, self.rpn_hidden = bool(pool_index), bool(rpn_hidden)
         check(lib().xdet_net_build(self.handle))
         self.max_batch = max_batch
         self.image_size = image_size
@@ -544,3 +551,51 @@ def head_backward(loss_func, to_feat=False):
     if to_feat:
         out['feat'] = d_feat
     return out
+
+
+def rpn_backward(rpn_loss_result):
+    """The backward of the RPN head (net/xception_body.py:381-400), called after get_rpn and losses.rpn_loss(...,
+    keep_device=True) on a detector built with rpn_hidden=True: d loss / d rpn_out (rpn_loss_result.grad_device, what
+    xdet_rpn_loss wrote) goes through the two 1x1 heads as one dense layer (xdet_dense_backward: x = the net's `rpn_hidden`
+    buffer as [N*h*w, 512] rows, the concatenated [512, 6A] kernel) and then, masked by the hidden ReLU, through the 3x3 conv
+    (xdet_conv_backward: x = `mid_x` with the ReLU in front of the conv, y = `rpn_hidden`) -- both on the detector's stream
+    with no host round trip in between.  -> a dict with the six gradients under the checkpoint's variable names
+    (rpn_head/{conv2d,conv2d_1,conv2d_2}/{kernel,bias}, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with
+    `mid_x`'s ld (zero where mid_x <= 0) and 'rpn_hidden': d loss / d rpn_hidden (in front of the ReLU mask) [N,h,w,512]."""
+    from . import ops
+    d = _det()
+    if not d.rpn_hidden:
+        raise InvalidArgumentError(-1, 'rpn_backward: needs a detector built with rpn_hidden=True (the RPN conv kept no f32 '
+                                       'output to go back through)')
+    g = getattr(rpn_loss_result, 'grad_device', None)
+    if g is None:
+        raise InvalidArgumentError(-1, 'rpn_backward: the loss left no gradient on the device (call losses.rpn_loss(..., '
+                                       'keep_device=True) on the tensors get_rpn returned)')
+    if len(d._rpn_kernels) != 3:
+        raise InvalidArgumentError(-1, 'rpn_backward: the detector was built without the rpn_head kernels')
+    n, A = g.shape[0], d.cfg.num_anchors
+    out_view = d.buffer('rpn_out', min(max(n, 1), d.max_batch))
+    if n > d.max_batch or tuple(g.shape[1:]) != tuple(out_view.shape[1:3]) + (6 * A,) or g.ld != out_view.ld:
+        raise InvalidArgumentError(-1, 'rpn_backward: gradient of shape %r (ld %d) but the detector\'s rpn_out is %r (ld %d), '
+                                       'max_batch %d' % (g.shape, g.ld, tuple(out_view.shape[1:]), out_view.ld, d.max_batch))
+    if not hasattr(d, '_rpn_kernels_dev'):
+        k0 = d._rpn_kernels['rpn_head/conv2d/kernel']
+        k1 = np.ascontiguousarray(np.concatenate([d._rpn_kernels['rpn_head/conv2d_1/kernel'].reshape(-1, 2 * A),
+                                                  d._rpn_kernels['rpn_head/conv2d_2/kernel'].reshape(-1, 4 * A)], axis=1))
+        b0, b1 = to_device(k0), to_device(k1)
+        d._rpn_kernels_dev = (DeviceTensor(b0.ptr, k0.shape, k0.shape[3], owner=b0),
+                              DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
+    w0, w1 = d._rpn_kernels_dev
+    hid, mid_x = d.buffer('rpn_hidden', n), d.buffer('mid_x', n)
+    dx1, dw1, db1 = ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
+    d_hid = DeviceTensor(dx1.ptr, hid.shape, dx1.ld, owner=dx1)
+    dx0, dw0, db0 = ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
+    _sync(d)
+    J = w0.shape[3]
+    kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
+    return {'rpn_head/conv2d/kernel': to_host(dw0.ptr, w0.shape), 'rpn_head/conv2d/bias': to_host(db0.ptr, (J,)),
+            'rpn_head/conv2d_1/kernel': np.ascontiguousarray(kw1[:, :2 * A]).reshape(1, 1, J, 2 * A),
+            'rpn_head/conv2d_1/bias': kb1[:2 * A].copy(),
+            'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
+            'rpn_head/conv2d_2/bias': kb1[2 * A:].copy(),
+            'mid': dx0, 'rpn_hidden': d_hid}

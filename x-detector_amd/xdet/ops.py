@@ -881,3 +881,103 @@ def dense_backward(x, w, dy, y=None, with_dx=True, stream=None):
     K = d_dw.nbytes // (4 * J)
     dx = to_host(d_dx.ptr, (d_dx.shape[0], K), np.float32, stream) if d_dx is not None else None
     return dx, to_host(d_dw.ptr, (K, J), np.float32, stream), to_host(d_db.ptr, (J,), np.float32, stream)
+
+
+# ---- the backward of a stride-1 'SAME' convolution (xdet_conv_backward, csrc/conv_backward.hip) ------------------------
+
+def host_conv_backward(x, w, dy, y=None, relu_in=False, dtype=np.float32, with_dx=True):
+    """The NumPy statement of xdet_conv_backward (include/xdet.h) for y = act(conv(xe, w) + b), stride 1, 'SAME', NHWC:
+    x [N,H,W,C], w [kh,kw,C,J] (kh, kw odd), dy [N,H,W,J], y [N,H,W,J] the forward's output after its ReLU (None: no ReLU);
+    xe = x, or with relu_in x where x > 0 and 0 elsewhere -> (dx [N,H,W,C], dw [kh,kw,C,J], db [J]) with g = dy, or dy where
+    y > 0 and 0 elsewhere (an exact zero and a NaN both give 0, in y and in x); with relu_in dx is 0 wherever x > 0 is
+    false.  One matrix product per tap, the taps added in storage order.  dtype float32, or float64: the accuracy yardstick.
+    with_dx=False: dx is None."""
+    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
+    N, H, W, C = x.shape
+    kh, kw, _, J = w.shape
+    g, xe = dy, x
+    with np.errstate(invalid='ignore'):
+        if y is not None:
+            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
+        if relu_in:
+            xe = np.where(x > 0, x, dtype(0))
+    ph, pw = kh // 2, kw // 2
+    border = ((0, 0), (ph, ph), (pw, pw), (0, 0))
+    xp, gp = np.pad(xe, border), np.pad(g, border)
+    g2 = g.reshape(-1, J)
+    dw = np.empty(w.shape, dtype)
+    dx = np.zeros((N * H * W, C), dtype) if with_dx else None
+    for a in range(kh):
+        for b in range(kw):
+            dw[a, b] = np.matmul(xp[:, a:a + H, b:b + W].reshape(-1, C).T, g2)
+            if with_dx:
+                dx += np.matmul(gp[:, 2 * ph - a:2 * ph - a + H, 2 * pw - b:2 * pw - b + W].reshape(-1, J), w[a, b].T)
+    if with_dx:
+        dx = dx.reshape(x.shape)
+        if relu_in:
+            with np.errstate(invalid='ignore'):
+                dx = np.where(x > 0, dx, dtype(0))
+    return dx, dw, g2.sum(axis=0, dtype=dtype)
+
+
+def _nhwc(a, what):
+    """a DeviceTensor or a 4-D array -> (shape, DeviceTensor or f32 array)"""
+    if isinstance(a, DeviceTensor):
+        return tuple(a.shape), a
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 4:
+        raise InvalidArgumentError(-1, 'conv_backward: %s must have four dimensions, got shape %r' % (what, a.shape))
+    return a.shape, a
+
+
+def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
+    """conv_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
+    dw DeviceBuffer [kh,kw,C,J], db DeviceBuffer [J]); nothing is synchronised.  A DeviceTensor w is [kh,kw,C,J] dense."""
+    (N, H, W, C), x_in = _nhwc(x, 'x')
+    (kh, kw, Cw, J), w_in = _nhwc(w, 'w')
+    sd, dy_in = _nhwc(dy, 'dy')
+    bad = Cw != C or sd != (N, H, W, J)
+    if y is not None:
+        sy, y_in = _nhwc(y, 'y')
+        bad = bad or sy != (N, H, W, J)
+    if bad:
+        raise InvalidArgumentError(-1, 'conv_backward: x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J] and y [N,H,W,J] expected, got %r'
+                                   % ([(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else []),))
+    M = N * H * W
+    if (min(M, C, J, kh, kw) <= 0 or kh % 2 == 0 or kw % 2 == 0 or max(kh, kw) > 15 or max(C, J) > 4096
+            or M * max(C, J) >= 2 ** 31):
+        raise InvalidArgumentError(-1, 'conv_backward: N*H*W = %d, C = %d, J = %d, kernel %d x %d (sizes positive, kh and kw odd '
+                                       'and at most 15, C and J at most 4096, N*H*W * max(C, J) below 2^31)' % (M, C, J, kh, kw))
+    if isinstance(w_in, DeviceTensor) and w_in.ld != J:
+        raise InvalidArgumentError(-1, 'conv_backward: w must be dense on the device (ld %d, J = %d)' % (w_in.ld, J))
+
+    def dev(a, width):
+        if isinstance(a, DeviceTensor):
+            return a, a.ptr, a.ld
+        b = to_device(a)
+        return b, b.ptr, width
+    kx, px, ldx = dev(x_in, C)
+    kw_, pw, _ = dev(w_in, J)
+    kd, pd, ldd = dev(dy_in, J)
+    ky, py, ldy = dev(y_in, J) if y is not None else (None, None, 0)
+    d_dx = DeviceTensor.empty((N, H, W, C), ld=ldx) if with_dx else None
+    d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
+    ws = DeviceBuffer(lib().xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw))
+    check(lib().xdet_conv_backward(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, 1 if relu_in else 0,
+                                   d_dx.ptr if with_dx else None, ldx, d_dw.ptr, d_db.ptr, ws.ptr,
+                                   stream.handle if stream else None))
+    if d_dx is not None:
+        d_dx._keep = (kx, kw_, kd, ky, ws)     # operands and workspace live until the stream has run the call
+    d_dw._keep = (kx, kw_, kd, ky, ws)
+    return d_dx, d_dw, d_db
+
+
+def conv_backward(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
+    """host_conv_backward on the GPU (xdet_conv_backward): x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J], y [N,H,W,J] or None as
+    NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [kh,kw,C,J], db [J]) as NumPy
+    arrays."""
+    d_dx, d_dw, d_db = conv_backward_device(x, w, dy, y, relu_in, with_dx, stream)
+    synchronize(stream)
+    ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
+    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
+    return dx, to_host(d_dw.ptr, ws, np.float32, stream), to_host(d_db.ptr, (ws[-1],), np.float32, stream)
