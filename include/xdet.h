@@ -628,6 +628,51 @@ int xdet_conv_backward(const float* x, int ld_x, const float* w, const float* y,
                        int H, int W, int C, int J, int kh, int kw, int relu_in, float* dx, int ld_dx, float* dw, float* db,
                        void* workspace, void* stream);
 
+/* ---- batch normalisation over NHWC rows, forward and backward, with batch or moving statistics (csrc/batchnorm.hip; the
+ * NumPy statements of the same contract are xdet.ops.host_batch_norm_forward / host_batch_norm_backward).  A tensor is
+ * M = N * H * W rows of C channels with a row stride ld >= C; every statistic is per channel -----------------------------
+ *   x f32 [M,C], row stride ld_x;  gamma, beta f32 [C];  eps, momentum: the layer's constants (the reference uses 1e-5 and
+ *   0.997 for the large-separable block, net/resnet_v2.py, and 1e-4 and 0.99 for the Xception layers)
+ * Forward, training != 0:
+ *     mean[c] = sum_m x[m,c] / M,   var[c] = sum_m (x[m,c] - mean[c])^2 / M   -- centred on the finished mean: two sum passes
+ *     over x.  E[x^2] - E[x]^2 is not this contract (it loses the variance of a channel whose mean is large).
+ *     invstd = 1 / sqrt(var + eps);  xhat = (x - mean) * invstd;  y = xhat * gamma + beta, then max(., 0) when relu != 0
+ *     -> y f32 [M,C], row stride ld_y;  save_mean, save_invstd f32 [C] (what the backward takes)
+ *     moving_mean, moving_var f32 [C] (both or neither; NULL: no update): TensorFlow's fused update
+ *       moving_mean -= (moving_mean - mean) * (1 - momentum);   moving_var -= (moving_var - var * M / max(M - 1, 1)) * (1 - momentum)
+ * Forward, training == 0: the same y with mean = moving_mean, var = moving_var, which are required and not written;
+ *     save_mean and save_invstd receive what was used.
+ * Backward:  y f32 [M,C], row stride ld_y, or NULL: the forward's output AFTER its ReLU;  dy f32 [M,C], row stride ld_dy
+ *     g = dy, or y > 0 ? dy : 0 with a y (exact zeros of y mask, and so does a NaN in y, as in xdet_dense_backward); the
+ *     mask is the forward's own y, never a recomputed one.  xhat is recomputed from x, save_mean and save_invstd.
+ *     -> dbeta f32 [C] = sum_m g;   dgamma f32 [C] = sum_m g * xhat;
+ *        dx f32 [M,C], row stride ld_dx (NULL: skipped; dgamma and dbeta are written all the same)
+ *           = gamma * invstd * (g - dbeta / M - xhat * dgamma / M)   training != 0 (the gradient through the statistics)
+ *           = gamma * invstd * g                                     training == 0
+ * Channels at or beyond C are never read -- padding may hold NaN -- and nothing is written beyond channel C - 1 of y or dx.
+ * x must not overlap y or dx (x is read again after the first rows of the output are written).
+ * Order of the sums: every per-channel sum over the M rows is cut into chunks of max(64, ceil(M / 1024)) rows (at most 1024
+ *   chunks).  Inside a chunk the rows are dealt to sixteen sums by (row - first row of the chunk) mod 16, each added in row
+ *   order, and the sixteen are added in index order; the chunks are then added in index order.  All of it depends on M alone:
+ *   pointer alignment and strides (vector or scalar loads) do not change a bit.  No float atomics: the same call gives the
+ *   same bits, whatever the workspace held.  Every sum is a plain f32 add of plain f32 products (no fused multiply-add, no
+ *   rescaling), and the divisions by M are f32 divisions, so scaling dy by a power of two scales dx, dgamma and dbeta by
+ *   exactly that power (bit for bit, short of f32 underflow).
+ * workspace: xdet_batch_norm_workspace_bytes(M, C) bytes for either call (never 0 inside the limits, 0 outside them); it
+ *   needs no initialisation and may be larger.  Neither call synchronises or reads anything on the host.
+ * Limits: C <= 4096; M * max(C, every ld given) < 2^31.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, an ld below C (ld_y and ld_dx only
+ *   with a y / dx in the backward), a NULL x, gamma, beta, y, save_mean, save_invstd (forward), a NULL x, dy, gamma,
+ *   save_mean, save_invstd, dgamma, dbeta (backward), a NULL workspace, training == 0 without both moving statistics, one
+ *   moving statistic without the other. */
+size_t xdet_batch_norm_workspace_bytes(int M, int C);
+int xdet_batch_norm_forward(const float* x, int ld_x, int M, int C, const float* gamma, const float* beta, float eps,
+                            int training, float momentum, float* moving_mean, float* moving_var, int relu, float* y, int ld_y,
+                            float* save_mean, float* save_invstd, void* workspace, void* stream);
+int xdet_batch_norm_backward(const float* x, int ld_x, const float* y, int ld_y, const float* dy, int ld_dy, int M, int C,
+                             const float* gamma, const float* save_mean, const float* save_invstd, int training, float* dx,
+                             int ld_dx, float* dgamma, float* dbeta, void* workspace, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

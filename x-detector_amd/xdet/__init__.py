@@ -26,6 +26,10 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   dense_backward, conv_backward, host_dense_backward, host_conv_backward; rpn_backward, head_backward (xdet.model)
   (xdet.ops)              <- what tf.gradients derives for the reference's dense layers and stride-1 'SAME' convs
                              (net/xception_body.py:381-400, 536-557): the RPN head's and the detection head's backward
+  batch_norm_forward, batch_norm_backward, host_batch_norm_forward, host_batch_norm_backward;
+  large_sep_kernel(..., is_training=True), large_sep_backward (xdet.model; LightHeadDetector(large_sep_train=True))
+  (xdet.ops)              <- tf.layers.batch_normalization with training=True and its gradient (net/xception_body.py:
+                             450-475): batch statistics, the moving-average updates, the large-separable block's backward
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

@@ -144,6 +144,11 @@ SIGNATURES = {
     'xdet_dense_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'xdet_dense_backward': (c_int, [PF, c_int, PF, PF, c_int, PF, c_int, c_int, c_int, c_int, PF, c_int, PF, PF, c_void_p,
                                     c_void_p]),
+    'xdet_batch_norm_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'xdet_batch_norm_forward': (c_int, [PF, c_int, c_int, c_int, PF, PF, c_float, c_int, c_float, PF, PF, c_int, PF, c_int, PF,
+                                        PF, c_void_p, c_void_p]),
+    'xdet_batch_norm_backward': (c_int, [PF, c_int, PF, c_int, PF, c_int, c_int, c_int, PF, PF, PF, c_int, PF, c_int, PF, PF,
+                                         c_void_p, c_void_p]),
     'xdet_conv_backward_workspace_bytes': (c_size_t, [c_int] * 7),
     'xdet_conv_backward': (c_int, [PF, c_int, PF, PF, c_int, PF, c_int] + [c_int] * 8 + [PF, c_int, PF, PF, c_void_p, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),

@@ -31,6 +31,7 @@ SOURCES = [
     ('losses.hip', ['-ffp-contract=off']),
     ('dense_backward.hip', []),
     ('conv_backward.hip', []),
+    ('batchnorm.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

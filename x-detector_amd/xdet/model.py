@@ -16,13 +16,44 @@ from .runtime import DeviceBuffer, DeviceTensor, Stream, to_device, to_host, syn
 
 _current = []
 
+LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
+                            for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
+    ('large_sep_feature/batch_normalization/gamma', 'large_sep_feature/batch_normalization/beta')
+LARGE_SEP_MOVING = ('large_sep_feature/batch_normalization/moving_mean', 'large_sep_feature/batch_normalization/moving_variance')
+LARGE_SEP_EPS, LARGE_SEP_MOMENTUM = 1e-5, 0.997        # net/resnet_v2.py: _BATCH_NORM_EPSILON, _BATCH_NORM_DECAY
+
+
+def merge_large_sep(weights, dtype=np.float32):
+    """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
+    native net's, without the BN fold): both (15,1) convs read the same input -> one kernel [15,1,cin,2*mid] with the
+    branches side by side along the outputs and the bias [2*mid]; branch_0b + branch_1b -> one (1,15) kernel [1,15,2*mid,co]
+    with the branches stacked along the inputs and the bias b0 + b1.  -> (K_a, b_a, K_b, b_b)"""
+    g = lambda br, name: np.asarray(weights['large_sep_feature/%s/%s' % (br, name)], dtype)
+    ka = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d/kernel'), g('Branch_1', 'conv2d/kernel')], axis=3))
+    ba = np.concatenate([g('Branch_0', 'conv2d/bias'), g('Branch_1', 'conv2d/bias')])
+    kb = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d_1/kernel'), g('Branch_1', 'conv2d_1/kernel')], axis=2))
+    return ka, ba, kb, g('Branch_0', 'conv2d_1/bias') + g('Branch_1', 'conv2d_1/bias')
+
+
+def split_large_sep_grads(d_ka, d_ba, d_kb, d_bb, mid):
+    """merge_large_sep's adjoint: the gradients of the merged tensors -> the eight conv gradients under the checkpoint's names
+    and in its shapes.  Both conv2d_1 biases enter the block as b0 + b1, so both get d_bb."""
+    out = {}
+    for i, br in enumerate(('Branch_0', 'Branch_1')):
+        p, sl = 'large_sep_feature/%s/' % br, slice(i * mid, (i + 1) * mid)
+        out[p + 'conv2d/kernel'] = np.ascontiguousarray(d_ka[..., sl])
+        out[p + 'conv2d/bias'] = np.ascontiguousarray(d_ba[sl])
+        out[p + 'conv2d_1/kernel'] = np.ascontiguousarray(d_kb[:, :, sl, :])
+        out[p + 'conv2d_1/bias'] = np.array(d_bb)
+    return out
+
 
 class LightHeadDetector(object):
     def __init__(self, weights, image_size=480, max_batch=1, num_classes=21, rpn_pre_nms_top_n=5000,
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
-                 pool_index=False, rpn_hidden=False):
+                 pool_index=False, rpn_hidden=False, large_sep_train=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -34,7 +65,12 @@ class LightHeadDetector(object):
         pool_index=True: the head's PsRoiAlign keeps its argmax sample ids (buffer 'pool_index'), which
         head_backward(..., to_feat=True) needs; the default forward writes none and allocates nothing for them.
         rpn_hidden=True: rpn_head/conv2d keeps its f32 output (buffer 'rpn_hidden'), which rpn_backward needs; the default
-        forward writes only the split planes the 1x1 heads read."""
+        forward writes only the split planes the 1x1 heads read.
+        large_sep_train=True: the ten large_sep_feature/ variables are kept as the checkpoint stores them, unfolded, and the
+        block's two merged kernels, biases, gamma, beta and moving statistics are put on the device:
+        large_sep_kernel(..., is_training=True) then runs the block with batch statistics (xdet_batch_norm_forward) and
+        large_sep_backward takes the gradient through it.  The default detector keeps none of this and allocates nothing for
+        it; is_training=False is the same forward either way."""
         if device is not None:
             check(lib().xdet_set_device(int(device)))
         self.cfg = LightHeadConfig(image_size=image_size, max_batch=max_batch, num_classes=num_classes,
@@ -84,6 +120,53 @@ class LightHeadDetector(object):
         self._det_scores = DeviceBuffer(B * nc * k * 4)
         self._det_boxes = DeviceBuffer(B * nc * k * 16)
         self._N = 0
+        self.large_sep_train = bool(large_sep_train)
+        if large_sep_train:
+            self._build_large_sep_train(weights)
+
+    def _build_large_sep_train(self, weights):
+        """the training form of the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as
+        dense device tensors for the backward, the BN vectors, and the tensors a training forward keeps"""
+        from . import ops
+        from .runtime import get_precision, set_precision
+        miss = [k for k in LARGE_SEP_VARIABLES + LARGE_SEP_MOVING if k not in weights]
+        if miss:
+            raise InvalidArgumentError(-1, 'large_sep_train: the weights lack %s' % ', '.join(miss))
+        self._large_sep_variables = {k: np.ascontiguousarray(weights[k], np.float32) for k in LARGE_SEP_VARIABLES + LARGE_SEP_MOVING}
+        ka, ba, kb, bb = merge_large_sep(self._large_sep_variables)
+        before = get_precision()
+        set_precision('f16x3')
+        try:
+            conv_a, conv_b = ops.Conv2D(ka, shift=ba), ops.Conv2D(kb, shift=bb)
+        finally:
+            set_precision(before)
+
+        def dense(k):
+            b = to_device(k)
+            return DeviceTensor(b.ptr, k.shape, k.shape[3], owner=b)
+        bn = 'large_sep_feature/batch_normalization/'
+        B, (_, H, W, _) = self.max_batch, self.buffer('out', 1).shape
+        co, mid2 = kb.shape[3], ka.shape[3]
+        vec = lambda a: to_device(np.ascontiguousarray(a, np.float32))
+        ws = max(lib().xdet_batch_norm_workspace_bytes(n * H * W, co) for n in range(1, B + 1))
+        self._lsep = {'conv_a': conv_a, 'conv_b': conv_b, 'K_a': dense(ka), 'K_b': dense(kb), 'mid': mid2 // 2,
+                      'gamma': vec(weights[bn + 'gamma']), 'beta': vec(weights[bn + 'beta']),
+                      'moving_mean': vec(weights[bn + 'moving_mean']), 'moving_variance': vec(weights[bn + 'moving_variance']),
+                      't': DeviceTensor.empty((B, H, W, mid2)), 'z': DeviceTensor.empty((B, H, W, co)),
+                      'save_mean': DeviceBuffer(co * 4), 'save_invstd': DeviceBuffer(co * 4), 'ws': DeviceBuffer(ws), 'n': 0}
+
+    def large_sep_saved(self):
+        """what the last large_sep_kernel(..., is_training=True) left on the device, as DeviceTensors: 't' [n,h,w,2*mid] =
+        conv_a(out) + b_a, 'z' [n,h,w,co] = conv_b(t) + b_b (the batch norm's input), 'save_mean' and 'save_invstd'
+        [1,1,1,co] (the batch statistics), 'moving_mean' and 'moving_variance' [1,1,1,co] (after their update)"""
+        if not self.large_sep_train or not self._lsep['n']:
+            raise InvalidArgumentError(-1, 'large_sep_saved: no large_sep_kernel(..., is_training=True) has run on this detector')
+        s, n = self._lsep, self._lsep['n']
+        out = {k: DeviceTensor(s[k].ptr, (n,) + s[k].shape[1:], s[k].ld, owner=s[k]) for k in ('t', 'z')}
+        co = s['z'].shape[3]
+        for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
+            out[k] = DeviceTensor(s[k].ptr, (1, 1, 1, co), co, owner=s[k])
+        return out
 
     # ---- plumbing -------------------------------------------------------------------
     def buffer(self, name, n=None):
@@ -412,12 +495,32 @@ def get_rpn(net_input, num_anchors, is_training, data_format, var_scope):
 
 
 def large_sep_kernel(net_input, depth_mid, depth_output, is_training, data_format, var_scope):
-    """net/xception_body.py:450-475 -> thin feature map [N,h,w,depth_output]."""
+    """net/xception_body.py:450-475 -> thin feature map [N,h,w,depth_output].
+    is_training=True (a detector built with large_sep_train=True): the block as the reference trains it, t = conv_a(out) + b_a,
+    z = conv_b(t) + b_b on the merged kernels (xdet_conv_forward, split precision, f32 out), then feat = relu(bn(z)) with the
+    batch's statistics and the moving-average updates (xdet_batch_norm_forward, eps 1e-5, momentum 0.997) written straight
+    into the net's `feat` buffer -- three calls on the detector's stream with no host round trip in between.  t, z and the
+    statistics stay on the device (detector.large_sep_saved()) for large_sep_backward."""
     d = _det()
     n = net_input.shape[0]
+    if is_training and not d.large_sep_train:
+        raise InvalidArgumentError(-1, 'large_sep_kernel: is_training=True needs a detector built with large_sep_train=True '
+                                       '(the default detector folds the moving statistics into the conv weights)')
     view = d.buffer('out', n)
     if not _same(net_input, view):
         d.write('out', net_input.numpy() if isinstance(net_input, DeviceTensor) else net_input)
+    if is_training:
+        s, feat, h = d._lsep, d.buffer('feat', n), d.stream.handle
+        _, H, W, _ = view.shape
+        t, z = s['t'], s['z']
+        check(lib().xdet_conv_forward(s['conv_a'].handle, view.ptr, n, H, W, view.ld, t.ptr, t.ld, None, 0, h))
+        check(lib().xdet_conv_forward(s['conv_b'].handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
+        check(lib().xdet_batch_norm_forward(z.ptr, z.ld, n * H * W, z.shape[3], s['gamma'].ptr, s['beta'].ptr, LARGE_SEP_EPS, 1,
+                                            LARGE_SEP_MOMENTUM, s['moving_mean'].ptr, s['moving_variance'].ptr, 1, feat.ptr,
+                                            feat.ld, s['save_mean'].ptr, s['save_invstd'].ptr, s['ws'].ptr, h))
+        s['n'] = n
+        _sync(d)
+        return feat
     check(lib().xdet_net_large_sep(d.handle, n, d.stream.handle))
     _sync(d)
     return d.buffer('feat', n)
@@ -599,3 +702,39 @@ def rpn_backward(rpn_loss_result):
             'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
             'rpn_head/conv2d_2/bias': kb1[2 * A:].copy(),
             'mid': dx0, 'rpn_hidden': d_hid}
+
+
+def large_sep_backward(d_feat):
+    """The backward of the large-separable block in training mode, called after large_sep_kernel(..., is_training=True) on a
+    detector built with large_sep_train=True: d_feat = head_backward(..., to_feat=True)['feat'] (d loss / d feat, with the
+    `feat` buffer's shape and ld) goes through the batch norm and its ReLU (xdet_batch_norm_backward on the kept z, masked
+    by the net's own `feat`), then through the merged (1,15) conv (xdet_conv_backward, x = the kept t) and the merged (15,1)
+    conv (x = the net's `out`) -- three calls on the detector's stream with no host round trip in between.  -> a dict with the
+    ten gradients under the checkpoint's variable names and in its shapes (the merged tensors split back; both conv2d_1
+    biases get the merged bias gradient), 'out': d loss / d out as a DeviceTensor [N,h,w,2048] with `out`'s ld, 'z':
+    d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read)."""
+    from . import ops
+    d = _det()
+    if not d.large_sep_train:
+        raise InvalidArgumentError(-1, 'large_sep_backward: needs a detector built with large_sep_train=True')
+    s = d._lsep
+    n = s['n']
+    if not n:
+        raise InvalidArgumentError(-1, 'large_sep_backward: call large_sep_kernel(..., is_training=True) first')
+    feat, out = d.buffer('feat', n), d.buffer('out', n)
+    if not isinstance(d_feat, DeviceTensor) or tuple(d_feat.shape) != tuple(feat.shape) or d_feat.ld != feat.ld:
+        raise InvalidArgumentError(-1, 'large_sep_backward: d_feat must be a DeviceTensor of shape %r with ld %d, got %r'
+                                   % (tuple(feat.shape), feat.ld, (getattr(d_feat, 'shape', None), getattr(d_feat, 'ld', None))))
+    saved = d.large_sep_saved()
+    dz, dgamma, dbeta = ops.batch_norm_backward_device(saved['z'], feat, d_feat, s['gamma'], s['save_mean'], s['save_invstd'],
+                                                       True, stream=d.stream)
+    dt, dkb, dbb = ops.conv_backward_device(saved['t'], s['K_b'], dz, None, stream=d.stream)
+    d_out, dka, dba = ops.conv_backward_device(out, s['K_a'], dt, None, stream=d.stream)
+    _sync(d)
+    co, mid2 = s['K_b'].shape[3], s['K_a'].shape[3]
+    grads = split_large_sep_grads(to_host(dka.ptr, s['K_a'].shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s['K_b'].shape),
+                                  to_host(dbb.ptr, (co,)), s['mid'])
+    grads['large_sep_feature/batch_normalization/gamma'] = to_host(dgamma.ptr, (co,))
+    grads['large_sep_feature/batch_normalization/beta'] = to_host(dbeta.ptr, (co,))
+    grads['out'], grads['z'], grads['t'] = d_out, dz, dt
+    return grads

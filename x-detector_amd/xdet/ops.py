@@ -981,3 +981,181 @@ def conv_backward(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
     ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
     dx = d_dx.numpy(stream=stream) if d_dx is not None else None
     return dx, to_host(d_dw.ptr, ws, np.float32, stream), to_host(d_db.ptr, (ws[-1],), np.float32, stream)
+
+
+# ---- batch normalisation in both directions and both modes (xdet_batch_norm_*, csrc/batchnorm.hip) ---------------------
+
+def host_batch_norm_forward(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None, relu=False,
+                            dtype=np.float32):
+    """The NumPy statement of xdet_batch_norm_forward (include/xdet.h): x [..., C] (every leading axis is a row axis), gamma,
+    beta, moving_mean, moving_var [C] -> (y like x, save_mean [C], save_invstd [C], new moving_mean, new moving_var).
+    training: mean and the CENTRED variance sum (x - mean)^2 / M of the batch, and TensorFlow's fused update of the moving
+    statistics, moving -= (moving - batch) * (1 - momentum), the variance times M / max(M - 1, 1) first (None: no update,
+    None returned).  Not training: mean and var are the moving statistics, returned as they came.  dtype float32, or
+    float64: the accuracy yardstick."""
+    x = np.asarray(x, dtype)
+    C = x.shape[-1]
+    x2 = x.reshape(-1, C)
+    M = x2.shape[0]
+    gamma, beta = np.asarray(gamma, dtype), np.asarray(beta, dtype)
+    mm = None if moving_mean is None else np.asarray(moving_mean, dtype)
+    mv = None if moving_var is None else np.asarray(moving_var, dtype)
+    if training:
+        mean = x2.sum(axis=0, dtype=dtype) / dtype(M)
+        d = x2 - mean
+        var = (d * d).sum(axis=0, dtype=dtype) / dtype(M)
+        if mm is not None:
+            keep = dtype(1) - dtype(momentum)
+            mm = mm - (mm - mean) * keep
+            mv = mv - (mv - var * (dtype(M) / dtype(max(M - 1, 1)))) * keep
+    else:
+        if mm is None or mv is None:
+            raise InvalidArgumentError(-1, 'batch_norm_forward: training=False needs the moving statistics')
+        mean, var = mm, mv
+    invstd = dtype(1) / np.sqrt(var + dtype(eps))
+    y = ((x2 - mean) * invstd) * gamma + beta
+    if relu:
+        y = np.maximum(y, dtype(0))
+    return y.astype(dtype).reshape(x.shape), mean, invstd.astype(dtype), mm, mv
+
+
+def host_batch_norm_backward(x, y, dy, gamma, save_mean, save_invstd, training=True, dtype=np.float32, with_dx=True):
+    """The NumPy statement of xdet_batch_norm_backward: x, dy [..., C], y like x the forward's output after its ReLU (None: no
+    ReLU), gamma, save_mean, save_invstd [C] -> (dx like x or None, dgamma [C], dbeta [C]) with g = dy, or dy where y > 0
+    and 0 elsewhere (an exact zero and a NaN in y both give 0), xhat = (x - save_mean) * save_invstd, dbeta = sum g,
+    dgamma = sum g xhat, dx = gamma invstd (g - dbeta / M - xhat dgamma / M) in training mode and gamma invstd g otherwise."""
+    x, dy = np.asarray(x, dtype), np.asarray(dy, dtype)
+    C = x.shape[-1]
+    x2, g = x.reshape(-1, C), dy.reshape(-1, C)
+    M = x2.shape[0]
+    gamma, mean, invstd = np.asarray(gamma, dtype), np.asarray(save_mean, dtype), np.asarray(save_invstd, dtype)
+    if y is not None:
+        with np.errstate(invalid='ignore'):
+            g = np.where(np.asarray(y, dtype).reshape(-1, C) > 0, g, dtype(0))
+    xhat = (x2 - mean) * invstd
+    dbeta = g.sum(axis=0, dtype=dtype)
+    dgamma = (g * xhat).sum(axis=0, dtype=dtype)
+    dx = None
+    if with_dx:
+        if training:
+            dx = (gamma * invstd) * ((g - dbeta / dtype(M)) - xhat * (dgamma / dtype(M)))
+        else:
+            dx = (gamma * invstd) * g
+        dx = dx.astype(dtype).reshape(x.shape)
+    return dx, dgamma, dbeta
+
+
+def _bn_rows(a, what):
+    """a DeviceTensor ([N,H,W,C] with its ld) or an array [..., C] -> (shape, M, C, DeviceTensor or f32 array)"""
+    if isinstance(a, DeviceTensor):
+        return tuple(a.shape), int(np.prod(a.shape[:-1])), int(a.shape[-1]), a
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim < 2:
+        raise InvalidArgumentError(-1, 'batch_norm: %s must have rows of channels, got shape %r' % (what, a.shape))
+    return a.shape, int(np.prod(a.shape[:-1])), a.shape[-1], a
+
+
+def _bn_vec(a, C, what):
+    """a [C] vector: a DeviceBuffer / DeviceTensor stays, anything else is copied to the device -> (keep-alive, pointer)"""
+    if isinstance(a, (DeviceBuffer, DeviceTensor)):
+        return a, a.ptr
+    a = np.ascontiguousarray(a, np.float32).reshape(-1)
+    if a.shape[0] != C:
+        raise InvalidArgumentError(-1, 'batch_norm: %s must hold %d values, got %d' % (what, C, a.shape[0]))
+    b = to_device(a)
+    return b, b.ptr
+
+
+def _bn_check_sizes(M, C, who):
+    if min(M, C) <= 0 or C > 4096 or M * C >= 2 ** 31:
+        raise InvalidArgumentError(-1, '%s: M = %d, C = %d (positive, C at most 4096, M * C below 2^31)' % (who, M, C))
+
+
+def _bn_dev(a, C):
+    if isinstance(a, DeviceTensor):
+        return a, a.ptr, a.ld
+    b = to_device(a)
+    return b, b.ptr, C
+
+
+def batch_norm_forward_device(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None,
+                              relu=False, stream=None):
+    """batch_norm_forward with the results left on the GPU: (y DeviceTensor with x's shape and ld (C for a NumPy x), save_mean,
+    save_invstd, moving_mean, moving_var as DeviceBuffers [C]; the moving ones None when none were given); nothing is
+    synchronised.  Moving statistics given as DeviceBuffers are updated in place (training) and returned; NumPy ones are
+    copied to the device first."""
+    shape, M, C, x_in = _bn_rows(x, 'x')
+    _bn_check_sizes(M, C, 'batch_norm_forward')
+    if (moving_mean is None) != (moving_var is None) or (not training and moving_mean is None):
+        raise InvalidArgumentError(-1, 'batch_norm_forward: training=False needs both moving statistics; training mode takes '
+                                       'both or neither')
+    kx, px, ldx = _bn_dev(x_in, C)
+    kg, pg = _bn_vec(gamma, C, 'gamma')
+    kb, pb = _bn_vec(beta, C, 'beta')
+    d_mm, pmm = _bn_vec(moving_mean, C, 'moving_mean') if moving_mean is not None else (None, None)
+    d_mv, pmv = _bn_vec(moving_var, C, 'moving_var') if moving_var is not None else (None, None)
+    d_y = DeviceTensor.empty(shape if len(shape) == 4 else (M, 1, 1, C), ld=ldx)
+    d_mean, d_inv = DeviceBuffer(max(C * 4, 16)), DeviceBuffer(max(C * 4, 16))
+    ws = DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
+    check(lib().xdet_batch_norm_forward(px, ldx, M, C, pg, pb, float(eps), 1 if training else 0, float(momentum), pmm, pmv,
+                                        1 if relu else 0, d_y.ptr, d_y.ld, d_mean.ptr, d_inv.ptr, ws.ptr,
+                                        stream.handle if stream else None))
+    d_mean._keep = (kx, kg, kb, ws, d_y)         # operands and workspace live until the stream has run the call
+    return d_y, d_mean, d_inv, d_mm, d_mv
+
+
+def batch_norm_forward(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None, relu=False,
+                       stream=None):
+    """host_batch_norm_forward on the GPU (xdet_batch_norm_forward): x [..., C] as a NumPy array or a DeviceTensor (read in
+    place with its ld) -> (y with x's shape, save_mean, save_invstd, moving_mean, moving_var) as NumPy arrays (the moving
+    ones None when none were given)."""
+    d_y, d_mean, d_inv, d_mm, d_mv = batch_norm_forward_device(x, gamma, beta, eps, training, momentum, moving_mean,
+                                                                moving_var, relu, stream)
+    synchronize(stream)
+    shape = tuple(x.shape) if isinstance(x, DeviceTensor) else np.shape(x)
+    C = shape[-1]
+    y = to_host(d_y.ptr, (int(np.prod(shape[:-1])), d_y.ld), np.float32, stream)[:, :C].reshape(shape)
+    vec = lambda b: to_host(b.ptr, (C,), np.float32, stream) if b is not None else None
+    return np.ascontiguousarray(y), vec(d_mean), vec(d_inv), vec(d_mm), vec(d_mv)
+
+
+def batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None):
+    """batch_norm_backward with the results left on the GPU: (dx DeviceTensor with x's shape and ld (C for a NumPy x) or None,
+    dgamma DeviceBuffer [C], dbeta DeviceBuffer [C]); nothing is synchronised."""
+    shape, M, C, x_in = _bn_rows(x, 'x')
+    sd, Md, Cd, dy_in = _bn_rows(dy, 'dy')
+    bad = (Md, Cd) != (M, C)
+    if y is not None:
+        sy, My, Cy, y_in = _bn_rows(y, 'y')
+        bad = bad or (My, Cy) != (M, C)
+    if bad:
+        raise InvalidArgumentError(-1, 'batch_norm_backward: x, dy and y of one shape expected, got %r'
+                                   % ([shape, sd] + ([sy] if y is not None else []),))
+    _bn_check_sizes(M, C, 'batch_norm_backward')
+    kx, px, ldx = _bn_dev(x_in, C)
+    kd, pd, ldd = _bn_dev(dy_in, C)
+    ky, py, ldy = _bn_dev(y_in, C) if y is not None else (None, None, 0)
+    kg, pg = _bn_vec(gamma, C, 'gamma')
+    km, pm = _bn_vec(save_mean, C, 'save_mean')
+    ki, pi = _bn_vec(save_invstd, C, 'save_invstd')
+    d_dx = DeviceTensor.empty(shape if len(shape) == 4 else (M, 1, 1, C), ld=ldx) if with_dx else None
+    d_dg, d_db = DeviceBuffer(max(C * 4, 16)), DeviceBuffer(max(C * 4, 16))
+    ws = DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
+    check(lib().xdet_batch_norm_backward(px, ldx, py, ldy, pd, ldd, M, C, pg, pm, pi, 1 if training else 0,
+                                         d_dx.ptr if with_dx else None, ldx, d_dg.ptr, d_db.ptr, ws.ptr,
+                                         stream.handle if stream else None))
+    d_dg._keep = (kx, kd, ky, kg, km, ki, ws)    # operands and workspace live until the stream has run the call
+    return d_dx, d_dg, d_db
+
+
+def batch_norm_backward(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None):
+    """host_batch_norm_backward on the GPU (xdet_batch_norm_backward): NumPy arrays or DeviceTensors (read in place with their
+    ld) -> (dx with x's shape or None, dgamma [C], dbeta [C]) as NumPy arrays."""
+    d_dx, d_dg, d_db = batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training, with_dx, stream)
+    synchronize(stream)
+    shape = tuple(x.shape) if isinstance(x, DeviceTensor) else np.shape(x)
+    C = shape[-1]
+    dx = None
+    if d_dx is not None:
+        dx = np.ascontiguousarray(to_host(d_dx.ptr, (int(np.prod(shape[:-1])), d_dx.ld), np.float32, stream)[:, :C].reshape(shape))
+    return dx, to_host(d_dg.ptr, (C,), np.float32, stream), to_host(d_db.ptr, (C,), np.float32, stream)
