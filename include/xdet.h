@@ -673,6 +673,43 @@ int xdet_batch_norm_backward(const float* x, int ld_x, const float* y, int ld_y,
                              const float* gamma, const float* save_mean, const float* save_invstd, int training, float* dx,
                              int ld_dx, float* dgamma, float* dbeta, void* workspace, void* stream);
 
+/* ---- the backward of the depthwise 3x3 conv y = depthwise(xe, k), xe = x or max(x, 0): stride 1, 'SAME', dilation d = 1 or 2
+ * (csrc/depthwise_backward.hip; the NumPy statement of the same contract is xdet.ops.host_depthwise_backward).  NHWC, zero
+ * padding of d rows and d columns on either side; M = N * H * W pixels ----------------------------------------------------
+ *   x  f32 [N,H,W,C], pixel stride ld_x          the layer's input (relu_in != 0: the conv read max(x, 0))
+ *   k  f32 [3,3,C,1] dense                       the depthwise kernel as the checkpoint stores it, on the device
+ *   dy f32 [N,H,W,C], pixel stride ld_dy         g = d loss / d y
+ *     xe = x,  or x > 0 ? x : 0 with relu_in (a NaN in x counts as 0 and gets the gradient 0, as in xdet_conv_backward)
+ *   -> dx f32 [N,H,W,C], pixel stride ld_dx (NULL: skipped; dw is written all the same):
+ *        dx[n,h,w,c] = sum over taps (a,b) of g[n, h - (a-1)d, w - (b-1)d, c] * k[a,b,c], and with relu_in 0 wherever x > 0
+ *        is false;
+ *      dw f32 [3,3,C,1] dense: dw[a,b,c] = sum over pixels of xe[n, h + (a-1)d, w + (b-1)d, c] * g[n,h,w,c].
+ * A term whose source pixel lies outside the image is absent and its pixel is not read: a shift never leaves its image.
+ * Channels at or beyond C are never read -- padding may hold NaN -- and nothing is written to dx beyond channel C - 1.
+ * x and dy must not overlap dx.
+ * Arithmetic and order of the sums: every term is a plain f32 product, added in f32 to a running sum that starts at 0 (no
+ *   fused multiply-add, no rescaling), so scaling dy by a power of two scales dx and dw by exactly that power (bit for bit,
+ *   short of f32 underflow).  dx adds its taps in storage order, (0,0), (0,1), ..., (2,2): it is the f32 host statement bit
+ *   for bit, but for the sign of a zero.  dw[a,b,c] is summed over the pixel of ITS xe factor, m = (n H + h) W + w in
+ *   0 .. M - 1 (the term of pixel m is xe[m] * g[n, h - (a-1)d, w - (b-1)d]): the pixels are cut into chunks of
+ *   max(64, ceil(M / 1024)) consecutive m (at most 1024 chunks); inside a chunk the pixels are dealt to four sums by
+ *   (m - first m of the chunk) mod 4, each added in pixel order, and the four are added in index order; the chunks are then
+ *   added in index order.  All of it depends on (N, H, W) alone: pointer alignment and strides (vector or scalar accesses) do
+ *   not change a bit.  No float atomics: the same call gives the same bits, whatever the workspace held.
+ * workspace: xdet_depthwise_backward_workspace_bytes(N, H, W, C) bytes (never 0 inside the limits, 0 outside them); it needs
+ *   no initialisation and may be larger.  The call does not synchronise and reads nothing on the host.
+ * Limits: d = 1 or 2; C <= 4096; M * max(C, every ld given) < 2^31.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, another dilation, ld_x < C,
+ *   ld_dy < C, ld_dx < C with a dx, a NULL x, k, dy, dw or workspace. */
+size_t xdet_depthwise_backward_workspace_bytes(int N, int H, int W, int C);
+int xdet_depthwise_backward(const float* x, int ld_x, const float* k, const float* dy, int ld_dy, int N, int H, int W, int C,
+                            int dilation, int relu_in, float* dx, int ld_dx, float* dw, void* workspace, void* stream);
+/* out = a + b over M rows of C channels, f32, each tensor with a row stride ld >= C (the exit flow's residual add behind a
+ * training-mode batch norm, and the join of two gradients).  out may be a (or b) itself; any other overlap is not allowed.
+ * Nothing at or beyond channel C is read or written.  Limits: C <= 2^24, M * max(ld) < 2^31.  Errors ->
+ * XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, an ld below C, a NULL a, b or out. */
+int xdet_add_rows(const float* a, int ld_a, const float* b, int ld_b, float* out, int ld_out, int M, int C, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

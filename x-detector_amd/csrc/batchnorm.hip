@@ -24,6 +24,7 @@
 // -ffp-contract=off: every sum is a plain f32 add of plain f32 products, so dy * 2^k gives dx, dgamma, dbeta * 2^k exactly.
 #include "common.h"
 #include "batchnorm_layout.h"
+#include "channel_quad.h"
 #include <algorithm>
 
 namespace xdet {
@@ -46,28 +47,6 @@ struct BnArgs {
   float *first, *second;            // the workspace's chunk sums
 };
 
-static inline int bn_vec(const void* p, int ld) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0; }
-
-// four consecutive floats at p, of which `left` exist (the others read as 0 and are never fetched)
-__device__ __forceinline__ void bn_load4(const float* __restrict__ p, int left, bool vec, float (&v)[4]) {
-  if (vec && left >= 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = e < left ? p[e] : 0.f;
-  }
-}
-__device__ __forceinline__ void bn_store4(float* __restrict__ p, int left, bool vec, const float (&v)[4]) {
-  if (vec && left >= 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < left) p[e] = v[e];
-  }
-}
-
 // y > 0 is false for a NaN: the gradient behind a NaN activation is 0
 __device__ __forceinline__ float bn_mask(float dy, float y) { return y > 0.f ? dy : 0.f; }
 
@@ -80,12 +59,12 @@ __global__ __launch_bounds__(BN_T) void bn_sum_kernel(BnArgs a) {
   float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
   if (left > 0) {
     float mean[4] = {0.f, 0.f, 0.f, 0.f}, inv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (MODE >= 1) bn_load4(a.mean + c0, left, false, mean);
-    if (MODE == 2) bn_load4(a.invstd + c0, left, false, inv);
+    if (MODE >= 1) quad_load(a.mean + c0, left, false, mean);
+    if (MODE == 2) quad_load(a.invstd + c0, left, false, inv);
 #pragma unroll 4
     for (int m = m0 + rl; m < m1; m += BN_RL) {
       float x[4];
-      bn_load4(a.x + (int64_t)m * a.ld_x + c0, left, a.vec_x, x);
+      quad_load(a.x + (int64_t)m * a.ld_x + c0, left, a.vec_x, x);
       if (MODE == 0) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) s0[e] += x[e];
@@ -97,10 +76,10 @@ __global__ __launch_bounds__(BN_T) void bn_sum_kernel(BnArgs a) {
         }
       } else {
         float g[4];
-        bn_load4(a.dy + (int64_t)m * a.ld_dy + c0, left, a.vec_dy, g);
+        quad_load(a.dy + (int64_t)m * a.ld_dy + c0, left, a.vec_dy, g);
         if (a.y) {
           float y[4];
-          bn_load4(a.y + (int64_t)m * a.ld_y + c0, left, a.vec_y, y);
+          quad_load(a.y + (int64_t)m * a.ld_y + c0, left, a.vec_y, y);
 #pragma unroll
           for (int e = 0; e < 4; ++e) g[e] = bn_mask(g[e], y[e]);
         }
@@ -141,39 +120,24 @@ struct BnStats {
   float *dgamma, *dbeta;
 };
 
-// the chunks of one channel added in index order; 32 loads are in flight before the first add (one load per add was a
-// dependent round trip per chunk: 113 of them at the block's size, most of a call's time)
-__device__ __forceinline__ float bn_fold(const float* __restrict__ partial, int n_chunks, int C, int c) {
-  float s = 0.f;
-  for (int k = 0; k < n_chunks; k += 32) {
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = partial[(int64_t)min(k + i, n_chunks - 1) * C + c];
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-      if (k + i < n_chunks) s += v[i];
-  }
-  return s;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(BN_STATS_T) void bn_stats_kernel(BnStats a) {
   const int c = blockIdx.x * BN_STATS_T + threadIdx.x;
   if (c >= a.C) return;
   if (MODE == 0) {
-    const float mean = bn_fold(a.first, a.n_chunks, a.C, c) / (float)a.M;
+    const float mean = fold_chunks(a.first, a.n_chunks, a.C, c) / (float)a.M;
     a.save_mean[c] = mean;
     if (a.moving_mean) a.moving_mean[c] -= (a.moving_mean[c] - mean) * (1.f - a.momentum);
   } else if (MODE == 1) {
-    const float var = bn_fold(a.second, a.n_chunks, a.C, c) / (float)a.M;
+    const float var = fold_chunks(a.second, a.n_chunks, a.C, c) / (float)a.M;
     a.save_invstd[c] = 1.f / sqrtf(var + a.eps);
     if (a.moving_var) {
       const float unbiased = var * ((float)a.M / (float)max(a.M - 1, 1));
       a.moving_var[c] -= (a.moving_var[c] - unbiased) * (1.f - a.momentum);
     }
   } else if (MODE == 2) {
-    a.dbeta[c] = bn_fold(a.first, a.n_chunks, a.C, c);
-    a.dgamma[c] = bn_fold(a.second, a.n_chunks, a.C, c);
+    a.dbeta[c] = fold_chunks(a.first, a.n_chunks, a.C, c);
+    a.dgamma[c] = fold_chunks(a.second, a.n_chunks, a.C, c);
   } else {
     a.save_mean[c] = a.moving_mean[c];
     a.save_invstd[c] = 1.f / sqrtf(a.moving_var[c] + a.eps);
@@ -187,15 +151,15 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(BnArgs a) {
   if (left <= 0) return;
   const int m0 = blockIdx.x * BN_APPLY_ROWS, m1 = min(a.M, m0 + BN_APPLY_ROWS);
   float mean[4], inv[4], gamma[4], b[4], k[4] = {0.f, 0.f, 0.f, 0.f};
-  bn_load4(a.mean + c0, left, false, mean);
-  bn_load4(a.invstd + c0, left, false, inv);
-  bn_load4(a.gamma + c0, left, false, gamma);
+  quad_load(a.mean + c0, left, false, mean);
+  quad_load(a.invstd + c0, left, false, inv);
+  quad_load(a.gamma + c0, left, false, gamma);
   if (BWD) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) b[e] = 0.f;
     if (a.training) {     // b = dbeta / M, k = dgamma / M
-      bn_load4(a.dbeta + c0, left, false, b);
-      bn_load4(a.dgamma + c0, left, false, k);
+      quad_load(a.dbeta + c0, left, false, b);
+      quad_load(a.dgamma + c0, left, false, k);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         b[e] = b[e] / (float)a.M;
@@ -205,18 +169,18 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(BnArgs a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) gamma[e] = gamma[e] * inv[e];
   } else {
-    bn_load4(a.beta + c0, left, false, b);
+    quad_load(a.beta + c0, left, false, b);
   }
 #pragma unroll 4
   for (int m = m0 + rl; m < m1; m += BN_RL) {
     float x[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-    if (!BWD || a.training) bn_load4(a.x + (int64_t)m * a.ld_x + c0, left, a.vec_x, x);
+    if (!BWD || a.training) quad_load(a.x + (int64_t)m * a.ld_x + c0, left, a.vec_x, x);
     if (BWD) {
       float g[4];
-      bn_load4(a.dy + (int64_t)m * a.ld_dy + c0, left, a.vec_dy, g);
+      quad_load(a.dy + (int64_t)m * a.ld_dy + c0, left, a.vec_dy, g);
       if (a.y) {
         float y[4];
-        bn_load4(a.y + (int64_t)m * a.ld_y + c0, left, a.vec_y, y);
+        quad_load(a.y + (int64_t)m * a.ld_y + c0, left, a.vec_y, y);
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] = bn_mask(g[e], y[e]);
       }
@@ -230,7 +194,7 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(BnArgs a) {
         if (a.relu) o[e] = fmaxf(o[e], 0.f);
       }
     }
-    bn_store4(a.out + (int64_t)m * a.ld_out + c0, left, a.vec_out, o);
+    quad_store(a.out + (int64_t)m * a.ld_out + c0, left, a.vec_out, o);
   }
 }
 
@@ -285,7 +249,7 @@ int xdet_batch_norm_forward(const float* x, int ld_x, int M, int C, const float*
   a.x = x; a.ld_x = ld_x; a.ld_out = ld_y;
   a.M = M; a.C = C;
   a.rows_per_chunk = pl.rows_per_chunk; a.n_chunks = pl.n_chunks;
-  a.vec_x = bn_vec(x, ld_x); a.vec_out = bn_vec(y, ld_y);
+  a.vec_x = quad_vec(x, ld_x); a.vec_out = quad_vec(y, ld_y);
   a.relu = relu != 0; a.training = training != 0;
   a.gamma = gamma; a.beta = beta; a.mean = save_mean; a.invstd = save_invstd;
   a.out = y;
@@ -329,7 +293,7 @@ int xdet_batch_norm_backward(const float* x, int ld_x, const float* y, int ld_y,
   a.ld_x = ld_x; a.ld_y = ld_y; a.ld_dy = ld_dy; a.ld_out = ld_dx;
   a.M = M; a.C = C;
   a.rows_per_chunk = pl.rows_per_chunk; a.n_chunks = pl.n_chunks;
-  a.vec_x = bn_vec(x, ld_x); a.vec_y = bn_vec(y, ld_y); a.vec_dy = bn_vec(dy, ld_dy); a.vec_out = bn_vec(dx, ld_dx);
+  a.vec_x = quad_vec(x, ld_x); a.vec_y = quad_vec(y, ld_y); a.vec_dy = quad_vec(dy, ld_dy); a.vec_out = quad_vec(dx, ld_dx);
   a.training = training != 0;
   a.gamma = gamma; a.mean = save_mean; a.invstd = save_invstd; a.dgamma = dgamma; a.dbeta = dbeta;
   a.out = dx;

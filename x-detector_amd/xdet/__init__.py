@@ -30,6 +30,10 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   large_sep_kernel(..., is_training=True), large_sep_backward (xdet.model; LightHeadDetector(large_sep_train=True))
   (xdet.ops)              <- tf.layers.batch_normalization with training=True and its gradient (net/xception_body.py:
                              450-475): batch statistics, the moving-average updates, the large-separable block's backward
+  depthwise_backward, host_depthwise_backward, add_rows_device; exit_flow_train, exit_flow_backward (xdet.model;
+  LightHeadDetector(exit_flow_train=True))
+  (xdet.ops)              <- what tf.gradients derives for the depthwise half of tf.layers.separable_conv2d, and the
+                             Xception exit flow (net/xception_body.py:339-376) with batch statistics and its backward
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

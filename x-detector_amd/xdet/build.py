@@ -32,6 +32,7 @@ SOURCES = [
     ('dense_backward.hip', []),
     ('conv_backward.hip', []),
     ('batchnorm.hip', ['-ffp-contract=off']),
+    ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

@@ -22,6 +22,16 @@ LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br 
 LARGE_SEP_MOVING = ('large_sep_feature/batch_normalization/moving_mean', 'large_sep_feature/batch_normalization/moving_variance')
 LARGE_SEP_EPS, LARGE_SEP_MOMENTUM = 1e-5, 0.997        # net/resnet_v2.py: _BATCH_NORM_EPSILON, _BATCH_NORM_DECAY
 
+# the Xception exit flow (net/xception_body.py:339-376): four separable units (name, dilation, ReLU in front of the depthwise
+# conv, ReLU behind the batch norm) and the 1x1 projection of the residual branch
+EXIT_FLOW_UNITS = (('block13_sepconv1', 1, True, False), ('block13_sepconv2', 1, True, False),
+                   ('block14_sepconv1', 2, False, True), ('block14_sepconv2', 2, False, True))
+EXIT_FLOW_BNS = tuple(u[0] + '_bn' for u in EXIT_FLOW_UNITS) + ('batch_normalization_4',)
+EXIT_FLOW_VARIABLES = tuple('%s/%s' % (u[0], v) for u in EXIT_FLOW_UNITS for v in ('depthwise_kernel', 'pointwise_kernel')) + \
+    ('conv2d_4/kernel',) + tuple('%s/%s' % (b, v) for b in EXIT_FLOW_BNS for v in ('gamma', 'beta'))
+EXIT_FLOW_MOVING = tuple('%s/%s' % (b, v) for b in EXIT_FLOW_BNS for v in ('moving_mean', 'moving_variance'))
+EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM = 1e-4, 0.99         # net/xception_body.py: the Xception layers' batch norm
+
 
 def merge_large_sep(weights, dtype=np.float32):
     """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
@@ -53,7 +63,7 @@ class LightHeadDetector(object):
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
-                 pool_index=False, rpn_hidden=False, large_sep_train=False):
+                 pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -70,7 +80,20 @@ class LightHeadDetector(object):
         block's two merged kernels, biases, gamma, beta and moving statistics are put on the device:
         large_sep_kernel(..., is_training=True) then runs the block with batch statistics (xdet_batch_norm_forward) and
         large_sep_backward takes the gradient through it.  The default detector keeps none of this and allocates nothing for
-        it; is_training=False is the same forward either way."""
+        it; is_training=False is the same forward either way.
+        exit_flow_train=True (needs large_sep_train=True: a training-mode `out` is consumed by the training-mode block): the
+        exit flow's 19 variables (EXIT_FLOW_VARIABLES) and the moving statistics of its five batch norms are kept unfolded on
+        the device, with the tensors a training forward saves and the workspaces, all sized for max_batch:
+        model.exit_flow_train() then recomputes the exit flow from `mid_x` with batch statistics into the net's `out`, and
+        model.exit_flow_backward takes the gradient through it down to `mid_x`.  The default detector allocates and runs none
+        of this."""
+        if exit_flow_train and not large_sep_train:
+            raise InvalidArgumentError(-1, 'exit_flow_train=True needs large_sep_train=True (the training-mode `out` it writes is '
+                                           'consumed by the large-separable block in training mode)')
+        if exit_flow_train:                      # (ahead of the native net, which would miss them under another error)
+            miss = [k for k in EXIT_FLOW_VARIABLES + EXIT_FLOW_MOVING if k not in weights]
+            if miss:
+                raise InvalidArgumentError(-1, 'exit_flow_train: the weights lack %s' % ', '.join(miss))
         if device is not None:
             check(lib().xdet_set_device(int(device)))
         self.cfg = LightHeadConfig(image_size=image_size, max_batch=max_batch, num_classes=num_classes,
@@ -123,6 +146,9 @@ class LightHeadDetector(object):
         self.large_sep_train = bool(large_sep_train)
         if large_sep_train:
             self._build_large_sep_train(weights)
+        self.exit_flow_train = bool(exit_flow_train)
+        if exit_flow_train:
+            self._build_exit_flow_train(weights)
 
     def _build_large_sep_train(self, weights):
         """the training form of the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as
@@ -166,6 +192,71 @@ class LightHeadDetector(object):
         co = s['z'].shape[3]
         for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
             out[k] = DeviceTensor(s[k].ptr, (1, 1, 1, co), co, owner=s[k])
+        return out
+
+    def _build_exit_flow_train(self, weights):
+        """the training form of the exit flow: per separable unit the depthwise layer, the pointwise conv (split precision, f32
+        out, no scale or shift), both kernels as dense device tensors for the backward, the BN vectors and the tensors a
+        training forward keeps (the depthwise output, the BN input, the BN output); the same for the projection branch"""
+        from . import ops
+        from .runtime import get_precision, set_precision
+        g = lambda k: np.ascontiguousarray(weights[k], np.float32)
+        vec = lambda a: to_device(np.ascontiguousarray(a, np.float32))
+
+        def dense(k):
+            b = to_device(k)
+            return DeviceTensor(b.ptr, k.shape, k.shape[3], owner=b)
+
+        def bn(name, co):
+            return {'gamma': vec(g(name + '/gamma')), 'beta': vec(g(name + '/beta')), 'moving_mean': vec(g(name + '/moving_mean')),
+                    'moving_variance': vec(g(name + '/moving_variance')), 'save_mean': DeviceBuffer(co * 4),
+                    'save_invstd': DeviceBuffer(co * 4)}
+        B, (_, H, W, cin) = self.max_batch, self.buffer('mid_x', 1).shape
+        before = get_precision()
+        set_precision('f16x3')
+        try:
+            pw = {u[0]: ops.Conv2D(g(u[0] + '/pointwise_kernel')) for u in EXIT_FLOW_UNITS}
+            proj = ops.Conv2D(g('conv2d_4/kernel'))
+        finally:
+            set_precision(before)
+        e = {'n': 0, 'units': [], 'proj': {'conv': proj, 'K': dense(g('conv2d_4/kernel'))}}
+        widths = [proj.cout]
+        for name, dil, relu_in, relu_out in EXIT_FLOW_UNITS:
+            kd, kp = g(name + '/depthwise_kernel'), g(name + '/pointwise_kernel')
+            C, J = kp.shape[2], kp.shape[3]
+            u = {'name': name, 'dil': dil, 'relu_in': relu_in, 'relu_out': relu_out, 'dw': ops.DepthwiseConv2D(kd, dil),
+                 'pw': pw[name], 'K_dw': dense(kd), 'K_pw': dense(kp), 'bn': bn(name + '_bn', J),
+                 't': DeviceTensor.empty((B, H, W, C)), 'z': DeviceTensor.empty((B, H, W, J))}
+            if name != EXIT_FLOW_UNITS[-1][0]:           # (the last batch norm writes the net's `out`)
+                u['y'] = DeviceTensor.empty((B, H, W, J))
+            e['units'].append(u)
+            widths += [C, J]
+        e['proj'].update(bn=bn('batch_normalization_4', proj.cout), z=DeviceTensor.empty((B, H, W, proj.cout)),
+                         r=DeviceTensor.empty((B, H, W, proj.cout)))
+        e['b2'] = DeviceTensor.empty((B, H, W, proj.cout))
+        e['ws_bn'] = DeviceBuffer(max(lib().xdet_batch_norm_workspace_bytes(n * H * W, max(widths)) for n in range(1, B + 1)))
+        e['ws_dw'] = DeviceBuffer(max(lib().xdet_depthwise_backward_workspace_bytes(n, H, W, max(widths)) for n in range(1, B + 1)))
+        self._exit = e
+
+    def exit_flow_saved(self):
+        """what the last model.exit_flow_train() left on the device, as DeviceTensors: per separable unit '<unit>/dw' (the
+        depthwise conv's output, the pointwise conv's input) and '<unit>/z' (the pointwise conv's output, the batch norm's
+        input), 'conv2d_4/z'; 'a', 'r', 'y2' (block13_sepconv2's batch norm output, b2 = y2 + r), 'b2', 'c3'; and per batch
+        norm '<bn>/save_mean', '<bn>/save_invstd' (the batch statistics), '<bn>/moving_mean', '<bn>/moving_variance' (after
+        their update), each [1,1,1,C]"""
+        if not self.exit_flow_train or not self._exit['n']:
+            raise InvalidArgumentError(-1, 'exit_flow_saved: no model.exit_flow_train() has run on this detector')
+        e, n = self._exit, self._exit['n']
+        view = lambda t: DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+        out = {'conv2d_4/z': view(e['proj']['z']), 'r': view(e['proj']['r']), 'b2': view(e['b2'])}
+        for u, y in zip(e['units'], ('a', 'y2', 'c3', None)):
+            out[u['name'] + '/dw'], out[u['name'] + '/z'] = view(u['t']), view(u['z'])
+            if y:
+                out[y] = view(u['y'])
+        for name, b in [(u['name'] + '_bn', u['bn']) for u in e['units']] + [('batch_normalization_4', e['proj']['bn'])]:
+            co = b['save_mean'].nbytes // 4
+            for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
+                out['%s/%s' % (name, k)] = DeviceTensor(b[k].ptr, (1, 1, 1, co), co, owner=b[k])
         return out
 
     # ---- plumbing -------------------------------------------------------------------
@@ -737,4 +828,119 @@ def large_sep_backward(d_feat):
     grads['large_sep_feature/batch_normalization/gamma'] = to_host(dgamma.ptr, (co,))
     grads['large_sep_feature/batch_normalization/beta'] = to_host(dbeta.ptr, (co,))
     grads['out'], grads['z'], grads['t'] = d_out, dz, dt
+    return grads
+
+
+def exit_flow_train():
+    """The Xception exit flow in training mode (net/xception_body.py:339-376), called after XceptionBody(...,
+    is_training=False) on a detector built with exit_flow_train=True: the exit flow is computed again from the net's `mid_x`
+    buffer with batch statistics -- per separable unit xdet_depthwise_forward, the 1x1 conv (xdet_conv_forward, split
+    precision, f32 out) and xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the ReLU inside where the graph
+    has one, the moving statistics updated on their device copies) --
+
+        r  = BN4(conv2d_4(mid_x))                          a  = BN(pw(dw(relu(mid_x))))
+        b2 = BN(pw(dw(relu(a)))) + r   (xdet_add_rows)     c3 = relu(BN(pw(dw_dil2(b2))))     out = relu(BN(pw(dw_dil2(c3))))
+
+    all on the detector's stream with no host round trip; the last batch norm writes straight into the net's `out` buffer
+    (with its ld), so large_sep_kernel(..., is_training=True), get_head, head_backward and large_sep_backward go on unchanged.
+    `mid_x` is not written: get_rpn is unaffected.  What exit_flow_backward needs stays on the device
+    (detector.exit_flow_saved()).  -> `out` [N,h,w,2048]."""
+    d = _det()
+    if not d.exit_flow_train:
+        raise InvalidArgumentError(-1, 'exit_flow_train: needs a detector built with exit_flow_train=True (the default detector '
+                                       'folds the moving statistics into the conv weights)')
+    n = d._N
+    if not n:
+        raise InvalidArgumentError(-1, 'exit_flow_train: call XceptionBody(..., is_training=False) first')
+    e, h, l = d._exit, d.stream.handle, lib()
+    mid_x, out = d.buffer('mid_x', n), d.buffer('out', n)
+    _, H, W, _ = mid_x.shape
+    M = n * H * W
+
+    def batch_norm(b, z, relu, y):
+        check(l.xdet_batch_norm_forward(z.ptr, z.ld, M, z.shape[3], b['gamma'].ptr, b['beta'].ptr, EXIT_FLOW_EPS, 1,
+                                        EXIT_FLOW_MOMENTUM, b['moving_mean'].ptr, b['moving_variance'].ptr, 1 if relu else 0,
+                                        y.ptr, y.ld, b['save_mean'].ptr, b['save_invstd'].ptr, e['ws_bn'].ptr, h))
+    p = e['proj']
+    check(l.xdet_conv_forward(p['conv'].handle, mid_x.ptr, n, H, W, mid_x.ld, p['z'].ptr, p['z'].ld, None, 0, h))
+    batch_norm(p['bn'], p['z'], False, p['r'])
+    x = mid_x
+    for i, u in enumerate(e['units']):
+        t, z = u['t'], u['z']
+        check(l.xdet_depthwise_forward(u['dw'].handle, x.ptr, n, H, W, x.ld, t.ptr, 1 if u['relu_in'] else 0, h))
+        check(l.xdet_conv_forward(u['pw'].handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
+        y = u.get('y', out)
+        batch_norm(u['bn'], z, u['relu_out'], y)
+        if i == 1:                                   # block13's residual add behind its second batch norm
+            check(l.xdet_add_rows(y.ptr, y.ld, p['r'].ptr, p['r'].ld, e['b2'].ptr, e['b2'].ld, M, y.shape[3], h))
+            y = e['b2']
+        x = y
+    e['n'] = n
+    _sync(d)
+    return out
+
+
+def exit_flow_backward(d_out, d_mid=None):
+    """The backward of the exit flow in training mode, called after exit_flow_train() on a detector built with
+    exit_flow_train=True: d_out = large_sep_backward(...)['out'] (d loss / d out, with the `out` buffer's shape and ld) and
+    optionally d_mid = rpn_backward(...)['mid'] (the RPN branch's share of d loss / d mid_x, with `mid_x`'s shape and ld).  Per
+    separable unit, last to first: xdet_batch_norm_backward on the kept BN input (masked by the unit's own output where the
+    graph has a ReLU: the net's `out`, the kept c3), xdet_conv_backward at 1x1 on the kept depthwise output, then
+    xdet_depthwise_backward (dilation 2 in block14; relu_in on `a` and on `mid_x` in block13).  d loss / d b2 feeds both
+    batch_normalization_4's backward, whose conv_backward on `mid_x` gives share A, and block13's two units, which give share
+    B; the call ends with d loss / d mid_x = (B + A) + d_mid, in that order, by xdet_add_rows -- everything on the detector's
+    stream with no host round trip.  The bias gradient xdet_conv_backward insists on is computed and dropped: these convs
+    have none.  -> a dict with the 19 gradients under the checkpoint's variable names and in its shapes
+    (EXIT_FLOW_VARIABLES, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with `mid_x`'s ld, its addends
+    'mid_A' and 'mid_B', and the intermediate gradients 'b2', 'c3', 'a' and 'r' (d loss / d r is d loss / d b2: the same
+    tensor), 'dw/<unit>' = d loss / d (the unit's depthwise output) and 'z/<unit>', 'z/conv2d_4' = d loss / d (a batch norm's
+    input) likewise."""
+    from . import ops
+    d = _det()
+    if not d.exit_flow_train:
+        raise InvalidArgumentError(-1, 'exit_flow_backward: needs a detector built with exit_flow_train=True')
+    e = d._exit
+    n = e['n']
+    if not n:
+        raise InvalidArgumentError(-1, 'exit_flow_backward: call exit_flow_train() first')
+    out, mid_x = d.buffer('out', n), d.buffer('mid_x', n)
+    for what, t, like in (('d_out', d_out, out), ('d_mid', d_mid, mid_x)):
+        if t is None and what == 'd_mid':
+            continue
+        if not isinstance(t, DeviceTensor) or tuple(t.shape) != tuple(like.shape) or t.ld != like.ld:
+            raise InvalidArgumentError(-1, 'exit_flow_backward: %s must be a DeviceTensor of shape %r with ld %d, got %r'
+                                       % (what, tuple(like.shape), like.ld, (getattr(t, 'shape', None), getattr(t, 'ld', None))))
+    saved = d.exit_flow_saved()
+    grads, dev = {}, {}
+
+    def unit_backward(u, x, y, dy):
+        """-> d loss / d x through BN (masked by y), the 1x1 conv and the depthwise conv"""
+        name, b = u['name'], u['bn']
+        dz, dgamma, dbeta = ops.batch_norm_backward_device(saved[name + '/z'], y, dy, b['gamma'], b['save_mean'], b['save_invstd'],
+                                                           True, stream=d.stream)
+        dt, dkp, _ = ops.conv_backward_device(saved[name + '/dw'], u['K_pw'], dz, None, stream=d.stream)
+        dx, dkd = ops.depthwise_backward_device(x, u['K_dw'], dt, u['dil'], u['relu_in'], stream=d.stream, workspace=e['ws_dw'])
+        dev[name + '/depthwise_kernel'], dev[name + '/pointwise_kernel'] = (dkd, u['K_dw'].shape), (dkp, u['K_pw'].shape)
+        dev[name + '_bn/gamma'], dev[name + '_bn/beta'] = (dgamma, (u['K_pw'].shape[3],)), (dbeta, (u['K_pw'].shape[3],))
+        grads['dw/' + name], grads['z/' + name] = dt, dz
+        return dx
+    u1, u2, u3, u4 = e['units']
+    d_c3 = unit_backward(u4, saved['c3'], out, d_out)
+    d_b2 = unit_backward(u3, saved['b2'], saved['c3'], d_c3)
+    p = e['proj']
+    dzr, dgamma, dbeta = ops.batch_norm_backward_device(saved['conv2d_4/z'], None, d_b2, p['bn']['gamma'], p['bn']['save_mean'],
+                                                        p['bn']['save_invstd'], True, stream=d.stream)
+    share_a, dk4, _ = ops.conv_backward_device(mid_x, p['K'], dzr, None, relu_in=False, stream=d.stream)
+    co = p['K'].shape[3]
+    dev['conv2d_4/kernel'] = (dk4, p['K'].shape)
+    dev['batch_normalization_4/gamma'], dev['batch_normalization_4/beta'] = (dgamma, (co,)), (dbeta, (co,))
+    d_a = unit_backward(u2, saved['a'], None, d_b2)
+    share_b = unit_backward(u1, mid_x, None, d_a)
+    mid = ops.add_rows_device(share_b, share_a, stream=d.stream)
+    if d_mid is not None:
+        ops.add_rows_device(mid, d_mid, out=mid, stream=d.stream)
+    _sync(d)
+    for k, (buf, shape) in dev.items():
+        grads[k] = to_host(buf.ptr, shape)
+    grads.update({'mid': mid, 'mid_A': share_a, 'mid_B': share_b, 'b2': d_b2, 'r': d_b2, 'c3': d_c3, 'a': d_a, 'z/conv2d_4': dzr})
     return grads

@@ -1159,3 +1159,105 @@ def batch_norm_backward(x, y, dy, gamma, save_mean, save_invstd, training=True, 
     if d_dx is not None:
         dx = np.ascontiguousarray(to_host(d_dx.ptr, (int(np.prod(shape[:-1])), d_dx.ld), np.float32, stream)[:, :C].reshape(shape))
     return dx, to_host(d_dg.ptr, (C,), np.float32, stream), to_host(d_db.ptr, (C,), np.float32, stream)
+
+
+# ---- the backward of the depthwise 3x3 conv, and the row add (xdet_depthwise_backward / xdet_add_rows,
+#      csrc/depthwise_backward.hip) ------------------------------------------------------------------------------------
+
+def host_depthwise_backward(x, k, dy, dilation=1, relu_in=False, dtype=np.float32, with_dx=True):
+    """The NumPy statement of xdet_depthwise_backward (include/xdet.h) for y = depthwise3x3(xe, k), stride 1, 'SAME', NHWC:
+    x, dy [N,H,W,C], k [3,3,C,1], dilation d; xe = x, or with relu_in x where x > 0 and 0 elsewhere -> (dx [N,H,W,C],
+    dw [3,3,C,1]): dx[n,h,w,c] = sum over taps of dy[n, h - (a-1)d, w - (b-1)d, c] * k[a,b,c], the taps in storage order, each
+    product rounded and then added (the op's own order: in float32 dx is the op's dx bit for bit, but for the sign of a
+    zero), 0 wherever x > 0 is false with relu_in; dw[a,b,c] = sum over pixels of xe[n, h + (a-1)d, w + (b-1)d, c] *
+    dy[n,h,w,c], NumPy's sequential sum over the pixels.  Terms outside the image are absent.  dtype float32, or float64: the
+    accuracy yardstick.  with_dx=False: dx is None."""
+    x, k, dy = np.asarray(x, dtype), np.asarray(k, dtype), np.asarray(dy, dtype)
+    N, H, W, C = x.shape
+    d = int(dilation)
+    xe = x
+    if relu_in:
+        with np.errstate(invalid='ignore'):
+            xe = np.where(x > 0, x, dtype(0))
+    border = ((0, 0), (d, d), (d, d), (0, 0))
+    xp, gp = np.pad(xe, border), np.pad(dy, border)
+    dw = np.empty((3, 3, C, 1), dtype)
+    dx = np.zeros(x.shape, dtype) if with_dx else None
+    for a in range(3):
+        for b in range(3):
+            dw[a, b, :, 0] = (xp[:, a * d:a * d + H, b * d:b * d + W] * dy).reshape(-1, C).sum(axis=0, dtype=dtype)
+            if with_dx:
+                dx += gp[:, (2 - a) * d:(2 - a) * d + H, (2 - b) * d:(2 - b) * d + W] * k[a, b, :, 0]
+    if with_dx and relu_in:
+        with np.errstate(invalid='ignore'):
+            dx = np.where(x > 0, dx, dtype(0))
+    return dx, dw
+
+
+def depthwise_backward_device(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None, workspace=None):
+    """depthwise_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
+    dw DeviceBuffer [3,3,C,1]); nothing is synchronised.  A DeviceTensor k is [3,3,C,1] dense (ld 1).  workspace: a
+    DeviceBuffer of at least xdet_depthwise_backward_workspace_bytes(N, H, W, C) bytes (default: allocated here)."""
+    (N, H, W, C), x_in = _nhwc(x, 'x')
+    sk, k_in = _nhwc(k, 'k')
+    sd, dy_in = _nhwc(dy, 'dy')
+    if tuple(sk) != (3, 3, C, 1) or tuple(sd) != (N, H, W, C):
+        raise InvalidArgumentError(-1, 'depthwise_backward: x [N,H,W,C], k [3,3,C,1] and dy [N,H,W,C] expected, got %r'
+                                   % ([(N, H, W, C), tuple(sk), tuple(sd)],))
+    M = N * H * W
+    if min(M, C) <= 0 or C > 4096 or M * C >= 2 ** 31 or dilation not in (1, 2):
+        raise InvalidArgumentError(-1, 'depthwise_backward: N*H*W = %d, C = %d, dilation %r (sizes positive, C at most 4096, '
+                                       'N*H*W * C below 2^31, dilation 1 or 2)' % (M, C, dilation))
+    if isinstance(k_in, DeviceTensor) and k_in.ld != 1:
+        raise InvalidArgumentError(-1, 'depthwise_backward: k must be dense on the device (ld %d)' % k_in.ld)
+
+    def dev(a, width):
+        if isinstance(a, DeviceTensor):
+            return a, a.ptr, a.ld
+        b = to_device(a)
+        return b, b.ptr, width
+    kx, px, ldx = dev(x_in, C)
+    kk, pk, _ = dev(k_in, 1)
+    kd, pd, ldd = dev(dy_in, C)
+    d_dx = DeviceTensor.empty((N, H, W, C), ld=ldx) if with_dx else None
+    d_dw = DeviceBuffer(max(9 * C * 4, 16))
+    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_depthwise_backward_workspace_bytes(N, H, W, C))
+    check(lib().xdet_depthwise_backward(px, ldx, pk, pd, ldd, N, H, W, C, int(dilation), 1 if relu_in else 0,
+                                        d_dx.ptr if with_dx else None, ldx, d_dw.ptr, ws.ptr,
+                                        stream.handle if stream else None))
+    if d_dx is not None:
+        d_dx._keep = (kx, kk, kd, ws)          # operands and workspace live until the stream has run the call
+    d_dw._keep = (kx, kk, kd, ws)
+    return d_dx, d_dw
+
+
+def depthwise_backward(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None):
+    """host_depthwise_backward on the GPU (xdet_depthwise_backward): x, dy [N,H,W,C] and k [3,3,C,1] as NumPy arrays or
+    DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [3,3,C,1]) as NumPy arrays."""
+    d_dx, d_dw = depthwise_backward_device(x, k, dy, dilation, relu_in, with_dx, stream)
+    synchronize(stream)
+    C = int((x.shape if isinstance(x, DeviceTensor) else np.shape(x))[-1])
+    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
+    return dx, to_host(d_dw.ptr, (3, 3, C, 1), np.float32, stream)
+
+
+def add_rows_device(a, b, out=None, stream=None):
+    """out = a + b on the GPU (xdet_add_rows): a, b DeviceTensors of one shape, each read with its own ld (NumPy arrays are
+    copied to the device first); out: a DeviceTensor of that shape -- it may be a itself -- or None: a new one with a's ld.
+    -> out; nothing is synchronised."""
+    sa, a_in = _nhwc(a, 'a')
+    sb, b_in = _nhwc(b, 'b')
+    if tuple(sa) != tuple(sb) or (out is not None and (not isinstance(out, DeviceTensor) or tuple(out.shape) != tuple(sa))):
+        raise InvalidArgumentError(-1, 'add_rows: a, b and out of one shape expected, got %r'
+                                   % ([tuple(sa), tuple(sb), getattr(out, 'shape', None)],))
+    M, C = int(np.prod(sa[:3])), int(sa[3])
+    if min(M, C) <= 0 or M * C >= 2 ** 31:
+        raise InvalidArgumentError(-1, 'add_rows: %d rows of %d channels (positive, their product below 2^31)' % (M, C))
+    ta = a_in if isinstance(a_in, DeviceTensor) else DeviceTensor.from_numpy(a_in)
+    tb = b_in if isinstance(b_in, DeviceTensor) else DeviceTensor.from_numpy(b_in)
+    if out is None:
+        out = DeviceTensor.empty(sa, ld=ta.ld)
+    check(lib().xdet_add_rows(ta.ptr, ta.ld, tb.ptr, tb.ld, out.ptr, out.ld, M, C, stream.handle if stream else None))
+    # operands live until the stream has run the call (on top of what out already keeps alive)
+    out._keep = (getattr(out, '_keep', None),) + tuple(t for t in (ta, tb) if t is not out)
+    return out
