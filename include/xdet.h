@@ -761,18 +761,30 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   "rpn_hidden" = "off" | "keep": rpn_head/conv2d (net/xception_body.py:384) also writes its output after the ReLU as an
  *   f32 tensor [max_batch, h, w, 512] (xdet_net_buffer "rpn_hidden"), the ReLU mask and dense-layer input of the RPN head's
  *   backward (xdet_dense_backward, then xdet_conv_backward).  off (default): the conv writes the split planes its 1x1
- *   heads read and nothing else, and the name is refused.  "rpn_out" has the same bits either way. */
+ *   heads read and nothing else, and the name is refused.  "rpn_out" has the same bits either way.
+ *   "entry_x" = "off" | "keep": block 4's sum -- the input of the middle flow (net/xception_body.py:328), f32, in front of
+ *   block5's ReLU -- stays a named buffer [max_batch, h, w, 728] (xdet_net_buffer "entry_x") instead of going back to the
+ *   workspace pool when block 5 has read it: what a training-mode middle flow starts from.  off (default): the plan, the
+ *   kernels and their arguments are the same as ever and the name is refused.  keep: every tensor of the forward has the same
+ *   bits; only addresses inside the workspace move. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
 /* named workspace buffers (views, owned by the net): "mid","out","rpn_out","feat","objectness",
  * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts"; "pool_index" (i32, dims / ld of "pooled")
  * with option "pool_index" = "keep" only, "rpn_hidden" (f32 [max_batch,h,w,512]) with option "rpn_hidden" = "keep" only,
- * otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU */
+ * "entry_x" (f32 [max_batch,h,w,728]) with option "entry_x" = "keep" only, otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in
+ * front of its ReLU */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */
 int xdet_net_get_rpn(void* net, int N, void* stream);                                  /* :381 -> "rpn_out" */
+/* "mid_x" was rewritten from outside the net (a training-mode middle flow): re-derive from the f32 "mid_x" of the first N
+ * images everything else the net keeps of that tensor -- the ReLU split planes rpn_head/conv2d reads (block12_sepconv3's
+ * epilogue wrote them; here xdet_split_f32's pass with relu = 1 at the planes' own pre-scale, the same bits on finite data)
+ * and the "mid" buffer (ReLU(mid_x)).  A net in f32 precision has no planes: only the copy runs.  On `stream`, without a
+ * synchronisation or a host read.  XDET_ERR_INVALID_ARG for N outside 1..max_batch. */
+int xdet_net_mid_refresh(void* net, int N, void* stream);
 int xdet_net_large_sep(void* net, int N, void* stream);                                /* :450 -> "feat" */
 int xdet_net_rpn_decode(void* net, int N, void* stream);                               /* -> "objectness","rpn_boxes" */
 int xdet_net_get_proposals(void* net, int N, void* stream);                            /* :402 -> "proposals" */

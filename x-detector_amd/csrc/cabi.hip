@@ -588,6 +588,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->keep_rpn_hidden = v == "keep";
     return XDET_OK;
   }
+  if (k == "entry_x") {
+    XDET_REQUIRE(v == "keep" || v == "off", "entry_x must be keep | off");
+    n->keep_entry_x = v == "keep";
+    return XDET_OK;
+  }
   set_last_error("unknown option: " + k);
   return XDET_ERR_INVALID_ARG;
 }
@@ -623,6 +628,10 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
     XDET_REQUIRE(n->rpn_hidden.p != nullptr, "net_buffer: rpn_hidden needs a net built with the option rpn_hidden=keep");
     from_buf(n->rpn_hidden);
   }
+  else if (s == "entry_x") {
+    XDET_REQUIRE(n->entry_x.p != nullptr, "net_buffer: entry_x needs a net built with the option entry_x=keep");
+    from_buf(n->entry_x);
+  }
   else if (s == "fc") from_buf(n->fc);
   else if (s == "cls_reg") from_buf(n->cls_reg);
   else if (s == "objectness") { *dptr = n->objectness; dims[0] = B; dims[1] = n->n_anchor; dims[2] = 1; dims[3] = 1; *ld = 1; }
@@ -644,6 +653,10 @@ int xdet_net_xception_body(void* net, const float* images, int N, void* stream) 
   XDET_TRY(n->xception_body(images, N, S(stream)));
   // materialise mid_outputs = ReLU(x) for API users (the fused forward applies it on load instead)
   return launch_relu_copy(n->mid_x.p, n->mid_relu, (int64_t)N * n->mid_x.per_image(), S(stream));
+}
+int xdet_net_mid_refresh(void* net, int N, void* stream) {
+  XDET_LIGHTHEAD(n, net, "net_mid_refresh");
+  return n->mid_refresh(N, S(stream));
 }
 int xdet_net_get_rpn(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_get_rpn");

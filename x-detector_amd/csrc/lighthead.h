@@ -17,6 +17,8 @@ struct LightHeadNet : Plan {
   bool keep_pool_index = false;
   Buf rpn_hidden;                 // relu(rpn_head/conv2d) as f32 [B,h,w,512] (option "rpn_hidden" = "keep"; p stays NULL without)
   bool keep_rpn_hidden = false;
+  Buf entry_x;                    // block 4's sum, the middle flow's input, f32 [B,h,w,728] (option "entry_x" = "keep"; p stays NULL without)
+  bool keep_entry_x = false;
   float* class_probs = nullptr;   // [B][num_classes][R] softmax of the head's logits, class-major (head_decode_probs_kernel)
   float *anc_yx = nullptr, *anc_hw = nullptr;
   float* mid_relu = nullptr;   // materialised ReLU(x) ("mid_outputs", xception_body.py:339) for API users
@@ -134,6 +136,7 @@ struct LightHeadNet : Plan {
                               shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
                               cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
   }
+  int mid_refresh(int N, hipStream_t s);
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);
   int forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                     hipStream_t s);

@@ -94,7 +94,8 @@ int LightHeadNet::build_body() {
     XDET_TRY(sep_bn(pre + "_sepconv3", eps, ST_BODY, b2, sep, &c3));
     release_f32(a);                              // a block's three tensors die with it: the middle flow lives in four
     release_f32(b2);                             // f32 blocks and one planes pair instead of 24 + 24
-    release_f32(res);
+    if (blk == 5 && keep_entry_x) entry_x = res;   // a named buffer: never handed back to the pool
+    else release_f32(res);
     x = c3;
   }
   mid_x = x;   // mid_outputs = ReLU(mid_x); consumers apply the ReLU on load
@@ -375,6 +376,21 @@ int LightHeadNet::build() {
   w.clear();   // host copies are no longer needed
   built = true;
   return XDET_OK;
+}
+
+// Everything the net keeps of mid_x besides the f32 tensor, re-derived from it: the ReLU split planes block12_sepconv3's
+// epilogue wrote for the RPN 3x3 conv (the pass Plan::add_split would plan for this Buf, at the planes' own scale and form)
+// and the materialised `mid` buffer.  In f32 mode, or where the RPN conv makes its own planes per call, only the copy runs.
+int LightHeadNet::mid_refresh(int N, hipStream_t s) {
+  XDET_TRY(check(N));
+  if (mid_x.hi) {
+    XDET_REQUIRE(mid_x.planes_relu && !mid_x.no_f32, "net_mid_refresh: mid_x's planes are not the ReLU planes of an f32 tensor");
+    int x8_exp = 0;
+    const int x8 = plane_x8(mid_x.pidx, &x8_exp) ? 1 : 0;
+    XDET_TRY(launch_split_f32(mid_x.p, mid_x.hi, mid_x.lo, (int64_t)N * mid_x.H * mid_x.W, mid_x.ld, /*relu=*/1, s,
+                              pmul(mid_x.pidx), x8, x8_exp));
+  }
+  return launch_relu_copy(mid_x.p, mid_relu, (int64_t)N * mid_x.per_image(), s);
 }
 
 int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_scaled) {

@@ -34,6 +34,10 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   LightHeadDetector(exit_flow_train=True))
   (xdet.ops)              <- what tf.gradients derives for the depthwise half of tf.layers.separable_conv2d, and the
                              Xception exit flow (net/xception_body.py:339-376) with batch statistics and its backward
+  middle_flow_train, middle_flow_backward, host_middle_flow_train, host_middle_flow_backward, MIDDLE_FLOW_UNITS,
+  MIDDLE_FLOW_VARIABLES (xdet.model; LightHeadDetector(middle_flow_train=True), detector.middle_flow_saved())
+                          <- the Xception middle flow (net/xception_body.py:328-337: blocks 5-12, 24 separable units and
+                             eight residual adds) with batch statistics and its backward, from `mid_x` down to `entry_x`
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

@@ -163,6 +163,7 @@ SIGNATURES = {
                                 ctypes.POINTER(c_int)]),
     'xdet_net_xception_body': (c_int, [c_void_p, PF, c_int, c_void_p]),
     'xdet_net_get_rpn': (c_int, [c_void_p, c_int, c_void_p]),
+    'xdet_net_mid_refresh': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_large_sep': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_rpn_decode': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_get_proposals': (c_int, [c_void_p, c_int, c_void_p]),

@@ -32,6 +32,14 @@ EXIT_FLOW_VARIABLES = tuple('%s/%s' % (u[0], v) for u in EXIT_FLOW_UNITS for v i
 EXIT_FLOW_MOVING = tuple('%s/%s' % (b, v) for b in EXIT_FLOW_BNS for v in ('moving_mean', 'moving_variance'))
 EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM = 1e-4, 0.99         # net/xception_body.py: the Xception layers' batch norm
 
+# the Xception middle flow (net/xception_body.py:328-337): eight blocks of three relu -> separable 3x3 -> BN units at 728
+# channels, each block closed by a residual add of its input
+MIDDLE_FLOW_BLOCKS = tuple(range(5, 13))
+MIDDLE_FLOW_UNITS = tuple('block%d_sepconv%d' % (b, i) for b in MIDDLE_FLOW_BLOCKS for i in (1, 2, 3))
+MIDDLE_FLOW_VARIABLES = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('/depthwise_kernel', '/pointwise_kernel', '_bn/gamma', '_bn/beta'))
+MIDDLE_FLOW_MOVING = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('_bn/moving_mean', '_bn/moving_variance'))
+MIDDLE_FLOW_EPS, MIDDLE_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
+
 
 def merge_large_sep(weights, dtype=np.float32):
     """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
@@ -58,12 +66,95 @@ def split_large_sep_grads(d_ka, d_ba, d_kb, d_bb, mid):
     return out
 
 
+# ---- one `(relu ->) separable 3x3 -> BN (-> relu)` unit in training mode: what the exit flow and the middle flow share ----
+
+def _dense(k):
+    """a kernel as the checkpoint stores it -> a dense DeviceTensor (the w / k operand of the backward ops)"""
+    b = to_device(k)
+    return DeviceTensor(b.ptr, k.shape, k.shape[3], owner=b)
+
+
+def _bn_state(weights, name, co):
+    """a batch norm's vectors on the device: gamma, beta, the moving statistics (updated in place by a training forward) and
+    room for the batch statistics"""
+    vec = lambda k: to_device(np.ascontiguousarray(weights[name + '/' + k], np.float32))
+    return {'gamma': vec('gamma'), 'beta': vec('beta'), 'moving_mean': vec('moving_mean'), 'moving_variance': vec('moving_variance'),
+            'save_mean': DeviceBuffer(co * 4), 'save_invstd': DeviceBuffer(co * 4)}
+
+
+def _pointwise_layers(weights, names):
+    """{name: the 1x1 conv of <name>/pointwise_kernel in split precision, f32 out, no scale or shift}"""
+    from . import ops
+    from .runtime import get_precision, set_precision
+    before = get_precision()
+    set_precision('f16x3')
+    try:
+        return {n: ops.Conv2D(np.ascontiguousarray(weights[n + '/pointwise_kernel'], np.float32)) for n in names}
+    finally:
+        set_precision(before)
+
+
+def _build_unit(weights, name, dil, relu_in, relu_out, pw, B, H, W, own_y):
+    """the depthwise layer, the pointwise conv `pw`, both kernels as dense device tensors for the backward, the BN vectors and
+    the tensors a training forward keeps: 't' (the depthwise output), 'z' (the BN input) and, with own_y, 'y' (the BN output)"""
+    from . import ops
+    kd = np.ascontiguousarray(weights[name + '/depthwise_kernel'], np.float32)
+    kp = np.ascontiguousarray(weights[name + '/pointwise_kernel'], np.float32)
+    C, J = kp.shape[2], kp.shape[3]
+    u = {'name': name, 'dil': dil, 'relu_in': relu_in, 'relu_out': relu_out, 'dw': ops.DepthwiseConv2D(kd, dil), 'pw': pw,
+         'K_dw': _dense(kd), 'K_pw': _dense(kp), 'bn': _bn_state(weights, name + '_bn', J),
+         't': DeviceTensor.empty((B, H, W, C)), 'z': DeviceTensor.empty((B, H, W, J))}
+    if own_y:
+        u['y'] = DeviceTensor.empty((B, H, W, J))
+    return u
+
+
+def _bn_train_forward(d, b, z, relu, y, M, ws, eps=EXIT_FLOW_EPS, momentum=EXIT_FLOW_MOMENTUM):
+    check(lib().xdet_batch_norm_forward(z.ptr, z.ld, M, z.shape[3], b['gamma'].ptr, b['beta'].ptr, eps, 1, momentum,
+                                        b['moving_mean'].ptr, b['moving_variance'].ptr, 1 if relu else 0, y.ptr, y.ld,
+                                        b['save_mean'].ptr, b['save_invstd'].ptr, ws.ptr, d.stream.handle))
+
+
+def _unit_forward(d, u, x, y, n, H, W, ws_bn):
+    """y = (relu)(BN(pw(dw((relu)(x))))) with batch statistics, t and z kept in the unit: three calls on the detector's stream"""
+    t, z, h = u['t'], u['z'], d.stream.handle
+    check(lib().xdet_depthwise_forward(u['dw'].handle, x.ptr, n, H, W, x.ld, t.ptr, 1 if u['relu_in'] else 0, h))
+    check(lib().xdet_conv_forward(u['pw'].handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
+    _bn_train_forward(d, u['bn'], z, u['relu_out'], y, n * H * W, ws_bn)
+
+
+def _unit_backward(d, u, x, y, dy, z, t, dev, ws_dw, into=None):
+    """d loss / d y -> d loss / d x through the unit's BN (masked by y, the unit's own output, where it ends in a ReLU; None
+    otherwise), the 1x1 conv (its bias gradient computed and dropped: the conv has none) and the depthwise conv: three calls
+    on the detector's stream.  z, t: the kept BN input and depthwise output; dev: gains the four weight gradients as
+    (DeviceBuffer, shape) under the checkpoint's names.  into: {'dz', 'dt', 'dx': DeviceTensors to write, 'ws_bn', 'ws_conv':
+    workspaces} -- without it every call allocates its own.  -> (dx, dt, dz)"""
+    from . import ops
+    into = into or {}
+    name, b = u['name'], u['bn']
+    dz, dgamma, dbeta = ops.batch_norm_backward_device(z, y, dy, b['gamma'], b['save_mean'], b['save_invstd'], True, stream=d.stream,
+                                                       dx=into.get('dz'), workspace=into.get('ws_bn'))
+    dt, dkp, _ = ops.conv_backward_device(t, u['K_pw'], dz, None, stream=d.stream, dx=into.get('dt'), workspace=into.get('ws_conv'))
+    dx, dkd = ops.depthwise_backward_device(x, u['K_dw'], dt, u['dil'], u['relu_in'], stream=d.stream, workspace=ws_dw,
+                                            dx=into.get('dx'))
+    J = u['K_pw'].shape[3]
+    dev[name + '/depthwise_kernel'], dev[name + '/pointwise_kernel'] = (dkd, u['K_dw'].shape), (dkp, u['K_pw'].shape)
+    dev[name + '_bn/gamma'], dev[name + '_bn/beta'] = (dgamma, (J,)), (dbeta, (J,))
+    return dx, dt, dz
+
+
+def _bn_views(out, name, b):
+    co = b['save_mean'].nbytes // 4
+    for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
+        out['%s/%s' % (name, k)] = DeviceTensor(b[k].ptr, (1, 1, 1, co), co, owner=b[k])
+
+
 class LightHeadDetector(object):
     def __init__(self, weights, image_size=480, max_batch=1, num_classes=21, rpn_pre_nms_top_n=5000,
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
-                 pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False):
+                 pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -86,7 +177,21 @@ class LightHeadDetector(object):
         the device, with the tensors a training forward saves and the workspaces, all sized for max_batch:
         model.exit_flow_train() then recomputes the exit flow from `mid_x` with batch statistics into the net's `out`, and
         model.exit_flow_backward takes the gradient through it down to `mid_x`.  The default detector allocates and runs none
-        of this."""
+        of this.
+        middle_flow_train=True (needs exit_flow_train=True: the training-mode `mid_x` it writes is consumed by the training-mode
+        exit flow): the net keeps the middle flow's input (option "entry_x", buffer 'entry_x'), and the 96 variables of the 24
+        units of blocks 5-12 (MIDDLE_FLOW_VARIABLES) and their moving statistics are kept unfolded on the device with the 72
+        tensors a training forward saves (9 per block: t and z of each unit, y1, y2, the block output; ~189 MB per image at
+        480 pixels): model.middle_flow_train() recomputes `mid_x` from `entry_x` with batch statistics and refreshes what the
+        net derived from it, model.middle_flow_backward takes the gradient from `mid_x` down to `entry_x`.  The default detector
+        allocates and runs none of this."""
+        if middle_flow_train and not exit_flow_train:
+            raise InvalidArgumentError(-1, 'middle_flow_train=True needs exit_flow_train=True (the training-mode `mid_x` it writes '
+                                           'is consumed by the exit flow in training mode)')
+        if middle_flow_train:
+            miss = [k for k in MIDDLE_FLOW_VARIABLES + MIDDLE_FLOW_MOVING if k not in weights]
+            if miss:
+                raise InvalidArgumentError(-1, 'middle_flow_train: the weights lack %s' % ', '.join(miss))
         if exit_flow_train and not large_sep_train:
             raise InvalidArgumentError(-1, 'exit_flow_train=True needs large_sep_train=True (the training-mode `out` it writes is '
                                            'consumed by the large-separable block in training mode)')
@@ -130,6 +235,8 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'pool_index', b'keep'))
         if rpn_hidden:
             check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
+        if middle_flow_train:
+            check(lib().xdet_net_set_option(self.handle, b'entry_x', b'keep'))
         self.pool_index, self.rpn_hidden = bool(pool_index), bool(rpn_hidden)
         check(lib().xdet_net_build(self.handle))
         self.max_batch = max_batch
@@ -149,6 +256,9 @@ class LightHeadDetector(object):
         self.exit_flow_train = bool(exit_flow_train)
         if exit_flow_train:
             self._build_exit_flow_train(weights)
+        self.middle_flow_train = bool(middle_flow_train)
+        if middle_flow_train:
+            self._build_middle_flow_train(weights)
 
     def _build_large_sep_train(self, weights):
         """the training form of the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as
@@ -201,37 +311,22 @@ class LightHeadDetector(object):
         from . import ops
         from .runtime import get_precision, set_precision
         g = lambda k: np.ascontiguousarray(weights[k], np.float32)
-        vec = lambda a: to_device(np.ascontiguousarray(a, np.float32))
-
-        def dense(k):
-            b = to_device(k)
-            return DeviceTensor(b.ptr, k.shape, k.shape[3], owner=b)
-
-        def bn(name, co):
-            return {'gamma': vec(g(name + '/gamma')), 'beta': vec(g(name + '/beta')), 'moving_mean': vec(g(name + '/moving_mean')),
-                    'moving_variance': vec(g(name + '/moving_variance')), 'save_mean': DeviceBuffer(co * 4),
-                    'save_invstd': DeviceBuffer(co * 4)}
         B, (_, H, W, cin) = self.max_batch, self.buffer('mid_x', 1).shape
+        pw = _pointwise_layers(weights, [u[0] for u in EXIT_FLOW_UNITS])
         before = get_precision()
         set_precision('f16x3')
         try:
-            pw = {u[0]: ops.Conv2D(g(u[0] + '/pointwise_kernel')) for u in EXIT_FLOW_UNITS}
             proj = ops.Conv2D(g('conv2d_4/kernel'))
         finally:
             set_precision(before)
-        e = {'n': 0, 'units': [], 'proj': {'conv': proj, 'K': dense(g('conv2d_4/kernel'))}}
+        e = {'n': 0, 'units': [], 'proj': {'conv': proj, 'K': _dense(g('conv2d_4/kernel'))}}
         widths = [proj.cout]
         for name, dil, relu_in, relu_out in EXIT_FLOW_UNITS:
-            kd, kp = g(name + '/depthwise_kernel'), g(name + '/pointwise_kernel')
-            C, J = kp.shape[2], kp.shape[3]
-            u = {'name': name, 'dil': dil, 'relu_in': relu_in, 'relu_out': relu_out, 'dw': ops.DepthwiseConv2D(kd, dil),
-                 'pw': pw[name], 'K_dw': dense(kd), 'K_pw': dense(kp), 'bn': bn(name + '_bn', J),
-                 't': DeviceTensor.empty((B, H, W, C)), 'z': DeviceTensor.empty((B, H, W, J))}
-            if name != EXIT_FLOW_UNITS[-1][0]:           # (the last batch norm writes the net's `out`)
-                u['y'] = DeviceTensor.empty((B, H, W, J))
+            # (the last batch norm writes the net's `out`)
+            u = _build_unit(weights, name, dil, relu_in, relu_out, pw[name], B, H, W, own_y=name != EXIT_FLOW_UNITS[-1][0])
             e['units'].append(u)
-            widths += [C, J]
-        e['proj'].update(bn=bn('batch_normalization_4', proj.cout), z=DeviceTensor.empty((B, H, W, proj.cout)),
+            widths += [u['t'].shape[3], u['z'].shape[3]]
+        e['proj'].update(bn=_bn_state(weights, 'batch_normalization_4', proj.cout), z=DeviceTensor.empty((B, H, W, proj.cout)),
                          r=DeviceTensor.empty((B, H, W, proj.cout)))
         e['b2'] = DeviceTensor.empty((B, H, W, proj.cout))
         e['ws_bn'] = DeviceBuffer(max(lib().xdet_batch_norm_workspace_bytes(n * H * W, max(widths)) for n in range(1, B + 1)))
@@ -254,9 +349,47 @@ class LightHeadDetector(object):
             if y:
                 out[y] = view(u['y'])
         for name, b in [(u['name'] + '_bn', u['bn']) for u in e['units']] + [('batch_normalization_4', e['proj']['bn'])]:
-            co = b['save_mean'].nbytes // 4
-            for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
-                out['%s/%s' % (name, k)] = DeviceTensor(b[k].ptr, (1, 1, 1, co), co, owner=b[k])
+            _bn_views(out, name, b)
+        return out
+
+    def _build_middle_flow_train(self, weights):
+        """the training form of the middle flow: per unit what _build_exit_flow_train builds, the BN outputs y1, y2 and the
+        block's output (block 12's is the net's `mid_x`), one BN workspace, one depthwise-backward and one conv-backward
+        workspace for all units, and the four gradient tensors middle_flow_backward rotates through; all sized for max_batch"""
+        B, (_, H, W, C) = self.max_batch, self.buffer('entry_x', 1).shape
+        pw = _pointwise_layers(weights, MIDDLE_FLOW_UNITS)
+        m = {'n': 0, 'blocks': []}
+        for b in MIDDLE_FLOW_BLOCKS:
+            units = [_build_unit(weights, 'block%d_sepconv%d' % (b, i), 1, True, False, pw['block%d_sepconv%d' % (b, i)], B, H, W,
+                                 own_y=i < 3) for i in (1, 2, 3)]
+            m['blocks'].append({'b': b, 'units': units, 'out': DeviceTensor.empty((B, H, W, C)) if b != MIDDLE_FLOW_BLOCKS[-1] else None})
+        sizes = range(1, B + 1)
+        m['ws_bn'] = DeviceBuffer(max(lib().xdet_batch_norm_workspace_bytes(n * H * W, C) for n in sizes))
+        m['ws_dw'] = DeviceBuffer(max(lib().xdet_depthwise_backward_workspace_bytes(n, H, W, C) for n in sizes))
+        m['ws_conv'] = DeviceBuffer(max(lib().xdet_conv_backward_workspace_bytes(n, H, W, C, C, 1, 1) for n in sizes))
+        m['rot'] = {k: DeviceTensor.empty((B, H, W, C)) for k in ('dz', 'dt', 'da', 'db')}
+        self._middle = m
+
+    def middle_flow_saved(self):
+        """what the last model.middle_flow_train() left on the device, as DeviceTensors of the n images it ran on: per unit
+        '<unit>/dw' (the depthwise conv's output) and '<unit>/z' (the batch norm's input); the block inputs 'x5' (the net's
+        `entry_x`) ... 'x12' (block b's output is 'x<b+1>', block 12's the net's `mid_x`); 'block<b>/y1', 'block<b>/y2' (the
+        first two batch norm outputs; the third is overwritten by the residual add, y3 + x, in place); and per batch norm
+        '<unit>_bn/save_mean', '/save_invstd' (the batch statistics), '/moving_mean', '/moving_variance' (after their update),
+        each [1,1,1,728]"""
+        if not self.middle_flow_train or not self._middle['n']:
+            raise InvalidArgumentError(-1, 'middle_flow_saved: no model.middle_flow_train() has run on this detector')
+        m, n = self._middle, self._middle['n']
+        view = lambda t: DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+        out, x = {}, self.buffer('entry_x', n)
+        for blk in m['blocks']:
+            out['x%d' % blk['b']] = x
+            for u, y in zip(blk['units'], ('y1', 'y2', None)):
+                out[u['name'] + '/dw'], out[u['name'] + '/z'] = view(u['t']), view(u['z'])
+                if y:
+                    out['block%d/%s' % (blk['b'], y)] = view(u['y'])
+                _bn_views(out, u['name'] + '_bn', u['bn'])
+            x = view(blk['out']) if blk['out'] is not None else None
         return out
 
     # ---- plumbing -------------------------------------------------------------------
@@ -857,20 +990,13 @@ def exit_flow_train():
     _, H, W, _ = mid_x.shape
     M = n * H * W
 
-    def batch_norm(b, z, relu, y):
-        check(l.xdet_batch_norm_forward(z.ptr, z.ld, M, z.shape[3], b['gamma'].ptr, b['beta'].ptr, EXIT_FLOW_EPS, 1,
-                                        EXIT_FLOW_MOMENTUM, b['moving_mean'].ptr, b['moving_variance'].ptr, 1 if relu else 0,
-                                        y.ptr, y.ld, b['save_mean'].ptr, b['save_invstd'].ptr, e['ws_bn'].ptr, h))
     p = e['proj']
     check(l.xdet_conv_forward(p['conv'].handle, mid_x.ptr, n, H, W, mid_x.ld, p['z'].ptr, p['z'].ld, None, 0, h))
-    batch_norm(p['bn'], p['z'], False, p['r'])
+    _bn_train_forward(d, p['bn'], p['z'], False, p['r'], M, e['ws_bn'])
     x = mid_x
     for i, u in enumerate(e['units']):
-        t, z = u['t'], u['z']
-        check(l.xdet_depthwise_forward(u['dw'].handle, x.ptr, n, H, W, x.ld, t.ptr, 1 if u['relu_in'] else 0, h))
-        check(l.xdet_conv_forward(u['pw'].handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
         y = u.get('y', out)
-        batch_norm(u['bn'], z, u['relu_out'], y)
+        _unit_forward(d, u, x, y, n, H, W, e['ws_bn'])
         if i == 1:                                   # block13's residual add behind its second batch norm
             check(l.xdet_add_rows(y.ptr, y.ld, p['r'].ptr, p['r'].ld, e['b2'].ptr, e['b2'].ld, M, y.shape[3], h))
             y = e['b2']
@@ -915,13 +1041,8 @@ def exit_flow_backward(d_out, d_mid=None):
 
     def unit_backward(u, x, y, dy):
         """-> d loss / d x through BN (masked by y), the 1x1 conv and the depthwise conv"""
-        name, b = u['name'], u['bn']
-        dz, dgamma, dbeta = ops.batch_norm_backward_device(saved[name + '/z'], y, dy, b['gamma'], b['save_mean'], b['save_invstd'],
-                                                           True, stream=d.stream)
-        dt, dkp, _ = ops.conv_backward_device(saved[name + '/dw'], u['K_pw'], dz, None, stream=d.stream)
-        dx, dkd = ops.depthwise_backward_device(x, u['K_dw'], dt, u['dil'], u['relu_in'], stream=d.stream, workspace=e['ws_dw'])
-        dev[name + '/depthwise_kernel'], dev[name + '/pointwise_kernel'] = (dkd, u['K_dw'].shape), (dkp, u['K_pw'].shape)
-        dev[name + '_bn/gamma'], dev[name + '_bn/beta'] = (dgamma, (u['K_pw'].shape[3],)), (dbeta, (u['K_pw'].shape[3],))
+        name = u['name']
+        dx, dt, dz = _unit_backward(d, u, x, y, dy, saved[name + '/z'], saved[name + '/dw'], dev, e['ws_dw'])
         grads['dw/' + name], grads['z/' + name] = dt, dz
         return dx
     u1, u2, u3, u4 = e['units']
@@ -944,3 +1065,172 @@ def exit_flow_backward(d_out, d_mid=None):
         grads[k] = to_host(buf.ptr, shape)
     grads.update({'mid': mid, 'mid_A': share_a, 'mid_B': share_b, 'b2': d_b2, 'r': d_b2, 'c3': d_c3, 'a': d_a, 'z/conv2d_4': dzr})
     return grads
+
+
+def middle_flow_train():
+    """The Xception middle flow in training mode (net/xception_body.py:328-337), called after XceptionBody(...,
+    is_training=False) on a detector built with middle_flow_train=True: blocks 5-12 are computed again from the net's `entry_x`
+    buffer with batch statistics, per block
+
+        y1 = BN(pw(dw(relu(x))))    y2 = BN(pw(dw(relu(y1))))    y3 = BN(pw(dw(relu(y2))))    x' = y3 + x   (xdet_add_rows)
+
+    -- per unit xdet_depthwise_forward, the 1x1 conv (xdet_conv_forward, split precision, f32 out) and
+    xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the moving statistics updated on their device copies);
+    the third batch norm writes the block's output tensor and the add runs on it in place; block 12's is the net's `mid_x`
+    (with its ld).  Then xdet_net_mid_refresh re-derives what the net keeps of `mid_x` -- the ReLU split planes the RPN's 3x3
+    conv reads and the `mid` buffer -- so get_rpn, rpn_backward and exit_flow_train all see the training-mode tensor.  24 x 3
+    calls, 8 adds and the refresh on the detector's stream with no host round trip; `entry_x` is not written.  The exit flow's
+    saved state is dropped: exit_flow_backward refuses until exit_flow_train() has run on the new `mid_x`.  What
+    middle_flow_backward needs stays on the device (detector.middle_flow_saved()).  -> `mid` [N,h,w,728], the tensor get_rpn
+    accepts."""
+    d = _det()
+    if not d.middle_flow_train:
+        raise InvalidArgumentError(-1, 'middle_flow_train: needs a detector built with middle_flow_train=True (the default '
+                                       'detector folds the moving statistics into the conv weights and keeps no entry_x)')
+    n = d._N
+    if not n:
+        raise InvalidArgumentError(-1, 'middle_flow_train: call XceptionBody(..., is_training=False) first')
+    m, h, l = d._middle, d.stream.handle, lib()
+    x, mid_x = d.buffer('entry_x', n), d.buffer('mid_x', n)
+    _, H, W, C = x.shape
+    for blk in m['blocks']:
+        u1, u2, u3 = blk['units']
+        out = blk['out'] if blk['out'] is not None else mid_x
+        _unit_forward(d, u1, x, u1['y'], n, H, W, m['ws_bn'])
+        _unit_forward(d, u2, u1['y'], u2['y'], n, H, W, m['ws_bn'])
+        _unit_forward(d, u3, u2['y'], out, n, H, W, m['ws_bn'])
+        check(l.xdet_add_rows(out.ptr, out.ld, x.ptr, x.ld, out.ptr, out.ld, n * H * W, C, h))
+        x = out
+    check(l.xdet_net_mid_refresh(d.handle, n, h))
+    m['n'] = n
+    d._exit['n'] = 0                                 # what exit_flow_train saved belongs to another mid_x
+    _sync(d)
+    return d.buffer('mid', n)
+
+
+def middle_flow_backward(d_mid, intermediates=False):
+    """The backward of the middle flow in training mode, called after middle_flow_train() on a detector built with
+    middle_flow_train=True: d_mid = exit_flow_backward(...)['mid'] (d loss / d mid_x, with `mid_x`'s shape and ld).  From
+    block 12 back to block 5, with g = the gradient of the block's output, y1, y2 the kept batch norm outputs and x the
+    block's input:
+
+        d3 = unit_backward(u3, y2, g)    d2 = unit_backward(u2, y1, d3)    d1 = unit_backward(u1, x, d2)
+        g' = d1 + g   (xdet_add_rows, in that order)
+
+    where unit_backward is the exit flow's: xdet_batch_norm_backward on the kept BN input (no mask: these units end without a
+    ReLU), xdet_conv_backward at 1x1 on the kept depthwise output (its bias gradient computed and dropped), then
+    xdet_depthwise_backward with relu_in.  24 x 3 calls and 8 adds on the detector's stream, no float atomics, no host round trip
+    until the end: the gradients inside a block go through four tensors the detector owns, the workspaces are the detector's,
+    and what the call returns on the device is allocated in front of the first launch.  -> a dict with the 96 gradients under
+    the checkpoint's variable names and in its shapes (MIDDLE_FLOW_VARIABLES, NumPy), 'entry': d loss / d entry_x as a
+    DeviceTensor [N,h,w,728] with `entry_x`'s ld, and 'x6' ... 'x12': the gradients at the block boundaries ('x<b>' = d loss /
+    d (block b's input)).  intermediates=True: also 'dw/<unit>' = d loss / d (the unit's depthwise output), 'z/<unit>' =
+    d loss / d (its batch norm's input) and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>' (the units' input gradients; d1 is the
+    addend of the join), each in a tensor of its own."""
+    d = _det()
+    if not d.middle_flow_train:
+        raise InvalidArgumentError(-1, 'middle_flow_backward: needs a detector built with middle_flow_train=True')
+    m = d._middle
+    n = m['n']
+    if not n:
+        raise InvalidArgumentError(-1, 'middle_flow_backward: call middle_flow_train() first')
+    mid_x, entry = d.buffer('mid_x', n), d.buffer('entry_x', n)
+    if not isinstance(d_mid, DeviceTensor) or tuple(d_mid.shape) != tuple(mid_x.shape) or d_mid.ld != mid_x.ld:
+        raise InvalidArgumentError(-1, 'middle_flow_backward: d_mid must be a DeviceTensor of shape %r with ld %d, got %r'
+                                   % (tuple(mid_x.shape), mid_x.ld, (getattr(d_mid, 'shape', None), getattr(d_mid, 'ld', None))))
+    from . import ops
+    saved = d.middle_flow_saved()
+    view = lambda t: DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+    rot = {k: view(t) for k, t in m['rot'].items()}
+    shape = tuple(entry.shape)
+    # everything the call returns on the device, allocated ahead of the launches
+    grads = {('x%d' % blk['b'] if blk['b'] != MIDDLE_FLOW_BLOCKS[0] else 'entry'): DeviceTensor.empty(shape, ld=entry.ld)
+             for blk in m['blocks']}
+    if intermediates:
+        for blk in m['blocks']:
+            for i, u in enumerate(blk['units']):
+                grads['d%d/block%d' % (i + 1, blk['b'])] = DeviceTensor.empty(shape, ld=entry.ld)
+                grads['dw/' + u['name']], grads['z/' + u['name']] = DeviceTensor.empty(shape), DeviceTensor.empty(shape)
+    dev, g = {}, d_mid
+    for blk in reversed(m['blocks']):
+        b = blk['b']
+        u1, u2, u3 = blk['units']
+        x, y1, y2 = saved['x%d' % b], saved['block%d/y1' % b], saved['block%d/y2' % b]
+        dy = g
+        # the three unit gradients alternate between two tensors: a unit's dx is read by the next unit's BN backward only
+        for i, u, xin, dst in ((3, u3, y2, 'da'), (2, u2, y1, 'db'), (1, u1, x, 'da')):
+            into = {'ws_bn': m['ws_bn'], 'ws_conv': m['ws_conv'], 'dz': rot['dz'], 'dt': rot['dt'], 'dx': rot[dst]}
+            if intermediates:
+                into.update(dz=grads['z/' + u['name']], dt=grads['dw/' + u['name']], dx=grads['d%d/block%d' % (i, b)])
+            dy, _, _ = _unit_backward(d, u, xin, None, dy, saved[u['name'] + '/z'], saved[u['name'] + '/dw'], dev, m['ws_dw'], into)
+        g = ops.add_rows_device(dy, g, out=grads['x%d' % b if b != MIDDLE_FLOW_BLOCKS[0] else 'entry'], stream=d.stream)
+    _sync(d)
+    for t in list(rot.values()) + list(grads.values()):       # the stream has run every call: nothing needs keeping alive, and
+        t._keep = None                                         # the wrappers' references form a ring through the rotating views
+    for k, (buf, shp) in dev.items():
+        grads[k] = to_host(buf.ptr, shp)
+    return grads
+
+
+# ---- the middle flow's host statements: NumPy, any channel count (the weights decide), float64 as the yardstick ----------
+
+def _host_depthwise_forward(x, k, relu_in, dtype):
+    x, k = np.asarray(x, dtype), np.asarray(k, dtype)
+    N, H, W, C = x.shape
+    xp = np.pad(np.maximum(x, dtype(0)) if relu_in else x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    out = np.zeros(x.shape, dtype)
+    for a in range(3):
+        for b in range(3):
+            out += xp[:, a:a + H, b:b + W] * k[a, b, :, 0]
+    return out
+
+
+def host_middle_flow_train(entry_x, weights, dtype=np.float64, blocks=MIDDLE_FLOW_BLOCKS):
+    """The NumPy statement of middle_flow_train: entry_x [N,h,w,C] and the blocks' variables and moving statistics under the
+    checkpoint's names (C comes from the weights) -> (mid_x, saved): the output of the last block and a dict with
+    detector.middle_flow_saved()'s keys for `blocks` -- 'x<b>', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per
+    batch norm '/save_mean', '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's
+    update as ops.host_batch_norm_forward states it) -- plus 'block<b>/y3'."""
+    from . import ops
+    x, saved = np.asarray(entry_x, dtype), {}
+    for b in blocks:
+        saved['x%d' % b] = x
+        y = x
+        for i in (1, 2, 3):
+            u = 'block%d_sepconv%d' % (b, i)
+            t = _host_depthwise_forward(y, weights[u + '/depthwise_kernel'], True, dtype)
+            z = np.matmul(t, np.asarray(weights[u + '/pointwise_kernel'], dtype)[0, 0])
+            bn = u + '_bn/'
+            y, mean, invstd, mm, mv = ops.host_batch_norm_forward(z, weights[bn + 'gamma'], weights[bn + 'beta'], MIDDLE_FLOW_EPS,
+                                                                  True, MIDDLE_FLOW_MOMENTUM, weights[bn + 'moving_mean'],
+                                                                  weights[bn + 'moving_variance'], False, dtype)
+            saved[u + '/dw'], saved[u + '/z'], saved['block%d/y%d' % (b, i)] = t, z, y
+            saved.update({bn + 'save_mean': mean, bn + 'save_invstd': invstd, bn + 'moving_mean': mm, bn + 'moving_variance': mv})
+        x = y + x
+    return x, saved
+
+
+def host_middle_flow_backward(saved, weights, d_mid, dtype=np.float64, blocks=MIDDLE_FLOW_BLOCKS):
+    """The NumPy statement of middle_flow_backward(d_mid, intermediates=True): saved = what host_middle_flow_train (or
+    detector.middle_flow_saved(), as NumPy arrays) left, d_mid = d loss / d (the last block's output) -> a dict with the four
+    gradients of every unit of `blocks` under the checkpoint's names and in its shapes, 'entry' = d loss / d (the first block's
+    input), 'x<b>' for every later block, 'dw/<unit>', 'z/<unit>' and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>'.  Composed of ops.host_batch_norm_backward,
+    ops.host_conv_backward and ops.host_depthwise_backward."""
+    from . import ops
+    blocks = tuple(blocks)
+    vec = lambda a: np.asarray(a, dtype).reshape(-1)
+    g, out = np.asarray(d_mid, dtype), {}
+    for b in reversed(blocks):
+        dy = g
+        for i, xin in ((3, saved['block%d/y2' % b]), (2, saved['block%d/y1' % b]), (1, saved['x%d' % b])):
+            u = 'block%d_sepconv%d' % (b, i)
+            bn = u + '_bn/'
+            dz, dgamma, dbeta = ops.host_batch_norm_backward(saved[u + '/z'], None, dy, weights[bn + 'gamma'], vec(saved[bn + 'save_mean']),
+                                                             vec(saved[bn + 'save_invstd']), True, dtype)
+            dt, dkp, _ = ops.host_conv_backward(saved[u + '/dw'], weights[u + '/pointwise_kernel'], dz, None, False, dtype)
+            dy, dkd = ops.host_depthwise_backward(xin, weights[u + '/depthwise_kernel'], dt, 1, True, dtype)
+            out[u + '/depthwise_kernel'], out[u + '/pointwise_kernel'], out[bn + 'gamma'], out[bn + 'beta'] = dkd, dkp, dgamma, dbeta
+            out['dw/' + u], out['z/' + u], out['d%d/block%d' % (i, b)] = dt, dz, dy
+        g = dy + g
+        out['entry' if b == blocks[0] else 'x%d' % b] = g
+    return out

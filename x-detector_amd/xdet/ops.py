@@ -930,9 +930,19 @@ def _nhwc(a, what):
     return a.shape, a
 
 
-def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
+def _own_dx(dx, shape, who):
+    """a caller's gradient tensor (the dx= of the *_backward_device calls): a DeviceTensor of dx's shape, written with its ld"""
+    if not isinstance(dx, DeviceTensor) or tuple(dx.shape) != tuple(shape):
+        raise InvalidArgumentError(-1, '%s: dx must be a DeviceTensor of shape %r, got %r' % (who, tuple(shape), getattr(dx, 'shape', None)))
+    return dx
+
+
+def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, dx=None, workspace=None):
     """conv_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
-    dw DeviceBuffer [kh,kw,C,J], db DeviceBuffer [J]); nothing is synchronised.  A DeviceTensor w is [kh,kw,C,J] dense."""
+    dw DeviceBuffer [kh,kw,C,J], db DeviceBuffer [J]); nothing is synchronised.  A DeviceTensor w is [kh,kw,C,J] dense.
+    dx: a DeviceTensor [N,H,W,C] to write instead of a new one (with its ld); workspace: a DeviceBuffer of at least
+    xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw) bytes (default: allocated here) -- a chain of calls on one
+    stream then allocates no activation-sized memory per call."""
     (N, H, W, C), x_in = _nhwc(x, 'x')
     (kh, kw, Cw, J), w_in = _nhwc(w, 'w')
     sd, dy_in = _nhwc(dy, 'dy')
@@ -960,11 +970,13 @@ def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=N
     kw_, pw, _ = dev(w_in, J)
     kd, pd, ldd = dev(dy_in, J)
     ky, py, ldy = dev(y_in, J) if y is not None else (None, None, 0)
-    d_dx = DeviceTensor.empty((N, H, W, C), ld=ldx) if with_dx else None
+    d_dx = None
+    if with_dx:
+        d_dx = _own_dx(dx, (N, H, W, C), 'conv_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=ldx)
     d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
-    ws = DeviceBuffer(lib().xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw))
+    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw))
     check(lib().xdet_conv_backward(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, 1 if relu_in else 0,
-                                   d_dx.ptr if with_dx else None, ldx, d_dw.ptr, d_db.ptr, ws.ptr,
+                                   d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, d_db.ptr, ws.ptr,
                                    stream.handle if stream else None))
     if d_dx is not None:
         d_dx._keep = (kx, kw_, kd, ky, ws)     # operands and workspace live until the stream has run the call
@@ -1119,9 +1131,12 @@ def batch_norm_forward(x, gamma, beta, eps, training=True, momentum=0.997, movin
     return np.ascontiguousarray(y), vec(d_mean), vec(d_inv), vec(d_mm), vec(d_mv)
 
 
-def batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None):
+def batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None, dx=None,
+                               workspace=None):
     """batch_norm_backward with the results left on the GPU: (dx DeviceTensor with x's shape and ld (C for a NumPy x) or None,
-    dgamma DeviceBuffer [C], dbeta DeviceBuffer [C]); nothing is synchronised."""
+    dgamma DeviceBuffer [C], dbeta DeviceBuffer [C]); nothing is synchronised.  dx: a DeviceTensor of x's shape to write
+    instead of a new one (with its ld; it must not overlap x); workspace: a DeviceBuffer of at least
+    xdet_batch_norm_workspace_bytes(M, C) bytes (default: allocated here)."""
     shape, M, C, x_in = _bn_rows(x, 'x')
     sd, Md, Cd, dy_in = _bn_rows(dy, 'dy')
     bad = (Md, Cd) != (M, C)
@@ -1138,11 +1153,14 @@ def batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training
     kg, pg = _bn_vec(gamma, C, 'gamma')
     km, pm = _bn_vec(save_mean, C, 'save_mean')
     ki, pi = _bn_vec(save_invstd, C, 'save_invstd')
-    d_dx = DeviceTensor.empty(shape if len(shape) == 4 else (M, 1, 1, C), ld=ldx) if with_dx else None
+    d_dx = None
+    if with_dx:
+        shape4 = shape if len(shape) == 4 else (M, 1, 1, C)
+        d_dx = _own_dx(dx, shape4, 'batch_norm_backward') if dx is not None else DeviceTensor.empty(shape4, ld=ldx)
     d_dg, d_db = DeviceBuffer(max(C * 4, 16)), DeviceBuffer(max(C * 4, 16))
-    ws = DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
+    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
     check(lib().xdet_batch_norm_backward(px, ldx, py, ldy, pd, ldd, M, C, pg, pm, pi, 1 if training else 0,
-                                         d_dx.ptr if with_dx else None, ldx, d_dg.ptr, d_db.ptr, ws.ptr,
+                                         d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dg.ptr, d_db.ptr, ws.ptr,
                                          stream.handle if stream else None))
     d_dg._keep = (kx, kd, ky, kg, km, ki, ws)    # operands and workspace live until the stream has run the call
     return d_dx, d_dg, d_db
@@ -1194,10 +1212,11 @@ def host_depthwise_backward(x, k, dy, dilation=1, relu_in=False, dtype=np.float3
     return dx, dw
 
 
-def depthwise_backward_device(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None, workspace=None):
+def depthwise_backward_device(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None, workspace=None, dx=None):
     """depthwise_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
     dw DeviceBuffer [3,3,C,1]); nothing is synchronised.  A DeviceTensor k is [3,3,C,1] dense (ld 1).  workspace: a
-    DeviceBuffer of at least xdet_depthwise_backward_workspace_bytes(N, H, W, C) bytes (default: allocated here)."""
+    DeviceBuffer of at least xdet_depthwise_backward_workspace_bytes(N, H, W, C) bytes (default: allocated here).  dx: a
+    DeviceTensor [N,H,W,C] to write instead of a new one (with its ld; it must not overlap x or dy)."""
     (N, H, W, C), x_in = _nhwc(x, 'x')
     sk, k_in = _nhwc(k, 'k')
     sd, dy_in = _nhwc(dy, 'dy')
@@ -1219,11 +1238,13 @@ def depthwise_backward_device(x, k, dy, dilation=1, relu_in=False, with_dx=True,
     kx, px, ldx = dev(x_in, C)
     kk, pk, _ = dev(k_in, 1)
     kd, pd, ldd = dev(dy_in, C)
-    d_dx = DeviceTensor.empty((N, H, W, C), ld=ldx) if with_dx else None
+    d_dx = None
+    if with_dx:
+        d_dx = _own_dx(dx, (N, H, W, C), 'depthwise_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=ldx)
     d_dw = DeviceBuffer(max(9 * C * 4, 16))
     ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_depthwise_backward_workspace_bytes(N, H, W, C))
     check(lib().xdet_depthwise_backward(px, ldx, pk, pd, ldd, N, H, W, C, int(dilation), 1 if relu_in else 0,
-                                        d_dx.ptr if with_dx else None, ldx, d_dw.ptr, ws.ptr,
+                                        d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, ws.ptr,
                                         stream.handle if stream else None))
     if d_dx is not None:
         d_dx._keep = (kx, kk, kd, ws)          # operands and workspace live until the stream has run the call
