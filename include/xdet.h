@@ -710,6 +710,29 @@ int xdet_depthwise_backward(const float* x, int ld_x, const float* k, const floa
  * XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, an ld below C, a NULL a, b or out. */
 int xdet_add_rows(const float* a, int ld_a, const float* b, int ld_b, float* out, int ld_out, int M, int C, void* stream);
 
+/* ---- the backward of max_pooling2d(3, 2, 'same') and the stride-2 gather / scatter of a 1x1 / stride-2 projection
+ *      (csrc/pool_backward.hip): what the Xception entry flow's backward adds to the op set ------------------------------
+ * x [N,H,W,C] (the pool's input), dy [N,Ho,Wo,C], dx [N,H,W,C], f32 NHWC, each with a pixel stride ld >= C.  Geometry is
+ * TensorFlow's 'SAME': Ho = ceil(H / 2), Wo = ceil(W / 2), total padding max((Ho - 1) * 2 + 3 - H, 0) with the smaller half in
+ * front (1 / 1 on an odd extent, 0 / 1 on an even one); a padded position never wins and windows never cross an image.
+ *   Each window sends its dy to its FIRST maximum in row-major window order: strict > against the running best, which starts
+ *   at the window's first in-image element (so a NaN wins only from that place).  A pixel lies in at most 2 x 2 windows; their
+ *   shares are added to 0 in ascending (oh, ow) order, each add rounded: ops.host_max_pool_backward in float32, bit for bit.
+ *   dx is written completely (0 where nothing arrives); its columns C .. ld - 1 are not written, and those of x and dy are
+ *   read into no result.  A gather over x -- no stored argmax, no float atomics: the same call gives the same bits.
+ * Limits: C <= 4096; N * H * W * max(C, every ld) < 2^31.  The call does not synchronise and reads nothing on the host.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a size <= 0 or outside the limits, an ld below C, a NULL x, dy or dx. */
+int xdet_maxpool3x3s2_backward(const float* x, int ld_x, const float* dy, int ld_dy, int N, int H, int W, int C, float* dx, int ld_dx,
+                               void* stream);
+/* out[n,i,j,:] = x[n,2i,2j,:], out [N, ceil(H/2), ceil(W/2), C]: the input a 1x1 / stride-2 'SAME' conv reads (its padding is 0
+ * for every H), dense for xdet_conv_backward.  Same limits and errors as above (N, H, W are x's). */
+int xdet_subsample2(const float* x, int ld_x, int N, int H, int W, int C, float* out, int ld_out, void* stream);
+/* out[n,h,w,:] = a[n,h,w,:] + b[n,h/2,w/2,:] where h and w are both even, a's bits everywhere else; a, out [N,H,W,C],
+ * b [N, ceil(H/2), ceil(W/2), C]: the adjoint of xdet_subsample2 added to a, the join of a block's two input gradients.  out
+ * may be a itself; any other overlap is not allowed.  Same limits and errors as above. */
+int xdet_add_upsample2(const float* a, int ld_a, const float* b, int ld_b, int N, int H, int W, int C, float* out, int ld_out,
+                       void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {
@@ -766,15 +789,20 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   block5's ReLU -- stays a named buffer [max_batch, h, w, 728] (xdet_net_buffer "entry_x") instead of going back to the
  *   workspace pool when block 5 has read it: what a training-mode middle flow starts from.  off (default): the plan, the
  *   kernels and their arguments are the same as ever and the name is refused.  keep: every tensor of the forward has the same
- *   bits; only addresses inside the workspace move. */
+ *   bits; only addresses inside the workspace move.
+ *   "stem_out" = "off" | "keep": the output of block1_conv2 + BN + ReLU -- the input of the entry flow's block 2
+ *   (net/xception_body.py:260), f32 in every plan -- stays a named buffer [max_batch, h, w, 64] (xdet_net_buffer "stem_out")
+ *   instead of going back to the workspace pool when block 2 has read it: what a training-mode entry flow starts from.  off
+ *   (default): the plan, the kernels and their arguments are the same as ever and the name is refused.  keep: every tensor of
+ *   the forward has the same bits; only addresses inside the workspace move. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
 /* named workspace buffers (views, owned by the net): "mid","out","rpn_out","feat","objectness",
  * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts"; "pool_index" (i32, dims / ld of "pooled")
  * with option "pool_index" = "keep" only, "rpn_hidden" (f32 [max_batch,h,w,512]) with option "rpn_hidden" = "keep" only,
- * "entry_x" (f32 [max_batch,h,w,728]) with option "entry_x" = "keep" only, otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in
- * front of its ReLU */
+ * "entry_x" (f32 [max_batch,h,w,728]) with option "entry_x" = "keep" only, "stem_out" (f32 [max_batch,h,w,64]) with option
+ * "stem_out" = "keep" only, otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */

@@ -593,6 +593,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->keep_entry_x = v == "keep";
     return XDET_OK;
   }
+  if (k == "stem_out") {
+    XDET_REQUIRE(v == "keep" || v == "off", "stem_out must be keep | off");
+    n->keep_stem_out = v == "keep";
+    return XDET_OK;
+  }
   set_last_error("unknown option: " + k);
   return XDET_ERR_INVALID_ARG;
 }
@@ -631,6 +636,10 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
   else if (s == "entry_x") {
     XDET_REQUIRE(n->entry_x.p != nullptr, "net_buffer: entry_x needs a net built with the option entry_x=keep");
     from_buf(n->entry_x);
+  }
+  else if (s == "stem_out") {
+    XDET_REQUIRE(n->stem_out.p != nullptr, "net_buffer: stem_out needs a net built with the option stem_out=keep");
+    from_buf(n->stem_out);
   }
   else if (s == "fc") from_buf(n->fc);
   else if (s == "cls_reg") from_buf(n->cls_reg);

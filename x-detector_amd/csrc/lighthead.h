@@ -19,6 +19,8 @@ struct LightHeadNet : Plan {
   bool keep_rpn_hidden = false;
   Buf entry_x;                    // block 4's sum, the middle flow's input, f32 [B,h,w,728] (option "entry_x" = "keep"; p stays NULL without)
   bool keep_entry_x = false;
+  Buf stem_out;                   // relu(BN(block1_conv2)), the entry flow's input, f32 [B,h,w,64] (option "stem_out" = "keep"; p stays NULL without)
+  bool keep_stem_out = false;
   float* class_probs = nullptr;   // [B][num_classes][R] softmax of the head's logits, class-major (head_decode_probs_kernel)
   float *anc_yx = nullptr, *anc_hw = nullptr;
   float* mid_relu = nullptr;   // materialised ReLU(x) ("mid_outputs", xception_body.py:339) for API users

@@ -44,6 +44,7 @@ int LightHeadNet::build_body() {
   ConvArgs c2;
   c2.k = 3; c2.cout = 64; c2.pad_mode = 0; c2.relu_out = 1;
   XDET_TRY(conv_bn("block1_conv2", "block1_conv2_bn", eps, ST_BODY, x, c2, &t));
+  XDET_REQUIRE(!keep_stem_out || (t.p && !t.no_f32), "plan: stem_out=keep, but block1_conv2 writes no f32 output");
   x = t;
   struct Blk { const char* res; const char* bn; const char* s1; const char* s2; int c; int first_relu; };
   const Blk blks[3] = {{"conv2d_1", "batch_normalization_1", "block2_sepconv1", "block2_sepconv2", 128, 0},
@@ -76,7 +77,8 @@ int LightHeadNet::build_body() {
     XDET_TRY(sep_bn(b.s2, eps, ST_BODY, a, s2, &p));
     presub = nsub;
     x_is_relu = nsub.hi != nullptr;
-    release_f32(x);                              // the block input: read by the projection and sepconv1
+    if (bi == 0 && keep_stem_out) stem_out = x;  // a named buffer: never handed back to the pool
+    else release_f32(x);                         // the block input: read by the projection and sepconv1
     release_f32(a);
     release_f32(r);
     x = p;

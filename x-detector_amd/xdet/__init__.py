@@ -38,6 +38,12 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
   MIDDLE_FLOW_VARIABLES (xdet.model; LightHeadDetector(middle_flow_train=True), detector.middle_flow_saved())
                           <- the Xception middle flow (net/xception_body.py:328-337: blocks 5-12, 24 separable units and
                              eight residual adds) with batch statistics and its backward, from `mid_x` down to `entry_x`
+  max_pool_backward, host_max_pool_backward, subsample2_device, add_upsample2_device (xdet.ops); entry_flow_train,
+  entry_flow_backward, host_entry_flow_train, host_entry_flow_backward, ENTRY_FLOW_UNITS, ENTRY_FLOW_VARIABLES (xdet.model;
+  LightHeadDetector(entry_flow_train=True), detector.entry_flow_saved())
+                          <- the gradient of max_pooling2d(3, 2, 'same') and blocks 2-4 of the Xception entry flow
+                             (net/xception_body.py:260-326) with batch statistics and their backward, from `entry_x` down to
+                             the stem's output `stem_out`
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

@@ -154,6 +154,9 @@ SIGNATURES = {
     'xdet_depthwise_backward_workspace_bytes': (c_size_t, [c_int] * 4),
     'xdet_depthwise_backward': (c_int, [PF, c_int, PF, PF, c_int] + [c_int] * 6 + [PF, c_int, PF, c_void_p, c_void_p]),
     'xdet_add_rows': (c_int, [PF, c_int, PF, c_int, PF, c_int, c_int, c_int, c_void_p]),
+    'xdet_maxpool3x3s2_backward': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
+    'xdet_subsample2': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
+    'xdet_add_upsample2': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),

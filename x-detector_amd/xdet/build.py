@@ -33,6 +33,7 @@ SOURCES = [
     ('conv_backward.hip', []),
     ('batchnorm.hip', ['-ffp-contract=off']),
     ('depthwise_backward.hip', ['-ffp-contract=off']),
+    ('pool_backward.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

@@ -40,6 +40,28 @@ MIDDLE_FLOW_VARIABLES = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('/depth
 MIDDLE_FLOW_MOVING = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('_bn/moving_mean', '_bn/moving_variance'))
 MIDDLE_FLOW_EPS, MIDDLE_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
 
+# blocks 2-4 of the Xception entry flow (net/xception_body.py:260-326): a 1x1 / stride-2 projection with its batch norm, two
+# (relu ->) separable 3x3 -> BN units, max_pooling2d(3, 2, 'same') and the residual add; block 2's first unit has no ReLU in
+# front (its input is the stem's ReLU output)
+ENTRY_FLOW_BLOCKS = (2, 3, 4)
+ENTRY_FLOW_UNITS = tuple('block%d_sepconv%d' % (b, i) for b in ENTRY_FLOW_BLOCKS for i in (1, 2))
+
+
+def _entry_block_variables(b):
+    return ('conv2d_%d/kernel' % (b - 1), 'batch_normalization_%d/gamma' % (b - 1), 'batch_normalization_%d/beta' % (b - 1)) + \
+        tuple('block%d_sepconv%d%s' % (b, i, v) for i in (1, 2) for v in ('/depthwise_kernel', '/pointwise_kernel', '_bn/gamma', '_bn/beta'))
+
+
+ENTRY_FLOW_VARIABLES = tuple(v for b in ENTRY_FLOW_BLOCKS for v in _entry_block_variables(b))
+ENTRY_FLOW_MOVING = tuple('%s/%s' % (bn, v) for b in ENTRY_FLOW_BLOCKS
+                          for bn in ('batch_normalization_%d' % (b - 1), 'block%d_sepconv1_bn' % b, 'block%d_sepconv2_bn' % b)
+                          for v in ('moving_mean', 'moving_variance'))
+ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
+
+
+def _entry_relu_in(b, i):
+    return not (b == 2 and i == 1)
+
 
 def merge_large_sep(weights, dtype=np.float32):
     """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
@@ -154,7 +176,8 @@ class LightHeadDetector(object):
                  rpn_post_nms_top_n=1000, rpn_nms_thres=0.7, rpn_min_size=None, select_threshold=0.01,
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
-                 pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False):
+                 pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
+                 entry_flow_train=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -184,7 +207,22 @@ class LightHeadDetector(object):
         tensors a training forward saves (9 per block: t and z of each unit, y1, y2, the block output; ~189 MB per image at
         480 pixels): model.middle_flow_train() recomputes `mid_x` from `entry_x` with batch statistics and refreshes what the
         net derived from it, model.middle_flow_backward takes the gradient from `mid_x` down to `entry_x`.  The default detector
-        allocates and runs none of this."""
+        allocates and runs none of this.
+        entry_flow_train=True (needs middle_flow_train=True: the training-mode `entry_x` it writes is consumed by the
+        training-mode middle flow): the net keeps the stem's output (option "stem_out", buffer 'stem_out'), and the 33 variables
+        of blocks 2-4 (ENTRY_FLOW_VARIABLES) and the moving statistics of their nine batch norms are kept unfolded on the device
+        with the tensors a training forward saves (per block the subsampled input xs, the projection's z and r, t, z and y of
+        both units and the block's output), the workspaces and the gradient tensors the backward writes, all sized for
+        max_batch: model.entry_flow_train() recomputes `entry_x` from `stem_out` with batch statistics,
+        model.entry_flow_backward takes the gradient from `entry_x` down to `stem_out`.  The default detector allocates and runs
+        none of this."""
+        if entry_flow_train and not middle_flow_train:
+            raise InvalidArgumentError(-1, 'entry_flow_train=True needs middle_flow_train=True (the training-mode `entry_x` it '
+                                           'writes is consumed by the middle flow in training mode)')
+        if entry_flow_train:
+            miss = [k for k in ENTRY_FLOW_VARIABLES + ENTRY_FLOW_MOVING if k not in weights]
+            if miss:
+                raise InvalidArgumentError(-1, 'entry_flow_train: the weights lack %s' % ', '.join(miss))
         if middle_flow_train and not exit_flow_train:
             raise InvalidArgumentError(-1, 'middle_flow_train=True needs exit_flow_train=True (the training-mode `mid_x` it writes '
                                            'is consumed by the exit flow in training mode)')
@@ -237,6 +275,8 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
         if middle_flow_train:
             check(lib().xdet_net_set_option(self.handle, b'entry_x', b'keep'))
+        if entry_flow_train:
+            check(lib().xdet_net_set_option(self.handle, b'stem_out', b'keep'))
         self.pool_index, self.rpn_hidden = bool(pool_index), bool(rpn_hidden)
         check(lib().xdet_net_build(self.handle))
         self.max_batch = max_batch
@@ -259,6 +299,9 @@ class LightHeadDetector(object):
         self.middle_flow_train = bool(middle_flow_train)
         if middle_flow_train:
             self._build_middle_flow_train(weights)
+        self.entry_flow_train = bool(entry_flow_train)
+        if entry_flow_train:
+            self._build_entry_flow_train(weights)
 
     def _build_large_sep_train(self, weights):
         """the training form of the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as
@@ -390,6 +433,78 @@ class LightHeadDetector(object):
                     out['block%d/%s' % (blk['b'], y)] = view(u['y'])
                 _bn_views(out, u['name'] + '_bn', u['bn'])
             x = view(blk['out']) if blk['out'] is not None else None
+        return out
+
+    def _build_entry_flow_train(self, weights):
+        """the training form of blocks 2-4: per block both units as _build_unit builds them (each keeps its y), the projection
+        (conv layer in split precision, dense kernel, BN vectors, z and r), the subsampled input xs, the block's output (block
+        4's is the net's `entry_x`) and the gradient tensors entry_flow_backward writes inside the block; one BN, one
+        depthwise-backward and one conv-backward workspace for all; everything sized for max_batch"""
+        from . import ops
+        from .runtime import get_precision, set_precision
+        g = lambda k: np.ascontiguousarray(weights[k], np.float32)
+        B, (_, H, W, cin) = self.max_batch, self.buffer('stem_out', 1).shape
+        pw = _pointwise_layers(weights, ENTRY_FLOW_UNITS)
+        e = {'n': 0, 'blocks': []}
+        sizes, need = range(1, B + 1), {'bn': 0, 'dw': 0, 'conv': 0}
+        l = lib()
+        for b in ENTRY_FLOW_BLOCKS:
+            kname, bn = 'conv2d_%d/kernel' % (b - 1), 'batch_normalization_%d' % (b - 1)
+            before = get_precision()
+            set_precision('f16x3')
+            try:
+                proj = ops.Conv2D(g(kname))
+            finally:
+                set_precision(before)
+            c, Ho, Wo = proj.cout, -(-H // 2), -(-W // 2)
+            units = [_build_unit(weights, 'block%d_sepconv%d' % (b, i), 1, _entry_relu_in(b, i), False, pw['block%d_sepconv%d' % (b, i)],
+                                 B, H, W, own_y=True) for i in (1, 2)]
+            full, half = (lambda ch: DeviceTensor.empty((B, H, W, ch))), (lambda ch: DeviceTensor.empty((B, Ho, Wo, ch)))
+            e['blocks'].append({'b': b, 'units': units, 'H': H, 'W': W, 'cin': cin, 'c': c, 'xs': half(cin),
+                                'proj': {'name': 'conv2d_%d' % (b - 1), 'bn_name': bn, 'conv': proj, 'K': _dense(g(kname)),
+                                         'bn': _bn_state(weights, bn, c), 'z': half(c), 'r': half(c)},
+                                'out': half(c) if b != ENTRY_FLOW_BLOCKS[-1] else None,
+                                # a unit's dz is dead once its conv backward has run: one tensor serves both units
+                                'rot': {'dzr': half(c), 'dxs': half(cin), 'dy2': full(c), 'dz': full(c), 'dt2': full(c),
+                                        'd2': full(c), 'dt1': full(cin), 'd1': full(cin)}})
+            for n in sizes:
+                need['bn'] = max(need['bn'], l.xdet_batch_norm_workspace_bytes(n * H * W, c), l.xdet_batch_norm_workspace_bytes(n * Ho * Wo, c))
+                need['dw'] = max(need['dw'], l.xdet_depthwise_backward_workspace_bytes(n, H, W, c),
+                                 l.xdet_depthwise_backward_workspace_bytes(n, H, W, cin))
+                need['conv'] = max(need['conv'], l.xdet_conv_backward_workspace_bytes(n, Ho, Wo, cin, c, 1, 1),
+                                   l.xdet_conv_backward_workspace_bytes(n, H, W, cin, c, 1, 1),
+                                   l.xdet_conv_backward_workspace_bytes(n, H, W, c, c, 1, 1))
+            H, W, cin = Ho, Wo, c
+        ex = self.buffer('entry_x', 1)
+        if tuple(ex.shape[1:]) != (H, W, cin):
+            raise InvalidArgumentError(-1, 'entry_flow_train: block 4 gives %r but the net\'s entry_x is %r' % ((H, W, cin), tuple(ex.shape[1:])))
+        e['ws_bn'], e['ws_dw'], e['ws_conv'] = DeviceBuffer(need['bn']), DeviceBuffer(need['dw']), DeviceBuffer(need['conv'])
+        self._entry = e
+
+    def entry_flow_saved(self):
+        """what the last model.entry_flow_train() left on the device, as DeviceTensors of the n images it ran on: the block
+        inputs 'x2' (the net's `stem_out`), 'x3', 'x4' and 'x5' (block 4's output, the net's `entry_x`); per block 'block<b>/xs'
+        (the subsampled input), 'conv2d_<b-1>/z' (the projection's output, its batch norm's input), 'block<b>/r' (that batch
+        norm's output, the shortcut), 'block<b>/y1', 'block<b>/y2' (the units' batch norm outputs; y2 is the pool's input); per
+        unit '<unit>/dw' (the depthwise conv's output) and '<unit>/z' (the batch norm's input); and per batch norm
+        '<bn>/save_mean', '/save_invstd' (the batch statistics), '/moving_mean', '/moving_variance' (after their update), each
+        [1,1,1,C]"""
+        if not self.entry_flow_train or not self._entry['n']:
+            raise InvalidArgumentError(-1, 'entry_flow_saved: no model.entry_flow_train() has run on this detector')
+        e, n = self._entry, self._entry['n']
+        view = lambda t: DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+        out, x = {}, self.buffer('stem_out', n)
+        for blk in e['blocks']:
+            b, p = blk['b'], blk['proj']
+            out['x%d' % b] = x
+            out['block%d/xs' % b], out[p['name'] + '/z'], out['block%d/r' % b] = view(blk['xs']), view(p['z']), view(p['r'])
+            _bn_views(out, p['bn_name'], p['bn'])
+            for u, y in zip(blk['units'], ('y1', 'y2')):
+                out[u['name'] + '/dw'], out[u['name'] + '/z'] = view(u['t']), view(u['z'])
+                out['block%d/%s' % (b, y)] = view(u['y'])
+                _bn_views(out, u['name'] + '_bn', u['bn'])
+            x = view(blk['out']) if blk['out'] is not None else self.buffer('entry_x', n)
+        out['x%d' % (ENTRY_FLOW_BLOCKS[-1] + 1)] = x
         return out
 
     # ---- plumbing -------------------------------------------------------------------
@@ -1172,6 +1287,131 @@ def middle_flow_backward(d_mid, intermediates=False):
     return grads
 
 
+def entry_flow_train():
+    """Blocks 2-4 of the Xception entry flow in training mode (net/xception_body.py:260-326), called after XceptionBody(...,
+    is_training=False) on a detector built with entry_flow_train=True: the three blocks are computed again from the net's
+    `stem_out` buffer with batch statistics, per block with x its input
+
+        xs = subsample2(x)   (xdet_subsample2)        r  = BN(conv1x1(xs))
+        y1 = BN(pw(dw(relu?(x))))                     y2 = BN(pw(dw(relu(y1))))       (no ReLU in front of block2_sepconv1)
+        x' = maxpool3x3s2(y2) + r                     (xdet_maxpool3x3s2_add)
+
+    -- the convs by xdet_depthwise_forward and xdet_conv_forward (split precision, f32 out), the batch norms by
+    xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the moving statistics updated on their device copies);
+    block 4's x' is written into the net's `entry_x` (with its ld).  33 calls on the detector's stream with no host round
+    trip; `stem_out` is not written.  The middle and the exit flow's saved state is dropped: their backwards refuse until
+    middle_flow_train() / exit_flow_train() have run on the new tensors.  What entry_flow_backward needs stays on the device
+    (detector.entry_flow_saved()).  -> `entry_x` [N,h,w,728]."""
+    d = _det()
+    if not getattr(d, 'entry_flow_train', False):
+        raise InvalidArgumentError(-1, 'entry_flow_train: needs a detector built with entry_flow_train=True (the default detector '
+                                       'folds the moving statistics into the conv weights and keeps no stem_out)')
+    n = d._N
+    if not n:
+        raise InvalidArgumentError(-1, 'entry_flow_train: call XceptionBody(..., is_training=False) first')
+    e, h, l = d._entry, d.stream.handle, lib()
+    x = d.buffer('stem_out', n)
+    for blk in e['blocks']:
+        (u1, u2), p, xs = blk['units'], blk['proj'], blk['xs']
+        H, W, cin, c = blk['H'], blk['W'], blk['cin'], blk['c']
+        Ho, Wo = -(-H // 2), -(-W // 2)
+        out = blk['out'] if blk['out'] is not None else d.buffer('entry_x', n)
+        check(l.xdet_subsample2(x.ptr, x.ld, n, H, W, cin, xs.ptr, xs.ld, h))
+        check(l.xdet_conv_forward(p['conv'].handle, xs.ptr, n, Ho, Wo, xs.ld, p['z'].ptr, p['z'].ld, None, 0, h))
+        _bn_train_forward(d, p['bn'], p['z'], False, p['r'], n * Ho * Wo, e['ws_bn'])
+        _unit_forward(d, u1, x, u1['y'], n, H, W, e['ws_bn'])
+        _unit_forward(d, u2, u1['y'], u2['y'], n, H, W, e['ws_bn'])
+        y2, r = u2['y'], p['r']
+        if not (y2.ld == r.ld == out.ld):
+            raise XdetError(-3, 'entry_flow_train: pixel strides %r of y2, r and the block output differ' % ((y2.ld, r.ld, out.ld),))
+        check(l.xdet_maxpool3x3s2_add(y2.ptr, r.ptr, out.ptr, n, H, W, c, y2.ld, h))
+        x = out
+    e['n'] = n
+    d._middle['n'] = 0                               # what the later flows saved belongs to another entry_x
+    d._exit['n'] = 0
+    _sync(d)
+    return d.buffer('entry_x', n)
+
+
+def entry_flow_backward(d_entry, intermediates=False):
+    """The backward of blocks 2-4 in training mode, called after entry_flow_train() on a detector built with
+    entry_flow_train=True: d_entry = middle_flow_backward(...)['entry'] (d loss / d entry_x, with `entry_x`'s shape and ld).
+    From block 4 back to block 2, with g the gradient of the block's output, x the block's input and y1, y2 the kept batch
+    norm outputs:
+
+        dzr = BN_backward(proj, g)       dxs, dK = conv_backward(xs, K, dzr)          (the bias gradient is dropped)
+        dy2 = maxpool_backward(y2, g)    (xdet_maxpool3x3s2_backward)
+        d2  = unit_backward(u2, y1, dy2)       d1 = unit_backward(u1, x, d2)
+        g'  = add_upsample2(d1, dxs)     (xdet_add_upsample2: the shortcut's share lands on the even pixels)
+
+    where unit_backward is the other flows': xdet_batch_norm_backward, xdet_conv_backward at 1x1, xdet_depthwise_backward.
+    Everything runs on the detector's stream with no host round trip until the end and no float atomics; the gradients inside
+    a block go through tensors the detector owns, the workspaces are the detector's, and what the call returns on the device
+    is allocated in front of the first launch.  -> a dict with the 33 gradients under the checkpoint's variable names and in
+    its shapes (ENTRY_FLOW_VARIABLES, NumPy), 'stem': d loss / d stem_out as a DeviceTensor [N,h,w,64] with `stem_out`'s ld, and
+    'x3', 'x4': the gradients at the block boundaries ('x<b>' = d loss / d (block b's input)).  intermediates=True: also
+    'dxs/block<b>', 'z/conv2d_<b-1>' (dzr), 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>' and per unit 'dw/<unit>' =
+    d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own."""
+    d = _det()
+    if not getattr(d, 'entry_flow_train', False):
+        raise InvalidArgumentError(-1, 'entry_flow_backward: needs a detector built with entry_flow_train=True')
+    e = d._entry
+    n = e['n']
+    if not n:
+        raise InvalidArgumentError(-1, 'entry_flow_backward: call entry_flow_train() first')
+    entry = d.buffer('entry_x', n)
+    if not isinstance(d_entry, DeviceTensor) or tuple(d_entry.shape) != tuple(entry.shape) or d_entry.ld != entry.ld:
+        raise InvalidArgumentError(-1, 'entry_flow_backward: d_entry must be a DeviceTensor of shape %r with ld %d, got %r'
+                                   % (tuple(entry.shape), entry.ld, (getattr(d_entry, 'shape', None), getattr(d_entry, 'ld', None))))
+    from . import ops
+    saved = d.entry_flow_saved()
+    view = lambda t: DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+    first = ENTRY_FLOW_BLOCKS[0]
+    # everything the call returns on the device, allocated ahead of the launches
+    grads, inner = {}, {}
+    for blk in e['blocks']:
+        b, x = blk['b'], saved['x%d' % blk['b']]
+        grads['stem' if b == first else 'x%d' % b] = DeviceTensor.empty(tuple(x.shape), ld=x.ld)
+        rot = {k: view(t) for k, t in blk['rot'].items()}
+        if intermediates:
+            u1, u2 = blk['units']
+            names = {'dzr': 'z/' + blk['proj']['name'], 'dxs': 'dxs/block%d' % b, 'dy2': 'dy2/block%d' % b, 'd2': 'd2/block%d' % b,
+                     'd1': 'd1/block%d' % b, 'dt2': 'dw/' + u2['name'], 'dt1': 'dw/' + u1['name'], 'dz': 'z/' + u2['name'],
+                     'dz1': 'z/' + u1['name']}
+            rot['dz1'] = rot['dz']
+            for k, key in names.items():
+                grads[key] = rot[k] = DeviceTensor.empty(tuple(rot[k].shape), ld=rot[k].ld)
+        else:
+            rot['dz1'] = rot['dz']
+        inner[b] = rot
+    dev, g = {}, d_entry
+    for blk in reversed(e['blocks']):
+        b, p, rot = blk['b'], blk['proj'], inner[blk['b']]
+        u1, u2 = blk['units']
+        x, y1, y2 = saved['x%d' % b], saved['block%d/y1' % b], saved['block%d/y2' % b]
+        dzr, dgamma, dbeta = ops.batch_norm_backward_device(saved[p['name'] + '/z'], None, g, p['bn']['gamma'], p['bn']['save_mean'],
+                                                            p['bn']['save_invstd'], True, stream=d.stream, dx=rot['dzr'],
+                                                            workspace=e['ws_bn'])
+        dxs, dk, _ = ops.conv_backward_device(saved['block%d/xs' % b], p['K'], dzr, None, stream=d.stream, dx=rot['dxs'],
+                                              workspace=e['ws_conv'])
+        c = p['K'].shape[3]
+        dev[p['name'] + '/kernel'] = (dk, p['K'].shape)
+        dev[p['bn_name'] + '/gamma'], dev[p['bn_name'] + '/beta'] = (dgamma, (c,)), (dbeta, (c,))
+        dy2 = ops.max_pool_backward_device(y2, g, dx=rot['dy2'], stream=d.stream)
+        ws = {'ws_bn': e['ws_bn'], 'ws_conv': e['ws_conv']}
+        d2, _, _ = _unit_backward(d, u2, y1, None, dy2, saved[u2['name'] + '/z'], saved[u2['name'] + '/dw'], dev, e['ws_dw'],
+                                  dict(ws, dz=rot['dz'], dt=rot['dt2'], dx=rot['d2']))
+        d1, _, _ = _unit_backward(d, u1, x, None, d2, saved[u1['name'] + '/z'], saved[u1['name'] + '/dw'], dev, e['ws_dw'],
+                                  dict(ws, dz=rot['dz1'], dt=rot['dt1'], dx=rot['d1']))
+        g = ops.add_upsample2_device(d1, dxs, out=grads['stem' if b == first else 'x%d' % b], stream=d.stream)
+    _sync(d)
+    for t in [t for rot in inner.values() for t in rot.values()] + list(grads.values()):   # the stream has run every call: nothing
+        t._keep = None                                                                      # needs keeping alive any longer
+    for k, (buf, shp) in dev.items():
+        grads[k] = to_host(buf.ptr, shp)
+    return grads
+
+
 # ---- the middle flow's host statements: NumPy, any channel count (the weights decide), float64 as the yardstick ----------
 
 def _host_depthwise_forward(x, k, relu_in, dtype):
@@ -1233,4 +1473,90 @@ def host_middle_flow_backward(saved, weights, d_mid, dtype=np.float64, blocks=MI
             out['dw/' + u], out['z/' + u], out['d%d/block%d' % (i, b)] = dt, dz, dy
         g = dy + g
         out['entry' if b == blocks[0] else 'x%d' % b] = g
+    return out
+
+
+# ---- the entry flow's host statements: NumPy, any channel counts and map sizes (the weights and the input decide) ---------
+
+def _host_max_pool_forward(x, dtype):
+    """max_pooling2d(3, 2, 'same') of x [N,H,W,C]: padded positions are absent"""
+    from .ops import _same_pad_front
+    x = np.asarray(x, dtype)
+    N, H, W, C = x.shape
+    (Ho, pt), (Wo, pl) = _same_pad_front(H), _same_pad_front(W)
+    xp = np.full((N, 2 * Ho + 1, 2 * Wo + 1, C), -np.inf, dtype)
+    xp[:, pt:pt + H, pl:pl + W] = x
+    out = np.full((N, Ho, Wo, C), -np.inf, dtype)
+    for a in range(3):
+        for b in range(3):
+            out = np.maximum(out, xp[:, a:a + 2 * Ho:2, b:b + 2 * Wo:2])
+    return out
+
+
+def host_entry_flow_train(stem_out, weights, dtype=np.float64, blocks=ENTRY_FLOW_BLOCKS):
+    """The NumPy statement of entry_flow_train: stem_out [N,h,w,C] (the first block's input) and the blocks' variables and
+    moving statistics under the checkpoint's names (the channel counts come from the weights) -> (entry_x, saved): the output
+    of the last block and a dict with detector.entry_flow_saved()'s keys for `blocks` -- 'x<b>', 'block<b>/xs',
+    'conv2d_<b-1>/z', 'block<b>/r', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per batch norm '/save_mean',
+    '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's update as
+    ops.host_batch_norm_forward states it)."""
+    from . import ops
+    x, saved = np.asarray(stem_out, dtype), {}
+
+    def bn_forward(z, bn):
+        y, mean, invstd, mm, mv = ops.host_batch_norm_forward(z, weights[bn + 'gamma'], weights[bn + 'beta'], ENTRY_FLOW_EPS, True,
+                                                              ENTRY_FLOW_MOMENTUM, weights[bn + 'moving_mean'],
+                                                              weights[bn + 'moving_variance'], False, dtype)
+        saved.update({bn + 'save_mean': mean, bn + 'save_invstd': invstd, bn + 'moving_mean': mm, bn + 'moving_variance': mv})
+        return y
+    for b in blocks:
+        saved['x%d' % b] = x
+        proj = 'conv2d_%d' % (b - 1)
+        xs = ops.host_subsample2(x, dtype)
+        zr = np.matmul(xs, np.asarray(weights[proj + '/kernel'], dtype)[0, 0])
+        r = bn_forward(zr, 'batch_normalization_%d/' % (b - 1))
+        saved['block%d/xs' % b], saved[proj + '/z'], saved['block%d/r' % b] = xs, zr, r
+        y = x
+        for i in (1, 2):
+            u = 'block%d_sepconv%d' % (b, i)
+            t = _host_depthwise_forward(y, weights[u + '/depthwise_kernel'], _entry_relu_in(b, i), dtype)
+            z = np.matmul(t, np.asarray(weights[u + '/pointwise_kernel'], dtype)[0, 0])
+            y = bn_forward(z, u + '_bn/')
+            saved[u + '/dw'], saved[u + '/z'], saved['block%d/y%d' % (b, i)] = t, z, y
+        x = _host_max_pool_forward(y, dtype) + r
+    saved['x%d' % (blocks[-1] + 1)] = x
+    return x, saved
+
+
+def host_entry_flow_backward(saved, weights, d_entry, dtype=np.float64, blocks=ENTRY_FLOW_BLOCKS):
+    """The NumPy statement of entry_flow_backward(d_entry, intermediates=True): saved = what host_entry_flow_train (or
+    detector.entry_flow_saved(), as NumPy arrays) left, d_entry = d loss / d (the last block's output) -> a dict with the eleven
+    gradients of every block of `blocks` under the checkpoint's names and in its shapes, 'stem' = d loss / d (the first block's
+    input), 'x<b>' for every later block, and 'dxs/block<b>', 'z/conv2d_<b-1>', 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>',
+    'dw/<unit>', 'z/<unit>'.  Composed of ops.host_batch_norm_backward, ops.host_conv_backward, ops.host_depthwise_backward,
+    ops.host_max_pool_backward and ops.host_add_upsample2."""
+    from . import ops
+    blocks = tuple(blocks)
+    vec = lambda a: np.asarray(a, dtype).reshape(-1)
+    g, out = np.asarray(d_entry, dtype), {}
+    for b in reversed(blocks):
+        proj, bn = 'conv2d_%d' % (b - 1), 'batch_normalization_%d/' % (b - 1)
+        dzr, dgamma, dbeta = ops.host_batch_norm_backward(saved[proj + '/z'], None, g, weights[bn + 'gamma'], vec(saved[bn + 'save_mean']),
+                                                          vec(saved[bn + 'save_invstd']), True, dtype)
+        dxs, dk, _ = ops.host_conv_backward(saved['block%d/xs' % b], weights[proj + '/kernel'], dzr, None, False, dtype)
+        out[proj + '/kernel'], out[bn + 'gamma'], out[bn + 'beta'] = dk, dgamma, dbeta
+        out['z/' + proj], out['dxs/block%d' % b] = dzr, dxs
+        dy = ops.host_max_pool_backward(saved['block%d/y2' % b], g, dtype)
+        out['dy2/block%d' % b] = dy
+        for i, xin in ((2, saved['block%d/y1' % b]), (1, saved['x%d' % b])):
+            u = 'block%d_sepconv%d' % (b, i)
+            ubn = u + '_bn/'
+            dz, dgamma, dbeta = ops.host_batch_norm_backward(saved[u + '/z'], None, dy, weights[ubn + 'gamma'], vec(saved[ubn + 'save_mean']),
+                                                             vec(saved[ubn + 'save_invstd']), True, dtype)
+            dt, dkp, _ = ops.host_conv_backward(saved[u + '/dw'], weights[u + '/pointwise_kernel'], dz, None, False, dtype)
+            dy, dkd = ops.host_depthwise_backward(xin, weights[u + '/depthwise_kernel'], dt, 1, _entry_relu_in(b, i), dtype)
+            out[u + '/depthwise_kernel'], out[u + '/pointwise_kernel'], out[ubn + 'gamma'], out[ubn + 'beta'] = dkd, dkp, dgamma, dbeta
+            out['dw/' + u], out['z/' + u], out['d%d/block%d' % (i, b)] = dt, dz, dy
+        g = ops.host_add_upsample2(dy, dxs, dtype)
+        out['stem' if b == blocks[0] else 'x%d' % b] = g
     return out

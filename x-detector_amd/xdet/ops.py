@@ -1282,3 +1282,132 @@ def add_rows_device(a, b, out=None, stream=None):
     # operands live until the stream has run the call (on top of what out already keeps alive)
     out._keep = (getattr(out, '_keep', None),) + tuple(t for t in (ta, tb) if t is not out)
     return out
+
+
+# ---- the backward of max_pooling2d(3, 2, 'same') and the stride-2 gather / scatter of a 1x1 / stride-2 projection
+#      (xdet_maxpool3x3s2_backward / xdet_subsample2 / xdet_add_upsample2, csrc/pool_backward.hip) --------------------------
+
+def _same_pad_front(n):
+    """TensorFlow's 'SAME' for a 3-wide window at stride 2: (outputs, padding in front): the smaller half of the total"""
+    o = -(-n // 2)
+    return o, max((o - 1) * 2 + 3 - n, 0) // 2
+
+
+def host_max_pool_backward(x, dy, dtype=np.float32):
+    """The NumPy statement of xdet_maxpool3x3s2_backward (include/xdet.h): x [N,H,W,C], the input of
+    max_pooling2d(3, 2, 'same'), dy [N,ceil(H/2),ceil(W/2),C] -> dx [N,H,W,C].  Every window sends its dy to its first maximum
+    in row-major window order (strict > against the running best, which starts at the window's first in-image element; padded
+    positions are absent), and the shares a pixel receives are added to 0 in ascending (oh, ow) order, each add rounded.
+    dtype float32: the op's dx bit for bit; float64: the yardstick."""
+    x, dy = np.asarray(x, dtype), np.asarray(dy, dtype)
+    N, H, W, C = x.shape
+    (Ho, pt), (Wo, pl) = _same_pad_front(H), _same_pad_front(W)
+    if dy.shape != (N, Ho, Wo, C):
+        raise InvalidArgumentError(-1, 'max_pool_backward: x %r needs dy %r, got %r' % (x.shape, (N, Ho, Wo, C), dy.shape))
+    best = np.zeros((N, Ho, Wo, C), dtype)
+    bh, bw = np.zeros((N, Ho, Wo, C), np.intp), np.zeros((N, Ho, Wo, C), np.intp)
+    has = np.zeros((1, Ho, Wo, 1), bool)
+    for a in range(3):
+        r = 2 * np.arange(Ho) - pt + a
+        rv, rc = (r >= 0) & (r < H), np.clip(r, 0, H - 1)
+        for b in range(3):
+            c = 2 * np.arange(Wo) - pl + b
+            cv, cc = (c >= 0) & (c < W), np.clip(c, 0, W - 1)
+            live = (rv[:, None] & cv[None, :])[None, :, :, None]
+            v = x[:, rc][:, :, cc]
+            with np.errstate(invalid='ignore'):
+                take = live & (~has | (v > best))
+            best = np.where(take, v, best)
+            bh = np.where(take, rc[None, :, None, None], bh)
+            bw = np.where(take, cc[None, None, :, None], bw)
+            has = has | live
+    dx = np.zeros(x.shape, dtype)
+    n, c = np.arange(N)[:, None, None, None], np.arange(C)[None, None, None, :]
+    # unbuffered and in the index arrays' order: for one (n, pixel, c) the windows arrive ascending in (oh, ow)
+    np.add.at(dx, tuple(np.broadcast_arrays(n, bh, bw, c)), dy)
+    return dx
+
+
+def host_subsample2(x, dtype=np.float32):
+    """x[:, ::2, ::2]: what a 1x1 / stride-2 'SAME' conv reads of x [N,H,W,C] -> [N,ceil(H/2),ceil(W/2),C]"""
+    return np.ascontiguousarray(np.asarray(x, dtype)[:, ::2, ::2])
+
+
+def host_add_upsample2(a, b, dtype=np.float32):
+    """a [N,H,W,C] + the adjoint of host_subsample2 applied to b [N,ceil(H/2),ceil(W/2),C]: b added at the pixels whose h and
+    w are both even, a unchanged (its bits) everywhere else"""
+    out = np.array(a, dtype)
+    b = np.asarray(b, dtype)
+    if out.ndim != 4 or b.shape != out[:, ::2, ::2].shape:
+        raise InvalidArgumentError(-1, 'add_upsample2: a %r needs b %r, got %r' % (out.shape, out[:, ::2, ::2].shape, b.shape))
+    out[:, ::2, ::2] += b
+    return out
+
+
+def _pool_sizes(who, N, H, W, C):
+    if min(N, H, W, C) <= 0 or C > 4096 or N * H * W * C >= 2 ** 31:
+        raise InvalidArgumentError(-1, '%s: [%d,%d,%d,%d] (sizes positive, C at most 4096, N*H*W*C below 2^31)' % (who, N, H, W, C))
+
+
+def _pool_dev(a):
+    return a if isinstance(a, DeviceTensor) else DeviceTensor.from_numpy(a)
+
+
+def max_pool_backward_device(x, dy, dx=None, stream=None):
+    """max_pool_backward with the result left on the GPU: dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x); nothing is
+    synchronised.  x, dy: NumPy arrays or DeviceTensors read in place with their ld.  dx: a DeviceTensor [N,H,W,C] to write
+    instead of a new one (with its ld; it must not overlap x or dy)."""
+    (N, H, W, C), x_in = _nhwc(x, 'x')
+    sd, dy_in = _nhwc(dy, 'dy')
+    if tuple(sd) != (N, -(-H // 2), -(-W // 2), C):
+        raise InvalidArgumentError(-1, 'max_pool_backward: x [N,H,W,C] and dy [N,ceil(H/2),ceil(W/2),C] expected, got %r'
+                                   % ([(N, H, W, C), tuple(sd)],))
+    _pool_sizes('max_pool_backward', N, H, W, C)
+    tx, td = _pool_dev(x_in), _pool_dev(dy_in)
+    d_dx = _own_dx(dx, (N, H, W, C), 'max_pool_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=tx.ld)
+    check(lib().xdet_maxpool3x3s2_backward(tx.ptr, tx.ld, td.ptr, td.ld, N, H, W, C, d_dx.ptr, d_dx.ld,
+                                           stream.handle if stream else None))
+    d_dx._keep = (tx, td)                      # operands live until the stream has run the call
+    return d_dx
+
+
+def max_pool_backward(x, dy, stream=None):
+    """host_max_pool_backward on the GPU (xdet_maxpool3x3s2_backward) -> dx [N,H,W,C] as a NumPy array"""
+    d_dx = max_pool_backward_device(x, dy, stream=stream)
+    synchronize(stream)
+    return d_dx.numpy(stream=stream)
+
+
+def subsample2_device(x, out=None, stream=None):
+    """host_subsample2 on the GPU (xdet_subsample2): x [N,H,W,C] as a NumPy array or a DeviceTensor read with its ld -> out
+    DeviceTensor [N,ceil(H/2),ceil(W/2),C] (a caller's, written with its ld, or a new dense one); nothing is synchronised."""
+    (N, H, W, C), x_in = _nhwc(x, 'x')
+    so = (N, -(-H // 2), -(-W // 2), C)
+    if out is not None and (not isinstance(out, DeviceTensor) or tuple(out.shape) != so):
+        raise InvalidArgumentError(-1, 'subsample2: out must be a DeviceTensor of shape %r, got %r' % (so, getattr(out, 'shape', None)))
+    _pool_sizes('subsample2', N, H, W, C)
+    tx = _pool_dev(x_in)
+    if out is None:
+        out = DeviceTensor.empty(so)
+    check(lib().xdet_subsample2(tx.ptr, tx.ld, N, H, W, C, out.ptr, out.ld, stream.handle if stream else None))
+    out._keep = (tx,)
+    return out
+
+
+def add_upsample2_device(a, b, out=None, stream=None):
+    """host_add_upsample2 on the GPU (xdet_add_upsample2): a [N,H,W,C], b [N,ceil(H/2),ceil(W/2),C], each read with its own ld
+    (NumPy arrays are copied to the device first); out: a DeviceTensor of a's shape -- it may be a itself -- or None: a new
+    one with a's ld.  -> out; nothing is synchronised."""
+    (N, H, W, C), a_in = _nhwc(a, 'a')
+    sb, b_in = _nhwc(b, 'b')
+    if tuple(sb) != (N, -(-H // 2), -(-W // 2), C) or (out is not None and (not isinstance(out, DeviceTensor)
+                                                                             or tuple(out.shape) != (N, H, W, C))):
+        raise InvalidArgumentError(-1, 'add_upsample2: a [N,H,W,C], b [N,ceil(H/2),ceil(W/2),C] and out like a expected, got %r'
+                                   % ([(N, H, W, C), tuple(sb), getattr(out, 'shape', None)],))
+    _pool_sizes('add_upsample2', N, H, W, C)
+    ta, tb = _pool_dev(a_in), _pool_dev(b_in)
+    if out is None:
+        out = DeviceTensor.empty((N, H, W, C), ld=ta.ld)
+    check(lib().xdet_add_upsample2(ta.ptr, ta.ld, tb.ptr, tb.ld, N, H, W, C, out.ptr, out.ld, stream.handle if stream else None))
+    out._keep = (getattr(out, '_keep', None),) + tuple(t for t in (ta, tb) if t is not out)
+    return out
