@@ -26,6 +26,11 @@
 
 namespace xdet {
 
+#if CD_PROBE_LEVEL == 1
+unsigned long long* g_conv_dma_probe = nullptr;   // [virtual blocks][5][2]; set by the probe program
+int g_conv_dma_probe_no_walk = 0;                 // 1: the one-tile-per-workgroup launch whatever the grid
+#endif
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef int x8frag __attribute__((ext_vector_type(8)));     // 32 fp8 of one row: a lane's operand of the 32x32x64 block-scaled MFMA
@@ -35,6 +40,43 @@ typedef unsigned short u16;
 #define XDET_GLDS16(gptr, lptr)                                                                        \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),              \
                                    (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
+
+// Timeline probe for tools/ubench/conv_walk_probe.hip ONLY (the product is compiled with level 0: no stamps, no extra
+// argument).  Level 1: lane 0 of wave 0 writes s_memrealtime (100 MHz) and s_memtime (shader clocks) per tile it computes,
+// [virtual block][slot][2]; slots: 0 = tile entry, 1 = stage 0 landed (the first MFMA can issue), 2 = K loop done,
+// 3 = last epilogue store issued, 4 = stores acknowledged (the tile's exit).
+#ifndef CD_PROBE_LEVEL
+#define CD_PROBE_LEVEL 0
+#endif
+#if CD_PROBE_LEVEL == 1
+#define CD_PROBE_PARAM , unsigned long long* dbg
+#define CD_PROBE_ARG , g_conv_dma_probe
+#define CD_STAMP(vblk, slot)                                                      \
+  do {                                                                            \
+    if (dbg && threadIdx.x == 0) {                                                \
+      dbg[((size_t)(vblk) * 5 + (slot)) * 2] = __builtin_amdgcn_s_memrealtime();  \
+      dbg[((size_t)(vblk) * 5 + (slot)) * 2 + 1] = __builtin_amdgcn_s_memtime();  \
+    }                                                                             \
+  } while (0)
+#define CD_STAMP_DRAINED(vblk, slot)                        \
+  do {                                                      \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        \
+    CD_STAMP(vblk, slot);                                   \
+  } while (0)
+#else
+#define CD_PROBE_PARAM
+#define CD_PROBE_ARG
+#define CD_STAMP(vblk, slot) do {} while (0)
+#define CD_STAMP_DRAINED(vblk, slot) do {} while (0)
+#endif
+
+// Dynamic LDS of conv_dma_f16_kernel: two operand stages; with the tile walk the epilogue's staging (a [32][WN + 4] f32
+// slab per wave, conv_epilogue.h) lies behind stage 0 instead of on top of it.
+constexpr int conv_dma_lds_bytes(int bm, int bn, int waves_m, int waves_n, bool walk) {
+  const int stage = (2 * bm + 2 * bn) * 32 * 2;
+  const int staging = waves_m * waves_n * 32 * (bn / waves_n + 4) * 4;
+  return walk && stage + staging > 2 * stage ? stage + staging : 2 * stage;
+}
 
 // PW (pointwise: 1x1, stride 1, no padding -- 30 of the detector's 46 contractions, all of the dominant ones): the DMA
 // sources are raw BUFFER loads whose per-lane offsets never change along K -- a 16-pixel x 32-channel block of the planes
@@ -61,12 +103,19 @@ typedef unsigned short u16;
 // the weights' K block ride in the scalar offset, and (cc, ky, kx) advance incrementally instead of by division: ~22 VALU
 // + ~25 SALU per K step next to the 48 MFMAs where the pointer form spends ~55 + ~70.  Same bytes into the same LDS
 // places: bit-identical.
+// WALK (round 7; the buffer forms of the 256 x 256 tile, grids of more than one round): one workgroup per compute unit walks
+// its tiles instead of one workgroup per tile -- start-up and argument set-up once per workgroup, and the next tile's first
+// operand stage requested in the last K step of the current tile, to land under its epilogue (whose staging then lies behind
+// stage 0, not on it).  Tiles are assigned statically (vb = blockIdx.x + i * gridDim.x): no atomics, no workgroup waits for
+// another.  Same K order, product order and epilogue per tile: bit-identical (tests/test_gpu_pointwise_walk.py); timeline and
+// A/B: profiles/r07_tile_walk_timeline.txt, profiles/NOTES_r07.md.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSPLIT, int NSTAGE, bool PW = false, bool FOLD = false, bool X8 = false,
-          bool GBUF = false>
-__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(ConvParams p_in) {
+          bool GBUF = false, bool WALK = false>
+__global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(ConvParams p_in, int nvb CD_PROBE_PARAM) {
   static_assert(NSTAGE == 2, "two LDS stages");
   static_assert(!(GBUF && PW), "GBUF is the buffer form of the NON-pointwise layers");
   static_assert(!X8 || (PW && NSPLIT == 3 && !FOLD), "x8: pointwise f16x3 layers only");
+  static_assert(!WALK || ((PW || GBUF) && !FOLD), "the tile walk: the buffer forms (their weights are aimed per tile through a resource)");
   constexpr int NW = WAVES_M * WAVES_N;          // waves per workgroup (4 or 8)
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -75,6 +124,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   static_assert(A_IT >= 1 && B_IT >= 1, "tile too small for the wave count");
   constexpr int ROWB = 32;                       // halves per LDS row (64 B)
   constexpr int STAGE = (2 * BM + 2 * BN) * ROWB;   // halves per stage
+  // WALK: the epilogue's staging starts at stage 1, so that stage 0 can take the next tile's first operands meanwhile
+  constexpr int EP_OFF = WALK ? STAGE : 0;       // halves
+  constexpr int EP_BYTES = conv_dma_lds_bytes(BM, BN, WAVES_M, WAVES_N, WALK) - EP_OFF * 2;
+  static_assert(conv_dma_lds_bytes(BM, BN, WAVES_M, WAVES_N, WALK) <= 160 * 1024, "stages + epilogue staging must fit a CU's LDS");
 
   extern __shared__ __attribute__((aligned(16))) u16 smem16[];
 
@@ -85,64 +138,57 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (private L2s): give every
   // XCD whole M-tiles, all N-tiles of one M-tile back to back, so an activation tile is pulled over
   // the fabric once and then re-read from that XCD's L2 (the weights are small and shared by all).
+  // WALK: a workgroup takes the virtual block indices vb = blockIdx.x + i * gridDim.x, i = 0, 1, ... below nvb, one after the
+  // other.  gridDim.x is a multiple of 8, so vb & 7 -- the XCD a tile's operands are cached on -- is the workgroup's own, and
+  // the tiles of one round are the ones a one-tile-per-workgroup grid would have running together.  The assignment is
+  // static: no workgroup waits for another.
   const int nby = p_in.Cout_pad / BN;
-  const int slot = blockIdx.x >> 3;
-  int bx, n0;
   ConvParams p = p_in;
-  if (p_in.group_rows) {
-    // Grouped GEMM (frequency bins): every group has its own weight matrix, so ALL tiles of a group go to
-    // ONE XCD -- its L2 then holds that group's weights and activations once, instead of eight L2s each
-    // pulling every group's weights over the fabric.  Workgroups are dealt round-robin to the XCDs:
-    // blockIdx & 7 is the XCD, group = 8 * round + XCD, tiles of the group in slot order (N fastest).
-    const int mt = p_in.group_rows / BM;           // M tiles per group
-    const int tpg = mt * nby;
-    const int g = (slot / tpg) * 8 + (blockIdx.x & 7);
-    const int w = slot - (slot / tpg) * tpg;
-    if ((int64_t)g * p_in.group_rows >= p_in.M) return;
-    if (p_in.group_live_rows && (w / nby) * BM >= p_in.group_live_rows) return;     // a tile of padding rows only
-    bx = g * mt + w / nby;
-    n0 = (w % nby) * BN;
-    p.wt_hi = p_in.wt_hi + (size_t)g * p_in.group_wt_stride;
-    p.wt_lo = p_in.wt_lo ? p_in.wt_lo + (size_t)g * p_in.group_wt_stride : nullptr;
-    p.scale = p_in.scale + (size_t)g * p_in.Cout_pad;
-    p.shift = p_in.shift + (size_t)g * p_in.Cout_pad;
+  // tile of virtual block vb: first row, first column, group; false = nothing to compute there
+  auto tile_of = [&](int vb, int& tm0, int& tn0, int& tg) -> bool {
+    const int slot = vb >> 3;
+    if (p_in.group_rows) {
+      // Grouped GEMM (frequency bins): every group has its own weight matrix, so ALL tiles of a group go to
+      // ONE XCD -- its L2 then holds that group's weights and activations once, instead of eight L2s each
+      // pulling every group's weights over the fabric.  Workgroups are dealt round-robin to the XCDs:
+      // vb & 7 is the XCD, group = 8 * round + XCD, tiles of the group in slot order (N fastest).
+      const int mt = p_in.group_rows / BM;           // M tiles per group
+      const int tpg = mt * nby;
+      const int g = (slot / tpg) * 8 + (vb & 7);
+      const int w = slot - (slot / tpg) * tpg;
+      if ((int64_t)g * p_in.group_rows >= p_in.M) return false;
+      if (p_in.group_live_rows && (w / nby) * BM >= p_in.group_live_rows) return false;     // a tile of padding rows only
+      tm0 = (g * mt + w / nby) * BM;
+      tn0 = (w % nby) * BN;
+      tg = g;
+    } else {
+      const int bx = (slot / nby) * 8 + (vb & 7);
+      if (bx * BM >= p_in.M) return false;
+      tm0 = bx * BM;
+      tn0 = (slot % nby) * BN;
+      tg = 0;
+    }
+    return true;
+  };
+  int vb = blockIdx.x;                             // WALK: the virtual block the DMA descriptors are aimed at
+  int m0, n0, grp;
+  if constexpr (WALK) {
+    while (vb < nvb && !tile_of(vb, m0, n0, grp)) vb += gridDim.x;
+    if (vb >= nvb) return;
   } else {
-    bx = (slot / nby) * 8 + (blockIdx.x & 7);
-    if (bx * BM >= p_in.M) return;
-    n0 = (slot % nby) * BN;
+    if (!tile_of(vb, m0, n0, grp)) return;
   }
-  const int m0 = bx * BM;
+  if (!WALK && p_in.group_rows) {
+    p.wt_hi = p_in.wt_hi + (size_t)grp * p_in.group_wt_stride;
+    p.wt_lo = p_in.wt_lo ? p_in.wt_lo + (size_t)grp * p_in.group_wt_stride : nullptr;
+    p.scale = p_in.scale + (size_t)grp * p_in.Cout_pad;
+    p.shift = p_in.shift + (size_t)grp * p_in.Cout_pad;
+  }
+  CD_STAMP(vb, 0);
 
   // ---- per-lane DMA descriptors ----
-  const int lr = lane >> 2;                      // row within a 16-row DMA slab
-  const int pos = lane & 3;                      // 16-B slot within the 64-B LDS row
   int iy0[A_IT], ix0[A_IT], pbase[A_IT], achunk[A_IT];
-#pragma unroll
-  for (int q = 0; q < A_IT; ++q) {
-    const int rt = (wave * A_IT + q) * 16 + lr;  // tile row
-    achunk[q] = (pos ^ ((rt >> 2) & 3)) * 8;     // which 8-half chunk of the row this lane fetches
-    const int m = m0 + rt;
-    if (m < p.M) {
-      const int hw = p.Ho * p.Wo;
-      const int n = m / hw;
-      const int rem = m - n * hw;
-      const int oy = rem / p.Wo;
-      const int ox = rem - oy * p.Wo;
-      iy0[q] = oy * p.stride - p.pad_t;
-      ix0[q] = ox * p.stride - p.pad_l;
-      pbase[q] = n * p.H * p.W;
-    } else {
-      iy0[q] = -(1 << 20);
-      ix0[q] = 0;
-      pbase[q] = 0;
-    }
-  }
   size_t boff[B_IT];
-#pragma unroll
-  for (int q = 0; q < B_IT; ++q) {
-    const int rt = (wave * B_IT + q) * 16 + lr;
-    boff[q] = (size_t)(n0 + rt) * 32 + (pos ^ ((rt >> 2) & 3)) * 8;   // K-blocked weights [Kp/32][Cout_pad][32]
-  }
   const int nk = p.Kp / 32;
   const int ntaps = p.KH * p.KW;
   const unsigned c32n = (unsigned)(p.ldi >> 5);   // channel blocks per 16-pixel group of a split plane
@@ -152,32 +198,60 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   __amdgpu_buffer_rsrc_t r_ah, r_al, r_bh, r_bl;
   unsigned a_vo[A_IT], b_vo[B_IT];
   int g_cc = 0, g_ky = 0, g_kx = 0, g_tap = 0;   // GBUF: (channel block, tap) of the NEXT issue() -- calls come with kt = 0, 1, 2, ...
-  if (GBUF) {
-    const unsigned a_bytes = (unsigned)(((size_t)(((size_t)p.N * p.H * p.W + 15) >> 4) * c32n) << 10);
-    const unsigned b_bytes = (unsigned)((size_t)nk * p.Cout_pad * 64);
+  if (PW || GBUF) {
+    const unsigned a_bytes = GBUF ? (unsigned)(((size_t)(((size_t)p.N * p.H * p.W + 15) >> 4) * c32n) << 10)
+                                  : (unsigned)(((size_t)((p.M + 15) >> 4) * c32n) << 10);
     r_ah = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.in_hi), 0, (int)a_bytes, 0x00020000);
     r_al = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(NSPLIT > 1 ? p.in_lo : p.in_hi), 0, (int)a_bytes, 0x00020000);
-    r_bh = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.wt_hi), 0, (int)b_bytes, 0x00020000);
-    r_bl = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(NSPLIT > 1 ? p.wt_lo : p.wt_hi), 0, (int)b_bytes, 0x00020000);
-#pragma unroll
-    for (int q = 0; q < B_IT; ++q) b_vo[q] = (unsigned)(boff[q] * 2);
   }
-  if (PW) {
-    const unsigned a_bytes = (unsigned)(((size_t)((p.M + 15) >> 4) * c32n) << 10);
-    const unsigned b_bytes = (unsigned)((size_t)nk * p.Cout_pad * 64);
-    r_ah = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.in_hi), 0, (int)a_bytes, 0x00020000);
-    r_al = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(NSPLIT > 1 ? p.in_lo : p.in_hi), 0, (int)a_bytes, 0x00020000);
-    r_bh = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.wt_hi), 0, (int)b_bytes, 0x00020000);
-    r_bl = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(NSPLIT > 1 ? p.wt_lo : p.wt_hi), 0, (int)b_bytes, 0x00020000);
+  // aim the descriptors at the tile (tm0, tn0) of group tg.  WALK: called again for every further tile, after the last
+  // issue() of the tile before it -- one set of descriptors, never two.
+  auto aim = [&](int ln, int tm0, int tn0, int tg) {
+    const int lr = ln >> 2;                        // row within a 16-row DMA slab
+    const int pos = ln & 3;                        // 16-B slot within the 64-B LDS row
 #pragma unroll
     for (int q = 0; q < A_IT; ++q) {
-      const int rt = (wave * A_IT + q) * 16 + lr;
-      const int m = m0 + rt;                       // input pixel == output pixel
-      a_vo[q] = m < p.M ? (((unsigned)(m >> 4) * c32n) << 10) + (unsigned)((((m & 15) << 5) + achunk[q]) * 2) : 0xffffffffu;
+      const int rt = (wave * A_IT + q) * 16 + lr;  // tile row
+      achunk[q] = (pos ^ ((rt >> 2) & 3)) * 8;     // which 8-half chunk of the row this lane fetches
+      const int m = tm0 + rt;
+      if (!PW) {
+        if (m < p.M) {
+          int hw = p.Ho * p.Wo, wo = p.Wo;
+          // (WALK: the divisors' reciprocals are worked out here, per call, not once in front of the walk and kept in
+          // vector registers across every tile)
+          if (WALK) asm volatile("" : "+s"(hw), "+s"(wo));
+          const int n = m / hw;
+          const int rem = m - n * hw;
+          const int oy = rem / wo;
+          const int ox = rem - oy * wo;
+          iy0[q] = oy * p.stride - p.pad_t;
+          ix0[q] = ox * p.stride - p.pad_l;
+          pbase[q] = n * p.H * p.W;
+        } else {
+          iy0[q] = -(1 << 20);
+          ix0[q] = 0;
+          pbase[q] = 0;
+        }
+      } else {                                     // input pixel == output pixel
+        a_vo[q] = m < p.M ? (((unsigned)(m >> 4) * c32n) << 10) + (unsigned)((((m & 15) << 5) + achunk[q]) * 2) : 0xffffffffu;
+      }
     }
 #pragma unroll
-    for (int q = 0; q < B_IT; ++q) b_vo[q] = (unsigned)(boff[q] * 2);
-  }
+    for (int q = 0; q < B_IT; ++q) {
+      const int rt = (wave * B_IT + q) * 16 + lr;
+      boff[q] = (size_t)(tn0 + rt) * 32 + (pos ^ ((rt >> 2) & 3)) * 8;   // K-blocked weights [Kp/32][Cout_pad][32]
+      if (PW || GBUF) b_vo[q] = (unsigned)(boff[q] * 2);
+    }
+    if (PW || GBUF) {
+      // (WALK: this tile's group; else p.wt_* are the workgroup's group already)
+      const size_t wo = WALK ? (size_t)tg * p_in.group_wt_stride : 0;
+      const unsigned b_bytes = (unsigned)((size_t)nk * p.Cout_pad * 64);
+      r_bh = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>(p.wt_hi + wo), 0, (int)b_bytes, 0x00020000);
+      r_bl = __builtin_amdgcn_make_buffer_rsrc(const_cast<u16*>((NSPLIT > 1 ? p.wt_lo : p.wt_hi) + wo), 0, (int)b_bytes, 0x00020000);
+    }
+    g_cc = g_ky = g_kx = g_tap = 0;
+  };
+  aim(lane, m0, n0, grp);
 
   auto issue = [&](int kt, int buf) {
     u16* Ah = smem16 + buf * STAGE;
@@ -266,15 +340,32 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int frow = lane & 31;
-  const int fh = lane >> 5;
+  // WALK: the tile after this one.  Called in the last K step of a tile, behind its barrier: every wave has read both
+  // stages for the last time and this tile's last issue() is long gone, so the descriptors are re-aimed and the next
+  // tile's stage 0 goes out to land under the rest of the step and the epilogue (whose staging starts at stage 1).
+  bool more = false;
+  int m0_nx = 0, n0_nx = 0, grp_nx = 0;
+  int lane_t = lane;
+  auto next_tile = [&]() {
+    vb += gridDim.x;
+    while (vb < nvb && !tile_of(vb, m0_nx, n0_nx, grp_nx)) vb += gridDim.x;
+    if (vb < nvb) {
+      more = true;
+      aim(lane_t, m0_nx, n0_nx, grp_nx);
+      issue(0, 0);
+    }
+  };
+  int vbc = vb;                                    // (probe builds: the virtual block being computed)
+  (void)vbc;
+  bool first_tile = true;
+  issue(0, 0);
+  do {
+  more = false;
+  // WALK: the lane id anew for every tile (two VALU instructions), and what derives from it with it: kept from the kernel's
+  // `lane` all of it would have to stay alive across every tile's epilogue, which has no register to spare (conv_epilogue.h)
+  if (WALK) lane_t = ep_lane();
+  const int frow = lane_t & 31;
+  const int fh = lane_t >> 5;
   // operand rows of this lane and their chunk permutation (tile-row bits 2..3)
   int aoff[TM], boffs[TN], asw[TM], bsw[TN];
 #pragma unroll
@@ -289,6 +380,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
     boffs[j] = rt * ROWB;
     bsw[j] = (rt >> 2) & 3;
   }
+
+  // (pointwise form: the descriptors again from the fresh lane id, ~20 VALU instructions, instead of four registers kept
+  // across the epilogue)
+  if (WALK && PW) aim(lane_t, m0, n0, grp);
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   // Main loop.  Fragments are double-buffered in registers and the single barrier of a K step sits
   // BETWEEN its two 16-deep halves, so the matrix pipe never waits for LDS across the barrier:
@@ -388,9 +489,12 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   f16x8 a0h[TM], a0l[X8 ? 1 : TM], b0h[TN], b0l[X8 ? 1 : TN];      // set A: half 0 of the current stage
   f16x8 a1h[TM], a1l[X8 ? 1 : TM], b1h[TN], b1l[X8 ? 1 : TN];      // set B: half 1
   x8frag a8[X8 ? TM : 1], b8[X8 ? TN : 1];                         // x8: the cross-term operands of the whole 32-deep step
-  issue(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();                               // stage 0 landed
+  // (stage 0 is in flight: issued in front of the walk -- or by next_tile() in the tile before this one, and waited for in
+  // front of that tile's epilogue)
+  if (!WALK || first_tile) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();                               // stage 0 landed (WALK: and every wave has read the last of its epilogue staging,
+                                                 // which stage 1 overlaps)
+  CD_STAMP(vbc, 1);
   if (nk > 1) issue(1, 1);
   load_frags(0, 0, a0h, a0l, b0h, b0l);
   // one K step; STEADY = both the DMA two stages ahead and the next stage's fragments exist, so the
@@ -427,6 +531,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
     // placed after issue() could not move up between the DMA pieces
     if (STEADY || kt + 1 < nk) load_frags(buf ^ 1, 0, a0h, a0l, b0h, b0l);
     if (STEADY || kt + 2 < nk) issue(kt + 2, buf);
+    else if (WALK && kt + 1 == nk) next_tile();
     if (!STEADY) __builtin_amdgcn_sched_barrier(0);
     mma(a1h, a1l, b1h, b1l);
     if constexpr (X8) mma_x8(a8, b8);
@@ -466,9 +571,42 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
         for (int j = 0; j < TN; ++j) acc[i][j] = tot[i][j] + acc[i][j];
     }
   }
+  CD_STAMP(vbc, 2);
   // (all rows below M -- every tile but a ragged last one: the form without per-row predicates, conv_epilogue.h)
-  if (m0 + BM <= p.M) conv_epilogue_full<WM, WN, TM, TN, NW, NSTAGE * STAGE * 2>(p, acc, smem16, wave, lane, wm, wn, m0, n0);
-  else conv_epilogue<WM, WN, TM, TN, NW, NSTAGE * STAGE * 2>(p, acc, smem16, wave, lane, wm, wn, m0, n0);
+  if constexpr (WALK) {
+    // The epilogue's two dozen pointers and strides are read from the kernel arguments again for every tile.  As values
+    // of `p` they are invariant in the walk, so the compiler loaded them once in front of it and kept them across every K
+    // loop -- more scalar registers than there are (the overflow lives in lanes of vector registers, which this kernel
+    // does not have either).
+    const __attribute__((address_space(4))) ConvParams* kp =
+        (const __attribute__((address_space(4))) ConvParams*)__builtin_amdgcn_kernarg_segment_ptr();   // p_in: the first argument
+    asm volatile("" : "+s"(kp));
+    ConvParams pe = {};                            // (field by field: scalar loads; a struct copy went through vector registers)
+    pe.out = kp->out; pe.out_hi = kp->out_hi; pe.out_lo = kp->out_lo; pe.res = kp->res;
+    pe.planes_relu = kp->planes_relu; pe.pl_c32 = kp->pl_c32; pe.pl_scale = kp->pl_scale; pe.pl_shift = kp->pl_shift;
+    pe.ldo = kp->ldo; pe.ldr = kp->ldr; pe.M = kp->M; pe.relu_out = kp->relu_out;
+    pe.scale = kp->scale + (size_t)grp * kp->Cout_pad;         // (one group: grp = 0)
+    pe.shift = kp->shift + (size_t)grp * kp->Cout_pad;
+    // the next tile's stage 0 (next_tile(), half a K step ago) has landed: waited for HERE, in front of the epilogue's own
+    // loads and stores, so that the barrier at the top of the next tile need not wait for those stores to be acknowledged
+    // (the compiler puts the same wait in front of the epilogue's first LDS access: it cannot tell the staging from the
+    // DMA's destination)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (m0 + BM <= pe.M) conv_epilogue_full<WM, WN, TM, TN, NW, EP_BYTES>(pe, acc, smem16 + EP_OFF, wave, lane, wm, wn, m0, n0);
+    else conv_epilogue<WM, WN, TM, TN, NW, EP_BYTES>(pe, acc, smem16 + EP_OFF, wave, lane, wm, wn, m0, n0);
+  } else {
+    if (m0 + BM <= p.M) conv_epilogue_full<WM, WN, TM, TN, NW, EP_BYTES>(p, acc, smem16 + EP_OFF, wave, lane, wm, wn, m0, n0);
+    else conv_epilogue<WM, WN, TM, TN, NW, EP_BYTES>(p, acc, smem16 + EP_OFF, wave, lane, wm, wn, m0, n0);
+  }
+  CD_STAMP(vbc, 3);
+  CD_STAMP_DRAINED(vbc, 4);
+  m0 = m0_nx;
+  n0 = n0_nx;
+  grp = grp_nx;
+  vbc = vb;
+  first_tile = false;
+  if (more) CD_STAMP(vbc, 0);
+  } while (WALK && more);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -763,6 +901,20 @@ static bool gbuf_eligible(const ConvParams& p) {
   return a_bytes < ((size_t)1 << 32) && b_bytes < ((size_t)1 << 32) && p.Kp == p.Cin_p * p.KH * p.KW;
 }
 
+// compute units of the current device (one lookup per device ordinal)
+static int device_cu_count(int* n_out) {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  XDET_HIP(hipGetDevice(&dev));
+  int n = cus[dev & 63].load(std::memory_order_acquire);
+  if (n <= 0) {
+    XDET_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    cus[dev & 63].store(n, std::memory_order_release);
+  }
+  *n_out = n;
+  return XDET_OK;
+}
+
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSPLIT, int NSTAGE = 2, bool PW = false, bool X8 = false, bool GBUF = false>
 static int launch_d(const ConvParams& p, hipStream_t s) {
   if (!PW && pw_eligible(p)) return launch_d<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, true>(p, s);
@@ -770,19 +922,39 @@ static int launch_d(const ConvParams& p, hipStream_t s) {
     if (p.x8) return launch_d<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, true, true>(p, s);
   }
   XDET_REQUIRE(X8 || !p.x8, "conv(dma): x8 planes need a pointwise f16x3 layer below 4 GiB");
-  constexpr size_t lds = (size_t)NSTAGE * (2 * BM + 2 * BN) * 32 * sizeof(u16);
+  constexpr size_t lds = conv_dma_lds_bytes(BM, BN, WAVES_M, WAVES_N, false);
   if constexpr (!PW && !X8 && !GBUF && BM == 256 && BN == 256) {
     if (gbuf_eligible(p)) return launch_d<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, false, false, true>(p, s);
+  }
+  int64_t nvb = cdiv(cdiv(p.M, BM), 8) * 8 * (p.Cout_pad / BN);      // virtual blocks: the tiles, M tiles rounded up to the 8 XCDs
+  if (p.group_rows) {
+    const int64_t groups = p.M / p.group_rows, tpg = (int64_t)(p.group_rows / BM) * (p.Cout_pad / BN);
+    nvb = cdiv(groups, 8) * 8 * tpg;
+  }
+  if constexpr (BM == 256 && BN == 256 && (PW || GBUF)) {
+    // More than one round of the one-workgroup-per-CU tiles: a workgroup per CU (a multiple of 8: the XCD of a virtual block
+    // is then the same for every tile of a workgroup) walks its tiles, see WALK in the kernel.
+    int cus = 0;
+    XDET_TRY(device_cu_count(&cus));
+    const int64_t wgs = cus / 8 * 8;
+    bool walk = wgs >= 8 && nvb > wgs;
+#if CD_PROBE_LEVEL == 1
+    if (g_conv_dma_probe_no_walk) walk = false;
+#endif
+    if (walk) {
+      constexpr size_t lds_w = conv_dma_lds_bytes(BM, BN, WAVES_M, WAVES_N, true);
+      auto kern_w = conv_dma_f16_kernel<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, PW, false, X8, GBUF, true>;
+      static DeviceOnce once_w;
+      XDET_TRY(ensure_dynamic_lds(once_w, reinterpret_cast<const void*>(kern_w), (int)lds_w));
+      hipLaunchKernelGGL(kern_w, dim3((unsigned)wgs), dim3(64 * WAVES_M * WAVES_N), lds_w, s, p, (int)nvb CD_PROBE_ARG);
+      XDET_LAUNCH_CHECK();
+      return XDET_OK;
+    }
   }
   auto kern = conv_dma_f16_kernel<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, PW, false, X8, GBUF>;
   static DeviceOnce once;
   XDET_TRY(ensure_dynamic_lds(once, reinterpret_cast<const void*>(kern), (int)lds));
-  dim3 grid((unsigned)(cdiv(cdiv(p.M, BM), 8) * 8 * (p.Cout_pad / BN)));
-  if (p.group_rows) {
-    const int64_t groups = p.M / p.group_rows, tpg = (int64_t)(p.group_rows / BM) * (p.Cout_pad / BN);
-    grid = dim3((unsigned)(cdiv(groups, 8) * 8 * tpg));
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(64 * WAVES_M * WAVES_N), lds, s, p);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nvb), dim3(64 * WAVES_M * WAVES_N), lds, s, p, (int)nvb CD_PROBE_ARG);
   XDET_LAUNCH_CHECK();
   return XDET_OK;
 }
@@ -797,7 +969,7 @@ int launch_conv_mfma_dma_fold(const ConvParams& p, hipStream_t s) {
   static DeviceOnce once;
   XDET_TRY(ensure_dynamic_lds(once, reinterpret_cast<const void*>(kern), (int)lds));
   dim3 grid((unsigned)(cdiv(cdiv(p.M, 256), 8) * 8 * (p.Cout_pad / 128)));
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p);
+  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p, (int)grid.x CD_PROBE_ARG);
   XDET_LAUNCH_CHECK();
   return XDET_OK;
 }
