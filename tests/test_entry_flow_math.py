@@ -1,4 +1,4 @@
-"""host_entry_flow_train / host_entry_flow_backward (xdet/model.py), the NumPy statements of blocks 2-4 of the entry flow in
+"""host_entry_flow_train / host_entry_flow_backward (xdet/train.py, re-exported by xdet.model), the NumPy statements of blocks 2-4 of the entry flow in
 training mode: in float64 against torch.autograd on the same graph -- per block the 1x1 conv on x[:, ::2, ::2] with its
 batch_norm(training=True), two (relu ->) conv2d(groups=C) -> 1x1 conv2d -> batch_norm units at eps 1e-4, max_pool2d(3, 2) on
 the input padded with -inf by TensorFlow's 'SAME' rule, and the add; the loss (entry_x * d_entry).sum() -- at 2 images x 9 x 7

@@ -23,9 +23,10 @@ import batch_norm_cases as BC
 import conv_backward_cases as CC
 import depthwise_backward_cases as DC
 
+from flow_train_cases import S, P, NC, bits, rel_err, close, depthwise_forward64, bn_forward_distances, head_and_rpn_inputs, downstream
+
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
-S, P, NC, A, MID, CO = 256, 64, 21, 22, 256, 490
 DEPTHWISE_FORWARD_TOL = 1e-6     # tests/test_gpu_layers.py::test_depthwise_matches_oracle
 CONV_FORWARD_TOL = 3e-5          # tests/test_gpu_layers.py::test_conv_matches_oracle, f16x3
 STAGE_TOL = 1e-4                 # tests/test_gpu_e2e.py::test_dense_stages
@@ -36,77 +37,20 @@ UPPER = dict(pool_index=True, rpn_hidden=True, large_sep_train=True, exit_flow_t
 TRAIN = dict(UPPER, entry_flow_train=True)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def rel_err(a, b):
-    return float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max()))
-
-
-def close(what, a, b, tol):
-    scale = max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    assert err <= tol * scale, (what, err, scale)
-    return err / (tol * scale)
-
-
 def relu_in(b, i):
     return not (b == 2 and i == 1)
-
-
-def depthwise_forward64(x, k, relu):
-    x, k = np.asarray(x, f64), np.asarray(k, f64)
-    N, H, W, C = x.shape
-    xp = np.pad(np.maximum(x, 0) if relu else x, ((0, 0), (1, 1), (1, 1), (0, 0)))
-    out = np.zeros(x.shape)
-    for a in range(3):
-        for b in range(3):
-            out += xp[:, a:a + H, b:b + W] * k[a, b, :, 0]
-    return out
-
-
-def bn_forward_distances(x, gamma, beta, moving_mean, moving_var, got):
-    """batch_norm_cases.forward_distances in training mode at this flow's eps and momentum (that module's own is pinned to the
-    large-separable block's 1e-5 / 0.997): the same metric per tensor, the statement called locally in float64"""
-    from xdet.ops import host_batch_norm_forward
-    C = x.shape[-1]
-    x = np.asarray(x, f64).reshape(-1, C)
-    y, mean, invstd, mm, mv = (np.asarray(a).reshape(-1, C) if i == 0 else np.asarray(a).reshape(-1) for i, a in enumerate(got))
-    M = x.shape[0]
-    ax, ga, be = np.abs(x), np.abs(np.asarray(gamma, f64)), np.abs(np.asarray(beta, f64))
-    _, rmean, rinv, rmm, rmv = host_batch_norm_forward(x, gamma, beta, EPS, True, MOMENTUM, moving_mean, moving_var, False, f64)
-    assert (1. / rinv ** 2 - EPS > 0).all(), 'a batch variance is 0'
-    keep = 1 - MOMENTUM
-    amm, amv = np.abs(np.asarray(moving_mean, f64)), np.abs(np.asarray(moving_var, f64))
-    out = {'mean': BC._dist(mean, rmean, ax.sum(axis=0) / M),
-           'var': BC._dist(1. / np.asarray(invstd, f64) ** 2, 1. / rinv ** 2, 1. / rinv ** 2),
-           'moving_mean': BC._dist(mm, rmm, amm + (amm + ax.sum(axis=0) / M) * keep),
-           'moving_var': BC._dist(mv, rmv, amv + (amv + (1. / rinv ** 2 - EPS) * (M / max(M - 1, 1))) * keep)}
-    m64, i64 = np.asarray(mean, f64), np.asarray(invstd, f64)       # the statistics the forward under test used
-    ry = ((x - m64) * i64) * np.asarray(gamma, f64) + np.asarray(beta, f64)
-    out['y'] = BC._dist(y, ry, ((ax + np.abs(m64)) * i64) * ga + be)
-    return out
 
 
 @pytest.fixture(scope='module')
 def run(lh_weights):
     """one pass over the whole path; the tests below look at what it left"""
-    import target_cases as C
-    from xdet import model as M, losses as L, targets as T, weights as W, InvalidArgumentError
+    from xdet import model as M, weights as W, InvalidArgumentError
     from xdet.model import LightHeadDetector
     from xdet.runtime import DeviceTensor, get_precision, set_precision
     r = {}
     w = lh_weights
     images = W.synthetic_images(2, S, seed=3)
-    rng = np.random.default_rng(11)
-    ctr, hw = rng.uniform(0.25, 0.75, (2, P, 2)), rng.uniform(0.1, 0.4, (2, P, 2))
-    rois = np.concatenate([ctr - hw / 2, ctr + hw / 2], -1).astype(f32)
-    labels = rng.integers(-1, NC, (2, P)).astype(np.int32)
-    targets = (rng.standard_normal((2, P, 4)) * 0.2).astype(f32)
-    anchor = C.anchors(S)
-    gl, gb = C.make_ground_truth(61, 2, anchor)
-    a_l, a_t, _ = T.host_encode_anchors(anchor, gl, gb)
+    inputs = head_and_rpn_inputs()
 
     before = get_precision()
     set_precision('f16x3')
@@ -138,15 +82,7 @@ def run(lh_weights):
         with pytest.raises(InvalidArgumentError):    # what middle_flow_train saved belongs to the eval-mode entry_x
             M.middle_flow_backward(DeviceTensor.empty(mid_x.shape, ld=mid_x.ld))
         mid_t = M.middle_flow_train()
-        cls, box = M.get_rpn(mid_t, A, False, 'channels_first', 'rpn_head')
-        out_t = M.exit_flow_train()
-        feat = M.large_sep_kernel(out_t, MID, CO, True, 'channels_first', 'large_sep_feature')
-        loss_func = L.HeadLoss(labels, targets, 0.25)
-        M.get_head(feat, None, 7, 7, loss_func, rois, NC, True, True, 32, 'channels_first', 'final_head')
-        head = M.head_backward(loss_func, to_feat=True)
-        lsep = M.large_sep_backward(head['feat'])
-        res = L.rpn_loss(cls, box, a_l, a_t, 256, 0.25, seed=5, keep_device=True)
-        rpn = M.rpn_backward(res)
+        lsep, rpn = downstream(M.exit_flow_train(), mid_t, inputs)
         ef = M.exit_flow_backward(lsep['out'], rpn['mid'])
         mf = M.middle_flow_backward(ef['mid'])
         r['d_entry_t'], r['d_entry'] = mf['entry'], mf['entry'].numpy()
@@ -210,7 +146,7 @@ def test_conditions_from_the_float64_statements(run, lh_weights):
     for name, b, i, x, _ in units(run):
         if relu_in(b, i):
             share.append(float((x > 0).mean()))
-        t = depthwise_forward64(x, w[name + '/depthwise_kernel'], relu_in(b, i))
+        t = depthwise_forward64(x, w[name + '/depthwise_kernel'], relu_in=relu_in(b, i))
         z = CC.conv_forward64(t, w[name + '/pointwise_kernel'], False)
         y, _, invstd, _, _ = host_batch_norm_forward(z, w[name + '_bn/gamma'], w[name + '_bn/beta'], EPS, True, MOMENTUM, None, None,
                                                      False, f64)
@@ -242,7 +178,8 @@ def test_training_forward(run, oracle, lh_weights):
 
     def judge_bn(what, z, bn, y):
         d = bn_forward_distances(z, w[bn + 'gamma'], w[bn + 'beta'], w[bn + 'moving_mean'], w[bn + 'moving_variance'],
-                                 (y, sv[bn + 'save_mean'], sv[bn + 'save_invstd'], sv[bn + 'moving_mean'], sv[bn + 'moving_variance']))
+                                 (y, sv[bn + 'save_mean'], sv[bn + 'save_invstd'], sv[bn + 'moving_mean'], sv[bn + 'moving_variance']),
+                                 eps=EPS, momentum=MOMENTUM)
         assert max(d.values()) <= BC.bar(), (what, d)
         worst['bn'] = max(worst['bn'], max(d.values()) / BC.bar())
         assert not np.array_equal(sv[bn + 'moving_mean'].reshape(-1), w[bn + 'moving_mean'])
@@ -263,7 +200,7 @@ def test_training_forward(run, oracle, lh_weights):
         assert want.dtype == f32 and np.array_equal(bits(sv['x%d' % (b + 1)]), bits(want)), b
     for name, b, i, x, y in units(run):
         worst['depthwise'] = max(worst['depthwise'], close(name + ' depthwise', sv[name + '/dw'],
-                                                           depthwise_forward64(x, w[name + '/depthwise_kernel'], relu_in(b, i)),
+                                                           depthwise_forward64(x, w[name + '/depthwise_kernel'], relu_in=relu_in(b, i)),
                                                            DEPTHWISE_FORWARD_TOL))
         worst['pointwise'] = max(worst['pointwise'], close(name + ' pointwise', sv[name + '/z'],
                                                            CC.conv_forward64(sv[name + '/dw'], w[name + '/pointwise_kernel'], False),

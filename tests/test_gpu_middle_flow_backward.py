@@ -21,64 +21,17 @@ import batch_norm_cases as BC
 import conv_backward_cases as CC
 import depthwise_backward_cases as DC
 
+from flow_train_cases import S, P, NC, A, bits, rel_err, close, depthwise_forward64, bn_forward_distances, head_and_rpn_inputs, \
+    downstream
+
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
-S, P, NC, A, MID, CO = 256, 64, 21, 22, 256, 490
 DEPTHWISE_FORWARD_TOL = 1e-6     # tests/test_gpu_layers.py::test_depthwise_matches_oracle
 CONV_FORWARD_TOL = 3e-5          # tests/test_gpu_layers.py::test_conv_matches_oracle, f16x3
 STAGE_TOL = 1e-4                 # tests/test_gpu_e2e.py::test_dense_stages
 EPS, MOMENTUM = 1e-4, 0.99       # the Xception layers' batch norm (model.MIDDLE_FLOW_EPS / _MOMENTUM)
 BLOCKS = tuple(range(5, 13))
 TRAIN = dict(pool_index=True, rpn_hidden=True, large_sep_train=True, exit_flow_train=True, middle_flow_train=True)
-
-
-def bits(a):
-    return np.asarray(a).view(np.uint32)
-
-
-def rel_err(a, b):
-    return float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max()))
-
-
-def close(what, a, b, tol):
-    scale = max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    assert err <= tol * scale, (what, err, scale)
-    return err / (tol * scale)
-
-
-def depthwise_forward64(x, k, relu_in=True):
-    x, k = np.asarray(x, f64), np.asarray(k, f64)
-    N, H, W, C = x.shape
-    xp = np.pad(np.maximum(x, 0) if relu_in else x, ((0, 0), (1, 1), (1, 1), (0, 0)))
-    out = np.zeros(x.shape)
-    for a in range(3):
-        for b in range(3):
-            out += xp[:, a:a + H, b:b + W] * k[a, b, :, 0]
-    return out
-
-
-def bn_forward_distances(x, gamma, beta, moving_mean, moving_var, got):
-    """batch_norm_cases.forward_distances in training mode at this flow's eps and momentum (that module's own is pinned to the
-    large-separable block's 1e-5 / 0.997): the same metric per tensor, the statement called locally in float64"""
-    from xdet.ops import host_batch_norm_forward
-    C = x.shape[-1]
-    x = np.asarray(x, f64).reshape(-1, C)
-    y, mean, invstd, mm, mv = (np.asarray(a).reshape(-1, C) if i == 0 else np.asarray(a).reshape(-1) for i, a in enumerate(got))
-    M = x.shape[0]
-    ax, ga, be = np.abs(x), np.abs(np.asarray(gamma, f64)), np.abs(np.asarray(beta, f64))
-    _, rmean, rinv, rmm, rmv = host_batch_norm_forward(x, gamma, beta, EPS, True, MOMENTUM, moving_mean, moving_var, False, f64)
-    assert (1. / rinv ** 2 - EPS > 0).all(), 'a batch variance is 0'
-    keep = 1 - MOMENTUM
-    amm, amv = np.abs(np.asarray(moving_mean, f64)), np.abs(np.asarray(moving_var, f64))
-    out = {'mean': BC._dist(mean, rmean, ax.sum(axis=0) / M),
-           'var': BC._dist(1. / np.asarray(invstd, f64) ** 2, 1. / rinv ** 2, 1. / rinv ** 2),
-           'moving_mean': BC._dist(mm, rmm, amm + (amm + ax.sum(axis=0) / M) * keep),
-           'moving_var': BC._dist(mv, rmv, amv + (amv + (1. / rinv ** 2 - EPS) * (M / max(M - 1, 1))) * keep)}
-    m64, i64 = np.asarray(mean, f64), np.asarray(invstd, f64)       # the statistics the forward under test used
-    ry = ((x - m64) * i64) * np.asarray(gamma, f64) + np.asarray(beta, f64)
-    out['y'] = BC._dist(y, ry, ((ax + np.abs(m64)) * i64) * ga + be)
-    return out
 
 
 def refresh_and_rpn(det, M, mid, n):
@@ -94,21 +47,13 @@ def refresh_and_rpn(det, M, mid, n):
 @pytest.fixture(scope='module')
 def run(lh_weights):
     """one pass over the whole path; the tests below look at what it left"""
-    import target_cases as C
-    from xdet import model as M, losses as L, targets as T, weights as W, ops, InvalidArgumentError
+    from xdet import model as M, weights as W, ops, InvalidArgumentError
     from xdet.model import LightHeadDetector
     from xdet.runtime import DeviceTensor, get_precision, set_precision
     r = {}
     w = lh_weights
     images = W.synthetic_images(2, S, seed=3)
-    rng = np.random.default_rng(11)
-    ctr, hw = rng.uniform(0.25, 0.75, (2, P, 2)), rng.uniform(0.1, 0.4, (2, P, 2))
-    rois = np.concatenate([ctr - hw / 2, ctr + hw / 2], -1).astype(f32)
-    labels = rng.integers(-1, NC, (2, P)).astype(np.int32)
-    targets = (rng.standard_normal((2, P, 4)) * 0.2).astype(f32)
-    anchor = C.anchors(S)
-    gl, gb = C.make_ground_truth(61, 2, anchor)
-    a_l, a_t, _ = T.host_encode_anchors(anchor, gl, gb)
+    inputs = head_and_rpn_inputs()
 
     before = get_precision()
     set_precision('f16x3')
@@ -148,19 +93,11 @@ def run(lh_weights):
                                                                                EPS, True, MOMENTUM, stream=det.stream)
             assert np.array_equal(bits(m2), bits(r['saved'][u + '_bn/save_mean'].reshape(-1)))
             assert np.array_equal(bits(i2), bits(r['saved'][u + '_bn/save_invstd'].reshape(-1)))
-        cls, box = M.get_rpn(mid_t, A, False, 'channels_first', 'rpn_head')
-        r['rpn_out'] = det.buffer('rpn_out', 2).numpy()
         d_out0 = DeviceTensor.empty(out.shape, ld=out.ld)
         with pytest.raises(InvalidArgumentError):    # what exit_flow_train saved belongs to the eval-mode mid_x
             M.exit_flow_backward(d_out0)
-        out_t = M.exit_flow_train()
-        feat = M.large_sep_kernel(out_t, MID, CO, True, 'channels_first', 'large_sep_feature')
-        loss_func = L.HeadLoss(labels, targets, 0.25)
-        M.get_head(feat, None, 7, 7, loss_func, rois, NC, True, True, 32, 'channels_first', 'final_head')
-        head = M.head_backward(loss_func, to_feat=True)
-        lsep = M.large_sep_backward(head['feat'])
-        res = L.rpn_loss(cls, box, a_l, a_t, 256, 0.25, seed=5, keep_device=True)
-        rpn = M.rpn_backward(res)
+        lsep, rpn = downstream(M.exit_flow_train(), mid_t, inputs)
+        r['rpn_out'] = det.buffer('rpn_out', 2).numpy()
         ef = M.exit_flow_backward(lsep['out'], rpn['mid'])
         r['d_mid_t'], r['d_mid'] = ef['mid'], ef['mid'].numpy()
         host = lambda g: {k: (v.numpy() if hasattr(v, 'numpy') else v) for k, v in g.items()}
@@ -275,7 +212,8 @@ def test_training_forward(run, lh_weights):
                                                            CONV_FORWARD_TOL))
         bn = name + '_bn/'
         d = bn_forward_distances(sv[name + '/z'], w[bn + 'gamma'], w[bn + 'beta'], w[bn + 'moving_mean'], w[bn + 'moving_variance'],
-                                 (y, sv[bn + 'save_mean'], sv[bn + 'save_invstd'], sv[bn + 'moving_mean'], sv[bn + 'moving_variance']))
+                                 (y, sv[bn + 'save_mean'], sv[bn + 'save_invstd'], sv[bn + 'moving_mean'], sv[bn + 'moving_variance']),
+                                 eps=EPS, momentum=MOMENTUM)
         assert max(d.values()) <= BC.bar(), (name, d)
         worst['bn'] = max(worst['bn'], max(d.values()) / BC.bar())
         assert not np.array_equal(sv[bn + 'moving_mean'].reshape(-1), w[bn + 'moving_mean'])

@@ -1,4 +1,4 @@
-"""host_middle_flow_train / host_middle_flow_backward (xdet/model.py), the NumPy statements of the middle flow in training mode:
+"""host_middle_flow_train / host_middle_flow_backward (xdet/train.py, re-exported by xdet.model), the NumPy statements of the middle flow in training mode:
 in float64 against torch.autograd on the same graph -- per unit relu -> conv2d(groups=C) -> 1x1 conv2d ->
 batch_norm(training=True) at eps 1e-4, per block the residual add, the loss (mid_x * d_mid).sum() -- at 2 images x 6 x 5
 pixels x 8 channels.  Every weight gradient and d entry agree to 1e-10 of the tensor's scale, and the moving statistics follow

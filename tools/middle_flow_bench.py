@@ -72,25 +72,25 @@ def main():
             fw = median(M.middle_flow_train)
             bw = median(lambda: M.middle_flow_backward(d_mid))
             bwi = median(lambda: M.middle_flow_backward(d_mid, intermediates=True), reps=2)
-            units = [u for blk in m['blocks'] for u in blk['units']]
-            rot = m['rot']
+            units = [u for blk in m.blocks for u in blk.units]
+            rot = m.rot
             small = [DeviceBuffer(C * C * 4) for _ in range(2)] + [DeviceBuffer(max(9 * C * 4, 4096)) for _ in range(3)]
 
             def dw_f():
                 for u in units:
-                    check(l.xdet_depthwise_forward(u['dw'].handle, entry.ptr, n, H, Wd, entry.ld, u['t'].ptr, 1, h))
+                    check(l.xdet_depthwise_forward(u.dw.handle, entry.ptr, n, H, Wd, entry.ld, u.t.ptr, 1, h))
 
             def pw_f():
                 for u in units:
-                    check(l.xdet_conv_forward(u['pw'].handle, u['t'].ptr, n, H, Wd, u['t'].ld, u['z'].ptr, u['z'].ld, None, 0, h))
+                    check(l.xdet_conv_forward(u.pw.handle, u.t.ptr, n, H, Wd, u.t.ld, u.z.ptr, u.z.ld, None, 0, h))
 
             def bn_f():
                 for u in units:
-                    b = u['bn']
+                    b = u.bn
                     # (no moving statistics: the timing loop must not walk them away; their update is 2 x 728 floats)
-                    check(l.xdet_batch_norm_forward(u['z'].ptr, u['z'].ld, Mrows, C, b['gamma'].ptr, b['beta'].ptr, 1e-4, 1, 0.99, None,
-                                                    None, 0, rot['da'].ptr, rot['da'].ld, b['save_mean'].ptr, b['save_invstd'].ptr,
-                                                    m['ws_bn'].ptr, h))
+                    check(l.xdet_batch_norm_forward(u.z.ptr, u.z.ld, Mrows, C, b.gamma.ptr, b.beta.ptr, 1e-4, 1, 0.99, None,
+                                                    None, 0, rot['da'].ptr, rot['da'].ld, b.save_mean.ptr, b.save_invstd.ptr,
+                                                    m.ws_bn.ptr, h))
 
             def adds():
                 for _ in range(8):
@@ -101,20 +101,20 @@ def main():
 
             def bn_b():
                 for u in units:
-                    b = u['bn']
-                    check(l.xdet_batch_norm_backward(u['z'].ptr, u['z'].ld, None, 0, d_mid.ptr, d_mid.ld, Mrows, C, b['gamma'].ptr,
-                                                     b['save_mean'].ptr, b['save_invstd'].ptr, 1, rot['dz'].ptr, rot['dz'].ld,
-                                                     small[2].ptr, small[3].ptr, m['ws_bn'].ptr, h))
+                    b = u.bn
+                    check(l.xdet_batch_norm_backward(u.z.ptr, u.z.ld, None, 0, d_mid.ptr, d_mid.ld, Mrows, C, b.gamma.ptr,
+                                                     b.save_mean.ptr, b.save_invstd.ptr, 1, rot['dz'].ptr, rot['dz'].ld,
+                                                     small[2].ptr, small[3].ptr, m.ws_bn.ptr, h))
 
             def pw_b():
                 for u in units:
-                    check(l.xdet_conv_backward(u['t'].ptr, u['t'].ld, u['K_pw'].ptr, None, 0, rot['dz'].ptr, rot['dz'].ld, n, H, Wd, C, C,
-                                               1, 1, 0, rot['dt'].ptr, rot['dt'].ld, small[0].ptr, small[4].ptr, m['ws_conv'].ptr, h))
+                    check(l.xdet_conv_backward(u.t.ptr, u.t.ld, u.K_pw.ptr, None, 0, rot['dz'].ptr, rot['dz'].ld, n, H, Wd, C, C,
+                                               1, 1, 0, rot['dt'].ptr, rot['dt'].ld, small[0].ptr, small[4].ptr, m.ws_conv.ptr, h))
 
             def dw_b():
                 for u in units:
-                    check(l.xdet_depthwise_backward(entry.ptr, entry.ld, u['K_dw'].ptr, rot['dt'].ptr, rot['dt'].ld, n, H, Wd, C, 1, 1,
-                                                    rot['da'].ptr, rot['da'].ld, small[2].ptr, m['ws_dw'].ptr, h))
+                    check(l.xdet_depthwise_backward(entry.ptr, entry.ld, u.K_dw.ptr, rot['dt'].ptr, rot['dt'].ld, n, H, Wd, C, 1, 1,
+                                                    rot['da'].ptr, rot['da'].ld, small[2].ptr, m.ws_dw.ptr, h))
             f_parts = [('pointwise', pw_f), ('batch norm', bn_f), ('depthwise', dw_f), ('adds', adds), ('refresh', refresh)]
             b_parts = [('pointwise', pw_b), ('batch norm', bn_b), ('depthwise', dw_b), ('adds', adds)]
             f_t = [(k, median(fn)[0]) for k, fn in f_parts]

@@ -44,6 +44,8 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the gradient of max_pooling2d(3, 2, 'same') and blocks 2-4 of the Xception entry flow
                              (net/xception_body.py:260-326) with batch statistics and their backward, from `entry_x` down to
                              the stem's output `stem_out`
+The training names above that are marked (xdet.model) are written in xdet/train.py (the stages, their state classes, the
+backwards and the host statements) and re-exported by xdet/model.py, which holds the eval graph and the detector classes.
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """

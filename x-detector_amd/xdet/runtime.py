@@ -176,3 +176,19 @@ class DeviceTensor(object):
         nb = n * self.shape[1] * self.shape[2] * self.ld * 4
         check(lib().xdet_memcpy_d2d(self.ptr, other.ptr, nb, None))
         synchronize()
+
+
+# ---- the current detector: `with detector.scope():` pushes it, the graph-builder functions of xdet.model and xdet.train read the top
+
+_current = []
+
+
+def _det():
+    if not _current:
+        from ._lib import XdetError
+        raise XdetError(-3, 'no current LightHeadDetector: use `with detector.scope():`')
+    return _current[-1]
+
+
+def _sync(d):
+    d.stream.synchronize()

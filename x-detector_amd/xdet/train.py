@@ -1,0 +1,1029 @@
+"""The training graph of the Light-Head R-CNN net: what `xdet.model` re-exports under the training names.
+
+Four stages can be rebuilt in training mode (batch statistics, moving-average updates, a backward), each consuming what the one
+above it writes: the large-separable block <- the exit flow <- the middle flow <- blocks 2-4 of the entry flow (`STAGES`).  A
+detector built with a stage's flag keeps one state object for it (`LargeSepState`, `ExitFlowState`, `MiddleFlowState`,
+`EntryFlowState`), made of `BatchNorm`, `SepUnit` and `Projection`; the module-level functions run a stage of the detector
+that is current (`with det.scope():`).  The head's and the RPN head's backward (`head_backward`, `rpn_backward`) and the NumPy
+statements of the middle and the entry flow (`host_*`) live here too.
+"""
+import collections
+import contextlib
+
+import numpy as np
+
+from ._lib import lib, check, XdetError, InvalidArgumentError
+from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, _det, _sync
+
+__all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
+           'EXIT_FLOW_UNITS', 'EXIT_FLOW_BNS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
+           'MIDDLE_FLOW_BLOCKS', 'MIDDLE_FLOW_UNITS', 'MIDDLE_FLOW_VARIABLES', 'MIDDLE_FLOW_MOVING', 'MIDDLE_FLOW_EPS',
+           'MIDDLE_FLOW_MOMENTUM', 'ENTRY_FLOW_BLOCKS', 'ENTRY_FLOW_UNITS', 'ENTRY_FLOW_VARIABLES', 'ENTRY_FLOW_MOVING',
+           'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
+           'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
+           'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
+           'host_entry_flow_train', 'host_entry_flow_backward']
+
+LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
+                            for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
+    ('large_sep_feature/batch_normalization/gamma', 'large_sep_feature/batch_normalization/beta')
+LARGE_SEP_MOVING = ('large_sep_feature/batch_normalization/moving_mean', 'large_sep_feature/batch_normalization/moving_variance')
+LARGE_SEP_EPS, LARGE_SEP_MOMENTUM = 1e-5, 0.997        # net/resnet_v2.py: _BATCH_NORM_EPSILON, _BATCH_NORM_DECAY
+
+# the Xception exit flow (net/xception_body.py:339-376): four separable units (name, dilation, ReLU in front of the depthwise
+# conv, ReLU behind the batch norm) and the 1x1 projection of the residual branch
+EXIT_FLOW_UNITS = (('block13_sepconv1', 1, True, False), ('block13_sepconv2', 1, True, False),
+                   ('block14_sepconv1', 2, False, True), ('block14_sepconv2', 2, False, True))
+EXIT_FLOW_BNS = tuple(u[0] + '_bn' for u in EXIT_FLOW_UNITS) + ('batch_normalization_4',)
+EXIT_FLOW_VARIABLES = tuple('%s/%s' % (u[0], v) for u in EXIT_FLOW_UNITS for v in ('depthwise_kernel', 'pointwise_kernel')) + \
+    ('conv2d_4/kernel',) + tuple('%s/%s' % (b, v) for b in EXIT_FLOW_BNS for v in ('gamma', 'beta'))
+EXIT_FLOW_MOVING = tuple('%s/%s' % (b, v) for b in EXIT_FLOW_BNS for v in ('moving_mean', 'moving_variance'))
+EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM = 1e-4, 0.99         # net/xception_body.py: the Xception layers' batch norm
+
+# the Xception middle flow (net/xception_body.py:328-337): eight blocks of three relu -> separable 3x3 -> BN units at 728
+# channels, each block closed by a residual add of its input
+MIDDLE_FLOW_BLOCKS = tuple(range(5, 13))
+MIDDLE_FLOW_UNITS = tuple('block%d_sepconv%d' % (b, i) for b in MIDDLE_FLOW_BLOCKS for i in (1, 2, 3))
+MIDDLE_FLOW_VARIABLES = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('/depthwise_kernel', '/pointwise_kernel', '_bn/gamma', '_bn/beta'))
+MIDDLE_FLOW_MOVING = tuple(u + v for u in MIDDLE_FLOW_UNITS for v in ('_bn/moving_mean', '_bn/moving_variance'))
+MIDDLE_FLOW_EPS, MIDDLE_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
+
+# blocks 2-4 of the Xception entry flow (net/xception_body.py:260-326): a 1x1 / stride-2 projection with its batch norm, two
+# (relu ->) separable 3x3 -> BN units, max_pooling2d(3, 2, 'same') and the residual add; block 2's first unit has no ReLU in
+# front (its input is the stem's ReLU output)
+ENTRY_FLOW_BLOCKS = (2, 3, 4)
+ENTRY_FLOW_UNITS = tuple('block%d_sepconv%d' % (b, i) for b in ENTRY_FLOW_BLOCKS for i in (1, 2))
+
+
+def _entry_block_variables(b):
+    return ('conv2d_%d/kernel' % (b - 1), 'batch_normalization_%d/gamma' % (b - 1), 'batch_normalization_%d/beta' % (b - 1)) + \
+        tuple('block%d_sepconv%d%s' % (b, i, v) for i in (1, 2) for v in ('/depthwise_kernel', '/pointwise_kernel', '_bn/gamma', '_bn/beta'))
+
+
+ENTRY_FLOW_VARIABLES = tuple(v for b in ENTRY_FLOW_BLOCKS for v in _entry_block_variables(b))
+ENTRY_FLOW_MOVING = tuple('%s/%s' % (bn, v) for b in ENTRY_FLOW_BLOCKS
+                          for bn in ('batch_normalization_%d' % (b - 1), 'block%d_sepconv1_bn' % b, 'block%d_sepconv2_bn' % b)
+                          for v in ('moving_mean', 'moving_variance'))
+ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
+
+
+def _entry_relu_in(b, i):
+    return not (b == 2 and i == 1)
+
+
+def merge_large_sep(weights, dtype=np.float32):
+    """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
+    native net's, without the BN fold): both (15,1) convs read the same input -> one kernel [15,1,cin,2*mid] with the
+    branches side by side along the outputs and the bias [2*mid]; branch_0b + branch_1b -> one (1,15) kernel [1,15,2*mid,co]
+    with the branches stacked along the inputs and the bias b0 + b1.  -> (K_a, b_a, K_b, b_b)"""
+    g = lambda br, name: np.asarray(weights['large_sep_feature/%s/%s' % (br, name)], dtype)
+    ka = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d/kernel'), g('Branch_1', 'conv2d/kernel')], axis=3))
+    ba = np.concatenate([g('Branch_0', 'conv2d/bias'), g('Branch_1', 'conv2d/bias')])
+    kb = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d_1/kernel'), g('Branch_1', 'conv2d_1/kernel')], axis=2))
+    return ka, ba, kb, g('Branch_0', 'conv2d_1/bias') + g('Branch_1', 'conv2d_1/bias')
+
+
+def split_large_sep_grads(d_ka, d_ba, d_kb, d_bb, mid):
+    """merge_large_sep's adjoint: the gradients of the merged tensors -> the eight conv gradients under the checkpoint's names
+    and in its shapes.  Both conv2d_1 biases enter the block as b0 + b1, so both get d_bb."""
+    out = {}
+    for i, br in enumerate(('Branch_0', 'Branch_1')):
+        p, sl = 'large_sep_feature/%s/' % br, slice(i * mid, (i + 1) * mid)
+        out[p + 'conv2d/kernel'] = np.ascontiguousarray(d_ka[..., sl])
+        out[p + 'conv2d/bias'] = np.ascontiguousarray(d_ba[sl])
+        out[p + 'conv2d_1/kernel'] = np.ascontiguousarray(d_kb[:, :, sl, :])
+        out[p + 'conv2d_1/bias'] = np.array(d_bb)
+    return out
+
+
+# ---- what the stages share ------------------------------------------------------------------------------------------------
+
+@contextlib.contextmanager
+def _f16x3():
+    """layers built inside are split-precision ones whatever the process-wide setting is"""
+    before = get_precision()
+    set_precision('f16x3')
+    try:
+        yield
+    finally:
+        set_precision(before)
+
+
+def _dense(k):
+    """a kernel as the checkpoint stores it -> a dense DeviceTensor (the w / k operand of the backward ops)"""
+    b = to_device(k)
+    return DeviceTensor(b.ptr, k.shape, k.shape[3], owner=b)
+
+
+def _first(t, n):
+    """the first n images of a tensor sized for max_batch"""
+    return DeviceTensor(t.ptr, (n,) + tuple(t.shape[1:]), t.ld, owner=t)
+
+
+def _check_grad(fn, what, t, like):
+    if not isinstance(t, DeviceTensor) or tuple(t.shape) != tuple(like.shape) or t.ld != like.ld:
+        raise InvalidArgumentError(-1, '%s: %s must be a DeviceTensor of shape %r with ld %d, got %r'
+                                   % (fn, what, tuple(like.shape), like.ld, (getattr(t, 'shape', None), getattr(t, 'ld', None))))
+
+
+def _download(dev, grads):
+    """the weight gradients a backward left in `dev` as (DeviceBuffer, shape) -> NumPy arrays in `grads` (behind the sync)"""
+    for k, (buf, shape) in dev.items():
+        grads[k] = to_host(buf.ptr, shape)
+
+
+def _release(tensors):
+    """the stream has run every call: nothing needs keeping alive any longer, and the wrappers' references form a ring through
+    the rotating views"""
+    for t in tensors:
+        t._keep = None
+
+
+class BatchNorm(object):
+    """a batch norm in training mode: gamma, beta, the moving statistics (updated in place by forward) and room for the batch
+    statistics, all on the device, under the checkpoint's name"""
+    __slots__ = ('name', 'eps', 'momentum', 'co', 'gamma', 'beta', 'moving_mean', 'moving_variance', 'save_mean', 'save_invstd')
+
+    def __init__(self, weights, name, eps=EXIT_FLOW_EPS, momentum=EXIT_FLOW_MOMENTUM):
+        self.name, self.eps, self.momentum = name, eps, momentum
+        for k in ('gamma', 'beta', 'moving_mean', 'moving_variance'):
+            setattr(self, k, to_device(np.ascontiguousarray(weights[name + '/' + k], np.float32)))
+        self.co = np.asarray(weights[name + '/gamma']).size
+        self.save_mean, self.save_invstd = DeviceBuffer(self.co * 4), DeviceBuffer(self.co * 4)
+
+    def forward(self, d, z, relu, y, M, ws):
+        """y = (relu)(BN(z)) over z's M rows with their own statistics, which stay in save_mean / save_invstd"""
+        check(lib().xdet_batch_norm_forward(z.ptr, z.ld, M, z.shape[3], self.gamma.ptr, self.beta.ptr, self.eps, 1, self.momentum,
+                                            self.moving_mean.ptr, self.moving_variance.ptr, 1 if relu else 0, y.ptr, y.ld,
+                                            self.save_mean.ptr, self.save_invstd.ptr, ws.ptr, d.stream.handle))
+
+    def backward(self, d, z, y, dy, dx=None, workspace=None):
+        """-> (dz, dgamma, dbeta) on the device; y: the output to mask by where a ReLU follows, else None"""
+        from . import ops
+        return ops.batch_norm_backward_device(z, y, dy, self.gamma, self.save_mean, self.save_invstd, True, stream=d.stream,
+                                              dx=dx, workspace=workspace)
+
+    def views(self, out, prefix=None):
+        """out gains the batch and the moving statistics as [1,1,1,C] tensors under '<name>/...'"""
+        prefix = self.name + '/' if prefix is None else prefix
+        for k in ('save_mean', 'save_invstd', 'moving_mean', 'moving_variance'):
+            b = getattr(self, k)
+            out[prefix + k] = DeviceTensor(b.ptr, (1, 1, 1, self.co), self.co, owner=b)
+
+
+class SepUnit(object):
+    """one `(relu ->) separable 3x3 -> BN (-> relu)` unit in training mode, what all three flows are made of: the depthwise
+    layer, the pointwise conv `pw`, both kernels as dense device tensors for the backward, the batch norm and the tensors a
+    training forward keeps: t (the depthwise output), z (the BN input) and, with own_y, y (the BN output)"""
+    __slots__ = ('name', 'dil', 'relu_in', 'relu_out', 'dw', 'pw', 'K_dw', 'K_pw', 'bn', 't', 'z', 'y')
+
+    def __init__(self, weights, name, dil, relu_in, relu_out, pw, B, H, W, own_y):
+        from . import ops
+        kd = np.ascontiguousarray(weights[name + '/depthwise_kernel'], np.float32)
+        kp = np.ascontiguousarray(weights[name + '/pointwise_kernel'], np.float32)
+        C, J = kp.shape[2], kp.shape[3]
+        self.name, self.dil, self.relu_in, self.relu_out = name, dil, relu_in, relu_out
+        self.dw, self.pw, self.K_dw, self.K_pw = ops.DepthwiseConv2D(kd, dil), pw, _dense(kd), _dense(kp)
+        self.bn = BatchNorm(weights, name + '_bn')
+        self.t, self.z = DeviceTensor.empty((B, H, W, C)), DeviceTensor.empty((B, H, W, J))
+        self.y = DeviceTensor.empty((B, H, W, J)) if own_y else None
+
+    def forward(self, d, x, y, n, H, W, ws_bn):
+        """y = (relu)(BN(pw(dw((relu)(x))))) with batch statistics, t and z kept in the unit: three calls on the detector's stream"""
+        t, z, h = self.t, self.z, d.stream.handle
+        check(lib().xdet_depthwise_forward(self.dw.handle, x.ptr, n, H, W, x.ld, t.ptr, 1 if self.relu_in else 0, h))
+        check(lib().xdet_conv_forward(self.pw.handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
+        self.bn.forward(d, z, self.relu_out, y, n * H * W, ws_bn)
+
+    def backward(self, d, x, y, dy, dev, ws_dw, into=None):
+        """d loss / d y -> d loss / d x through the unit's BN (masked by y, the unit's own output, where it ends in a ReLU; None
+        otherwise), the 1x1 conv (its bias gradient computed and dropped: the conv has none) and the depthwise conv: three calls
+        on the detector's stream, on the kept z and t of x's images.  dev: gains the four weight gradients as (DeviceBuffer,
+        shape) under the checkpoint's names.  into: {'dz', 'dt', 'dx': DeviceTensors to write, 'ws_bn', 'ws_conv': workspaces}
+        -- without it every call allocates its own.  -> (dx, dt, dz)"""
+        from . import ops
+        into = into or {}
+        n, name = x.shape[0], self.name
+        dz, dgamma, dbeta = self.bn.backward(d, _first(self.z, n), y, dy, into.get('dz'), into.get('ws_bn'))
+        dt, dkp, _ = ops.conv_backward_device(_first(self.t, n), self.K_pw, dz, None, stream=d.stream, dx=into.get('dt'),
+                                              workspace=into.get('ws_conv'))
+        dx, dkd = ops.depthwise_backward_device(x, self.K_dw, dt, self.dil, self.relu_in, stream=d.stream, workspace=ws_dw,
+                                                dx=into.get('dx'))
+        J = self.K_pw.shape[3]
+        dev[name + '/depthwise_kernel'], dev[name + '/pointwise_kernel'] = (dkd, self.K_dw.shape), (dkp, self.K_pw.shape)
+        dev[name + '_bn/gamma'], dev[name + '_bn/beta'] = (dgamma, (J,)), (dbeta, (J,))
+        return dx, dt, dz
+
+    def views(self, out, n):
+        """out gains '<unit>/dw', '<unit>/z' of the first n images and the batch norm's statistics"""
+        out[self.name + '/dw'], out[self.name + '/z'] = _first(self.t, n), _first(self.z, n)
+        self.bn.views(out)
+
+
+def _pointwise_layers(weights, names):
+    """{name: the 1x1 conv of <name>/pointwise_kernel in split precision, f32 out, no scale or shift}"""
+    from . import ops
+    with _f16x3():
+        return {n: ops.Conv2D(np.ascontiguousarray(weights[n + '/pointwise_kernel'], np.float32)) for n in names}
+
+
+class Projection(object):
+    """the residual branch of an exit- or entry-flow block, r = BN(conv1x1(x)): the conv layer `<name>/kernel` (split precision,
+    f32 out, no scale or shift), the kernel as a dense device tensor for the backward, the batch norm and the kept z (the BN
+    input) and r, [B,H,W,cout]"""
+    __slots__ = ('name', 'conv', 'K', 'bn', 'z', 'r')
+
+    def __init__(self, weights, name, bn_name, B, H, W):
+        from . import ops
+        k = np.ascontiguousarray(weights[name + '/kernel'], np.float32)
+        with _f16x3():
+            self.conv = ops.Conv2D(k)
+        self.name, self.K, self.bn = name, _dense(k), BatchNorm(weights, bn_name)
+        self.z, self.r = DeviceTensor.empty((B, H, W, k.shape[3])), DeviceTensor.empty((B, H, W, k.shape[3]))
+
+    def forward(self, d, x, n, H, W, ws_bn):
+        z = self.z
+        check(lib().xdet_conv_forward(self.conv.handle, x.ptr, n, H, W, x.ld, z.ptr, z.ld, None, 0, d.stream.handle))
+        self.bn.forward(d, z, False, self.r, n * H * W, ws_bn)
+
+    def backward(self, d, x, g, dev, into=None):
+        """g = d loss / d r -> d loss / d x through the batch norm and the conv (its bias gradient dropped), on the kept z of x's
+        images; dev gains '<conv>/kernel', '<bn>/gamma' and '<bn>/beta'.  into: {'dz', 'dx': DeviceTensors to write, 'ws_bn',
+        'ws_conv': workspaces} -- without it every call allocates its own.  -> (dx, dzr)"""
+        from . import ops
+        into = into or {}
+        dzr, dgamma, dbeta = self.bn.backward(d, _first(self.z, x.shape[0]), None, g, into.get('dz'), into.get('ws_bn'))
+        dx, dk, _ = ops.conv_backward_device(x, self.K, dzr, None, stream=d.stream, dx=into.get('dx'), workspace=into.get('ws_conv'))
+        co = self.K.shape[3]
+        dev[self.name + '/kernel'] = (dk, self.K.shape)
+        dev[self.bn.name + '/gamma'], dev[self.bn.name + '/beta'] = (dgamma, (co,)), (dbeta, (co,))
+        return dx, dzr
+
+    def views(self, out, n, r):
+        """out gains '<conv>/z' and r (under that key) of the first n images and the batch norm's statistics"""
+        out[self.name + '/z'], out[r] = _first(self.z, n), _first(self.r, n)
+        self.bn.views(out)
+
+
+def _max_over_batches(B, nbytes):
+    """a workspace for every batch size up to B"""
+    return DeviceBuffer(max(nbytes(n) for n in range(1, B + 1)))
+
+
+# ---- one state object per stage: built from (detector, weights), sized for max_batch; n = the images its last training forward
+# ---- ran on (0: none, or an earlier stage has run since) ---------------------------------------------------------------------
+
+class LargeSepState(object):
+    """the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as dense device tensors
+    for the backward, the batch norm (eps 1e-5, momentum 0.997), the kept t and z and the BN workspace"""
+
+    def __init__(self, d, weights):
+        from . import ops
+        ka, ba, kb, bb = merge_large_sep({k: np.ascontiguousarray(weights[k], np.float32) for k in LARGE_SEP_VARIABLES})
+        with _f16x3():
+            self.conv_a, self.conv_b = ops.Conv2D(ka, shift=ba), ops.Conv2D(kb, shift=bb)
+        B, (_, H, W, _) = d.max_batch, d.buffer('out', 1).shape
+        co, mid2 = kb.shape[3], ka.shape[3]
+        self.K_a, self.K_b, self.mid, self.n = _dense(ka), _dense(kb), mid2 // 2, 0
+        self.bn = BatchNorm(weights, 'large_sep_feature/batch_normalization', LARGE_SEP_EPS, LARGE_SEP_MOMENTUM)
+        self.t, self.z = DeviceTensor.empty((B, H, W, mid2)), DeviceTensor.empty((B, H, W, co))
+        self.ws = _max_over_batches(B, lambda n: lib().xdet_batch_norm_workspace_bytes(n * H * W, co))
+
+    def forward(self, d, out, n):
+        """large_sep_kernel's training branch: out = the net's `out` of n images -> the net's `feat`"""
+        feat, h = d.buffer('feat', n), d.stream.handle
+        _, H, W, _ = out.shape
+        t, z = self.t, self.z
+        check(lib().xdet_conv_forward(self.conv_a.handle, out.ptr, n, H, W, out.ld, t.ptr, t.ld, None, 0, h))
+        check(lib().xdet_conv_forward(self.conv_b.handle, t.ptr, n, H, W, t.ld, z.ptr, z.ld, None, 0, h))
+        self.bn.forward(d, z, True, feat, n * H * W, self.ws)
+        _ran(d, LARGE_SEP, n)
+        _sync(d)
+        return feat
+
+    def saved(self, d):
+        out = {'t': _first(self.t, self.n), 'z': _first(self.z, self.n)}
+        self.bn.views(out, '')
+        return out
+
+
+class ExitFlowState(object):
+    """the exit flow: its four units (the last batch norm writes the net's `out`), the projection, b2 and one BN and one
+    depthwise-backward workspace for the widest tensor"""
+
+    def __init__(self, d, weights):
+        B, (_, H, W, _) = d.max_batch, d.buffer('mid_x', 1).shape
+        pw = _pointwise_layers(weights, [u[0] for u in EXIT_FLOW_UNITS])
+        self.n, self.proj = 0, Projection(weights, 'conv2d_4', 'batch_normalization_4', B, H, W)
+        self.units = [SepUnit(weights, name, dil, relu_in, relu_out, pw[name], B, H, W, own_y=name != EXIT_FLOW_UNITS[-1][0])
+                      for name, dil, relu_in, relu_out in EXIT_FLOW_UNITS]
+        co = self.proj.conv.cout
+        widest = max([co] + [c for u in self.units for c in (u.t.shape[3], u.z.shape[3])])
+        self.b2 = DeviceTensor.empty((B, H, W, co))
+        self.ws_bn = _max_over_batches(B, lambda n: lib().xdet_batch_norm_workspace_bytes(n * H * W, widest))
+        self.ws_dw = _max_over_batches(B, lambda n: lib().xdet_depthwise_backward_workspace_bytes(n, H, W, widest))
+
+    def saved(self, d):
+        n, out = self.n, {}
+        self.proj.views(out, n, 'r')
+        out['b2'] = _first(self.b2, n)
+        for u, y in zip(self.units, ('a', 'y2', 'c3', None)):
+            u.views(out, n)
+            if y:
+                out[y] = _first(u.y, n)
+        return out
+
+
+MiddleBlock = collections.namedtuple('MiddleBlock', 'b units out')        # out: None for the last block (the net's `mid_x`)
+
+
+class MiddleFlowState(object):
+    """the middle flow: per block three units (the first two keep their y) and the block's output, one BN, one
+    depthwise-backward and one conv-backward workspace for all units, and the four gradient tensors middle_flow_backward
+    rotates through"""
+
+    def __init__(self, d, weights):
+        B, (_, H, W, C) = d.max_batch, d.buffer('entry_x', 1).shape
+        pw = _pointwise_layers(weights, MIDDLE_FLOW_UNITS)
+        self.n, self.blocks = 0, []
+        for b in MIDDLE_FLOW_BLOCKS:
+            units = [SepUnit(weights, 'block%d_sepconv%d' % (b, i), 1, True, False, pw['block%d_sepconv%d' % (b, i)], B, H, W,
+                             own_y=i < 3) for i in (1, 2, 3)]
+            self.blocks.append(MiddleBlock(b, units, DeviceTensor.empty((B, H, W, C)) if b != MIDDLE_FLOW_BLOCKS[-1] else None))
+        self.ws_bn = _max_over_batches(B, lambda n: lib().xdet_batch_norm_workspace_bytes(n * H * W, C))
+        self.ws_dw = _max_over_batches(B, lambda n: lib().xdet_depthwise_backward_workspace_bytes(n, H, W, C))
+        self.ws_conv = _max_over_batches(B, lambda n: lib().xdet_conv_backward_workspace_bytes(n, H, W, C, C, 1, 1))
+        self.rot = {k: DeviceTensor.empty((B, H, W, C)) for k in ('dz', 'dt', 'da', 'db')}
+
+    def saved(self, d):
+        n = self.n
+        out, x = {}, d.buffer('entry_x', n)
+        for blk in self.blocks:
+            out['x%d' % blk.b] = x
+            for u, y in zip(blk.units, ('y1', 'y2', None)):
+                u.views(out, n)
+                if y:
+                    out['block%d/%s' % (blk.b, y)] = _first(u.y, n)
+            x = _first(blk.out, n) if blk.out is not None else None
+        return out
+
+
+# out: None for the last block (the net's `entry_x`); rot: the gradient tensors entry_flow_backward writes inside the block
+EntryBlock = collections.namedtuple('EntryBlock', 'b units H W cin c xs proj out rot')
+
+
+class EntryFlowState(object):
+    """blocks 2-4: per block both units (each keeps its y), the projection, the subsampled input xs, the block's output and the
+    gradient tensors of the backward; one BN, one depthwise-backward and one conv-backward workspace for all"""
+
+    def __init__(self, d, weights):
+        B, (_, H, W, cin) = d.max_batch, d.buffer('stem_out', 1).shape
+        pw = _pointwise_layers(weights, ENTRY_FLOW_UNITS)
+        self.n, self.blocks = 0, []
+        l, need = lib(), {'bn': [], 'dw': [], 'conv': []}
+        for b in ENTRY_FLOW_BLOCKS:
+            Ho, Wo = -(-H // 2), -(-W // 2)
+            proj = Projection(weights, 'conv2d_%d' % (b - 1), 'batch_normalization_%d' % (b - 1), B, Ho, Wo)
+            c = proj.conv.cout
+            units = [SepUnit(weights, 'block%d_sepconv%d' % (b, i), 1, _entry_relu_in(b, i), False, pw['block%d_sepconv%d' % (b, i)],
+                             B, H, W, own_y=True) for i in (1, 2)]
+            full, half = (lambda ch: DeviceTensor.empty((B, H, W, ch))), (lambda ch: DeviceTensor.empty((B, Ho, Wo, ch)))
+            # a unit's dz is dead once its conv backward has run: one tensor serves both units
+            rot = {'dzr': half(c), 'dxs': half(cin), 'dy2': full(c), 'dz': full(c), 'dt2': full(c), 'd2': full(c), 'dt1': full(cin),
+                   'd1': full(cin)}
+            self.blocks.append(EntryBlock(b, units, H, W, cin, c, half(cin), proj, half(c) if b != ENTRY_FLOW_BLOCKS[-1] else None, rot))
+            for n in range(1, B + 1):
+                need['bn'] += [l.xdet_batch_norm_workspace_bytes(n * H * W, c), l.xdet_batch_norm_workspace_bytes(n * Ho * Wo, c)]
+                need['dw'] += [l.xdet_depthwise_backward_workspace_bytes(n, H, W, c), l.xdet_depthwise_backward_workspace_bytes(n, H, W, cin)]
+                need['conv'] += [l.xdet_conv_backward_workspace_bytes(n, Ho, Wo, cin, c, 1, 1),
+                                 l.xdet_conv_backward_workspace_bytes(n, H, W, cin, c, 1, 1),
+                                 l.xdet_conv_backward_workspace_bytes(n, H, W, c, c, 1, 1)]
+            H, W, cin = Ho, Wo, c
+        ex = d.buffer('entry_x', 1)
+        if tuple(ex.shape[1:]) != (H, W, cin):
+            raise InvalidArgumentError(-1, 'entry_flow_train: block 4 gives %r but the net\'s entry_x is %r' % ((H, W, cin), tuple(ex.shape[1:])))
+        self.ws_bn, self.ws_dw, self.ws_conv = DeviceBuffer(max(need['bn'])), DeviceBuffer(max(need['dw'])), DeviceBuffer(max(need['conv']))
+
+    def saved(self, d):
+        n = self.n
+        out, x = {}, d.buffer('stem_out', n)
+        for blk in self.blocks:
+            out['x%d' % blk.b] = x
+            out['block%d/xs' % blk.b] = _first(blk.xs, n)
+            blk.proj.views(out, n, 'block%d/r' % blk.b)
+            for u, y in zip(blk.units, ('y1', 'y2')):
+                u.views(out, n)
+                out['block%d/%s' % (blk.b, y)] = _first(u.y, n)
+            x = _first(blk.out, n) if blk.out is not None else d.buffer('entry_x', n)
+        out['x%d' % (ENTRY_FLOW_BLOCKS[-1] + 1)] = x
+        return out
+
+
+# The stages in the order the data flows backward through them, each consuming what the next one writes in training mode:
+# (the constructor flag and detector attribute, where the detector keeps the state, its class, the weights it needs, the
+# forward its *_saved() names, and why it cannot do without the stage above it in this table)
+Stage = collections.namedtuple('Stage', 'flag attr state names forward needs')
+STAGES = (
+    Stage('large_sep_train', '_lsep', LargeSepState, LARGE_SEP_VARIABLES + LARGE_SEP_MOVING,
+          'large_sep_kernel(..., is_training=True)', None),
+    Stage('exit_flow_train', '_exit', ExitFlowState, EXIT_FLOW_VARIABLES + EXIT_FLOW_MOVING, 'model.exit_flow_train()',
+          'the training-mode `out` it writes is consumed by the large-separable block in training mode'),
+    Stage('middle_flow_train', '_middle', MiddleFlowState, MIDDLE_FLOW_VARIABLES + MIDDLE_FLOW_MOVING, 'model.middle_flow_train()',
+          'the training-mode `mid_x` it writes is consumed by the exit flow in training mode'),
+    Stage('entry_flow_train', '_entry', EntryFlowState, ENTRY_FLOW_VARIABLES + ENTRY_FLOW_MOVING, 'model.entry_flow_train()',
+          'the training-mode `entry_x` it writes is consumed by the middle flow in training mode'))
+LARGE_SEP, EXIT, MIDDLE, ENTRY = range(4)
+
+
+def check_stages(on, weights):
+    """LightHeadDetector.__init__'s refusals, ahead of the native net (which would miss the weights under another error), from
+    the last stage of the table up: stage k needs stage k - 1, then its own variables and moving statistics.  on: one flag per
+    stage, in the table's order"""
+    for k in reversed(range(len(STAGES))):
+        s = STAGES[k]
+        if not on[k]:
+            continue
+        if k and not on[k - 1]:
+            raise InvalidArgumentError(-1, '%s=True needs %s=True (%s)' % (s.flag, STAGES[k - 1].flag, s.needs))
+        miss = [v for v in s.names if v not in weights]
+        if miss:
+            raise InvalidArgumentError(-1, '%s: the weights lack %s' % (s.flag, ', '.join(miss)))
+
+
+def build_stages(d, on, weights):
+    """the detector gains one flag per stage and, for those that are on, the stage's state"""
+    for s, flag in zip(STAGES, on):
+        setattr(d, s.flag, bool(flag))
+        if flag:
+            setattr(d, s.attr, s.state(d, weights))
+
+
+def saved(d, k):
+    """detector.<stage>_saved(): what stage k's last training forward left on the device, as DeviceTensors of its n images"""
+    s = STAGES[k]
+    state = getattr(d, s.attr) if getattr(d, s.flag) else None
+    if state is None or not state.n:
+        raise InvalidArgumentError(-1, '%s: no %s has run on this detector' % (s.flag.replace('_train', '_saved'), s.forward))
+    return state.saved(d)
+
+
+def _stage(d, k, fn, first=None, keeps=''):
+    """the two refusals an entry point opens with -> (stage k's state, the images to run on).  A backward names the training
+    forward it follows (`first`) and runs on that one's images; a training forward follows the eval body and runs on its"""
+    s = STAGES[k]
+    if not getattr(d, s.flag):
+        why = '' if first else ' (the default detector folds the moving statistics into the conv weights%s)' % keeps
+        raise InvalidArgumentError(-1, '%s: needs a detector built with %s=True%s' % (fn, s.flag, why))
+    state = getattr(d, s.attr)
+    n = state.n if first else d._N
+    if not n:
+        raise InvalidArgumentError(-1, '%s: call %s first' % (fn, first or 'XceptionBody(..., is_training=False)'))
+    return state, n
+
+
+def _ran(d, k, n):
+    """stage k's training forward has run on n images: what the stages it feeds had saved belongs to another tensor"""
+    for s in STAGES[:k]:
+        if getattr(d, s.flag):
+            getattr(d, s.attr).n = 0
+    getattr(d, STAGES[k].attr).n = n
+
+
+# ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
+
+def head_backward(loss_func, to_feat=False):
+    """The backward of the head's dense layers, called after get_head(..., is_training=True, ...) on the same detector:
+    d loss / d cls_reg (loss_func.grad_device, what xdet_head_loss wrote) goes through `fc_cls+fc_loc` (x = the net's `fc`
+    buffer, the concatenated [2048, nc + 4] kernel) and then, masked by fc's ReLU, through `subnet_fc` (x = `pooled`) -- two
+    calls of xdet_dense_backward on the net's buffers with their own ld.  -> a dict with the six gradients under the
+    checkpoint's variable names (final_head/{subnet_fc,fc_cls,fc_loc}/{kernel,bias}, NumPy) and 'pooled': d loss / d pooled
+    as a DeviceTensor [N,R,1,C] ([N * R, C] rows, ld C) and 'fc': d loss / d fc (in front of fc's ReLU mask) likewise.
+    to_feat=True (a detector built with pool_index=True): d loss / d pooled goes on through xdet_net_head_pool_backward -- the
+    order-exact PsRoiAlign gradient on the net's `proposals` and the argmax get_head kept -- on the same stream, with no host
+    round trip in between, and the dict gains 'feat': d loss / d feat as a DeviceTensor [N,H,W,C] with the `feat` buffer's
+    ld (padding channels zero), what the large-separable backward will read."""
+    from . import ops
+    d = _det()
+    if to_feat and not d.pool_index:
+        raise InvalidArgumentError(-1, 'head_backward: to_feat=True needs a detector built with pool_index=True (the head '
+                                       'kept no argmax to go back through)')
+    g = getattr(loss_func, 'grad_device', None)
+    if getattr(loss_func, 'result', None) is None or g is None:
+        raise InvalidArgumentError(-1, 'head_backward: the losses ran without a gradient (call get_head(..., is_training=True, '
+                                       '...) with this loss_func first)')
+    n, nc = g.shape[0], d.cfg.num_classes
+    if (g.shape[1], g.shape[3]) != (d.R, nc + 4) or n > d.max_batch:
+        raise InvalidArgumentError(-1, 'head_backward: gradient of shape %r but the detector has %d ROIs per image, %d classes, '
+                                       'max_batch %d' % (g.shape, d.R, nc, d.max_batch))
+    if len(d._head_kernels) != 3:
+        raise InvalidArgumentError(-1, 'head_backward: the detector was built without the final_head kernels')
+    if not hasattr(d, '_head_kernels_dev'):
+        k0 = d._head_kernels['final_head/subnet_fc/kernel']
+        k1 = np.concatenate([d._head_kernels['final_head/fc_cls/kernel'], d._head_kernels['final_head/fc_loc/kernel']], axis=1)
+        d._head_kernels_dev = []
+        for k in (k0, np.ascontiguousarray(k1)):
+            b = to_device(k)
+            d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
+    w0, w1 = d._head_kernels_dev
+    fc, pooled = d.buffer('fc', n), d.buffer('pooled', n)
+    d_feat = None
+    if to_feat:                                    # (allocated ahead of the launches, not between the last two)
+        fb = d.buffer('feat', n)
+        d_feat = DeviceTensor.empty(fb.shape, ld=fb.ld)
+    dx1, dw1, db1 = ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
+    dx0, dw0, db0 = ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
+    if to_feat:
+        check(lib().xdet_net_head_pool_backward(d.handle, n, dx0.ptr, dx0.ld, d_feat.ptr, d.stream.handle))
+    _sync(d)
+    K0, K1 = w0.shape[0], w1.shape[0]
+    kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
+    out = {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
+           'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
+           'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy(),
+           'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
+           'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)}
+    if to_feat:
+        out['feat'] = d_feat
+    return out
+
+
+def rpn_backward(rpn_loss_result):
+    """The backward of the RPN head (net/xception_body.py:381-400), called after get_rpn and losses.rpn_loss(...,
+    keep_device=True) on a detector built with rpn_hidden=True: d loss / d rpn_out (rpn_loss_result.grad_device, what
+    xdet_rpn_loss wrote) goes through the two 1x1 heads as one dense layer (xdet_dense_backward: x = the net's `rpn_hidden`
+    buffer as [N*h*w, 512] rows, the concatenated [512, 6A] kernel) and then, masked by the hidden ReLU, through the 3x3 conv
+    (xdet_conv_backward: x = `mid_x` with the ReLU in front of the conv, y = `rpn_hidden`) -- both on the detector's stream
+    with no host round trip in between.  -> a dict with the six gradients under the checkpoint's variable names
+    (rpn_head/{conv2d,conv2d_1,conv2d_2}/{kernel,bias}, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with
+    `mid_x`'s ld (zero where mid_x <= 0) and 'rpn_hidden': d loss / d rpn_hidden (in front of the ReLU mask) [N,h,w,512]."""
+    from . import ops
+    d = _det()
+    if not d.rpn_hidden:
+        raise InvalidArgumentError(-1, 'rpn_backward: needs a detector built with rpn_hidden=True (the RPN conv kept no f32 '
+                                       'output to go back through)')
+    g = getattr(rpn_loss_result, 'grad_device', None)
+    if g is None:
+        raise InvalidArgumentError(-1, 'rpn_backward: the loss left no gradient on the device (call losses.rpn_loss(..., '
+                                       'keep_device=True) on the tensors get_rpn returned)')
+    if len(d._rpn_kernels) != 3:
+        raise InvalidArgumentError(-1, 'rpn_backward: the detector was built without the rpn_head kernels')
+    n, A = g.shape[0], d.cfg.num_anchors
+    out_view = d.buffer('rpn_out', min(max(n, 1), d.max_batch))
+    if n > d.max_batch or tuple(g.shape[1:]) != tuple(out_view.shape[1:3]) + (6 * A,) or g.ld != out_view.ld:
+        raise InvalidArgumentError(-1, 'rpn_backward: gradient of shape %r (ld %d) but the detector\'s rpn_out is %r (ld %d), '
+                                       'max_batch %d' % (g.shape, g.ld, tuple(out_view.shape[1:]), out_view.ld, d.max_batch))
+    if not hasattr(d, '_rpn_kernels_dev'):
+        k0 = d._rpn_kernels['rpn_head/conv2d/kernel']
+        k1 = np.ascontiguousarray(np.concatenate([d._rpn_kernels['rpn_head/conv2d_1/kernel'].reshape(-1, 2 * A),
+                                                  d._rpn_kernels['rpn_head/conv2d_2/kernel'].reshape(-1, 4 * A)], axis=1))
+        b0, b1 = to_device(k0), to_device(k1)
+        d._rpn_kernels_dev = (DeviceTensor(b0.ptr, k0.shape, k0.shape[3], owner=b0),
+                              DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
+    w0, w1 = d._rpn_kernels_dev
+    hid, mid_x = d.buffer('rpn_hidden', n), d.buffer('mid_x', n)
+    dx1, dw1, db1 = ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
+    d_hid = DeviceTensor(dx1.ptr, hid.shape, dx1.ld, owner=dx1)
+    dx0, dw0, db0 = ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
+    _sync(d)
+    J = w0.shape[3]
+    kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
+    return {'rpn_head/conv2d/kernel': to_host(dw0.ptr, w0.shape), 'rpn_head/conv2d/bias': to_host(db0.ptr, (J,)),
+            'rpn_head/conv2d_1/kernel': np.ascontiguousarray(kw1[:, :2 * A]).reshape(1, 1, J, 2 * A),
+            'rpn_head/conv2d_1/bias': kb1[:2 * A].copy(),
+            'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
+            'rpn_head/conv2d_2/bias': kb1[2 * A:].copy(),
+            'mid': dx0, 'rpn_hidden': d_hid}
+
+
+# ---- the four stages, forward and backward -------------------------------------------------------------------------------------
+
+def large_sep_backward(d_feat):
+    """The backward of the large-separable block in training mode, called after large_sep_kernel(..., is_training=True) on a
+    detector built with large_sep_train=True: d_feat = head_backward(..., to_feat=True)['feat'] (d loss / d feat, with the
+    `feat` buffer's shape and ld) goes through the batch norm and its ReLU (xdet_batch_norm_backward on the kept z, masked
+    by the net's own `feat`), then through the merged (1,15) conv (xdet_conv_backward, x = the kept t) and the merged (15,1)
+    conv (x = the net's `out`) -- three calls on the detector's stream with no host round trip in between.  -> a dict with the
+    ten gradients under the checkpoint's variable names and in its shapes (the merged tensors split back; both conv2d_1
+    biases get the merged bias gradient), 'out': d loss / d out as a DeviceTensor [N,h,w,2048] with `out`'s ld, 'z':
+    d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read)."""
+    from . import ops
+    d = _det()
+    s, n = _stage(d, LARGE_SEP, 'large_sep_backward', 'large_sep_kernel(..., is_training=True)')
+    feat, out = d.buffer('feat', n), d.buffer('out', n)
+    _check_grad('large_sep_backward', 'd_feat', d_feat, feat)
+    dz, dgamma, dbeta = s.bn.backward(d, _first(s.z, n), feat, d_feat)
+    dt, dkb, dbb = ops.conv_backward_device(_first(s.t, n), s.K_b, dz, None, stream=d.stream)
+    d_out, dka, dba = ops.conv_backward_device(out, s.K_a, dt, None, stream=d.stream)
+    _sync(d)
+    co, mid2 = s.K_b.shape[3], s.K_a.shape[3]
+    grads = split_large_sep_grads(to_host(dka.ptr, s.K_a.shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s.K_b.shape),
+                                  to_host(dbb.ptr, (co,)), s.mid)
+    _download({s.bn.name + '/gamma': (dgamma, (co,)), s.bn.name + '/beta': (dbeta, (co,))}, grads)
+    grads['out'], grads['z'], grads['t'] = d_out, dz, dt
+    return grads
+
+
+def exit_flow_train():
+    """The Xception exit flow in training mode (net/xception_body.py:339-376), called after XceptionBody(...,
+    is_training=False) on a detector built with exit_flow_train=True: the exit flow is computed again from the net's `mid_x`
+    buffer with batch statistics -- per separable unit xdet_depthwise_forward, the 1x1 conv (xdet_conv_forward, split
+    precision, f32 out) and xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the ReLU inside where the graph
+    has one, the moving statistics updated on their device copies) --
+
+        r  = BN4(conv2d_4(mid_x))                          a  = BN(pw(dw(relu(mid_x))))
+        b2 = BN(pw(dw(relu(a)))) + r   (xdet_add_rows)     c3 = relu(BN(pw(dw_dil2(b2))))     out = relu(BN(pw(dw_dil2(c3))))
+
+    all on the detector's stream with no host round trip; the last batch norm writes straight into the net's `out` buffer
+    (with its ld), so large_sep_kernel(..., is_training=True), get_head, head_backward and large_sep_backward go on unchanged.
+    `mid_x` is not written: get_rpn is unaffected.  The large-separable block's saved state is dropped: large_sep_backward
+    refuses until large_sep_kernel(..., is_training=True) has run on the new `out`.  What exit_flow_backward needs stays on
+    the device (detector.exit_flow_saved()).  -> `out` [N,h,w,2048]."""
+    d = _det()
+    e, n = _stage(d, EXIT, 'exit_flow_train')
+    h, l = d.stream.handle, lib()
+    mid_x, out = d.buffer('mid_x', n), d.buffer('out', n)
+    _, H, W, _ = mid_x.shape
+    p = e.proj
+    p.forward(d, mid_x, n, H, W, e.ws_bn)
+    x = mid_x
+    for i, u in enumerate(e.units):
+        y = u.y if u.y is not None else out
+        u.forward(d, x, y, n, H, W, e.ws_bn)
+        if i == 1:                                   # block13's residual add behind its second batch norm
+            check(l.xdet_add_rows(y.ptr, y.ld, p.r.ptr, p.r.ld, e.b2.ptr, e.b2.ld, n * H * W, y.shape[3], h))
+            y = e.b2
+        x = y
+    _ran(d, EXIT, n)
+    _sync(d)
+    return out
+
+
+def exit_flow_backward(d_out, d_mid=None):
+    """The backward of the exit flow in training mode, called after exit_flow_train() on a detector built with
+    exit_flow_train=True: d_out = large_sep_backward(...)['out'] (d loss / d out, with the `out` buffer's shape and ld) and
+    optionally d_mid = rpn_backward(...)['mid'] (the RPN branch's share of d loss / d mid_x, with `mid_x`'s shape and ld).  Per
+    separable unit, last to first: xdet_batch_norm_backward on the kept BN input (masked by the unit's own output where the
+    graph has a ReLU: the net's `out`, the kept c3), xdet_conv_backward at 1x1 on the kept depthwise output, then
+    xdet_depthwise_backward (dilation 2 in block14; relu_in on `a` and on `mid_x` in block13).  d loss / d b2 feeds both
+    batch_normalization_4's backward, whose conv_backward on `mid_x` gives share A, and block13's two units, which give share
+    B; the call ends with d loss / d mid_x = (B + A) + d_mid, in that order, by xdet_add_rows -- everything on the detector's
+    stream with no host round trip.  The bias gradient xdet_conv_backward insists on is computed and dropped: these convs
+    have none.  -> a dict with the 19 gradients under the checkpoint's variable names and in its shapes
+    (EXIT_FLOW_VARIABLES, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with `mid_x`'s ld, its addends
+    'mid_A' and 'mid_B', and the intermediate gradients 'b2', 'c3', 'a' and 'r' (d loss / d r is d loss / d b2: the same
+    tensor), 'dw/<unit>' = d loss / d (the unit's depthwise output) and 'z/<unit>', 'z/conv2d_4' = d loss / d (a batch norm's
+    input) likewise."""
+    from . import ops
+    d = _det()
+    e, n = _stage(d, EXIT, 'exit_flow_backward', 'exit_flow_train()')
+    out, mid_x = d.buffer('out', n), d.buffer('mid_x', n)
+    _check_grad('exit_flow_backward', 'd_out', d_out, out)
+    if d_mid is not None:
+        _check_grad('exit_flow_backward', 'd_mid', d_mid, mid_x)
+    grads, dev = {}, {}
+
+    def unit_backward(u, x, y, dy):
+        """-> d loss / d x through BN (masked by y), the 1x1 conv and the depthwise conv"""
+        dx, grads['dw/' + u.name], grads['z/' + u.name] = u.backward(d, x, y, dy, dev, e.ws_dw)
+        return dx
+    u1, u2, u3, u4 = e.units
+    a, b2, c3 = _first(u1.y, n), _first(e.b2, n), _first(u3.y, n)
+    d_c3 = unit_backward(u4, c3, out, d_out)
+    d_b2 = unit_backward(u3, b2, c3, d_c3)
+    share_a, dzr = e.proj.backward(d, mid_x, d_b2, dev)
+    d_a = unit_backward(u2, a, None, d_b2)
+    share_b = unit_backward(u1, mid_x, None, d_a)
+    mid = ops.add_rows_device(share_b, share_a, stream=d.stream)
+    if d_mid is not None:
+        ops.add_rows_device(mid, d_mid, out=mid, stream=d.stream)
+    _sync(d)
+    _download(dev, grads)
+    grads.update({'mid': mid, 'mid_A': share_a, 'mid_B': share_b, 'b2': d_b2, 'r': d_b2, 'c3': d_c3, 'a': d_a, 'z/conv2d_4': dzr})
+    return grads
+
+
+def middle_flow_train():
+    """The Xception middle flow in training mode (net/xception_body.py:328-337), called after XceptionBody(...,
+    is_training=False) on a detector built with middle_flow_train=True: blocks 5-12 are computed again from the net's `entry_x`
+    buffer with batch statistics, per block
+
+        y1 = BN(pw(dw(relu(x))))    y2 = BN(pw(dw(relu(y1))))    y3 = BN(pw(dw(relu(y2))))    x' = y3 + x   (xdet_add_rows)
+
+    -- per unit xdet_depthwise_forward, the 1x1 conv (xdet_conv_forward, split precision, f32 out) and
+    xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the moving statistics updated on their device copies);
+    the third batch norm writes the block's output tensor and the add runs on it in place; block 12's is the net's `mid_x`
+    (with its ld).  Then xdet_net_mid_refresh re-derives what the net keeps of `mid_x` -- the ReLU split planes the RPN's 3x3
+    conv reads and the `mid` buffer -- so get_rpn, rpn_backward and exit_flow_train all see the training-mode tensor.  24 x 3
+    calls, 8 adds and the refresh on the detector's stream with no host round trip; `entry_x` is not written.  The exit flow's
+    saved state is dropped: exit_flow_backward refuses until exit_flow_train() has run on the new `mid_x`.  What
+    middle_flow_backward needs stays on the device (detector.middle_flow_saved()).  -> `mid` [N,h,w,728], the tensor get_rpn
+    accepts."""
+    d = _det()
+    m, n = _stage(d, MIDDLE, 'middle_flow_train', keeps=' and keeps no entry_x')
+    h, l = d.stream.handle, lib()
+    x, mid_x = d.buffer('entry_x', n), d.buffer('mid_x', n)
+    _, H, W, C = x.shape
+    for blk in m.blocks:
+        u1, u2, u3 = blk.units
+        out = blk.out if blk.out is not None else mid_x
+        u1.forward(d, x, u1.y, n, H, W, m.ws_bn)
+        u2.forward(d, u1.y, u2.y, n, H, W, m.ws_bn)
+        u3.forward(d, u2.y, out, n, H, W, m.ws_bn)
+        check(l.xdet_add_rows(out.ptr, out.ld, x.ptr, x.ld, out.ptr, out.ld, n * H * W, C, h))
+        x = out
+    check(l.xdet_net_mid_refresh(d.handle, n, h))
+    _ran(d, MIDDLE, n)                               # (what exit_flow_train saved belongs to another mid_x)
+    _sync(d)
+    return d.buffer('mid', n)
+
+
+def middle_flow_backward(d_mid, intermediates=False):
+    """The backward of the middle flow in training mode, called after middle_flow_train() on a detector built with
+    middle_flow_train=True: d_mid = exit_flow_backward(...)['mid'] (d loss / d mid_x, with `mid_x`'s shape and ld).  From
+    block 12 back to block 5, with g = the gradient of the block's output, y1, y2 the kept batch norm outputs and x the
+    block's input:
+
+        d3 = unit_backward(u3, y2, g)    d2 = unit_backward(u2, y1, d3)    d1 = unit_backward(u1, x, d2)
+        g' = d1 + g   (xdet_add_rows, in that order)
+
+    where unit_backward is the exit flow's: xdet_batch_norm_backward on the kept BN input (no mask: these units end without a
+    ReLU), xdet_conv_backward at 1x1 on the kept depthwise output (its bias gradient computed and dropped), then
+    xdet_depthwise_backward with relu_in.  24 x 3 calls and 8 adds on the detector's stream, no float atomics, no host round trip
+    until the end: the gradients inside a block go through four tensors the detector owns, the workspaces are the detector's,
+    and what the call returns on the device is allocated in front of the first launch.  -> a dict with the 96 gradients under
+    the checkpoint's variable names and in its shapes (MIDDLE_FLOW_VARIABLES, NumPy), 'entry': d loss / d entry_x as a
+    DeviceTensor [N,h,w,728] with `entry_x`'s ld, and 'x6' ... 'x12': the gradients at the block boundaries ('x<b>' = d loss /
+    d (block b's input)).  intermediates=True: also 'dw/<unit>' = d loss / d (the unit's depthwise output), 'z/<unit>' =
+    d loss / d (its batch norm's input) and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>' (the units' input gradients; d1 is the
+    addend of the join), each in a tensor of its own."""
+    from . import ops
+    d = _det()
+    m, n = _stage(d, MIDDLE, 'middle_flow_backward', 'middle_flow_train()')
+    mid_x, entry = d.buffer('mid_x', n), d.buffer('entry_x', n)
+    _check_grad('middle_flow_backward', 'd_mid', d_mid, mid_x)
+    rot = {k: _first(t, n) for k, t in m.rot.items()}
+    shape = tuple(entry.shape)
+    key = lambda blk: 'x%d' % blk.b if blk.b != MIDDLE_FLOW_BLOCKS[0] else 'entry'
+    # everything the call returns on the device, allocated ahead of the launches
+    grads = {key(blk): DeviceTensor.empty(shape, ld=entry.ld) for blk in m.blocks}
+    if intermediates:
+        for blk in m.blocks:
+            for i, u in enumerate(blk.units):
+                grads['d%d/block%d' % (i + 1, blk.b)] = DeviceTensor.empty(shape, ld=entry.ld)
+                grads['dw/' + u.name], grads['z/' + u.name] = DeviceTensor.empty(shape), DeviceTensor.empty(shape)
+    dev, g = {}, d_mid
+    inputs = [entry] + [_first(blk.out, n) for blk in m.blocks[:-1]]
+    for blk, x in reversed(list(zip(m.blocks, inputs))):
+        u1, u2, u3 = blk.units
+        dy = g
+        # the three unit gradients alternate between two tensors: a unit's dx is read by the next unit's BN backward only
+        for i, u, xin, dst in ((3, u3, _first(u2.y, n), 'da'), (2, u2, _first(u1.y, n), 'db'), (1, u1, x, 'da')):
+            into = {'ws_bn': m.ws_bn, 'ws_conv': m.ws_conv, 'dz': rot['dz'], 'dt': rot['dt'], 'dx': rot[dst]}
+            if intermediates:
+                into.update(dz=grads['z/' + u.name], dt=grads['dw/' + u.name], dx=grads['d%d/block%d' % (i, blk.b)])
+            dy, _, _ = u.backward(d, xin, None, dy, dev, m.ws_dw, into)
+        g = ops.add_rows_device(dy, g, out=grads[key(blk)], stream=d.stream)
+    _sync(d)
+    _release(list(rot.values()) + list(grads.values()))
+    _download(dev, grads)
+    return grads
+
+
+def entry_flow_train():
+    """Blocks 2-4 of the Xception entry flow in training mode (net/xception_body.py:260-326), called after XceptionBody(...,
+    is_training=False) on a detector built with entry_flow_train=True: the three blocks are computed again from the net's
+    `stem_out` buffer with batch statistics, per block with x its input
+
+        xs = subsample2(x)   (xdet_subsample2)        r  = BN(conv1x1(xs))
+        y1 = BN(pw(dw(relu?(x))))                     y2 = BN(pw(dw(relu(y1))))       (no ReLU in front of block2_sepconv1)
+        x' = maxpool3x3s2(y2) + r                     (xdet_maxpool3x3s2_add)
+
+    -- the convs by xdet_depthwise_forward and xdet_conv_forward (split precision, f32 out), the batch norms by
+    xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the moving statistics updated on their device copies);
+    block 4's x' is written into the net's `entry_x` (with its ld).  33 calls on the detector's stream with no host round
+    trip; `stem_out` is not written.  The middle and the exit flow's saved state is dropped: their backwards refuse until
+    middle_flow_train() / exit_flow_train() have run on the new tensors.  What entry_flow_backward needs stays on the device
+    (detector.entry_flow_saved()).  -> `entry_x` [N,h,w,728]."""
+    d = _det()
+    e, n = _stage(d, ENTRY, 'entry_flow_train', keeps=' and keeps no stem_out')
+    h, l = d.stream.handle, lib()
+    x = d.buffer('stem_out', n)
+    for blk in e.blocks:
+        (u1, u2), p, xs = blk.units, blk.proj, blk.xs
+        H, W = blk.H, blk.W
+        out = blk.out if blk.out is not None else d.buffer('entry_x', n)
+        check(l.xdet_subsample2(x.ptr, x.ld, n, H, W, blk.cin, xs.ptr, xs.ld, h))
+        p.forward(d, xs, n, -(-H // 2), -(-W // 2), e.ws_bn)
+        u1.forward(d, x, u1.y, n, H, W, e.ws_bn)
+        u2.forward(d, u1.y, u2.y, n, H, W, e.ws_bn)
+        y2, r = u2.y, p.r
+        if not (y2.ld == r.ld == out.ld):
+            raise XdetError(-3, 'entry_flow_train: pixel strides %r of y2, r and the block output differ' % ((y2.ld, r.ld, out.ld),))
+        check(l.xdet_maxpool3x3s2_add(y2.ptr, r.ptr, out.ptr, n, H, W, blk.c, y2.ld, h))
+        x = out
+    _ran(d, ENTRY, n)                                # (what the later flows saved belongs to another entry_x)
+    _sync(d)
+    return d.buffer('entry_x', n)
+
+
+def entry_flow_backward(d_entry, intermediates=False):
+    """The backward of blocks 2-4 in training mode, called after entry_flow_train() on a detector built with
+    entry_flow_train=True: d_entry = middle_flow_backward(...)['entry'] (d loss / d entry_x, with `entry_x`'s shape and ld).
+    From block 4 back to block 2, with g the gradient of the block's output, x the block's input and y1, y2 the kept batch
+    norm outputs:
+
+        dzr = BN_backward(proj, g)       dxs, dK = conv_backward(xs, K, dzr)          (the bias gradient is dropped)
+        dy2 = maxpool_backward(y2, g)    (xdet_maxpool3x3s2_backward)
+        d2  = unit_backward(u2, y1, dy2)       d1 = unit_backward(u1, x, d2)
+        g'  = add_upsample2(d1, dxs)     (xdet_add_upsample2: the shortcut's share lands on the even pixels)
+
+    where unit_backward is the other flows': xdet_batch_norm_backward, xdet_conv_backward at 1x1, xdet_depthwise_backward.
+    Everything runs on the detector's stream with no host round trip until the end and no float atomics; the gradients inside
+    a block go through tensors the detector owns, the workspaces are the detector's, and what the call returns on the device
+    is allocated in front of the first launch.  -> a dict with the 33 gradients under the checkpoint's variable names and in
+    its shapes (ENTRY_FLOW_VARIABLES, NumPy), 'stem': d loss / d stem_out as a DeviceTensor [N,h,w,64] with `stem_out`'s ld, and
+    'x3', 'x4': the gradients at the block boundaries ('x<b>' = d loss / d (block b's input)).  intermediates=True: also
+    'dxs/block<b>', 'z/conv2d_<b-1>' (dzr), 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>' and per unit 'dw/<unit>' =
+    d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own."""
+    from . import ops
+    d = _det()
+    e, n = _stage(d, ENTRY, 'entry_flow_backward', 'entry_flow_train()')
+    _check_grad('entry_flow_backward', 'd_entry', d_entry, d.buffer('entry_x', n))
+    key = lambda blk: 'stem' if blk.b == ENTRY_FLOW_BLOCKS[0] else 'x%d' % blk.b
+    inputs = [d.buffer('stem_out', n)] + [_first(blk.out, n) for blk in e.blocks[:-1]]
+    # everything the call returns on the device, allocated ahead of the launches
+    grads, inner = {}, {}
+    for blk, x in zip(e.blocks, inputs):
+        b = blk.b
+        grads[key(blk)] = DeviceTensor.empty(tuple(x.shape), ld=x.ld)
+        rot = {k: _first(t, n) for k, t in blk.rot.items()}
+        rot['dz1'] = rot['dz']
+        if intermediates:
+            u1, u2 = blk.units
+            names = {'dzr': 'z/' + blk.proj.name, 'dxs': 'dxs/block%d' % b, 'dy2': 'dy2/block%d' % b, 'd2': 'd2/block%d' % b,
+                     'd1': 'd1/block%d' % b, 'dt2': 'dw/' + u2.name, 'dt1': 'dw/' + u1.name, 'dz': 'z/' + u2.name,
+                     'dz1': 'z/' + u1.name}
+            for k, name in names.items():
+                grads[name] = rot[k] = DeviceTensor.empty(tuple(rot[k].shape), ld=rot[k].ld)
+        inner[b] = rot
+    dev, g = {}, d_entry
+    for blk, x in reversed(list(zip(e.blocks, inputs))):
+        (u1, u2), rot = blk.units, inner[blk.b]
+        ws = {'ws_bn': e.ws_bn, 'ws_conv': e.ws_conv}
+        dxs, _ = blk.proj.backward(d, _first(blk.xs, n), g, dev, dict(ws, dz=rot['dzr'], dx=rot['dxs']))
+        dy2 = ops.max_pool_backward_device(_first(u2.y, n), g, dx=rot['dy2'], stream=d.stream)
+        d2, _, _ = u2.backward(d, _first(u1.y, n), None, dy2, dev, e.ws_dw, dict(ws, dz=rot['dz'], dt=rot['dt2'], dx=rot['d2']))
+        d1, _, _ = u1.backward(d, x, None, d2, dev, e.ws_dw, dict(ws, dz=rot['dz1'], dt=rot['dt1'], dx=rot['d1']))
+        g = ops.add_upsample2_device(d1, dxs, out=grads[key(blk)], stream=d.stream)
+    _sync(d)
+    _release([t for rot in inner.values() for t in rot.values()] + list(grads.values()))
+    _download(dev, grads)
+    return grads
+
+
+# ---- the flows' host statements: NumPy, any channel counts and map sizes (the weights and the input decide), float64 as the
+# ---- yardstick ---------------------------------------------------------------------------------------------------------------
+
+def _host_depthwise_forward(x, k, relu_in, dtype):
+    x, k = np.asarray(x, dtype), np.asarray(k, dtype)
+    N, H, W, C = x.shape
+    xp = np.pad(np.maximum(x, dtype(0)) if relu_in else x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    out = np.zeros(x.shape, dtype)
+    for a in range(3):
+        for b in range(3):
+            out += xp[:, a:a + H, b:b + W] * k[a, b, :, 0]
+    return out
+
+
+def _host_max_pool_forward(x, dtype):
+    """max_pooling2d(3, 2, 'same') of x [N,H,W,C]: padded positions are absent"""
+    from .ops import _same_pad_front
+    x = np.asarray(x, dtype)
+    N, H, W, C = x.shape
+    (Ho, pt), (Wo, pl) = _same_pad_front(H), _same_pad_front(W)
+    xp = np.full((N, 2 * Ho + 1, 2 * Wo + 1, C), -np.inf, dtype)
+    xp[:, pt:pt + H, pl:pl + W] = x
+    out = np.full((N, Ho, Wo, C), -np.inf, dtype)
+    for a in range(3):
+        for b in range(3):
+            out = np.maximum(out, xp[:, a:a + 2 * Ho:2, b:b + 2 * Wo:2])
+    return out
+
+
+def _host_bn_forward(z, weights, bn, eps, momentum, dtype, saved):
+    """y = BN(z) with batch statistics; saved gains the four statistics under '<bn>/...'"""
+    from . import ops
+    y, mean, invstd, mm, mv = ops.host_batch_norm_forward(z, weights[bn + '/gamma'], weights[bn + '/beta'], eps, True, momentum,
+                                                          weights[bn + '/moving_mean'], weights[bn + '/moving_variance'], False, dtype)
+    saved.update({bn + '/save_mean': mean, bn + '/save_invstd': invstd, bn + '/moving_mean': mm, bn + '/moving_variance': mv})
+    return y
+
+
+def _host_unit_forward(x, weights, unit, relu_in, eps, momentum, dtype, saved):
+    """y = BN(pw(dw((relu)(x)))); saved gains '<unit>/dw', '<unit>/z' and the batch norm's statistics"""
+    t = _host_depthwise_forward(x, weights[unit + '/depthwise_kernel'], relu_in, dtype)
+    z = np.matmul(t, np.asarray(weights[unit + '/pointwise_kernel'], dtype)[0, 0])
+    saved[unit + '/dw'], saved[unit + '/z'] = t, z
+    return _host_bn_forward(z, weights, unit + '_bn', eps, momentum, dtype, saved)
+
+
+def _host_bn_backward(saved, weights, z, bn, dy, dtype):
+    from . import ops
+    vec = lambda a: np.asarray(a, dtype).reshape(-1)
+    return ops.host_batch_norm_backward(saved[z], None, dy, weights[bn + '/gamma'], vec(saved[bn + '/save_mean']),
+                                        vec(saved[bn + '/save_invstd']), True, dtype)
+
+
+def _host_unit_backward(x, dy, saved, weights, unit, relu_in, dtype, out):
+    """d loss / d y -> d loss / d x through the unit's BN, 1x1 conv and depthwise conv; out gains the unit's four weight
+    gradients, 'dw/<unit>' and 'z/<unit>'"""
+    from . import ops
+    bn = unit + '_bn'
+    dz, out[bn + '/gamma'], out[bn + '/beta'] = _host_bn_backward(saved, weights, unit + '/z', bn, dy, dtype)
+    dt, out[unit + '/pointwise_kernel'], _ = ops.host_conv_backward(saved[unit + '/dw'], weights[unit + '/pointwise_kernel'], dz, None, False, dtype)
+    dx, out[unit + '/depthwise_kernel'] = ops.host_depthwise_backward(x, weights[unit + '/depthwise_kernel'], dt, 1, relu_in, dtype)
+    out['dw/' + unit], out['z/' + unit] = dt, dz
+    return dx
+
+
+def host_middle_flow_train(entry_x, weights, dtype=np.float64, blocks=MIDDLE_FLOW_BLOCKS):
+    """The NumPy statement of middle_flow_train: entry_x [N,h,w,C] and the blocks' variables and moving statistics under the
+    checkpoint's names (C comes from the weights) -> (mid_x, saved): the output of the last block and a dict with
+    detector.middle_flow_saved()'s keys for `blocks` -- 'x<b>', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per
+    batch norm '/save_mean', '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's
+    update as ops.host_batch_norm_forward states it) -- plus 'block<b>/y3'."""
+    x, saved = np.asarray(entry_x, dtype), {}
+    for b in blocks:
+        saved['x%d' % b] = x
+        y = x
+        for i in (1, 2, 3):
+            y = saved['block%d/y%d' % (b, i)] = _host_unit_forward(y, weights, 'block%d_sepconv%d' % (b, i), True, MIDDLE_FLOW_EPS,
+                                                                   MIDDLE_FLOW_MOMENTUM, dtype, saved)
+        x = y + x
+    return x, saved
+
+
+def host_middle_flow_backward(saved, weights, d_mid, dtype=np.float64, blocks=MIDDLE_FLOW_BLOCKS):
+    """The NumPy statement of middle_flow_backward(d_mid, intermediates=True): saved = what host_middle_flow_train (or
+    detector.middle_flow_saved(), as NumPy arrays) left, d_mid = d loss / d (the last block's output) -> a dict with the four
+    gradients of every unit of `blocks` under the checkpoint's names and in its shapes, 'entry' = d loss / d (the first block's
+    input), 'x<b>' for every later block, 'dw/<unit>', 'z/<unit>' and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>'.  Composed of ops.host_batch_norm_backward,
+    ops.host_conv_backward and ops.host_depthwise_backward."""
+    blocks = tuple(blocks)
+    g, out = np.asarray(d_mid, dtype), {}
+    for b in reversed(blocks):
+        dy = g
+        for i, xin in ((3, saved['block%d/y2' % b]), (2, saved['block%d/y1' % b]), (1, saved['x%d' % b])):
+            dy = out['d%d/block%d' % (i, b)] = _host_unit_backward(xin, dy, saved, weights, 'block%d_sepconv%d' % (b, i), True, dtype, out)
+        g = dy + g
+        out['entry' if b == blocks[0] else 'x%d' % b] = g
+    return out
+
+
+def host_entry_flow_train(stem_out, weights, dtype=np.float64, blocks=ENTRY_FLOW_BLOCKS):
+    """The NumPy statement of entry_flow_train: stem_out [N,h,w,C] (the first block's input) and the blocks' variables and
+    moving statistics under the checkpoint's names (the channel counts come from the weights) -> (entry_x, saved): the output
+    of the last block and a dict with detector.entry_flow_saved()'s keys for `blocks` -- 'x<b>', 'block<b>/xs',
+    'conv2d_<b-1>/z', 'block<b>/r', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per batch norm '/save_mean',
+    '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's update as
+    ops.host_batch_norm_forward states it)."""
+    from . import ops
+    x, saved = np.asarray(stem_out, dtype), {}
+    for b in blocks:
+        saved['x%d' % b] = x
+        proj = 'conv2d_%d' % (b - 1)
+        xs = ops.host_subsample2(x, dtype)
+        zr = np.matmul(xs, np.asarray(weights[proj + '/kernel'], dtype)[0, 0])
+        r = _host_bn_forward(zr, weights, 'batch_normalization_%d' % (b - 1), ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM, dtype, saved)
+        saved['block%d/xs' % b], saved[proj + '/z'], saved['block%d/r' % b] = xs, zr, r
+        y = x
+        for i in (1, 2):
+            y = saved['block%d/y%d' % (b, i)] = _host_unit_forward(y, weights, 'block%d_sepconv%d' % (b, i), _entry_relu_in(b, i),
+                                                                   ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM, dtype, saved)
+        x = _host_max_pool_forward(y, dtype) + r
+    saved['x%d' % (blocks[-1] + 1)] = x
+    return x, saved
+
+
+def host_entry_flow_backward(saved, weights, d_entry, dtype=np.float64, blocks=ENTRY_FLOW_BLOCKS):
+    """The NumPy statement of entry_flow_backward(d_entry, intermediates=True): saved = what host_entry_flow_train (or
+    detector.entry_flow_saved(), as NumPy arrays) left, d_entry = d loss / d (the last block's output) -> a dict with the eleven
+    gradients of every block of `blocks` under the checkpoint's names and in its shapes, 'stem' = d loss / d (the first block's
+    input), 'x<b>' for every later block, and 'dxs/block<b>', 'z/conv2d_<b-1>', 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>',
+    'dw/<unit>', 'z/<unit>'.  Composed of ops.host_batch_norm_backward, ops.host_conv_backward, ops.host_depthwise_backward,
+    ops.host_max_pool_backward and ops.host_add_upsample2."""
+    from . import ops
+    blocks = tuple(blocks)
+    g, out = np.asarray(d_entry, dtype), {}
+    for b in reversed(blocks):
+        proj, bn = 'conv2d_%d' % (b - 1), 'batch_normalization_%d' % (b - 1)
+        dzr, out[bn + '/gamma'], out[bn + '/beta'] = _host_bn_backward(saved, weights, proj + '/z', bn, g, dtype)
+        dxs, out[proj + '/kernel'], _ = ops.host_conv_backward(saved['block%d/xs' % b], weights[proj + '/kernel'], dzr, None, False, dtype)
+        out['z/' + proj], out['dxs/block%d' % b] = dzr, dxs
+        dy = out['dy2/block%d' % b] = ops.host_max_pool_backward(saved['block%d/y2' % b], g, dtype)
+        for i, xin in ((2, saved['block%d/y1' % b]), (1, saved['x%d' % b])):
+            dy = out['d%d/block%d' % (i, b)] = _host_unit_backward(xin, dy, saved, weights, 'block%d_sepconv%d' % (b, i),
+                                                                   _entry_relu_in(b, i), dtype, out)
+        g = ops.host_add_upsample2(dy, dxs, dtype)
+        out['stem' if b == blocks[0] else 'x%d' % b] = g
+    return out
