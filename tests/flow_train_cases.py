@@ -64,18 +64,19 @@ def bn_forward_distances(x, gamma, beta, moving_mean, moving_var, got, relu=Fals
     return out
 
 
-def head_and_rpn_inputs():
-    """-> (rois [2,P,4], labels [2,P], targets [2,P,4], anchor labels, anchor targets): what the head loss and the RPN loss of the
-    pass are fed"""
+def head_and_rpn_inputs(n=2):
+    """-> (rois [n,P,4], labels [n,P], targets [n,P,4], anchor labels, anchor targets): what the head loss and the RPN loss of a
+    pass on n images are fed.  One generator draws the same arrays in the same order for every n, so n = 2 gives the values the
+    flow tests' recorded fractions were measured with (tests/test_gpu_train_partial_batch.py holds the two calls equal)"""
     import target_cases as C
     from xdet import targets as T
     rng = np.random.default_rng(11)
-    ctr, hw = rng.uniform(0.25, 0.75, (2, P, 2)), rng.uniform(0.1, 0.4, (2, P, 2))
+    ctr, hw = rng.uniform(0.25, 0.75, (n, P, 2)), rng.uniform(0.1, 0.4, (n, P, 2))
     rois = np.concatenate([ctr - hw / 2, ctr + hw / 2], -1).astype(f32)
-    labels = rng.integers(-1, NC, (2, P)).astype(np.int32)
-    targets = (rng.standard_normal((2, P, 4)) * 0.2).astype(f32)
+    labels = rng.integers(-1, NC, (n, P)).astype(np.int32)
+    targets = (rng.standard_normal((n, P, 4)) * 0.2).astype(f32)
     anchor = C.anchors(S)
-    gl, gb = C.make_ground_truth(61, 2, anchor)
+    gl, gb = C.make_ground_truth(61, n, anchor)
     a_l, a_t, _ = T.host_encode_anchors(anchor, gl, gb)
     return rois, labels, targets, a_l, a_t
 

@@ -195,9 +195,13 @@ class LightHeadDetector(object):
             _current.pop()
 
     def set_images(self, images_nchw):
+        """whitened f32 [N,3,S,S] -> the detector's image buffer (what XceptionBody, forward and calibrate run on) -> N.  The
+        eval body that follows overwrites `stem_out`, `entry_x`, `mid_x` and `out`, so every training stage's saved state is
+        dropped here: a *_backward or *_saved() refuses until its training forward has run on the new tensors."""
         a = np.ascontiguousarray(images_nchw, np.float32)
         assert a.ndim == 4 and a.shape[1] == 3 and a.shape[2] == a.shape[3] == self.image_size, a.shape
         assert a.shape[0] <= self.max_batch
+        _train.new_body(self)                            # (the stages' saved state belongs to the images that go now)
         check(lib().xdet_memcpy_h2d(self._images.ptr, _host(a), a.nbytes, self.stream.handle))
         self._N = a.shape[0]
         return self._N
@@ -205,8 +209,11 @@ class LightHeadDetector(object):
     # ---- the whole forward (lighr_head_model_fn, eval) -----------------------------------
     def forward_device(self, n=None, use_graph=False, images_ptr=None, image_shapes_ptr=None, bbox_img_ptr=None,
                        det_scores_ptr=None, det_boxes_ptr=None):
-        """asynchronous: images already resident (set_images or caller-owned device pointer)."""
+        """asynchronous: images already resident (set_images or caller-owned device pointer).  Like set_images, a caller-owned
+        pointer drops what the training stages had saved (train.new_body)."""
         n = n or self._N
+        if images_ptr:
+            _train.new_body(self)                        # (images that never went through set_images)
         check(lib().xdet_net_forward(self.handle, images_ptr or self._images.ptr, n, image_shapes_ptr, bbox_img_ptr,
                                      det_scores_ptr or self._det_scores.ptr, det_boxes_ptr or self._det_boxes.ptr,
                                      1 if use_graph else 0, self.stream.handle))
@@ -293,6 +300,7 @@ class LightHeadDetector(object):
         if bufs['packed'] is None or bufs['packed'].nbytes < packed.nbytes:
             cap = max(packed.nbytes, 2 * bufs['packed'].nbytes if bufs['packed'] is not None else 0)
             bufs['packed'] = DeviceBuffer(cap)
+        _train.new_body(self)
         h = self.stream.handle
         check(lib().xdet_memcpy_h2d(bufs['packed'].ptr, _host(packed), packed.nbytes, h))
         check(lib().xdet_memcpy_h2d(bufs['offsets'].ptr, _host(offsets), offsets.nbytes, h))
@@ -477,7 +485,8 @@ def large_sep_kernel(net_input, depth_mid, depth_output, is_training, data_forma
     z = conv_b(t) + b_b on the merged kernels (xdet_conv_forward, split precision, f32 out), then feat = relu(bn(z)) with the
     batch's statistics and the moving-average updates (xdet_batch_norm_forward, eps 1e-5, momentum 0.997) written straight
     into the net's `feat` buffer -- three calls on the detector's stream with no host round trip in between.  t, z and the
-    statistics stay on the device (detector.large_sep_saved()) for large_sep_backward."""
+    statistics stay on the device (detector.large_sep_saved()) for large_sep_backward, until a training forward of one
+    of the flows or a new eval body (set_images, forward, calibrate, detect_images) runs: either drops them."""
     d = _det()
     n = net_input.shape[0]
     if is_training and not d.large_sep_train:

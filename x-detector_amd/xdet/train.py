@@ -271,7 +271,7 @@ def _max_over_batches(B, nbytes):
 
 
 # ---- one state object per stage: built from (detector, weights), sized for max_batch; n = the images its last training forward
-# ---- ran on (0: none, or an earlier stage has run since) ---------------------------------------------------------------------
+# ---- ran on (0: none, or a stage it consumes or a new eval body has run since: _ran, new_body) -----------------------------
 
 class LargeSepState(object):
     """the large-separable block: the merged kernels as conv layers (split precision, f32 out) and as dense device tensors
@@ -489,6 +489,16 @@ def _ran(d, k, n):
     getattr(d, STAGES[k].attr).n = n
 
 
+def new_body(d):
+    """the eval body is about to run on new images (set_images, a caller-owned image pointer, the uint8 ingest): `stem_out`,
+    `entry_x`, `mid_x` and `out` will hold their eval tensors, so what every stage had saved belongs to tensors that are gone.
+    Each *_backward and *_saved() refuses until its stage's training forward has run again.  A detector built without
+    training flags pays the four attribute reads"""
+    for s in STAGES:
+        if getattr(d, s.flag):
+            getattr(d, s.attr).n = 0
+
+
 # ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
 
 def head_backward(loss_func, to_feat=False):
@@ -605,7 +615,9 @@ def large_sep_backward(d_feat):
     conv (x = the net's `out`) -- three calls on the detector's stream with no host round trip in between.  -> a dict with the
     ten gradients under the checkpoint's variable names and in its shapes (the merged tensors split back; both conv2d_1
     biases get the merged bias gradient), 'out': d loss / d out as a DeviceTensor [N,h,w,2048] with `out`'s ld, 'z':
-    d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read)."""
+    d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read).  Refused once a new eval
+    body (set_images, forward, calibrate, detect_images) or a training forward of one of the flows has run since the block's
+    own: the kept t and z belong to another `out`."""
     from . import ops
     d = _det()
     s, n = _stage(d, LARGE_SEP, 'large_sep_backward', 'large_sep_kernel(..., is_training=True)')
@@ -637,7 +649,9 @@ def exit_flow_train():
     (with its ld), so large_sep_kernel(..., is_training=True), get_head, head_backward and large_sep_backward go on unchanged.
     `mid_x` is not written: get_rpn is unaffected.  The large-separable block's saved state is dropped: large_sep_backward
     refuses until large_sep_kernel(..., is_training=True) has run on the new `out`.  What exit_flow_backward needs stays on
-    the device (detector.exit_flow_saved()).  -> `out` [N,h,w,2048]."""
+    the device (detector.exit_flow_saved()) until the next eval body: whatever puts new images through the net (set_images, hence
+    XceptionBody, forward and calibrate; forward_device on a caller's pointer; detect_images) drops the saved state of all four
+    stages.  -> `out` [N,h,w,2048]."""
     d = _det()
     e, n = _stage(d, EXIT, 'exit_flow_train')
     h, l = d.stream.handle, lib()
@@ -672,7 +686,8 @@ def exit_flow_backward(d_out, d_mid=None):
     (EXIT_FLOW_VARIABLES, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with `mid_x`'s ld, its addends
     'mid_A' and 'mid_B', and the intermediate gradients 'b2', 'c3', 'a' and 'r' (d loss / d r is d loss / d b2: the same
     tensor), 'dw/<unit>' = d loss / d (the unit's depthwise output) and 'z/<unit>', 'z/conv2d_4' = d loss / d (a batch norm's
-    input) likewise."""
+    input) likewise.  Refused once a new eval body (set_images, forward, calibrate, detect_images) or a training forward of
+    the middle or the entry flow has run since exit_flow_train(): the kept tensors belong to another `mid_x`."""
     from . import ops
     d = _det()
     e, n = _stage(d, EXIT, 'exit_flow_backward', 'exit_flow_train()')
@@ -716,8 +731,8 @@ def middle_flow_train():
     conv reads and the `mid` buffer -- so get_rpn, rpn_backward and exit_flow_train all see the training-mode tensor.  24 x 3
     calls, 8 adds and the refresh on the detector's stream with no host round trip; `entry_x` is not written.  The exit flow's
     saved state is dropped: exit_flow_backward refuses until exit_flow_train() has run on the new `mid_x`.  What
-    middle_flow_backward needs stays on the device (detector.middle_flow_saved()).  -> `mid` [N,h,w,728], the tensor get_rpn
-    accepts."""
+    middle_flow_backward needs stays on the device (detector.middle_flow_saved()) until the next eval body, which drops the
+    saved state of all four stages (see exit_flow_train).  -> `mid` [N,h,w,728], the tensor get_rpn accepts."""
     d = _det()
     m, n = _stage(d, MIDDLE, 'middle_flow_train', keeps=' and keeps no entry_x')
     h, l = d.stream.handle, lib()
@@ -755,7 +770,8 @@ def middle_flow_backward(d_mid, intermediates=False):
     DeviceTensor [N,h,w,728] with `entry_x`'s ld, and 'x6' ... 'x12': the gradients at the block boundaries ('x<b>' = d loss /
     d (block b's input)).  intermediates=True: also 'dw/<unit>' = d loss / d (the unit's depthwise output), 'z/<unit>' =
     d loss / d (its batch norm's input) and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>' (the units' input gradients; d1 is the
-    addend of the join), each in a tensor of its own."""
+    addend of the join), each in a tensor of its own.  Refused once a new eval body (set_images, forward, calibrate,
+    detect_images) or entry_flow_train() has run since middle_flow_train(): the kept tensors belong to another `entry_x`."""
     from . import ops
     d = _det()
     m, n = _stage(d, MIDDLE, 'middle_flow_backward', 'middle_flow_train()')
@@ -803,7 +819,8 @@ def entry_flow_train():
     block 4's x' is written into the net's `entry_x` (with its ld).  33 calls on the detector's stream with no host round
     trip; `stem_out` is not written.  The middle and the exit flow's saved state is dropped: their backwards refuse until
     middle_flow_train() / exit_flow_train() have run on the new tensors.  What entry_flow_backward needs stays on the device
-    (detector.entry_flow_saved()).  -> `entry_x` [N,h,w,728]."""
+    (detector.entry_flow_saved()) until the next eval body, which drops the saved state of all four stages (see
+    exit_flow_train).  -> `entry_x` [N,h,w,728]."""
     d = _det()
     e, n = _stage(d, ENTRY, 'entry_flow_train', keeps=' and keeps no stem_out')
     h, l = d.stream.handle, lib()
@@ -844,7 +861,9 @@ def entry_flow_backward(d_entry, intermediates=False):
     its shapes (ENTRY_FLOW_VARIABLES, NumPy), 'stem': d loss / d stem_out as a DeviceTensor [N,h,w,64] with `stem_out`'s ld, and
     'x3', 'x4': the gradients at the block boundaries ('x<b>' = d loss / d (block b's input)).  intermediates=True: also
     'dxs/block<b>', 'z/conv2d_<b-1>' (dzr), 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>' and per unit 'dw/<unit>' =
-    d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own."""
+    d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own.  Refused
+    once a new eval body (set_images, forward, calibrate, detect_images) has run since entry_flow_train(): the kept tensors
+    belong to another `stem_out`."""
     from . import ops
     d = _det()
     e, n = _stage(d, ENTRY, 'entry_flow_backward', 'entry_flow_train()')
