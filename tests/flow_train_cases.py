@@ -1,7 +1,8 @@
 """What the training-flow GPU tests share (tests/test_gpu_exit_flow_backward.py, test_gpu_middle_flow_backward.py,
-test_gpu_entry_flow_backward.py): the sizes of their one pass, its ROIs, labels, targets and anchor encodings, the chain behind
-the exit flow that all three run, and the float64 statements and metrics they judge the forward steps with.  The bars stay in
-the test files."""
+test_gpu_entry_flow_backward.py, test_gpu_train_partial_batch.py, test_gpu_train_derivative.py): the sizes of their one pass, its
+ROIs, labels, targets and anchor encodings, the chain behind the exit flow that all run, the whole training forward down to the
+scalar loss (the derivative check's instrument), and the float64 statements and metrics the forward steps are judged with.  The
+bars stay in the test files."""
 import numpy as np
 
 import batch_norm_cases as BC
@@ -96,3 +97,28 @@ def downstream(out_t, mid, inputs):
     cls, box = M.get_rpn(mid, A, False, 'channels_first', 'rpn_head')
     res = L.rpn_loss(cls, box, a_l, a_t, 256, 0.25, seed=5, keep_device=True)
     return lsep, M.rpn_backward(res)
+
+
+def forward_losses(inputs):
+    """the whole training forward on the current detector, behind an eval body that left `stem_out`: entry_flow_train,
+    middle_flow_train, exit_flow_train and what `downstream` runs forward of there, with its arguments -- the training
+    large-separable block, the head with OHEM 32 and its loss, the RPN and its loss (seed 5) -- and no backward; nothing of the
+    net is downloaded but the losses' own result fields.
+    -> L = the head loss + the RPN loss as a Python float: the two scalars whose derivatives the chain's backward starts from
+    (xdet/losses.py: grad_cls / grad_reg are d HeadLossResult.losses[0] / d cls_reg, grad_cls / grad_loc and grad_device
+    d RpnLossResult.losses[2] / d rpn_out; tests/test_losses_math.py::test_gradients_equal_central_differences holds both),
+    each summed in float64 from the finest fields the losses return, by its definition in that module's contract: losses[0] is
+    the mean of per_roi over the N * K rows of `select`, losses[2] is ce + loc = losses[0] + losses[1].  The f32 scalars
+    themselves carry 2^-24 of L, which a difference quotient over a step that moves L by 1e-5 of itself would magnify to 1e-2"""
+    from xdet import model as M, losses as L
+    rois, labels, targets, a_l, a_t = inputs
+    M.entry_flow_train()
+    mid = M.middle_flow_train()
+    feat = M.large_sep_kernel(M.exit_flow_train(), MID, CO, True, 'channels_first', 'large_sep_feature')
+    loss_func = L.HeadLoss(labels, targets, 0.25)
+    M.get_head(feat, None, 7, 7, loss_func, rois, NC, True, True, 32, 'channels_first', 'final_head')
+    cls, box = M.get_rpn(mid, A, False, 'channels_first', 'rpn_head')
+    res = L.rpn_loss(cls, box, a_l, a_t, 256, 0.25, seed=5, with_grad=False)
+    head = loss_func.result
+    kept = np.asarray(head.per_roi, f64)[np.arange(head.select.shape[0])[:, None], head.select]
+    return float(kept.mean() + (f64(res.losses[0]) + f64(res.losses[1])))

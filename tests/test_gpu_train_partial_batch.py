@@ -112,8 +112,10 @@ def backward_order(section, keys):
     return [k for _, k in order]
 
 
-def one_pass(det, images, inputs, keep=True):
-    """the pass of the module docstring on `det` -> {'<section>/<key>': Kept} in the order of the flow (None without keep)"""
+def one_pass(det, images, inputs, keep=True, raw=None):
+    """the pass of the module docstring on `det` -> {'<section>/<key>': Kept} in the order of the flow (None without keep).
+    raw: a dict that gains what the calls returned, as they returned it ('head_loss', 'rpn_loss', 'large_sep_backward',
+    'rpn_backward', 'exit_flow_backward', 'middle_flow_backward', 'entry_flow_backward')"""
     from xdet import model as M
     n, losses = images.shape[0], {}
     with det.scope():
@@ -125,6 +127,9 @@ def one_pass(det, images, inputs, keep=True):
         ef = M.exit_flow_backward(lsep['out'], rpn['mid'])
         mf = M.middle_flow_backward(ef['mid'], intermediates=True)
         en = M.entry_flow_backward(mf['entry'], intermediates=True)
+        if raw is not None:
+            raw.update(losses, large_sep_backward=lsep, rpn_backward=rpn, exit_flow_backward=ef, middle_flow_backward=mf,
+                       entry_flow_backward=en)
         if not keep:
             return None
         got = {}
