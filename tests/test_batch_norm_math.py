@@ -1,4 +1,4 @@
-"""host_batch_norm_forward / host_batch_norm_backward (xdet/ops.py), the NumPy statements of xdet_batch_norm_forward /
+"""host_batch_norm_forward / host_batch_norm_backward (xdet/train_ops.py), the NumPy statements of xdet_batch_norm_forward /
 _backward: in float64 against torch.nn.functional.batch_norm and torch.autograd in both modes, with and without ReLU; the f32
 statement's distance from the float64 one on every case of tests/batch_norm_cases.py, which
 tests/golden/batch_norm_f32_distance.npz records and the GPU bar is read from; that the bar has teeth (an E[x^2] - E[x]^2
@@ -192,11 +192,11 @@ def test_merged_branches_reproduce_the_per_branch_gradients():
 
 def test_python_door_refuses_before_any_gpu_work(monkeypatch):
     import xdet
-    from xdet import ops, runtime
+    from xdet import ops, runtime, train_ops
 
     def no_gpu(*a, **k):
         raise AssertionError('GPU work before the argument checks')
-    for mod in (runtime, ops):
+    for mod in (runtime, ops, train_ops):
         monkeypatch.setattr(mod, 'to_device', no_gpu)
         monkeypatch.setattr(mod, 'DeviceBuffer', no_gpu)
     z = lambda *s: np.zeros(s, f32)

@@ -1,4 +1,4 @@
-"""host_conv_backward (xdet/ops.py), the NumPy statement of xdet_conv_backward: in float64 against torch.autograd of
+"""host_conv_backward (xdet/train_ops.py), the NumPy statement of xdet_conv_backward: in float64 against torch.autograd of
 torch.nn.functional.conv2d on every case of tests/conv_backward_cases.py (both ReLU masks included), the adjoint identities,
 1 x 1 against host_dense_backward, the mask rule for NaN in y and x, the argument checks of the C door -- and the f32
 statement's distance from the float64 one, which tests/golden/conv_backward_f32_distance.npz records and the GPU bar is read
@@ -126,11 +126,11 @@ def test_dx_skipped_and_padded_views():
 
 def test_python_door_refuses_before_any_gpu_work(monkeypatch):
     import xdet
-    from xdet import ops, runtime
+    from xdet import ops, runtime, train_ops
 
     def no_gpu(*a, **k):
         raise AssertionError('GPU work before the argument checks')
-    for mod in (runtime, ops):
+    for mod in (runtime, ops, train_ops):
         monkeypatch.setattr(mod, 'to_device', no_gpu)
         monkeypatch.setattr(mod, 'DeviceBuffer', no_gpu)
     z = lambda *s: np.zeros(s, np.float32)

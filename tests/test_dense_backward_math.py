@@ -1,4 +1,4 @@
-"""host_dense_backward (xdet/ops.py), the NumPy statement of xdet_dense_backward: in float64 against central differences of
+"""host_dense_backward (xdet/train_ops.py), the NumPy statement of xdet_dense_backward: in float64 against central differences of
 sum(c * act(x w + b)), the mask rule (exact zeros and NaN in y), dx skipped, padded rows with NaN behind the width, the
 argument checks of the GPU door -- and the f32 statement's distance from the float64 one over the cases of
 tests/dense_backward_cases.py, which tests/golden/dense_backward_f32_distance.npz records and the GPU bar is read from."""
@@ -84,11 +84,11 @@ def test_wider_rows_with_nan_padding():
 
 def test_python_door_refuses_before_any_gpu_work(monkeypatch):
     import xdet
-    from xdet import ops, runtime
+    from xdet import ops, runtime, train_ops
 
     def no_gpu(*a, **k):
         raise AssertionError('GPU work before the argument checks')
-    for mod in (runtime, ops):
+    for mod in (runtime, ops, train_ops):
         monkeypatch.setattr(mod, 'to_device', no_gpu)
         monkeypatch.setattr(mod, 'DeviceBuffer', no_gpu)
     z = lambda *s: np.zeros(s, np.float32)

@@ -1,4 +1,4 @@
-"""host_depthwise_backward (xdet/ops.py), the NumPy statement of xdet_depthwise_backward: in float64 against torch.autograd
+"""host_depthwise_backward (xdet/train_ops.py), the NumPy statement of xdet_depthwise_backward: in float64 against torch.autograd
 through torch.nn.functional.conv2d(groups=C, dilation=d, padding=d) on relu(x), on every case of
 tests/depthwise_backward_cases.py; the f32 statement's distance from the float64 one, which
 tests/golden/depthwise_backward_f32_distance.npz records and the GPU bar for dw is read from (measured here: 9.9e-08, so 4 x it
@@ -104,11 +104,11 @@ def test_power_of_two_scaling_is_exact(name):
 
 def test_python_door_refuses_before_any_gpu_work(monkeypatch):
     import xdet
-    from xdet import ops, runtime
+    from xdet import ops, runtime, train_ops
 
     def no_gpu(*a, **k):
         raise AssertionError('GPU work before the argument checks')
-    for mod in (runtime, ops):
+    for mod in (runtime, ops, train_ops):
         monkeypatch.setattr(mod, 'to_device', no_gpu)
         monkeypatch.setattr(mod, 'DeviceBuffer', no_gpu)
     z = lambda *s: np.zeros(s, f32)

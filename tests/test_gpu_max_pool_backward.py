@@ -132,13 +132,15 @@ def test_python_doors_of_the_gather_and_the_join():
     assert same is tx and np.array_equal(bits(tx.numpy()), bits(host_add_upsample2(x, b)))
 
 
-def test_refusals():
-    """the refusals of tests/test_max_pool_backward_math.py with a device present, and dx / out of the wrong shape"""
+def test_refusals(monkeypatch):
+    """the refusals of tests/test_max_pool_backward_math.py with a device present (the Python doors' with every upload and
+    allocation turned into a failure, as there), and dx / out of the wrong shape"""
     import xdet
     from xdet.runtime import DeviceTensor
     import test_max_pool_backward_math as T
     T.test_c_door_refuses_before_any_gpu_work()
-    T.test_python_door_refusals_need_no_gpu()
+    with monkeypatch.context() as m:
+        T.test_python_door_refusals_need_no_gpu(m)
     z = lambda *s: np.zeros(s, f32)
     with pytest.raises(xdet.InvalidArgumentError):
         xdet.max_pool_backward_device(z(1, 4, 4, 8), z(1, 2, 2, 8), dx=DeviceTensor.empty((1, 4, 5, 8)))

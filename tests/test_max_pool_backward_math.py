@@ -1,4 +1,4 @@
-"""ops.host_max_pool_backward, host_subsample2 and host_add_upsample2 (xdet/ops.py), the NumPy statements of
+"""ops.host_max_pool_backward, host_subsample2 and host_add_upsample2 (xdet/train_ops.py), the NumPy statements of
 xdet_maxpool3x3s2_backward, xdet_subsample2 and xdet_add_upsample2: in float64 against torch.autograd, exactly
 (np.array_equal) -- a max pool's gradient only moves and adds values of dy, and the adds of at most four shares happen in the
 same order on both sides, or in any order where a pixel gets at most two.  The tie rule is the point: the first maximum in
@@ -137,9 +137,18 @@ def test_c_door_refuses_before_any_gpu_work():
         assert up(**kw) == XDET_ERR_INVALID_ARG, kw
 
 
-def test_python_door_refusals_need_no_gpu():
+def test_python_door_refusals_need_no_gpu(monkeypatch):
     import xdet
+    from xdet import ops, runtime, train_ops
+
+    def no_gpu(*a, **k):
+        raise AssertionError('GPU work before the argument checks')
+    for mod in (runtime, ops, train_ops):             # (DeviceTensor.from_numpy and .empty allocate through runtime's names)
+        monkeypatch.setattr(mod, 'to_device', no_gpu)
+        monkeypatch.setattr(mod, 'DeviceBuffer', no_gpu)
     z = lambda *s: np.zeros(s, f32)
+    with pytest.raises(xdet.InvalidArgumentError):
+        xdet.add_rows_device(z(1, 4, 4, 8), z(1, 4, 3, 8))              # b of another shape
     with pytest.raises(xdet.InvalidArgumentError):
         xdet.max_pool_backward(z(1, 4, 4, 8), z(1, 2, 3, 8))            # dy of another map
     with pytest.raises(xdet.InvalidArgumentError):
@@ -157,3 +166,8 @@ def test_python_door_refusals_need_no_gpu():
         xdet.subsample2_device(big)
     with pytest.raises(xdet.InvalidArgumentError):
         xdet.add_upsample2_device(big, half)
+    # a caller's dx / out of another shape, with NumPy operands: refused ahead of their upload
+    with pytest.raises(xdet.InvalidArgumentError):
+        xdet.max_pool_backward_device(z(1, 4, 4, 8), z(1, 2, 2, 8), dx=DeviceTensor(4096, (1, 4, 4, 4), 4))
+    with pytest.raises(xdet.InvalidArgumentError):
+        xdet.subsample2_device(z(1, 4, 4, 8), out=DeviceTensor(4096, (1, 4, 4, 8), 8))

@@ -46,6 +46,7 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                              the stem's output `stem_out`
 The training names above that are marked (xdet.model) are written in xdet/train.py (the stages, their state classes, the
 backwards and the host statements) and re-exported by xdet/model.py, which holds the eval graph and the detector classes.
+The training names marked (xdet.ops) are written in xdet/train_ops.py and re-exported by xdet/ops.py, which holds the eval path.
 Importing this package does not load the HIP library; the first op call does and fails
 loudly if it is missing (no CPU fallback).
 """
@@ -58,7 +59,10 @@ from . import augment                                                         # 
 
 def __getattr__(name):
     import importlib
-    for mod in ('ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets', 'losses'):
+    modules = ('ops', 'train_ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets', 'losses')
+    if name in modules:           # `from . import ops` inside the package asks here first: the module itself, and no other
+        return importlib.import_module('.' + name, __name__)
+    for mod in modules:
         m = importlib.import_module('.' + mod, __name__)
         if hasattr(m, name):
             return getattr(m, name)

@@ -806,608 +806,5 @@ def light_head_preprocess_for_test(image, out_shape, data_format='NHWC', resize=
     return light_head_preprocess_for_eval(image, None, None, out_shape, data_format, resize=resize, stream=stream)[0]
 
 
-# ---- the backward of a dense layer (xdet_dense_backward, csrc/dense_backward.hip) -------------------------------------
-
-def host_dense_backward(x, w, dy, y=None, dtype=np.float32, with_dx=True):
-    """The NumPy statement of xdet_dense_backward (include/xdet.h) for a layer y = act(x w + b): x [M,K], w [K,J], dy [M,J],
-    y [M,J] the forward's output after its ReLU (None: no ReLU) -> (dx [M,K] = g w^T, dw [K,J] = x^T g, db [J] = column
-    sums of g) with g = dy, or dy where y > 0 and 0 elsewhere (an exact zero and a NaN in y both give 0).  dtype float32,
-    or float64: the accuracy yardstick.  with_dx=False: dx is None."""
-    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
-    g = dy
-    if y is not None:
-        with np.errstate(invalid='ignore'):
-            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
-    dx = np.matmul(g, w.T).astype(dtype) if with_dx else None
-    return dx, np.matmul(x.T, g).astype(dtype), g.sum(axis=0, dtype=dtype)
-
-
-def _matrix(a, what):
-    """a DeviceTensor ([N,H,W,C] with its ld: N*H*W rows of C) or a 2-D array -> (rows, width, DeviceTensor or f32 array)"""
-    if isinstance(a, DeviceTensor):
-        return int(np.prod(a.shape[:-1])), int(a.shape[-1]), a
-    a = np.ascontiguousarray(a, np.float32)
-    if a.ndim != 2:
-        raise InvalidArgumentError(-1, 'dense_backward: %s must be a matrix, got shape %r' % (what, a.shape))
-    return a.shape[0], a.shape[1], a
-
-
-def dense_backward_device(x, w, dy, y=None, with_dx=True, stream=None):
-    """dense_backward with the results left on the GPU: (dx DeviceTensor [M,1,1,K] or None, dw DeviceBuffer [K,J],
-    db DeviceBuffer [J]); nothing is synchronised."""
-    M, K, dx_in = _matrix(x, 'x')
-    Kw, J, dw_in = _matrix(w, 'w')
-    Md, Jd, dy_in = _matrix(dy, 'dy')
-    bad = (Kw, Md, Jd) != (K, M, J)
-    if y is not None:
-        My, Jy, y_in = _matrix(y, 'y')
-        bad = bad or (My, Jy) != (M, J)
-    if bad:
-        raise InvalidArgumentError(-1, 'dense_backward: x [M,K], w [K,J], dy [M,J] and y [M,J] expected, got %r'
-                                   % ([(M, K), (Kw, J), (Md, Jd)] + ([(My, Jy)] if y is not None else []),))
-    if min(M, K, J) <= 0 or max(K, J) > 4096 or M * max(K, J) >= 2 ** 31:
-        raise InvalidArgumentError(-1, 'dense_backward: M = %d, K = %d, J = %d (positive, K and J at most 4096, '
-                                       'M * max(K, J) below 2^31)' % (M, K, J))
-    if isinstance(dw_in, DeviceTensor) and dw_in.ld != J:
-        raise InvalidArgumentError(-1, 'dense_backward: w must be dense on the device (ld %d, J = %d)' % (dw_in.ld, J))
-
-    def dev(a, width):
-        if isinstance(a, DeviceTensor):
-            return a, a.ptr, a.ld
-        b = to_device(a)
-        return b, b.ptr, width
-    kx, px, ldx = dev(dx_in, K)
-    kw, pw, _ = dev(dw_in, J)
-    kd, pd, ldd = dev(dy_in, J)
-    ky, py, ldy = dev(y_in, J) if y is not None else (None, None, 0)
-    d_dx = DeviceTensor.empty((M, 1, 1, K), ld=K) if with_dx else None
-    d_dw, d_db = DeviceBuffer(K * J * 4), DeviceBuffer(max(J * 4, 16))
-    ws = DeviceBuffer(lib().xdet_dense_backward_workspace_bytes(M, K, J))
-    check(lib().xdet_dense_backward(px, ldx, pw, py, ldy, pd, ldd, M, K, J, d_dx.ptr if with_dx else None, K, d_dw.ptr,
-                                    d_db.ptr, ws.ptr, stream.handle if stream else None))
-    if d_dx is not None:
-        d_dx._keep = (kx, kw, kd, ky, ws)      # operands and workspace live until the stream has run the call
-    d_dw._keep = (kx, kw, kd, ky, ws)
-    return d_dx, d_dw, d_db
-
-
-def dense_backward(x, w, dy, y=None, with_dx=True, stream=None):
-    """host_dense_backward on the GPU (xdet_dense_backward): x [M,K], w [K,J], dy [M,J], y [M,J] or None as NumPy arrays or
-    DeviceTensors (read in place with their ld; [N,H,W,C] counts as N*H*W rows of C) -> (dx [M,K] or None, dw [K,J],
-    db [J]) as NumPy arrays."""
-    d_dx, d_dw, d_db = dense_backward_device(x, w, dy, y, with_dx, stream)
-    synchronize(stream)
-    J = int((w.shape if isinstance(w, DeviceTensor) else np.shape(w))[-1])
-    K = d_dw.nbytes // (4 * J)
-    dx = to_host(d_dx.ptr, (d_dx.shape[0], K), np.float32, stream) if d_dx is not None else None
-    return dx, to_host(d_dw.ptr, (K, J), np.float32, stream), to_host(d_db.ptr, (J,), np.float32, stream)
-
-
-# ---- the backward of a stride-1 'SAME' convolution (xdet_conv_backward, csrc/conv_backward.hip) ------------------------
-
-def host_conv_backward(x, w, dy, y=None, relu_in=False, dtype=np.float32, with_dx=True):
-    """The NumPy statement of xdet_conv_backward (include/xdet.h) for y = act(conv(xe, w) + b), stride 1, 'SAME', NHWC:
-    x [N,H,W,C], w [kh,kw,C,J] (kh, kw odd), dy [N,H,W,J], y [N,H,W,J] the forward's output after its ReLU (None: no ReLU);
-    xe = x, or with relu_in x where x > 0 and 0 elsewhere -> (dx [N,H,W,C], dw [kh,kw,C,J], db [J]) with g = dy, or dy where
-    y > 0 and 0 elsewhere (an exact zero and a NaN both give 0, in y and in x); with relu_in dx is 0 wherever x > 0 is
-    false.  One matrix product per tap, the taps added in storage order.  dtype float32, or float64: the accuracy yardstick.
-    with_dx=False: dx is None."""
-    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
-    N, H, W, C = x.shape
-    kh, kw, _, J = w.shape
-    g, xe = dy, x
-    with np.errstate(invalid='ignore'):
-        if y is not None:
-            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
-        if relu_in:
-            xe = np.where(x > 0, x, dtype(0))
-    ph, pw = kh // 2, kw // 2
-    border = ((0, 0), (ph, ph), (pw, pw), (0, 0))
-    xp, gp = np.pad(xe, border), np.pad(g, border)
-    g2 = g.reshape(-1, J)
-    dw = np.empty(w.shape, dtype)
-    dx = np.zeros((N * H * W, C), dtype) if with_dx else None
-    for a in range(kh):
-        for b in range(kw):
-            dw[a, b] = np.matmul(xp[:, a:a + H, b:b + W].reshape(-1, C).T, g2)
-            if with_dx:
-                dx += np.matmul(gp[:, 2 * ph - a:2 * ph - a + H, 2 * pw - b:2 * pw - b + W].reshape(-1, J), w[a, b].T)
-    if with_dx:
-        dx = dx.reshape(x.shape)
-        if relu_in:
-            with np.errstate(invalid='ignore'):
-                dx = np.where(x > 0, dx, dtype(0))
-    return dx, dw, g2.sum(axis=0, dtype=dtype)
-
-
-def _nhwc(a, what):
-    """a DeviceTensor or a 4-D array -> (shape, DeviceTensor or f32 array)"""
-    if isinstance(a, DeviceTensor):
-        return tuple(a.shape), a
-    a = np.ascontiguousarray(a, np.float32)
-    if a.ndim != 4:
-        raise InvalidArgumentError(-1, 'conv_backward: %s must have four dimensions, got shape %r' % (what, a.shape))
-    return a.shape, a
-
-
-def _own_dx(dx, shape, who):
-    """a caller's gradient tensor (the dx= of the *_backward_device calls): a DeviceTensor of dx's shape, written with its ld"""
-    if not isinstance(dx, DeviceTensor) or tuple(dx.shape) != tuple(shape):
-        raise InvalidArgumentError(-1, '%s: dx must be a DeviceTensor of shape %r, got %r' % (who, tuple(shape), getattr(dx, 'shape', None)))
-    return dx
-
-
-def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, dx=None, workspace=None):
-    """conv_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
-    dw DeviceBuffer [kh,kw,C,J], db DeviceBuffer [J]); nothing is synchronised.  A DeviceTensor w is [kh,kw,C,J] dense.
-    dx: a DeviceTensor [N,H,W,C] to write instead of a new one (with its ld); workspace: a DeviceBuffer of at least
-    xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw) bytes (default: allocated here) -- a chain of calls on one
-    stream then allocates no activation-sized memory per call."""
-    (N, H, W, C), x_in = _nhwc(x, 'x')
-    (kh, kw, Cw, J), w_in = _nhwc(w, 'w')
-    sd, dy_in = _nhwc(dy, 'dy')
-    bad = Cw != C or sd != (N, H, W, J)
-    if y is not None:
-        sy, y_in = _nhwc(y, 'y')
-        bad = bad or sy != (N, H, W, J)
-    if bad:
-        raise InvalidArgumentError(-1, 'conv_backward: x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J] and y [N,H,W,J] expected, got %r'
-                                   % ([(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else []),))
-    M = N * H * W
-    if (min(M, C, J, kh, kw) <= 0 or kh % 2 == 0 or kw % 2 == 0 or max(kh, kw) > 15 or max(C, J) > 4096
-            or M * max(C, J) >= 2 ** 31):
-        raise InvalidArgumentError(-1, 'conv_backward: N*H*W = %d, C = %d, J = %d, kernel %d x %d (sizes positive, kh and kw odd '
-                                       'and at most 15, C and J at most 4096, N*H*W * max(C, J) below 2^31)' % (M, C, J, kh, kw))
-    if isinstance(w_in, DeviceTensor) and w_in.ld != J:
-        raise InvalidArgumentError(-1, 'conv_backward: w must be dense on the device (ld %d, J = %d)' % (w_in.ld, J))
-
-    def dev(a, width):
-        if isinstance(a, DeviceTensor):
-            return a, a.ptr, a.ld
-        b = to_device(a)
-        return b, b.ptr, width
-    kx, px, ldx = dev(x_in, C)
-    kw_, pw, _ = dev(w_in, J)
-    kd, pd, ldd = dev(dy_in, J)
-    ky, py, ldy = dev(y_in, J) if y is not None else (None, None, 0)
-    d_dx = None
-    if with_dx:
-        d_dx = _own_dx(dx, (N, H, W, C), 'conv_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=ldx)
-    d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
-    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw))
-    check(lib().xdet_conv_backward(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, 1 if relu_in else 0,
-                                   d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, d_db.ptr, ws.ptr,
-                                   stream.handle if stream else None))
-    if d_dx is not None:
-        d_dx._keep = (kx, kw_, kd, ky, ws)     # operands and workspace live until the stream has run the call
-    d_dw._keep = (kx, kw_, kd, ky, ws)
-    return d_dx, d_dw, d_db
-
-
-def conv_backward(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
-    """host_conv_backward on the GPU (xdet_conv_backward): x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J], y [N,H,W,J] or None as
-    NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [kh,kw,C,J], db [J]) as NumPy
-    arrays."""
-    d_dx, d_dw, d_db = conv_backward_device(x, w, dy, y, relu_in, with_dx, stream)
-    synchronize(stream)
-    ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
-    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
-    return dx, to_host(d_dw.ptr, ws, np.float32, stream), to_host(d_db.ptr, (ws[-1],), np.float32, stream)
-
-
-# ---- batch normalisation in both directions and both modes (xdet_batch_norm_*, csrc/batchnorm.hip) ---------------------
-
-def host_batch_norm_forward(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None, relu=False,
-                            dtype=np.float32):
-    """The NumPy statement of xdet_batch_norm_forward (include/xdet.h): x [..., C] (every leading axis is a row axis), gamma,
-    beta, moving_mean, moving_var [C] -> (y like x, save_mean [C], save_invstd [C], new moving_mean, new moving_var).
-    training: mean and the CENTRED variance sum (x - mean)^2 / M of the batch, and TensorFlow's fused update of the moving
-    statistics, moving -= (moving - batch) * (1 - momentum), the variance times M / max(M - 1, 1) first (None: no update,
-    None returned).  Not training: mean and var are the moving statistics, returned as they came.  dtype float32, or
-    float64: the accuracy yardstick."""
-    x = np.asarray(x, dtype)
-    C = x.shape[-1]
-    x2 = x.reshape(-1, C)
-    M = x2.shape[0]
-    gamma, beta = np.asarray(gamma, dtype), np.asarray(beta, dtype)
-    mm = None if moving_mean is None else np.asarray(moving_mean, dtype)
-    mv = None if moving_var is None else np.asarray(moving_var, dtype)
-    if training:
-        mean = x2.sum(axis=0, dtype=dtype) / dtype(M)
-        d = x2 - mean
-        var = (d * d).sum(axis=0, dtype=dtype) / dtype(M)
-        if mm is not None:
-            keep = dtype(1) - dtype(momentum)
-            mm = mm - (mm - mean) * keep
-            mv = mv - (mv - var * (dtype(M) / dtype(max(M - 1, 1)))) * keep
-    else:
-        if mm is None or mv is None:
-            raise InvalidArgumentError(-1, 'batch_norm_forward: training=False needs the moving statistics')
-        mean, var = mm, mv
-    invstd = dtype(1) / np.sqrt(var + dtype(eps))
-    y = ((x2 - mean) * invstd) * gamma + beta
-    if relu:
-        y = np.maximum(y, dtype(0))
-    return y.astype(dtype).reshape(x.shape), mean, invstd.astype(dtype), mm, mv
-
-
-def host_batch_norm_backward(x, y, dy, gamma, save_mean, save_invstd, training=True, dtype=np.float32, with_dx=True):
-    """The NumPy statement of xdet_batch_norm_backward: x, dy [..., C], y like x the forward's output after its ReLU (None: no
-    ReLU), gamma, save_mean, save_invstd [C] -> (dx like x or None, dgamma [C], dbeta [C]) with g = dy, or dy where y > 0
-    and 0 elsewhere (an exact zero and a NaN in y both give 0), xhat = (x - save_mean) * save_invstd, dbeta = sum g,
-    dgamma = sum g xhat, dx = gamma invstd (g - dbeta / M - xhat dgamma / M) in training mode and gamma invstd g otherwise."""
-    x, dy = np.asarray(x, dtype), np.asarray(dy, dtype)
-    C = x.shape[-1]
-    x2, g = x.reshape(-1, C), dy.reshape(-1, C)
-    M = x2.shape[0]
-    gamma, mean, invstd = np.asarray(gamma, dtype), np.asarray(save_mean, dtype), np.asarray(save_invstd, dtype)
-    if y is not None:
-        with np.errstate(invalid='ignore'):
-            g = np.where(np.asarray(y, dtype).reshape(-1, C) > 0, g, dtype(0))
-    xhat = (x2 - mean) * invstd
-    dbeta = g.sum(axis=0, dtype=dtype)
-    dgamma = (g * xhat).sum(axis=0, dtype=dtype)
-    dx = None
-    if with_dx:
-        if training:
-            dx = (gamma * invstd) * ((g - dbeta / dtype(M)) - xhat * (dgamma / dtype(M)))
-        else:
-            dx = (gamma * invstd) * g
-        dx = dx.astype(dtype).reshape(x.shape)
-    return dx, dgamma, dbeta
-
-
-def _bn_rows(a, what):
-    """a DeviceTensor ([N,H,W,C] with its ld) or an array [..., C] -> (shape, M, C, DeviceTensor or f32 array)"""
-    if isinstance(a, DeviceTensor):
-        return tuple(a.shape), int(np.prod(a.shape[:-1])), int(a.shape[-1]), a
-    a = np.ascontiguousarray(a, np.float32)
-    if a.ndim < 2:
-        raise InvalidArgumentError(-1, 'batch_norm: %s must have rows of channels, got shape %r' % (what, a.shape))
-    return a.shape, int(np.prod(a.shape[:-1])), a.shape[-1], a
-
-
-def _bn_vec(a, C, what):
-    """a [C] vector: a DeviceBuffer / DeviceTensor stays, anything else is copied to the device -> (keep-alive, pointer)"""
-    if isinstance(a, (DeviceBuffer, DeviceTensor)):
-        return a, a.ptr
-    a = np.ascontiguousarray(a, np.float32).reshape(-1)
-    if a.shape[0] != C:
-        raise InvalidArgumentError(-1, 'batch_norm: %s must hold %d values, got %d' % (what, C, a.shape[0]))
-    b = to_device(a)
-    return b, b.ptr
-
-
-def _bn_check_sizes(M, C, who):
-    if min(M, C) <= 0 or C > 4096 or M * C >= 2 ** 31:
-        raise InvalidArgumentError(-1, '%s: M = %d, C = %d (positive, C at most 4096, M * C below 2^31)' % (who, M, C))
-
-
-def _bn_dev(a, C):
-    if isinstance(a, DeviceTensor):
-        return a, a.ptr, a.ld
-    b = to_device(a)
-    return b, b.ptr, C
-
-
-def batch_norm_forward_device(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None,
-                              relu=False, stream=None):
-    """batch_norm_forward with the results left on the GPU: (y DeviceTensor with x's shape and ld (C for a NumPy x), save_mean,
-    save_invstd, moving_mean, moving_var as DeviceBuffers [C]; the moving ones None when none were given); nothing is
-    synchronised.  Moving statistics given as DeviceBuffers are updated in place (training) and returned; NumPy ones are
-    copied to the device first."""
-    shape, M, C, x_in = _bn_rows(x, 'x')
-    _bn_check_sizes(M, C, 'batch_norm_forward')
-    if (moving_mean is None) != (moving_var is None) or (not training and moving_mean is None):
-        raise InvalidArgumentError(-1, 'batch_norm_forward: training=False needs both moving statistics; training mode takes '
-                                       'both or neither')
-    kx, px, ldx = _bn_dev(x_in, C)
-    kg, pg = _bn_vec(gamma, C, 'gamma')
-    kb, pb = _bn_vec(beta, C, 'beta')
-    d_mm, pmm = _bn_vec(moving_mean, C, 'moving_mean') if moving_mean is not None else (None, None)
-    d_mv, pmv = _bn_vec(moving_var, C, 'moving_var') if moving_var is not None else (None, None)
-    d_y = DeviceTensor.empty(shape if len(shape) == 4 else (M, 1, 1, C), ld=ldx)
-    d_mean, d_inv = DeviceBuffer(max(C * 4, 16)), DeviceBuffer(max(C * 4, 16))
-    ws = DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
-    check(lib().xdet_batch_norm_forward(px, ldx, M, C, pg, pb, float(eps), 1 if training else 0, float(momentum), pmm, pmv,
-                                        1 if relu else 0, d_y.ptr, d_y.ld, d_mean.ptr, d_inv.ptr, ws.ptr,
-                                        stream.handle if stream else None))
-    d_mean._keep = (kx, kg, kb, ws, d_y)         # operands and workspace live until the stream has run the call
-    return d_y, d_mean, d_inv, d_mm, d_mv
-
-
-def batch_norm_forward(x, gamma, beta, eps, training=True, momentum=0.997, moving_mean=None, moving_var=None, relu=False,
-                       stream=None):
-    """host_batch_norm_forward on the GPU (xdet_batch_norm_forward): x [..., C] as a NumPy array or a DeviceTensor (read in
-    place with its ld) -> (y with x's shape, save_mean, save_invstd, moving_mean, moving_var) as NumPy arrays (the moving
-    ones None when none were given)."""
-    d_y, d_mean, d_inv, d_mm, d_mv = batch_norm_forward_device(x, gamma, beta, eps, training, momentum, moving_mean,
-                                                                moving_var, relu, stream)
-    synchronize(stream)
-    shape = tuple(x.shape) if isinstance(x, DeviceTensor) else np.shape(x)
-    C = shape[-1]
-    y = to_host(d_y.ptr, (int(np.prod(shape[:-1])), d_y.ld), np.float32, stream)[:, :C].reshape(shape)
-    vec = lambda b: to_host(b.ptr, (C,), np.float32, stream) if b is not None else None
-    return np.ascontiguousarray(y), vec(d_mean), vec(d_inv), vec(d_mm), vec(d_mv)
-
-
-def batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None, dx=None,
-                               workspace=None):
-    """batch_norm_backward with the results left on the GPU: (dx DeviceTensor with x's shape and ld (C for a NumPy x) or None,
-    dgamma DeviceBuffer [C], dbeta DeviceBuffer [C]); nothing is synchronised.  dx: a DeviceTensor of x's shape to write
-    instead of a new one (with its ld; it must not overlap x); workspace: a DeviceBuffer of at least
-    xdet_batch_norm_workspace_bytes(M, C) bytes (default: allocated here)."""
-    shape, M, C, x_in = _bn_rows(x, 'x')
-    sd, Md, Cd, dy_in = _bn_rows(dy, 'dy')
-    bad = (Md, Cd) != (M, C)
-    if y is not None:
-        sy, My, Cy, y_in = _bn_rows(y, 'y')
-        bad = bad or (My, Cy) != (M, C)
-    if bad:
-        raise InvalidArgumentError(-1, 'batch_norm_backward: x, dy and y of one shape expected, got %r'
-                                   % ([shape, sd] + ([sy] if y is not None else []),))
-    _bn_check_sizes(M, C, 'batch_norm_backward')
-    kx, px, ldx = _bn_dev(x_in, C)
-    kd, pd, ldd = _bn_dev(dy_in, C)
-    ky, py, ldy = _bn_dev(y_in, C) if y is not None else (None, None, 0)
-    kg, pg = _bn_vec(gamma, C, 'gamma')
-    km, pm = _bn_vec(save_mean, C, 'save_mean')
-    ki, pi = _bn_vec(save_invstd, C, 'save_invstd')
-    d_dx = None
-    if with_dx:
-        shape4 = shape if len(shape) == 4 else (M, 1, 1, C)
-        d_dx = _own_dx(dx, shape4, 'batch_norm_backward') if dx is not None else DeviceTensor.empty(shape4, ld=ldx)
-    d_dg, d_db = DeviceBuffer(max(C * 4, 16)), DeviceBuffer(max(C * 4, 16))
-    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_batch_norm_workspace_bytes(M, C))
-    check(lib().xdet_batch_norm_backward(px, ldx, py, ldy, pd, ldd, M, C, pg, pm, pi, 1 if training else 0,
-                                         d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dg.ptr, d_db.ptr, ws.ptr,
-                                         stream.handle if stream else None))
-    d_dg._keep = (kx, kd, ky, kg, km, ki, ws)    # operands and workspace live until the stream has run the call
-    return d_dx, d_dg, d_db
-
-
-def batch_norm_backward(x, y, dy, gamma, save_mean, save_invstd, training=True, with_dx=True, stream=None):
-    """host_batch_norm_backward on the GPU (xdet_batch_norm_backward): NumPy arrays or DeviceTensors (read in place with their
-    ld) -> (dx with x's shape or None, dgamma [C], dbeta [C]) as NumPy arrays."""
-    d_dx, d_dg, d_db = batch_norm_backward_device(x, y, dy, gamma, save_mean, save_invstd, training, with_dx, stream)
-    synchronize(stream)
-    shape = tuple(x.shape) if isinstance(x, DeviceTensor) else np.shape(x)
-    C = shape[-1]
-    dx = None
-    if d_dx is not None:
-        dx = np.ascontiguousarray(to_host(d_dx.ptr, (int(np.prod(shape[:-1])), d_dx.ld), np.float32, stream)[:, :C].reshape(shape))
-    return dx, to_host(d_dg.ptr, (C,), np.float32, stream), to_host(d_db.ptr, (C,), np.float32, stream)
-
-
-# ---- the backward of the depthwise 3x3 conv, and the row add (xdet_depthwise_backward / xdet_add_rows,
-#      csrc/depthwise_backward.hip) ------------------------------------------------------------------------------------
-
-def host_depthwise_backward(x, k, dy, dilation=1, relu_in=False, dtype=np.float32, with_dx=True):
-    """The NumPy statement of xdet_depthwise_backward (include/xdet.h) for y = depthwise3x3(xe, k), stride 1, 'SAME', NHWC:
-    x, dy [N,H,W,C], k [3,3,C,1], dilation d; xe = x, or with relu_in x where x > 0 and 0 elsewhere -> (dx [N,H,W,C],
-    dw [3,3,C,1]): dx[n,h,w,c] = sum over taps of dy[n, h - (a-1)d, w - (b-1)d, c] * k[a,b,c], the taps in storage order, each
-    product rounded and then added (the op's own order: in float32 dx is the op's dx bit for bit, but for the sign of a
-    zero), 0 wherever x > 0 is false with relu_in; dw[a,b,c] = sum over pixels of xe[n, h + (a-1)d, w + (b-1)d, c] *
-    dy[n,h,w,c], NumPy's sequential sum over the pixels.  Terms outside the image are absent.  dtype float32, or float64: the
-    accuracy yardstick.  with_dx=False: dx is None."""
-    x, k, dy = np.asarray(x, dtype), np.asarray(k, dtype), np.asarray(dy, dtype)
-    N, H, W, C = x.shape
-    d = int(dilation)
-    xe = x
-    if relu_in:
-        with np.errstate(invalid='ignore'):
-            xe = np.where(x > 0, x, dtype(0))
-    border = ((0, 0), (d, d), (d, d), (0, 0))
-    xp, gp = np.pad(xe, border), np.pad(dy, border)
-    dw = np.empty((3, 3, C, 1), dtype)
-    dx = np.zeros(x.shape, dtype) if with_dx else None
-    for a in range(3):
-        for b in range(3):
-            dw[a, b, :, 0] = (xp[:, a * d:a * d + H, b * d:b * d + W] * dy).reshape(-1, C).sum(axis=0, dtype=dtype)
-            if with_dx:
-                dx += gp[:, (2 - a) * d:(2 - a) * d + H, (2 - b) * d:(2 - b) * d + W] * k[a, b, :, 0]
-    if with_dx and relu_in:
-        with np.errstate(invalid='ignore'):
-            dx = np.where(x > 0, dx, dtype(0))
-    return dx, dw
-
-
-def depthwise_backward_device(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None, workspace=None, dx=None):
-    """depthwise_backward with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or None,
-    dw DeviceBuffer [3,3,C,1]); nothing is synchronised.  A DeviceTensor k is [3,3,C,1] dense (ld 1).  workspace: a
-    DeviceBuffer of at least xdet_depthwise_backward_workspace_bytes(N, H, W, C) bytes (default: allocated here).  dx: a
-    DeviceTensor [N,H,W,C] to write instead of a new one (with its ld; it must not overlap x or dy)."""
-    (N, H, W, C), x_in = _nhwc(x, 'x')
-    sk, k_in = _nhwc(k, 'k')
-    sd, dy_in = _nhwc(dy, 'dy')
-    if tuple(sk) != (3, 3, C, 1) or tuple(sd) != (N, H, W, C):
-        raise InvalidArgumentError(-1, 'depthwise_backward: x [N,H,W,C], k [3,3,C,1] and dy [N,H,W,C] expected, got %r'
-                                   % ([(N, H, W, C), tuple(sk), tuple(sd)],))
-    M = N * H * W
-    if min(M, C) <= 0 or C > 4096 or M * C >= 2 ** 31 or dilation not in (1, 2):
-        raise InvalidArgumentError(-1, 'depthwise_backward: N*H*W = %d, C = %d, dilation %r (sizes positive, C at most 4096, '
-                                       'N*H*W * C below 2^31, dilation 1 or 2)' % (M, C, dilation))
-    if isinstance(k_in, DeviceTensor) and k_in.ld != 1:
-        raise InvalidArgumentError(-1, 'depthwise_backward: k must be dense on the device (ld %d)' % k_in.ld)
-
-    def dev(a, width):
-        if isinstance(a, DeviceTensor):
-            return a, a.ptr, a.ld
-        b = to_device(a)
-        return b, b.ptr, width
-    kx, px, ldx = dev(x_in, C)
-    kk, pk, _ = dev(k_in, 1)
-    kd, pd, ldd = dev(dy_in, C)
-    d_dx = None
-    if with_dx:
-        d_dx = _own_dx(dx, (N, H, W, C), 'depthwise_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=ldx)
-    d_dw = DeviceBuffer(max(9 * C * 4, 16))
-    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_depthwise_backward_workspace_bytes(N, H, W, C))
-    check(lib().xdet_depthwise_backward(px, ldx, pk, pd, ldd, N, H, W, C, int(dilation), 1 if relu_in else 0,
-                                        d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, ws.ptr,
-                                        stream.handle if stream else None))
-    if d_dx is not None:
-        d_dx._keep = (kx, kk, kd, ws)          # operands and workspace live until the stream has run the call
-    d_dw._keep = (kx, kk, kd, ws)
-    return d_dx, d_dw
-
-
-def depthwise_backward(x, k, dy, dilation=1, relu_in=False, with_dx=True, stream=None):
-    """host_depthwise_backward on the GPU (xdet_depthwise_backward): x, dy [N,H,W,C] and k [3,3,C,1] as NumPy arrays or
-    DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [3,3,C,1]) as NumPy arrays."""
-    d_dx, d_dw = depthwise_backward_device(x, k, dy, dilation, relu_in, with_dx, stream)
-    synchronize(stream)
-    C = int((x.shape if isinstance(x, DeviceTensor) else np.shape(x))[-1])
-    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
-    return dx, to_host(d_dw.ptr, (3, 3, C, 1), np.float32, stream)
-
-
-def add_rows_device(a, b, out=None, stream=None):
-    """out = a + b on the GPU (xdet_add_rows): a, b DeviceTensors of one shape, each read with its own ld (NumPy arrays are
-    copied to the device first); out: a DeviceTensor of that shape -- it may be a itself -- or None: a new one with a's ld.
-    -> out; nothing is synchronised."""
-    sa, a_in = _nhwc(a, 'a')
-    sb, b_in = _nhwc(b, 'b')
-    if tuple(sa) != tuple(sb) or (out is not None and (not isinstance(out, DeviceTensor) or tuple(out.shape) != tuple(sa))):
-        raise InvalidArgumentError(-1, 'add_rows: a, b and out of one shape expected, got %r'
-                                   % ([tuple(sa), tuple(sb), getattr(out, 'shape', None)],))
-    M, C = int(np.prod(sa[:3])), int(sa[3])
-    if min(M, C) <= 0 or M * C >= 2 ** 31:
-        raise InvalidArgumentError(-1, 'add_rows: %d rows of %d channels (positive, their product below 2^31)' % (M, C))
-    ta = a_in if isinstance(a_in, DeviceTensor) else DeviceTensor.from_numpy(a_in)
-    tb = b_in if isinstance(b_in, DeviceTensor) else DeviceTensor.from_numpy(b_in)
-    if out is None:
-        out = DeviceTensor.empty(sa, ld=ta.ld)
-    check(lib().xdet_add_rows(ta.ptr, ta.ld, tb.ptr, tb.ld, out.ptr, out.ld, M, C, stream.handle if stream else None))
-    # operands live until the stream has run the call (on top of what out already keeps alive)
-    out._keep = (getattr(out, '_keep', None),) + tuple(t for t in (ta, tb) if t is not out)
-    return out
-
-
-# ---- the backward of max_pooling2d(3, 2, 'same') and the stride-2 gather / scatter of a 1x1 / stride-2 projection
-#      (xdet_maxpool3x3s2_backward / xdet_subsample2 / xdet_add_upsample2, csrc/pool_backward.hip) --------------------------
-
-def _same_pad_front(n):
-    """TensorFlow's 'SAME' for a 3-wide window at stride 2: (outputs, padding in front): the smaller half of the total"""
-    o = -(-n // 2)
-    return o, max((o - 1) * 2 + 3 - n, 0) // 2
-
-
-def host_max_pool_backward(x, dy, dtype=np.float32):
-    """The NumPy statement of xdet_maxpool3x3s2_backward (include/xdet.h): x [N,H,W,C], the input of
-    max_pooling2d(3, 2, 'same'), dy [N,ceil(H/2),ceil(W/2),C] -> dx [N,H,W,C].  Every window sends its dy to its first maximum
-    in row-major window order (strict > against the running best, which starts at the window's first in-image element; padded
-    positions are absent), and the shares a pixel receives are added to 0 in ascending (oh, ow) order, each add rounded.
-    dtype float32: the op's dx bit for bit; float64: the yardstick."""
-    x, dy = np.asarray(x, dtype), np.asarray(dy, dtype)
-    N, H, W, C = x.shape
-    (Ho, pt), (Wo, pl) = _same_pad_front(H), _same_pad_front(W)
-    if dy.shape != (N, Ho, Wo, C):
-        raise InvalidArgumentError(-1, 'max_pool_backward: x %r needs dy %r, got %r' % (x.shape, (N, Ho, Wo, C), dy.shape))
-    best = np.zeros((N, Ho, Wo, C), dtype)
-    bh, bw = np.zeros((N, Ho, Wo, C), np.intp), np.zeros((N, Ho, Wo, C), np.intp)
-    has = np.zeros((1, Ho, Wo, 1), bool)
-    for a in range(3):
-        r = 2 * np.arange(Ho) - pt + a
-        rv, rc = (r >= 0) & (r < H), np.clip(r, 0, H - 1)
-        for b in range(3):
-            c = 2 * np.arange(Wo) - pl + b
-            cv, cc = (c >= 0) & (c < W), np.clip(c, 0, W - 1)
-            live = (rv[:, None] & cv[None, :])[None, :, :, None]
-            v = x[:, rc][:, :, cc]
-            with np.errstate(invalid='ignore'):
-                take = live & (~has | (v > best))
-            best = np.where(take, v, best)
-            bh = np.where(take, rc[None, :, None, None], bh)
-            bw = np.where(take, cc[None, None, :, None], bw)
-            has = has | live
-    dx = np.zeros(x.shape, dtype)
-    n, c = np.arange(N)[:, None, None, None], np.arange(C)[None, None, None, :]
-    # unbuffered and in the index arrays' order: for one (n, pixel, c) the windows arrive ascending in (oh, ow)
-    np.add.at(dx, tuple(np.broadcast_arrays(n, bh, bw, c)), dy)
-    return dx
-
-
-def host_subsample2(x, dtype=np.float32):
-    """x[:, ::2, ::2]: what a 1x1 / stride-2 'SAME' conv reads of x [N,H,W,C] -> [N,ceil(H/2),ceil(W/2),C]"""
-    return np.ascontiguousarray(np.asarray(x, dtype)[:, ::2, ::2])
-
-
-def host_add_upsample2(a, b, dtype=np.float32):
-    """a [N,H,W,C] + the adjoint of host_subsample2 applied to b [N,ceil(H/2),ceil(W/2),C]: b added at the pixels whose h and
-    w are both even, a unchanged (its bits) everywhere else"""
-    out = np.array(a, dtype)
-    b = np.asarray(b, dtype)
-    if out.ndim != 4 or b.shape != out[:, ::2, ::2].shape:
-        raise InvalidArgumentError(-1, 'add_upsample2: a %r needs b %r, got %r' % (out.shape, out[:, ::2, ::2].shape, b.shape))
-    out[:, ::2, ::2] += b
-    return out
-
-
-def _pool_sizes(who, N, H, W, C):
-    if min(N, H, W, C) <= 0 or C > 4096 or N * H * W * C >= 2 ** 31:
-        raise InvalidArgumentError(-1, '%s: [%d,%d,%d,%d] (sizes positive, C at most 4096, N*H*W*C below 2^31)' % (who, N, H, W, C))
-
-
-def _pool_dev(a):
-    return a if isinstance(a, DeviceTensor) else DeviceTensor.from_numpy(a)
-
-
-def max_pool_backward_device(x, dy, dx=None, stream=None):
-    """max_pool_backward with the result left on the GPU: dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x); nothing is
-    synchronised.  x, dy: NumPy arrays or DeviceTensors read in place with their ld.  dx: a DeviceTensor [N,H,W,C] to write
-    instead of a new one (with its ld; it must not overlap x or dy)."""
-    (N, H, W, C), x_in = _nhwc(x, 'x')
-    sd, dy_in = _nhwc(dy, 'dy')
-    if tuple(sd) != (N, -(-H // 2), -(-W // 2), C):
-        raise InvalidArgumentError(-1, 'max_pool_backward: x [N,H,W,C] and dy [N,ceil(H/2),ceil(W/2),C] expected, got %r'
-                                   % ([(N, H, W, C), tuple(sd)],))
-    _pool_sizes('max_pool_backward', N, H, W, C)
-    tx, td = _pool_dev(x_in), _pool_dev(dy_in)
-    d_dx = _own_dx(dx, (N, H, W, C), 'max_pool_backward') if dx is not None else DeviceTensor.empty((N, H, W, C), ld=tx.ld)
-    check(lib().xdet_maxpool3x3s2_backward(tx.ptr, tx.ld, td.ptr, td.ld, N, H, W, C, d_dx.ptr, d_dx.ld,
-                                           stream.handle if stream else None))
-    d_dx._keep = (tx, td)                      # operands live until the stream has run the call
-    return d_dx
-
-
-def max_pool_backward(x, dy, stream=None):
-    """host_max_pool_backward on the GPU (xdet_maxpool3x3s2_backward) -> dx [N,H,W,C] as a NumPy array"""
-    d_dx = max_pool_backward_device(x, dy, stream=stream)
-    synchronize(stream)
-    return d_dx.numpy(stream=stream)
-
-
-def subsample2_device(x, out=None, stream=None):
-    """host_subsample2 on the GPU (xdet_subsample2): x [N,H,W,C] as a NumPy array or a DeviceTensor read with its ld -> out
-    DeviceTensor [N,ceil(H/2),ceil(W/2),C] (a caller's, written with its ld, or a new dense one); nothing is synchronised."""
-    (N, H, W, C), x_in = _nhwc(x, 'x')
-    so = (N, -(-H // 2), -(-W // 2), C)
-    if out is not None and (not isinstance(out, DeviceTensor) or tuple(out.shape) != so):
-        raise InvalidArgumentError(-1, 'subsample2: out must be a DeviceTensor of shape %r, got %r' % (so, getattr(out, 'shape', None)))
-    _pool_sizes('subsample2', N, H, W, C)
-    tx = _pool_dev(x_in)
-    if out is None:
-        out = DeviceTensor.empty(so)
-    check(lib().xdet_subsample2(tx.ptr, tx.ld, N, H, W, C, out.ptr, out.ld, stream.handle if stream else None))
-    out._keep = (tx,)
-    return out
-
-
-def add_upsample2_device(a, b, out=None, stream=None):
-    """host_add_upsample2 on the GPU (xdet_add_upsample2): a [N,H,W,C], b [N,ceil(H/2),ceil(W/2),C], each read with its own ld
-    (NumPy arrays are copied to the device first); out: a DeviceTensor of a's shape -- it may be a itself -- or None: a new
-    one with a's ld.  -> out; nothing is synchronised."""
-    (N, H, W, C), a_in = _nhwc(a, 'a')
-    sb, b_in = _nhwc(b, 'b')
-    if tuple(sb) != (N, -(-H // 2), -(-W // 2), C) or (out is not None and (not isinstance(out, DeviceTensor)
-                                                                             or tuple(out.shape) != (N, H, W, C))):
-        raise InvalidArgumentError(-1, 'add_upsample2: a [N,H,W,C], b [N,ceil(H/2),ceil(W/2),C] and out like a expected, got %r'
-                                   % ([(N, H, W, C), tuple(sb), getattr(out, 'shape', None)],))
-    _pool_sizes('add_upsample2', N, H, W, C)
-    ta, tb = _pool_dev(a_in), _pool_dev(b_in)
-    if out is None:
-        out = DeviceTensor.empty((N, H, W, C), ld=ta.ld)
-    check(lib().xdet_add_upsample2(ta.ptr, ta.ld, tb.ptr, tb.ld, N, H, W, C, out.ptr, out.ld, stream.handle if stream else None))
-    out._keep = (getattr(out, '_keep', None),) + tuple(t for t in (ta, tb) if t is not out)
-    return out
+# the training path's doors (the *_backward ops, batch norm, add_rows, subsample2, add_upsample2) are written in xdet/train_ops.py
+from .train_ops import *              # noqa: E402,F401,F403  (their names are this module's too)

@@ -12,6 +12,7 @@ import contextlib
 
 import numpy as np
 
+from . import train_ops, ops
 from ._lib import lib, check, XdetError, InvalidArgumentError
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, _det, _sync
 
@@ -159,8 +160,7 @@ class BatchNorm(object):
 
     def backward(self, d, z, y, dy, dx=None, workspace=None):
         """-> (dz, dgamma, dbeta) on the device; y: the output to mask by where a ReLU follows, else None"""
-        from . import ops
-        return ops.batch_norm_backward_device(z, y, dy, self.gamma, self.save_mean, self.save_invstd, True, stream=d.stream,
+        return train_ops.batch_norm_backward_device(z, y, dy, self.gamma, self.save_mean, self.save_invstd, True, stream=d.stream,
                                               dx=dx, workspace=workspace)
 
     def views(self, out, prefix=None):
@@ -178,7 +178,6 @@ class SepUnit(object):
     __slots__ = ('name', 'dil', 'relu_in', 'relu_out', 'dw', 'pw', 'K_dw', 'K_pw', 'bn', 't', 'z', 'y')
 
     def __init__(self, weights, name, dil, relu_in, relu_out, pw, B, H, W, own_y):
-        from . import ops
         kd = np.ascontiguousarray(weights[name + '/depthwise_kernel'], np.float32)
         kp = np.ascontiguousarray(weights[name + '/pointwise_kernel'], np.float32)
         C, J = kp.shape[2], kp.shape[3]
@@ -201,13 +200,12 @@ class SepUnit(object):
         on the detector's stream, on the kept z and t of x's images.  dev: gains the four weight gradients as (DeviceBuffer,
         shape) under the checkpoint's names.  into: {'dz', 'dt', 'dx': DeviceTensors to write, 'ws_bn', 'ws_conv': workspaces}
         -- without it every call allocates its own.  -> (dx, dt, dz)"""
-        from . import ops
         into = into or {}
         n, name = x.shape[0], self.name
         dz, dgamma, dbeta = self.bn.backward(d, _first(self.z, n), y, dy, into.get('dz'), into.get('ws_bn'))
-        dt, dkp, _ = ops.conv_backward_device(_first(self.t, n), self.K_pw, dz, None, stream=d.stream, dx=into.get('dt'),
+        dt, dkp, _ = train_ops.conv_backward_device(_first(self.t, n), self.K_pw, dz, None, stream=d.stream, dx=into.get('dt'),
                                               workspace=into.get('ws_conv'))
-        dx, dkd = ops.depthwise_backward_device(x, self.K_dw, dt, self.dil, self.relu_in, stream=d.stream, workspace=ws_dw,
+        dx, dkd = train_ops.depthwise_backward_device(x, self.K_dw, dt, self.dil, self.relu_in, stream=d.stream, workspace=ws_dw,
                                                 dx=into.get('dx'))
         J = self.K_pw.shape[3]
         dev[name + '/depthwise_kernel'], dev[name + '/pointwise_kernel'] = (dkd, self.K_dw.shape), (dkp, self.K_pw.shape)
@@ -222,7 +220,6 @@ class SepUnit(object):
 
 def _pointwise_layers(weights, names):
     """{name: the 1x1 conv of <name>/pointwise_kernel in split precision, f32 out, no scale or shift}"""
-    from . import ops
     with _f16x3():
         return {n: ops.Conv2D(np.ascontiguousarray(weights[n + '/pointwise_kernel'], np.float32)) for n in names}
 
@@ -234,7 +231,6 @@ class Projection(object):
     __slots__ = ('name', 'conv', 'K', 'bn', 'z', 'r')
 
     def __init__(self, weights, name, bn_name, B, H, W):
-        from . import ops
         k = np.ascontiguousarray(weights[name + '/kernel'], np.float32)
         with _f16x3():
             self.conv = ops.Conv2D(k)
@@ -250,10 +246,9 @@ class Projection(object):
         """g = d loss / d r -> d loss / d x through the batch norm and the conv (its bias gradient dropped), on the kept z of x's
         images; dev gains '<conv>/kernel', '<bn>/gamma' and '<bn>/beta'.  into: {'dz', 'dx': DeviceTensors to write, 'ws_bn',
         'ws_conv': workspaces} -- without it every call allocates its own.  -> (dx, dzr)"""
-        from . import ops
         into = into or {}
         dzr, dgamma, dbeta = self.bn.backward(d, _first(self.z, x.shape[0]), None, g, into.get('dz'), into.get('ws_bn'))
-        dx, dk, _ = ops.conv_backward_device(x, self.K, dzr, None, stream=d.stream, dx=into.get('dx'), workspace=into.get('ws_conv'))
+        dx, dk, _ = train_ops.conv_backward_device(x, self.K, dzr, None, stream=d.stream, dx=into.get('dx'), workspace=into.get('ws_conv'))
         co = self.K.shape[3]
         dev[self.name + '/kernel'] = (dk, self.K.shape)
         dev[self.bn.name + '/gamma'], dev[self.bn.name + '/beta'] = (dgamma, (co,)), (dbeta, (co,))
@@ -278,7 +273,6 @@ class LargeSepState(object):
     for the backward, the batch norm (eps 1e-5, momentum 0.997), the kept t and z and the BN workspace"""
 
     def __init__(self, d, weights):
-        from . import ops
         ka, ba, kb, bb = merge_large_sep({k: np.ascontiguousarray(weights[k], np.float32) for k in LARGE_SEP_VARIABLES})
         with _f16x3():
             self.conv_a, self.conv_b = ops.Conv2D(ka, shift=ba), ops.Conv2D(kb, shift=bb)
@@ -512,7 +506,6 @@ def head_backward(loss_func, to_feat=False):
     order-exact PsRoiAlign gradient on the net's `proposals` and the argmax get_head kept -- on the same stream, with no host
     round trip in between, and the dict gains 'feat': d loss / d feat as a DeviceTensor [N,H,W,C] with the `feat` buffer's
     ld (padding channels zero), what the large-separable backward will read."""
-    from . import ops
     d = _det()
     if to_feat and not d.pool_index:
         raise InvalidArgumentError(-1, 'head_backward: to_feat=True needs a detector built with pool_index=True (the head '
@@ -540,8 +533,8 @@ def head_backward(loss_func, to_feat=False):
     if to_feat:                                    # (allocated ahead of the launches, not between the last two)
         fb = d.buffer('feat', n)
         d_feat = DeviceTensor.empty(fb.shape, ld=fb.ld)
-    dx1, dw1, db1 = ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
-    dx0, dw0, db0 = ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
+    dx1, dw1, db1 = train_ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
+    dx0, dw0, db0 = train_ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
     if to_feat:
         check(lib().xdet_net_head_pool_backward(d.handle, n, dx0.ptr, dx0.ld, d_feat.ptr, d.stream.handle))
     _sync(d)
@@ -566,7 +559,6 @@ def rpn_backward(rpn_loss_result):
     with no host round trip in between.  -> a dict with the six gradients under the checkpoint's variable names
     (rpn_head/{conv2d,conv2d_1,conv2d_2}/{kernel,bias}, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with
     `mid_x`'s ld (zero where mid_x <= 0) and 'rpn_hidden': d loss / d rpn_hidden (in front of the ReLU mask) [N,h,w,512]."""
-    from . import ops
     d = _det()
     if not d.rpn_hidden:
         raise InvalidArgumentError(-1, 'rpn_backward: needs a detector built with rpn_hidden=True (the RPN conv kept no f32 '
@@ -591,9 +583,9 @@ def rpn_backward(rpn_loss_result):
                               DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
     w0, w1 = d._rpn_kernels_dev
     hid, mid_x = d.buffer('rpn_hidden', n), d.buffer('mid_x', n)
-    dx1, dw1, db1 = ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
+    dx1, dw1, db1 = train_ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
     d_hid = DeviceTensor(dx1.ptr, hid.shape, dx1.ld, owner=dx1)
-    dx0, dw0, db0 = ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
+    dx0, dw0, db0 = train_ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
     _sync(d)
     J = w0.shape[3]
     kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
@@ -618,14 +610,13 @@ def large_sep_backward(d_feat):
     d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read).  Refused once a new eval
     body (set_images, forward, calibrate, detect_images) or a training forward of one of the flows has run since the block's
     own: the kept t and z belong to another `out`."""
-    from . import ops
     d = _det()
     s, n = _stage(d, LARGE_SEP, 'large_sep_backward', 'large_sep_kernel(..., is_training=True)')
     feat, out = d.buffer('feat', n), d.buffer('out', n)
     _check_grad('large_sep_backward', 'd_feat', d_feat, feat)
     dz, dgamma, dbeta = s.bn.backward(d, _first(s.z, n), feat, d_feat)
-    dt, dkb, dbb = ops.conv_backward_device(_first(s.t, n), s.K_b, dz, None, stream=d.stream)
-    d_out, dka, dba = ops.conv_backward_device(out, s.K_a, dt, None, stream=d.stream)
+    dt, dkb, dbb = train_ops.conv_backward_device(_first(s.t, n), s.K_b, dz, None, stream=d.stream)
+    d_out, dka, dba = train_ops.conv_backward_device(out, s.K_a, dt, None, stream=d.stream)
     _sync(d)
     co, mid2 = s.K_b.shape[3], s.K_a.shape[3]
     grads = split_large_sep_grads(to_host(dka.ptr, s.K_a.shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s.K_b.shape),
@@ -688,7 +679,6 @@ def exit_flow_backward(d_out, d_mid=None):
     tensor), 'dw/<unit>' = d loss / d (the unit's depthwise output) and 'z/<unit>', 'z/conv2d_4' = d loss / d (a batch norm's
     input) likewise.  Refused once a new eval body (set_images, forward, calibrate, detect_images) or a training forward of
     the middle or the entry flow has run since exit_flow_train(): the kept tensors belong to another `mid_x`."""
-    from . import ops
     d = _det()
     e, n = _stage(d, EXIT, 'exit_flow_backward', 'exit_flow_train()')
     out, mid_x = d.buffer('out', n), d.buffer('mid_x', n)
@@ -708,9 +698,9 @@ def exit_flow_backward(d_out, d_mid=None):
     share_a, dzr = e.proj.backward(d, mid_x, d_b2, dev)
     d_a = unit_backward(u2, a, None, d_b2)
     share_b = unit_backward(u1, mid_x, None, d_a)
-    mid = ops.add_rows_device(share_b, share_a, stream=d.stream)
+    mid = train_ops.add_rows_device(share_b, share_a, stream=d.stream)
     if d_mid is not None:
-        ops.add_rows_device(mid, d_mid, out=mid, stream=d.stream)
+        train_ops.add_rows_device(mid, d_mid, out=mid, stream=d.stream)
     _sync(d)
     _download(dev, grads)
     grads.update({'mid': mid, 'mid_A': share_a, 'mid_B': share_b, 'b2': d_b2, 'r': d_b2, 'c3': d_c3, 'a': d_a, 'z/conv2d_4': dzr})
@@ -772,7 +762,6 @@ def middle_flow_backward(d_mid, intermediates=False):
     d loss / d (its batch norm's input) and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>' (the units' input gradients; d1 is the
     addend of the join), each in a tensor of its own.  Refused once a new eval body (set_images, forward, calibrate,
     detect_images) or entry_flow_train() has run since middle_flow_train(): the kept tensors belong to another `entry_x`."""
-    from . import ops
     d = _det()
     m, n = _stage(d, MIDDLE, 'middle_flow_backward', 'middle_flow_train()')
     mid_x, entry = d.buffer('mid_x', n), d.buffer('entry_x', n)
@@ -798,7 +787,7 @@ def middle_flow_backward(d_mid, intermediates=False):
             if intermediates:
                 into.update(dz=grads['z/' + u.name], dt=grads['dw/' + u.name], dx=grads['d%d/block%d' % (i, blk.b)])
             dy, _, _ = u.backward(d, xin, None, dy, dev, m.ws_dw, into)
-        g = ops.add_rows_device(dy, g, out=grads[key(blk)], stream=d.stream)
+        g = train_ops.add_rows_device(dy, g, out=grads[key(blk)], stream=d.stream)
     _sync(d)
     _release(list(rot.values()) + list(grads.values()))
     _download(dev, grads)
@@ -864,7 +853,6 @@ def entry_flow_backward(d_entry, intermediates=False):
     d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own.  Refused
     once a new eval body (set_images, forward, calibrate, detect_images) has run since entry_flow_train(): the kept tensors
     belong to another `stem_out`."""
-    from . import ops
     d = _det()
     e, n = _stage(d, ENTRY, 'entry_flow_backward', 'entry_flow_train()')
     _check_grad('entry_flow_backward', 'd_entry', d_entry, d.buffer('entry_x', n))
@@ -890,10 +878,10 @@ def entry_flow_backward(d_entry, intermediates=False):
         (u1, u2), rot = blk.units, inner[blk.b]
         ws = {'ws_bn': e.ws_bn, 'ws_conv': e.ws_conv}
         dxs, _ = blk.proj.backward(d, _first(blk.xs, n), g, dev, dict(ws, dz=rot['dzr'], dx=rot['dxs']))
-        dy2 = ops.max_pool_backward_device(_first(u2.y, n), g, dx=rot['dy2'], stream=d.stream)
+        dy2 = train_ops.max_pool_backward_device(_first(u2.y, n), g, dx=rot['dy2'], stream=d.stream)
         d2, _, _ = u2.backward(d, _first(u1.y, n), None, dy2, dev, e.ws_dw, dict(ws, dz=rot['dz'], dt=rot['dt2'], dx=rot['d2']))
         d1, _, _ = u1.backward(d, x, None, d2, dev, e.ws_dw, dict(ws, dz=rot['dz1'], dt=rot['dt1'], dx=rot['d1']))
-        g = ops.add_upsample2_device(d1, dxs, out=grads[key(blk)], stream=d.stream)
+        g = train_ops.add_upsample2_device(d1, dxs, out=grads[key(blk)], stream=d.stream)
     _sync(d)
     _release([t for rot in inner.values() for t in rot.values()] + list(grads.values()))
     _download(dev, grads)
@@ -916,10 +904,9 @@ def _host_depthwise_forward(x, k, relu_in, dtype):
 
 def _host_max_pool_forward(x, dtype):
     """max_pooling2d(3, 2, 'same') of x [N,H,W,C]: padded positions are absent"""
-    from .ops import _same_pad_front
     x = np.asarray(x, dtype)
     N, H, W, C = x.shape
-    (Ho, pt), (Wo, pl) = _same_pad_front(H), _same_pad_front(W)
+    (Ho, pt), (Wo, pl) = train_ops._same_pad_front(H), train_ops._same_pad_front(W)
     xp = np.full((N, 2 * Ho + 1, 2 * Wo + 1, C), -np.inf, dtype)
     xp[:, pt:pt + H, pl:pl + W] = x
     out = np.full((N, Ho, Wo, C), -np.inf, dtype)
@@ -931,8 +918,7 @@ def _host_max_pool_forward(x, dtype):
 
 def _host_bn_forward(z, weights, bn, eps, momentum, dtype, saved):
     """y = BN(z) with batch statistics; saved gains the four statistics under '<bn>/...'"""
-    from . import ops
-    y, mean, invstd, mm, mv = ops.host_batch_norm_forward(z, weights[bn + '/gamma'], weights[bn + '/beta'], eps, True, momentum,
+    y, mean, invstd, mm, mv = train_ops.host_batch_norm_forward(z, weights[bn + '/gamma'], weights[bn + '/beta'], eps, True, momentum,
                                                           weights[bn + '/moving_mean'], weights[bn + '/moving_variance'], False, dtype)
     saved.update({bn + '/save_mean': mean, bn + '/save_invstd': invstd, bn + '/moving_mean': mm, bn + '/moving_variance': mv})
     return y
@@ -947,20 +933,18 @@ def _host_unit_forward(x, weights, unit, relu_in, eps, momentum, dtype, saved):
 
 
 def _host_bn_backward(saved, weights, z, bn, dy, dtype):
-    from . import ops
     vec = lambda a: np.asarray(a, dtype).reshape(-1)
-    return ops.host_batch_norm_backward(saved[z], None, dy, weights[bn + '/gamma'], vec(saved[bn + '/save_mean']),
+    return train_ops.host_batch_norm_backward(saved[z], None, dy, weights[bn + '/gamma'], vec(saved[bn + '/save_mean']),
                                         vec(saved[bn + '/save_invstd']), True, dtype)
 
 
 def _host_unit_backward(x, dy, saved, weights, unit, relu_in, dtype, out):
     """d loss / d y -> d loss / d x through the unit's BN, 1x1 conv and depthwise conv; out gains the unit's four weight
     gradients, 'dw/<unit>' and 'z/<unit>'"""
-    from . import ops
     bn = unit + '_bn'
     dz, out[bn + '/gamma'], out[bn + '/beta'] = _host_bn_backward(saved, weights, unit + '/z', bn, dy, dtype)
-    dt, out[unit + '/pointwise_kernel'], _ = ops.host_conv_backward(saved[unit + '/dw'], weights[unit + '/pointwise_kernel'], dz, None, False, dtype)
-    dx, out[unit + '/depthwise_kernel'] = ops.host_depthwise_backward(x, weights[unit + '/depthwise_kernel'], dt, 1, relu_in, dtype)
+    dt, out[unit + '/pointwise_kernel'], _ = train_ops.host_conv_backward(saved[unit + '/dw'], weights[unit + '/pointwise_kernel'], dz, None, False, dtype)
+    dx, out[unit + '/depthwise_kernel'] = train_ops.host_depthwise_backward(x, weights[unit + '/depthwise_kernel'], dt, 1, relu_in, dtype)
     out['dw/' + unit], out['z/' + unit] = dt, dz
     return dx
 
@@ -970,7 +954,7 @@ def host_middle_flow_train(entry_x, weights, dtype=np.float64, blocks=MIDDLE_FLO
     checkpoint's names (C comes from the weights) -> (mid_x, saved): the output of the last block and a dict with
     detector.middle_flow_saved()'s keys for `blocks` -- 'x<b>', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per
     batch norm '/save_mean', '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's
-    update as ops.host_batch_norm_forward states it) -- plus 'block<b>/y3'."""
+    update as train_ops.host_batch_norm_forward states it) -- plus 'block<b>/y3'."""
     x, saved = np.asarray(entry_x, dtype), {}
     for b in blocks:
         saved['x%d' % b] = x
@@ -986,8 +970,8 @@ def host_middle_flow_backward(saved, weights, d_mid, dtype=np.float64, blocks=MI
     """The NumPy statement of middle_flow_backward(d_mid, intermediates=True): saved = what host_middle_flow_train (or
     detector.middle_flow_saved(), as NumPy arrays) left, d_mid = d loss / d (the last block's output) -> a dict with the four
     gradients of every unit of `blocks` under the checkpoint's names and in its shapes, 'entry' = d loss / d (the first block's
-    input), 'x<b>' for every later block, 'dw/<unit>', 'z/<unit>' and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>'.  Composed of ops.host_batch_norm_backward,
-    ops.host_conv_backward and ops.host_depthwise_backward."""
+    input), 'x<b>' for every later block, 'dw/<unit>', 'z/<unit>' and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>'.  Composed of train_ops.host_batch_norm_backward,
+    train_ops.host_conv_backward and train_ops.host_depthwise_backward."""
     blocks = tuple(blocks)
     g, out = np.asarray(d_mid, dtype), {}
     for b in reversed(blocks):
@@ -1005,13 +989,12 @@ def host_entry_flow_train(stem_out, weights, dtype=np.float64, blocks=ENTRY_FLOW
     of the last block and a dict with detector.entry_flow_saved()'s keys for `blocks` -- 'x<b>', 'block<b>/xs',
     'conv2d_<b-1>/z', 'block<b>/r', '<unit>/dw', '<unit>/z', 'block<b>/y1', 'block<b>/y2', and per batch norm '/save_mean',
     '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after TensorFlow's update as
-    ops.host_batch_norm_forward states it)."""
-    from . import ops
+    train_ops.host_batch_norm_forward states it)."""
     x, saved = np.asarray(stem_out, dtype), {}
     for b in blocks:
         saved['x%d' % b] = x
         proj = 'conv2d_%d' % (b - 1)
-        xs = ops.host_subsample2(x, dtype)
+        xs = train_ops.host_subsample2(x, dtype)
         zr = np.matmul(xs, np.asarray(weights[proj + '/kernel'], dtype)[0, 0])
         r = _host_bn_forward(zr, weights, 'batch_normalization_%d' % (b - 1), ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM, dtype, saved)
         saved['block%d/xs' % b], saved[proj + '/z'], saved['block%d/r' % b] = xs, zr, r
@@ -1029,20 +1012,19 @@ def host_entry_flow_backward(saved, weights, d_entry, dtype=np.float64, blocks=E
     detector.entry_flow_saved(), as NumPy arrays) left, d_entry = d loss / d (the last block's output) -> a dict with the eleven
     gradients of every block of `blocks` under the checkpoint's names and in its shapes, 'stem' = d loss / d (the first block's
     input), 'x<b>' for every later block, and 'dxs/block<b>', 'z/conv2d_<b-1>', 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>',
-    'dw/<unit>', 'z/<unit>'.  Composed of ops.host_batch_norm_backward, ops.host_conv_backward, ops.host_depthwise_backward,
-    ops.host_max_pool_backward and ops.host_add_upsample2."""
-    from . import ops
+    'dw/<unit>', 'z/<unit>'.  Composed of train_ops.host_batch_norm_backward, train_ops.host_conv_backward, train_ops.host_depthwise_backward,
+    train_ops.host_max_pool_backward and train_ops.host_add_upsample2."""
     blocks = tuple(blocks)
     g, out = np.asarray(d_entry, dtype), {}
     for b in reversed(blocks):
         proj, bn = 'conv2d_%d' % (b - 1), 'batch_normalization_%d' % (b - 1)
         dzr, out[bn + '/gamma'], out[bn + '/beta'] = _host_bn_backward(saved, weights, proj + '/z', bn, g, dtype)
-        dxs, out[proj + '/kernel'], _ = ops.host_conv_backward(saved['block%d/xs' % b], weights[proj + '/kernel'], dzr, None, False, dtype)
+        dxs, out[proj + '/kernel'], _ = train_ops.host_conv_backward(saved['block%d/xs' % b], weights[proj + '/kernel'], dzr, None, False, dtype)
         out['z/' + proj], out['dxs/block%d' % b] = dzr, dxs
-        dy = out['dy2/block%d' % b] = ops.host_max_pool_backward(saved['block%d/y2' % b], g, dtype)
+        dy = out['dy2/block%d' % b] = train_ops.host_max_pool_backward(saved['block%d/y2' % b], g, dtype)
         for i, xin in ((2, saved['block%d/y1' % b]), (1, saved['x%d' % b])):
             dy = out['d%d/block%d' % (i, b)] = _host_unit_backward(xin, dy, saved, weights, 'block%d_sepconv%d' % (b, i),
                                                                    _entry_relu_in(b, i), dtype, out)
-        g = ops.host_add_upsample2(dy, dxs, dtype)
+        g = train_ops.host_add_upsample2(dy, dxs, dtype)
         out['stem' if b == blocks[0] else 'x%d' % b] = g
     return out
