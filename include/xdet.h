@@ -733,6 +733,61 @@ int xdet_subsample2(const float* x, int ld_x, int N, int H, int W, int C, float*
 int xdet_add_upsample2(const float* a, int ld_a, const float* b, int ld_b, int N, int H, int W, int C, float* out, int ld_out,
                        void* stream);
 
+/* ---- the optimizer step (csrc/optimizer.hip): tf.train.MomentumOptimizer with the reference's L2 term over a table of
+ * tensors, and the refresh of a forward layer's operands from a kernel in device memory ------------------------------------
+ * A slot is one variable: var, grad and accum (the momentum slot) are dense f32 arrays of n elements in device memory; var
+ * and accum are updated in place.  decay != 0: the variable is in the L2 set (light_head_rfcn_train.py:420,435).  Per
+ * element, every operation an f32 operation rounded on its own (no fused multiply-add):
+ *     g     = grad + weight_decay * var        (decay != 0;  g = grad otherwise)
+ *     accum = momentum * accum + g
+ *     var   = var - lr * accum
+ * -- the NumPy statement of the same contract is xdet.ops.host_momentum_step, and the call equals it bit for bit (f32
+ * denormals and signed zeros included).  One launch serves the whole table: the element space is cut into chunks of 4096
+ * consecutive elements of one slot (a slot's last chunk is short; chunks are numbered slot by slot, in table order), one
+ * workgroup per chunk; the chunk table is built here and uploaded into the workspace with the slot table.  Accesses are
+ * 128-bit wide in a slot whose three pointers are 16-byte aligned.
+ * l2 (a device float, or NULL: not computed) = sum over the decayed slots of sum var^2 / 2 on the values BEFORE the update,
+ * in f32, in this fixed order (no float atomics: the same call gives the same bits):
+ *   - element j of a chunk belongs to vector q = j / 4; vector q to thread q % 256, as its vector i = q / 256 (0..3); an
+ *     element beyond the slot's end counts as +0;
+ *   - a vector's sum is (v0^2 + v1^2) + (v2^2 + v3^2); a thread's is (t0 + t1) + (t2 + t3) over its four vectors;
+ *   - the 256 thread sums of a chunk fold pairwise: for w = 128, 64 .. 1: s[i] += s[i + w] for i < w; s[0] is the chunk's
+ *     partial (0 for a chunk of a slot without decay);
+ *   - the C chunk partials fold the same way with P = the power of two at or above C: for w = P/2 .. 1: p[i] += p[i + w]
+ *     for i < w where i + w < C; l2 = p[0] / 2.
+ *   Every term is non-negative and passes through at most 1 + 2 + 2 + 8 + ceil(log2(C)) roundings, which bounds the
+ *   relative error against the exact sum by that count times 2^-24 (to first order).
+ * workspace: xdet_momentum_step_workspace_bytes(slots, n_slots) bytes of device memory (0 for a table the call refuses); it
+ *   needs no initialisation and may be larger; the call after a call on the same stream may reuse it.  The call does not
+ *   synchronise.  Limits: at most 65536 slots and 2^22 chunks.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work, never a skipped slot: a NULL or empty table, a slot with a NULL var,
+ *   grad or accum or with n <= 0, a NULL workspace, a table beyond the limits. */
+typedef struct {
+  float* var;
+  const float* grad;
+  float* accum;
+  int64_t n;
+  int decay;
+} xdet_momentum_slot;
+size_t xdet_momentum_step_workspace_bytes(const xdet_momentum_slot* slots_host, int n_slots);
+int xdet_momentum_step(const xdet_momentum_slot* slots_host, int n_slots, float lr, float momentum, float weight_decay, float* l2,
+                       void* workspace, void* stream);
+/* Rewrite, on the device and in place, every operand buffer a conv layer (xdet_conv_create) owns from a dense f32
+ * [kh,kw,cin,cout] kernel in device memory: the transposed matrix of the f32 mode, or the per-row power-of-two pre-scale, the
+ * f16 hi / lo split, the K-blocked copies, the fp8 x8 copy of a pointwise f16x3 layer and the epilogue scale (the scale the
+ * layer was created with times 2^-shift of the row) -- each buffer holds exactly what xdet_conv_create would have made from
+ * the same values; padding rows and channels stay +0.  shift_dev (f32 [cout] in device memory, or NULL: kept) replaces the
+ * epilogue shift.  Two passes over the kernel (the row maxima, then exponent, split and scatter) on `stream`, no
+ * synchronisation, nothing read on the host.  Errors -> XDET_ERR_INVALID_ARG with the layer unchanged: a NULL kernel, a
+ * grouped or spectral layer, a layer that carries an activation or planes exponent or a planes affine (a calibrated or
+ * net-owned layer: its scale arrays are no longer the ones it was created with).  The shape is the layer's: the caller
+ * vouches for kh * kw * cin * cout floats.  Afterwards the layer's host copy of the scale is stale: a later activation
+ * exponent (a plan's calibration) is refused for this layer. */
+int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const float* shift_dev, void* stream);
+/* The same for a depthwise layer (xdet_depthwise_create): its taps [9][round_up(C,32)] from a dense f32 [3,3,C,1] kernel in
+ * device memory, padding channels +0.  Errors: a NULL kernel, a layer whose taps carry an activation pre-scale. */
+int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

@@ -26,15 +26,16 @@ struct Pow2Scaled {
 
 extern int g_default_precision;   // precision mode new layers and plans are created in (cabi.hip)
 
-static inline unsigned short f32_to_f16_rne(float f) {
+// (the three converters below also run on the device: the operand repack of optimizer.hip makes the same bits with them)
+__host__ __device__ static inline unsigned short f32_to_f16_rne(float f) {
   unsigned x;
-  memcpy(&x, &f, 4);
+  __builtin_memcpy(&x, &f, 4);
   const unsigned sign = (x >> 16) & 0x8000u;
   x &= 0x7FFFFFFFu;
   if (x >= 0x47800000u) return (unsigned short)(sign | (x > 0x7F800000u ? 0x7E00u : 0x7C00u));   // inf / nan
   if (x < 0x38800000u) {                       // below 2^-14: subnormal half = round(|f| * 2^24)
     float af;
-    memcpy(&af, &x, 4);
+    __builtin_memcpy(&af, &x, 4);
     return (unsigned short)(sign | (unsigned)lrintf(af * 16777216.0f));
   }
   const unsigned mant = x & 0x7FFFFFu, exp = (x >> 23) - 127 + 15;
@@ -45,7 +46,7 @@ static inline unsigned short f32_to_f16_rne(float f) {
 }
 // OCP fp8 e4m3 (bias 7, largest 448 = 0x7e, no infinities), round to nearest even, saturating: the format of the x8 cross-term
 // operands (conv_params.h; the device side is v_cvt_pk_fp8_f32 in the producing kernels)
-static inline unsigned char f32_to_e4m3(float f) {
+__host__ __device__ static inline unsigned char f32_to_e4m3(float f) {
   const unsigned char sgn = std::signbit(f) ? 0x80 : 0;
   const float a = std::fabs(f);
   if (!(a == a)) return 0x7f;
@@ -61,16 +62,16 @@ static inline unsigned char f32_to_e4m3(float f) {
   if (q == 16) { q = 8; ++e; }
   return sgn | (unsigned char)(((e + 7) << 3) | (q - 8));
 }
-static inline float f16_to_f32(unsigned short h) {
+__host__ __device__ static inline float f16_to_f32(unsigned short h) {
   const unsigned sign = (unsigned)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
   float v;
   if (e == 0) v = ldexpf((float)m, -24);
   else if (e == 31) v = m ? NAN : INFINITY;
   else v = ldexpf((float)(m | 0x400u), (int)e - 25);
   unsigned u;
-  memcpy(&u, &v, 4);
+  __builtin_memcpy(&u, &v, 4);
   u |= sign;
-  memcpy(&v, &u, 4);
+  __builtin_memcpy(&v, &u, 4);
   return v;
 }
 
@@ -154,7 +155,18 @@ struct ConvLayer : LayerBase {
     return XDET_OK;
   }
   DevMem<float> d_pl_scale, d_pl_shift;
+  // The operands rebuilt on the device from a dense f32 [kh,kw,cin,cout] kernel in device memory (optimizer.hip): every
+  // buffer above holds what init() would have made of the same values.  scale0: the epilogue scale init() was given, in
+  // front of the rows' pre-scale (its device copy and the row maxima's scratch are made by the first refresh).  Afterwards
+  // in_scale.host no longer describes d_scale: host_stale, and set_in_exp refuses.
+  std::vector<float> scale0;
+  DevMem<float> d_repack_scale0;
+  DevMem<unsigned> d_repack_max;
+  bool host_stale = false;
+  int set_kernel_device(const float* k_hwio, const float* shift, hipStream_t s);
   int set_in_exp(int e) {
+    XDET_REQUIRE(!host_stale, "conv: the kernel was refreshed on the device (xdet_conv_set_kernel_device): the host copy of the "
+                              "epilogue scale is stale, an activation exponent cannot be applied");
     XDET_TRY(in_scale.upload(e));
     in_exp = e;
     return XDET_OK;
@@ -216,6 +228,7 @@ struct ConvLayer : LayerBase {
     }
     precision = g_default_precision;
     XDET_REQUIRE(groups == 1 || precision != PREC_F32, "conv: grouped GEMMs need a split-precision mode");
+    if (groups == 1) scale0 = sc;
     XDET_HIP(hipGetDevice(&device));
     if (precision != PREC_F32 && !small_cin) {
       XDET_TRY(d_zeros.alloc_zeroed(128));
@@ -423,7 +436,11 @@ struct DepthwiseLayer : LayerBase {
   DevMem<float> d_w;
   Pow2Scaled taps;               // d_w and its host copy: a planes-producing depthwise carries its activation pre-scale in them
   int out_exp = 0;
+  bool host_stale = false;       // d_w was rewritten on the device (set_kernel_device, optimizer.hip): taps.host is not d_w
+  int set_kernel_device(const float* k33c1, hipStream_t s);
   int set_out_exp(int e) {       // every partial sum of the FMA chain scales exactly with a power of two
+    XDET_REQUIRE(!host_stale, "depthwise: the kernel was refreshed on the device (xdet_depthwise_set_kernel_device): the host "
+                              "copy of the taps is stale, an activation exponent cannot be applied");
     XDET_TRY(taps.upload(-e));
     out_exp = e;
     return XDET_OK;

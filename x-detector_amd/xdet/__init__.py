@@ -44,6 +44,11 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the gradient of max_pooling2d(3, 2, 'same') and blocks 2-4 of the Xception entry flow
                              (net/xception_body.py:260-326) with batch statistics and their backward, from `entry_x` down to
                              the stem's output `stem_out`
+  host_momentum_step, momentum_step_device (xdet.ops); Conv2D.set_kernel_device, DepthwiseConv2D.set_kernel_device;
+  MomentumOptimizer, piecewise_learning_rate (xdet.model; the flow backwards' weight_grads='device')
+                          <- tf.train.MomentumOptimizer with the L2 term and the learning-rate schedule of
+                             light_head_rfcn_train.py:420-436 over the three flows' variables, and the refresh of their
+                             forward layers' operands on the device
 The training names above that are marked (xdet.model) are written in xdet/train.py (the stages, their state classes, the
 backwards and the host statements) and re-exported by xdet/model.py, which holds the eval graph and the detector classes.
 The training names marked (xdet.ops) are written in xdet/train_ops.py and re-exported by xdet/ops.py, which holds the eval path.

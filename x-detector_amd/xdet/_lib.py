@@ -48,6 +48,11 @@ class LightHeadConfig(ctypes.Structure):
                                   nms_topk, grid, bank)
 
 
+class MomentumSlot(ctypes.Structure):
+    """xdet_momentum_slot: one variable of xdet_momentum_step -- var, grad, accum device pointers, n elements, the L2 flag"""
+    _fields_ = [('var', c_void_p), ('grad', c_void_p), ('accum', c_void_p), ('n', c_int64), ('decay', c_int)]
+
+
 # name -> (restype, argtypes); must list every symbol include/xdet.h declares
 SIGNATURES = {
     'xdet_last_error': (ctypes.c_char_p, []),
@@ -157,6 +162,10 @@ SIGNATURES = {
     'xdet_maxpool3x3s2_backward': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_subsample2': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_add_upsample2': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
+    'xdet_momentum_step_workspace_bytes': (c_size_t, [ctypes.POINTER(MomentumSlot), c_int]),
+    'xdet_momentum_step': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_void_p]),
+    'xdet_conv_set_kernel_device': (c_int, [c_void_p, PF, PF, c_void_p]),
+    'xdet_depthwise_set_kernel_device': (c_int, [c_void_p, PF, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),

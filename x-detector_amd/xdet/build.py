@@ -34,6 +34,7 @@ SOURCES = [
     ('batchnorm.hip', ['-ffp-contract=off']),
     ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('pool_backward.hip', ['-ffp-contract=off']),
+    ('optimizer.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),

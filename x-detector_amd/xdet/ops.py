@@ -250,6 +250,21 @@ class Conv2D(object):
             max_parallel_tiles = 448 // max(int(ksplit), 1)
         check(lib().xdet_conv_set_ksplit(self.handle, int(ksplit), int(mode), int(max_parallel_tiles)))
 
+    def set_kernel_device(self, t, shift=None, stream=None):
+        """Rewrite every operand buffer of the layer from a kernel in device memory (xdet_conv_set_kernel_device): t is a dense
+        DeviceTensor [kh,kw,cin,cout] (ld cout), shift a DeviceBuffer / DeviceTensor of cout floats or None (kept).  The
+        layer then holds what Conv2D(t's values, ...) would hold, bit for bit; nothing is synchronised or read on the host.
+        Refused for a grouped or calibrated layer (the library's refusal) and for a wrong shape."""
+        want = (self.kh, self.kw, self.cin, self.cout)
+        if not isinstance(t, DeviceTensor) or tuple(t.shape) != want or t.ld != self.cout:
+            raise InvalidArgumentError(-1, 'Conv2D.set_kernel_device: a dense DeviceTensor of shape %r expected, got %r (ld %r)'
+                                       % (want, getattr(t, 'shape', None), getattr(t, 'ld', None)))
+        if shift is not None and (not isinstance(shift, (DeviceBuffer, DeviceTensor))
+                                  or (isinstance(shift, DeviceBuffer) and shift.nbytes < 4 * self.cout)):
+            raise InvalidArgumentError(-1, 'Conv2D.set_kernel_device: shift must be a device array of %d floats' % self.cout)
+        check(lib().xdet_conv_set_kernel_device(self.handle, t.ptr, shift.ptr if shift is not None else None,
+                                                stream.handle if stream else None))
+
     def out_shape(self, H, W):
         ho, wo = ctypes.c_int(), ctypes.c_int()
         check(lib().xdet_conv_out_shape(self.handle, H, W, ctypes.byref(ho), ctypes.byref(wo)))
@@ -337,6 +352,14 @@ class DepthwiseConv2D(object):
         h = c_void_p()
         check(lib().xdet_depthwise_create(ctypes.byref(h), self.C, dilation, _host(k)))
         self.handle = h
+
+    def set_kernel_device(self, t, stream=None):
+        """Rewrite the layer's taps from a kernel in device memory (xdet_depthwise_set_kernel_device): t is a dense
+        DeviceTensor [3,3,C,1] (ld 1); nothing is synchronised or read on the host."""
+        if not isinstance(t, DeviceTensor) or tuple(t.shape) != (3, 3, self.C, 1) or t.ld != 1:
+            raise InvalidArgumentError(-1, 'DepthwiseConv2D.set_kernel_device: a dense DeviceTensor of shape %r expected, got %r '
+                                           '(ld %r)' % ((3, 3, self.C, 1), getattr(t, 'shape', None), getattr(t, 'ld', None)))
+        check(lib().xdet_depthwise_set_kernel_device(self.handle, t.ptr, stream.handle if stream else None))
 
     def __call__(self, x, relu_in=False, stream=None):
         N, H, W, C = x.shape

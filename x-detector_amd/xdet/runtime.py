@@ -158,6 +158,8 @@ class DeviceTensor(object):
         return cls(buf.ptr, shape, ld, buf)
 
     def numpy(self, layout='NHWC', n=None, stream=None):
+        if len(self.shape) != 4:                         # a dense array of another rank (a [C] weight gradient): as it lies
+            return to_host(self.ptr, self.shape, np.float32, stream)
         N, H, W, C = self.shape
         N = n or N
         raw = to_host(self.ptr, (N, H, W, self.ld), np.float32, stream)

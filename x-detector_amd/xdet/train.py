@@ -5,15 +5,17 @@ above it writes: the large-separable block <- the exit flow <- the middle flow <
 detector built with a stage's flag keeps one state object for it (`LargeSepState`, `ExitFlowState`, `MiddleFlowState`,
 `EntryFlowState`), made of `BatchNorm`, `SepUnit` and `Projection`; the module-level functions run a stage of the detector
 that is current (`with det.scope():`).  The head's and the RPN head's backward (`head_backward`, `rpn_backward`) and the NumPy
-statements of the middle and the entry flow (`host_*`) live here too.
+statements of the middle and the entry flow (`host_*`) live here too, and the optimizer step over the three flows' variables
+(`MomentumOptimizer`, `piecewise_learning_rate`).
 """
 import collections
 import contextlib
+import math
 
 import numpy as np
 
 from . import train_ops, ops
-from ._lib import lib, check, XdetError, InvalidArgumentError
+from ._lib import lib, check, XdetError, InvalidArgumentError, MomentumSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, _det, _sync
 
 __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
@@ -23,7 +25,7 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'LARGE_SEP_EPS', 'LARGE_SE
            'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
-           'host_entry_flow_train', 'host_entry_flow_backward']
+           'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'MomentumOptimizer']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
                             for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
@@ -131,6 +133,21 @@ def _download(dev, grads):
     """the weight gradients a backward left in `dev` as (DeviceBuffer, shape) -> NumPy arrays in `grads` (behind the sync)"""
     for k, (buf, shape) in dev.items():
         grads[k] = to_host(buf.ptr, shape)
+
+
+def _check_weight_grads(fn, weight_grads):
+    if weight_grads not in ('host', 'device'):
+        raise InvalidArgumentError(-1, "%s: weight_grads must be 'host' or 'device', got %r" % (fn, weight_grads))
+
+
+def _deliver(dev, grads, weight_grads):
+    """the weight gradients of a flow's backward, behind the sync: 'host' -> NumPy arrays (_download); 'device' -> dense
+    DeviceTensors in the checkpoint's shapes that own their memory, nothing downloaded (what MomentumOptimizer.step reads)"""
+    if weight_grads == 'host':
+        return _download(dev, grads)
+    for k, (buf, shape) in dev.items():
+        buf._keep = None                                 # (the stream has run: the operands need no keeping alive)
+        grads[k] = DeviceTensor(buf.ptr, shape, shape[-1], owner=buf)
 
 
 def _release(tensors):
@@ -663,7 +680,7 @@ def exit_flow_train():
     return out
 
 
-def exit_flow_backward(d_out, d_mid=None):
+def exit_flow_backward(d_out, d_mid=None, weight_grads='host'):
     """The backward of the exit flow in training mode, called after exit_flow_train() on a detector built with
     exit_flow_train=True: d_out = large_sep_backward(...)['out'] (d loss / d out, with the `out` buffer's shape and ld) and
     optionally d_mid = rpn_backward(...)['mid'] (the RPN branch's share of d loss / d mid_x, with `mid_x`'s shape and ld).  Per
@@ -678,8 +695,11 @@ def exit_flow_backward(d_out, d_mid=None):
     'mid_A' and 'mid_B', and the intermediate gradients 'b2', 'c3', 'a' and 'r' (d loss / d r is d loss / d b2: the same
     tensor), 'dw/<unit>' = d loss / d (the unit's depthwise output) and 'z/<unit>', 'z/conv2d_4' = d loss / d (a batch norm's
     input) likewise.  Refused once a new eval body (set_images, forward, calibrate, detect_images) or a training forward of
-    the middle or the entry flow has run since exit_flow_train(): the kept tensors belong to another `mid_x`."""
+    the middle or the entry flow has run since exit_flow_train(): the kept tensors belong to another `mid_x`.
+    weight_grads='device': the 19 variables come back as dense DeviceTensors in the checkpoint's shapes instead and nothing is
+    downloaded (what MomentumOptimizer.step takes); everything else the call returns is unchanged."""
     d = _det()
+    _check_weight_grads('exit_flow_backward', weight_grads)
     e, n = _stage(d, EXIT, 'exit_flow_backward', 'exit_flow_train()')
     out, mid_x = d.buffer('out', n), d.buffer('mid_x', n)
     _check_grad('exit_flow_backward', 'd_out', d_out, out)
@@ -702,7 +722,7 @@ def exit_flow_backward(d_out, d_mid=None):
     if d_mid is not None:
         train_ops.add_rows_device(mid, d_mid, out=mid, stream=d.stream)
     _sync(d)
-    _download(dev, grads)
+    _deliver(dev, grads, weight_grads)
     grads.update({'mid': mid, 'mid_A': share_a, 'mid_B': share_b, 'b2': d_b2, 'r': d_b2, 'c3': d_c3, 'a': d_a, 'z/conv2d_4': dzr})
     return grads
 
@@ -742,7 +762,7 @@ def middle_flow_train():
     return d.buffer('mid', n)
 
 
-def middle_flow_backward(d_mid, intermediates=False):
+def middle_flow_backward(d_mid, intermediates=False, weight_grads='host'):
     """The backward of the middle flow in training mode, called after middle_flow_train() on a detector built with
     middle_flow_train=True: d_mid = exit_flow_backward(...)['mid'] (d loss / d mid_x, with `mid_x`'s shape and ld).  From
     block 12 back to block 5, with g = the gradient of the block's output, y1, y2 the kept batch norm outputs and x the
@@ -761,8 +781,11 @@ def middle_flow_backward(d_mid, intermediates=False):
     d (block b's input)).  intermediates=True: also 'dw/<unit>' = d loss / d (the unit's depthwise output), 'z/<unit>' =
     d loss / d (its batch norm's input) and 'd3/block<b>', 'd2/block<b>', 'd1/block<b>' (the units' input gradients; d1 is the
     addend of the join), each in a tensor of its own.  Refused once a new eval body (set_images, forward, calibrate,
-    detect_images) or entry_flow_train() has run since middle_flow_train(): the kept tensors belong to another `entry_x`."""
+    detect_images) or entry_flow_train() has run since middle_flow_train(): the kept tensors belong to another `entry_x`.
+    weight_grads='device': the 96 variables come back as dense DeviceTensors in the checkpoint's shapes instead and nothing is
+    downloaded (what MomentumOptimizer.step takes); everything else the call returns is unchanged."""
     d = _det()
+    _check_weight_grads('middle_flow_backward', weight_grads)
     m, n = _stage(d, MIDDLE, 'middle_flow_backward', 'middle_flow_train()')
     mid_x, entry = d.buffer('mid_x', n), d.buffer('entry_x', n)
     _check_grad('middle_flow_backward', 'd_mid', d_mid, mid_x)
@@ -790,7 +813,7 @@ def middle_flow_backward(d_mid, intermediates=False):
         g = train_ops.add_rows_device(dy, g, out=grads[key(blk)], stream=d.stream)
     _sync(d)
     _release(list(rot.values()) + list(grads.values()))
-    _download(dev, grads)
+    _deliver(dev, grads, weight_grads)
     return grads
 
 
@@ -832,7 +855,7 @@ def entry_flow_train():
     return d.buffer('entry_x', n)
 
 
-def entry_flow_backward(d_entry, intermediates=False):
+def entry_flow_backward(d_entry, intermediates=False, weight_grads='host'):
     """The backward of blocks 2-4 in training mode, called after entry_flow_train() on a detector built with
     entry_flow_train=True: d_entry = middle_flow_backward(...)['entry'] (d loss / d entry_x, with `entry_x`'s shape and ld).
     From block 4 back to block 2, with g the gradient of the block's output, x the block's input and y1, y2 the kept batch
@@ -852,8 +875,11 @@ def entry_flow_backward(d_entry, intermediates=False):
     'dxs/block<b>', 'z/conv2d_<b-1>' (dzr), 'dy2/block<b>', 'd2/block<b>', 'd1/block<b>' and per unit 'dw/<unit>' =
     d loss / d (its depthwise output), 'z/<unit>' = d loss / d (its batch norm's input), each in a tensor of its own.  Refused
     once a new eval body (set_images, forward, calibrate, detect_images) has run since entry_flow_train(): the kept tensors
-    belong to another `stem_out`."""
+    belong to another `stem_out`.
+    weight_grads='device': the 33 variables come back as dense DeviceTensors in the checkpoint's shapes instead and nothing is
+    downloaded (what MomentumOptimizer.step takes); everything else the call returns is unchanged."""
     d = _det()
+    _check_weight_grads('entry_flow_backward', weight_grads)
     e, n = _stage(d, ENTRY, 'entry_flow_backward', 'entry_flow_train()')
     _check_grad('entry_flow_backward', 'd_entry', d_entry, d.buffer('entry_x', n))
     key = lambda blk: 'stem' if blk.b == ENTRY_FLOW_BLOCKS[0] else 'x%d' % blk.b
@@ -884,8 +910,136 @@ def entry_flow_backward(d_entry, intermediates=False):
         g = train_ops.add_upsample2_device(d1, dxs, out=grads[key(blk)], stream=d.stream)
     _sync(d)
     _release([t for rot in inner.values() for t in rot.values()] + list(grads.values()))
-    _download(dev, grads)
+    _deliver(dev, grads, weight_grads)
     return grads
+
+
+# ---- the optimizer step: the reference's schedule and tf.train.MomentumOptimizer over the three flows' variables ---------------
+
+def piecewise_learning_rate(step, base=1e-3, boundaries=(60000, 80000), factors=(1, 0.8, 0.1), end=1e-4):
+    """The reference's learning rate at global step `step` (light_head_rfcn_train.py:426-430): tf.train.piecewise_constant over
+    `boundaries` with the values base * factor -- the earlier value holds while step <= boundary -- and end_learning_rate as the
+    floor.  -> a Python float"""
+    if len(factors) != len(boundaries) + 1:
+        raise InvalidArgumentError(-1, 'piecewise_learning_rate: %d boundaries need %d factors, got %d'
+                                   % (len(boundaries), len(boundaries) + 1, len(factors)))
+    i = 0
+    while i < len(boundaries) and step > boundaries[i]:
+        i += 1
+    return max(float(base) * float(factors[i]), float(end))
+
+
+def decayed(name):
+    """the reference's L2 set (light_head_rfcn_train.py:420): every trainable variable whose name contains neither
+    'batch_normalization' nor '_bn'"""
+    return 'batch_normalization' not in name and '_bn' not in name
+
+
+class MomentumOptimizer(object):
+    """tf.train.MomentumOptimizer(lr, momentum) over the loss the reference minimises, loss + weight_decay * sum l2_loss(v) over
+    the variables `decayed` names (light_head_rfcn_train.py:420,435), for the flow stages `det` was built with: the variables
+    of ENTRY_FLOW_VARIABLES + MIDDLE_FLOW_VARIABLES + EXIT_FLOW_VARIABLES whose stage is on, in that order (148 with all
+    three, 15 + 48 + 9 = 72 of them kernels in the L2 set).  The masters are the buffers the stages already hold -- SepUnit.K_dw,
+    SepUnit.K_pw, Projection.K, BatchNorm.gamma, BatchNorm.beta -- updated in place; the optimizer allocates the momentum slots
+    (zero) and the step's workspace and holds a second copy of nothing.
+    Out of its reach: the large-separable block, the head, the RPN head and the stem keep their weights, and the NATIVE EVAL
+    NET keeps the weights it folded when the detector was built -- XceptionBody(..., is_training=False), forward and
+    detect_images go on computing with the checkpoint the detector was made from until a new LightHeadDetector is built from
+    export_weights(...)."""
+
+    def __init__(self, det, momentum=0.9, weight_decay=2e-4):
+        flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
+        on = [(k, names) for k, names in flows if getattr(det, STAGES[k].flag, False)]
+        if not on:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer: needs a detector built with exit_flow_train=True (and optionally '
+                                           'middle_flow_train, entry_flow_train): no flow stage is on')
+        self.det, self.momentum, self.weight_decay, self.steps = det, float(momentum), float(weight_decay), 0
+        self._stages = [k for k, _ in on]
+        masters = {}
+        for u in self._units():
+            masters[u.name + '/depthwise_kernel'], masters[u.name + '/pointwise_kernel'] = (u.K_dw, u.K_dw.shape), (u.K_pw, u.K_pw.shape)
+        for p in self._projections():
+            masters[p.name + '/kernel'] = (p.K, p.K.shape)
+        for bn in self._batch_norms():
+            masters[bn.name + '/gamma'], masters[bn.name + '/beta'] = (bn.gamma, (bn.co,)), (bn.beta, (bn.co,))
+        self.variables = tuple(v for _, names in on for v in names)
+        self._master = {v: masters[v] for v in self.variables}            # name -> (device array, shape)
+        self._decayed = {v: decayed(v) for v in self.variables}
+        self._slot = {v: DeviceBuffer(4 * int(np.prod(self._master[v][1])), zero=True) for v in self.variables}
+        table = (MomentumSlot * len(self.variables))()
+        for i, v in enumerate(self.variables):                            # (sizes only: the workspace depends on nothing else)
+            table[i] = MomentumSlot(1, 1, 1, int(np.prod(self._master[v][1])), 0)
+        self._ws = DeviceBuffer(lib().xdet_momentum_step_workspace_bytes(table, len(self.variables)))
+
+    def _states(self):
+        return [getattr(self.det, STAGES[k].attr) for k in self._stages]
+
+    def _units(self):
+        """the SepUnits of the stages that are on, as the stages hold them at this moment"""
+        return [u for s in self._states() for u in (s.units if hasattr(s, 'units') else [u for blk in s.blocks for u in blk.units])]
+
+    def _projections(self):
+        return [p for s in self._states() for p in ([s.proj] if hasattr(s, 'proj') else [blk.proj for blk in s.blocks if hasattr(blk, 'proj')])]
+
+    def _batch_norms(self):
+        return [u.bn for u in self._units()] + [p.bn for p in self._projections()]
+
+    def step(self, grads, lr):
+        """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
+        backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
+        stream: one xdet_momentum_step over all variables; the refresh of the forward layers (every unit's pointwise and
+        depthwise layer and every projection's conv, as the units hold them at this moment) from the updated masters by
+        xdet_conv_set_kernel_device / xdet_depthwise_set_kernel_device; and the drop of every stage's saved state, as a new eval
+        body drops it: the kept tensors belong to the old weights, so each *_backward refuses until its training forward has run
+        again (the eval body need not: `stem_out` does not depend on these variables).
+        -> {'step': the number of steps taken, 'lr': lr, 'l2': sum over the L2 set of sum v^2 / 2 before the update, a float}.
+        Refused ahead of any launch: a missing gradient (by name), a host array, a wrong shape."""
+        miss = [v for v in self.variables if v not in grads]
+        if miss:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradients lack %s' % ', '.join(miss))
+        for v in self.variables:
+            g, (master, shape) = grads[v], self._master[v]
+            if not isinstance(g, DeviceTensor) or tuple(g.shape) != tuple(shape) or g.ld != shape[-1]:
+                raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradient of %s must be a dense DeviceTensor of shape %r '
+                                               '(a backward\'s weight_grads=\'device\'), got %s %r'
+                                           % (v, tuple(shape), type(g).__name__, getattr(g, 'shape', None)))
+        slots = [(self._master[v][0], grads[v], self._slot[v], math.prod(self._master[v][1]), self._decayed[v]) for v in self.variables]
+        d = self.det
+        l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws)
+        for u in self._units():
+            u.pw.set_kernel_device(u.K_pw, stream=d.stream)
+            u.dw.set_kernel_device(u.K_dw, stream=d.stream)
+        for p in self._projections():
+            p.conv.set_kernel_device(p.K, stream=d.stream)
+        new_body(d)
+        _sync(d)
+        l2._keep = None
+        self.steps += 1
+        return {'step': self.steps, 'lr': float(lr), 'l2': float(to_host(l2.ptr, (1,))[0])}
+
+    def read(self):
+        """-> {name: ndarray} for every variable and, under '<name>/Momentum', its momentum slot, in the checkpoint's shapes"""
+        _sync(self.det)
+        out = {}
+        for v in self.variables:
+            master, shape = self._master[v]
+            out[v], out[v + '/Momentum'] = to_host(master.ptr, shape), to_host(self._slot[v].ptr, shape)
+        return out
+
+    def export_weights(self, base):
+        """a copy of the weights dict `base` with the optimizer's variables and the current moving statistics of the training
+        stages' batch norms replaced by what the device holds: fit for a new LightHeadDetector, whose eval net then folds the
+        trained weights"""
+        _sync(self.det)
+        out = dict(base)
+        for v in self.variables:
+            master, shape = self._master[v]
+            out[v] = to_host(master.ptr, shape)
+        lsep = STAGES[LARGE_SEP]                           # (its training forward moves its statistics too)
+        for bn in self._batch_norms() + ([getattr(self.det, lsep.attr).bn] if getattr(self.det, lsep.flag, False) else []):
+            for k in ('moving_mean', 'moving_variance'):
+                out['%s/%s' % (bn.name, k)] = to_host(getattr(bn, k).ptr, (bn.co,))
+        return out
 
 
 # ---- the flows' host statements: NumPy, any channel counts and map sizes (the weights and the input decide), float64 as the

@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from ._lib import lib, check, InvalidArgumentError
+from ._lib import lib, check, InvalidArgumentError, MomentumSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
@@ -15,7 +15,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'batch_norm_backward_device', 'batch_norm_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
-           'subsample2_device', 'add_upsample2_device']
+           'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device']
 
 
 # ---- the operand path every door below takes ------------------------------------------------------------------------------
@@ -598,3 +598,65 @@ def add_upsample2_device(a, b, out=None, stream=None):
     check(lib().xdet_add_upsample2(pa, lda, pb, ldb, N, H, W, C, out.ptr, out.ld, _handle(stream)))
     _keep_alive((out,), (ta, tb), chain=True)
     return out
+
+
+# ---- the optimizer step: tf.train.MomentumOptimizer with the reference's L2 term (xdet_momentum_step, csrc/optimizer.hip) --
+
+def host_momentum_step(var, grad, accum, lr, momentum=0.9, weight_decay=0.0, decay=True, dtype=np.float32):
+    """The NumPy statement of xdet_momentum_step (include/xdet.h) for one variable: var, grad, accum of one shape ->
+    (new var, new accum),
+
+        g = grad + weight_decay * var      (decay; g = grad otherwise)
+        accum = momentum * accum + g
+        var = var - lr * accum
+
+    every operation rounded on its own in `dtype`: float32 is the op's result bit for bit; float64 the yardstick."""
+    var, grad, accum = np.asarray(var, dtype), np.asarray(grad, dtype), np.asarray(accum, dtype)
+    g = grad + dtype(weight_decay) * var if decay else grad
+    accum = dtype(momentum) * accum + g
+    return var - dtype(lr) * accum, accum
+
+
+def _momentum_array(a, n, what):
+    """one of a slot's three arrays: a DeviceBuffer of at least n floats or a dense DeviceTensor of n elements -> pointer"""
+    if isinstance(a, DeviceTensor):
+        if a.ld != a.shape[-1] or math.prod(a.shape) != n:
+            raise InvalidArgumentError(-1, 'momentum_step: %s must be dense and hold %d elements, got shape %r with ld %d'
+                                       % (what, n, a.shape, a.ld))
+    elif not isinstance(a, DeviceBuffer):
+        raise InvalidArgumentError(-1, 'momentum_step: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                   % (what, type(a).__name__))
+    elif a.nbytes < 4 * n:
+        raise InvalidArgumentError(-1, 'momentum_step: %s holds %d bytes, %d elements need %d' % (what, a.nbytes, n, 4 * n))
+    if not a.ptr:
+        raise InvalidArgumentError(-1, 'momentum_step: %s is a NULL pointer' % what)
+    return a.ptr
+
+
+def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, stream=None, workspace=None):
+    """host_momentum_step over a table of variables in one launch (xdet_momentum_step): slots is a sequence of (var, grad, accum,
+    n, decay) with var, grad, accum dense DeviceTensors of n elements or DeviceBuffers of at least n floats; var and accum are
+    updated in place.  l2=True: -> a DeviceBuffer holding one float, sum over the decayed slots of sum var^2 / 2 on the values
+    before the update, summed in the fixed order include/xdet.h documents (None otherwise).  workspace: a DeviceBuffer of at
+    least xdet_momentum_step_workspace_bytes bytes (default: allocated here).  Nothing is synchronised."""
+    slots = list(slots)
+    if not slots:
+        raise InvalidArgumentError(-1, 'momentum_step: an empty slot table')
+    table = (MomentumSlot * len(slots))()
+    for i, slot in enumerate(slots):
+        if len(slot) != 5:
+            raise InvalidArgumentError(-1, 'momentum_step: slot %d must be (var, grad, accum, n, decay)' % i)
+        var, grad, accum, n, decay = slot
+        n = int(n)
+        _check_sizes((n,), (1,), 'momentum_step: slot %d holds n = %d elements (positive, below 2^31)', (i, n), widest=None)
+        ptrs = [_momentum_array(a, n, 'slot %d\'s %s' % (i, what)) for a, what in ((var, 'var'), (grad, 'grad'), (accum, 'accum'))]
+        table[i] = MomentumSlot(ptrs[0], ptrs[1], ptrs[2], n, 1 if decay else 0)
+    need = lib().xdet_momentum_step_workspace_bytes(table, len(slots))
+    if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
+        raise InvalidArgumentError(-1, 'momentum_step: workspace must be a DeviceBuffer of at least %d bytes' % need)
+    ws = workspace if workspace is not None else DeviceBuffer(need)
+    d_l2 = DeviceBuffer(16) if l2 else None
+    check(lib().xdet_momentum_step(table, len(slots), float(lr), float(momentum), float(weight_decay),
+                                   d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
+    _keep_alive((d_l2,), (ws,) + tuple(a for s in slots for a in s[:3]))
+    return d_l2
