@@ -256,7 +256,8 @@ int xdet_resnet_bneck_forward(void* conv_a, void* conv_b, void* conv_c, const fl
                               const float* next_shift, uint16_t* out_hi, uint16_t* out_lo, void* stream);
 /* A (taps,1) [axis 0] or (1,taps) [axis 1] SAME convolution in the DFT domain of the convolved axis (csrc/spectral.hip;
  * the large-separable convs, net/xception_body.py:450-475): forward DFT of every line of the F x F map -> one real GEMM
- * [N*F, 2 Cin] x [2 Cin, 2 Cout] per frequency bin (grouped split-precision GEMM) -> inverse DFT with
+ * [N*F, 2 Cin] x [2 Cin, 2 Cout] per frequency bin (grouped split-precision GEMM; L/2 bins of the shortest even transform
+ * without wrap-around into the F outputs, L >= F + 7: 12 / 19 / 29 bins, which the workspace scales with) -> inverse DFT with
  * out = relu?(y * scale + shift).  kernel_host f32 [taps][cin][cout] (taps odd, <= 15); scale_host / shift_host [cout] or NULL;
  * F must be 16, 30 or 50 and the layer must be created in a split-precision mode (anything else: XDET_ERR_INVALID_ARG, nothing
  * is launched).  in: NHWC f32 [N][F][F][ld_in], ld_in = round_up(cin, 32); out: NHWC f32 [N][F][F][ld_out], ld_out a multiple

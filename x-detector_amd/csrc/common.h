@@ -115,7 +115,11 @@ int launch_depthwise3x3_split(const float* in, const float* w9c, unsigned short*
 
 // ---- spectral large-separable conv: DFT passes around the grouped GEMM (spectral.hip) ----
 bool spectral_supported(int F);
-int spectral_points(int F);
+// Transform length of an F-long axis: the smallest even L >= F + 7 (spectral.hip's header has the argument), sized for
+// the longest kernel SpectralConv::init admits.  The host tables, the block matrices and the kernels' instantiations
+// all take it from here.
+constexpr int kSpectralMaxTaps = 15;
+constexpr int spectral_points(int F) { return (F + kSpectralMaxTaps / 2 + 1) / 2 * 2; }
 void spectral_tables(int F, std::vector<float>* fwd, std::vector<float>* inv);
 void spectral_weights(const float* w, int T, int cin, int cout, int cin_ld, int cout_ld, int F, std::vector<float>* out);
 int launch_dft_fwd(const float* in, int F, int ld, int axis, int N, int m_pad, const float* tab, unsigned short* hi,

@@ -148,16 +148,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_dma_f16_kernel(Co
   auto tile_of = [&](int vb, int& tm0, int& tn0, int& tg) -> bool {
     const int slot = vb >> 3;
     if (p_in.group_rows) {
-      // Grouped GEMM (frequency bins): every group has its own weight matrix, so ALL tiles of a group go to
-      // ONE XCD -- its L2 then holds that group's weights and activations once, instead of eight L2s each
-      // pulling every group's weights over the fabric.  Workgroups are dealt round-robin to the XCDs:
-      // vb & 7 is the XCD, group = 8 * round + XCD, tiles of the group in slot order (N fastest).
+      // Grouped GEMM (frequency bins): every group has its own weight matrix, so the tiles of a group stay
+      // together on an XCD -- its L2 then holds that group's weights and activations once, instead of eight L2s
+      // each pulling every group's weights over the fabric -- and the XCDs get equal shares of the LIVE tiles
+      // (whole groups per XCD leave 19 groups at 3 : 2 across the XCDs, and the fullest XCD is the launch).
+      // The live tiles -- tiles of padding rows only are not enumerated -- are numbered group-major (group, then
+      // M tile, N fastest), and XCD x = vb & 7 takes the q = nvb / 8 = cdiv(live tiles, 8) of them from x * q
+      // on, in slot order: with eight or more groups a group spans at most two XCDs (its weights are fetched
+      // twice at most), and an M tile's N tiles still run back to back.
       const int mt = p_in.group_rows / BM;           // M tiles per group
-      const int tpg = mt * nby;
-      const int g = (slot / tpg) * 8 + (vb & 7);
-      const int w = slot - (slot / tpg) * tpg;
-      if ((int64_t)g * p_in.group_rows >= p_in.M) return false;
-      if (p_in.group_live_rows && (w / nby) * BM >= p_in.group_live_rows) return false;     // a tile of padding rows only
+      const int live = p_in.group_live_rows ? p_in.group_live_rows : p_in.group_rows;
+      const int tpg = ((live + BM - 1) / BM) * nby;  // live tiles per group
+      const int q = nvb >> 3;
+      const int t = (vb & 7) * q + slot;
+      if (slot >= q || t >= (p_in.M / p_in.group_rows) * tpg) return false;
+      const int g = t / tpg;
+      const int w = t - g * tpg;
       tm0 = (g * mt + w / nby) * BM;
       tn0 = (w % nby) * BN;
       tg = g;
@@ -658,7 +664,9 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void conv_dma_deep_kernel(ConvParam
   const int slot = blockIdx.x >> 3;
   int bx, n0;
   ConvParams p = p_in;
-  if (p_in.group_rows) {                           // grouped GEMM: see conv_dma_f16_kernel
+  // grouped GEMM (small batches: one round of workgroups or less): whole groups per XCD, group = 8 * round + XCD, the
+  // tiles of the group in slot order (N fastest) -- not the equal shares of conv_dma_f16_kernel's tile_of
+  if (p_in.group_rows) {
     const int mt = p_in.group_rows / BM;
     const int tpg = mt * nby;
     const int g = (slot / tpg) * 8 + (blockIdx.x & 7);
@@ -927,9 +935,10 @@ static int launch_d(const ConvParams& p, hipStream_t s) {
     if (gbuf_eligible(p)) return launch_d<BM, BN, WAVES_M, WAVES_N, NSPLIT, NSTAGE, false, false, true>(p, s);
   }
   int64_t nvb = cdiv(cdiv(p.M, BM), 8) * 8 * (p.Cout_pad / BN);      // virtual blocks: the tiles, M tiles rounded up to the 8 XCDs
-  if (p.group_rows) {
-    const int64_t groups = p.M / p.group_rows, tpg = (int64_t)(p.group_rows / BM) * (p.Cout_pad / BN);
-    nvb = cdiv(groups, 8) * 8 * tpg;
+  if (p.group_rows) {                                                // grouped: the live tiles, in equal shares per XCD (tile_of)
+    const int64_t live = p.group_live_rows ? p.group_live_rows : p.group_rows;
+    const int64_t groups = p.M / p.group_rows, tpg = cdiv(live, BM) * (p.Cout_pad / BN);
+    nvb = cdiv(groups * tpg, 8) * 8;
   }
   if constexpr (BM == 256 && BN == 256 && (PW || GBUF)) {
     // More than one round of the one-workgroup-per-CU tiles: a workgroup per CU (a multiple of 8: the XCD of a virtual block

@@ -333,6 +333,7 @@ struct ConvLayer : LayerBase {
     if (groups > 1) {
       XDET_REQUIRE(io.in_hi && io.group_rows > 0 && io.group_rows % 128 == 0 && (int64_t)io.group_rows * groups == p.M,
                    "conv(grouped): M must be groups * group_rows, group_rows a multiple of 128, input as planes");
+      XDET_REQUIRE(io.group_live_rows >= 0 && io.group_live_rows <= io.group_rows, "conv(grouped): live rows beyond the group");
       p.group_rows = io.group_rows;
       p.group_wt_stride = (long long)cout_pad * kp;
       p.group_live_rows = io.group_live_rows;
@@ -383,7 +384,7 @@ struct SpectralConv : LayerBase {
   size_t y_floats(int N) const { return (size_t)NB * m_pad(N) * 2 * cout_ld; }
   // w: [T][cin][cout] (the taps along `axis`: 0 = y, 1 = x); scale / shift: [cout] or NULL (ones / zeros)
   int init(const float* w, int T, int cin_, int cout_, int axis_, int F_, const float* scale, const float* shift, int relu_) {
-    XDET_REQUIRE(w && T > 0 && T % 2 == 1 && T <= 15 && cin_ > 0 && cout_ > 0 && (axis_ == 0 || axis_ == 1),
+    XDET_REQUIRE(w && T > 0 && T % 2 == 1 && T <= kSpectralMaxTaps && cin_ > 0 && cout_ > 0 && (axis_ == 0 || axis_ == 1),
                  "spectral conv: an odd number of taps (<= 15) along axis 0 | 1");
     XDET_REQUIRE(spectral_supported(F_), "spectral conv: the feature-map side must be 16, 30 or 50");
     XDET_REQUIRE(g_default_precision != PREC_F32, "spectral conv: needs a split-precision mode");

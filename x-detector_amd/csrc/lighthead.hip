@@ -114,9 +114,9 @@ int LightHeadNet::build_body() {
   s14.cout = 1536; s14.dilation = 2; s14.relu_out = 1;
   XDET_TRY(sep_bn("block14_sepconv1", eps, ST_EXIT, b2, s14, &c3));
   // The large-separable convs run either as direct implicit GEMMs over split planes or in the DFT domain
-  // (spectral.hip: ~5x fewer MFMA FLOPs; one GEMM per frequency bin with M = N*fmap rows).  The spectral form
+  // (spectral.hip: ~6x fewer MFMA FLOPs; one GEMM per frequency bin with M = N*fmap rows).  The spectral form
   // wins at every batch size -- at one image the direct (15,1) conv is a 900-row GEMM with K = 30,720 on 32
-  // workgroups (0.9 ms), the 22 bins are 176 workgroups with K = 4,096 -- so `auto` takes it whenever the
+  // workgroups (0.9 ms), the 19 bins are 304 workgroups of 64 x 64 tiles with K = 4,096 -- so `auto` takes it whenever the
   // feature-map size has a transform instantiated.  Decided per NET, never per call: an image's result
   // does not depend on the batch it arrives in.
   large_sep_spectral = g_default_precision != PREC_F32 && spectral_supported(c3.H) && c3.H == c3.W && large_sep_mode != 1;

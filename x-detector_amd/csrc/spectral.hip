@@ -1,12 +1,19 @@
 // Spectral form of the large-separable convolutions (net/xception_body.py:450-475): a (15,1) / (1,15)
 // SAME convolution is a 1-D correlation along one image axis, i.e. a pointwise product in the DFT
-// domain of that axis.  With L = F + 14 >= F + 15 - 1 points (F = feature-map side) the circular
-// convolution equals the zero-padded linear one, so
+// domain of that axis:
 //
 //     y = IDFT_L( DFT_L(x) . DFT_L(g) ),   g[(7 - t) mod L] = w[t]
 //
-// exactly (in exact arithmetic), and the 15 x Cin x Cout MACs per output pixel of the direct form become
-// L/2 complex bins x 4 x Cin x Cout / F per pixel: 5.2x fewer at F = 30 (22 bins), 3.7x at F = 50.
+// is the circular convolution y[i] = sum_t w[t] x[(i + t - 7) mod L] of the line x, zero beyond its F samples.
+// The layer keeps the outputs i = 0..F-1 only, and output i reads the indices i - 7 .. i + 7, i.e. -7 .. F + 6 over
+// all of them.  The circular sum equals the zero-padded linear one as soon as every such index lands on its own
+// sample or on a zero: F .. F + 6 are zeros when L >= F + 7, and -7 .. -1 wrap to L - 7 .. L - 1, zeros under the
+// same condition.  (L = F + 14 would make the FULL linear convolution alias-free; its other 14 outputs are never
+// kept.)  At L = F + 6 output 0 reads x[F - 1] through tap 0.  spectral_points(F) (common.h) is the smallest even
+// such L -- even, so that the Nyquist bin exists and is real: 24, 38 and 58 points for F = 16, 30 and 50.
+// Exact in exact arithmetic, and the 15 x Cin x Cout MACs per output pixel of the direct form become
+// L/2 complex bins x 4 x Cin x Cout / F per pixel: 15 / (4 * 19 / 30) = 5.9x fewer at F = 30 (19 bins), 6.5x at
+// F = 50 (29 bins), 5.0x at F = 16 (12 bins).
 // The per-bin contractions stay on the split-precision MFMA kernel (conv_mfma_dma.hip, grouped GEMM:
 // bin b = rows [b*m_pad, (b+1)*m_pad) with its own [2Cin x 2Cout] real block matrix [[Gr, Gi], [-Gi, Gr]]);
 // this file holds the two transforms around them:
@@ -149,7 +156,6 @@ __global__ __launch_bounds__(256) void dft_inv_kernel(const float* __restrict__ 
 }
 
 bool spectral_supported(int F) { return F == 16 || F == 30 || F == 50; }
-int spectral_points(int F) { return F + 14; }   // even for every supported F
 
 // host: the DFT tables of one axis length.  fwd/inv: [L/2][2][F] as the kernels read them.
 void spectral_tables(int F, std::vector<float>* fwd, std::vector<float>* inv) {
@@ -231,7 +237,7 @@ static int launch_fwd_t(const float* in, int ld, int axis, int N, int m_pad, con
   const int64_t wgs = cdiv(M, 8) * cdiv(ld / 32, 4);
   const unsigned z = wgs >= 512 ? 1u : wgs >= 256 ? 2u : wgs >= 128 ? 4u : 6u;
   dim3 grid((unsigned)cdiv(M, 8), (unsigned)cdiv(ld / 32, 4), z);
-  hipLaunchKernelGGL((dft_fwd_kernel<F, F + 14>), grid, dim3(256), 0, s, in, ld, axis, M, m_pad, tab, hi, lo);
+  hipLaunchKernelGGL((dft_fwd_kernel<F, spectral_points(F)>), grid, dim3(256), 0, s, in, ld, axis, M, m_pad, tab, hi, lo);
   XDET_LAUNCH_CHECK();
   return XDET_OK;
 }
@@ -241,11 +247,11 @@ static int launch_inv_t(const float* Y, int ldn, int C_ld, int N, int m_pad, con
   const int M = N * F;
   if (cdiv(M, 8) * cdiv(C_ld / 32, 4) < 256) {        // few lines: two workgroups per line
     dim3 grid((unsigned)cdiv(M, 8), (unsigned)cdiv(C_ld / 32, 4), 2);
-    hipLaunchKernelGGL((dft_inv_kernel<F, F + 14, 2>), grid, dim3(256), 0, s, Y, ldn, C_ld, M, m_pad, tab, scale, shift, relu,
+    hipLaunchKernelGGL((dft_inv_kernel<F, spectral_points(F), 2>), grid, dim3(256), 0, s, Y, ldn, C_ld, M, m_pad, tab, scale, shift, relu,
                        out, ldo, axis);
   } else {
     dim3 grid((unsigned)cdiv(M, 8), (unsigned)cdiv(C_ld / 32, 4));
-    hipLaunchKernelGGL((dft_inv_kernel<F, F + 14, 1>), grid, dim3(256), 0, s, Y, ldn, C_ld, M, m_pad, tab, scale, shift, relu,
+    hipLaunchKernelGGL((dft_inv_kernel<F, spectral_points(F), 1>), grid, dim3(256), 0, s, Y, ldn, C_ld, M, m_pad, tab, scale, shift, relu,
                        out, ldo, axis);
   }
   XDET_LAUNCH_CHECK();
