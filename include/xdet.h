@@ -735,7 +735,7 @@ int xdet_add_upsample2(const float* a, int ld_a, const float* b, int ld_b, int N
                        void* stream);
 
 /* ---- the optimizer step (csrc/optimizer.hip): tf.train.MomentumOptimizer with the reference's L2 term over a table of
- * tensors, and the refresh of a forward layer's operands from a kernel in device memory ------------------------------------
+ * tensors, and the refresh of a forward layer's operands from a kernel in device memory (csrc/conv_repack.hip) -------------
  * A slot is one variable: var, grad and accum (the momentum slot) are dense f32 arrays of n elements in device memory; var
  * and accum are updated in place.  decay != 0: the variable is in the L2 set (light_head_rfcn_train.py:420,435).  Per
  * element, every operation an f32 operation rounded on its own (no fused multiply-add):
@@ -776,8 +776,9 @@ int xdet_momentum_step(const xdet_momentum_slot* slots_host, int n_slots, float 
 /* Rewrite, on the device and in place, every operand buffer a conv layer (xdet_conv_create) owns from a dense f32
  * [kh,kw,cin,cout] kernel in device memory: the transposed matrix of the f32 mode, or the per-row power-of-two pre-scale, the
  * f16 hi / lo split, the K-blocked copies, the fp8 x8 copy of a pointwise f16x3 layer and the epilogue scale (the scale the
- * layer was created with times 2^-shift of the row) -- each buffer holds exactly what xdet_conv_create would have made from
- * the same values; padding rows and channels stay +0.  shift_dev (f32 [cout] in device memory, or NULL: kept) replaces the
+ * layer was created with times 2^-shift of the row).  xdet_conv_create makes the buffers by this same repack, from the kernel
+ * it uploads (csrc/conv_repack.hip is the one statement of their layouts), so each buffer holds exactly what xdet_conv_create
+ * would have made from the same values; padding rows and channels stay +0.  shift_dev (f32 [cout] in device memory, or NULL: kept) replaces the
  * epilogue shift.  Two passes over the kernel (the row maxima, then exponent, split and scatter) on `stream`, no
  * synchronisation, nothing read on the host.  Errors -> XDET_ERR_INVALID_ARG with the layer unchanged: a NULL kernel, a
  * grouped or spectral layer, a layer that carries an activation or planes exponent or a planes affine (a calibrated or

@@ -1,6 +1,7 @@
 """The optimizer step's ops on the GPU (csrc/optimizer.hip): xdet_momentum_step against its NumPy statement bit for bit and
 its l2 against float64 within the rounding bound of the documented order; xdet_conv_set_kernel_device and
-xdet_depthwise_set_kernel_device against a layer built from the same values, through every forward door the layer has."""
+xdet_depthwise_set_kernel_device (csrc/conv_repack.hip) against a layer built from the same values, through every forward door
+the layer has (the conv's creation runs the same repack: what its bits must be is tests/test_gpu_conv_operands.py's)."""
 import math
 
 import numpy as np

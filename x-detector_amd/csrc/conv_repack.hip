@@ -1,0 +1,237 @@
+// The operand buffers of a conv layer, made on the device from a dense f32 kernel in device memory: the one statement of
+// their layouts (layers.h names the buffers).  Two callers: ConvLayer::init uploads the kernel it was given and repacks it
+// once, at creation (all groups of a grouped layer in one launch); xdet_conv_set_kernel_device (include/xdet.h) repacks a
+// layer in place from the optimizer's master copy after a step.  Both run the same two kernels, so a refreshed layer and
+// a created one hold the same bits.  The depthwise refresh, xdet_depthwise_set_kernel_device, is here too: its layout is
+// DepthwiseLayer::init's padded host copy, restated in five lines.
+//
+// The repack makes two passes over the kernel [kh*kw][cin][cout] (a row of the transposed matrix, kh*kw*cin_p values of one
+// output channel strided by cout, does not fit in LDS for the 15x1 convs): the largest |w| per output channel (an integer
+// atomicMax on the bits of |w|: a maximum has no order to fix), then per 32 (K) x 64 (cout) tile the exponent, the
+// pre-scale, the hi / lo split and the scatter into every buffer the layer owns.  The tile is read along cout (256 B per
+// K index), transposed through LDS and written along K: 16 B per thread, 64 B per output row of d_wt_hi / d_wt_lo and one
+// contiguous 4 KiB run of the K-blocked copies.  The number formats are layers.h's converters.  The file is compiled with
+// -ffp-contract=off, as it was when these kernels were part of optimizer.hip.
+#include "layers.h"
+
+namespace xdet {
+
+constexpr int RP_T = 256;
+constexpr int RP_CO = 64, RP_K = 32;    // a tile: 64 output channels x one K block
+
+// (arrays "per row": [groups][cout_pad]; a matrix: [groups][cout_pad][kp], K-blocked [groups][kp/32][cout_pad][32])
+struct ConvRepack {
+  const float* w;                       // [groups][taps][cin][cout] dense
+  const float* shift;                   // [groups][cout], or NULL: d_shift stays as it is
+  const float* scale0;                  // per row: the epilogue scale the layer was created with
+  unsigned* mx;                         // per row: bits of the largest |w| (pass 1)
+  float* wt;                            // f32 mode: the matrix
+  unsigned short *hi, *lo, *hi_b, *lo_b;
+  unsigned char* x8_b;
+  float *d_scale, *d_shift;
+  int taps, cin, cout, cin_p, kp, cout_pad;
+};
+
+// the value of row co, column k of group g's padded [cout_pad][kp] matrix: k = tap * cin_p + ci
+__device__ __forceinline__ float repack_source(const ConvRepack& a, int g, int co, int k) {
+  const int tap = k / a.cin_p, ci = k - tap * a.cin_p;
+  return (tap < a.taps && ci < a.cin && co < a.cout) ? a.w[(((size_t)g * a.taps + tap) * a.cin + ci) * a.cout + co] : 0.f;
+}
+
+__global__ __launch_bounds__(RP_T) void conv_repack_max_kernel(ConvRepack a) {
+  const int g = blockIdx.z;
+  const int co = blockIdx.x * RP_CO + (threadIdx.x & (RP_CO - 1));
+  const int k0 = blockIdx.y * RP_K + (threadIdx.x / RP_CO) * (RP_K / 4);
+  if (co >= a.cout) return;
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < RP_K / 4; ++i) {
+    const float f = fabsf(repack_source(a, g, co, k0 + i));
+    m = m < f ? f : m;                  // (std::max's own comparison: a NaN never becomes the maximum)
+  }
+  if (m > 0.f) atomicMax(a.mx + (size_t)g * a.cout_pad + co, __float_as_uint(m));
+}
+
+__global__ __launch_bounds__(RP_T) void conv_repack_kernel(ConvRepack a, int precision) {
+  __shared__ float tile[RP_K][RP_CO + 1];
+  const int tid = threadIdx.x;
+  const int co0 = blockIdx.x * RP_CO, kb = blockIdx.y, g = blockIdx.z;
+  {
+    const int c = tid & (RP_CO - 1), kq = tid / RP_CO;
+#pragma unroll
+    for (int i = 0; i < RP_K / 4; ++i) tile[kq * (RP_K / 4) + i][c] = repack_source(a, g, co0 + c, kb * RP_K + kq * (RP_K / 4) + i);
+  }
+  __syncthreads();
+  const int c = tid >> 2, q = tid & 3;                      // output row co0 + c, columns kb * 32 + q * 8 .. + 7
+  const int co = co0 + c;
+  const size_t grow = (size_t)g * a.cout_pad + co;          // the row among all groups' rows
+  const size_t row = grow * a.kp + (size_t)kb * RP_K + q * 8;
+  if (precision == PREC_F32) {
+    float4 lo4 = make_float4(tile[q * 8 + 0][c], tile[q * 8 + 1][c], tile[q * 8 + 2][c], tile[q * 8 + 3][c]);
+    float4 hi4 = make_float4(tile[q * 8 + 4][c], tile[q * 8 + 5][c], tile[q * 8 + 6][c], tile[q * 8 + 7][c]);
+    *reinterpret_cast<float4*>(a.wt + row) = lo4;
+    *reinterpret_cast<float4*>(a.wt + row + 4) = hi4;
+    if (kb == 0 && q == 0 && a.shift && co < a.cout) a.d_shift[grow] = a.shift[(size_t)g * a.cout + co];
+    return;
+  }
+  // per-output-channel power-of-two pre-scale so that max|w| lands in [512, 1024): w_hi cannot overflow f16 and
+  // w_lo (~2^-11 |w|) stays a normal f16; undone exactly in the epilogue scale
+  const float mx = __uint_as_float(a.mx[grow]);
+  int e = 0;
+  if (mx > 0.f) (void)frexpf(mx, &e);
+  const int sh_k = mx > 0.f ? 10 - e : 0;
+  union { unsigned short h[8]; uint4 v; } H, L;
+  union { unsigned char b[8]; uint2 v; } X_lo, X_hi;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const float wv = ldexpf(tile[q * 8 + i][c], sh_k);
+    const unsigned short h = f32_to_f16_rne(wv);
+    H.h[i] = h;
+    L.h[i] = precision == PREC_F16X3 ? f32_to_f16_rne(wv - f16_to_f32(h)) : (unsigned short)0;
+    if (a.x8_b) {
+      X_lo.b[i] = f32_to_e4m3(ldexpf(f16_to_f32(L.h[i]), 9));
+      X_hi.b[i] = f32_to_e4m3(ldexpf(f16_to_f32(h), -2));
+    }
+  }
+  const size_t brow = ((size_t)g * (a.kp / RP_K) + kb) * a.cout_pad + co;   // the row of K block kb
+  const size_t blk = brow * RP_K + q * 8;
+  if (a.hi) *reinterpret_cast<uint4*>(a.hi + row) = H.v;
+  if (a.lo) *reinterpret_cast<uint4*>(a.lo + row) = L.v;
+  if (a.hi_b) *reinterpret_cast<uint4*>(a.hi_b + blk) = H.v;
+  if (a.lo_b) *reinterpret_cast<uint4*>(a.lo_b + blk) = L.v;
+  if (a.x8_b) {
+    unsigned char* rec = a.x8_b + brow * 64 + q * 8;
+    *reinterpret_cast<uint2*>(rec) = X_lo.v;
+    *reinterpret_cast<uint2*>(rec + 32) = X_hi.v;
+  }
+  if (kb == 0 && q == 0) {
+    a.d_scale[grow] = ldexpf(a.scale0[grow], -sh_k);
+    if (a.shift && co < a.cout) a.d_shift[grow] = a.shift[(size_t)g * a.cout + co];
+  }
+}
+
+// every operand buffer of L from the dense kernel w (device memory); shift NULL: d_shift stays as it is
+static int launch_conv_repack(const ConvLayer& L, const float* w, const float* shift, hipStream_t s) {
+  XDET_REQUIRE(L.cout_pad % RP_CO == 0 && L.kp % RP_K == 0, "conv repack: unexpected padding");
+  ConvRepack a;
+  a.w = w; a.shift = shift; a.scale0 = L.d_repack_scale0; a.mx = L.d_repack_max;
+  a.wt = L.d_wt; a.hi = L.d_wt_hi; a.lo = L.d_wt_lo; a.hi_b = L.d_wt_hi_b; a.lo_b = L.d_wt_lo_b;
+  a.x8_b = reinterpret_cast<unsigned char*>(L.d_wt_x8_b.get());
+  a.d_scale = L.d_scale; a.d_shift = L.d_shift;
+  a.taps = L.kh * L.kw; a.cin = L.cin; a.cout = L.cout; a.cin_p = L.cin_p; a.kp = L.kp; a.cout_pad = L.cout_pad;
+  const dim3 grid((unsigned)(a.cout_pad / RP_CO), (unsigned)(a.kp / RP_K), (unsigned)L.groups);
+  if (L.precision != PREC_F32) {
+    XDET_HIP(hipMemsetAsync(a.mx, 0, (size_t)L.groups * a.cout_pad * sizeof(unsigned), s));
+    hipLaunchKernelGGL(conv_repack_max_kernel, grid, dim3(RP_T), 0, s, a);
+    XDET_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(conv_repack_kernel, grid, dim3(RP_T), 0, s, a, L.precision);
+  XDET_LAUNCH_CHECK();
+  return XDET_OK;
+}
+
+int ConvLayer::init(int kh_, int kw_, int cin_, int cout_, int stride_, int dil_, int pad_mode_, int pad_t_, int pad_l_,
+                    const float* w_hwio, const float* scale, const float* shift, int relu_out_, int groups_) {
+  XDET_REQUIRE(kh_ > 0 && kw_ > 0 && cin_ > 0 && cout_ > 0 && stride_ > 0 && dil_ > 0, "conv: bad geometry");
+  XDET_REQUIRE(groups_ >= 1 && (groups_ == 1 || (kh_ == 1 && kw_ == 1 && stride_ == 1 && cin_ % 32 == 0)),
+               "conv: grouped GEMMs are 1x1, stride 1, cin % 32 == 0");
+  groups = groups_;
+  XDET_REQUIRE(pad_mode_ >= 0 && pad_mode_ <= 2, "conv: pad_mode must be 0|1|2");
+  XDET_REQUIRE(w_hwio != nullptr, "conv: kernel is NULL");
+  kind = 1;
+  kh = kh_; kw = kw_; cin = cin_; cout = cout_; stride = stride_; dil = dil_;
+  pad_mode = pad_mode_; pad_t = pad_t_; pad_l = pad_l_; relu_out = relu_out_;
+  small_cin = cin <= 4;
+  cin_p = small_cin ? 4 : round_up(cin, 32);
+  kp = round_up(kh * kw * cin_p, 32);
+  n_tile = round_up(cout, 64) < round_up(cout, 128) ? 64 : 128;
+  cout_pad = round_up(cout, n_tile);
+  precision = g_default_precision;
+  XDET_REQUIRE(groups == 1 || precision != PREC_F32, "conv: grouped GEMMs need a split-precision mode");
+  XDET_HIP(hipGetDevice(&device));
+  const size_t G = (size_t)groups, mat = (size_t)cout_pad * kp, rows = G * cout_pad;
+  std::vector<float> sc(rows, 0.f), sh(rows, 0.f);          // the creation-time scale and the shift, zero in the padded rows
+  for (size_t g = 0; g < G; ++g)
+    for (int co = 0; co < cout; ++co) {
+      sc[g * cout_pad + co] = scale ? scale[g * cout + co] : 1.f;
+      sh[g * cout_pad + co] = shift ? shift[g * cout + co] : 0.f;
+    }
+  if (precision == PREC_F32) {
+    XDET_TRY(d_wt.alloc(mat));
+    XDET_TRY(d_scale.upload(sc.data(), rows));              // (no pre-scale: the repack leaves it alone)
+  } else {
+    const bool x3 = precision == PREC_F16X3;
+    if (groups == 1) {      // [Cout_pad][Kp] copies: the register-staged kernel (strided / small-cin convs)
+      XDET_TRY(d_wt_hi.alloc(mat));
+      if (x3) XDET_TRY(d_wt_lo.alloc(mat));
+    }
+    if (!small_cin) {       // K-blocked copies: the LDS-DMA kernel
+      XDET_TRY(d_zeros.alloc_zeroed(128));
+      XDET_TRY(d_wt_hi_b.alloc(G * mat));
+      if (x3) XDET_TRY(d_wt_lo_b.alloc(G * mat));
+      if (x3 && kh == 1 && kw == 1 && stride == 1 && groups == 1) XDET_TRY(d_wt_x8_b.alloc(mat));   // a pointwise layer may be fed x8 planes
+    }
+    XDET_TRY(d_repack_scale0.upload(sc.data(), rows));
+    XDET_TRY(d_repack_max.alloc(rows));
+    XDET_TRY(d_scale.alloc(rows));
+  }
+  XDET_TRY(d_shift.upload(sh.data(), rows));
+  DevMem<float> dense;                                      // (freed on return)
+  XDET_TRY(dense.upload(w_hwio, G * kh * kw * cin * cout));
+  XDET_TRY(launch_conv_repack(*this, dense, nullptr, nullptr));
+  XDET_HIP(hipStreamSynchronize(nullptr));
+  // the host copy of the epilogue scale (set_in_exp, the calibration) is the device's own
+  in_scale.host.resize(rows);
+  XDET_HIP(hipMemcpy(in_scale.host.data(), d_scale, rows * sizeof(float), hipMemcpyDeviceToHost));
+  in_scale.dev = d_scale;
+  return XDET_OK;
+}
+
+int ConvLayer::set_kernel_device(const float* k_hwio, const float* shift, hipStream_t s) {
+  XDET_REQUIRE(k_hwio, "conv_set_kernel_device: kernel is NULL");
+  XDET_REQUIRE(groups == 1, "conv_set_kernel_device: a grouped layer's block matrices are not a conv kernel");
+  XDET_REQUIRE(in_exp == 0 && out_exp == 0 && pl_shift.host.empty(),
+               "conv_set_kernel_device: the layer carries an activation or planes exponent or a planes affine (a calibrated or "
+               "net-owned layer): its scale arrays are not the ones it was created with");
+  host_stale = true;
+  return launch_conv_repack(*this, k_hwio, shift, s);
+}
+
+__global__ __launch_bounds__(256) void depthwise_repack_kernel(const float* __restrict__ k, float* __restrict__ w, int C, int ld) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 9 * ld) return;
+  const int t = i / ld, c = i - t * ld;
+  w[i] = c < C ? k[t * C + c] : 0.f;
+}
+
+int DepthwiseLayer::set_kernel_device(const float* k33c1, hipStream_t s) {
+  XDET_REQUIRE(k33c1, "depthwise_set_kernel_device: kernel is NULL");
+  XDET_REQUIRE(out_exp == 0, "depthwise_set_kernel_device: the layer's taps carry an activation pre-scale (a calibrated layer)");
+  host_stale = true;
+  hipLaunchKernelGGL(depthwise_repack_kernel, dim3((unsigned)cdiv(9 * ld, 256)), dim3(256), 0, s, k33c1, d_w.get(), C, ld);
+  XDET_LAUNCH_CHECK();
+  return XDET_OK;
+}
+
+}  // namespace xdet
+
+using namespace xdet;
+
+extern "C" {
+
+int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const float* shift_dev, void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && (b->kind == 1 || b->kind == 3), "not a conv layer");
+  XDET_REQUIRE(b->kind == 1, "conv_set_kernel_device: a spectral layer keeps its kernel as DFT-domain block matrices");
+  DeviceGuard guard(b->device);
+  return static_cast<ConvLayer*>(b)->set_kernel_device(kernel_hwio_dev, shift_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 2, "not a depthwise layer");
+  DeviceGuard guard(b->device);
+  return static_cast<DepthwiseLayer*>(b)->set_kernel_device(k33c1_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// Layer objects of libxdet_hip.so: a convolution / a depthwise 3x3 with their weight re-layouts, and the host-side
-// number-format helpers they share with the plans.
+// Layer objects of libxdet_hip.so: a convolution (its operand buffers are laid out by conv_repack.hip, at creation and at
+// every refresh) / a depthwise 3x3 with its padded taps, and the number-format helpers they share with the plans.
 #pragma once
 #include "common.h"
 #include "device_mem.h"
@@ -26,7 +26,7 @@ struct Pow2Scaled {
 
 extern int g_default_precision;   // precision mode new layers and plans are created in (cabi.hip)
 
-// (the three converters below also run on the device: the operand repack of optimizer.hip makes the same bits with them)
+// (the three converters below run on the device too: the operand repack of conv_repack.hip makes the layers' weights with them)
 __host__ __device__ static inline unsigned short f32_to_f16_rne(float f) {
   unsigned x;
   __builtin_memcpy(&x, &f, 4);
@@ -155,11 +155,11 @@ struct ConvLayer : LayerBase {
     return XDET_OK;
   }
   DevMem<float> d_pl_scale, d_pl_shift;
-  // The operands rebuilt on the device from a dense f32 [kh,kw,cin,cout] kernel in device memory (optimizer.hip): every
-  // buffer above holds what init() would have made of the same values.  scale0: the epilogue scale init() was given, in
-  // front of the rows' pre-scale (its device copy and the row maxima's scratch are made by the first refresh).  Afterwards
-  // in_scale.host no longer describes d_scale: host_stale, and set_in_exp refuses.
-  std::vector<float> scale0;
+  // Every buffer above is filled by the repack of conv_repack.hip from a dense f32 [kh,kw,cin,cout] kernel in device
+  // memory: by init() at creation and again by set_kernel_device, which holds what init() would have made of the same
+  // values.  What the repack keeps between the two (split-precision layers): the epilogue scale init() was given, in
+  // front of the rows' pre-scale, and the row maxima's scratch.  After a refresh in_scale.host no longer describes
+  // d_scale: host_stale, and set_in_exp refuses.
   DevMem<float> d_repack_scale0;
   DevMem<unsigned> d_repack_max;
   bool host_stale = false;
@@ -195,103 +195,11 @@ struct ConvLayer : LayerBase {
     return XDET_OK;
   }
 
-  // groups_ > 1: w_hwio is [groups][cin][cout] (1x1), scale/shift are [groups][cout]
+  // groups_ > 1: w_hwio is [groups][cin][cout] (1x1), scale/shift are [groups][cout].  Allocates the operand buffers of the
+  // layer's precision / small_cin / groups combination, uploads the dense kernel and has the repack fill them
+  // (conv_repack.hip); synchronous: the layer is complete on return
   int init(int kh_, int kw_, int cin_, int cout_, int stride_, int dil_, int pad_mode_, int pad_t_, int pad_l_,
-           const float* w_hwio, const float* scale, const float* shift, int relu_out_, int groups_ = 1) {
-    XDET_REQUIRE(kh_ > 0 && kw_ > 0 && cin_ > 0 && cout_ > 0 && stride_ > 0 && dil_ > 0, "conv: bad geometry");
-    XDET_REQUIRE(groups_ >= 1 && (groups_ == 1 || (kh_ == 1 && kw_ == 1 && stride_ == 1 && cin_ % 32 == 0)),
-                 "conv: grouped GEMMs are 1x1, stride 1, cin % 32 == 0");
-    groups = groups_;
-    XDET_REQUIRE(pad_mode_ >= 0 && pad_mode_ <= 2, "conv: pad_mode must be 0|1|2");
-    XDET_REQUIRE(w_hwio != nullptr, "conv: kernel is NULL");
-    kind = 1;
-    kh = kh_; kw = kw_; cin = cin_; cout = cout_; stride = stride_; dil = dil_;
-    pad_mode = pad_mode_; pad_t = pad_t_; pad_l = pad_l_; relu_out = relu_out_;
-    small_cin = cin <= 4;
-    cin_p = small_cin ? 4 : round_up(cin, 32);
-    kp = round_up(kh * kw * cin_p, 32);
-    n_tile = round_up(cout, 64) < round_up(cout, 128) ? 64 : 128;
-    cout_pad = round_up(cout, n_tile);
-    const size_t G = (size_t)groups, mat = (size_t)cout_pad * kp;
-    std::vector<float> wt(G * mat, 0.f), sc(G * cout_pad, 0.f), sh(G * cout_pad, 0.f);
-    for (size_t g = 0; g < G; ++g) {
-      for (int t = 0; t < kh * kw; ++t)
-        for (int ci = 0; ci < cin; ++ci) {
-          const float* src = w_hwio + ((g * kh * kw + t) * cin + ci) * cout;
-          float* dst = &wt[g * mat + (size_t)t * cin_p + ci];
-          for (int co = 0; co < cout; ++co) dst[(size_t)co * kp] = src[co];
-        }
-      for (int co = 0; co < cout; ++co) {
-        sc[g * cout_pad + co] = scale ? scale[g * cout + co] : 1.f;
-        sh[g * cout_pad + co] = shift ? shift[g * cout + co] : 0.f;
-      }
-    }
-    precision = g_default_precision;
-    XDET_REQUIRE(groups == 1 || precision != PREC_F32, "conv: grouped GEMMs need a split-precision mode");
-    if (groups == 1) scale0 = sc;
-    XDET_HIP(hipGetDevice(&device));
-    if (precision != PREC_F32 && !small_cin) {
-      XDET_TRY(d_zeros.alloc_zeroed(128));
-    }
-    if (precision == PREC_F32) {
-      XDET_TRY(d_wt.upload(wt.data(), wt.size()));
-    } else {
-      // per-output-channel power-of-two pre-scale so that max|w| lands in [512, 1024): w_hi cannot
-      // overflow f16 and w_lo (~2^-11 |w|) stays a normal f16; undone exactly in the epilogue scale
-      std::vector<unsigned short> hi(wt.size()), lo(precision == PREC_F16X3 ? wt.size() : 0);
-      for (size_t gc = 0; gc < G * cout_pad; ++gc) {
-        float* row = &wt[gc * kp];
-        float mx = 0.f;
-        for (int k = 0; k < kp; ++k) mx = std::max(mx, std::fabs(row[k]));
-        int e = 0;
-        if (mx > 0.f) (void)frexpf(mx, &e);
-        const int sh_k = mx > 0.f ? 10 - e : 0;
-        for (int k = 0; k < kp; ++k) {
-          const float wv = ldexpf(row[k], sh_k);
-          const unsigned short h = f32_to_f16_rne(wv);
-          hi[gc * kp + k] = h;
-          if (precision == PREC_F16X3) lo[gc * kp + k] = f32_to_f16_rne(wv - f16_to_f32(h));
-        }
-        sc[gc] = ldexpf(sc[gc], -sh_k);
-      }
-      std::vector<float>().swap(wt);
-      if (groups == 1) {      // [Cout_pad][Kp] copies: the register-staged kernel (strided / small-cin convs)
-        XDET_TRY(d_wt_hi.upload(hi.data(), hi.size()));
-        if (precision == PREC_F16X3) XDET_TRY(d_wt_lo.upload(lo.data(), lo.size()));
-      }
-      if (!small_cin) {       // K-blocked [g][Kp/32][Cout_pad][32] copies: the LDS-DMA kernel
-        std::vector<unsigned short> blk(hi.size());
-        auto kblock = [&](const std::vector<unsigned short>& src) {
-          for (size_t g = 0; g < G; ++g)
-            for (int co = 0; co < cout_pad; ++co) {
-              const unsigned short* r = &src[(g * cout_pad + co) * kp];
-              for (int k = 0; k < kp; ++k) blk[g * mat + ((size_t)(k >> 5) * cout_pad + co) * 32 + (k & 31)] = r[k];
-            }
-        };
-        kblock(hi);
-        XDET_TRY(d_wt_hi_b.upload(blk.data(), blk.size()));
-        if (precision == PREC_F16X3) {
-          kblock(lo);
-          XDET_TRY(d_wt_lo_b.upload(blk.data(), blk.size()));
-          if (kh == 1 && kw == 1 && stride == 1 && groups == 1) {   // a pointwise layer may be fed x8 planes
-            unsigned char* b8 = reinterpret_cast<unsigned char*>(blk.data());
-            for (int co = 0; co < cout_pad; ++co)
-              for (int k = 0; k < kp; ++k) {
-                unsigned char* rec = b8 + ((size_t)(k >> 5) * cout_pad + co) * 64;
-                rec[k & 31] = f32_to_e4m3(std::ldexp(f16_to_f32(lo[(size_t)co * kp + k]), 9));
-                rec[32 + (k & 31)] = f32_to_e4m3(std::ldexp(f16_to_f32(hi[(size_t)co * kp + k]), -2));
-              }
-            XDET_TRY(d_wt_x8_b.upload(blk.data(), blk.size()));
-          }
-        }
-      }
-    }
-    XDET_TRY(d_scale.upload(sc.data(), sc.size()));
-    XDET_TRY(d_shift.upload(sh.data(), sh.size()));
-    in_scale.host = sc;
-    in_scale.dev = d_scale;
-    return XDET_OK;
-  }
+           const float* w_hwio, const float* scale, const float* shift, int relu_out_, int groups_ = 1);
 
   void out_shape(int H, int W, int* Ho, int* Wo, int* pt, int* pl) const {
     if (pad_mode == 1) {
@@ -437,7 +345,7 @@ struct DepthwiseLayer : LayerBase {
   DevMem<float> d_w;
   Pow2Scaled taps;               // d_w and its host copy: a planes-producing depthwise carries its activation pre-scale in them
   int out_exp = 0;
-  bool host_stale = false;       // d_w was rewritten on the device (set_kernel_device, optimizer.hip): taps.host is not d_w
+  bool host_stale = false;       // d_w was rewritten on the device (set_kernel_device, conv_repack.hip): taps.host is not d_w
   int set_kernel_device(const float* k33c1, hipStream_t s);
   int set_out_exp(int e) {       // every partial sum of the FMA chain scales exactly with a power of two
     XDET_REQUIRE(!host_stale, "depthwise: the kernel was refreshed on the device (xdet_depthwise_set_kernel_device): the host "

@@ -35,6 +35,7 @@ SOURCES = [
     ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('pool_backward.hip', ['-ffp-contract=off']),
     ('optimizer.hip', ['-ffp-contract=off']),
+    ('conv_repack.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('plan.hip', []),
