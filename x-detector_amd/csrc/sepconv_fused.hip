@@ -9,7 +9,10 @@
 //   (straight from the accumulators: no LDS bounce)
 //
 // Tiles of 4 rows x 30 pixels (a 128-row GEMM tile with 8 idle rows: 30 + 2 halo pixels are exactly four 1 KB DMA
-// pieces) x 128 or 256 output channels; channel chunks of 32 are the K steps.  Arithmetic and accumulation order are
+// pieces) x 128 or 256 output channels; channel chunks of 32 are the K steps.  The horizontally pooled form (HPOOL)
+// computes 31 pixels per tile row -- 15 pooling windows, tiles still 30 columns apart -- from a 33rd patch pixel that
+// lives in a pad of the patch row (SF_XP below: 4 idle GEMM rows, and 8 / 4 tiles per 237 / 119-pixel row).
+// Arithmetic and accumulation order are
 // exactly those of depthwise3x3_tile_kernel + split + conv_dma_f16_kernel, so the result is bit-identical to the
 // two-kernel form (tests/test_gpu_layers.py).  Wider layers run as 256-wide passes over the same patch (block4_sepconv1:
 // three); the 30 x 30 layers (728 channels) stay on the two-kernel path (profiles/NOTES_r05.md: why).
@@ -84,9 +87,18 @@ __device__ __forceinline__ float sf_relu(float x) {
   return r;
 }
 
-// HPOOL tiles are 28 output columns apart and start pool_pad_l columns left of a multiple of 28: the 30 columns a tile
-// computes then hold every window of its 14 pooled columns (window k = local columns 2k .. 2k+2).
-constexpr int SF_XP = 28;
+// HPOOL tiles are 30 output columns apart and start pool_pad_l columns left of a multiple of 30, and they compute 31
+// valid columns: those hold every window of the tile's 15 pooled columns (window k = local columns 2k .. 2k+2; with
+// 30 valid columns it was 14 windows, 28 columns apart, and 237 / 119 columns took 9 / 5 tiles instead of 8 / 4).
+// Column 30 needs a 33rd patch pixel (input column x0 + 31), which no DMA piece holds: wave 0 fetches it per patch
+// row with a plain buffer load and writes it into the 128-byte pad behind the row's THIRD piece (SF_XCOL_F), where
+// strip 7 -- the only reader -- takes its fifth window pixel.  That pad, not the idle one behind the fourth piece:
+// in 128-byte units from the row's start strip 7's fifth / sixth reads are then 26 / 27 against 27 / 28 of strip 5,
+// the strip that shares its ds_read_b128 lane group -- opposite bank halves, as everywhere else in the stencil; behind
+// the fourth piece they would be 35 / 36: the same halves as strip 5's, a 2-way conflict on both reads.  (The sixth
+// read, patch pixel 24, feeds output column 31 only, which is in no window and is never stored.)
+constexpr int SF_XP = 30;
+constexpr int SF_XCOL_F = 2 * SF_PIECE_F + 8 * 32;   // the 33rd pixel of a patch row: floats from the row's start
 
 // Not split4 (cu_prims.h): the same bits from other instructions.
 // hi = f16(a), lo = f16(a - float(hi)) of four values, as two packed pairs each.  v_fma_mixlo/hi_f16 take the f16 hi half
@@ -117,6 +129,11 @@ __device__ __forceinline__ void sf_split4(f32x4 a, uint2* h, uint2* l) {
 //  asm -- round 5 found window maxima built from a stale register once the BN multiply sat directly in front.)
 __device__ __forceinline__ void sf_permlane32_swap(float& a, float& b) {
   asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+
+// an LDS write next to in-flight LDS DMA (cu_prims.h: why asm); the caller owes the lgkmcnt wait
+__device__ __forceinline__ void sf_ds_write_b128(unsigned addr, f32x4 v) {
+  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -189,9 +206,26 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
     // the chunk's 128 bytes in the scalar offset -- a single wave issues one instruction every ~4-5 clocks, and the
     // per-step address arithmetic (~140 SALU) used to be a third of the producer's step.
     unsigned pvoff[SF_NJ];
+    // HPOOL: the 33rd pixel (input column x0 + 31) of the six patch rows, 8 lanes x 16 B per row, is wave 0's: one
+    // plain buffer_load_dwordx4 per step (same descriptor: a row or column outside the image reads zero) in FRONT of
+    // the step's DMA pieces, and one ds_write_b128 into the same ring slot at the END of the same step behind
+    // `vmcnt(SF_NJ)` -- only the pieces just requested stay in flight, so the producers' counted wait at the top of a
+    // step is the same immediate for every wave -- NSLOT - 2 steps before the barrier that hands the slot to the
+    // stencil.  Lanes 48 .. 63 repeat rows 0 and 1 (same bytes to the same place: no exec mask).
+    const bool xwave = HPOOL && wave == 0;
+    const int xrow = (lane >> 3) < SF_ROWS ? (lane >> 3) : (lane >> 3) - SF_ROWS;
+    const unsigned x_rel = (unsigned)((xrow * SF_ROW_F + SF_XCOL_F + (lane & 7) * 4) * 4);
+    unsigned xvoff = 0xffffffffu;
+    int xslot = 0;
+    f32x4 xcol = {0.f, 0.f, 0.f, 0.f};
     auto tile_offsets = [&](const Coord& c, bool live) {
       const int y0 = c.ty * SF_R, x0 = HPOOL ? c.tx * SF_XP - p.pool_pad_l : c.tx * SF_X;
       const int tile_base = (((c.n * p.H + y0) * p.W + x0) * p.ld) * 4;                 // bytes, < 2^31 (host check)
+      if (xwave) {
+        const bool ok = live && (unsigned)(y0 + xrow - 1) < (unsigned)p.H && x0 + SF_P - 1 < p.W;
+        const int soff = tile_base + ((xrow - 1) * p.W + SF_P - 1) * p.ld * 4;
+        xvoff = ok ? (unsigned)(soff + (lane & 7) * 16) : 0xffffffffu;
+      }
 #pragma unroll
       for (int jj = 0; jj < SF_NJ; ++jj) {
         const int i = wave + 4 * jj;
@@ -203,6 +237,16 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
       }
     };
     auto issue = [&](int chunk, int slot) {
+      if (xwave) {
+        // (s_nop: the descriptor / offset SGPRs may come straight from a v_readfirstlane, a hazard the compiler does
+        //  not see through the asm.  The load is asm so that its wait is the counted one in store_xcol, not a
+        //  compiler-placed vmcnt that would drain the DMA ring)
+        asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen"
+                     : "=v"(xcol)
+                     : "v"(xvoff), "s"(rsrc), "s"(chunk * 128)
+                     : "memory");
+        xslot = slot;
+      }
 #pragma unroll
       for (int jj = 0; jj < SF_NJ; ++jj) {
         const int i = wave + 4 * jj;
@@ -224,8 +268,18 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
         tile_offsets(decode(min(it, p.ntiles - 1)), it < t_end && SF_DO_DMA);
       }
     };
+    const unsigned patch0 = lds_addr(&s_patch[0][0]);
+    auto store_xcol = [&]() {
+      if (xwave) {
+        asm volatile("s_waitcnt vmcnt(%1)" : "+v"(xcol) : "n"(SF_NJ) : "memory");
+        sf_ds_write_b128(patch0 + (unsigned)xslot * (unsigned)(SF_PATCH_F * 4) + x_rel, xcol);
+      }
+    };
 #pragma unroll
-    for (int k = 0; k < NSLOT - 1; ++k) issue_next();
+    for (int k = 0; k < NSLOT - 1; ++k) {
+      issue_next();
+      store_xcol();
+    }
 
     const int c4 = lane & 7, strip = lane >> 3;     // wave = tile row, 4 pixels x 4 channels per lane
     const int pxb = strip * 4;
@@ -240,8 +294,10 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
       wa_k[k] = lds_addr(&s_a[0][0]) +
                 (unsigned)((wave * 32 + (strip & 4) * 4 + k * 4 + (strip & 3)) * 32 + (((c4 >> 1) ^ k) << 3) + (c4 & 1) * 4) * 2u;
     const unsigned t_rel = (unsigned)((wave * SF_ROW_F + pxb * 32 + (pxb >> 3) * 32 + c4 * 4) * 4);
-    const unsigned hi_rel = 512u + ((pxb & 7) == 4 ? 128u : 0u);
-    const unsigned patch0 = lds_addr(&s_patch[0][0]);
+    // fifth / sixth window pixel: 4 pixels on, across the pad where the strip ends a piece; HPOOL's strip 7 (patch
+    // pixels 28 .. 31) finds its fifth, the 33rd pixel, in the pad behind the third piece (SF_XCOL_F)
+    const unsigned hi_rel = HPOOL && strip == 7 ? (unsigned)((SF_XCOL_F - (28 * 32 + 3 * 32)) * 4)
+                                                : 512u + ((pxb & 7) == 4 ? 128u : 0u);
     const unsigned w_base = lds_addr(s_w) + (unsigned)(c4 * 4 * 4);
 
     int rslot = 0, abuf = 0, pchunk = 0;
@@ -322,6 +378,7 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
         ds_write_b64<0>(wa_k[k] + wa_off, h);
         if (SPLIT3) ds_write_b64<8192>(wa_k[k] + wa_off, l);
       }
+      store_xcol();                                  // HPOOL, wave 0: the 33rd column of the patch requested in this step
       SF_STAMP(3);                                   // stencil + A-tile writes issued
       rslot = rslot == NSLOT - 1 ? 0 : rslot + 1;
       abuf ^= 1;
@@ -475,7 +532,7 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
     for (int j = 0; j < 2; ++j) {
       const int co = n0 + wn * 64 + j * 32 + frow;
       lane_off_j[j] = co < p.ldo ? (unsigned)(((HPOOL ? 8 : 4) * fh * p.ldo + co) * 4) : 0xffffffffu;
-      tail_off_j[j] = fh ? 0xffffffffu : lane_off_j[j];       // upper half: windows 6, 7 / columns 30, 31 do not exist
+      tail_off_j[j] = fh ? 0xffffffffu : lane_off_j[j];       // upper half: window 15 / columns 30, 31 do not exist
     }
     if (HPOOL) {
       const int nwin = min(SF_XP / 2, p.Wo - cur.tx * (SF_XP / 2));          // wave-uniform
@@ -522,7 +579,7 @@ __global__ __launch_bounds__(512, 1) void sepconv_pc_kernel(SepFusedParams p) {
           if (interior) {
 #pragma unroll
             for (int kk = 0; kk < 8; ++kk)
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, m[kk]), orsrc, kk < 6 ? lane_off_j[j] : tail_off_j[j],
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, m[kk]), orsrc, kk < 7 ? lane_off_j[j] : tail_off_j[j],
                                                     row_off + kk * p.ldo * 4, 0);
           } else {
 #pragma unroll
