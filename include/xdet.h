@@ -629,6 +629,42 @@ int xdet_conv_backward(const float* x, int ld_x, const float* w, const float* y,
                        int H, int W, int C, int J, int kh, int kw, int relu_in, float* dx, int ld_dx, float* dw, float* db,
                        void* workspace, void* stream);
 
+/* ---- the backward of a convolution at stride 1 or 2, 'VALID' or 'SAME' (csrc/conv_backward_strided.hip; the NumPy statement
+ * of the same contract is xdet.ops.host_conv_backward_strided): the stem convs.  Everything xdet_conv_backward's comment says
+ * holds here -- NHWC and HWIO, g and xe with their NaN rules, channels at or beyond a count never read or written, dx == NULL
+ * skips dx, no synchronisation and no host read, no patch matrix, no float atomics, the same bits from the same call over a
+ * workspace of any contents, a power of two on dy taken out of dx, dw and db exactly -- except the geometry ------------------
+ *   stride 1 or 2; padding 0 = 'VALID', 1 = 'SAME' (pad_mode of xdet_conv_create); dilation 1; kh, kw odd and <= 15.
+ *   x, dx [N,H,W,C] (M = N*H*W pixels);  y, dy [N,Ho,Wo,J] (Mo = N*Ho*Wo pixels);  w, dw [kh,kw,C,J];  db [J].
+ *   'VALID': Ho = floor((H - kh) / stride) + 1, no padding.  'SAME' (TensorFlow's): Ho = ceil(H / stride), total padding
+ *   max((Ho - 1) * stride + kh - H, 0), the smaller half pt in front.  Wo and pl follow the same rules from W and kw.
+ *     dw[a,b,c,j] = sum over n, oh, ow of xe[n, oh*stride + a - pt, ow*stride + b - pl, c] * g[n,oh,ow,j]
+ *     dx[n,h,w,c] = sum over taps (a,b) and j of g[n, (h + pt - a) / stride, (w + pl - b) / stride, j] * w[a,b,c,j], over the
+ *                   taps for which both quotients are integers inside the output map; with relu_in 0 wherever x > 0 is false
+ *     db = column sums of g
+ *   Terms outside the image are absent and their pixels are not read.  Under 'VALID' at stride 2 an input row or column that
+ *   no window covers (the last row of an even H with kh = 3) is never read -- it may hold NaN -- and gets dx exactly +0: dx
+ *   is written completely.
+ * Arithmetic and order of the sums: xdet_conv_backward's.  dx reduces over (tap, j), taps in storage order, in one pipeline
+ *   (at stride 2 a pixel whose parity does not match a tap feeds that tap zeros).  dw's sum over the Mo OUTPUT pixels is cut
+ *   into ranges by xdet_dense_backward's rule with M = Mo, the ranges added in index order.  Two tile shapes:
+ *     kh * kw * C > 32 or J > 32: 128 rows of dw by 32 (J <= 32) or 128 columns, tiles = ceil(kh * kw * C / 128) *
+ *       ceil(J / (J <= 32 ? 32 : 128)), a range summed in pixel order -- xdet_conv_backward's;
+ *     kh * kw * C <= 32 and J <= 32 (block1_conv1: 27 x 32): one tile of 32 x 32, tiles = 1 (up to 512 ranges: the ranges are
+ *       the parallelism).  A range is walked in steps of 128 pixels; the pixels [32 q, 32 q + 32) of every step are summed,
+ *       in pixel order, into quarter q = 0 .. 3, and a range's sum is ((q0 + q1) + q2) + q3.
+ *   db in chunks of max(64, ceil(Mo / 1024)) output pixels added in index order.  At stride 1 'SAME' with kh * kw * C > 32
+ *   (or J > 32) the three results have the bits of xdet_conv_backward; dx and db have them always.
+ * workspace: xdet_conv_backward_strided_workspace_bytes(...) bytes (never 0 inside the limits, 0 outside them); it needs no
+ *   initialisation and may be larger.
+ * Limits: C, J <= 4096; M * max(C, ld_x, ld_dx) < 2^31 and Mo * max(J, ld_y, ld_dy) < 2^31.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: those of xdet_conv_backward, another stride, another padding, a 'VALID'
+ *   geometry with Ho < 1 or Wo < 1. */
+size_t xdet_conv_backward_strided_workspace_bytes(int N, int H, int W, int C, int J, int kh, int kw, int stride, int padding);
+int xdet_conv_backward_strided(const float* x, int ld_x, const float* w, const float* y, int ld_y, const float* dy, int ld_dy,
+                               int N, int H, int W, int C, int J, int kh, int kw, int stride, int padding, int relu_in,
+                               float* dx, int ld_dx, float* dw, float* db, void* workspace, void* stream);
+
 /* ---- batch normalisation over NHWC rows, forward and backward, with batch or moving statistics (csrc/batchnorm.hip; the
  * NumPy statements of the same contract are xdet.ops.host_batch_norm_forward / host_batch_norm_backward).  A tensor is
  * M = N * H * W rows of C channels with a row stride ld >= C; every statistic is per channel -----------------------------

@@ -1,4 +1,4 @@
-// What the backward kernels on the matrix pipe share (dense_backward.hip, conv_backward.hip): the operand pre-pass that
+// What the backward kernels on the matrix pipe share (dense_backward.hip, conv_backward.hip, conv_backward_strided.hip): the operand pre-pass that
 // finds the three power-of-two scales and db, the fold of dW's range slabs, and the CU side of the split-precision GEMM
 // tile -- everything except how an operand element is fetched from global memory, which is each file's own loader.
 //
@@ -58,12 +58,16 @@ static inline DbWorkspace db_layout(WsWalk& w, const DbSums& p, int k_rows, int 
 // The pre-pass of one call (dense_backward.hip): the largest magnitudes of x [M, x_cols] (relu_x: of max(x, 0), where a
 // NaN counts as 0), w [w_rows, J] dense and g = mask(dy, y) [M, J] into ctl[DB_MAX_*] (ctl is zeroed first), their
 // exponents into ctl[DB_EXP_*], db's chunk sums into partial [n_chunks][J] and db itself.
+// A conv whose output map is not its input map has x of its own row count, x_rows (0: M), and may leave input pixels under
+// no window: with x_w > 0 x's rows are the pixels of [x_h, x_w] maps, of which rows below x_hc and columns below x_wc count
+// and the others are not read.
 struct DbPre {
   const float *x, *w, *y, *dy;
   int ld_x, ld_y, ld_dy, M, x_cols, w_rows, J, relu_x;
   int rows_per_chunk, n_chunks;
   unsigned* ctl;
   float* partial;
+  int x_rows, x_h, x_w, x_hc, x_wc;
 };
 int db_launch_prepass(const DbPre& a, float* db, hipStream_t s);
 // dw [n] = slabs [n_ranges][n] added in index order
@@ -73,11 +77,18 @@ static inline int db_vec(const float* p, int ld) { return p && (reinterpret_cast
 
 __device__ __forceinline__ unsigned db_abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
 
-// every thread of the workgroup calls it
+// every thread of the workgroup calls it, once per kernel: the workgroup's maximum, then ONE atomic -- a few thousand
+// atomics on one address take longer than a stem-sized pre-pass needs for its loads
 __device__ __forceinline__ void db_block_max(unsigned v, unsigned* dst) {
+  __shared__ unsigned wave_max[DB_T / 64];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-  if ((threadIdx.x & 63) == 0 && v) atomicMax(dst, v);
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    if (v) atomicMax(dst, v);
+  }
 }
 
 // the power of two that moves a largest magnitude with the f32 bits m into [2^DB_TARGET, 2^(DB_TARGET + 1)); 0 for 0
@@ -89,6 +100,33 @@ __device__ __forceinline__ int db_scale_exp(unsigned m) {
 
 // y > 0 is false for a NaN: the gradient behind a NaN activation is 0
 __device__ __forceinline__ float db_mask(float dy, float y) { return y > 0.f ? dy : 0.f; }
+
+// ---- what the two conv backwards share (conv_backward.hip, conv_backward_strided.hip) ----
+
+constexpr int CB_MAX_TAPS = 15;     // kh, kw
+
+// n / d for n < 2^31 as (umulhi(n, mul) + n) >> shift (Granlund & Montgomery's round-up multiplier)
+struct CbDiv {
+  unsigned mul, shift;
+};
+static inline CbDiv cb_div(unsigned d) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  return {(unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1), l};
+}
+__device__ __forceinline__ int cb_quot(int n, CbDiv d) { return (int)((__umulhi((unsigned)n, d.mul) + (unsigned)n) >> d.shift); }
+
+// four consecutive floats at p, of which `left` exist
+__device__ __forceinline__ void cb_load_row4(const float* __restrict__ p, int left, bool vec, float (&v)[4]) {
+  if (vec && left >= 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < left) v[e] = p[e];
+  }
+}
 
 template <int BN>
 struct DbTile {

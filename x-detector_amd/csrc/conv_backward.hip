@@ -24,19 +24,6 @@
 
 namespace xdet {
 
-constexpr int CB_MAX_TAPS = 15;     // kh, kw
-
-// n / d for n < 2^31 as (umulhi(n, mul) + n) >> shift (Granlund & Montgomery's round-up multiplier)
-struct CbDiv {
-  unsigned mul, shift;
-};
-static CbDiv cb_div(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  return {(unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1), l};
-}
-__device__ __forceinline__ int cb_quot(int n, CbDiv d) { return (int)((__umulhi((unsigned)n, d.mul) + (unsigned)n) >> d.shift); }
-
 struct CbGemm {
   const float *x, *w, *y, *dy;
   int ld_x, ld_y, ld_dy;
@@ -50,18 +37,6 @@ struct CbGemm {
   int64_t range_stride;         // dW: floats between the outputs of two ranges
   int vec_w, vec_dy, vec_y;     // dx: rows may be read as aligned float4
 };
-
-// four consecutive floats at p, of which `left` exist
-__device__ __forceinline__ void cb_load_row4(const float* __restrict__ p, int left, bool vec, float (&v)[4]) {
-  if (vec && left >= 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < left) v[e] = p[e];
-  }
-}
 
 template <int BN>
 __global__ __launch_bounds__(DB_T) void cb_dw_kernel(CbGemm g) {

@@ -44,6 +44,9 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the gradient of max_pooling2d(3, 2, 'same') and blocks 2-4 of the Xception entry flow
                              (net/xception_body.py:260-326) with batch statistics and their backward, from `entry_x` down to
                              the stem's output `stem_out`
+  conv_backward_strided, conv_backward_strided_device, host_conv_backward_strided
+  (xdet.ops)              <- what tf.gradients derives for a conv at stride 1 or 2, 'VALID' or 'SAME': the two stem convs
+                             (net/xception_body.py:243-258), block1_conv1 at stride 2 from the image and block1_conv2
   host_momentum_step, momentum_step_device (xdet.ops); Conv2D.set_kernel_device, DepthwiseConv2D.set_kernel_device;
   MomentumOptimizer, piecewise_learning_rate (xdet.model; the flow backwards' weight_grads='device')
                           <- tf.train.MomentumOptimizer with the L2 term and the learning-rate schedule of

@@ -156,6 +156,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     'xdet_conv_backward_workspace_bytes': (c_size_t, [c_int] * 7),
     'xdet_conv_backward': (c_int, [PF, c_int, PF, PF, c_int, PF, c_int] + [c_int] * 8 + [PF, c_int, PF, PF, c_void_p, c_void_p]),
+    'xdet_conv_backward_strided_workspace_bytes': (c_size_t, [c_int] * 9),
+    'xdet_conv_backward_strided': (c_int, [PF, c_int, PF, PF, c_int, PF, c_int] + [c_int] * 10 + [PF, c_int, PF, PF, c_void_p,
+                                                                                                c_void_p]),
     'xdet_depthwise_backward_workspace_bytes': (c_size_t, [c_int] * 4),
     'xdet_depthwise_backward': (c_int, [PF, c_int, PF, PF, c_int] + [c_int] * 6 + [PF, c_int, PF, c_void_p, c_void_p]),
     'xdet_add_rows': (c_int, [PF, c_int, PF, c_int, PF, c_int, c_int, c_int, c_void_p]),

@@ -11,6 +11,7 @@ from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'host_conv_backward', 'conv_backward_device', 'conv_backward',
+           'host_conv_backward_strided', 'conv_backward_strided_device', 'conv_backward_strided',
            'host_batch_norm_forward', 'host_batch_norm_backward', 'batch_norm_forward_device', 'batch_norm_forward',
            'batch_norm_backward_device', 'batch_norm_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
@@ -221,6 +222,123 @@ def conv_backward(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
     NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [kh,kw,C,J], db [J]) as NumPy
     arrays."""
     d_dx, d_dw, d_db = conv_backward_device(x, w, dy, y, relu_in, with_dx, stream)
+    synchronize(stream)
+    ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
+    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
+    return dx, to_host(d_dw.ptr, ws, np.float32, stream), to_host(d_db.ptr, (ws[-1],), np.float32, stream)
+
+
+# ---- the backward of a conv at stride 1 or 2, 'VALID' or 'SAME' (xdet_conv_backward_strided, csrc/conv_backward_strided.hip) ----
+
+_PADDINGS = {'VALID': 0, 'SAME': 1}          # pad_mode of xdet_conv_create
+
+
+def _strided_geometry(H, W, kh, kw, stride, padding):
+    """-> (Ho, Wo, pt, pl): the output map and the padding in front, by include/xdet.h's rules ('SAME' is TensorFlow's); the
+    refusals that need no tensor come from here"""
+    who = 'conv_backward_strided'
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise InvalidArgumentError(-1, '%s: stride must be 1 or 2, got %r' % (who, stride))
+    if not isinstance(padding, str) or padding not in _PADDINGS:
+        raise InvalidArgumentError(-1, "%s: padding must be 'VALID' or 'SAME', got %r" % (who, padding))
+    if min(kh, kw) <= 0 or kh % 2 == 0 or kw % 2 == 0 or max(kh, kw) > 15:
+        raise InvalidArgumentError(-1, '%s: kernel %d x %d (kh and kw odd and at most 15)' % (who, kh, kw))
+    if padding == 'SAME':
+        Ho, Wo = -(-H // stride), -(-W // stride)
+        return Ho, Wo, max((Ho - 1) * stride + kh - H, 0) // 2, max((Wo - 1) * stride + kw - W, 0) // 2
+    if kh > H or kw > W:
+        raise InvalidArgumentError(-1, "%s: a 'VALID' kernel %d x %d is larger than the map %d x %d" % (who, kh, kw, H, W))
+    return (H - kh) // stride + 1, (W - kw) // stride + 1, 0, 0
+
+
+def host_conv_backward_strided(x, w, dy, y=None, relu_in=False, dtype=np.float32, with_dx=True, stride=1, padding='SAME'):
+    """The NumPy statement of xdet_conv_backward_strided (include/xdet.h): host_conv_backward with stride 1 or 2 and padding
+    'VALID' or 'SAME' (TensorFlow's: the smaller half in front).  x [N,H,W,C], w [kh,kw,C,J], dy and y [N,Ho,Wo,J] ->
+    (dx [N,H,W,C], dw [kh,kw,C,J], db [J]); output pixel (oh, ow) read input pixel (oh*stride + a - pt, ow*stride + b - pl)
+    through tap (a, b).  One matrix product per tap, the taps added in storage order: dw's over the strided view of the padded
+    xe, dx's over g spread out on a zero map of stride `stride` -- an input pixel under no window gets exactly 0 and its x
+    decides nothing.  At stride=1, padding='SAME' these are host_conv_backward's products: the same bits."""
+    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
+    N, H, W, C = x.shape
+    kh, kw, _, J = w.shape
+    s = stride
+    Ho, Wo, pt, pl = _strided_geometry(H, W, kh, kw, s, padding)
+    if dy.shape != (N, Ho, Wo, J):
+        raise InvalidArgumentError(-1, 'conv_backward_strided: dy must be [N,Ho,Wo,J] = %r, got %r' % ((N, Ho, Wo, J), dy.shape))
+    g, xe = dy, x
+    with np.errstate(invalid='ignore'):
+        if y is not None:
+            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
+        if relu_in:
+            xe = np.where(x > 0, x, dtype(0))
+    hs, ws = (Ho - 1) * s + 1, (Wo - 1) * s + 1               # the extent of the output map laid out at the stride
+    xp = np.pad(xe, ((0, 0), (pt, max(hs - 1 + kh - H - pt, 0)), (pl, max(ws - 1 + kw - W - pl, 0)), (0, 0)))
+    g2 = g.reshape(-1, J)
+    dw = np.empty(w.shape, dtype)
+    if with_dx:
+        gz = np.zeros((N, H + kh - 1, W + kw - 1, J), dtype)
+        gz[:, kh - 1 - pt:kh - 1 - pt + hs:s, kw - 1 - pl:kw - 1 - pl + ws:s] = g
+        dx = np.zeros((N * H * W, C), dtype)
+    for a in range(kh):
+        for b in range(kw):
+            dw[a, b] = np.matmul(xp[:, a:a + hs:s, b:b + ws:s].reshape(-1, C).T, g2)
+            if with_dx:
+                dx += np.matmul(gz[:, kh - 1 - a:kh - 1 - a + H, kw - 1 - b:kw - 1 - b + W].reshape(-1, J), w[a, b].T)
+    if not with_dx:
+        return None, dw, g2.sum(axis=0, dtype=dtype)
+    dx = dx.reshape(x.shape)
+    if relu_in:
+        with np.errstate(invalid='ignore'):
+            dx = np.where(x > 0, dx, dtype(0))
+    return dx, dw, g2.sum(axis=0, dtype=dtype)
+
+
+def conv_backward_strided_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, dx=None, workspace=None, stride=1,
+                                 padding='SAME'):
+    """conv_backward_strided with the results left on the GPU: (dx DeviceTensor [N,H,W,C] with x's ld (C for a NumPy x) or
+    None, dw DeviceBuffer [kh,kw,C,J], db DeviceBuffer [J]); nothing is synchronised.  A DeviceTensor w is [kh,kw,C,J] dense.
+    dx: a DeviceTensor [N,H,W,C] to write instead of a new one (with its ld); workspace: a DeviceBuffer of at least
+    xdet_conv_backward_strided_workspace_bytes(N, H, W, C, J, kh, kw, stride, padding) bytes (default: allocated here) -- a
+    chain of calls on one stream then allocates no activation-sized memory per call."""
+    who = 'conv_backward_strided'
+    (N, H, W, C), M, _, x_in = _operand(x, who, 'x', 4)
+    (kh, kw, Cw, J), _, _, w_in = _operand(w, who, 'w', 4)
+    sd, _, _, dy_in = _operand(dy, who, 'dy', 4)
+    if y is not None:
+        sy, _, _, y_in = _operand(y, who, 'y', 4)
+    Ho, Wo, _, _ = _strided_geometry(H, W, kh, kw, stride, padding)
+    if Cw != C or sd != (N, Ho, Wo, J) or (y is not None and sy != (N, Ho, Wo, J)):
+        raise InvalidArgumentError(-1, '%s: x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J] and y [N,Ho,Wo,J] expected with Ho = %d, '
+                                       'Wo = %d (stride %d, %s), got %r'
+                                   % (who, Ho, Wo, stride, padding, [(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else [])))
+    said = ('%s: N*H*W = %d, N*Ho*Wo = %d, C = %d, J = %d (sizes positive, C and J at most 4096, N*H*W * C and N*Ho*Wo * J '
+            'below 2^31)')
+    _check_sizes((M,), (C,), said, (who, M, N * Ho * Wo, C, J))
+    _check_sizes((N * Ho * Wo,), (J,), said, (who, M, N * Ho * Wo, C, J))
+    if isinstance(w_in, DeviceTensor) and w_in.ld != J:
+        raise InvalidArgumentError(-1, '%s: w must be dense on the device (ld %d, J = %d)' % (who, w_in.ld, J))
+    dx = _given(dx, (N, H, W, C), who) if with_dx else None
+    kx, px, ldx = _on_device(x_in, C)
+    kw_, pw, _ = _on_device(w_in, J)
+    kd, pd, ldd = _on_device(dy_in, J)
+    ky, py, ldy = _on_device(y_in, J) if y is not None else (None, None, 0)
+    d_dx = _result(dx, (N, H, W, C), ldx) if with_dx else None
+    d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
+    mode = _PADDINGS[padding]
+    ws = workspace if workspace is not None else DeviceBuffer(
+        lib().xdet_conv_backward_strided_workspace_bytes(N, H, W, C, J, kh, kw, stride, mode))
+    check(lib().xdet_conv_backward_strided(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, stride, mode,
+                                           1 if relu_in else 0, d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx,
+                                           d_dw.ptr, d_db.ptr, ws.ptr, _handle(stream)))
+    _keep_alive((d_dx, d_dw), (kx, kw_, kd, ky, ws))
+    return d_dx, d_dw, d_db
+
+
+def conv_backward_strided(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, stride=1, padding='SAME'):
+    """host_conv_backward_strided on the GPU (xdet_conv_backward_strided): x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J],
+    y [N,Ho,Wo,J] or None as NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None,
+    dw [kh,kw,C,J], db [J]) as NumPy arrays."""
+    d_dx, d_dw, d_db = conv_backward_strided_device(x, w, dy, y, relu_in, with_dx, stream, stride=stride, padding=padding)
     synchronize(stream)
     ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
     dx = d_dx.numpy(stream=stream) if d_dx is not None else None
