@@ -593,7 +593,8 @@ int xdet_dense_backward(const float* x, int ld_x, const float* w, const float* y
                         int K, int J, float* dx, int ld_dx, float* dw, float* db, void* workspace, void* stream);
 
 /* ---- the backward of a stride-1 'SAME' convolution y = act(conv(xe, w) + b), xe = x or max(x, 0), act = identity or ReLU
- * (csrc/conv_backward.hip; the NumPy statement of the same contract is xdet.ops.host_conv_backward).  NHWC, dilation 1,
+ * (csrc/conv_backward.hip: xdet_conv_backward_strided's code at stride 1, 'SAME', always on the 128-row tile of dw; the NumPy
+ * statement of the same contract is xdet.ops.host_conv_backward).  NHWC, dilation 1,
  * zero padding of (kh - 1) / 2 rows and (kw - 1) / 2 columns on either side; M = N * H * W pixels -------------------------
  *   x  f32 [N,H,W,C], pixel stride ld_x          the layer's input (relu_in != 0: the conv read max(x, 0))
  *   w  f32 [kh,kw,C,J] dense                     the kernel as the checkpoint stores it (HWIO), on the device
@@ -629,7 +630,7 @@ int xdet_conv_backward(const float* x, int ld_x, const float* w, const float* y,
                        int H, int W, int C, int J, int kh, int kw, int relu_in, float* dx, int ld_dx, float* dw, float* db,
                        void* workspace, void* stream);
 
-/* ---- the backward of a convolution at stride 1 or 2, 'VALID' or 'SAME' (csrc/conv_backward_strided.hip; the NumPy statement
+/* ---- the backward of a convolution at stride 1 or 2, 'VALID' or 'SAME' (csrc/conv_backward.hip; the NumPy statement
  * of the same contract is xdet.ops.host_conv_backward_strided): the stem convs.  Everything xdet_conv_backward's comment says
  * holds here -- NHWC and HWIO, g and xe with their NaN rules, channels at or beyond a count never read or written, dx == NULL
  * skips dx, no synchronisation and no host read, no patch matrix, no float atomics, the same bits from the same call over a

@@ -3,7 +3,7 @@ tests/test_gpu_conv_strided_backward.py and tests/test_gpu_stem_chain.py on the 
 tests/conv_backward_cases.py.
 
 Shapes (N, H, W, C, J, kh, kw, stride, padding, ReLU behind the conv, ReLU in front of it) are the smallest that reach every
-edge of csrc/conv_backward_strided.hip: a single output pixel with all nine taps live; the stem's first conv (3 channels, stride
+edge of csrc/conv_backward.hip's general geometry: a single output pixel with all nine taps live; the stem's first conv (3 channels, stride
 2, 'VALID') on a map every row of which lies under a window, and on one whose last row and column lie under none; the stem's
 second conv, whose 288 dW rows straddle tiles and taps; 'SAME' at stride 2 with the padding 1/1 and 0/1; 1 x 1 at stride 2, which
 is host_subsample2 in front of the dense layer; 7 x 7; the 32-row dW tile ragged and with two steps per range; dW's ranges

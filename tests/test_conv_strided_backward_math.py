@@ -64,7 +64,7 @@ def test_same_padding_is_tensorflows():
 @pytest.mark.parametrize('name', sorted(CS.SAME_S1_IS_OLD))
 @pytest.mark.parametrize('dtype', [np.float32, f64])
 def test_same_s1_is_old(name, dtype):
-    """stride 1 'SAME' is host_conv_backward, bit for bit, with and without dx"""
+    """stride 1 'SAME' is host_conv_backward (which is this statement at that geometry), bit for bit, with and without dx"""
     from xdet.ops import host_conv_backward, host_conv_backward_strided
     x, w, dy, y, relu_in, stride, padding = CS.make_case(name)
     assert (stride, padding) == (1, 'SAME')

@@ -76,11 +76,11 @@ def test_shapes(name, bar):
     print('worst distance / bar over the shape cases so far: %.4f' % _worst[0])
 
 
-@pytest.mark.parametrize('name', ['ragged_3x3', 'range_cuts_row', 'tall_15x1'])
+@pytest.mark.parametrize('name', ['ragged_3x3', 'range_cuts_row', 'tall_15x1', 'narrow_shape'])
 def test_padding_sentinel_null_dx_and_workspace(name, bar):
     """all four ld wider than their widths with NaN in the padding and in the workspace, a sentinel behind dx's width that
     survives; the same bits as the dense-stride call; dx = NULL leaves dw and db as they are; a larger workspace changes
-    nothing"""
+    nothing.  narrow_shape (conv_backward_cases.MORE): a dW of at most 32 x 32, which this door sums on the 128-row tile"""
     x, w, dy, y, relu_in = CC.make_case(name)
     dense = run_raw(x, w, dy, y, relu_in)
     wide = run_raw(x, w, dy, y, relu_in, pad=(14, 7, 3, 5), ws_extra=4096, poison_ws=True)

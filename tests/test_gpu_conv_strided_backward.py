@@ -1,4 +1,4 @@
-"""xdet_conv_backward_strided (csrc/conv_backward_strided.hip) against the float64 statement
+"""xdet_conv_backward_strided (csrc/conv_backward.hip) against the float64 statement
 (ops.host_conv_backward_strided, pinned by tests/test_conv_strided_backward_math.py), with the metric and the bar of
 tests/conv_strided_backward_cases.py: per output tensor max |got - ref| / max (|A| . |B|) <= max(4 x the f32 statement's
 distance, 3 * 2^-22) = 7.2e-07 (the statement's distance is 1.2e-07, so the floor decides).
@@ -173,7 +173,7 @@ def test_no_reach_across_the_image_border(name, bar):
 
 @pytest.mark.parametrize('name', sorted(CS.SAME_S1_IS_OLD))
 def test_same_s1_is_old(name):
-    """stride 1 'SAME' has xdet_conv_backward's bits: the geometry was generalised, not a second arithmetic written"""
+    """stride 1 'SAME' has xdet_conv_backward's bits: that op is this one's stride-1 'SAME' door onto the same kernels"""
     from xdet.ops import conv_backward
     old = conv_backward(*CC.make_case(CS.SAME_S1_IS_OLD[name]))
     assert same_bits(dense_run(name)[:3], old)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The strided conv backward (csrc/conv_backward_strided.hip): microseconds per call of xdet_conv_backward_strided for the two
+"""The strided conv backward (csrc/conv_backward.hip): microseconds per call of xdet_conv_backward_strided for the two
 stem convs at the training size -- block1_conv1 (3x3 / stride 2 / 'VALID', [N,480,480,3] -> [N,239,239,32], dx not asked for:
 it is the image's gradient) and block1_conv2 (3x3 / 'VALID', -> [N,237,237,64]), both behind a ReLU -- at 8 images and at one,
 event-timed on one stream, legs interleaved with xdet_conv_forward of the same layer (f16x3) in the same run.  Both layers move

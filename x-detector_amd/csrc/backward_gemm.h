@@ -1,6 +1,7 @@
-// What the backward kernels on the matrix pipe share (dense_backward.hip, conv_backward.hip, conv_backward_strided.hip): the operand pre-pass that
+// What the backward kernels on the matrix pipe share (dense_backward.hip, conv_backward.hip): the operand pre-pass that
 // finds the three power-of-two scales and db, the fold of dW's range slabs, and the CU side of the split-precision GEMM
-// tile -- everything except how an operand element is fetched from global memory, which is each file's own loader.
+// tile with its double-buffered step loop -- everything except how an operand element is fetched from global memory,
+// which is each file's own loader.
 //
 // The tile: 128 x BN outputs (BN 128: 2 x 2 waves of 64 x 64; BN 32: 4 x 1 waves of 32 x 32), reduction steps of 32.  A
 // thread holds quads: four consecutive reduction indices of one tile row.  Without TRANS (the reduction index is
@@ -101,7 +102,7 @@ __device__ __forceinline__ int db_scale_exp(unsigned m) {
 // y > 0 is false for a NaN: the gradient behind a NaN activation is 0
 __device__ __forceinline__ float db_mask(float dy, float y) { return y > 0.f ? dy : 0.f; }
 
-// ---- what the two conv backwards share (conv_backward.hip, conv_backward_strided.hip) ----
+// ---- the conv backward's index arithmetic (conv_backward.hip) ----
 
 constexpr int CB_MAX_TAPS = 15;     // kh, kw
 
@@ -209,6 +210,23 @@ __device__ __forceinline__ void db_compute(const u16* stage, f32x16 (&acc)[DbTil
     for (int i = 0; i < T::TM; ++i)
 #pragma unroll
       for (int j = 0; j < T::TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+  }
+}
+
+// The reduction over `nk` steps on two LDS stages: step kt + 1 is requested from global memory while step kt is
+// multiplied, then split into the other stage.  load(kt): the step's operands into the thread's registers; store(stage):
+// those registers into a stage; compute(stage): one step of the product.
+template <class Load, class Store, class Compute>
+__device__ __forceinline__ void db_pipeline(int nk, Load&& load, Store&& store, Compute&& compute) {
+  load(0);
+  store(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const bool more = kt + 1 < nk;
+    if (more) load(kt + 1);
+    compute(kt & 1);
+    if (more) store((kt + 1) & 1);
+    __syncthreads();
   }
 }
 

@@ -173,11 +173,11 @@ __global__ __launch_bounds__(DB_T) void db_gemm_kernel(DbGemm g) {
   const int nk = (r1 - r0 + DB_BK - 1) / DB_BK;
   const int ea = (int)g.ctl[g.ea_slot], eb = (int)g.ctl[g.eb_slot];
 
-  struct Regs {
+  struct {
     float a[A_IT][4], b[B_IT][4], m[A_MASK ? A_IT : B_IT][4];
-  };
+  } r;      // the step in flight
 
-  auto load_global = [&](int kt, Regs& r) {
+  auto load_global = [&](int kt) {
     const int rk = r0 + kt * DB_BK;
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(DB_T) void db_gemm_kernel(DbGemm g) {
         if (g.y) db_load4<TRANS>(g.y, g.ld_y, row, rr, g.Q, r1, g.vec_y, r.m[i]);
     }
   };
-  auto store_lds = [&](int buf, const Regs& r) {
+  auto store_lds = [&](int buf) {
     u16* Ah = db_smem + buf * T::STAGE;
     u16* Bh = Ah + 2 * BM * DB_LDH;
     db_store_quads<BM, A_IT, TRANS>(Ah, Ah + BM * DB_LDH, r.a, A_MASK && g.y ? r.m : nullptr, ea);
@@ -204,18 +204,7 @@ __global__ __launch_bounds__(DB_T) void db_gemm_kernel(DbGemm g) {
   f32x16 acc[T::TM][T::TN];
   db_zero<BN>(acc);
 
-  // step kt + 1 is requested from global memory while step kt is multiplied, then split into the other stage
-  Regs regs;
-  load_global(0, regs);
-  store_lds(0, regs);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) load_global(kt + 1, regs);
-    db_compute<BN>(db_smem + (kt & 1) * T::STAGE, acc);
-    if (more) store_lds((kt + 1) & 1, regs);
-    __syncthreads();
-  }
+  db_pipeline(nk, load_global, store_lds, [&](int buf) { db_compute<BN>(db_smem + buf * T::STAGE, acc); });
 
   float* out = g.out + (int64_t)blockIdx.z * g.range_stride;
   const int back = -(ea + eb);

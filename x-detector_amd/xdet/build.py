@@ -31,7 +31,6 @@ SOURCES = [
     ('losses.hip', ['-ffp-contract=off']),
     ('dense_backward.hip', []),
     ('conv_backward.hip', []),
-    ('conv_backward_strided.hip', []),
     ('batchnorm.hip', ['-ffp-contract=off']),
     ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('pool_backward.hip', ['-ffp-contract=off']),

@@ -151,33 +151,8 @@ def host_conv_backward(x, w, dy, y=None, relu_in=False, dtype=np.float32, with_d
     xe = x, or with relu_in x where x > 0 and 0 elsewhere -> (dx [N,H,W,C], dw [kh,kw,C,J], db [J]) with g = dy, or dy where
     y > 0 and 0 elsewhere (an exact zero and a NaN both give 0, in y and in x); with relu_in dx is 0 wherever x > 0 is
     false.  One matrix product per tap, the taps added in storage order.  dtype float32, or float64: the accuracy yardstick.
-    with_dx=False: dx is None."""
-    x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
-    N, H, W, C = x.shape
-    kh, kw, _, J = w.shape
-    g, xe = dy, x
-    with np.errstate(invalid='ignore'):
-        if y is not None:
-            g = np.where(np.asarray(y, dtype) > 0, dy, dtype(0))
-        if relu_in:
-            xe = np.where(x > 0, x, dtype(0))
-    ph, pw = kh // 2, kw // 2
-    border = ((0, 0), (ph, ph), (pw, pw), (0, 0))
-    xp, gp = np.pad(xe, border), np.pad(g, border)
-    g2 = g.reshape(-1, J)
-    dw = np.empty(w.shape, dtype)
-    dx = np.zeros((N * H * W, C), dtype) if with_dx else None
-    for a in range(kh):
-        for b in range(kw):
-            dw[a, b] = np.matmul(xp[:, a:a + H, b:b + W].reshape(-1, C).T, g2)
-            if with_dx:
-                dx += np.matmul(gp[:, 2 * ph - a:2 * ph - a + H, 2 * pw - b:2 * pw - b + W].reshape(-1, J), w[a, b].T)
-    if with_dx:
-        dx = dx.reshape(x.shape)
-        if relu_in:
-            with np.errstate(invalid='ignore'):
-                dx = np.where(x > 0, dx, dtype(0))
-    return dx, dw, g2.sum(axis=0, dtype=dtype)
+    with_dx=False: dx is None.  It is host_conv_backward_strided's statement at stride 1, 'SAME'."""
+    return host_conv_backward_strided(x, w, dy, y, relu_in, dtype, with_dx, stride=1, padding='SAME')
 
 
 def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, dx=None, workspace=None):
@@ -186,57 +161,24 @@ def conv_backward_device(x, w, dy, y=None, relu_in=False, with_dx=True, stream=N
     dx: a DeviceTensor [N,H,W,C] to write instead of a new one (with its ld); workspace: a DeviceBuffer of at least
     xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw) bytes (default: allocated here) -- a chain of calls on one
     stream then allocates no activation-sized memory per call."""
-    who = 'conv_backward'
-    (N, H, W, C), M, _, x_in = _operand(x, who, 'x', 4)
-    (kh, kw, Cw, J), _, _, w_in = _operand(w, who, 'w', 4)
-    sd, _, _, dy_in = _operand(dy, who, 'dy', 4)
-    bad = Cw != C or sd != (N, H, W, J)
-    if y is not None:
-        sy, _, _, y_in = _operand(y, who, 'y', 4)
-        bad = bad or sy != (N, H, W, J)
-    if bad:
-        raise InvalidArgumentError(-1, 'conv_backward: x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J] and y [N,H,W,J] expected, got %r'
-                                   % ([(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else []),))
-    _check_sizes((M,), (C, J), 'conv_backward: N*H*W = %d, C = %d, J = %d, kernel %d x %d (sizes positive, kh and kw odd '
-                               'and at most 15, C and J at most 4096, N*H*W * max(C, J) below 2^31)', (M, C, J, kh, kw),
-                 also=min(kh, kw) > 0 and kh % 2 == 1 and kw % 2 == 1 and max(kh, kw) <= 15)
-    if isinstance(w_in, DeviceTensor) and w_in.ld != J:
-        raise InvalidArgumentError(-1, 'conv_backward: w must be dense on the device (ld %d, J = %d)' % (w_in.ld, J))
-    dx = _given(dx, (N, H, W, C), who) if with_dx else None
-    kx, px, ldx = _on_device(x_in, C)
-    kw_, pw, _ = _on_device(w_in, J)
-    kd, pd, ldd = _on_device(dy_in, J)
-    ky, py, ldy = _on_device(y_in, J) if y is not None else (None, None, 0)
-    d_dx = _result(dx, (N, H, W, C), ldx) if with_dx else None
-    d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
-    ws = workspace if workspace is not None else DeviceBuffer(lib().xdet_conv_backward_workspace_bytes(N, H, W, C, J, kh, kw))
-    check(lib().xdet_conv_backward(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, 1 if relu_in else 0,
-                                   d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, d_db.ptr, ws.ptr,
-                                   _handle(stream)))
-    _keep_alive((d_dx, d_dw), (kx, kw_, kd, ky, ws))
-    return d_dx, d_dw, d_db
+    return _conv_backward_device('conv_backward', x, w, dy, y, relu_in, with_dx, stream, dx, workspace, 1, 'SAME')
 
 
 def conv_backward(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None):
     """host_conv_backward on the GPU (xdet_conv_backward): x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J], y [N,H,W,J] or None as
     NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None, dw [kh,kw,C,J], db [J]) as NumPy
     arrays."""
-    d_dx, d_dw, d_db = conv_backward_device(x, w, dy, y, relu_in, with_dx, stream)
-    synchronize(stream)
-    ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
-    dx = d_dx.numpy(stream=stream) if d_dx is not None else None
-    return dx, to_host(d_dw.ptr, ws, np.float32, stream), to_host(d_db.ptr, (ws[-1],), np.float32, stream)
+    return _conv_results_to_host(conv_backward_device(x, w, dy, y, relu_in, with_dx, stream), w, stream)
 
 
-# ---- the backward of a conv at stride 1 or 2, 'VALID' or 'SAME' (xdet_conv_backward_strided, csrc/conv_backward_strided.hip) ----
+# ---- the backward of a conv at stride 1 or 2, 'VALID' or 'SAME' (xdet_conv_backward_strided, csrc/conv_backward.hip) ------
 
 _PADDINGS = {'VALID': 0, 'SAME': 1}          # pad_mode of xdet_conv_create
 
 
-def _strided_geometry(H, W, kh, kw, stride, padding):
+def _strided_geometry(H, W, kh, kw, stride, padding, who='conv_backward_strided'):
     """-> (Ho, Wo, pt, pl): the output map and the padding in front, by include/xdet.h's rules ('SAME' is TensorFlow's); the
     refusals that need no tensor come from here"""
-    who = 'conv_backward_strided'
     if isinstance(stride, bool) or stride not in (1, 2):
         raise InvalidArgumentError(-1, '%s: stride must be 1 or 2, got %r' % (who, stride))
     if not isinstance(padding, str) or padding not in _PADDINGS:
@@ -257,7 +199,7 @@ def host_conv_backward_strided(x, w, dy, y=None, relu_in=False, dtype=np.float32
     (dx [N,H,W,C], dw [kh,kw,C,J], db [J]); output pixel (oh, ow) read input pixel (oh*stride + a - pt, ow*stride + b - pl)
     through tap (a, b).  One matrix product per tap, the taps added in storage order: dw's over the strided view of the padded
     xe, dx's over g spread out on a zero map of stride `stride` -- an input pixel under no window gets exactly 0 and its x
-    decides nothing.  At stride=1, padding='SAME' these are host_conv_backward's products: the same bits."""
+    decides nothing.  At stride=1, padding='SAME' this is host_conv_backward."""
     x, w, dy = np.asarray(x, dtype), np.asarray(w, dtype), np.asarray(dy, dtype)
     N, H, W, C = x.shape
     kh, kw, _, J = w.shape
@@ -300,21 +242,43 @@ def conv_backward_strided_device(x, w, dy, y=None, relu_in=False, with_dx=True, 
     dx: a DeviceTensor [N,H,W,C] to write instead of a new one (with its ld); workspace: a DeviceBuffer of at least
     xdet_conv_backward_strided_workspace_bytes(N, H, W, C, J, kh, kw, stride, padding) bytes (default: allocated here) -- a
     chain of calls on one stream then allocates no activation-sized memory per call."""
-    who = 'conv_backward_strided'
+    return _conv_backward_device('conv_backward_strided', x, w, dy, y, relu_in, with_dx, stream, dx, workspace, stride, padding)
+
+
+def conv_backward_strided(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, stride=1, padding='SAME'):
+    """host_conv_backward_strided on the GPU (xdet_conv_backward_strided): x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J],
+    y [N,Ho,Wo,J] or None as NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None,
+    dw [kh,kw,C,J], db [J]) as NumPy arrays."""
+    d = conv_backward_strided_device(x, w, dy, y, relu_in, with_dx, stream, stride=stride, padding=padding)
+    return _conv_results_to_host(d, w, stream)
+
+
+def _conv_backward_device(who, x, w, dy, y, relu_in, with_dx, stream, dx, workspace, stride, padding):
+    """The device door of both conv backwards.  `who` is the door: it names itself in every message and calls its own C entry
+    points, xdet_<who> and xdet_<who>_workspace_bytes -- conv_backward's take no geometry and state the two size rules in the
+    words of a single map."""
     (N, H, W, C), M, _, x_in = _operand(x, who, 'x', 4)
     (kh, kw, Cw, J), _, _, w_in = _operand(w, who, 'w', 4)
     sd, _, _, dy_in = _operand(dy, who, 'dy', 4)
     if y is not None:
         sy, _, _, y_in = _operand(y, who, 'y', 4)
-    Ho, Wo, _, _ = _strided_geometry(H, W, kh, kw, stride, padding)
+    Ho, Wo, _, _ = _strided_geometry(H, W, kh, kw, stride, padding, who)
+    Mo = N * Ho * Wo
+    if who == 'conv_backward':
+        c_geometry = ()
+        expected = 'conv_backward: x [N,H,W,C], w [kh,kw,C,J], dy [N,H,W,J] and y [N,H,W,J] expected, got %r'
+        sizes = ('conv_backward: N*H*W = %d, C = %d, J = %d, kernel %d x %d (sizes positive, kh and kw odd and at most 15, '
+                 'C and J at most 4096, N*H*W * max(C, J) below 2^31)' % (M, C, J, kh, kw))
+    else:
+        c_geometry = (stride, _PADDINGS[padding])
+        expected = ('%s: x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J] and y [N,Ho,Wo,J] expected with Ho = %d, Wo = %d '
+                    '(stride %d, %s), got %%r' % (who, Ho, Wo, stride, padding))
+        sizes = ('%s: N*H*W = %d, N*Ho*Wo = %d, C = %d, J = %d (sizes positive, C and J at most 4096, N*H*W * C and '
+                 'N*Ho*Wo * J below 2^31)' % (who, M, Mo, C, J))
     if Cw != C or sd != (N, Ho, Wo, J) or (y is not None and sy != (N, Ho, Wo, J)):
-        raise InvalidArgumentError(-1, '%s: x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J] and y [N,Ho,Wo,J] expected with Ho = %d, '
-                                       'Wo = %d (stride %d, %s), got %r'
-                                   % (who, Ho, Wo, stride, padding, [(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else [])))
-    said = ('%s: N*H*W = %d, N*Ho*Wo = %d, C = %d, J = %d (sizes positive, C and J at most 4096, N*H*W * C and N*Ho*Wo * J '
-            'below 2^31)')
-    _check_sizes((M,), (C,), said, (who, M, N * Ho * Wo, C, J))
-    _check_sizes((N * Ho * Wo,), (J,), said, (who, M, N * Ho * Wo, C, J))
+        raise InvalidArgumentError(-1, expected % ([(N, H, W, C), (kh, kw, Cw, J), sd] + ([sy] if y is not None else []),))
+    _check_sizes((M,), (C,), sizes, ())
+    _check_sizes((Mo,), (J,), sizes, ())
     if isinstance(w_in, DeviceTensor) and w_in.ld != J:
         raise InvalidArgumentError(-1, '%s: w must be dense on the device (ld %d, J = %d)' % (who, w_in.ld, J))
     dx = _given(dx, (N, H, W, C), who) if with_dx else None
@@ -324,21 +288,18 @@ def conv_backward_strided_device(x, w, dy, y=None, relu_in=False, with_dx=True, 
     ky, py, ldy = _on_device(y_in, J) if y is not None else (None, None, 0)
     d_dx = _result(dx, (N, H, W, C), ldx) if with_dx else None
     d_dw, d_db = DeviceBuffer(kh * kw * C * J * 4), DeviceBuffer(max(J * 4, 16))
-    mode = _PADDINGS[padding]
     ws = workspace if workspace is not None else DeviceBuffer(
-        lib().xdet_conv_backward_strided_workspace_bytes(N, H, W, C, J, kh, kw, stride, mode))
-    check(lib().xdet_conv_backward_strided(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, stride, mode,
-                                           1 if relu_in else 0, d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx,
-                                           d_dw.ptr, d_db.ptr, ws.ptr, _handle(stream)))
+        getattr(lib(), 'xdet_%s_workspace_bytes' % who)(N, H, W, C, J, kh, kw, *c_geometry))
+    check(getattr(lib(), 'xdet_' + who)(px, ldx, pw, py, ldy, pd, ldd, N, H, W, C, J, kh, kw, *c_geometry, 1 if relu_in else 0,
+                                        d_dx.ptr if with_dx else None, d_dx.ld if with_dx else ldx, d_dw.ptr, d_db.ptr,
+                                        ws.ptr, _handle(stream)))
     _keep_alive((d_dx, d_dw), (kx, kw_, kd, ky, ws))
     return d_dx, d_dw, d_db
 
 
-def conv_backward_strided(x, w, dy, y=None, relu_in=False, with_dx=True, stream=None, stride=1, padding='SAME'):
-    """host_conv_backward_strided on the GPU (xdet_conv_backward_strided): x [N,H,W,C], w [kh,kw,C,J], dy [N,Ho,Wo,J],
-    y [N,Ho,Wo,J] or None as NumPy arrays or DeviceTensors (read in place with their ld) -> (dx [N,H,W,C] or None,
-    dw [kh,kw,C,J], db [J]) as NumPy arrays."""
-    d_dx, d_dw, d_db = conv_backward_strided_device(x, w, dy, y, relu_in, with_dx, stream, stride=stride, padding=padding)
+def _conv_results_to_host(results, w, stream):
+    """a device door's (dx or None, dw, db) as NumPy arrays, dw in w's shape"""
+    d_dx, d_dw, d_db = results
     synchronize(stream)
     ws = tuple((w.shape if isinstance(w, DeviceTensor) else np.shape(w)))
     dx = d_dx.numpy(stream=stream) if d_dx is not None else None
