@@ -827,6 +827,51 @@ int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const
  * device memory, padding channels +0.  Errors: a NULL kernel, a layer whose taps carry an activation pre-scale. */
 int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream);
 
+/* ---- the gradient average of data-parallel training (csrc/grad_average.hip; the exchange itself is
+ * xdet_comm_average_gradients in csrc/comm.hip): every rank's gradients become the rank-ordered mean, ahead of the step ------
+ * A slot is one dense f32 gradient of n elements in device memory, updated in place.  The table is the same on every rank.
+ * Flat element space: slot i occupies [o_i, o_i + n_i) with o_0 = 0 and o_{i+1} = o_i + round_up(n_i, 4); the elements between
+ * a slot's end and the next slot's start are padding: +0 in a packed buffer, never written back.  T = o_last +
+ * round_up(n_last, 4).  A chunk is chunk_elems consecutive flat elements, chunk c = [c * chunk_elems, min((c + 1) *
+ * chunk_elems, T)); chunk_elems is a positive multiple of 1024 and at most 2^24 (chunk_elems * 4 bytes <= 64 MiB: the unit one
+ * collective moves per rank); the last chunk is short, and every chunk's length is a multiple of 4.  Both sides of every copy
+ * are then 16-byte aligned whenever the slot's pointer is: accesses are 128-bit wide in such a slot and scalar otherwise.
+ * Per element, with g[r] the element in rank r's slab, every operation an f32 operation rounded on its own (denormals and
+ * signed zeros kept, NaN and inf propagate):
+ *     s = g[0];  for r = 1 .. world-1:  s = s + g[r];   out = s / (float)world
+ * -- the NumPy statement of the same contract is xdet.ops.host_average_gradients, and the calls equal it bit for bit: the sum
+ * runs in rank order on every rank, so every rank ends with the same bits whatever the transport did.
+ * xdet_grad_pack: chunk `chunk` of this rank's flat space -> flat_out (f32 [len(chunk)], device memory, 16-byte aligned).
+ * xdet_grad_reduce_ranks: gathered (f32 [world][len(chunk)], rank-major, device memory, 16-byte aligned) -> the statement
+ *   above, written into the slots' own memory for the elements of that chunk; no other element of a slot is touched.  No
+ *   communicator is involved: any world >= 1 runs in one process.
+ * Both are one launch, one workgroup per run of 4096 flat elements of the chunk; the slot table and the map from runs to
+ * slots are built here and uploaded into the workspace per call, as xdet_momentum_step does.
+ * workspace: xdet_grad_average_workspace_bytes(slots, n_slots, world, chunk_elems) bytes of device memory (0 for a table the
+ *   calls refuse): the two tables and, for world > 1, one packed chunk and `world` gathered chunks, which
+ *   xdet_comm_average_gradients carves from it (the two doors above are handed theirs and use the tables only).  It needs no
+ *   initialisation and may be larger; calls on one stream may reuse it.  Nothing synchronises.
+ * xdet_comm_average_gradients: the whole exchange.  The communicator's stream waits for an event recorded on `stream` (the
+ *   stream the backward ran on); per chunk, on the communicator's stream: pack, ncclAllGather(flat -> gathered, ncclFloat),
+ *   reduce; then ev_done is recorded and `stream` waits for it, so whatever the caller enqueues on `stream` next (the optimizer
+ *   step) sees the averaged gradients.  No host synchronisation: xdet_comm_wait(comm, NULL) is the host wait under the
+ *   watchdog.  world == 1 issues no collective and no launch and leaves the gradients' bits alone.
+ * Limits: at most 65536 slots and 2^22 runs.  Errors -> XDET_ERR_INVALID_ARG before any GPU work, never a skipped slot: a NULL
+ *   or empty table, a slot with a NULL pointer or n <= 0, chunk_elems that is not a positive multiple of 1024 or is above 2^24,
+ *   a chunk index outside the flat space, a NULL workspace, a NULL or misaligned flat_out / gathered, world < 1, a table beyond
+ *   the limits.  A communicator the watchdog aborted -> XDET_ERR_STATE, as for the other collectives. */
+typedef struct {
+  float* grad;
+  int64_t n;
+} xdet_grad_slot;
+size_t xdet_grad_average_workspace_bytes(const xdet_grad_slot* slots_host, int n_slots, int world, int64_t chunk_elems);
+int xdet_grad_pack(const xdet_grad_slot* slots_host, int n_slots, int64_t chunk, int64_t chunk_elems, float* flat_out,
+                   void* workspace, void* stream);
+int xdet_grad_reduce_ranks(const xdet_grad_slot* slots_host, int n_slots, int64_t chunk, int64_t chunk_elems,
+                           const float* gathered, int world, void* workspace, void* stream);
+int xdet_comm_average_gradients(void* comm, const xdet_grad_slot* slots_host, int n_slots, int64_t chunk_elems, void* workspace,
+                                void* stream);
+
 /* ---- the model: lighr_head_model_fn in eval mode (light_head_rfcn_eval.py:364-433) -------
  * Weights enter by TF variable name (scope prefix stripped), TF layouts (HWIO / [in,out]). */
 typedef struct {

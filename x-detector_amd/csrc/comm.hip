@@ -21,8 +21,12 @@
 // must wait for pack k before forward k+1 may overwrite them -- which joins all producer streams once per
 // step.  A caller that alternates between TWO pairs (det_double_buffered != 0: forward k+1 writes the
 // pair that call k-1 packed) waits for pack k-1 instead, which finished a step ago: no join at all.
+//
+// Data-parallel training adds a second exchange on the same stream, xdet_comm_average_gradients (its protocol is drawn above
+// it): per chunk of the gradients a pack, an all-gather and a sum of the slabs in rank order (grad_average.hip).
 #include "common.h"
 #include "device_mem.h"
+#include "grad_average.h"
 
 #include <rccl/rccl.h>
 
@@ -379,6 +383,49 @@ int xdet_comm_allgather_detections(void* comm, const float* det_scores, const fl
   XDET_RCCL(g_rccl.AllGather(packed_local, gathered, (size_t)slots * 5, ncclFloat, c->comm, c->stream));
   XDET_HIP(hipEventRecord(c->ev_done, c->stream));
   ++c->gathers;
+  return XDET_OK;
+}
+
+// Stream protocol of xdet_comm_average_gradients (no host synchronisation):
+//     `stream` (the backward's)                            comm stream
+//       ... backward -> gradients
+//       record ev_in[0]             ------------------->   wait ev_in[0]
+//                                                          tables -> workspace
+//                                                          per chunk: pack, ncclAllGather(flat -> gathered), reduce -> gradients
+//       wait ev_done <-----------------------------------  record ev_done
+//       ... the optimizer step ...
+// The chunks run in order on the one stream, so the packed chunk and the gathered slabs are reused from chunk to chunk and
+// from call to call.
+int xdet_comm_average_gradients(void* comm, const xdet_grad_slot* slots, int n_slots, int64_t chunk_elems, void* workspace,
+                                void* stream) {
+  Comm* c = static_cast<Comm*>(comm);
+  XDET_REQUIRE(c, "comm is NULL");
+  GradPlan plan;
+  size_t bytes = 0;
+  XDET_TRY(grad_plan_check(slots, n_slots, chunk_elems, c->world, "comm_average_gradients", &plan, &bytes));
+  XDET_REQUIRE(workspace, "comm_average_gradients: workspace is NULL");
+  if (c->dead) {
+    set_last_error("comm_average_gradients: the communicator was aborted by the watchdog");
+    return XDET_ERR_STATE;
+  }
+  if (c->world == 1) return XDET_OK;                         // the mean over one rank: nothing moves, nothing is launched
+  DeviceGuard guard(c->device);
+  if (c->ev_in.empty()) {
+    hipEvent_t e;
+    XDET_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    c->ev_in.push_back(e);
+  }
+  hipStream_t producer = reinterpret_cast<hipStream_t>(stream);
+  XDET_HIP(hipEventRecord(c->ev_in[0], producer));
+  XDET_HIP(hipStreamWaitEvent(c->stream, c->ev_in[0], 0));
+  XDET_TRY(grad_plan_upload(slots, n_slots, chunk_elems, c->world, workspace, c->stream, "comm_average_gradients", &plan));
+  for (int64_t k = 0; k < plan.n_chunks; ++k) {
+    XDET_TRY(grad_launch_pack(plan, k, plan.flat, c->stream));
+    XDET_RCCL(g_rccl.AllGather(plan.flat, plan.gathered, (size_t)plan.chunk_len(k), ncclFloat, c->comm, c->stream));
+    XDET_TRY(grad_launch_reduce(plan, k, plan.gathered, c->world, c->stream));
+  }
+  XDET_HIP(hipEventRecord(c->ev_done, c->stream));
+  XDET_HIP(hipStreamWaitEvent(producer, c->ev_done, 0));
   return XDET_OK;
 }
 

@@ -52,6 +52,11 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- tf.train.MomentumOptimizer with the L2 term and the learning-rate schedule of
                              light_head_rfcn_train.py:420-436 over the three flows' variables, and the refresh of their
                              forward layers' operands on the device
+  host_average_gradients, grad_pack_device, grad_reduce_ranks_device, grad_flat_offsets (xdet.ops);
+  Communicator.average_gradients (xdet.dist); MomentumOptimizer.step(grads, lr, comm=...)
+                          <- nothing in the reference (its trainer is one session; xdet_v5_resnet_train.py:144 only
+                             anticipates replicate_model_fn): data-parallel training, every rank's gradients become the
+                             rank-ordered f32 mean, the same bits on every rank, ahead of the step
 The training names above that are marked (xdet.model) are written in xdet/train.py (the stages, their state classes, the
 backwards and the host statements) and re-exported by xdet/model.py, which holds the eval graph and the detector classes.
 The training names marked (xdet.ops) are written in xdet/train_ops.py and re-exported by xdet/ops.py, which holds the eval path.

@@ -53,6 +53,11 @@ class MomentumSlot(ctypes.Structure):
     _fields_ = [('var', c_void_p), ('grad', c_void_p), ('accum', c_void_p), ('n', c_int64), ('decay', c_int)]
 
 
+class GradSlot(ctypes.Structure):
+    """xdet_grad_slot: one gradient of the gradient average -- its device pointer and n elements"""
+    _fields_ = [('grad', c_void_p), ('n', c_int64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/xdet.h declares
 SIGNATURES = {
     'xdet_last_error': (ctypes.c_char_p, []),
@@ -167,6 +172,9 @@ SIGNATURES = {
     'xdet_add_upsample2': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_momentum_step_workspace_bytes': (c_size_t, [ctypes.POINTER(MomentumSlot), c_int]),
     'xdet_momentum_step': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_void_p]),
+    'xdet_grad_average_workspace_bytes': (c_size_t, [ctypes.POINTER(GradSlot), c_int, c_int, c_int64]),
+    'xdet_grad_pack': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_void_p, c_void_p]),
+    'xdet_grad_reduce_ranks': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_int, c_void_p, c_void_p]),
     'xdet_conv_set_kernel_device': (c_int, [c_void_p, PF, PF, c_void_p]),
     'xdet_depthwise_set_kernel_device': (c_int, [c_void_p, PF, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
@@ -217,6 +225,7 @@ SIGNATURES = {
     'xdet_pack_detections': (c_int, [PF, PF, c_int64, PF, c_void_p]),
     'xdet_comm_allgather_detections': (c_int, [c_void_p, PF, PF, c_int, c_int, c_int, PF, PF,
                                                ctypes.POINTER(c_void_p), c_int, c_int]),
+    'xdet_comm_average_gradients': (c_int, [c_void_p, ctypes.POINTER(GradSlot), c_int, c_int64, c_void_p, c_void_p]),
     'xdet_comm_wait': (c_int, [c_void_p, c_void_p]),
     'xdet_comm_allreduce_max': (c_int, [c_void_p, ctypes.POINTER(c_double)]),
     'xdet_comm_barrier': (c_int, [c_void_p]),

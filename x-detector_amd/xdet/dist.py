@@ -94,6 +94,9 @@ class Communicator(object):
         self._bufs = None
         self._turn = 0
         self._last = None
+        self._grad_tables = set()
+        self._grad_ws = None
+        self._grad_keep = None
 
     def info(self):
         from ._lib import lib, check
@@ -148,6 +151,52 @@ class Communicator(object):
         self.wait()
         buf, shape = self._last
         return to_host(buf.ptr, shape, np.float32)
+
+    def average_gradients(self, tensors, stream, chunk_elems=8 << 20, workspace=None):
+        """Data-parallel training: every rank's gradients become the mean over the ranks, in place, ahead of the step.
+        `tensors` is a sequence of dense DeviceTensor / DeviceBuffer gradients, the same table (count and sizes) on every
+        rank; `stream` is the stream the backward ran on.  Per chunk of chunk_elems flat elements (a positive multiple of
+        1024, at most 2^24: 64 MiB per rank and collective) the communicator's stream packs the chunk, all-gathers it and
+        sums the `world` slabs in rank order, s = g[0]; s = s + g[r] for r = 1 .. world-1; s / world, each operation rounded
+        in f32 on its own (xdet_comm_average_gradients, include/xdet.h): every rank ends with the same bits, and they equal
+        xdet.ops.host_average_gradients.  The communicator's stream first waits for `stream`, and `stream` waits for the
+        result, so the optimizer step may be enqueued on `stream` at once; the call itself waits for nothing: wait() is the
+        host wait under the watchdog, wait(stream) the stream's, as for the detections.
+        Before the first exchange of a table (its tuple of sizes) the ranks compare (count, T, CRC32 of the sizes) through
+        allgather_bytes: a mismatch raises InvalidArgumentError on every rank before any gradient moves, where the collective
+        would hang or scramble the data.  The table is remembered: later calls with it synchronise nothing on the host.
+        workspace: a DeviceBuffer of at least xdet_grad_average_workspace_bytes bytes (default: kept by the communicator).
+        world == 1: nothing is launched, the gradients keep their bits."""
+        import struct
+        import zlib
+        from ._lib import lib, check, InvalidArgumentError
+        from . import train_ops
+        from .runtime import DeviceBuffer
+        tensors, table, sizes, total = train_ops._grad_table(tensors, chunk_elems)
+        if stream is None or not hasattr(stream, 'handle'):
+            raise InvalidArgumentError(-1, 'grad_average: stream must be the Stream the gradients were computed on, got %r' % (stream,))
+        if workspace is not None and not isinstance(workspace, DeviceBuffer):
+            raise InvalidArgumentError(-1, 'grad_average: workspace must be a DeviceBuffer')
+        if self.world > 1 and sizes not in self._grad_tables:
+            mine = struct.pack('<qqI', len(sizes), total, zlib.crc32(np.asarray(sizes, '<i8').tobytes()) & 0xffffffff)
+            seen = self.allgather_bytes(mine)
+            if any(b != seen[0] for b in seen):
+                said = ', '.join('rank %d: %d gradients, T = %d, crc %08x' % ((r,) + struct.unpack('<qqI', b)) for r, b in enumerate(seen))
+                raise InvalidArgumentError(-1, 'grad_average: the ranks hold different gradient tables (%s)' % said)
+            self._grad_tables.add(sizes)
+        need = lib().xdet_grad_average_workspace_bytes(table, len(sizes), self.world, int(chunk_elems))
+        if workspace is not None:
+            if workspace.nbytes < need:
+                raise InvalidArgumentError(-1, 'grad_average: workspace must be a DeviceBuffer of at least %d bytes' % need)
+            ws = workspace
+        else:
+            if self._grad_ws is None or self._grad_ws.nbytes < need:
+                if self._grad_ws is not None:
+                    self.wait()                # an exchange in flight still reads the buffer this one replaces
+                self._grad_ws = DeviceBuffer(need)
+            ws = self._grad_ws
+        check(lib().xdet_comm_average_gradients(self.handle, table, len(sizes), int(chunk_elems), ws.ptr, stream.handle))
+        self._grad_keep = (tensors, ws)
 
     def max_over_ranks(self, value):
         from ._lib import lib, check

@@ -984,7 +984,7 @@ class MomentumOptimizer(object):
     def _batch_norms(self):
         return [u.bn for u in self._units()] + [p.bn for p in self._projections()]
 
-    def step(self, grads, lr):
+    def step(self, grads, lr, comm=None):
         """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
         backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
         stream: one xdet_momentum_step over all variables; the refresh of the forward layers (every unit's pointwise and
@@ -993,7 +993,16 @@ class MomentumOptimizer(object):
         body drops it: the kept tensors belong to the old weights, so each *_backward refuses until its training forward has run
         again (the eval body need not: `stem_out` does not depend on these variables).
         -> {'step': the number of steps taken, 'lr': lr, 'l2': sum over the L2 set of sum v^2 / 2 before the update, a float}.
-        Refused ahead of any launch: a missing gradient (by name), a host array, a wrong shape."""
+        Refused ahead of any launch: a missing gradient (by name), a host array, a wrong shape.
+        comm (an xdet.dist.Communicator; data-parallel training, every rank calls step with its own batch's gradients): after
+        those refusals and ahead of xdet_momentum_step, the gradients of `self.variables` are replaced in place, in that order
+        and on the detector's stream, by their mean over the ranks (Communicator.average_gradients: the rank-ordered f32 sum
+        divided by the world size, the same bits on every rank, equal to xdet.ops.host_average_gradients), and the host waits
+        for the exchange with comm.wait() before the step's launches -- a dead peer is then the watchdog's error, not a hang
+        in the step's own synchronisation.  The ranks' variables and momentum slots stay bit-equal as long as they started
+        bit-equal.  What is NOT averaged: each rank's batch-norm moving statistics stay its own (export_weights of any rank
+        gives the same variables, but that rank's statistics), and so do the loss scalars.  The result dict is the same, and
+        `l2` is unchanged.  comm=None: a single process, no communicator is touched."""
         miss = [v for v in self.variables if v not in grads]
         if miss:
             raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradients lack %s' % ', '.join(miss))
@@ -1005,6 +1014,9 @@ class MomentumOptimizer(object):
                                            % (v, tuple(shape), type(g).__name__, getattr(g, 'shape', None)))
         slots = [(self._master[v][0], grads[v], self._slot[v], math.prod(self._master[v][1]), self._decayed[v]) for v in self.variables]
         d = self.det
+        if comm is not None:
+            comm.average_gradients([grads[v] for v in self.variables], d.stream)
+            comm.wait()
         l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws)
         for u in self._units():
             u.pw.set_kernel_device(u.K_pw, stream=d.stream)

@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from ._lib import lib, check, InvalidArgumentError, MomentumSlot
+from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
@@ -16,7 +16,8 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'batch_norm_backward_device', 'batch_norm_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
-           'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device']
+           'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
+           'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
 
 
 # ---- the operand path every door below takes ------------------------------------------------------------------------------
@@ -739,3 +740,147 @@ def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, st
                                    d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
     _keep_alive((d_l2,), (ws,) + tuple(a for s in slots for a in s[:3]))
     return d_l2
+
+
+# ---- the gradient average of data-parallel training (xdet_grad_pack / xdet_grad_reduce_ranks, csrc/grad_average.hip; the
+# ---- exchange is xdet.dist.Communicator.average_gradients) --------------------------------------------------------------------
+
+GRAD_CHUNK_MAX = 1 << 24          # elements of a chunk at most: 64 MiB of f32, what one collective moves per rank
+
+
+def host_average_gradients(per_rank, dtype=np.float32):
+    """The NumPy statement of the gradient average (include/xdet.h): per_rank[r][i] is gradient i of rank r -> a list with,
+    per gradient,
+
+        s = g[0];  for r = 1 .. world-1:  s = s + g[r];   out = s / world
+
+    every operation rounded on its own in `dtype`: float32 is what every rank holds after
+    Communicator.average_gradients, bit for bit; float64 the yardstick.  Refused: no ranks, no gradients, ranks whose counts
+    or shapes differ."""
+    per_rank = [[np.asarray(g, dtype) for g in grads] for grads in per_rank]
+    if not per_rank or not per_rank[0]:
+        raise InvalidArgumentError(-1, 'grad_average: needs at least one rank with at least one gradient')
+    for r, grads in enumerate(per_rank):
+        if len(grads) != len(per_rank[0]):
+            raise InvalidArgumentError(-1, 'grad_average: rank %d holds %d gradients, rank 0 holds %d' % (r, len(grads), len(per_rank[0])))
+        for i, (g, g0) in enumerate(zip(grads, per_rank[0])):
+            if g.shape != g0.shape:
+                raise InvalidArgumentError(-1, 'grad_average: gradient %d has shape %r on rank %d and %r on rank 0' % (i, g.shape, r, g0.shape))
+    world = dtype(len(per_rank))
+    out = []
+    with np.errstate(all='ignore'):
+        for i in range(len(per_rank[0])):
+            s = per_rank[0][i]
+            for grads in per_rank[1:]:
+                s = s + grads[i]
+            out.append(s / world)
+    return out
+
+
+def grad_flat_offsets(sizes):
+    """The flat element space of the gradient average (include/xdet.h) for slots of `sizes` elements -> (offsets, T): slot i
+    occupies [offsets[i], offsets[i] + sizes[i]), every slot starts on a multiple of 4, T is the padded total."""
+    offsets, at = [], 0
+    for n in sizes:
+        offsets.append(at)
+        at += (int(n) + 3) // 4 * 4
+    return offsets, at
+
+
+def _grad_size(a, i):
+    """gradient i of a table: a dense DeviceTensor or a DeviceBuffer of whole floats -> its element count"""
+    if isinstance(a, DeviceTensor):
+        n = math.prod(a.shape)
+        if a.ld != a.shape[-1] or n <= 0:
+            raise InvalidArgumentError(-1, 'grad_average: gradient %d must be dense and hold elements, got shape %r with ld %d' % (i, a.shape, a.ld))
+    elif isinstance(a, DeviceBuffer):
+        n = a.nbytes // 4
+        if a.nbytes % 4 or n <= 0:
+            raise InvalidArgumentError(-1, 'grad_average: gradient %d holds %d bytes, not a positive count of floats' % (i, a.nbytes))
+    else:
+        raise InvalidArgumentError(-1, 'grad_average: gradient %d must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                   % (i, type(a).__name__))
+    if not a.ptr:
+        raise InvalidArgumentError(-1, 'grad_average: gradient %d is a NULL pointer' % i)
+    return n
+
+
+def _grad_table(tensors, chunk_elems):
+    """the checks every door of the gradient average makes ahead of any device work -> (the gradients as a list, xdet_grad_slot table, sizes, T)"""
+    try:
+        tensors = list(tensors)
+    except TypeError:
+        tensors = None
+    if not tensors:
+        raise InvalidArgumentError(-1, 'grad_average: needs a non-empty sequence of gradients')
+    if len(tensors) > 65536:
+        raise InvalidArgumentError(-1, 'grad_average: at most 65536 gradients, got %d' % len(tensors))
+    if isinstance(chunk_elems, bool) or not isinstance(chunk_elems, (int, np.integer)) or chunk_elems <= 0 or chunk_elems % 1024 \
+            or chunk_elems > GRAD_CHUNK_MAX:
+        raise InvalidArgumentError(-1, 'grad_average: chunk_elems must be a positive multiple of 1024, at most 2^24 (64 MiB of f32), '
+                                       'got %r' % (chunk_elems,))
+    sizes = tuple(_grad_size(a, i) for i, a in enumerate(tensors))
+    table = (GradSlot * len(tensors))()
+    for i, (a, n) in enumerate(zip(tensors, sizes)):
+        table[i] = GradSlot(a.ptr, n)
+    return tensors, table, sizes, grad_flat_offsets(sizes)[1]
+
+
+def _grad_chunk(chunk, chunk_elems, total):
+    """-> the length of chunk `chunk`"""
+    n_chunks = -(-total // chunk_elems)
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 0 <= chunk < n_chunks:
+        raise InvalidArgumentError(-1, 'grad_average: chunk %r is outside the %d chunks of %d elements' % (chunk, n_chunks, chunk_elems))
+    return min(chunk_elems, total - chunk * chunk_elems)
+
+
+def _grad_span(buf, what, offset_elems, need_elems):
+    """a caller's chunk buffer: a DeviceBuffer that holds need_elems floats from a 16-byte aligned offset -> pointer"""
+    if not isinstance(buf, DeviceBuffer) or isinstance(offset_elems, bool) or not isinstance(offset_elems, (int, np.integer)) \
+            or offset_elems < 0 or offset_elems % 4 or buf.nbytes < 4 * (offset_elems + need_elems) or not buf.ptr or buf.ptr % 16:
+        raise InvalidArgumentError(-1, 'grad_average: %s must be a 16-byte aligned DeviceBuffer of at least %d floats behind an '
+                                       'offset that is a multiple of 4 elements' % (what, need_elems))
+    return buf.ptr + 4 * offset_elems
+
+
+def _grad_workspace(workspace, table, n, world, chunk_elems):
+    need = lib().xdet_grad_average_workspace_bytes(table, n, world, chunk_elems)
+    if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
+        raise InvalidArgumentError(-1, 'grad_average: workspace must be a DeviceBuffer of at least %d bytes' % need)
+    return workspace if workspace is not None else DeviceBuffer(need)
+
+
+def grad_pack_device(tensors, chunk, chunk_elems, flat_out=None, offset_elems=0, stream=None, workspace=None):
+    """Chunk `chunk` of the flat element space of `tensors` (dense DeviceTensors or DeviceBuffers; xdet_grad_pack) -> flat_out, a
+    DeviceBuffer that holds the chunk's length in floats from element `offset_elems` on (default: allocated here), padding
+    elements +0.  workspace: a DeviceBuffer of at least xdet_grad_average_workspace_bytes(table, 1, chunk_elems) bytes
+    (default: allocated here).  Nothing is synchronised."""
+    tensors, table, sizes, total = _grad_table(tensors, chunk_elems)
+    length = _grad_chunk(chunk, chunk_elems, total)
+    if workspace is not None and not isinstance(workspace, DeviceBuffer):
+        raise InvalidArgumentError(-1, 'grad_average: workspace must be a DeviceBuffer')
+    ptr = _grad_span(flat_out, 'flat_out', offset_elems, length) if flat_out is not None else None
+    ws = _grad_workspace(workspace, table, len(sizes), 1, chunk_elems)
+    if flat_out is None:
+        flat_out = DeviceBuffer(4 * length)
+        ptr = flat_out.ptr
+    check(lib().xdet_grad_pack(table, len(sizes), int(chunk), int(chunk_elems), ptr, ws.ptr, _handle(stream)))
+    _keep_alive((flat_out,), (ws,) + tuple(tensors))
+    return flat_out
+
+
+def grad_reduce_ranks_device(tensors, chunk, chunk_elems, gathered, world, stream=None, workspace=None):
+    """The rank-ordered mean of chunk `chunk` (xdet_grad_reduce_ranks): gathered is a DeviceBuffer of [world][len(chunk)] floats,
+    rank-major; the elements of `tensors` that lie in the chunk become host_average_gradients of the `world` slabs, in place.
+    No communicator is involved.  workspace as for grad_pack_device.  -> tensors; nothing is synchronised."""
+    tensors, table, sizes, total = _grad_table(tensors, chunk_elems)
+    length = _grad_chunk(chunk, chunk_elems, total)
+    if isinstance(world, bool) or not isinstance(world, (int, np.integer)) or world < 1:
+        raise InvalidArgumentError(-1, 'grad_average: world must be a positive integer, got %r' % (world,))
+    if workspace is not None and not isinstance(workspace, DeviceBuffer):
+        raise InvalidArgumentError(-1, 'grad_average: workspace must be a DeviceBuffer')
+    ptr = _grad_span(gathered, 'gathered', 0, world * length)
+    ws = _grad_workspace(workspace, table, len(sizes), 1, chunk_elems)
+    check(lib().xdet_grad_reduce_ranks(table, len(sizes), int(chunk), int(chunk_elems), ptr, int(world), ws.ptr, _handle(stream)))
+    _keep_alive(tensors[:1], (ws, gathered), chain=True)
+    return tensors
