@@ -335,6 +335,89 @@ enum { XDET_RESIZE_NONE = 1, XDET_RESIZE_CENTRAL_CROP = 2, XDET_RESIZE_PAD_AND_R
 int xdet_preprocess_eval_batch(const uint8_t* packed, int64_t packed_bytes, const int64_t* offsets,
                                const int32_t* image_shapes, int N, int out_size, int resize, float* out_nchw,
                                float* bbox_img, void* stream);
+/* ---- JPEG decode: the step in front of the ingest (the reference reads encoded JPEGs: dataset/dataset_common.py:542,
+ * tf.image.decode_image; demo/test.jpg).  Entropy decoding on the host, pixels on the GPU, written straight into the
+ * packed layout above.  The statement every stage equals bit for bit is xdet/jpeg.py (jpeg_info, host_jpeg_coefficients,
+ * host_decode_jpeg); the yardstick of that statement is libjpeg's default decode (Pillow / libjpeg-turbo: ISLOW IDCT,
+ * fancy upsampling where libjpeg applies it), equal byte for byte on the committed fixtures and on a sweep of every size
+ * 1 .. 19 x 1 .. 11 in all three samplings.
+ *
+ * Accepted: baseline sequential DCT (SOF0), 8-bit samples, Huffman coding, ONE interleaved scan, 8-bit quantisation
+ * tables; one component (grayscale, written R = G = B) or three (YCbCr) with luma sampling (1,1), (2,1) or (2,2) and
+ * chroma (1,1), i.e. 4:4:4, 4:2:2, 4:2:0; DRI with RST0-7, byte stuffing (FF 00), fill FF bytes in front of markers; up to
+ * four tables per class; APPn / COM skipped; height and width in 1 .. 8192.  A stream is complete once every MCU has been
+ * decoded: what follows the last MCU (EOI included) is ignored.
+ * Refused with XDET_ERR_INVALID_ARG, each by its own message, before anything is written:
+ *   "progressive JPEG (SOF2) is not supported", "extended sequential JPEG (SOF1) ...", "lossless or hierarchical JPEG
+ *   (SOFn) ...", "arithmetic coding (SOFn / DAC) ..."; "N-bit samples are not supported (8-bit only)"; "16-bit quantisation
+ *   tables are not supported"; "N components are not supported (1 or 3)"; "sampling factors HxV of component i are not
+ *   supported (4:4:4, 4:2:2, 4:2:0 only)"; "non-interleaved or multiple scans are not supported"; "spectral selection or
+ *   successive approximation in a baseline scan"; "an Adobe APP14 marker with transform 0 (RGB data) is not supported" and
+ *   "components named R, G, B (RGB data) ..." (both without a JFIF marker, as libjpeg decides); "height 0 (DNL) is not
+ *   supported", "DNL marker is not supported", "width 0", "images beyond 8192 x 8192 ..."; "missing quantisation table t",
+ *   "missing DC / AC Huffman table t"; "bad Huffman table" (a code that does not fit its length); "undefined Huffman code";
+ *   "truncated data" (any read past the end of the data, in the markers or in the entropy-coded bits: a bit behind the
+ *   last data byte of a restart interval is never invented); "restart marker missing or out of sequence"; "coefficient
+ *   index past 63"; "DC difference category past 11"; "not a JPEG (no SOI marker)", "a marker is expected", "a second SOI
+ *   marker", "no scan (EOI in front of SOS)", "more than one frame header (SOF)", "a scan without a frame header",
+ *   "malformed <name> segment".
+ *
+ * The arithmetic (int32, two's complement: products and sums wrap, >> is arithmetic; nothing wraps on a valid image):
+ *   entropy   DC = running sum of the differences per component and restart interval, kept as int16 (wrapping); AC values
+ *             at their natural (de-zigzagged) index; a ZRL that runs past 63 ends the block, a coefficient past 63 refuses.
+ *   IDCT      x = coef * q; jidctint.c with CONST_BITS 13, PASS1_BITS 2: even part z1 = (x2+x6)*4433, t2 = z1 - x6*15137,
+ *             t3 = z1 + x2*6270, t0 = (x0+x4)<<13, t1 = (x0-x4)<<13; odd part on (x7,x5,x3,x1) with z5 = (z3+z4)*9633 and
+ *             the constants 2446, 16819, 25172, 12299, -7373, -20995, -16069, -3196.  Pass 1 over columns, (v + 1024) >> 11;
+ *             pass 2 over rows, (v + (1<<17)) >> 18; range limit y = (v + 128) & 1023: y < 256 -> y, y < 640 -> 255, else 0.
+ *   chroma    on the component's true size cw x ch = ceil(W/hs) x ceil(H/vs), never the block padding.  With more than two
+ *             chroma columns (cw > 2) libjpeg's fancy upsampling, the edge row / column replicated:
+ *             4:2:0: s = 3*p[r] + p[r-1] for output row 2r, 3*p[r] + p[r+1] for row 2r+1; out[2c] = (3*s[c] + s[c-1] + 8) >> 4,
+ *             out[2c+1] = (3*s[c] + s[c+1] + 7) >> 4.  4:2:2: out[2c] = (3*p[c] + p[c-1] + 1) >> 2, out[2c+1] = (3*p[c] +
+ *             p[c+1] + 2) >> 2, the first and the last column of the 2*cw-wide row the input's own values.
+ *             With one or two chroma columns (cw <= 2, i.e. W <= 4) libjpeg does not filter (jdsample.c takes the fancy
+ *             routines only for downsampled_width > 2): plain replication in both directions, out[y][x] = p[y / vs][x / 2].
+ *   colour    cb, cr centred at 0: R = Y + ((91881*cr + 32768) >> 16), B = Y + ((116130*cb + 32768) >> 16),
+ *             G = Y + ((-22554*cb - 46802*cr + 32768) >> 16), each clamped to 0 .. 255.
+ *
+ * xdet_jpeg_desc: what the marker parser knows of an image.  blocks_x / blocks_y: a component's block grid padded to whole
+ * MCUs; coef_offset[c]: the index of component c's first block in the image's coefficient buffer (component-major, then
+ * rows of blocks); quant[c]: its quantisation table in natural order. */
+typedef struct xdet_jpeg_desc {
+  int32_t height, width, components, h_samp, v_samp, restart_interval, mcus_x, mcus_y;
+  int32_t blocks_x[3], blocks_y[3];
+  int64_t coef_offset[3];
+  int64_t total_blocks;
+  uint16_t quant[3][64];
+} xdet_jpeg_desc;
+/* the markers up to SOS -> *desc.  Host only: no device is touched. */
+int xdet_jpeg_info(const uint8_t* data_host, int64_t length, xdet_jpeg_desc* desc);
+/* the entropy stage of one image.  Host only, usable without a GPU.  coefficients_host: int16 [capacity_blocks][64];
+ * block b of the image (desc->coef_offset, above) in natural order, NOT dequantised.  Every block of the padded grids is
+ * written; on a refusal the buffer's contents are undefined. */
+int xdet_jpeg_entropy_decode(const uint8_t* data_host, int64_t length, int16_t* coefficients_host, int64_t capacity_blocks,
+                             xdet_jpeg_desc* desc);
+/* bytes of the workspace xdet_jpeg_decode_batch needs for N images, from their descriptors (xdet_jpeg_info's, nothing is
+ * parsed again): coefficients, the block table, tables and descriptors, the uint8 component planes.  0 = a refusal. */
+size_t xdet_jpeg_decode_workspace_bytes(const xdet_jpeg_desc* descs, int N);
+/* N (1 .. 65535) encoded images and their descriptors (descs[n] as xdet_jpeg_info wrote it for datas_host[n]) -> packed:
+ * the decoded uint8 HWC images back to back, image n at offsets[n] = 3 * sum of H*W of the images before it; offsets
+ * i64 [N] and image_shapes i32 [N][2] (device, either may be NULL) are written too -- the three buffers
+ * xdet_preprocess_eval_batch, xdet_preprocess_train_batch and xdet_net_forward_u8 read.
+ * Sizes and offsets come from the descriptors; each image is parsed once more, by the thread that decodes it (the Huffman
+ * tables live there), and a descriptor that is not the one its image gives is refused like a bad stream.  The entropy
+ * streams are decoded on at most `threads` host threads (clamped to 1 .. 16 and to N; never sized from the machine), one
+ * image per thread at a time, into pinned staging that the library owns: one buffer per device (the device current at the
+ * call, which must be `stream`'s), grown on demand and kept at its high-water mark until the process ends (the front of
+ * the workspace: 136 bytes per block, up to about 4.5 GB at the 2^31-byte plane limit), reused from call to call (calls on
+ * one device are serialised on it; a call waits for the copy of the call before).  Then one host-to-device copy, and
+ * jpeg_idct_kernel (all blocks of the batch, one launch) and jpeg_color_kernel on `stream`; the call does not wait for
+ * them.  Every refusal -- as "images[n]: <message>" with the lowest such n -- comes before the first copy: a batch decodes
+ * whole or not at all.  Bytes of packed outside the images are not written.
+ * workspace: 256-byte aligned, at least xdet_jpeg_decode_workspace_bytes, and alive until the kernels have run.  The host
+ * work makes the call unfit for stream capture; the kernels it enqueues precede a captured forward on the same stream. */
+int xdet_jpeg_decode_batch(const uint8_t* const* datas_host, const int64_t* lengths, const xdet_jpeg_desc* descs, int N,
+                           int threads, uint8_t* packed, int64_t packed_bytes, int64_t* offsets, int32_t* image_shapes,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* Training ingest: light_head_preprocess_for_train (preprocessing/common_preprocessing.py:328-381) for N decoded images
  * of any sizes and their ground truth, in one call: random colour distortion (distort_color, fast_mode=False, :212-262),
  * SSD expand and patch sampling (tf_image.py:602-630, 547-571, 393-545), random horizontal flip (tf_image.py:322-346),

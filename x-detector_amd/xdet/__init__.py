@@ -57,6 +57,11 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- nothing in the reference (its trainer is one session; xdet_v5_resnet_train.py:144 only
                              anticipates replicate_model_fn): data-parallel training, every rank's gradients become the
                              rank-ordered f32 mean, the same bits on every rank, ahead of the step
+  jpeg_info, host_jpeg_coefficients, host_decode_jpeg, decode_jpegs_device, decode_jpegs (xdet.jpeg);
+  LightHeadDetector.detect_jpegs (xdet.model)
+                          <- tf.image.decode_image in front of the eval and training pipelines (dataset/dataset_common.py:542)
+                             and the demo's demo/test.jpg: baseline JPEG, entropy decoding on the host, IDCT, upsampling and
+                             colour conversion on the GPU, written into the packed batch the ingest reads
 The training names above that are marked (xdet.model) are written in xdet/train.py (the stages, their state classes, the
 backwards and the host statements) and re-exported by xdet/model.py, which holds the eval graph and the detector classes.
 The training names marked (xdet.ops) are written in xdet/train_ops.py and re-exported by xdet/ops.py, which holds the eval path.
@@ -72,7 +77,7 @@ from . import augment                                                         # 
 
 def __getattr__(name):
     import importlib
-    modules = ('ops', 'train_ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets', 'losses')
+    modules = ('ops', 'train_ops', 'model', 'resnet', 'runtime', 'evaluation', 'targets', 'losses', 'jpeg')
     if name in modules:           # `from . import ops` inside the package asks here first: the module itself, and no other
         return importlib.import_module('.' + name, __name__)
     for mod in modules:

@@ -58,6 +58,16 @@ class GradSlot(ctypes.Structure):
     _fields_ = [('grad', c_void_p), ('n', c_int64)]
 
 
+class JpegDesc(ctypes.Structure):
+    """xdet_jpeg_desc: what the marker parser knows of one baseline JPEG -- size, components, the luma's sampling factors,
+    restart interval, MCU grid, per component its block grid (padded to whole MCUs), the offset of its blocks (in blocks)
+    inside the image's coefficient buffer, and its quantisation table in natural order"""
+    _fields_ = [('height', c_int), ('width', c_int), ('components', c_int), ('h_samp', c_int), ('v_samp', c_int),
+                ('restart_interval', c_int), ('mcus_x', c_int), ('mcus_y', c_int), ('blocks_x', c_int * 3),
+                ('blocks_y', c_int * 3), ('coef_offset', c_int64 * 3), ('total_blocks', c_int64),
+                ('quant', (ctypes.c_uint16 * 64) * 3)]
+
+
 # name -> (restype, argtypes); must list every symbol include/xdet.h declares
 SIGNATURES = {
     'xdet_last_error': (ctypes.c_char_p, []),
@@ -122,6 +132,12 @@ SIGNATURES = {
     'xdet_preprocess_train_workspace_bytes': (c_size_t, [c_int, c_int]),
     'xdet_preprocess_train_batch': (c_int, [c_void_p, c_int64, c_void_p, PI, PI, PF, PI, PI, c_int, c_int, c_int, ctypes.c_uint32,
                                             PF, PI, PF, PI, c_void_p, c_void_p, c_void_p]),
+    'xdet_jpeg_info': (c_int, [ctypes.c_char_p, c_int64, ctypes.POINTER(JpegDesc)]),
+    'xdet_jpeg_entropy_decode': (c_int, [ctypes.c_char_p, c_int64, c_void_p, c_int64, ctypes.POINTER(JpegDesc)]),
+    'xdet_jpeg_decode_workspace_bytes': (c_size_t, [ctypes.POINTER(JpegDesc), c_int]),
+    'xdet_jpeg_decode_batch': (c_int, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int64), ctypes.POINTER(JpegDesc), c_int, c_int,
+                                       c_void_p, c_int64,
+                                       c_void_p, PI, c_void_p, c_size_t, c_void_p]),
     'xdet_nchw_to_nhwc4': (c_int, [PF, PF, c_int, c_int, c_int, c_int, c_void_p]),
     'xdet_rpn_decode': (c_int, [PF, c_int, c_int, c_int, c_int, c_int, c_int, c_int, PF, PF, PF, PF, c_void_p]),
     'xdet_proposals_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),

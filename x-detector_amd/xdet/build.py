@@ -39,6 +39,7 @@ SOURCES = [
     ('grad_average.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
+    ('jpeg.hip', ['-ffp-contract=off']),
     ('plan.hip', []),
     ('lighthead.hip', []),
     ('resnet_trunk.hip', []),

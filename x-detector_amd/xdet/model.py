@@ -289,6 +289,30 @@ class LightHeadDetector(object):
         n = len(imgs)
         if before_upload is not None:
             before_upload(n)
+
+        def upload(bufs):
+            h = self.stream.handle
+            check(lib().xdet_memcpy_h2d(bufs['packed'].ptr, _host(packed), packed.nbytes, h))
+            check(lib().xdet_memcpy_h2d(bufs['offsets'].ptr, _host(offsets), offsets.nbytes, h))
+            check(lib().xdet_memcpy_h2d(bufs['shapes'].ptr, _host(shapes), shapes.nbytes, h))
+            self._host_keep = (packed, offsets, shapes)  # (referenced until the next call: nothing waits for the copies here)
+        return self._forward_u8(n, mode, packed.nbytes, upload, use_graph)
+
+    def _forward_u8(self, n, mode, packed_nbytes, fill, use_graph):
+        """The ingest doors' common tail: fill(bufs) puts n images of packed_nbytes bytes into the ingest's device buffers
+        ('packed', 'offsets', 'shapes') on self.stream, then xdet_net_forward_u8 runs on them -> n."""
+        bufs = self._ingest_buffers(packed_nbytes)
+        _train.new_body(self)
+        fill(bufs)
+        # packed_bytes = the buffer's capacity: the graph key stays the same for every batch that fits
+        check(lib().xdet_net_forward_u8(self.handle, bufs['packed'].ptr, bufs['packed'].nbytes, bufs['offsets'].ptr,
+                                        bufs['shapes'].ptr, n, int(mode), self._images.ptr, bufs['bbox_img'].ptr,
+                                        self._det_scores.ptr, self._det_boxes.ptr, 1 if use_graph else 0, self.stream.handle))
+        self._N = n
+        return n
+
+    def _ingest_buffers(self, packed_nbytes):
+        """the ingest's device buffers, `packed` holding at least packed_nbytes"""
         B = self.max_batch
         if not hasattr(self, '_ingest'):
             # offsets / image_shapes / bbox_img: max_batch entries, allocated once.  packed grows only: a regrown buffer
@@ -297,21 +321,27 @@ class LightHeadDetector(object):
             self._ingest = {'offsets': DeviceBuffer(B * 8), 'shapes': DeviceBuffer(B * 8),
                             'bbox_img': DeviceBuffer(B * 16), 'packed': None}
         bufs = self._ingest
-        if bufs['packed'] is None or bufs['packed'].nbytes < packed.nbytes:
-            cap = max(packed.nbytes, 2 * bufs['packed'].nbytes if bufs['packed'] is not None else 0)
+        if bufs['packed'] is None or bufs['packed'].nbytes < packed_nbytes:
+            cap = max(packed_nbytes, 2 * bufs['packed'].nbytes if bufs['packed'] is not None else 0)
             bufs['packed'] = DeviceBuffer(cap)
-        _train.new_body(self)
-        h = self.stream.handle
-        check(lib().xdet_memcpy_h2d(bufs['packed'].ptr, _host(packed), packed.nbytes, h))
-        check(lib().xdet_memcpy_h2d(bufs['offsets'].ptr, _host(offsets), offsets.nbytes, h))
-        check(lib().xdet_memcpy_h2d(bufs['shapes'].ptr, _host(shapes), shapes.nbytes, h))
-        # packed_bytes = the buffer's capacity: the graph key stays the same for every batch that fits
-        check(lib().xdet_net_forward_u8(self.handle, bufs['packed'].ptr, bufs['packed'].nbytes, bufs['offsets'].ptr,
-                                        bufs['shapes'].ptr, n, int(mode), self._images.ptr, bufs['bbox_img'].ptr,
-                                        self._det_scores.ptr, self._det_boxes.ptr, 1 if use_graph else 0, h))
-        self._N = n
-        self._host_keep = (packed, offsets, shapes)      # (referenced until the next call: nothing waits for the copies here)
-        return n
+        return bufs
+
+    def detect_jpegs(self, datas, resize=None, use_graph=True):
+        """detect_images from encoded baseline JPEGs (xdet.jpeg: the accepted forms and the refusals): the entropy streams
+        are decoded on the host, the decode kernels write the pixels into the ingest's own packed buffer, and
+        xdet_net_forward_u8 runs on them on the same stream -- no pixel upload, no host round trip.  The result equals
+        detect_images on the decoded arrays bit for bit, and batches of other sizes replay the same graph."""
+        from . import jpeg, ops
+        mode = ops._resize_mode(ops.Resize.WARP_RESIZE if resize is None else resize)
+        batch = jpeg._check_jpegs(datas, 'detect_jpegs', self.max_batch)
+        ops._check_sizes_for_mode(batch.shapes, self.image_size, mode, 'detect_jpegs: ')
+
+        def decode(bufs):
+            self._jpeg_workspace = jpeg._decode_into('detect_jpegs', batch, bufs['packed'], bufs['offsets'], bufs['shapes'],
+                                                     self.stream, None, getattr(self, '_jpeg_workspace', None))
+        n = self._forward_u8(batch.n, mode, batch.nbytes, decode, use_graph)
+        s, b = self.detections(n)
+        return [{c + 1: (s[i, c], b[i, c]) for c in range(self.num_classes - 1)} for i in range(n)]
 
     def evaluate_images(self, images, ground_truths, image_ids=None, resize=None, accumulator=None, matching_threshold=0.5,
                         use_graph=True):

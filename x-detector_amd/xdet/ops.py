@@ -733,12 +733,16 @@ def _check_batch(images, out_size, resize, max_images=None):
         raise InvalidArgumentError(-1, 'no images')
     if max_images is not None and len(imgs) > max_images:
         raise InvalidArgumentError(-1, '%d images but at most %d per call' % (len(imgs), max_images))
-    if mode == Resize.NONE:
-        for i, im in enumerate(imgs):
-            if im.shape[:2] != (S, S):
-                raise InvalidArgumentError(-1, 'images[%d]: Resize.NONE needs %dx%d images, got %dx%d'
-                                           % (i, S, S, im.shape[0], im.shape[1]))
+    _check_sizes_for_mode([im.shape[:2] for im in imgs], S, mode)
     return imgs, S, mode
+
+
+def _check_sizes_for_mode(shapes, S, mode, who=''):
+    """Resize.NONE takes S x S images only; shapes: (H, W) per image"""
+    if mode == Resize.NONE:
+        for i, (h, w) in enumerate(shapes):
+            if (int(h), int(w)) != (S, S):
+                raise InvalidArgumentError(-1, '%simages[%d]: Resize.NONE needs %dx%d images, got %dx%d' % (who, i, S, S, h, w))
 
 
 def pack_images(images):
