@@ -909,6 +909,43 @@ int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const
 /* The same for a depthwise layer (xdet_depthwise_create): its taps [9][round_up(C,32)] from a dense f32 [3,3,C,1] kernel in
  * device memory, padding channels +0.  Errors: a NULL kernel, a layer whose taps carry an activation pre-scale. */
 int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream);
+/* The inference fold of a batch norm on the device (csrc/conv_repack.hip): f32 arrays of C floats in device memory, bias NULL
+ * or C floats, no synchronisation.  Per channel, every operation an f32 operation rounded on its own (no fused multiply-add,
+ * correctly rounded division and square root), in the order of the host fold a net is built with:
+ *     sc    = gamma / sqrtf(moving_variance + eps)
+ *     shift = (beta - moving_mean * sc) + (bias ? bias * sc : 0.f)
+ * The + 0.f of a fold without bias is kept: it turns a -0 shift into +0, as on the host.  The NumPy statement of the same
+ * contract is xdet.ops.host_bn_fold, and the call equals it bit for bit.  Errors: a NULL array (bias excepted), C <= 0. */
+int xdet_bn_fold(const float* gamma, const float* beta, const float* moving_mean, const float* moving_variance,
+                 const float* bias_or_null, float eps, int C, float* scale_out, float* shift_out, void* stream);
+/* The repack of xdet_conv_set_kernel_device / xdet_depthwise_set_kernel_device over a table of layers, in a number of launches
+ * that does not depend on the table's length: one clear of the row maxima, one maxima pass and one repack pass over all conv
+ * slots, one pass over all depthwise slots (a pass without slots is left out), behind one upload of the slot descriptors and
+ * the tile -> slot tables, which are built here.  The per-tile device code is the per-layer doors' own, so a layer refreshed
+ * here holds the bits they, and a creation from the same values, would give it.  A slot is one conv layer (xdet_conv_create,
+ * or owned by a net) or one depthwise layer; all pointers are device memory.  kernel: as for the per-layer doors.  scale
+ * (f32 [cout], conv slots only; NULL: the creation-time epilogue scale is kept) replaces the epilogue scale the layer was
+ * created with -- in the split-precision modes the one in front of the rows' pre-scale, in f32 mode the scale itself.
+ * shift (f32 [cout], conv slots only; NULL: kept) replaces the epilogue shift.  Layers of different precisions, with or
+ * without the x8 copy, may share a table.
+ * Unlike the per-layer doors, the table door honours what a net-owned or calibrated layer carries: a conv layer with an
+ * activation exponent e ends with the epilogue scale creation plus that exponent would have left (the rescaled scale times
+ * 2^e, exact); a depthwise layer with an output exponent e gets its taps times 2^-e; a planes affine that comes from the
+ * layer's own output exponent alone is kept.  Refused: a layer whose planes copy carries a folded batch norm, a grouped
+ * layer, a spectral layer -- each by name of the reason.
+ * The call does not synchronise; the layers' host copies of the scale and of the taps are stale afterwards, as after the
+ * per-layer doors.  workspace: xdet_layers_refresh_workspace_bytes(slots, n) bytes of device memory (0 for a table the call
+ * refuses); it needs no initialisation and may be larger; a call behind a call on the same stream may reuse it.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work and with no layer touched: a NULL or empty table, a NULL layer or
+ * kernel, a layer listed twice, a refused layer kind, a scale or shift on a depthwise slot, a NULL workspace. */
+typedef struct {
+  void* layer;
+  const float* kernel;
+  const float* scale;
+  const float* shift;
+} xdet_layer_refresh;
+size_t xdet_layers_refresh_workspace_bytes(const xdet_layer_refresh* slots_host, int n);
+int xdet_layers_refresh_device(const xdet_layer_refresh* slots_host, int n, void* workspace, void* stream);
 
 /* ---- the gradient average of data-parallel training (csrc/grad_average.hip; the exchange itself is
  * xdet_comm_average_gradients in csrc/comm.hip): every rank's gradients become the rank-ordered mean, ahead of the step ------
@@ -1081,6 +1118,27 @@ int xdet_net_plane_scale_name(void* net, int idx, char* buf, int buflen);
  * the light-head net (net/xception_body.py:220-234, blocks 5-14). */
 int xdet_net_x8_planes(void* net, int* n_on);
 int xdet_net_graph_count(void* net, int* count);
+/* Refresh the built net's body from trained weights in device memory: names are the checkpoint's, data dense f32 in the
+ * checkpoint's shapes.  The reach is the body's blocks 2-14 -- the 72 layers of the entry, middle and exit flows (38 convs, 34
+ * depthwise), 148 variables and the 76 moving statistics of their 38 batch norms.  A layer group is refreshed only whole: a
+ * unit is <u>/depthwise_kernel, <u>/pointwise_kernel and <u>_bn/{gamma, beta, moving_mean, moving_variance}; a projection is
+ * <conv>/kernel and the four arrays of its batch norm.  Any set of whole groups is allowed.
+ * The call folds every group's batch norm with xdet_bn_fold into scratch the net owns (one block, allocated at the first refresh: xdet_net_memory then reports it), runs one
+ * xdet_layers_refresh_device table over all touched layers on `stream`, synchronises, and brings the host side back in line:
+ * every touched layer's host copy of the epilogue scale (at exponent 0) and of the depthwise taps is read back and the layers
+ * accept an activation exponent again (xdet_net_calibrate works as on a freshly built net); the range bound of a fused
+ * separable block's depthwise result is recomputed from the new taps; a host copy of a weight the net still holds is updated.
+ * Every exponent the plan holds is kept, and no pointer or scalar baked into a captured graph changes: xdet_net_graph_count is
+ * unchanged and a replayed graph computes with the new weights.  The stem, the RPN head, the large-separable block, the head
+ * and the detection tail are untouched.
+ * Errors -> XDET_ERR_INVALID_ARG, by name, before any GPU work and with the net unchanged: a name outside the reach (the stem's
+ * block1_ layers, rpn_head, large_sep_feature, final_head, anything unknown), a group given in part, a name given twice, a NULL
+ * pointer, an empty table, a net that is not built. */
+typedef struct {
+  const char* name;
+  const float* data;
+} xdet_net_weight_dev;
+int xdet_net_refresh_weights(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
 /* Device memory of the net's workspace and weights in bytes (everything the plan allocated), and how many bytes of
  * tensors were placed into blocks recycled from dead tensors (option "workspace" = "reuse", the default: a builder hands a
  * tensor's block back once its last consumer is planned and a later tensor takes it over -- a planes tensor only a block
@@ -1089,7 +1147,8 @@ int xdet_net_graph_count(void* net, int* count);
  * "poison" proves) -- the middle flow's 24 x 2 tensors live in a handful of blocks; "ssa": one block per tensor, which
  * option check_range selects by itself because its validation pass reads every tensor after the forward; "poison"
  * (tests): "reuse", with everything behind a recycled f32 tensor filled with NaN bits in front of its producer on every
- * forward -- the detections must still be those of "ssa", bit for bit). */
+ * forward -- the detections must still be those of "ssa", bit for bit).  The first xdet_net_refresh_weights adds its scratch
+ * (one block: the table workspace for the whole reach and two floats per output channel) to allocated_bytes. */
 int xdet_net_memory(void* net, size_t* allocated_bytes, size_t* recycled_bytes);
 /* per-kernel accounting of the last build: total dense FLOPs (2*MAC, unpadded) of one image */
 int xdet_net_flops_per_image(void* net, double* backbone, double* rpn, double* large_sep, double* head);

@@ -4,6 +4,8 @@ at 480 pixels): microseconds per call, medians of --reps calls, of
   (1) xdet_momentum_step over all variables (with its l2), and the bytes per second it moves at 20 bytes per element;
   (2) the refresh of the 38 conv and 34 depthwise forward layers on the device (xdet_conv_set_kernel_device /
       xdet_depthwise_set_kernel_device), the 72 calls enqueued back to back;
+  (2t) the same refresh as ONE table (xdet_layers_refresh_device, what opt.step runs): measured alternately with (2), twice each,
+      so that the two can be compared inside one run's own spread;
   (3) the same refresh done without them: every layer built again from a NumPy kernel (ops.Conv2D / ops.DepthwiseConv2D, what
       tests/test_gpu_train_derivative.py::perturbed does), kernels already on the host.
 (1) and (2) are event-timed on the detector's stream, with the wall time next to them; (3) is wall time: it is host work.  A
@@ -31,7 +33,8 @@ S = 480
 COPY_RATE = 5.07e12          # bytes per second of a device-to-device copy on this part
 
 
-KERNELS = ('momentum_step_kernel', 'momentum_l2_kernel', 'conv_repack_max_kernel', 'conv_repack_kernel', 'depthwise_repack_kernel')
+KERNELS = ('momentum_step_kernel', 'momentum_l2_kernel', 'conv_repack_max_kernel', 'conv_repack_kernel', 'depthwise_repack_kernel',
+           'conv_repack_max_table_kernel', 'conv_repack_table_kernel', 'depthwise_repack_table_kernel')
 
 
 def kernel_stats(a, say, elements):
@@ -112,6 +115,14 @@ def main():
         for p in projections:
             p.conv.set_kernel_device(p.K, stream=st)
 
+    table_slots = opt._refresh_slots()
+
+    def refresh_table():
+        train_ops.refresh_layers_device(table_slots, stream=st, workspace=opt._refresh_ws)
+
+    def refresh_one():                                    # (a table of one slot: the same launches as a table of 72)
+        train_ops.refresh_layers_device(table_slots[:1], stream=st, workspace=opt._refresh_ws)
+
     host = opt.read()
 
     def rebuild():
@@ -127,6 +138,10 @@ def main():
 
     ev_s, wall_s = medians(step, a.reps)
     ev_r, wall_r = medians(refresh, a.reps)
+    ev_t, wall_t = medians(refresh_table, a.reps)
+    ev_r2, wall_r2 = medians(refresh, a.reps)
+    ev_t2, wall_t2 = medians(refresh_table, a.reps)
+    ev_1, wall_1 = medians(refresh_one, a.reps)
     if a.child:
         return
     _, wall_b = medians(rebuild, a.reps)
@@ -137,6 +152,10 @@ def main():
     say('  xdet_momentum_step (one launch + the l2 fold)   %10.1f us on the stream, %10.1f us wall (the host builds and checks the '
         'table: %.2f TB/s end to end)' % (ev_s, wall_s, rate / 1e12))
     say('  %d layer refreshes on the device                %10.1f us on the stream, %10.1f us wall' % (layers, ev_r, wall_r))
+    say('  the same as one table (what opt.step runs)       %10.1f us on the stream, %10.1f us wall' % (ev_t, wall_t))
+    say('  %d layer refreshes, second round                 %10.1f us on the stream, %10.1f us wall' % (layers, ev_r2, wall_r2))
+    say('  one table, second round                          %10.1f us on the stream, %10.1f us wall' % (ev_t2, wall_t2))
+    say('  a table of one slot                              %10.1f us on the stream, %10.1f us wall' % (ev_1, wall_1))
     say('  %d layers built again from NumPy kernels        %10s    %13.1f us wall: %.0f x the device refresh (wall against wall)'
         % (layers, '', wall_b, wall_b / wall_r))
     if a.kernels:

@@ -667,6 +667,10 @@ int xdet_net_mid_refresh(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_mid_refresh");
   return n->mid_refresh(N, S(stream));
 }
+int xdet_net_refresh_weights(void* net, const xdet_net_weight_dev* table, int n, void* stream) {
+  XDET_LIGHTHEAD(nt, net, "net_refresh_weights");
+  return nt->refresh_weights(table, n, S(stream));
+}
 int xdet_net_get_rpn(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_get_rpn");
   XDET_TRY(n->check(N));

@@ -139,6 +139,11 @@ struct LightHeadNet : Plan {
                               cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
   }
   int mid_refresh(int N, hipStream_t s);
+  // xdet_net_refresh_weights: the body's blocks 2-14 from trained weights in device memory, through layer_recs
+  int refresh_weights(const xdet_net_weight_dev* table, int n, hipStream_t s);
+  float *rf_scale = nullptr, *rf_shift = nullptr;   // the folds' scratch, a record's channels at rf_off[record]: allocated at
+  void* rf_ws = nullptr;                            // the first refresh with the table door's workspace for the whole reach
+  std::vector<size_t> rf_off;
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);
   int forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                     hipStream_t s);

@@ -395,6 +395,115 @@ int LightHeadNet::mid_refresh(int N, hipStream_t s) {
   return launch_relu_copy(mid_x.p, mid_relu, (int64_t)N * mid_x.per_image(), s);
 }
 
+// The eval body from trained weights (include/xdet.h): names -> layer_recs, all checks, then the folds, one table repack, one
+// synchronisation, and the host copies the calibration works from.
+int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipStream_t s) {
+  XDET_REQUIRE(built, "net_refresh_weights: the net is not built");
+  XDET_REQUIRE(table && n > 0, "net_refresh_weights: an empty table");
+  enum { R_KERNEL, R_GAMMA, R_BETA, R_MEAN, R_VAR, R_DW, R_N };
+  auto role_name = [](const LayerRec& r, int role) {
+    switch (role) {
+      case R_KERNEL: return r.prefix + (r.dw ? "/pointwise_kernel" : "/kernel");
+      case R_DW: return r.prefix + "/depthwise_kernel";
+      case R_GAMMA: return r.bn + "/gamma";
+      case R_BETA: return r.bn + "/beta";
+      case R_MEAN: return r.bn + "/moving_mean";
+      default: return r.bn + "/moving_variance";
+    }
+  };
+  // the reach: what conv_bn / sep_bn built of blocks 2-14 (block1_* is the stem)
+  std::map<std::string, std::pair<int, int>> names;
+  std::vector<int> reach;
+  for (size_t i = 0; i < layer_recs.size(); ++i) {
+    const LayerRec& r = layer_recs[i];
+    if (r.bn.empty() || r.prefix.compare(0, 7, "block1_") == 0) continue;
+    reach.push_back((int)i);
+    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role) names[role_name(r, role)] = {(int)i, role};
+  }
+  std::map<int, std::array<const float*, R_N>> groups;
+  for (int i = 0; i < n; ++i) {
+    XDET_REQUIRE(table[i].name, "net_refresh_weights: a NULL name");
+    const std::string name(table[i].name);
+    auto it = names.find(name);
+    XDET_REQUIRE(it != names.end(), "net_refresh_weights: " + name + " is outside the reach (the variables and moving statistics of the "
+                                    "body's blocks 2-14)");
+    XDET_REQUIRE(table[i].data, "net_refresh_weights: " + name + " is a NULL pointer");
+    auto g = groups.find(it->second.first);
+    if (g == groups.end()) g = groups.emplace(it->second.first, std::array<const float*, R_N>{}).first;
+    XDET_REQUIRE(!g->second[it->second.second], "net_refresh_weights: " + name + " is given twice");
+    g->second[it->second.second] = table[i].data;
+  }
+  for (const auto& g : groups) {
+    const LayerRec& r = layer_recs[g.first];
+    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role)
+      XDET_REQUIRE(g.second[role], "net_refresh_weights: the group of " + r.prefix + " is given in part: " + role_name(r, role) +
+                                   " is missing");
+  }
+  if (!rf_ws) {
+    rf_off.assign(layer_recs.size(), 0);
+    size_t channels = 0;
+    std::vector<xdet_layer_refresh> all;
+    const float* some = groups.begin()->second[R_KERNEL];    // (measuring reads no kernel)
+    for (int i : reach) {
+      const LayerRec& r = layer_recs[i];
+      rf_off[i] = channels;
+      channels += (size_t)r.conv->cout;
+      all.push_back({r.conv, some, nullptr, nullptr});
+      if (r.dw) all.push_back({r.dw, some, nullptr, nullptr});
+    }
+    const size_t bytes = xdet_layers_refresh_workspace_bytes(all.data(), (int)all.size());
+    XDET_REQUIRE(bytes > 0, "net_refresh_weights: the plan holds a layer the table door refuses");
+    // one block [table workspace | scales | shifts]: either all of the scratch exists or none of it
+    const size_t ws_bytes = (bytes + 255) / 256 * 256, fold_bytes = (channels * sizeof(float) + 255) / 256 * 256;
+    void* block = nullptr;
+    XDET_TRY(alloc_bytes(ws_bytes + 2 * fold_bytes, &block, false));
+    rf_scale = reinterpret_cast<float*>(static_cast<char*>(block) + ws_bytes);
+    rf_shift = reinterpret_cast<float*>(static_cast<char*>(block) + ws_bytes + fold_bytes);
+    rf_ws = block;
+  }
+  std::vector<xdet_layer_refresh> slots;
+  for (const auto& g : groups) {
+    const LayerRec& r = layer_recs[g.first];
+    float *sc = rf_scale + rf_off[g.first], *sh = rf_shift + rf_off[g.first];
+    XDET_TRY(xdet_bn_fold(g.second[R_GAMMA], g.second[R_BETA], g.second[R_MEAN], g.second[R_VAR], nullptr, r.eps, r.conv->cout, sc, sh, s));
+    slots.push_back({r.conv, g.second[R_KERNEL], sc, sh});
+    if (r.dw) slots.push_back({r.dw, g.second[R_DW], nullptr, nullptr});
+  }
+  XDET_TRY(xdet_layers_refresh_device(slots.data(), (int)slots.size(), rf_ws, s));
+  XDET_HIP(hipStreamSynchronize(s));
+  // the host side back in line: the scale at exponent 0 (d_scale carries 2^in_exp, exactly), the taps from the kernel itself
+  std::vector<float> k;
+  auto download = [&](const float* d, size_t count) {
+    k.resize(count);
+    XDET_HIP(hipMemcpy(k.data(), d, count * sizeof(float), hipMemcpyDeviceToHost));
+    return (int)XDET_OK;
+  };
+  for (const auto& g : groups) {
+    const LayerRec& r = layer_recs[g.first];
+    ConvLayer* L = r.conv;
+    XDET_TRY(download(L->d_scale, (size_t)L->cout_pad));
+    for (float& v : k) v = ldexpf(v, -L->in_exp);
+    L->in_scale.host = k;
+    L->host_stale = false;
+    if (r.dw) {
+      DepthwiseLayer* D = r.dw;
+      XDET_TRY(download(g.second[R_DW], (size_t)9 * D->C));
+      std::fill(D->taps.host.begin(), D->taps.host.end(), 0.f);
+      for (int t = 0; t < 9; ++t)
+        for (int c = 0; c < D->C; ++c) D->taps.host[(size_t)t * D->ld + c] = k[(size_t)t * D->C + c];
+      D->host_stale = false;
+      if (r.pscale >= 0) pscales[r.pscale].bound = depthwise_bound(k.data(), D->C);
+    }
+    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role) {      // a host copy the net still holds (none once build() has dropped them)
+      auto hw = w.find(role_name(r, role));
+      if (hw == w.end()) continue;
+      XDET_TRY(download(g.second[role], hw->second.v.size()));
+      hw->second.v = k;
+    }
+  }
+  return XDET_OK;
+}
+
 int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_scaled) {
   XDET_TRY(check(N));
   XDET_REQUIRE(images != nullptr, "calibrate: images is NULL");

@@ -316,6 +316,28 @@ struct Plan {
   DepthwiseLayer* keep(DepthwiseLayer* L) { layers.emplace_back(L); return L; }
   SpectralConv* keep(SpectralConv* L) { layers.emplace_back(L); return L; }
 
+  // What conv_bn / sep_bn made of which checkpoint names: the door a refresh from trained weights reaches the layers by
+  // (LightHeadNet::refresh_weights).  A unit (sep_bn) has a depthwise layer, its kernels are <prefix>/depthwise_kernel and
+  // <prefix>/pointwise_kernel; a projection (conv_bn) has <prefix>/kernel.  bn is empty for a conv without one.
+  struct LayerRec {
+    std::string prefix, bn;
+    float eps = 0.f;
+    ConvLayer* conv = nullptr;
+    DepthwiseLayer* dw = nullptr;
+    int pscale = -1;                   // a fused separable block: the PlaneScale whose bound comes from the depthwise taps
+  };
+  std::vector<LayerRec> layer_recs;
+  // max over channels of sum_t |w[t, c]| of a dense [3,3,C,1] kernel: what bounds a fused block's depthwise result
+  static float depthwise_bound(const float* k33c1, int C) {
+    float bound = 0.f;
+    for (int c = 0; c < C; ++c) {
+      float a = 0.f;
+      for (int t = 0; t < 9; ++t) a += std::fabs(k33c1[(size_t)t * C + c]);
+      bound = std::max(bound, a);
+    }
+    return bound;
+  }
+
   // tf.layers.conv2d(use_bias=False) + BN (+ReLU); *layer (optional): the conv layer it made
   int conv_bn(const std::string& name, const std::string& bn, float eps, int stage, const Buf& in, const ConvArgs& args, Buf* out,
               ConvLayer** layer = nullptr);

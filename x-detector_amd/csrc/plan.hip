@@ -399,6 +399,11 @@ int Plan::conv_bn(const std::string& name, const std::string& bn, float eps, int
   }
   ConvLayer* L = keep(new ConvLayer());
   if (layer) *layer = L;
+  {
+    LayerRec rec;
+    rec.prefix = name; rec.bn = bn; rec.eps = eps; rec.conv = L;
+    layer_recs.push_back(rec);
+  }
   XDET_REQUIRE(!pre_sc || (k == 1 && stride == 2 && g_default_precision != PREC_F32 && in.C >= 32 && !in.no_f32 &&
                            in.ld % 32 == 0),
                "plan: a pre-activation can only be folded into a 1x1 stride-2 projection on the split path");
@@ -464,6 +469,11 @@ int Plan::sep_bn(const std::string& name, float eps, int stage, const Buf& in, c
   XDET_TRY(fold_bn(name + "_bn", cout, eps, nullptr, &sc, &sh));
   ConvLayer* L = keep(new ConvLayer());
   XDET_TRY(L->init(1, 1, in.C, cout, 1, 1, 1, 0, 0, pk->v.data(), sc.data(), sh.data(), relu_out));
+  {
+    LayerRec rec;
+    rec.prefix = name; rec.bn = name + "_bn"; rec.eps = eps; rec.conv = L; rec.dw = D;
+    layer_recs.push_back(rec);
+  }
   // Entry-flow shapes (<= 256 input channels, 128 / 256 outputs, dilation 1, no residual, f32 consumers only):
   // ONE fused kernel, the depthwise result never leaves the CU (sepconv_fused.hip); bit-identical to the
   // two-kernel form below, which the wide 30x30 layers keep (their GEMM needs the big MFMA tiles).
@@ -477,16 +487,11 @@ int Plan::sep_bn(const std::string& name, float eps, int stage, const Buf& in, c
       ps.src = in.p;
       ps.src_per_image = in.per_image();
       ps.src_relu = pre_relu;
-      float bound = 0.f;
-      for (int c = 0; c < in.C; ++c) {
-        float a = 0.f;
-        for (int t = 0; t < 9; ++t) a += std::fabs(dk->v[(size_t)t * in.C + c]);
-        bound = std::max(bound, a);
-      }
-      ps.bound = bound;
+      ps.bound = depthwise_bound(dk->v.data(), in.C);
       ps.apply.push_back([D](int e) { return D->set_out_exp(e); });
       ps.apply.push_back([L](int e) { return L->set_in_exp(e); });
       ps.op_index = (int)ops.size();               // the fused op is pushed next: its input is intact right behind it
+      layer_recs.back().pscale = (int)pscales.size();
       pscales.push_back(ps);
     }
     if (pool_res && fuse_hpool && in.H * in.W >= pool_fuse_min_pixels) {

@@ -58,6 +58,17 @@ class GradSlot(ctypes.Structure):
     _fields_ = [('grad', c_void_p), ('n', c_int64)]
 
 
+class LayerRefresh(ctypes.Structure):
+    """xdet_layer_refresh: one layer of xdet_layers_refresh_device -- the layer's handle, its new kernel and (conv layers) the
+    new epilogue scale and shift, device pointers; scale / shift NULL: kept"""
+    _fields_ = [('layer', c_void_p), ('kernel', c_void_p), ('scale', c_void_p), ('shift', c_void_p)]
+
+
+class NetWeightDev(ctypes.Structure):
+    """xdet_net_weight_dev: one array of xdet_net_refresh_weights -- the checkpoint's name and the dense f32 data on the device"""
+    _fields_ = [('name', ctypes.c_char_p), ('data', c_void_p)]
+
+
 class JpegDesc(ctypes.Structure):
     """xdet_jpeg_desc: what the marker parser knows of one baseline JPEG -- size, components, the luma's sampling factors,
     restart interval, MCU grid, per component its block grid (padded to whole MCUs), the offset of its blocks (in blocks)
@@ -193,6 +204,9 @@ SIGNATURES = {
     'xdet_grad_reduce_ranks': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_int, c_void_p, c_void_p]),
     'xdet_conv_set_kernel_device': (c_int, [c_void_p, PF, PF, c_void_p]),
     'xdet_depthwise_set_kernel_device': (c_int, [c_void_p, PF, c_void_p]),
+    'xdet_bn_fold': (c_int, [PF, PF, PF, PF, PF, c_float, c_int, PF, PF, c_void_p]),
+    'xdet_layers_refresh_workspace_bytes': (c_size_t, [ctypes.POINTER(LayerRefresh), c_int]),
+    'xdet_layers_refresh_device': (c_int, [ctypes.POINTER(LayerRefresh), c_int, c_void_p, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),
@@ -203,6 +217,7 @@ SIGNATURES = {
     'xdet_net_xception_body': (c_int, [c_void_p, PF, c_int, c_void_p]),
     'xdet_net_get_rpn': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_mid_refresh': (c_int, [c_void_p, c_int, c_void_p]),
+    'xdet_net_refresh_weights': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
     'xdet_net_large_sep': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_rpn_decode': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_get_proposals': (c_int, [c_void_p, c_int, c_void_p]),

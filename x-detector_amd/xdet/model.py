@@ -228,6 +228,24 @@ class LightHeadDetector(object):
         check(lib().xdet_net_calibrate(self.handle, self._images.ptr, n, ctypes.byref(k), self.stream.handle))
         return {name: e for name, e in self.plane_scales().items() if e}
 
+    def refresh_weights(self, tensors):
+        """Refresh the eval net's body from weights on the device (xdet_net_refresh_weights): tensors is {checkpoint name: dense
+        f32 DeviceTensor or DeviceBuffer in the checkpoint's shape} over whole layer groups of the body's blocks 2-14 (a unit's
+        two kernels and the four arrays of its batch norm; a projection's kernel and its batch norm's four; train.eval_net_groups).
+        The batch norms are folded on the device, all touched layers repacked by one table, the stream synchronised and the
+        host state a calibration works from brought back in line; exponents, plane_scales() and the captured graphs stay.
+        Refused ahead of any GPU work, by name: a host array, a name outside the reach, a group given in part."""
+        from ._lib import NetWeightDev
+        for name, t in tensors.items():
+            if not isinstance(t, (DeviceTensor, DeviceBuffer)) or not t.ptr:
+                raise InvalidArgumentError(-1, 'refresh_weights: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                           % (name, type(t).__name__))
+        _train.eval_net_groups(tensors)
+        table = (NetWeightDev * max(len(tensors), 1))()
+        for i, (name, t) in enumerate(tensors.items()):
+            table[i] = NetWeightDev(name.encode(), t.ptr)
+        check(lib().xdet_net_refresh_weights(self.handle, table, len(tensors), self.stream.handle))
+
     def x8_planes(self):
         """tensors in the x8 form (cross='fp8', after calibrate()): xdet_net_x8_planes"""
         n = ctypes.c_int()

@@ -25,7 +25,7 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'LARGE_SEP_EPS', 'LARGE_SE
            'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
-           'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'MomentumOptimizer']
+           'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'MomentumOptimizer']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
                             for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
@@ -935,6 +935,34 @@ def decayed(name):
     return 'batch_normalization' not in name and '_bn' not in name
 
 
+def eval_net_groups(names):
+    """The layer groups xdet_net_refresh_weights takes whole, from the names of a refresh table: a unit is
+    <u>/depthwise_kernel, <u>/pointwise_kernel and the four arrays of <u>_bn; a projection conv2d_<i>/kernel and the four arrays
+    of batch_normalization_<i>.  -> {group: the sorted names given of it}; a name outside the flows' variables and moving
+    statistics, and a group given in part, are refused by name."""
+    reach = set(ENTRY_FLOW_VARIABLES + MIDDLE_FLOW_VARIABLES + EXIT_FLOW_VARIABLES + ENTRY_FLOW_MOVING + MIDDLE_FLOW_MOVING + EXIT_FLOW_MOVING)
+    bn = ('gamma', 'beta', 'moving_mean', 'moving_variance')
+    groups = {}
+    for n in names:
+        if n not in reach:
+            raise InvalidArgumentError(-1, 'refresh_weights: %s is outside the reach (the variables and moving statistics of the '
+                                           "body's blocks 2-14)" % n)
+        head = n.rsplit('/', 1)[0]
+        g = head[:-3] if head.endswith('_bn') else head.replace('batch_normalization_', 'conv2d_')
+        groups.setdefault(g, []).append(n)
+    for g, have in groups.items():
+        if g.startswith('conv2d_'):
+            want = [g + '/kernel'] + ['batch_normalization_%s/%s' % (g[7:], k) for k in bn]
+        else:
+            want = [g + '/depthwise_kernel', g + '/pointwise_kernel'] + ['%s_bn/%s' % (g, k) for k in bn]
+        miss = sorted(set(want) - set(have))
+        if miss or len(have) != len(want):
+            raise InvalidArgumentError(-1, 'refresh_weights: the group of %s is given in part: %s' %
+                                       (g, (', '.join(miss) + ' is missing') if miss else 'a name is given twice'))
+        have.sort()
+    return groups
+
+
 class MomentumOptimizer(object):
     """tf.train.MomentumOptimizer(lr, momentum) over the loss the reference minimises, loss + weight_decay * sum l2_loss(v) over
     the variables `decayed` names (light_head_rfcn_train.py:420,435), for the flow stages `det` was built with: the variables
@@ -942,10 +970,10 @@ class MomentumOptimizer(object):
     three, 15 + 48 + 9 = 72 of them kernels in the L2 set).  The masters are the buffers the stages already hold -- SepUnit.K_dw,
     SepUnit.K_pw, Projection.K, BatchNorm.gamma, BatchNorm.beta -- updated in place; the optimizer allocates the momentum slots
     (zero) and the step's workspace and holds a second copy of nothing.
-    Out of its reach: the large-separable block, the head, the RPN head and the stem keep their weights, and the NATIVE EVAL
-    NET keeps the weights it folded when the detector was built -- XceptionBody(..., is_training=False), forward and
-    detect_images go on computing with the checkpoint the detector was made from until a new LightHeadDetector is built from
-    export_weights(...)."""
+    Out of its reach: the large-separable block, the head, the RPN head and the stem keep their weights.  The NATIVE EVAL NET
+    keeps the weights it last folded -- XceptionBody(..., is_training=False), forward, detect_images and evaluate compute with
+    them -- until refresh_eval_net() refolds the body's blocks 2-14 from the masters and the training stages' moving statistics
+    on the device (xdet_net_refresh_weights: no host round trip of the weights, no second net, the captured graphs stay)."""
 
     def __init__(self, det, momentum=0.9, weight_decay=2e-4):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
@@ -970,6 +998,10 @@ class MomentumOptimizer(object):
         for i, v in enumerate(self.variables):                            # (sizes only: the workspace depends on nothing else)
             table[i] = MomentumSlot(1, 1, 1, int(np.prod(self._master[v][1])), 0)
         self._ws = DeviceBuffer(lib().xdet_momentum_step_workspace_bytes(table, len(self.variables)))
+        self._refresh_ws = None                            # (an optimizer over no layers has none, and step refreshes nothing)
+        if self._refresh_slots():
+            rtable, _ = train_ops.refresh_layers_table(self._refresh_slots())
+            self._refresh_ws = DeviceBuffer(lib().xdet_layers_refresh_workspace_bytes(rtable, len(rtable)))
 
     def _states(self):
         return [getattr(self.det, STAGES[k].attr) for k in self._stages]
@@ -988,8 +1020,8 @@ class MomentumOptimizer(object):
         """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
         backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
         stream: one xdet_momentum_step over all variables; the refresh of the forward layers (every unit's pointwise and
-        depthwise layer and every projection's conv, as the units hold them at this moment) from the updated masters by
-        xdet_conv_set_kernel_device / xdet_depthwise_set_kernel_device; and the drop of every stage's saved state, as a new eval
+        depthwise layer and every projection's conv, as the units hold them at this moment) from the updated masters by one
+        xdet_layers_refresh_device table; and the drop of every stage's saved state, as a new eval
         body drops it: the kept tensors belong to the old weights, so each *_backward refuses until its training forward has run
         again (the eval body need not: `stem_out` does not depend on these variables).
         -> {'step': the number of steps taken, 'lr': lr, 'l2': sum over the L2 set of sum v^2 / 2 before the update, a float}.
@@ -1018,16 +1050,37 @@ class MomentumOptimizer(object):
             comm.average_gradients([grads[v] for v in self.variables], d.stream)
             comm.wait()
         l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws)
-        for u in self._units():
-            u.pw.set_kernel_device(u.K_pw, stream=d.stream)
-            u.dw.set_kernel_device(u.K_dw, stream=d.stream)
-        for p in self._projections():
-            p.conv.set_kernel_device(p.K, stream=d.stream)
+        layers = self._refresh_slots()
+        if layers:
+            train_ops.refresh_layers_device(layers, stream=d.stream, workspace=self._refresh_ws)
         new_body(d)
         _sync(d)
         l2._keep = None
         self.steps += 1
         return {'step': self.steps, 'lr': float(lr), 'l2': float(to_host(l2.ptr, (1,))[0])}
+
+    def _refresh_slots(self):
+        """the training forward layers and their masters, as the units hold them at this moment: refresh_layers_device's table"""
+        return [s for u in self._units() for s in ((u.pw, u.K_pw), (u.dw, u.K_dw))] + [(p.conv, p.K) for p in self._projections()]
+
+    def eval_net_tensors(self):
+        """{name: device array} of everything refresh_eval_net hands to the eval net: the masters of `self.variables` and the moving
+        statistics of the batch norms of the stages that are on"""
+        out = {v: self._master[v][0] for v in self.variables}
+        for bn in self._batch_norms():
+            out[bn.name + '/moving_mean'], out[bn.name + '/moving_variance'] = bn.moving_mean, bn.moving_variance
+        return out
+
+    def refresh_eval_net(self):
+        """Refold the native eval net's layers of the stages that are on from the masters and the training stages' moving statistics
+        as the device holds them (LightHeadDetector.refresh_weights: xdet_net_refresh_weights) -> the number of layers refreshed
+        (72 with all three flows: 38 convs and 34 depthwise).  Afterwards the eval net computes what a detector built from
+        export_weights(...) computes, bit for bit.  Under data-parallel training each rank folds its own moving statistics."""
+        if not hasattr(self.det, 'refresh_weights'):
+            raise InvalidArgumentError(-1, 'refresh_eval_net: a PipelinedDetector is out of scope: its two nets would each need the call')
+        tensors = self.eval_net_tensors()
+        self.det.refresh_weights(tensors)
+        return len(eval_net_groups(tensors)) + sum(1 for n in tensors if n.endswith('/depthwise_kernel'))
 
     def read(self):
         """-> {name: ndarray} for every variable and, under '<name>/Momentum', its momentum slot, in the checkpoint's shapes"""
@@ -1040,8 +1093,8 @@ class MomentumOptimizer(object):
 
     def export_weights(self, base):
         """a copy of the weights dict `base` with the optimizer's variables and the current moving statistics of the training
-        stages' batch norms replaced by what the device holds: fit for a new LightHeadDetector, whose eval net then folds the
-        trained weights"""
+        stages' batch norms replaced by what the device holds: fit for a checkpoint, or for a new LightHeadDetector, whose eval net then
+        folds the trained weights (refresh_eval_net() does that for this detector's own eval net without the download)"""
         _sync(self.det)
         out = dict(base)
         for v in self.variables:

@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot
+from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot, LayerRefresh
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
@@ -17,6 +17,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
            'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
+           'host_bn_fold', 'bn_fold_device', 'refresh_layers_table', 'refresh_layers_device',
            'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
 
 
@@ -740,6 +741,105 @@ def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, st
                                    d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
     _keep_alive((d_l2,), (ws,) + tuple(a for s in slots for a in s[:3]))
     return d_l2
+
+
+# ---- the refresh of forward layers from weights on the device (xdet_bn_fold, xdet_layers_refresh_device, csrc/conv_repack.hip) --
+
+def host_bn_fold(gamma, beta, moving_mean, moving_variance, eps, bias=None, dtype=np.float32):
+    """The NumPy statement of xdet_bn_fold (include/xdet.h), the inference fold of a batch norm -> (scale, shift),
+
+        scale = gamma / sqrt(moving_variance + eps)
+        shift = (beta - moving_mean * scale) + (bias * scale if bias is given else 0)
+
+    every operation rounded on its own in `dtype`: float32 is the op's result bit for bit (the + 0 of a fold without bias turns a
+    -0 shift into +0); float64 the yardstick."""
+    g, b, m, v = (np.asarray(a, dtype) for a in (gamma, beta, moving_mean, moving_variance))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        sc = g / np.sqrt(v + dtype(eps))
+    return sc, (b - m * sc) + (np.asarray(bias, dtype) * sc if bias is not None else dtype(0))
+
+
+def bn_fold_device(gamma, beta, moving_mean, moving_variance, eps, bias=None, C=None, stream=None):
+    """host_bn_fold on the device (xdet_bn_fold): four (five) device arrays of C floats (DeviceBuffers or dense DeviceTensors
+    whose last axis is C; C=: the count, where a buffer is larger than its array) -> (scale, shift) as DeviceBuffers of C floats.
+    Nothing is synchronised."""
+    arrs = [gamma, beta, moving_mean, moving_variance] + ([bias] if bias is not None else [])
+    if not all(isinstance(a, (DeviceBuffer, DeviceTensor)) for a in arrs):
+        raise InvalidArgumentError(-1, 'bn_fold: the arrays must be DeviceBuffers or DeviceTensors (device memory)')
+    C = int(C) if C is not None else (int(gamma.shape[-1]) if isinstance(gamma, DeviceTensor) else gamma.nbytes // 4)
+    if C <= 0 or any(isinstance(a, DeviceBuffer) and a.nbytes < 4 * C for a in arrs):
+        raise InvalidArgumentError(-1, 'bn_fold: every array must hold C = %d floats' % C)
+    sc, sh = DeviceBuffer(4 * C), DeviceBuffer(4 * C)
+    check(lib().xdet_bn_fold(gamma.ptr, beta.ptr, moving_mean.ptr, moving_variance.ptr, bias.ptr if bias is not None else None,
+                             float(eps), C, sc.ptr, sh.ptr, _handle(stream)))
+    _keep_alive((sc, sh), tuple(arrs))
+    return sc, sh
+
+
+def _refresh_array(a, n, what):
+    """a slot's kernel, scale or shift: a dense DeviceTensor of n elements or a DeviceBuffer of at least n floats -> pointer"""
+    if isinstance(a, DeviceTensor):
+        if a.ld != a.shape[-1] or math.prod(a.shape) != n:
+            raise InvalidArgumentError(-1, 'refresh_layers: %s must be dense and hold %d elements, got shape %r with ld %d'
+                                       % (what, n, a.shape, a.ld))
+    elif not isinstance(a, DeviceBuffer):
+        raise InvalidArgumentError(-1, 'refresh_layers: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                   % (what, type(a).__name__))
+    elif a.nbytes < 4 * n:
+        raise InvalidArgumentError(-1, 'refresh_layers: %s holds %d bytes, %d elements need %d' % (what, a.nbytes, n, 4 * n))
+    return a.ptr
+
+
+def refresh_layers_table(slots):
+    """the argument checks of refresh_layers_device, without touching the GPU -> (the xdet_layer_refresh table, the objects it
+    points to): what a caller sizes a workspace from (xdet_layers_refresh_workspace_bytes) ahead of the calls"""
+    slots = list(slots)
+    if not slots:
+        raise InvalidArgumentError(-1, 'refresh_layers: an empty slot table')
+    table, arrays = (LayerRefresh * len(slots))(), []
+    for i, slot in enumerate(slots):
+        slot = tuple(slot) + (None,) * (4 - len(slot)) if 2 <= len(slot) <= 4 else ()
+        if not slot:
+            raise InvalidArgumentError(-1, 'refresh_layers: slot %d must be (layer, kernel[, scale[, shift]])' % i)
+        layer, kernel, scale, shift = slot
+        if hasattr(layer, 'taps') and hasattr(layer, 'handle'):       # a SpectralConv: the library refuses it by name of the reason
+            n, co = layer.taps * layer.cin * layer.cout, layer.cout
+        elif hasattr(layer, 'kh') and hasattr(layer, 'handle'):
+            n, co = layer.kh * layer.kw * layer.cin * layer.cout, layer.cout
+        elif hasattr(layer, 'C') and hasattr(layer, 'handle'):
+            n, co = 9 * layer.C, 0
+            if scale is not None or shift is not None:
+                raise InvalidArgumentError(-1, 'refresh_layers: slot %d is a depthwise layer: it takes no scale and no shift' % i)
+        else:
+            raise InvalidArgumentError(-1, 'refresh_layers: slot %d\'s layer must be a Conv2D or a DepthwiseConv2D (a layer object of xdet.ops), got %s'
+                                       % (i, type(layer).__name__))
+        ptrs = [_refresh_array(a, m, 'slot %d\'s %s' % (i, what)) if a is not None else None
+                for a, m, what in ((kernel, n, 'kernel'), (scale, co, 'scale'), (shift, co, 'shift'))]
+        if not ptrs[0]:
+            raise InvalidArgumentError(-1, 'refresh_layers: slot %d has no kernel' % i)
+        table[i] = LayerRefresh(layer.handle, ptrs[0], ptrs[1], ptrs[2])
+        arrays += [a for a in (layer, kernel, scale, shift) if a is not None]
+    return table, arrays
+
+
+def refresh_layers_device(slots, stream=None, workspace=None):
+    """Conv2D.set_kernel_device / DepthwiseConv2D.set_kernel_device over a table of layers in a number of launches that does not
+    depend on its length (xdet_layers_refresh_device): slots is a sequence of (layer, kernel[, scale[, shift]]) with layer a
+    Conv2D or a DepthwiseConv2D, kernel a dense DeviceTensor in the layer's kernel shape (or a DeviceBuffer of that many floats),
+    scale / shift (Conv2D only) device arrays of cout floats or None (kept).  Every layer then holds what a layer created from
+    the same values would hold, bit for bit.  workspace: a DeviceBuffer of at least xdet_layers_refresh_workspace_bytes bytes
+    (default: allocated here and released on return, which waits for the device: pass one to keep the call asynchronous).  With a
+    workspace nothing is synchronised, and the caller keeps the workspace and the arrays alive until the stream has run the call.
+    The library refuses, by name of the reason, a layer listed twice, a grouped or spectral layer and a layer whose planes copy
+    carries a folded batch norm."""
+    table, arrays = refresh_layers_table(slots)
+    need = lib().xdet_layers_refresh_workspace_bytes(table, len(table))
+    if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
+        raise InvalidArgumentError(-1, 'refresh_layers: workspace must be a DeviceBuffer of at least %d bytes' % need)
+    if not need:
+        check(lib().xdet_layers_refresh_device(table, len(table), None, _handle(stream)))     # (the library names the reason)
+    ws = workspace if workspace is not None else DeviceBuffer(need)
+    check(lib().xdet_layers_refresh_device(table, len(table), ws.ptr, _handle(stream)))
 
 
 # ---- the gradient average of data-parallel training (xdet_grad_pack / xdet_grad_reduce_ranks, csrc/grad_average.hip; the
