@@ -946,6 +946,37 @@ typedef struct {
 } xdet_layer_refresh;
 size_t xdet_layers_refresh_workspace_bytes(const xdet_layer_refresh* slots_host, int n);
 int xdet_layers_refresh_device(const xdet_layer_refresh* slots_host, int n, void* workspace, void* stream);
+/* The pack op of the training step (csrc/weight_pack.hip): dense f32 tensors in device memory written side by side into a
+ * merged one, and back.  A slot is a merged tensor [outer, W] with W = the sum of its parts' widths, and 1 to 4 dense parts
+ * [outer, width_p]; with off_p = the sum of the widths in front of part p,
+ *     xdet_tensors_concat:   merged[o, off_p + c] = part_p[o, c]       for o < outer, c < width_p
+ *     xdet_tensors_split:    part_p[o, c] = merged[o, off_p + c]
+ * -- copies, no arithmetic: every bit pattern (NaN payloads, -0, denormals) arrives as it left, and the NumPy statements
+ * xdet.ops.host_concat / host_split equal the calls bit for bit.  This is every merge a plan does on the host when it is built:
+ * the large-separable block's K_a (outer 15 * cin, widths mid | mid), K_b (outer 15, widths mid * co | mid * co) and b_a (outer
+ * 1), the RPN's conv2d_1 | conv2d_2 (outer 512, widths 2A | 4A; their biases at outer 1) and the head's fc_cls | fc_loc (outer
+ * 2048, widths nc | 4); split is the adjoint, which takes the gradients of the merged tensors apart.  Slots are independent:
+ * two split slots may read one merged tensor (the gradient of a sum b0 + b1 goes to both addends).
+ * One launch serves the whole table: every part's dense element space is cut into runs of 4096 consecutive elements, one
+ * workgroup per run; the part and run tables are built here and uploaded into the workspace, as xdet_momentum_step does.  A
+ * part moves in 16-byte accesses when its width, its offset and (for outer > 1) W are multiples of 4 and both base pointers
+ * are 16-byte aligned, and in dwords otherwise.  Plain vector stores, no atomics; the call does not synchronise.
+ * workspace: xdet_tensors_concat_workspace_bytes / _split_workspace_bytes(slots, n_slots) bytes of device memory (the same
+ *   figure; 0 for a table the calls refuse); it needs no initialisation and may be larger; a call behind a call on the same
+ *   stream may reuse it.  Limits: at most 65536 slots, 2^22 runs, outer * W below 2^31 per slot.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work, never a skipped slot: a NULL or empty table, a NULL merged or part
+ *   pointer, outer <= 0, a width <= 0, n_parts outside 1..4, a NULL workspace, a table beyond the limits. */
+typedef struct {
+  float* merged;
+  int outer;
+  int n_parts;
+  float* part[4];
+  int width[4];
+} xdet_pack_slot;
+size_t xdet_tensors_concat_workspace_bytes(const xdet_pack_slot* slots_host, int n_slots);
+size_t xdet_tensors_split_workspace_bytes(const xdet_pack_slot* slots_host, int n_slots);
+int xdet_tensors_concat(const xdet_pack_slot* slots_host, int n_slots, void* workspace, void* stream);
+int xdet_tensors_split(const xdet_pack_slot* slots_host, int n_slots, void* workspace, void* stream);
 
 /* ---- the gradient average of data-parallel training (csrc/grad_average.hip; the exchange itself is
  * xdet_comm_average_gradients in csrc/comm.hip): every rank's gradients become the rank-ordered mean, ahead of the step ------
@@ -1139,6 +1170,26 @@ typedef struct {
   const float* data;
 } xdet_net_weight_dev;
 int xdet_net_refresh_weights(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
+/* The same for the layers the plan itself owns, outside xdet_net_refresh_weights' reach: the same table, three groups, each
+ * taken whole only --
+ *   rpn_head:          rpn_head/{conv2d, conv2d_1, conv2d_2}/{kernel, bias}: the 3x3 conv's layer from its kernel and bias,
+ *                      the fused 1x1 layer "rpn_head/conv2d_1+2" from conv2d_1 | conv2d_2 side by side (kernels and biases);
+ *   final_head:        final_head/{subnet_fc, fc_cls, fc_loc}/{kernel, bias}: "final_head/subnet_fc", and "fc_cls+fc_loc" from
+ *                      fc_cls | fc_loc side by side (a split-K layer: it reads the same K-blocked operand copies);
+ *   large_sep_feature: the eight conv tensors of Branch_0 and Branch_1 and batch_normalization/{gamma, beta, moving_mean,
+ *                      moving_variance}: the branches merged as the plan merges them when it is built (K_a, b_a, K_b), the
+ *                      bias b0 + b1 (xdet_add_rows on one row), xdet_bn_fold with eps 1e-5 and that bias, then the two
+ *                      direct-form layers.
+ * The merges are one xdet_tensors_concat table into scratch the net owns (one block at the first call: the two table doors'
+ * workspaces and every merged tensor but the large-separable kernels, which are a second block at the first call that names
+ * that group; xdet_net_memory reports both), then one xdet_layers_refresh_device table over the touched layers on `stream`,
+ * one synchronisation, and the host bookkeeping of xdet_net_refresh_weights: every touched layer's host copy of the epilogue
+ * scale is read back and the layers accept an activation exponent again.  Exponents and captured graphs stay.
+ * Errors -> XDET_ERR_INVALID_ARG, by name, before any GPU work and with no layer touched: a name outside the three groups (the
+ * body's variables among them), a group given in part, a name given twice, a NULL pointer, an empty table, a net that is not
+ * built, and a large_sep_feature group on a net whose block is in the spectral form (build it with the option
+ * large_sep=direct): a spectral layer keeps its kernel as DFT-domain block matrices. */
+int xdet_net_refresh_heads(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
 /* Device memory of the net's workspace and weights in bytes (everything the plan allocated), and how many bytes of
  * tensors were placed into blocks recycled from dead tensors (option "workspace" = "reuse", the default: a builder hands a
  * tensor's block back once its last consumer is planned and a later tensor takes it over -- a planes tensor only a block

@@ -13,7 +13,15 @@ call of (1) or (2) is shorter than the Python that issues it (the 148-slot table
 the host's; --kernels adds what the GPU alone needs, the kernels' own durations from a child run under
 `rocprofv3 --kernel-trace --stats`, and the step kernel's bytes per second against the copy rate.
 
-    python tools/optimizer_bench.py [--reps 20] [--kernels] [--txt profiles/optimizer_bench.txt]      (GPU box)"""
+--reach all: another measurement, on the flow tests' detector (256 pixels, 2 images, 64 ROIs, every training flag,
+large_sep='direct'): one whole MomentumOptimizer.step at reach='flows' (148 variables) and at reach='all' (170: the
+large-separable block, the RPN head and the head as well), wall time and time on the stream, medians of --reps calls; and the
+kernel launches of one step, counted from child runs under `rocprofv3 --kernel-trace --stats` -- at reach='flows', at
+reach='all', and at reach='all' on a detector with the exit flow alone (41 variables): the count does not depend on the
+number of variables.
+
+    python tools/optimizer_bench.py [--reps 20] [--kernels] [--txt profiles/optimizer_bench.txt]      (GPU box)
+    python tools/optimizer_bench.py --reach all [--reps 20] [--txt profiles/optimizer_heads_bench.txt]"""
 import argparse
 import csv
 import glob
@@ -60,8 +68,93 @@ def kernel_stats(a, say, elements):
                 say('    %-26s %5d calls  %8.1f us (fastest %.1f)%s' % (k, int(row['Calls']), us, lo, rate))
 
 
+STEP_KERNELS = ('momentum_step_kernel', 'momentum_l2_kernel', 'tensors_pack_kernel', 'add_rows_kernel', 'bn_fold_kernel',
+                'conv_repack_max_table_kernel', 'conv_repack_table_kernel', 'depthwise_repack_table_kernel')
+
+
+def heads_detector(stages):
+    flags = dict(pool_index=True, rpn_hidden=True, large_sep_train=True, exit_flow_train=True, large_sep='direct')
+    if stages == 'all':
+        flags.update(middle_flow_train=True, entry_flow_train=True)
+    return M.LightHeadDetector(W.make_lighthead_weights(1234), image_size=256, max_batch=2, rpn_post_nms_top_n=64, **flags)
+
+
+def tiny_gradients(opt):
+    rng = np.random.default_rng(0)
+    grads = {}
+    for v in opt.variables:
+        shape = opt._master[v][1]
+        b = to_device((rng.standard_normal(shape) * 1e-6).astype(np.float32))
+        grads[v] = DeviceTensor(b.ptr, shape, shape[-1], owner=b)
+    return grads
+
+
+def step_launches(a, reach, stages):
+    """{kernel: launches per step} of MomentumOptimizer.step: this script again as a child under the profiler, which takes
+    exactly --reps + 1 steps and launches none of these kernels otherwise"""
+    d = tempfile.mkdtemp(prefix='optimizer_bench_')
+    cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable,
+           os.path.abspath(__file__), '--child', '--reach', reach, '--stages', stages, '--reps', str(a.reps)]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    if p.returncode != 0:
+        raise SystemExit('the profiled child failed:\n' + p.stdout.decode()[-2000:])
+    files = glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True)
+    if not files:
+        raise SystemExit('no kernel_stats.csv under ' + d)
+    calls = {}
+    for row in csv.DictReader(open(sorted(files)[-1])):
+        for k in STEP_KERNELS:
+            if k + '(' in row['Name'] or k + '<' in row['Name']:
+                calls[k] = calls.get(k, 0) + int(row['Calls'])
+    return {k: n / float(a.reps + 1) for k, n in calls.items()}
+
+
+def reach_all(a, say):
+    set_precision('f16x3')
+    det = heads_detector(a.stages)
+    opts = [train.MomentumOptimizer(det, reach=r) for r in (('flows', 'all') if a.reach == 'all' and not a.child else (a.reach,))]
+    grads = tiny_gradients(opts[-1])
+    st = det.stream
+    results = []
+    for opt in opts:
+        opt.step(grads, 1e-9)
+        t = []
+        for _ in range(a.reps):
+            e0, e1 = Event(), Event()
+            st.synchronize()
+            t0 = time.perf_counter()
+            e0.record(st)
+            opt.step(grads, 1e-9)
+            e1.record(st)
+            st.synchronize()
+            t.append((e0.elapsed_ms(e1) * 1e3, (time.perf_counter() - t0) * 1e6))
+        results.append((opt, float(np.median([x[0] for x in t])), float(np.median([x[1] for x in t]))))
+    if a.child:
+        return
+    say('MomentumOptimizer.step on the flow tests\' detector (256 pixels, max_batch 2, 64 ROIs, every training stage, large_sep=direct); '
+        'medians of %d calls' % a.reps)
+    for opt, ev, wall in results:
+        elements = sum(int(np.prod(opt._master[v][1])) for v in opt.variables)
+        say("  reach='%s': %3d variables, %9d elements, %2d layers in the refresh table%s  %9.1f us on the stream, %9.1f us wall"
+            % (opt.reach, len(opt.variables), elements, len(opt._refresh_slots()),
+               ' + 4 behind xdet_net_refresh_heads' if opt.reach == 'all' else '                                  ', ev, wall))
+    say('  (the wall time holds the host\'s part: the slot tables of %d variables built and checked in Python, the result read back; at '
+        "reach='all' xdet_net_refresh_heads synchronises the stream once more and reads four layers' scales back)" % len(opts[-1].variables))
+    say('kernel launches of one step (rocprofv3 --kernel-trace --stats over %d steps of a child run):' % (a.reps + 1))
+    runs = [('flows', 'all'), ('all', 'all'), ('all', 'exit')]
+    counts = [step_launches(a, r, s) for r, s in runs]
+    say('  %-32s %s' % ('', '  '.join("reach='%s', %s" % (r, 'every stage (%d variables)' % (148 if r == 'flows' else 170) if s == 'all'
+                                                         else 'the exit flow alone (41 variables)') for r, s in runs)))
+    for k in STEP_KERNELS:
+        if any(k in c for c in counts):
+            say('  %-32s %s' % (k, '  '.join('%-36.4g' % c.get(k, 0) for c in counts)))
+    say('  %-32s %s' % ('all of them', '  '.join('%-36.4g' % sum(c.values()) for c in counts)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--reach', choices=('flows', 'all'), help="'all': the whole step at both reaches and its launch counts, see above")
+    ap.add_argument('--stages', choices=('all', 'exit'), default='all', help=argparse.SUPPRESS)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--kernels', action='store_true')
     ap.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
@@ -73,6 +166,12 @@ def main():
         lines.append(line)
         print(line, flush=True)
 
+    if a.reach:
+        reach_all(a, say)
+        if a.txt:
+            with open(a.txt, 'w') as fh:
+                fh.write('\n'.join(lines) + '\n')
+        return
     set_precision('f16x3')
     w = W.make_lighthead_weights(1234)
     det = M.LightHeadDetector(w, image_size=S, max_batch=2, rpn_post_nms_top_n=64, pool_index=True, rpn_hidden=True,

@@ -144,6 +144,15 @@ struct LightHeadNet : Plan {
   float *rf_scale = nullptr, *rf_shift = nullptr;   // the folds' scratch, a record's channels at rf_off[record]: allocated at
   void* rf_ws = nullptr;                            // the first refresh with the table door's workspace for the whole reach
   std::vector<size_t> rf_off;
+  int scale_read_back(ConvLayer* L);
+  // xdet_net_refresh_heads: the layers the plan owns -- the RPN head's two, the head's two dense layers and (direct form) the
+  // large-separable block's two -- from the checkpoint's tensors in device memory.  hd_*: the layers, set by the builders
+  // (hd_lsep stays NULL in the spectral form); hs_*: the merges' scratch, allocated at the first call
+  int refresh_heads(const xdet_net_weight_dev* table, int n, hipStream_t s);
+  ConvLayer *hd_rpn[2] = {nullptr, nullptr}, *hd_head[2] = {nullptr, nullptr}, *hd_lsep[2] = {nullptr, nullptr};
+  void *hs_block = nullptr, *hs_pack_ws = nullptr, *hs_repack_ws = nullptr;
+  float *hs_rpn_k = nullptr, *hs_rpn_b = nullptr, *hs_head_k = nullptr, *hs_head_b = nullptr;
+  float *hs_ka = nullptr, *hs_kb = nullptr, *hs_ba = nullptr, *hs_bsum = nullptr, *hs_scale = nullptr, *hs_shift = nullptr;
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);
   int forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                     hipStream_t s);

@@ -168,6 +168,7 @@ int LightHeadNet::build_rpn() {
   ConvLayer* L1 = keep(new ConvLayer());
   XDET_TRY(L1->init(1, 1, 512, co, 1, 1, 1, 0, 0, kc.data(), nullptr, bc.data(), 0));
   XDET_TRY(add_conv("rpn_head/conv2d_1+2", ST_RPN, hid, L1, nullptr, 0, &rpn_out));
+  hd_rpn[0] = L0; hd_rpn[1] = L1;
   return XDET_OK;
 }
 
@@ -216,6 +217,7 @@ int LightHeadNet::build_large_sep() {
   ConvLayer* LB = keep(new ConvLayer());
   XDET_TRY(LB->init(1, 15, 2 * mid, co, 1, 1, 1, 0, 0, kb.data(), sc.data(), sh.data(), 1));
   XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d_1", ST_LSEP, t, LB, nullptr, 0, &feat));
+  hd_lsep[0] = LA; hd_lsep[1] = LB;
   return XDET_OK;
 }
 
@@ -324,6 +326,7 @@ int LightHeadNet::build_head() {
   ConvEmit cls_emit;
   cls_emit.ksplit = latency_ksplit;     // 300 rows x 25 outputs: 3 tiles against 64 K steps
   XDET_TRY(add_conv("final_head/fc_cls+fc_loc", ST_HEAD, fc, L1, nullptr, 0, &cls_reg, cls_emit));
+  hd_head[0] = L0; hd_head[1] = L1;
   return XDET_OK;
 }
 
@@ -480,11 +483,7 @@ int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipSt
   };
   for (const auto& g : groups) {
     const LayerRec& r = layer_recs[g.first];
-    ConvLayer* L = r.conv;
-    XDET_TRY(download(L->d_scale, (size_t)L->cout_pad));
-    for (float& v : k) v = ldexpf(v, -L->in_exp);
-    L->in_scale.host = k;
-    L->host_stale = false;
+    XDET_TRY(scale_read_back(r.conv));
     if (r.dw) {
       DepthwiseLayer* D = r.dw;
       XDET_TRY(download(g.second[R_DW], (size_t)9 * D->C));
@@ -501,6 +500,151 @@ int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipSt
       hw->second.v = k;
     }
   }
+  return XDET_OK;
+}
+
+// behind a table repack and its synchronisation: the layer's host copy of the epilogue scale at exponent 0 (d_scale carries
+// 2^in_exp, exactly), so that a calibration may apply an activation exponent to it again
+int LightHeadNet::scale_read_back(ConvLayer* L) {
+  std::vector<float> k((size_t)L->cout_pad);
+  XDET_HIP(hipMemcpy(k.data(), L->d_scale, k.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (float& v : k) v = ldexpf(v, -L->in_exp);
+  L->in_scale.host = k;
+  L->host_stale = false;
+  return XDET_OK;
+}
+
+// The layers the plan itself owns from trained weights (include/xdet.h): names -> three groups, all checks, the merges by one
+// xdet_tensors_concat table into the net's scratch, the large-separable block's bias sum and fold, one table repack, one
+// synchronisation, and the host copies the calibration works from.
+int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStream_t s) {
+  XDET_REQUIRE(built, "net_refresh_heads: the net is not built");
+  XDET_REQUIRE(table && n > 0, "net_refresh_heads: an empty table");
+  enum { G_RPN, G_HEAD, G_LSEP, G_N };
+  static const char* const group_name[G_N] = {"rpn_head", "final_head", "large_sep_feature"};
+  std::vector<std::string> roles[G_N];
+  for (const char* l : {"conv2d", "conv2d_1", "conv2d_2"})
+    for (const char* v : {"/kernel", "/bias"}) roles[G_RPN].push_back(std::string("rpn_head/") + l + v);
+  for (const char* l : {"subnet_fc", "fc_cls", "fc_loc"})
+    for (const char* v : {"/kernel", "/bias"}) roles[G_HEAD].push_back(std::string("final_head/") + l + v);
+  for (const char* br : {"Branch_0", "Branch_1"})
+    for (const char* l : {"/conv2d", "/conv2d_1"})
+      for (const char* v : {"/kernel", "/bias"}) roles[G_LSEP].push_back(std::string("large_sep_feature/") + br + l + v);
+  for (const char* v : {"gamma", "beta", "moving_mean", "moving_variance"})
+    roles[G_LSEP].push_back(std::string("large_sep_feature/batch_normalization/") + v);
+  std::map<std::string, std::pair<int, int>> names;
+  for (int g = 0; g < G_N; ++g)
+    for (size_t r = 0; r < roles[g].size(); ++r) names[roles[g][r]] = {g, (int)r};
+  std::vector<const float*> given[G_N];
+  bool on[G_N] = {false, false, false};
+  for (int g = 0; g < G_N; ++g) given[g].assign(roles[g].size(), nullptr);
+  for (int i = 0; i < n; ++i) {
+    XDET_REQUIRE(table[i].name, "net_refresh_heads: a NULL name");
+    const std::string name(table[i].name);
+    auto it = names.find(name);
+    XDET_REQUIRE(it != names.end(), "net_refresh_heads: " + name + " is outside the reach (the rpn_head, final_head and "
+                                    "large_sep_feature groups; the body's blocks 2-14 are xdet_net_refresh_weights')");
+    XDET_REQUIRE(table[i].data, "net_refresh_heads: " + name + " is a NULL pointer");
+    const float*& slot = given[it->second.first][it->second.second];
+    XDET_REQUIRE(!slot, "net_refresh_heads: " + name + " is given twice");
+    slot = table[i].data;
+    on[it->second.first] = true;
+  }
+  for (int g = 0; g < G_N; ++g) {
+    if (!on[g]) continue;
+    for (size_t r = 0; r < roles[g].size(); ++r)
+      XDET_REQUIRE(given[g][r], std::string("net_refresh_heads: the group of ") + group_name[g] + " is given in part: " + roles[g][r] +
+                                " is missing");
+  }
+  XDET_REQUIRE(!on[G_LSEP] || !large_sep_spectral,
+               "net_refresh_heads: the large_sep_feature group needs a net whose block is in the direct form (option large_sep=direct): "
+               "this net's is in the spectral form, which keeps the kernels as DFT-domain block matrices");
+  XDET_REQUIRE((!on[G_RPN] || (hd_rpn[0] && hd_rpn[1])) && (!on[G_HEAD] || (hd_head[0] && hd_head[1])) &&
+               (!on[G_LSEP] || (hd_lsep[0] && hd_lsep[1])), "net_refresh_heads: the plan holds no such layers");
+  const int A = cfg.num_anchors, nc = cfg.num_classes, mid = 256, co = cfg.bank * cfg.grid * cfg.grid, cin = out.C;
+  const int hid = hd_rpn[0]->cout, fcw = hd_head[0]->cout;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  float* some = reinterpret_cast<float*>(this);              // (measuring reads no tensor)
+  // the concat slots of a group, from the table's arrays (measuring: from `some`) into the scratch
+  auto pack_slots = [&](int g, const std::vector<const float*>& src, std::vector<xdet_pack_slot>* slots) {
+    auto at = [&](int r) { return const_cast<float*>(src.empty() ? some : src[(size_t)r]); };
+    auto to = [&](float* d) { return src.empty() ? some : d; };
+    if (g == G_RPN) {
+      slots->push_back({to(hs_rpn_k), hid, 2, {at(2), at(4)}, {2 * A, 4 * A}});
+      slots->push_back({to(hs_rpn_b), 1, 2, {at(3), at(5)}, {2 * A, 4 * A}});
+    } else if (g == G_HEAD) {
+      slots->push_back({to(hs_head_k), fcw, 2, {at(2), at(4)}, {nc, 4}});
+      slots->push_back({to(hs_head_b), 1, 2, {at(3), at(5)}, {nc, 4}});
+    } else {
+      slots->push_back({to(hs_ka), 15 * cin, 2, {at(0), at(4)}, {mid, mid}});
+      slots->push_back({to(hs_ba), 1, 2, {at(1), at(5)}, {mid, mid}});
+      slots->push_back({to(hs_kb), 15, 2, {at(2), at(6)}, {mid * co, mid * co}});
+    }
+  };
+  if (!hs_block) {
+    // one block [pack workspace | repack workspace | rpn k, b | head k, b | b_a, b0 + b1, scale, shift]: either all of it
+    // exists or none; the large-separable block's two merged kernels are a second block, at the first call that names them
+    std::vector<xdet_pack_slot> slots;
+    for (int g = 0; g < G_N; ++g)
+      if (g != G_LSEP || !large_sep_spectral) pack_slots(g, {}, &slots);
+    const size_t pack_bytes = xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size());
+    std::vector<xdet_layer_refresh> all;
+    for (ConvLayer* L : {hd_rpn[0], hd_rpn[1], hd_head[0], hd_head[1], hd_lsep[0], hd_lsep[1]})
+      if (L) all.push_back({L, some, nullptr, nullptr});
+    const size_t rp_bytes = xdet_layers_refresh_workspace_bytes(all.data(), (int)all.size());
+    XDET_REQUIRE(pack_bytes > 0 && rp_bytes > 0, "net_refresh_heads: the plan holds a layer the table door refuses");
+    const size_t sizes[] = {up(pack_bytes), up(rp_bytes), up((size_t)hid * 6 * A * 4), up((size_t)6 * A * 4), up((size_t)fcw * (nc + 4) * 4),
+                            up((size_t)(nc + 4) * 4), up((size_t)2 * mid * 4), up((size_t)co * 4), up((size_t)co * 4), up((size_t)co * 4)};
+    size_t total = 0;
+    for (size_t b : sizes) total += b;
+    void* block = nullptr;
+    XDET_TRY(alloc_bytes(total, &block, false));
+    char* p = static_cast<char*>(block);
+    float** dst[] = {nullptr, nullptr, &hs_rpn_k, &hs_rpn_b, &hs_head_k, &hs_head_b, &hs_ba, &hs_bsum, &hs_scale, &hs_shift};
+    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
+      if (i == 0) hs_pack_ws = p;
+      else if (i == 1) hs_repack_ws = p;
+      else *dst[i] = reinterpret_cast<float*>(p);
+      p += sizes[i];
+    }
+    hs_block = block;
+  }
+  if (on[G_LSEP] && !hs_ka) {
+    const size_t ka_bytes = up((size_t)15 * cin * 2 * mid * 4), kb_bytes = up((size_t)15 * 2 * mid * co * 4);
+    void* block = nullptr;
+    XDET_TRY(alloc_bytes(ka_bytes + kb_bytes, &block, false));
+    hs_ka = static_cast<float*>(block);
+    hs_kb = reinterpret_cast<float*>(static_cast<char*>(block) + ka_bytes);
+  }
+  std::vector<xdet_pack_slot> slots;
+  std::vector<xdet_layer_refresh> layers;
+  for (int g = 0; g < G_N; ++g)
+    if (on[g]) pack_slots(g, given[g], &slots);
+  if (on[G_RPN]) {
+    layers.push_back({hd_rpn[0], given[G_RPN][0], nullptr, given[G_RPN][1]});
+    layers.push_back({hd_rpn[1], hs_rpn_k, nullptr, hs_rpn_b});
+  }
+  if (on[G_HEAD]) {
+    layers.push_back({hd_head[0], given[G_HEAD][0], nullptr, given[G_HEAD][1]});
+    layers.push_back({hd_head[1], hs_head_k, nullptr, hs_head_b});
+  }
+  if (on[G_LSEP]) {
+    layers.push_back({hd_lsep[0], hs_ka, nullptr, hs_ba});
+    layers.push_back({hd_lsep[1], hs_kb, hs_scale, hs_shift});
+  }
+  // every refusal the two table doors have is met here, ahead of the first launch: no layer is touched by a refused call
+  XDET_REQUIRE(xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size()) > 0 &&
+               xdet_layers_refresh_workspace_bytes(layers.data(), (int)layers.size()) > 0,
+               "net_refresh_heads: the plan holds a layer the table door refuses");
+  XDET_TRY(xdet_tensors_concat(slots.data(), (int)slots.size(), hs_pack_ws, s));
+  if (on[G_LSEP]) {
+    const std::vector<const float*>& g = given[G_LSEP];
+    XDET_TRY(xdet_add_rows(g[3], co, g[7], co, hs_bsum, co, 1, co, s));
+    XDET_TRY(xdet_bn_fold(g[8], g[9], g[10], g[11], hs_bsum, 1e-5f, co, hs_scale, hs_shift, s));
+  }
+  XDET_TRY(xdet_layers_refresh_device(layers.data(), (int)layers.size(), hs_repack_ws, s));
+  XDET_HIP(hipStreamSynchronize(s));
+  for (const xdet_layer_refresh& l : layers) XDET_TRY(scale_read_back(static_cast<ConvLayer*>(l.layer)));
   return XDET_OK;
 }
 

@@ -52,6 +52,12 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- tf.train.MomentumOptimizer with the L2 term and the learning-rate schedule of
                              light_head_rfcn_train.py:420-436 over the three flows' variables, and the refresh of their
                              forward layers' operands on the device
+  host_concat, host_split, concat_device, split_device (xdet.ops); LightHeadDetector.refresh_heads;
+  MomentumOptimizer(det, reach='all'), RPN_HEAD_VARIABLES, HEAD_VARIABLES (xdet.model; head_backward, rpn_backward and
+  large_sep_backward with weight_grads='device')
+                          <- the same optimizer over the large-separable block, the RPN head and the head as well (170
+                             variables): the merges the forward layers are built from, and the split of their gradients, as
+                             one table-driven copy on the device
   host_average_gradients, grad_pack_device, grad_reduce_ranks_device, grad_flat_offsets (xdet.ops);
   Communicator.average_gradients (xdet.dist); MomentumOptimizer.step(grads, lr, comm=...)
                           <- nothing in the reference (its trainer is one session; xdet_v5_resnet_train.py:144 only

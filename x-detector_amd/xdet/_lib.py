@@ -64,6 +64,12 @@ class LayerRefresh(ctypes.Structure):
     _fields_ = [('layer', c_void_p), ('kernel', c_void_p), ('scale', c_void_p), ('shift', c_void_p)]
 
 
+class PackSlot(ctypes.Structure):
+    """xdet_pack_slot: one slot of xdet_tensors_concat / xdet_tensors_split -- the merged tensor [outer, sum of widths], and 1 to 4
+    dense parts [outer, width] that lie side by side in it, device pointers"""
+    _fields_ = [('merged', c_void_p), ('outer', c_int), ('n_parts', c_int), ('part', c_void_p * 4), ('width', c_int * 4)]
+
+
 class NetWeightDev(ctypes.Structure):
     """xdet_net_weight_dev: one array of xdet_net_refresh_weights -- the checkpoint's name and the dense f32 data on the device"""
     _fields_ = [('name', ctypes.c_char_p), ('data', c_void_p)]
@@ -207,6 +213,10 @@ SIGNATURES = {
     'xdet_bn_fold': (c_int, [PF, PF, PF, PF, PF, c_float, c_int, PF, PF, c_void_p]),
     'xdet_layers_refresh_workspace_bytes': (c_size_t, [ctypes.POINTER(LayerRefresh), c_int]),
     'xdet_layers_refresh_device': (c_int, [ctypes.POINTER(LayerRefresh), c_int, c_void_p, c_void_p]),
+    'xdet_tensors_concat_workspace_bytes': (c_size_t, [ctypes.POINTER(PackSlot), c_int]),
+    'xdet_tensors_split_workspace_bytes': (c_size_t, [ctypes.POINTER(PackSlot), c_int]),
+    'xdet_tensors_concat': (c_int, [ctypes.POINTER(PackSlot), c_int, c_void_p, c_void_p]),
+    'xdet_tensors_split': (c_int, [ctypes.POINTER(PackSlot), c_int, c_void_p, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),
@@ -218,6 +228,7 @@ SIGNATURES = {
     'xdet_net_get_rpn': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_mid_refresh': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_refresh_weights': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
+    'xdet_net_refresh_heads': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
     'xdet_net_large_sep': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_rpn_decode': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_get_proposals': (c_int, [c_void_p, c_int, c_void_p]),

@@ -36,6 +36,7 @@ SOURCES = [
     ('pool_backward.hip', ['-ffp-contract=off']),
     ('optimizer.hip', ['-ffp-contract=off']),
     ('conv_repack.hip', ['-ffp-contract=off']),
+    ('weight_pack.hip', ['-ffp-contract=off']),
     ('grad_average.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),

@@ -235,6 +235,8 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
                         g_cls, g_loc)
     if keep_device:
         res.grad_device = DeviceTensor(d_grad.ptr, tuple(shp[:3]) + (6 * A,), ld, owner=d_grad)
+        from .train import forward_step
+        res.forward_step = forward_step(cls_score, '_rpn_step')      # (which weights the forward ran with: rpn_backward's guard)
     return res
 
 
@@ -310,4 +312,6 @@ class HeadLoss(object):
         self.result = head_loss(cls_score, bboxes_reg, labels, self.targets, self.fg_ratio, ohem_k, self.sigma, num_classes,
                                 stream=stream, device_grad=kept)
         self.grad_device = kept[0] if kept else None
+        from .train import forward_step
+        self.forward_step = forward_step(cls_score, '_head_step')    # (which weights the forward ran with: head_backward's guard)
         return self.result

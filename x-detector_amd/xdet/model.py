@@ -79,8 +79,13 @@ class LightHeadDetector(object):
         self.handle = h
         self._head_kernels = {}            # the dense layers' kernels as the checkpoint stores them (head_backward)
         self._rpn_kernels = {}             # ... and the RPN head's three (rpn_backward)
+        self._head_weights, self._rpn_weights = {}, {}     # both heads' kernels and biases (MomentumOptimizer(reach='all')'s masters)
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, np.float32)
+            if name in _train.HEAD_VARIABLES:
+                self._head_weights[name] = a
+            if rpn_hidden and name in _train.RPN_HEAD_VARIABLES:
+                self._rpn_weights[name] = a
             if name in ('final_head/subnet_fc/kernel', 'final_head/fc_cls/kernel', 'final_head/fc_loc/kernel'):
                 self._head_kernels[name] = a
             if rpn_hidden and name in ('rpn_head/conv2d/kernel', 'rpn_head/conv2d_1/kernel', 'rpn_head/conv2d_2/kernel'):
@@ -245,6 +250,24 @@ class LightHeadDetector(object):
         for i, (name, t) in enumerate(tensors.items()):
             table[i] = NetWeightDev(name.encode(), t.ptr)
         check(lib().xdet_net_refresh_weights(self.handle, table, len(tensors), self.stream.handle))
+
+    def refresh_heads(self, tensors):
+        """Refresh the layers the net's plan owns from weights on the device (xdet_net_refresh_heads): tensors is {checkpoint name:
+        dense f32 DeviceTensor or DeviceBuffer in the checkpoint's shape} over whole groups -- 'rpn_head' (train.RPN_HEAD_VARIABLES),
+        'final_head' (train.HEAD_VARIABLES), 'large_sep_feature' (train.LARGE_SEP_VARIABLES + LARGE_SEP_MOVING; a net whose block
+        is in the direct form only: large_sep='direct').  The merges run on the device into scratch the net owns, the touched
+        layers are repacked by one table, the stream is synchronised and the host state a calibration works from brought back in
+        line; exponents, plane_scales() and the captured graphs stay.  Refused ahead of any GPU work, by name: a host array, a name
+        outside the three groups, a group given in part, a duplicate, the large_sep_feature group on a spectral block."""
+        from ._lib import NetWeightDev
+        for name, t in tensors.items():
+            if not isinstance(t, (DeviceTensor, DeviceBuffer)) or not t.ptr:
+                raise InvalidArgumentError(-1, 'refresh_heads: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                           % (name, type(t).__name__))
+        table = (NetWeightDev * max(len(tensors), 1))()
+        for i, (name, t) in enumerate(tensors.items()):
+            table[i] = NetWeightDev(name.encode(), t.ptr)
+        check(lib().xdet_net_refresh_heads(self.handle, table, len(tensors), self.stream.handle))
 
     def x8_planes(self):
         """tensors in the x8 form (cross='fp8', after calibrate()): xdet_net_x8_planes"""
@@ -522,6 +545,7 @@ def get_rpn(net_input, num_anchors, is_training, data_format, var_scope):
     if not _same(net_input, d.buffer('mid', n)):
         raise XdetError(-1, 'get_rpn expects the mid_outputs tensor returned by XceptionBody')
     check(lib().xdet_net_get_rpn(d.handle, n, d.stream.handle))
+    _train.heads_ran(d, '_rpn_step')
     _sync(d)
     out = d.buffer('rpn_out', n)
     return out.channels(0, 2 * num_anchors), out.channels(2 * num_anchors, 6 * num_anchors)
@@ -616,6 +640,7 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
         d.write('feat', net_input.numpy() if isinstance(net_input, DeviceTensor) else net_input)
     d.write('proposals', np.asarray(proposals_bboxes, np.float32))
     check(lib().xdet_net_get_head(d.handle, n, d.stream.handle))
+    _train.heads_ran(d, '_head_step')
     _sync(d)
     if is_training:
         res = loss_func(d.buffer('cls_reg', n), None, int(ohem_roi_one_image) if using_ohem else 0, num_classes)

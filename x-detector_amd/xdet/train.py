@@ -6,7 +6,7 @@ detector built with a stage's flag keeps one state object for it (`LargeSepState
 `EntryFlowState`), made of `BatchNorm`, `SepUnit` and `Projection`; the module-level functions run a stage of the detector
 that is current (`with det.scope():`).  The head's and the RPN head's backward (`head_backward`, `rpn_backward`) and the NumPy
 statements of the middle and the entry flow (`host_*`) live here too, and the optimizer step over the three flows' variables
-(`MomentumOptimizer`, `piecewise_learning_rate`).
+and, at reach='all', the large-separable block's and both heads' (`MomentumOptimizer`, `piecewise_learning_rate`).
 """
 import collections
 import contextlib
@@ -18,20 +18,25 @@ from . import train_ops, ops
 from ._lib import lib, check, XdetError, InvalidArgumentError, MomentumSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, _det, _sync
 
-__all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
+__all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEAD_VARIABLES', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
            'EXIT_FLOW_UNITS', 'EXIT_FLOW_BNS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
            'MIDDLE_FLOW_BLOCKS', 'MIDDLE_FLOW_UNITS', 'MIDDLE_FLOW_VARIABLES', 'MIDDLE_FLOW_MOVING', 'MIDDLE_FLOW_EPS',
            'MIDDLE_FLOW_MOMENTUM', 'ENTRY_FLOW_BLOCKS', 'ENTRY_FLOW_UNITS', 'ENTRY_FLOW_VARIABLES', 'ENTRY_FLOW_MOVING',
            'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
-           'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'MomentumOptimizer']
+           'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'optimizer_variables',
+           'MomentumOptimizer']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
                             for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
     ('large_sep_feature/batch_normalization/gamma', 'large_sep_feature/batch_normalization/beta')
 LARGE_SEP_MOVING = ('large_sep_feature/batch_normalization/moving_mean', 'large_sep_feature/batch_normalization/moving_variance')
 LARGE_SEP_EPS, LARGE_SEP_MOMENTUM = 1e-5, 0.997        # net/resnet_v2.py: _BATCH_NORM_EPSILON, _BATCH_NORM_DECAY
+# the RPN head (net/xception_body.py:381-400) and the head's dense layers (:536-557): kernel, then bias, per layer, in the order
+# the native net's builders read them
+RPN_HEAD_VARIABLES = tuple('rpn_head/%s/%s' % (l, v) for l in ('conv2d', 'conv2d_1', 'conv2d_2') for v in ('kernel', 'bias'))
+HEAD_VARIABLES = tuple('final_head/%s/%s' % (l, v) for l in ('subnet_fc', 'fc_cls', 'fc_loc') for v in ('kernel', 'bias'))
 
 # the Xception exit flow (net/xception_body.py:339-376): four separable units (name, dilation, ReLU in front of the depthwise
 # conv, ReLU behind the batch norm) and the 1x1 projection of the residual branch
@@ -148,6 +153,50 @@ def _deliver(dev, grads, weight_grads):
     for k, (buf, shape) in dev.items():
         buf._keep = None                                 # (the stream has run: the operands need no keeping alive)
         grads[k] = DeviceTensor(buf.ptr, shape, shape[-1], owner=buf)
+
+
+def _new_grads(shapes):
+    """{name: a dense DeviceTensor of this shape that owns its memory}: what a backward's split writes, allocated ahead of its
+    launches"""
+    out = {}
+    for k, shape in shapes.items():
+        buf = DeviceBuffer(max(4 * math.prod(shape), 16))
+        out[k] = DeviceTensor(buf.ptr, shape, shape[-1], owner=buf)
+    return out
+
+
+def _as_grad(buf, shape):
+    """a gradient a backward op left in a DeviceBuffer of its own -> a dense DeviceTensor of the checkpoint's shape"""
+    buf._keep = None                                     # (called behind the sync: the operands need no keeping alive)
+    return DeviceTensor(buf.ptr, shape, shape[-1], owner=buf)
+
+
+# A step of MomentumOptimizer(reach='all') moves the RPN head's and the head's weights, so what get_rpn / get_head and the
+# losses left -- `rpn_hidden`, `fc`, `cls_reg`, the loss results and their gradients -- belongs to the old weights.  The
+# detector counts such steps (_heads_step), each of the two forwards records the count it ran at (_rpn_step, _head_step) and a
+# loss result carries its forward's (forward_step): rpn_backward / head_backward refuse a result whose count is not the
+# detector's, until the forward and the loss have run again.  A detector no such optimizer stepped has none of the attributes
+# and every count reads 0.
+_HEAD_FORWARDS = {'_rpn_step': 'get_rpn and losses.rpn_loss(..., keep_device=True)',
+                  '_head_step': 'get_head(..., is_training=True, ...)'}
+
+
+def heads_ran(d, attr):
+    """get_rpn ('_rpn_step') or get_head ('_head_step') has run on the detector's current weights"""
+    step = getattr(d, '_heads_step', 0)
+    if step or hasattr(d, attr):
+        setattr(d, attr, step)
+
+
+def forward_step(t, attr):
+    """what a loss result made from the tensor t (a view of a detector's buffer, or anything else) carries as forward_step"""
+    return getattr(getattr(t, '_owner', None), attr, 0)
+
+
+def _check_step(d, fn, result, attr):
+    if getattr(result, 'forward_step', 0) != getattr(d, '_heads_step', 0):
+        raise InvalidArgumentError(-1, '%s: call %s first (MomentumOptimizer.step has run since this loss result was made: it and '
+                                       'the tensors its forward kept belong to the old weights)' % (fn, _HEAD_FORWARDS[attr]))
 
 
 def _release(tensors):
@@ -290,6 +339,8 @@ class LargeSepState(object):
     for the backward, the batch norm (eps 1e-5, momentum 0.997), the kept t and z and the BN workspace"""
 
     def __init__(self, d, weights):
+        # (the eight conv tensors as the checkpoint stores them: what MomentumOptimizer(reach='all') makes its masters from)
+        self.host = {k: np.ascontiguousarray(weights[k], np.float32) for k in LARGE_SEP_VARIABLES[:8]}
         ka, ba, kb, bb = merge_large_sep({k: np.ascontiguousarray(weights[k], np.float32) for k in LARGE_SEP_VARIABLES})
         with _f16x3():
             self.conv_a, self.conv_b = ops.Conv2D(ka, shift=ba), ops.Conv2D(kb, shift=bb)
@@ -512,7 +563,34 @@ def new_body(d):
 
 # ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
 
-def head_backward(loss_func, to_feat=False):
+def _head_operands(d):
+    """the w operands of the head's two dense backwards, made once per detector: subnet_fc's kernel and fc_cls | fc_loc side by
+    side as [K,1,1,J] dense device tensors (MomentumOptimizer(reach='all') rebuilds them in place after a step)"""
+    if not hasattr(d, '_head_kernels_dev'):
+        k0 = d._head_kernels['final_head/subnet_fc/kernel']
+        k1 = np.concatenate([d._head_kernels['final_head/fc_cls/kernel'], d._head_kernels['final_head/fc_loc/kernel']], axis=1)
+        d._head_kernels_dev = []
+        for k in (k0, np.ascontiguousarray(k1)):
+            b = to_device(k)
+            d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
+    return d._head_kernels_dev
+
+
+def _rpn_operands(d):
+    """the w operands of the RPN head's backward, made once per detector: the 3x3 kernel, and conv2d_1 | conv2d_2 side by side
+    as a [512,1,1,6A] dense device tensor (MomentumOptimizer(reach='all') rebuilds them in place after a step)"""
+    if not hasattr(d, '_rpn_kernels_dev'):
+        A = d.cfg.num_anchors
+        k0 = d._rpn_kernels['rpn_head/conv2d/kernel']
+        k1 = np.ascontiguousarray(np.concatenate([d._rpn_kernels['rpn_head/conv2d_1/kernel'].reshape(-1, 2 * A),
+                                                  d._rpn_kernels['rpn_head/conv2d_2/kernel'].reshape(-1, 4 * A)], axis=1))
+        b0, b1 = to_device(k0), to_device(k1)
+        d._rpn_kernels_dev = (DeviceTensor(b0.ptr, k0.shape, k0.shape[3], owner=b0),
+                              DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
+    return d._rpn_kernels_dev
+
+
+def head_backward(loss_func, to_feat=False, weight_grads='host'):
     """The backward of the head's dense layers, called after get_head(..., is_training=True, ...) on the same detector:
     d loss / d cls_reg (loss_func.grad_device, what xdet_head_loss wrote) goes through `fc_cls+fc_loc` (x = the net's `fc`
     buffer, the concatenated [2048, nc + 4] kernel) and then, masked by fc's ReLU, through `subnet_fc` (x = `pooled`) -- two
@@ -522,8 +600,14 @@ def head_backward(loss_func, to_feat=False):
     to_feat=True (a detector built with pool_index=True): d loss / d pooled goes on through xdet_net_head_pool_backward -- the
     order-exact PsRoiAlign gradient on the net's `proposals` and the argmax get_head kept -- on the same stream, with no host
     round trip in between, and the dict gains 'feat': d loss / d feat as a DeviceTensor [N,H,W,C] with the `feat` buffer's
-    ld (padding channels zero), what the large-separable backward will read."""
+    ld (padding channels zero), what the large-separable backward will read.
+    weight_grads='device': the six variables come back as dense DeviceTensors in the checkpoint's shapes instead -- fc_cls and
+    fc_loc taken apart from the merged dW / db by one split_device table on the detector's stream -- and nothing is downloaded
+    (what MomentumOptimizer.step takes at reach='all'); everything else the call returns is unchanged.
+    Refused once a step of MomentumOptimizer(reach='all') has run since loss_func's result was made, until get_head has run
+    again: `fc`, `pooled` and the gradient belong to the old weights."""
     d = _det()
+    _check_weight_grads('head_backward', weight_grads)
     if to_feat and not d.pool_index:
         raise InvalidArgumentError(-1, 'head_backward: to_feat=True needs a detector built with pool_index=True (the head '
                                        'kept no argmax to go back through)')
@@ -537,37 +621,42 @@ def head_backward(loss_func, to_feat=False):
                                        'max_batch %d' % (g.shape, d.R, nc, d.max_batch))
     if len(d._head_kernels) != 3:
         raise InvalidArgumentError(-1, 'head_backward: the detector was built without the final_head kernels')
-    if not hasattr(d, '_head_kernels_dev'):
-        k0 = d._head_kernels['final_head/subnet_fc/kernel']
-        k1 = np.concatenate([d._head_kernels['final_head/fc_cls/kernel'], d._head_kernels['final_head/fc_loc/kernel']], axis=1)
-        d._head_kernels_dev = []
-        for k in (k0, np.ascontiguousarray(k1)):
-            b = to_device(k)
-            d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
-    w0, w1 = d._head_kernels_dev
+    _check_step(d, 'head_backward', loss_func, '_head_step')
+    w0, w1 = _head_operands(d)
     fc, pooled = d.buffer('fc', n), d.buffer('pooled', n)
+    K0, K1 = w0.shape[0], w1.shape[0]
     d_feat = None
     if to_feat:                                    # (allocated ahead of the launches, not between the last two)
         fb = d.buffer('feat', n)
         d_feat = DeviceTensor.empty(fb.shape, ld=fb.ld)
+    p, dev = 'final_head/', None
+    if weight_grads == 'device':
+        dev = _new_grads({p + 'fc_cls/kernel': (K1, nc), p + 'fc_cls/bias': (nc,), p + 'fc_loc/kernel': (K1, 4), p + 'fc_loc/bias': (4,)})
     dx1, dw1, db1 = train_ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
     dx0, dw0, db0 = train_ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
     if to_feat:
         check(lib().xdet_net_head_pool_backward(d.handle, n, dx0.ptr, dx0.ld, d_feat.ptr, d.stream.handle))
+    if dev is not None:
+        train_ops.split_device([(dw1, K1, [(dev[p + 'fc_cls/kernel'], nc), (dev[p + 'fc_loc/kernel'], 4)]),
+                                (db1, 1, [(dev[p + 'fc_cls/bias'], nc), (dev[p + 'fc_loc/bias'], 4)])], stream=d.stream)
     _sync(d)
-    K0, K1 = w0.shape[0], w1.shape[0]
-    kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
-    out = {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
-           'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
-           'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy(),
-           'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
-           'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)}
+    if dev is not None:
+        out = dict(dev)
+        out[p + 'subnet_fc/kernel'], out[p + 'subnet_fc/bias'] = _as_grad(dw0, (K0, K1)), _as_grad(db0, (K1,))
+        dw1._keep = None
+    else:
+        kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
+        out = {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
+               'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
+               'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy()}
+    out.update({'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
+                'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)})
     if to_feat:
         out['feat'] = d_feat
     return out
 
 
-def rpn_backward(rpn_loss_result):
+def rpn_backward(rpn_loss_result, weight_grads='host'):
     """The backward of the RPN head (net/xception_body.py:381-400), called after get_rpn and losses.rpn_loss(...,
     keep_device=True) on a detector built with rpn_hidden=True: d loss / d rpn_out (rpn_loss_result.grad_device, what
     xdet_rpn_loss wrote) goes through the two 1x1 heads as one dense layer (xdet_dense_backward: x = the net's `rpn_hidden`
@@ -575,8 +664,14 @@ def rpn_backward(rpn_loss_result):
     (xdet_conv_backward: x = `mid_x` with the ReLU in front of the conv, y = `rpn_hidden`) -- both on the detector's stream
     with no host round trip in between.  -> a dict with the six gradients under the checkpoint's variable names
     (rpn_head/{conv2d,conv2d_1,conv2d_2}/{kernel,bias}, NumPy), 'mid': d loss / d mid_x as a DeviceTensor [N,h,w,728] with
-    `mid_x`'s ld (zero where mid_x <= 0) and 'rpn_hidden': d loss / d rpn_hidden (in front of the ReLU mask) [N,h,w,512]."""
+    `mid_x`'s ld (zero where mid_x <= 0) and 'rpn_hidden': d loss / d rpn_hidden (in front of the ReLU mask) [N,h,w,512].
+    weight_grads='device': the six variables come back as dense DeviceTensors in the checkpoint's shapes instead -- conv2d_1
+    and conv2d_2 taken apart from the merged dW / db by one split_device table on the detector's stream -- and nothing is
+    downloaded (what MomentumOptimizer.step takes at reach='all'); everything else the call returns is unchanged.
+    Refused once a step of MomentumOptimizer(reach='all') has run since the loss result was made, until get_rpn and the loss
+    have run again: `rpn_hidden` and the gradient belong to the old weights."""
     d = _det()
+    _check_weight_grads('rpn_backward', weight_grads)
     if not d.rpn_hidden:
         raise InvalidArgumentError(-1, 'rpn_backward: needs a detector built with rpn_hidden=True (the RPN conv kept no f32 '
                                        'output to go back through)')
@@ -591,32 +686,38 @@ def rpn_backward(rpn_loss_result):
     if n > d.max_batch or tuple(g.shape[1:]) != tuple(out_view.shape[1:3]) + (6 * A,) or g.ld != out_view.ld:
         raise InvalidArgumentError(-1, 'rpn_backward: gradient of shape %r (ld %d) but the detector\'s rpn_out is %r (ld %d), '
                                        'max_batch %d' % (g.shape, g.ld, tuple(out_view.shape[1:]), out_view.ld, d.max_batch))
-    if not hasattr(d, '_rpn_kernels_dev'):
-        k0 = d._rpn_kernels['rpn_head/conv2d/kernel']
-        k1 = np.ascontiguousarray(np.concatenate([d._rpn_kernels['rpn_head/conv2d_1/kernel'].reshape(-1, 2 * A),
-                                                  d._rpn_kernels['rpn_head/conv2d_2/kernel'].reshape(-1, 4 * A)], axis=1))
-        b0, b1 = to_device(k0), to_device(k1)
-        d._rpn_kernels_dev = (DeviceTensor(b0.ptr, k0.shape, k0.shape[3], owner=b0),
-                              DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
-    w0, w1 = d._rpn_kernels_dev
+    _check_step(d, 'rpn_backward', rpn_loss_result, '_rpn_step')
+    w0, w1 = _rpn_operands(d)
     hid, mid_x = d.buffer('rpn_hidden', n), d.buffer('mid_x', n)
+    J, p, dev = w0.shape[3], 'rpn_head/', None
+    if weight_grads == 'device':
+        dev = _new_grads({p + 'conv2d_1/kernel': (1, 1, J, 2 * A), p + 'conv2d_1/bias': (2 * A,),
+                          p + 'conv2d_2/kernel': (1, 1, J, 4 * A), p + 'conv2d_2/bias': (4 * A,)})
     dx1, dw1, db1 = train_ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
     d_hid = DeviceTensor(dx1.ptr, hid.shape, dx1.ld, owner=dx1)
     dx0, dw0, db0 = train_ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
+    if dev is not None:
+        train_ops.split_device([(dw1, J, [(dev[p + 'conv2d_1/kernel'], 2 * A), (dev[p + 'conv2d_2/kernel'], 4 * A)]),
+                                (db1, 1, [(dev[p + 'conv2d_1/bias'], 2 * A), (dev[p + 'conv2d_2/bias'], 4 * A)])], stream=d.stream)
     _sync(d)
-    J = w0.shape[3]
-    kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
-    return {'rpn_head/conv2d/kernel': to_host(dw0.ptr, w0.shape), 'rpn_head/conv2d/bias': to_host(db0.ptr, (J,)),
-            'rpn_head/conv2d_1/kernel': np.ascontiguousarray(kw1[:, :2 * A]).reshape(1, 1, J, 2 * A),
-            'rpn_head/conv2d_1/bias': kb1[:2 * A].copy(),
-            'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
-            'rpn_head/conv2d_2/bias': kb1[2 * A:].copy(),
-            'mid': dx0, 'rpn_hidden': d_hid}
+    if dev is not None:
+        out = dict(dev)
+        out[p + 'conv2d/kernel'], out[p + 'conv2d/bias'] = _as_grad(dw0, w0.shape), _as_grad(db0, (J,))
+        dw1._keep = None
+    else:
+        kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
+        out = {'rpn_head/conv2d/kernel': to_host(dw0.ptr, w0.shape), 'rpn_head/conv2d/bias': to_host(db0.ptr, (J,)),
+               'rpn_head/conv2d_1/kernel': np.ascontiguousarray(kw1[:, :2 * A]).reshape(1, 1, J, 2 * A),
+               'rpn_head/conv2d_1/bias': kb1[:2 * A].copy(),
+               'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
+               'rpn_head/conv2d_2/bias': kb1[2 * A:].copy()}
+    out.update({'mid': dx0, 'rpn_hidden': d_hid})
+    return out
 
 
 # ---- the four stages, forward and backward -------------------------------------------------------------------------------------
 
-def large_sep_backward(d_feat):
+def large_sep_backward(d_feat, weight_grads='host'):
     """The backward of the large-separable block in training mode, called after large_sep_kernel(..., is_training=True) on a
     detector built with large_sep_train=True: d_feat = head_backward(..., to_feat=True)['feat'] (d loss / d feat, with the
     `feat` buffer's shape and ld) goes through the batch norm and its ReLU (xdet_batch_norm_backward on the kept z, masked
@@ -626,19 +727,38 @@ def large_sep_backward(d_feat):
     biases get the merged bias gradient), 'out': d loss / d out as a DeviceTensor [N,h,w,2048] with `out`'s ld, 'z':
     d loss / d z [N,h,w,co] and 't': d loss / d t [N,h,w,2*mid] (what the first conv backward read).  Refused once a new eval
     body (set_images, forward, calibrate, detect_images) or a training forward of one of the flows has run since the block's
-    own: the kept t and z belong to another `out`."""
+    own: the kept t and z belong to another `out`.
+    weight_grads='device': the ten variables come back as dense DeviceTensors in the checkpoint's shapes instead -- the eight
+    conv gradients taken apart from the merged ones by one split_device table on the detector's stream (split_large_sep_grads'
+    statement: both conv2d_1 biases get the merged bias gradient) -- and nothing is downloaded (what MomentumOptimizer.step
+    takes at reach='all'); everything else the call returns is unchanged."""
     d = _det()
+    _check_weight_grads('large_sep_backward', weight_grads)
     s, n = _stage(d, LARGE_SEP, 'large_sep_backward', 'large_sep_kernel(..., is_training=True)')
     feat, out = d.buffer('feat', n), d.buffer('out', n)
     _check_grad('large_sep_backward', 'd_feat', d_feat, feat)
+    co, mid2, mid, cin = s.K_b.shape[3], s.K_a.shape[3], s.mid, s.K_a.shape[2]
+    b0, b1, dev = 'large_sep_feature/Branch_0/', 'large_sep_feature/Branch_1/', None
+    if weight_grads == 'device':
+        dev = _new_grads({br + k: shape for br in (b0, b1) for k, shape in (('conv2d/kernel', (15, 1, cin, mid)), ('conv2d/bias', (mid,)),
+                                                                           ('conv2d_1/kernel', (1, 15, mid, co)), ('conv2d_1/bias', (co,)))})
     dz, dgamma, dbeta = s.bn.backward(d, _first(s.z, n), feat, d_feat)
     dt, dkb, dbb = train_ops.conv_backward_device(_first(s.t, n), s.K_b, dz, None, stream=d.stream)
     d_out, dka, dba = train_ops.conv_backward_device(out, s.K_a, dt, None, stream=d.stream)
+    if dev is not None:
+        train_ops.split_device([(dka, 15 * cin, [(dev[b0 + 'conv2d/kernel'], mid), (dev[b1 + 'conv2d/kernel'], mid)]),
+                                (dba, 1, [(dev[b0 + 'conv2d/bias'], mid), (dev[b1 + 'conv2d/bias'], mid)]),
+                                (dkb, 15, [(dev[b0 + 'conv2d_1/kernel'], mid * co), (dev[b1 + 'conv2d_1/kernel'], mid * co)]),
+                                (dbb, 1, [(dev[b0 + 'conv2d_1/bias'], co)]), (dbb, 1, [(dev[b1 + 'conv2d_1/bias'], co)])], stream=d.stream)
     _sync(d)
-    co, mid2 = s.K_b.shape[3], s.K_a.shape[3]
-    grads = split_large_sep_grads(to_host(dka.ptr, s.K_a.shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s.K_b.shape),
-                                  to_host(dbb.ptr, (co,)), s.mid)
-    _download({s.bn.name + '/gamma': (dgamma, (co,)), s.bn.name + '/beta': (dbeta, (co,))}, grads)
+    if dev is not None:
+        grads = dict(dev)
+        grads[s.bn.name + '/gamma'], grads[s.bn.name + '/beta'] = _as_grad(dgamma, (co,)), _as_grad(dbeta, (co,))
+        dka._keep = None
+    else:
+        grads = split_large_sep_grads(to_host(dka.ptr, s.K_a.shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s.K_b.shape),
+                                      to_host(dbb.ptr, (co,)), s.mid)
+        _download({s.bn.name + '/gamma': (dgamma, (co,)), s.bn.name + '/beta': (dbeta, (co,))}, grads)
     grads['out'], grads['z'], grads['t'] = d_out, dz, dt
     return grads
 
@@ -935,6 +1055,15 @@ def decayed(name):
     return 'batch_normalization' not in name and '_bn' not in name
 
 
+def optimizer_variables(on, reach='flows'):
+    """MomentumOptimizer.variables for a detector whose stages are `on` (one flag per stage, in STAGES' order): the entry, the
+    middle and the exit flow's variables of the stages that are on, in that order -- and with reach='all' LARGE_SEP_VARIABLES,
+    RPN_HEAD_VARIABLES and HEAD_VARIABLES behind them (170 with all stages on).  This is also the order of the gradient exchange."""
+    names = tuple(v for k, vs in ((ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES))
+                  if on[k] for v in vs)
+    return names + (LARGE_SEP_VARIABLES + RPN_HEAD_VARIABLES + HEAD_VARIABLES if reach == 'all' else ())
+
+
 def eval_net_groups(names):
     """The layer groups xdet_net_refresh_weights takes whole, from the names of a refresh table: a unit is
     <u>/depthwise_kernel, <u>/pointwise_kernel and the four arrays of <u>_bn; a projection conv2d_<i>/kernel and the four arrays
@@ -970,18 +1099,36 @@ class MomentumOptimizer(object):
     three, 15 + 48 + 9 = 72 of them kernels in the L2 set).  The masters are the buffers the stages already hold -- SepUnit.K_dw,
     SepUnit.K_pw, Projection.K, BatchNorm.gamma, BatchNorm.beta -- updated in place; the optimizer allocates the momentum slots
     (zero) and the step's workspace and holds a second copy of nothing.
-    Out of its reach: the large-separable block, the head, the RPN head and the stem keep their weights.  The NATIVE EVAL NET
+    Out of its reach (reach='flows', the default): the large-separable block, the head, the RPN head and the stem keep their weights.  The NATIVE EVAL NET
     keeps the weights it last folded -- XceptionBody(..., is_training=False), forward, detect_images and evaluate compute with
     them -- until refresh_eval_net() refolds the body's blocks 2-14 from the masters and the training stages' moving statistics
-    on the device (xdet_net_refresh_weights: no host round trip of the weights, no second net, the captured graphs stay)."""
+    on the device (xdet_net_refresh_weights: no host round trip of the weights, no second net, the captured graphs stay).
+    reach='all' (a detector built with large_sep_train=True and rpn_hidden=True that was given the rpn_head and final_head
+    weights): `variables` is the flows' list as above, then LARGE_SEP_VARIABLES, RPN_HEAD_VARIABLES and HEAD_VARIABLES -- 170
+    with all stages on, the 10 conv / dense kernels and their 10 biases of the three new groups in the L2 set (`decayed`; the
+    block's gamma and beta are not).  The masters of those 20 tensors are new device copies in the checkpoint's shapes, gamma
+    and beta the buffers LargeSepState.bn holds.  Only the two stem convs then stay at the checkpoint's values."""
 
-    def __init__(self, det, momentum=0.9, weight_decay=2e-4):
+    reach = 'flows'
+
+    def __init__(self, det, momentum=0.9, weight_decay=2e-4, reach='flows'):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
         on = [(k, names) for k, names in flows if getattr(det, STAGES[k].flag, False)]
         if not on:
             raise InvalidArgumentError(-1, 'MomentumOptimizer: needs a detector built with exit_flow_train=True (and optionally '
                                            'middle_flow_train, entry_flow_train): no flow stage is on')
-        self.det, self.momentum, self.weight_decay, self.steps = det, float(momentum), float(weight_decay), 0
+        if reach not in ('flows', 'all'):
+            raise InvalidArgumentError(-1, "MomentumOptimizer: reach must be 'flows' or 'all', got %r" % (reach,))
+        if reach == 'all':
+            hidden = getattr(det, 'rpn_hidden', False)
+            lack = [what for what, have in (('large_sep_train=True', getattr(det, 'large_sep_train', False)), ('rpn_hidden=True', hidden),
+                                            ('the three rpn_head kernels and biases in its weights',
+                                             not hidden or len(getattr(det, '_rpn_weights', ())) == 6),
+                                            ('the three final_head kernels and biases in its weights', len(getattr(det, '_head_weights', ())) == 6))
+                    if not have]
+            if lack:
+                raise InvalidArgumentError(-1, "MomentumOptimizer: reach='all' needs a detector built with %s" % ', '.join(lack))
+        self.det, self.momentum, self.weight_decay, self.steps, self.reach = det, float(momentum), float(weight_decay), 0, reach
         self._stages = [k for k, _ in on]
         masters = {}
         for u in self._units():
@@ -990,7 +1137,11 @@ class MomentumOptimizer(object):
             masters[p.name + '/kernel'] = (p.K, p.K.shape)
         for bn in self._batch_norms():
             masters[bn.name + '/gamma'], masters[bn.name + '/beta'] = (bn.gamma, (bn.co,)), (bn.beta, (bn.co,))
-        self.variables = tuple(v for _, names in on for v in names)
+        on_flags = [getattr(det, s.flag, False) for s in STAGES]
+        self._flow_variables = optimizer_variables(on_flags)
+        self.variables = optimizer_variables(on_flags, reach)
+        if reach == 'all':
+            self._reach_all(masters)
         self._master = {v: masters[v] for v in self.variables}            # name -> (device array, shape)
         self._decayed = {v: decayed(v) for v in self.variables}
         self._slot = {v: DeviceBuffer(4 * int(np.prod(self._master[v][1])), zero=True) for v in self.variables}
@@ -1002,6 +1153,41 @@ class MomentumOptimizer(object):
         if self._refresh_slots():
             rtable, _ = train_ops.refresh_layers_table(self._refresh_slots())
             self._refresh_ws = DeviceBuffer(lib().xdet_layers_refresh_workspace_bytes(rtable, len(rtable)))
+
+    def _reach_all(self, masters):
+        """reach='all': masters gains the 22 variables of the large-separable block, the RPN head and the head -- new device
+        copies of the 20 conv / dense tensors in the checkpoint's shapes, and the block's own gamma / beta -- and the optimizer the
+        concat table that rebuilds, from them, every merged tensor a forward layer or a backward reads: K_a, K_b and b_a of
+        LargeSepState, the two operands of rpn_backward and the two of head_backward (a one-part slot is a copy), with its
+        workspace; b_a and b_b = b0 + b1 live in two buffers the state gains here"""
+        d = self.det
+        s = d._lsep
+        host = dict(s.host)
+        host.update(d._rpn_weights)
+        host.update(d._head_weights)
+        m = {}
+        for v in LARGE_SEP_VARIABLES[:8] + RPN_HEAD_VARIABLES + HEAD_VARIABLES:
+            a = np.ascontiguousarray(host[v], np.float32)
+            b = to_device(a)
+            m[v] = DeviceTensor(b.ptr, a.shape, a.shape[-1], owner=b)
+            masters[v] = (m[v], a.shape)
+        masters[s.bn.name + '/gamma'], masters[s.bn.name + '/beta'] = (s.bn.gamma, (s.bn.co,)), (s.bn.beta, (s.bn.co,))
+        cin, mid2, co, mid = s.K_a.shape[2], s.K_a.shape[3], s.K_b.shape[3], s.mid
+        s.b_a, s.b_b = DeviceBuffer(4 * mid2), DeviceBuffer(4 * co)
+        (r0, r1), (h0, h1) = _rpn_operands(d), _head_operands(d)
+        A, nc, J, K0, K1 = d.cfg.num_anchors, d.cfg.num_classes, r0.shape[3], h0.shape[0], h1.shape[0]
+        b0, b1 = 'large_sep_feature/Branch_0/', 'large_sep_feature/Branch_1/'
+        self._bias_sum = (m[b0 + 'conv2d_1/bias'], m[b1 + 'conv2d_1/bias'], s.b_b, co)
+        self._concat = [(s.K_a, 15 * cin, [(m[b0 + 'conv2d/kernel'], mid), (m[b1 + 'conv2d/kernel'], mid)]),
+                        (s.K_b, 15, [(m[b0 + 'conv2d_1/kernel'], mid * co), (m[b1 + 'conv2d_1/kernel'], mid * co)]),
+                        (s.b_a, 1, [(m[b0 + 'conv2d/bias'], mid), (m[b1 + 'conv2d/bias'], mid)]),
+                        (r0, 9 * r0.shape[2], [(m['rpn_head/conv2d/kernel'], J)]),
+                        (r1, J, [(m['rpn_head/conv2d_1/kernel'], 2 * A), (m['rpn_head/conv2d_2/kernel'], 4 * A)]),
+                        (h0, K0, [(m['final_head/subnet_fc/kernel'], K1)]),
+                        (h1, K1, [(m['final_head/fc_cls/kernel'], nc), (m['final_head/fc_loc/kernel'], 4)])]
+        table, _ = train_ops._pack_table(self._concat, 'tensors_concat')
+        self._concat_ws = DeviceBuffer(lib().xdet_tensors_concat_workspace_bytes(table, len(table)))
+        self._head_names = RPN_HEAD_VARIABLES + HEAD_VARIABLES
 
     def _states(self):
         return [getattr(self.det, STAGES[k].attr) for k in self._stages]
@@ -1034,7 +1220,15 @@ class MomentumOptimizer(object):
         in the step's own synchronisation.  The ranks' variables and momentum slots stay bit-equal as long as they started
         bit-equal.  What is NOT averaged: each rank's batch-norm moving statistics stay its own (export_weights of any rank
         gives the same variables, but that rank's statistics), and so do the loss scalars.  The result dict is the same, and
-        `l2` is unchanged.  comm=None: a single process, no communicator is touched."""
+        `l2` is unchanged.  comm=None: a single process, no communicator is touched.
+        reach='all': `grads` also carries what head_backward, rpn_backward and large_sep_backward return with
+        weight_grads='device'.  Behind the one xdet_momentum_step, in this order: one concat_device table rebuilds from the masters
+        the merged K_a, K_b and b_a of LargeSepState and the operands rpn_backward and head_backward read, in place (and one
+        xdet_add_rows of one row b_b = b0 + b1), so the next backward differentiates the weights the forward used; conv_a and
+        conv_b join the xdet_layers_refresh_device table with their biases; and xdet_net_refresh_heads refreshes the net's own RPN
+        and head layers, which the eval net and the training forward share.  What get_rpn, get_head and the losses left is stale:
+        rpn_backward and head_backward refuse a loss result from before the step until the forward has run again.  The number
+        of launches does not depend on the number of variables."""
         miss = [v for v in self.variables if v not in grads]
         if miss:
             raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradients lack %s' % ', '.join(miss))
@@ -1050,37 +1244,66 @@ class MomentumOptimizer(object):
             comm.average_gradients([grads[v] for v in self.variables], d.stream)
             comm.wait()
         l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws)
+        if self.reach == 'all':                            # the merged tensors the layers and the backwards read, from the masters
+            train_ops.concat_device(self._concat, stream=d.stream, workspace=self._concat_ws)
+            b0, b1, bb, co = self._bias_sum
+            check(lib().xdet_add_rows(b0.ptr, co, b1.ptr, co, bb.ptr, co, 1, co, d.stream.handle))
         layers = self._refresh_slots()
         if layers:
             train_ops.refresh_layers_device(layers, stream=d.stream, workspace=self._refresh_ws)
+        if self.reach == 'all':
+            d.refresh_heads({v: self._master[v][0] for v in self._head_names})
+            d._heads_step = getattr(d, '_heads_step', 0) + 1
         new_body(d)
         _sync(d)
+        if self.reach == 'all':
+            self._concat[0][0]._keep = None                # (concat_device's keep-alive chain: the stream has run)
         l2._keep = None
         self.steps += 1
         return {'step': self.steps, 'lr': float(lr), 'l2': float(to_host(l2.ptr, (1,))[0])}
 
     def _refresh_slots(self):
         """the training forward layers and their masters, as the units hold them at this moment: refresh_layers_device's table"""
-        return [s for u in self._units() for s in ((u.pw, u.K_pw), (u.dw, u.K_dw))] + [(p.conv, p.K) for p in self._projections()]
+        slots = [s for u in self._units() for s in ((u.pw, u.K_pw), (u.dw, u.K_dw))] + [(p.conv, p.K) for p in self._projections()]
+        if self.reach == 'all':                            # the large-separable block's two merged convs, with their biases
+            s = self.det._lsep
+            slots += [(s.conv_a, s.K_a, None, s.b_a), (s.conv_b, s.K_b, None, s.b_b)]
+        return slots
 
     def eval_net_tensors(self):
         """{name: device array} of everything refresh_eval_net hands to the eval net: the masters of `self.variables` and the moving
         statistics of the batch norms of the stages that are on"""
-        out = {v: self._master[v][0] for v in self.variables}
+        out = {v: self._master[v][0] for v in self._flow_variables}
         for bn in self._batch_norms():
             out[bn.name + '/moving_mean'], out[bn.name + '/moving_variance'] = bn.moving_mean, bn.moving_variance
+        return out
+
+    def eval_net_large_sep_tensors(self):
+        """reach='all': {name: device array} of the large_sep_feature group refresh_eval_net hands to xdet_net_refresh_heads -- the
+        ten masters and the training stage's moving statistics"""
+        bn = self.det._lsep.bn
+        out = {v: self._master[v][0] for v in LARGE_SEP_VARIABLES}
+        out[bn.name + '/moving_mean'], out[bn.name + '/moving_variance'] = bn.moving_mean, bn.moving_variance
         return out
 
     def refresh_eval_net(self):
         """Refold the native eval net's layers of the stages that are on from the masters and the training stages' moving statistics
         as the device holds them (LightHeadDetector.refresh_weights: xdet_net_refresh_weights) -> the number of layers refreshed
         (72 with all three flows: 38 convs and 34 depthwise).  Afterwards the eval net computes what a detector built from
-        export_weights(...) computes, bit for bit.  Under data-parallel training each rank folds its own moving statistics."""
+        export_weights(...) computes, bit for bit.  Under data-parallel training each rank folds its own moving statistics.
+        reach='all': the large_sep_feature group -- the ten masters and the training stage's moving statistics -- goes through
+        xdet_net_refresh_heads first (LightHeadDetector.refresh_heads: merged, folded with eps 1e-5 and the bias b0 + b1, the two
+        direct-form layers repacked) -> 74.  A net whose block is in the spectral form refuses that group by name (build the
+        detector with large_sep='direct'), ahead of any launch of this call.  The RPN head and the head need nothing here: the
+        eval net and the training forward share those layers, and step has refreshed them."""
         if not hasattr(self.det, 'refresh_weights'):
             raise InvalidArgumentError(-1, 'refresh_eval_net: a PipelinedDetector is out of scope: its two nets would each need the call')
-        tensors = self.eval_net_tensors()
+        tensors, extra = self.eval_net_tensors(), 0
+        if self.reach == 'all':
+            self.det.refresh_heads(self.eval_net_large_sep_tensors())
+            extra = 2
         self.det.refresh_weights(tensors)
-        return len(eval_net_groups(tensors)) + sum(1 for n in tensors if n.endswith('/depthwise_kernel'))
+        return len(eval_net_groups(tensors)) + sum(1 for n in tensors if n.endswith('/depthwise_kernel')) + extra
 
     def read(self):
         """-> {name: ndarray} for every variable and, under '<name>/Momentum', its momentum slot, in the checkpoint's shapes"""

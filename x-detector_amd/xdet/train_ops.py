@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot, LayerRefresh
+from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot, LayerRefresh, PackSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
@@ -18,6 +18,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
            'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
            'host_bn_fold', 'bn_fold_device', 'refresh_layers_table', 'refresh_layers_device',
+           'host_concat', 'host_split', 'concat_device', 'split_device',
            'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
 
 
@@ -840,6 +841,102 @@ def refresh_layers_device(slots, stream=None, workspace=None):
         check(lib().xdet_layers_refresh_device(table, len(table), None, _handle(stream)))     # (the library names the reason)
     ws = workspace if workspace is not None else DeviceBuffer(need)
     check(lib().xdet_layers_refresh_device(table, len(table), ws.ptr, _handle(stream)))
+
+
+# ---- the pack op: dense tensors side by side in a merged one, and back (xdet_tensors_concat / _split, csrc/weight_pack.hip) ----
+
+def host_concat(parts, outer):
+    """The NumPy statement of xdet_tensors_concat (include/xdet.h) for one slot: every part, an array of outer * width_p elements
+    in any shape, is read as [outer, width_p] -> merged [outer, sum of widths], merged[o, off_p : off_p + width_p] =
+    part_p[o, :].  A copy: the bits pass through."""
+    outer = int(outer)
+    parts = [np.ascontiguousarray(p) for p in parts]
+    if outer <= 0 or not 1 <= len(parts) <= 4 or any(p.size == 0 or p.size % outer for p in parts):
+        raise InvalidArgumentError(-1, 'tensors_concat: 1 to 4 parts of outer * width elements each, width positive, got outer = %d '
+                                       'and sizes %r' % (outer, [p.size for p in parts]))
+    return np.ascontiguousarray(np.concatenate([p.reshape(outer, -1) for p in parts], axis=1))
+
+
+def host_split(merged, outer, widths):
+    """The NumPy statement of xdet_tensors_split for one slot: merged, an array of outer * sum(widths) elements in any shape ->
+    a list of the parts as [outer, width_p] arrays, part_p[o, :] = merged[o, off_p : off_p + width_p]"""
+    outer, widths = int(outer), [int(w) for w in widths]
+    m = np.ascontiguousarray(merged)
+    if outer <= 0 or not 1 <= len(widths) <= 4 or min(widths) <= 0 or m.size != outer * sum(widths):
+        raise InvalidArgumentError(-1, 'tensors_split: merged must hold outer * sum(widths) elements for 1 to 4 positive widths, got '
+                                       '%d elements, outer = %d, widths %r' % (m.size, outer, widths))
+    m = m.reshape(outer, sum(widths))
+    offs = np.cumsum([0] + widths)
+    return [np.ascontiguousarray(m[:, a:b]) for a, b in zip(offs[:-1], offs[1:])]
+
+
+def _pack_array(a, n, who, what):
+    """one tensor of a pack slot: a dense DeviceTensor of n elements or a DeviceBuffer of at least n floats -> pointer"""
+    if isinstance(a, DeviceTensor):
+        if a.ld != a.shape[-1] or math.prod(a.shape) != n:
+            raise InvalidArgumentError(-1, '%s: %s must be dense and hold %d elements, got shape %r with ld %d' % (who, what, n, a.shape, a.ld))
+    elif not isinstance(a, DeviceBuffer):
+        raise InvalidArgumentError(-1, '%s: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s' % (who, what, type(a).__name__))
+    elif a.nbytes < 4 * n:
+        raise InvalidArgumentError(-1, '%s: %s holds %d bytes, %d elements need %d' % (who, what, a.nbytes, n, 4 * n))
+    if not a.ptr:
+        raise InvalidArgumentError(-1, '%s: %s is a NULL pointer' % (who, what))
+    return a.ptr
+
+
+def _pack_table(slots, who):
+    """the argument checks of concat_device / split_device, without touching the GPU -> (the xdet_pack_slot table, the arrays it
+    points to)"""
+    slots = list(slots)
+    if not slots:
+        raise InvalidArgumentError(-1, '%s: an empty slot table' % who)
+    table, arrays = (PackSlot * len(slots))(), []
+    for i, slot in enumerate(slots):
+        if len(slot) != 3:
+            raise InvalidArgumentError(-1, '%s: slot %d must be (merged, outer, [(part, width), ...])' % (who, i))
+        merged, outer, parts = slot
+        parts = [tuple(p) for p in parts]
+        if isinstance(outer, bool) or not isinstance(outer, (int, np.integer)) or outer <= 0:
+            raise InvalidArgumentError(-1, '%s: slot %d has outer = %r (a positive integer)' % (who, i, outer))
+        if not 1 <= len(parts) <= 4 or any(len(p) != 2 for p in parts):
+            raise InvalidArgumentError(-1, '%s: slot %d must have 1 to 4 (part, width) pairs, got %d' % (who, i, len(parts)))
+        widths = [int(w) for _, w in parts]
+        if min(widths) <= 0 or int(outer) * sum(widths) >= 2 ** 31:
+            raise InvalidArgumentError(-1, '%s: slot %d has widths %r at outer = %d (positive, outer * their sum below 2^31)'
+                                       % (who, i, widths, outer))
+        s = PackSlot()
+        s.merged, s.outer, s.n_parts = _pack_array(merged, int(outer) * sum(widths), who, 'slot %d\'s merged tensor' % i), int(outer), len(parts)
+        for p, (a, w) in enumerate(parts):
+            s.part[p], s.width[p] = _pack_array(a, int(outer) * int(w), who, 'slot %d\'s part %d' % (i, p)), int(w)
+        table[i] = s
+        arrays += [merged] + [a for a, _ in parts]
+    return table, arrays
+
+
+def _pack_device(slots, who, sizer, door, stream, workspace):
+    table, arrays = _pack_table(slots, who)
+    need = sizer(table, len(table))
+    if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
+        raise InvalidArgumentError(-1, '%s: workspace must be a DeviceBuffer of at least %d bytes' % (who, need))
+    ws = workspace if workspace is not None else DeviceBuffer(need)
+    check(door(table, len(table), ws.ptr, _handle(stream)))
+    _keep_alive(arrays[:1], (ws,) + tuple(arrays), chain=True)
+
+
+def concat_device(slots, stream=None, workspace=None):
+    """host_concat over a table of slots in one launch (xdet_tensors_concat): slots is a sequence of (merged, outer, [(part,
+    width), ...]) with merged and the 1 to 4 parts dense DeviceTensors of exactly outer * W and outer * width elements (any
+    shape) or DeviceBuffers of at least that many floats; merged[o, off_p : off_p + width_p] = part_p[o, :].  workspace: a
+    DeviceBuffer of at least xdet_tensors_concat_workspace_bytes bytes (default: allocated here).  Nothing is synchronised."""
+    l = lib()
+    _pack_device(slots, 'tensors_concat', l.xdet_tensors_concat_workspace_bytes, l.xdet_tensors_concat, stream, workspace)
+
+
+def split_device(slots, stream=None, workspace=None):
+    """host_split over a table of slots in one launch (xdet_tensors_split): the slots of concat_device, copied the other way,
+    part_p[o, :] = merged[o, off_p : off_p + width_p].  Two slots may read one merged tensor."""
+    l = lib()
+    _pack_device(slots, 'tensors_split', l.xdet_tensors_split_workspace_bytes, l.xdet_tensors_split, stream, workspace)
 
 
 # ---- the gradient average of data-parallel training (xdet_grad_pack / xdet_grad_reduce_ranks, csrc/grad_average.hip; the
