@@ -11,6 +11,7 @@ TRAINING_NAMES = [
     'EXIT_FLOW_UNITS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
     'MIDDLE_FLOW_BLOCKS', 'MIDDLE_FLOW_UNITS', 'MIDDLE_FLOW_VARIABLES', 'MIDDLE_FLOW_MOVING', 'MIDDLE_FLOW_EPS', 'MIDDLE_FLOW_MOMENTUM',
     'ENTRY_FLOW_BLOCKS', 'ENTRY_FLOW_UNITS', 'ENTRY_FLOW_VARIABLES', 'ENTRY_FLOW_MOVING', 'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM',
+    'merged_layout', 'merged_shapes', 'LARGE_SEP_BIAS_SUM',
 ]
 
 

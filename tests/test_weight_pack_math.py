@@ -83,6 +83,18 @@ def test_concat_states_the_heads_operands():
     c1, c2 = rng.standard_normal((1, 1, J, 2 * A)).astype(f32), rng.standard_normal((1, 1, J, 4 * A)).astype(f32)
     r1 = np.ascontiguousarray(np.concatenate([c1.reshape(-1, 2 * A), c2.reshape(-1, 4 * A)], axis=1))      # rpn_backward
     assert np.array_equal(C.bits(host_concat([c1, c2], J)), C.bits(r1))
+    # ... which the backwards now build from xdet.train.merged_layout: the table's K_1 slots are those two concatenations
+    from xdet.train import merged_layout
+    head = {key: (outer, parts) for key, outer, parts in merged_layout('final_head', nc=nc, co=3, fcw=K)}
+    rpn = {key: (outer, parts) for key, outer, parts in merged_layout('rpn_head', A=A, cin=2, hid=J)}
+    assert head['K_1'] == (K, [('final_head/fc_cls/kernel', nc), ('final_head/fc_loc/kernel', 4)])
+    assert head['b_1'] == (1, [('final_head/fc_cls/bias', nc), ('final_head/fc_loc/bias', 4)])
+    assert rpn['K_1'] == (J, [('rpn_head/conv2d_1/kernel', 2 * A), ('rpn_head/conv2d_2/kernel', 4 * A)])
+    assert rpn['b_1'] == (1, [('rpn_head/conv2d_1/bias', 2 * A), ('rpn_head/conv2d_2/bias', 4 * A)])
+    for (outer, parts), tensors, want in ((head['K_1'], (cls, loc), k1), (rpn['K_1'], (c1, c2), r1)):
+        assert np.array_equal(C.bits(host_concat(tensors, outer)), C.bits(want))
+        for got, t in zip(host_split(want, outer, [w for _, w in parts]), tensors):
+            assert np.array_equal(C.bits(got.reshape(t.shape)), C.bits(t))
     # the gradients' way back: kw1[:, :nc] / kw1[:, nc:] and kb1[:nc] / kb1[nc:]
     g_cls, g_loc = host_split(k1, K, (nc, 4))
     assert np.array_equal(C.bits(g_cls), C.bits(np.ascontiguousarray(k1[:, :nc]))) and np.array_equal(C.bits(g_loc), C.bits(np.ascontiguousarray(k1[:, nc:])))

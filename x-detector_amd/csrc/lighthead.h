@@ -1,5 +1,6 @@
 // The Light-Head R-CNN eval graph (lighr_head_model_fn, light_head_rfcn_eval.py:364-433) as a static launch plan.
 #pragma once
+#include "merged_layers.h"
 #include "plan.h"
 
 namespace xdet {
@@ -54,8 +55,22 @@ struct LightHeadNet : Plan {
 
   int build_rpn();
 
-  int large_sep_weights(int cin, int mid, int co, std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb,
-                        std::vector<float>* sc, std::vector<float>* sh) const;
+  // the sizes merged_layers.h describes the three merged groups by (cin: known once build_body has run)
+  MergedSizes merged_sizes() const { return {cfg.num_anchors, cfg.num_classes, 512, 2048, out.C, 256, cfg.bank * cfg.grid * cfg.grid}; }
+  // a group's conv / dense tensors by role, each checked against its checkpoint shape -> their host arrays
+  int need_group(int g, std::initializer_list<std::initializer_list<int64_t>> dims, std::vector<const float*>* by_role) const {
+    const std::vector<std::string> names = merged_roles(g);
+    size_t role = 0;
+    for (const auto& d : dims) {
+      const HostTensor* t;
+      XDET_TRY(need(names[role++], &t, d));
+      by_role->push_back(t->v.data());
+    }
+    return XDET_OK;
+  }
+
+  int large_sep_weights(std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb, std::vector<float>* sc,
+                        std::vector<float>* sh) const;
 
   int build_large_sep();
 
@@ -141,18 +156,16 @@ struct LightHeadNet : Plan {
   int mid_refresh(int N, hipStream_t s);
   // xdet_net_refresh_weights: the body's blocks 2-14 from trained weights in device memory, through layer_recs
   int refresh_weights(const xdet_net_weight_dev* table, int n, hipStream_t s);
-  float *rf_scale = nullptr, *rf_shift = nullptr;   // the folds' scratch, a record's channels at rf_off[record]: allocated at
-  void* rf_ws = nullptr;                            // the first refresh with the table door's workspace for the whole reach
-  std::vector<size_t> rf_off;
+  BodyRefreshScratch rf;                            // one block for the whole reach, allocated at the first refresh; the folds
+  std::vector<size_t> rf_off;                       // of a record's channels at rf.scale / rf.shift + rf_off[record]
   int scale_read_back(ConvLayer* L);
   // xdet_net_refresh_heads: the layers the plan owns -- the RPN head's two, the head's two dense layers and (direct form) the
   // large-separable block's two -- from the checkpoint's tensors in device memory.  hd_*: the layers, set by the builders
-  // (hd_lsep stays NULL in the spectral form); hs_*: the merges' scratch, allocated at the first call
+  // (hd_lsep stays NULL in the spectral form); hs, hs_k: the merges' scratch, allocated at the first call (that names the block)
   int refresh_heads(const xdet_net_weight_dev* table, int n, hipStream_t s);
   ConvLayer *hd_rpn[2] = {nullptr, nullptr}, *hd_head[2] = {nullptr, nullptr}, *hd_lsep[2] = {nullptr, nullptr};
-  void *hs_block = nullptr, *hs_pack_ws = nullptr, *hs_repack_ws = nullptr;
-  float *hs_rpn_k = nullptr, *hs_rpn_b = nullptr, *hs_head_k = nullptr, *hs_head_b = nullptr;
-  float *hs_ka = nullptr, *hs_kb = nullptr, *hs_ba = nullptr, *hs_bsum = nullptr, *hs_scale = nullptr, *hs_shift = nullptr;
+  HeadsRefreshScratch hs;
+  LargeSepKernelScratch hs_k;
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);
   int forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                     hipStream_t s);

@@ -136,16 +136,12 @@ int LightHeadNet::build_body() {
 int LightHeadNet::build_rpn() {
   struct PoolGuard { int& p; int old; ~PoolGuard() { p = old; } } pool_guard{ws_pool, ws_pool};
   ws_pool = rpn_side_stream ? 1 : 0;      // the branch runs beside the exit flow: no workspace block shared with the main stream
-  const int A = cfg.num_anchors;
-  const HostTensor *k0, *b0, *k1, *b1, *k2, *b2;
-  XDET_TRY(need("rpn_head/conv2d/kernel", &k0, {3, 3, 728, 512}));
-  XDET_TRY(need("rpn_head/conv2d/bias", &b0, {512}));
-  XDET_TRY(need("rpn_head/conv2d_1/kernel", &k1, {1, 1, 512, 2 * A}));
-  XDET_TRY(need("rpn_head/conv2d_1/bias", &b1, {2 * A}));
-  XDET_TRY(need("rpn_head/conv2d_2/kernel", &k2, {1, 1, 512, 4 * A}));
-  XDET_TRY(need("rpn_head/conv2d_2/bias", &b2, {4 * A}));
+  const MergedSizes z = merged_sizes();
+  const int A = z.A, hw = z.hid;
+  std::vector<const float*> t;
+  XDET_TRY(need_group(MG_RPN, {{3, 3, 728, hw}, {hw}, {1, 1, hw, 2 * A}, {2 * A}, {1, 1, hw, 4 * A}, {4 * A}}, &t));
   ConvLayer* L0 = keep(new ConvLayer());
-  XDET_TRY(L0->init(3, 3, 728, 512, 1, 1, 1, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
+  XDET_TRY(L0->init(3, 3, 728, hw, 1, 1, 1, 0, 0, t[HEAD_K0], nullptr, t[HEAD_B0], 1));
   Buf hid;
   ConvEmit hid_emit;
   // only the fused 1x1 heads read it: planes alone -- unless the RPN's backward wants the f32 tensor for its ReLU mask
@@ -157,16 +153,10 @@ int LightHeadNet::build_rpn() {
   XDET_TRY(add_conv("rpn_head/conv2d", ST_RPN, mid_x, L0, nullptr, /*relu_in=*/1, &hid, hid_emit));
   if (keep_rpn_hidden) rpn_hidden = hid;      // a named buffer: never handed back to the pool
   // cls (2A) and box (4A) 1x1 heads share their input: one GEMM over the concatenated filters
-  const int co = 6 * A;
-  std::vector<float> kc((size_t)512 * co), bc(co);
-  for (int ci = 0; ci < 512; ++ci) {
-    for (int j = 0; j < 2 * A; ++j) kc[(size_t)ci * co + j] = k1->v[(size_t)ci * 2 * A + j];
-    for (int j = 0; j < 4 * A; ++j) kc[(size_t)ci * co + 2 * A + j] = k2->v[(size_t)ci * 4 * A + j];
-  }
-  for (int j = 0; j < 2 * A; ++j) bc[j] = b1->v[j];
-  for (int j = 0; j < 4 * A; ++j) bc[2 * A + j] = b2->v[j];
+  const std::vector<MergedSlot> slots = merged_slots(MG_RPN, z);
+  const std::vector<float> kc = merged_concat(slots[SLOT_K], t.data()), bc = merged_concat(slots[SLOT_B], t.data());
   ConvLayer* L1 = keep(new ConvLayer());
-  XDET_TRY(L1->init(1, 1, 512, co, 1, 1, 1, 0, 0, kc.data(), nullptr, bc.data(), 0));
+  XDET_TRY(L1->init(1, 1, hw, (int)slots[SLOT_K].W(), 1, 1, 1, 0, 0, kc.data(), nullptr, bc.data(), 0));
   XDET_TRY(add_conv("rpn_head/conv2d_1+2", ST_RPN, hid, L1, nullptr, 0, &rpn_out));
   hd_rpn[0] = L0; hd_rpn[1] = L1;
   return XDET_OK;
@@ -175,47 +165,33 @@ int LightHeadNet::build_rpn() {
 // The large-separable block's weights (net/xception_body.py:450-475) with its two branches fused: both (15,1) convs read
 // the same input -> ONE conv with the filters concatenated (2*mid outputs: ka, ba); branch_0b + branch_1b = ONE (1,15) conv
 // over the 2*mid stacked channels (kb), whose bias sum is folded into the BN(1e-5) + ReLU behind it (sc, sh)
-int LightHeadNet::large_sep_weights(int cin, int mid, int co, std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb,
-                      std::vector<float>* sc, std::vector<float>* sh) const {
-  const HostTensor *a0, *a0b, *a1, *a1b, *c0, *c0b, *c1, *c1b;
-  XDET_TRY(need("large_sep_feature/Branch_0/conv2d/kernel", &a0, {15, 1, cin, mid}));
-  XDET_TRY(need("large_sep_feature/Branch_0/conv2d/bias", &a0b, {mid}));
-  XDET_TRY(need("large_sep_feature/Branch_1/conv2d/kernel", &a1, {15, 1, cin, mid}));
-  XDET_TRY(need("large_sep_feature/Branch_1/conv2d/bias", &a1b, {mid}));
-  XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/kernel", &c0, {1, 15, mid, co}));
-  XDET_TRY(need("large_sep_feature/Branch_0/conv2d_1/bias", &c0b, {co}));
-  XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/kernel", &c1, {1, 15, mid, co}));
-  XDET_TRY(need("large_sep_feature/Branch_1/conv2d_1/bias", &c1b, {co}));
-  const int mid2 = 2 * mid;
-  ka->resize((size_t)15 * cin * mid2);
-  ba->resize(mid2);
-  kb->resize((size_t)15 * mid2 * co);
-  for (size_t tc = 0; tc < (size_t)15 * cin; ++tc) {
-    memcpy(&(*ka)[tc * mid2], &a0->v[tc * mid], mid * sizeof(float));
-    memcpy(&(*ka)[tc * mid2 + mid], &a1->v[tc * mid], mid * sizeof(float));
-  }
-  for (int j = 0; j < mid; ++j) { (*ba)[j] = a0b->v[j]; (*ba)[mid + j] = a1b->v[j]; }
-  for (int tap = 0; tap < 15; ++tap)
-    for (int ci = 0; ci < mid; ++ci) {
-      memcpy(&(*kb)[((size_t)tap * mid2 + ci) * co], &c0->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
-      memcpy(&(*kb)[((size_t)tap * mid2 + mid + ci) * co], &c1->v[((size_t)tap * mid + ci) * co], co * sizeof(float));
-    }
+int LightHeadNet::large_sep_weights(std::vector<float>* ka, std::vector<float>* ba, std::vector<float>* kb, std::vector<float>* sc,
+                                    std::vector<float>* sh) const {
+  const MergedSizes z = merged_sizes();
+  const int cin = z.cin, mid = z.mid, co = z.co;
+  std::vector<const float*> t;
+  XDET_TRY(need_group(MG_LSEP, {{15, 1, cin, mid}, {mid}, {1, 15, mid, co}, {co}, {15, 1, cin, mid}, {mid}, {1, 15, mid, co}, {co}}, &t));
+  const std::vector<MergedSlot> slots = merged_slots(MG_LSEP, z);
+  *ka = merged_concat(slots[SLOT_KA], t.data());
+  *ba = merged_concat(slots[SLOT_BA], t.data());
+  *kb = merged_concat(slots[SLOT_KB], t.data());
   std::vector<float> bsum(co);
-  for (int j = 0; j < co; ++j) bsum[j] = c0b->v[j] + c1b->v[j];
+  for (int j = 0; j < co; ++j) bsum[j] = t[LSEP_B0][j] + t[LSEP_B1][j];
   return fold_bn("large_sep_feature/batch_normalization", co, 1e-5f, bsum.data(), sc, sh);
 }
 
 int LightHeadNet::build_large_sep() {
-  const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid;
+  const MergedSizes z = merged_sizes();
+  const int mid2 = (int)merged_slots(MG_LSEP, z)[SLOT_KA].W(), co = z.co;
   std::vector<float> ka, ba, kb, sc, sh;
-  XDET_TRY(large_sep_weights(out.C, mid, co, &ka, &ba, &kb, &sc, &sh));
+  XDET_TRY(large_sep_weights(&ka, &ba, &kb, &sc, &sh));
   ConvLayer* LA = keep(new ConvLayer());
-  XDET_TRY(LA->init(15, 1, out.C, 2 * mid, 1, 1, 1, 0, 0, ka.data(), nullptr, ba.data(), 0));
+  XDET_TRY(LA->init(15, 1, out.C, mid2, 1, 1, 1, 0, 0, ka.data(), nullptr, ba.data(), 0));
   Buf t;
   // only the (1,15) conv reads it: planes only
   XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d", ST_LSEP, out, LA, nullptr, 0, &t, ConvEmit{3}));
   ConvLayer* LB = keep(new ConvLayer());
-  XDET_TRY(LB->init(1, 15, 2 * mid, co, 1, 1, 1, 0, 0, kb.data(), sc.data(), sh.data(), 1));
+  XDET_TRY(LB->init(1, 15, mid2, co, 1, 1, 1, 0, 0, kb.data(), sc.data(), sh.data(), 1));
   XDET_TRY(add_conv("large_sep_feature/Branch_0+1/conv2d_1", ST_LSEP, t, LB, nullptr, 0, &feat));
   hd_lsep[0] = LA; hd_lsep[1] = LB;
   return XDET_OK;
@@ -225,11 +201,11 @@ int LightHeadNet::build_large_sep() {
 // real GEMM [N*F, 2*Cin] x [2*Cin, 2*Cout] on the split-precision MFMA kernel (grouped launch), a forward
 // DFT pass in front and an inverse pass (+bias / +BN+ReLU) behind each of the two convolutions
 int LightHeadNet::build_large_sep_spectral() {
-  const int mid = 256, co = cfg.bank * cfg.grid * cfg.grid, F = out.H;
-  const int cin = out.C, mid2 = 2 * mid;
+  const MergedSizes z = merged_sizes();
+  const int co = z.co, F = out.H, cin = z.cin, mid2 = (int)merged_slots(MG_LSEP, z)[SLOT_KA].W();
   // the same branch fusion as the direct form: (15,1) with 2*mid outputs, (1,15) over the stacked channels
   std::vector<float> ka, kb, ba, sc, sh;
-  XDET_TRY(large_sep_weights(cin, mid, co, &ka, &ba, &kb, &sc, &sh));
+  XDET_TRY(large_sep_weights(&ka, &ba, &kb, &sc, &sh));
   // (15,1) + bias along y, then (1,15) + BN + ReLU along x: the layer the C ABI exposes as xdet_spectral_conv_*
   SpectralConv* SA = keep(new SpectralConv());
   SpectralConv* SB = keep(new SpectralConv());
@@ -299,30 +275,20 @@ int LightHeadNet::build_large_sep_spectral() {
 }
 
 int LightHeadNet::build_head() {
-  const int R = cfg.rpn_post_nms_top_n, C = cfg.bank * cfg.grid * cfg.grid, nc = cfg.num_classes;
-  const HostTensor *k0, *b0, *k1, *b1, *k2, *b2;
-  XDET_TRY(need("final_head/subnet_fc/kernel", &k0, {C, 2048}));
-  XDET_TRY(need("final_head/subnet_fc/bias", &b0, {2048}));
-  XDET_TRY(need("final_head/fc_cls/kernel", &k1, {2048, nc}));
-  XDET_TRY(need("final_head/fc_cls/bias", &b1, {nc}));
-  XDET_TRY(need("final_head/fc_loc/kernel", &k2, {2048, 4}));
-  XDET_TRY(need("final_head/fc_loc/bias", &b2, {4}));
+  const MergedSizes z = merged_sizes();
+  const int R = cfg.rpn_post_nms_top_n, C = z.co, nc = z.nc, fw = z.fcw;
+  std::vector<const float*> t;
+  XDET_TRY(need_group(MG_HEAD, {{C, fw}, {fw}, {fw, nc}, {nc}, {fw, 4}, {4}}, &t));
   // ROI rows are the GEMM M dimension: treat [N*R, C] as an NHWC tensor with H = R, W = 1
   XDET_TRY(new_buf(R, 1, C, &pooled));
   if (keep_pool_index) XDET_TRY(alloc_bytes((size_t)max_batch * R * pooled.ld * sizeof(int32_t), reinterpret_cast<void**>(&pool_index)));
   ConvLayer* L0 = keep(new ConvLayer());
-  XDET_TRY(L0->init(1, 1, C, 2048, 1, 1, 0, 0, 0, k0->v.data(), nullptr, b0->v.data(), 1));
+  XDET_TRY(L0->init(1, 1, C, fw, 1, 1, 0, 0, 0, t[HEAD_K0], nullptr, t[HEAD_B0], 1));
   XDET_TRY(add_conv("final_head/subnet_fc", ST_HEAD, pooled, L0, nullptr, 0, &fc, ConvEmit{1}));
-  const int co = nc + 4;
-  std::vector<float> kc((size_t)2048 * co), bc(co);
-  for (int ci = 0; ci < 2048; ++ci) {
-    for (int j = 0; j < nc; ++j) kc[(size_t)ci * co + j] = k1->v[(size_t)ci * nc + j];
-    for (int j = 0; j < 4; ++j) kc[(size_t)ci * co + nc + j] = k2->v[(size_t)ci * 4 + j];
-  }
-  for (int j = 0; j < nc; ++j) bc[j] = b1->v[j];
-  for (int j = 0; j < 4; ++j) bc[nc + j] = b2->v[j];
+  const std::vector<MergedSlot> slots = merged_slots(MG_HEAD, z);
+  const std::vector<float> kc = merged_concat(slots[SLOT_K], t.data()), bc = merged_concat(slots[SLOT_B], t.data());
   ConvLayer* L1 = keep(new ConvLayer());
-  XDET_TRY(L1->init(1, 1, 2048, co, 1, 1, 0, 0, 0, kc.data(), nullptr, bc.data(), 0));
+  XDET_TRY(L1->init(1, 1, fw, (int)slots[SLOT_K].W(), 1, 1, 0, 0, 0, kc.data(), nullptr, bc.data(), 0));
   ConvEmit cls_emit;
   cls_emit.ksplit = latency_ksplit;     // 300 rows x 25 outputs: 3 tiles against 64 K steps
   XDET_TRY(add_conv("final_head/fc_cls+fc_loc", ST_HEAD, fc, L1, nullptr, 0, &cls_reg, cls_emit));
@@ -398,55 +364,61 @@ int LightHeadNet::mid_refresh(int N, hipStream_t s) {
   return launch_relu_copy(mid_x.p, mid_relu, (int64_t)N * mid_x.per_image(), s);
 }
 
+// The name table of a refresh door (xdet_net_refresh_weights, xdet_net_refresh_heads): groups[g] holds a group's label and its
+// tensors' names by role.  -> given[g][role], the table's pointers; given[g] stays empty for a group the table does not name.
+// Refused, in this order: a NULL name, a name outside the reach, a NULL pointer, a name given twice; then, over the groups
+// and roles in order, a group given in part.
+struct NameGroup {
+  std::string label;
+  std::vector<std::string> names;
+};
+static int parse_weight_table(const std::string& door, const char* reach, const std::vector<NameGroup>& groups,
+                              const xdet_net_weight_dev* table, int n, std::vector<std::vector<const float*>>* given) {
+  std::map<std::string, std::pair<int, int>> names;
+  for (size_t g = 0; g < groups.size(); ++g)
+    for (size_t r = 0; r < groups[g].names.size(); ++r) names[groups[g].names[r]] = {(int)g, (int)r};
+  given->assign(groups.size(), {});
+  for (int i = 0; i < n; ++i) {
+    XDET_REQUIRE(table[i].name, door + ": a NULL name");
+    const std::string name(table[i].name);
+    auto it = names.find(name);
+    XDET_REQUIRE(it != names.end(), door + ": " + name + " is outside the reach (" + reach + ")");
+    XDET_REQUIRE(table[i].data, door + ": " + name + " is a NULL pointer");
+    std::vector<const float*>& g = (*given)[it->second.first];
+    g.resize(groups[it->second.first].names.size(), nullptr);
+    XDET_REQUIRE(!g[it->second.second], door + ": " + name + " is given twice");
+    g[it->second.second] = table[i].data;
+  }
+  for (size_t g = 0; g < groups.size(); ++g)
+    for (size_t r = 0; r < (*given)[g].size(); ++r)
+      XDET_REQUIRE((*given)[g][r], door + ": the group of " + groups[g].label + " is given in part: " + groups[g].names[r] + " is missing");
+  return XDET_OK;
+}
+
 // The eval body from trained weights (include/xdet.h): names -> layer_recs, all checks, then the folds, one table repack, one
 // synchronisation, and the host copies the calibration works from.
 int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipStream_t s) {
   XDET_REQUIRE(built, "net_refresh_weights: the net is not built");
   XDET_REQUIRE(table && n > 0, "net_refresh_weights: an empty table");
   enum { R_KERNEL, R_GAMMA, R_BETA, R_MEAN, R_VAR, R_DW, R_N };
-  auto role_name = [](const LayerRec& r, int role) {
-    switch (role) {
-      case R_KERNEL: return r.prefix + (r.dw ? "/pointwise_kernel" : "/kernel");
-      case R_DW: return r.prefix + "/depthwise_kernel";
-      case R_GAMMA: return r.bn + "/gamma";
-      case R_BETA: return r.bn + "/beta";
-      case R_MEAN: return r.bn + "/moving_mean";
-      default: return r.bn + "/moving_variance";
-    }
-  };
-  // the reach: what conv_bn / sep_bn built of blocks 2-14 (block1_* is the stem)
-  std::map<std::string, std::pair<int, int>> names;
+  // the reach: what conv_bn / sep_bn built of blocks 2-14 (block1_* is the stem), a record's tensors by role
   std::vector<int> reach;
+  std::vector<NameGroup> groups;
   for (size_t i = 0; i < layer_recs.size(); ++i) {
     const LayerRec& r = layer_recs[i];
     if (r.bn.empty() || r.prefix.compare(0, 7, "block1_") == 0) continue;
     reach.push_back((int)i);
-    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role) names[role_name(r, role)] = {(int)i, role};
+    groups.push_back({r.prefix, {r.prefix + (r.dw ? "/pointwise_kernel" : "/kernel"), r.bn + "/gamma", r.bn + "/beta", r.bn + "/moving_mean",
+                                 r.bn + "/moving_variance"}});
+    if (r.dw) groups.back().names.push_back(r.prefix + "/depthwise_kernel");
   }
-  std::map<int, std::array<const float*, R_N>> groups;
-  for (int i = 0; i < n; ++i) {
-    XDET_REQUIRE(table[i].name, "net_refresh_weights: a NULL name");
-    const std::string name(table[i].name);
-    auto it = names.find(name);
-    XDET_REQUIRE(it != names.end(), "net_refresh_weights: " + name + " is outside the reach (the variables and moving statistics of the "
-                                    "body's blocks 2-14)");
-    XDET_REQUIRE(table[i].data, "net_refresh_weights: " + name + " is a NULL pointer");
-    auto g = groups.find(it->second.first);
-    if (g == groups.end()) g = groups.emplace(it->second.first, std::array<const float*, R_N>{}).first;
-    XDET_REQUIRE(!g->second[it->second.second], "net_refresh_weights: " + name + " is given twice");
-    g->second[it->second.second] = table[i].data;
-  }
-  for (const auto& g : groups) {
-    const LayerRec& r = layer_recs[g.first];
-    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role)
-      XDET_REQUIRE(g.second[role], "net_refresh_weights: the group of " + r.prefix + " is given in part: " + role_name(r, role) +
-                                   " is missing");
-  }
-  if (!rf_ws) {
+  std::vector<std::vector<const float*>> given;
+  XDET_TRY(parse_weight_table("net_refresh_weights", "the variables and moving statistics of the body's blocks 2-14", groups, table, n, &given));
+  if (!rf.ws) {
     rf_off.assign(layer_recs.size(), 0);
     size_t channels = 0;
     std::vector<xdet_layer_refresh> all;
-    const float* some = groups.begin()->second[R_KERNEL];    // (measuring reads no kernel)
+    const float* some = table[0].data;                       // (measuring reads no kernel)
     for (int i : reach) {
       const LayerRec& r = layer_recs[i];
       rf_off[i] = channels;
@@ -456,23 +428,24 @@ int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipSt
     }
     const size_t bytes = xdet_layers_refresh_workspace_bytes(all.data(), (int)all.size());
     XDET_REQUIRE(bytes > 0, "net_refresh_weights: the plan holds a layer the table door refuses");
-    // one block [table workspace | scales | shifts]: either all of the scratch exists or none of it
-    const size_t ws_bytes = (bytes + 255) / 256 * 256, fold_bytes = (channels * sizeof(float) + 255) / 256 * 256;
+    // one block: either all of the scratch exists or none of it
     void* block = nullptr;
-    XDET_TRY(alloc_bytes(ws_bytes + 2 * fold_bytes, &block, false));
-    rf_scale = reinterpret_cast<float*>(static_cast<char*>(block) + ws_bytes);
-    rf_shift = reinterpret_cast<float*>(static_cast<char*>(block) + ws_bytes + fold_bytes);
-    rf_ws = block;
+    XDET_TRY(alloc_bytes(ws_measure(256, body_refresh_layout, bytes, channels), &block, false));
+    rf = ws_carve(block, 256, body_refresh_layout, bytes, channels);
   }
   std::vector<xdet_layer_refresh> slots;
-  for (const auto& g : groups) {
-    const LayerRec& r = layer_recs[g.first];
-    float *sc = rf_scale + rf_off[g.first], *sh = rf_shift + rf_off[g.first];
-    XDET_TRY(xdet_bn_fold(g.second[R_GAMMA], g.second[R_BETA], g.second[R_MEAN], g.second[R_VAR], nullptr, r.eps, r.conv->cout, sc, sh, s));
-    slots.push_back({r.conv, g.second[R_KERNEL], sc, sh});
-    if (r.dw) slots.push_back({r.dw, g.second[R_DW], nullptr, nullptr});
+  std::vector<size_t> on;                                    // the groups the table names, in the reach's order
+  for (size_t gi = 0; gi < given.size(); ++gi) {
+    const std::vector<const float*>& g = given[gi];
+    if (g.empty()) continue;
+    on.push_back(gi);
+    const LayerRec& r = layer_recs[reach[gi]];
+    float *sc = rf.scale + rf_off[reach[gi]], *sh = rf.shift + rf_off[reach[gi]];
+    XDET_TRY(xdet_bn_fold(g[R_GAMMA], g[R_BETA], g[R_MEAN], g[R_VAR], nullptr, r.eps, r.conv->cout, sc, sh, s));
+    slots.push_back({r.conv, g[R_KERNEL], sc, sh});
+    if (r.dw) slots.push_back({r.dw, g[R_DW], nullptr, nullptr});
   }
-  XDET_TRY(xdet_layers_refresh_device(slots.data(), (int)slots.size(), rf_ws, s));
+  XDET_TRY(xdet_layers_refresh_device(slots.data(), (int)slots.size(), rf.ws, s));
   XDET_HIP(hipStreamSynchronize(s));
   // the host side back in line: the scale at exponent 0 (d_scale carries 2^in_exp, exactly), the taps from the kernel itself
   std::vector<float> k;
@@ -481,22 +454,23 @@ int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipSt
     XDET_HIP(hipMemcpy(k.data(), d, count * sizeof(float), hipMemcpyDeviceToHost));
     return (int)XDET_OK;
   };
-  for (const auto& g : groups) {
-    const LayerRec& r = layer_recs[g.first];
+  for (size_t gi : on) {
+    const std::vector<const float*>& g = given[gi];
+    const LayerRec& r = layer_recs[reach[gi]];
     XDET_TRY(scale_read_back(r.conv));
     if (r.dw) {
       DepthwiseLayer* D = r.dw;
-      XDET_TRY(download(g.second[R_DW], (size_t)9 * D->C));
+      XDET_TRY(download(g[R_DW], (size_t)9 * D->C));
       std::fill(D->taps.host.begin(), D->taps.host.end(), 0.f);
       for (int t = 0; t < 9; ++t)
         for (int c = 0; c < D->C; ++c) D->taps.host[(size_t)t * D->ld + c] = k[(size_t)t * D->C + c];
       D->host_stale = false;
       if (r.pscale >= 0) pscales[r.pscale].bound = depthwise_bound(k.data(), D->C);
     }
-    for (int role = 0; role < (r.dw ? R_N : R_DW); ++role) {      // a host copy the net still holds (none once build() has dropped them)
-      auto hw = w.find(role_name(r, role));
+    for (size_t role = 0; role < g.size(); ++role) {      // a host copy the net still holds (none once build() has dropped them)
+      auto hw = w.find(groups[gi].names[role]);
       if (hw == w.end()) continue;
-      XDET_TRY(download(g.second[role], hw->second.v.size()));
+      XDET_TRY(download(g[role], hw->second.v.size()));
       hw->second.v = k;
     }
   }
@@ -520,129 +494,82 @@ int LightHeadNet::scale_read_back(ConvLayer* L) {
 int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStream_t s) {
   XDET_REQUIRE(built, "net_refresh_heads: the net is not built");
   XDET_REQUIRE(table && n > 0, "net_refresh_heads: an empty table");
-  enum { G_RPN, G_HEAD, G_LSEP, G_N };
-  static const char* const group_name[G_N] = {"rpn_head", "final_head", "large_sep_feature"};
-  std::vector<std::string> roles[G_N];
-  for (const char* l : {"conv2d", "conv2d_1", "conv2d_2"})
-    for (const char* v : {"/kernel", "/bias"}) roles[G_RPN].push_back(std::string("rpn_head/") + l + v);
-  for (const char* l : {"subnet_fc", "fc_cls", "fc_loc"})
-    for (const char* v : {"/kernel", "/bias"}) roles[G_HEAD].push_back(std::string("final_head/") + l + v);
-  for (const char* br : {"Branch_0", "Branch_1"})
-    for (const char* l : {"/conv2d", "/conv2d_1"})
-      for (const char* v : {"/kernel", "/bias"}) roles[G_LSEP].push_back(std::string("large_sep_feature/") + br + l + v);
-  for (const char* v : {"gamma", "beta", "moving_mean", "moving_variance"})
-    roles[G_LSEP].push_back(std::string("large_sep_feature/batch_normalization/") + v);
-  std::map<std::string, std::pair<int, int>> names;
-  for (int g = 0; g < G_N; ++g)
-    for (size_t r = 0; r < roles[g].size(); ++r) names[roles[g][r]] = {g, (int)r};
-  std::vector<const float*> given[G_N];
-  bool on[G_N] = {false, false, false};
-  for (int g = 0; g < G_N; ++g) given[g].assign(roles[g].size(), nullptr);
-  for (int i = 0; i < n; ++i) {
-    XDET_REQUIRE(table[i].name, "net_refresh_heads: a NULL name");
-    const std::string name(table[i].name);
-    auto it = names.find(name);
-    XDET_REQUIRE(it != names.end(), "net_refresh_heads: " + name + " is outside the reach (the rpn_head, final_head and "
-                                    "large_sep_feature groups; the body's blocks 2-14 are xdet_net_refresh_weights')");
-    XDET_REQUIRE(table[i].data, "net_refresh_heads: " + name + " is a NULL pointer");
-    const float*& slot = given[it->second.first][it->second.second];
-    XDET_REQUIRE(!slot, "net_refresh_heads: " + name + " is given twice");
-    slot = table[i].data;
-    on[it->second.first] = true;
-  }
-  for (int g = 0; g < G_N; ++g) {
-    if (!on[g]) continue;
-    for (size_t r = 0; r < roles[g].size(); ++r)
-      XDET_REQUIRE(given[g][r], std::string("net_refresh_heads: the group of ") + group_name[g] + " is given in part: " + roles[g][r] +
-                                " is missing");
-  }
-  XDET_REQUIRE(!on[G_LSEP] || !large_sep_spectral,
+  std::vector<NameGroup> groups;
+  for (int g = 0; g < MG_N; ++g) groups.push_back({merged_group_name(g), merged_roles(g)});
+  std::vector<std::vector<const float*>> given;
+  XDET_TRY(parse_weight_table("net_refresh_heads", "the rpn_head, final_head and large_sep_feature groups; the body's blocks 2-14 are "
+                              "xdet_net_refresh_weights'", groups, table, n, &given));
+  bool on[MG_N];
+  for (int g = 0; g < MG_N; ++g) on[g] = !given[g].empty();
+  XDET_REQUIRE(!on[MG_LSEP] || !large_sep_spectral,
                "net_refresh_heads: the large_sep_feature group needs a net whose block is in the direct form (option large_sep=direct): "
                "this net's is in the spectral form, which keeps the kernels as DFT-domain block matrices");
-  XDET_REQUIRE((!on[G_RPN] || (hd_rpn[0] && hd_rpn[1])) && (!on[G_HEAD] || (hd_head[0] && hd_head[1])) &&
-               (!on[G_LSEP] || (hd_lsep[0] && hd_lsep[1])), "net_refresh_heads: the plan holds no such layers");
-  const int A = cfg.num_anchors, nc = cfg.num_classes, mid = 256, co = cfg.bank * cfg.grid * cfg.grid, cin = out.C;
-  const int hid = hd_rpn[0]->cout, fcw = hd_head[0]->cout;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  ConvLayer* const* hd[MG_N] = {hd_rpn, hd_head, hd_lsep};
+  for (int g = 0; g < MG_N; ++g) XDET_REQUIRE(!on[g] || (hd[g][0] && hd[g][1]), "net_refresh_heads: the plan holds no such layers");
+  const MergedSizes z = merged_sizes();
   float* some = reinterpret_cast<float*>(this);              // (measuring reads no tensor)
-  // the concat slots of a group, from the table's arrays (measuring: from `some`) into the scratch
-  auto pack_slots = [&](int g, const std::vector<const float*>& src, std::vector<xdet_pack_slot>* slots) {
-    auto at = [&](int r) { return const_cast<float*>(src.empty() ? some : src[(size_t)r]); };
-    auto to = [&](float* d) { return src.empty() ? some : d; };
-    if (g == G_RPN) {
-      slots->push_back({to(hs_rpn_k), hid, 2, {at(2), at(4)}, {2 * A, 4 * A}});
-      slots->push_back({to(hs_rpn_b), 1, 2, {at(3), at(5)}, {2 * A, 4 * A}});
-    } else if (g == G_HEAD) {
-      slots->push_back({to(hs_head_k), fcw, 2, {at(2), at(4)}, {nc, 4}});
-      slots->push_back({to(hs_head_b), 1, 2, {at(3), at(5)}, {nc, 4}});
-    } else {
-      slots->push_back({to(hs_ka), 15 * cin, 2, {at(0), at(4)}, {mid, mid}});
-      slots->push_back({to(hs_ba), 1, 2, {at(1), at(5)}, {mid, mid}});
-      slots->push_back({to(hs_kb), 15, 2, {at(2), at(6)}, {mid * co, mid * co}});
+  // a group's xdet_pack_slots by merged_layers.h: from the table's arrays into the scratch (measuring: `some` for both)
+  auto pack_slots = [&](int g, bool measure, std::vector<xdet_pack_slot>* slots) {
+    float* const dst[MG_N][3] = {{hs.rpn[0], hs.rpn[1]}, {hs.head[0], hs.head[1]}, {hs_k.k_a, hs.b_a, hs_k.k_b}};
+    const std::vector<MergedSlot> ms = merged_slots(g, z);
+    for (size_t i = 0; i < ms.size(); ++i) {
+      xdet_pack_slot p = {measure ? some : dst[g][i], ms[i].outer, 2, {}, {}};
+      for (int k = 0; k < 2; ++k) {
+        p.part[k] = measure ? some : const_cast<float*>(given[g][(size_t)ms[i].role[k]]);
+        p.width[k] = ms[i].width[k];
+      }
+      slots->push_back(p);
     }
   };
-  if (!hs_block) {
-    // one block [pack workspace | repack workspace | rpn k, b | head k, b | b_a, b0 + b1, scale, shift]: either all of it
-    // exists or none; the large-separable block's two merged kernels are a second block, at the first call that names them
+  if (!hs.pack_ws) {
+    // one block: either all of it exists or none; the large-separable block's two merged kernels are a second block, at the
+    // first call that names them
     std::vector<xdet_pack_slot> slots;
-    for (int g = 0; g < G_N; ++g)
-      if (g != G_LSEP || !large_sep_spectral) pack_slots(g, {}, &slots);
+    for (int g = 0; g < MG_N; ++g)
+      if (g != MG_LSEP || !large_sep_spectral) pack_slots(g, true, &slots);
     const size_t pack_bytes = xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size());
     std::vector<xdet_layer_refresh> all;
     for (ConvLayer* L : {hd_rpn[0], hd_rpn[1], hd_head[0], hd_head[1], hd_lsep[0], hd_lsep[1]})
       if (L) all.push_back({L, some, nullptr, nullptr});
     const size_t rp_bytes = xdet_layers_refresh_workspace_bytes(all.data(), (int)all.size());
     XDET_REQUIRE(pack_bytes > 0 && rp_bytes > 0, "net_refresh_heads: the plan holds a layer the table door refuses");
-    const size_t sizes[] = {up(pack_bytes), up(rp_bytes), up((size_t)hid * 6 * A * 4), up((size_t)6 * A * 4), up((size_t)fcw * (nc + 4) * 4),
-                            up((size_t)(nc + 4) * 4), up((size_t)2 * mid * 4), up((size_t)co * 4), up((size_t)co * 4), up((size_t)co * 4)};
-    size_t total = 0;
-    for (size_t b : sizes) total += b;
     void* block = nullptr;
-    XDET_TRY(alloc_bytes(total, &block, false));
-    char* p = static_cast<char*>(block);
-    float** dst[] = {nullptr, nullptr, &hs_rpn_k, &hs_rpn_b, &hs_head_k, &hs_head_b, &hs_ba, &hs_bsum, &hs_scale, &hs_shift};
-    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-      if (i == 0) hs_pack_ws = p;
-      else if (i == 1) hs_repack_ws = p;
-      else *dst[i] = reinterpret_cast<float*>(p);
-      p += sizes[i];
-    }
-    hs_block = block;
+    XDET_TRY(alloc_bytes(ws_measure(256, heads_refresh_layout, pack_bytes, rp_bytes, z), &block, false));
+    hs = ws_carve(block, 256, heads_refresh_layout, pack_bytes, rp_bytes, z);
   }
-  if (on[G_LSEP] && !hs_ka) {
-    const size_t ka_bytes = up((size_t)15 * cin * 2 * mid * 4), kb_bytes = up((size_t)15 * 2 * mid * co * 4);
+  if (on[MG_LSEP] && !hs_k.k_a) {
     void* block = nullptr;
-    XDET_TRY(alloc_bytes(ka_bytes + kb_bytes, &block, false));
-    hs_ka = static_cast<float*>(block);
-    hs_kb = reinterpret_cast<float*>(static_cast<char*>(block) + ka_bytes);
+    XDET_TRY(alloc_bytes(ws_measure(256, large_sep_kernel_layout, z), &block, false));
+    hs_k = ws_carve(block, 256, large_sep_kernel_layout, z);
   }
   std::vector<xdet_pack_slot> slots;
   std::vector<xdet_layer_refresh> layers;
-  for (int g = 0; g < G_N; ++g)
-    if (on[g]) pack_slots(g, given[g], &slots);
-  if (on[G_RPN]) {
-    layers.push_back({hd_rpn[0], given[G_RPN][0], nullptr, given[G_RPN][1]});
-    layers.push_back({hd_rpn[1], hs_rpn_k, nullptr, hs_rpn_b});
+  for (int g = 0; g < MG_N; ++g)
+    if (on[g]) pack_slots(g, false, &slots);
+  if (on[MG_RPN]) {
+    layers.push_back({hd_rpn[0], given[MG_RPN][HEAD_K0], nullptr, given[MG_RPN][HEAD_B0]});
+    layers.push_back({hd_rpn[1], hs.rpn[SLOT_K], nullptr, hs.rpn[SLOT_B]});
   }
-  if (on[G_HEAD]) {
-    layers.push_back({hd_head[0], given[G_HEAD][0], nullptr, given[G_HEAD][1]});
-    layers.push_back({hd_head[1], hs_head_k, nullptr, hs_head_b});
+  if (on[MG_HEAD]) {
+    layers.push_back({hd_head[0], given[MG_HEAD][HEAD_K0], nullptr, given[MG_HEAD][HEAD_B0]});
+    layers.push_back({hd_head[1], hs.head[SLOT_K], nullptr, hs.head[SLOT_B]});
   }
-  if (on[G_LSEP]) {
-    layers.push_back({hd_lsep[0], hs_ka, nullptr, hs_ba});
-    layers.push_back({hd_lsep[1], hs_kb, hs_scale, hs_shift});
+  if (on[MG_LSEP]) {
+    layers.push_back({hd_lsep[0], hs_k.k_a, nullptr, hs.b_a});
+    layers.push_back({hd_lsep[1], hs_k.k_b, hs.scale, hs.shift});
   }
   // every refusal the two table doors have is met here, ahead of the first launch: no layer is touched by a refused call
   XDET_REQUIRE(xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size()) > 0 &&
                xdet_layers_refresh_workspace_bytes(layers.data(), (int)layers.size()) > 0,
                "net_refresh_heads: the plan holds a layer the table door refuses");
-  XDET_TRY(xdet_tensors_concat(slots.data(), (int)slots.size(), hs_pack_ws, s));
-  if (on[G_LSEP]) {
-    const std::vector<const float*>& g = given[G_LSEP];
-    XDET_TRY(xdet_add_rows(g[3], co, g[7], co, hs_bsum, co, 1, co, s));
-    XDET_TRY(xdet_bn_fold(g[8], g[9], g[10], g[11], hs_bsum, 1e-5f, co, hs_scale, hs_shift, s));
+  XDET_TRY(xdet_tensors_concat(slots.data(), (int)slots.size(), hs.pack_ws, s));
+  if (on[MG_LSEP]) {
+    const std::vector<const float*>& g = given[MG_LSEP];
+    const int co = z.co;
+    XDET_TRY(xdet_add_rows(g[LSEP_B0], co, g[LSEP_B1], co, hs.b_sum, co, 1, co, s));
+    XDET_TRY(xdet_bn_fold(g[LSEP_GAMMA], g[LSEP_BETA], g[LSEP_MEAN], g[LSEP_VAR], hs.b_sum, 1e-5f, co, hs.scale, hs.shift, s));
   }
-  XDET_TRY(xdet_layers_refresh_device(layers.data(), (int)layers.size(), hs_repack_ws, s));
+  XDET_TRY(xdet_layers_refresh_device(layers.data(), (int)layers.size(), hs.repack_ws, s));
   XDET_HIP(hipStreamSynchronize(s));
   for (const xdet_layer_refresh& l : layers) XDET_TRY(scale_read_back(static_cast<ConvLayer*>(l.layer)));
   return XDET_OK;

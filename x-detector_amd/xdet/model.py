@@ -77,19 +77,15 @@ class LightHeadDetector(object):
         h = c_void_p()
         check(lib().xdet_net_create(ctypes.byref(h), ctypes.byref(self.cfg)))
         self.handle = h
-        self._head_kernels = {}            # the dense layers' kernels as the checkpoint stores them (head_backward)
-        self._rpn_kernels = {}             # ... and the RPN head's three (rpn_backward)
-        self._head_weights, self._rpn_weights = {}, {}     # both heads' kernels and biases (MomentumOptimizer(reach='all')'s masters)
+        # both heads' kernels and biases as the checkpoint stores them: the kernels are what head_backward / rpn_backward make
+        # their operands from, all of them MomentumOptimizer(reach='all')'s masters
+        self._head_weights, self._rpn_weights = {}, {}
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, np.float32)
             if name in _train.HEAD_VARIABLES:
                 self._head_weights[name] = a
             if rpn_hidden and name in _train.RPN_HEAD_VARIABLES:
                 self._rpn_weights[name] = a
-            if name in ('final_head/subnet_fc/kernel', 'final_head/fc_cls/kernel', 'final_head/fc_loc/kernel'):
-                self._head_kernels[name] = a
-            if rpn_hidden and name in ('rpn_head/conv2d/kernel', 'rpn_head/conv2d_1/kernel', 'rpn_head/conv2d_2/kernel'):
-                self._rpn_kernels[name] = a
             dims = (ctypes.c_int64 * a.ndim)(*a.shape)
             check(lib().xdet_net_set_weight(self.handle, name.encode(), _host(a), a.ndim, dims))
         check(lib().xdet_net_set_option(self.handle, b'large_sep', large_sep.encode()))

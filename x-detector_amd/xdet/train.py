@@ -22,7 +22,7 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEA
            'EXIT_FLOW_UNITS', 'EXIT_FLOW_BNS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
            'MIDDLE_FLOW_BLOCKS', 'MIDDLE_FLOW_UNITS', 'MIDDLE_FLOW_VARIABLES', 'MIDDLE_FLOW_MOVING', 'MIDDLE_FLOW_EPS',
            'MIDDLE_FLOW_MOMENTUM', 'ENTRY_FLOW_BLOCKS', 'ENTRY_FLOW_UNITS', 'ENTRY_FLOW_VARIABLES', 'ENTRY_FLOW_MOVING',
-           'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
+           'ENTRY_FLOW_EPS', 'ENTRY_FLOW_MOMENTUM', 'LARGE_SEP_BIAS_SUM', 'merged_layout', 'merged_shapes', 'merge_large_sep', 'split_large_sep_grads', 'head_backward', 'rpn_backward',
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
            'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'optimizer_variables',
@@ -79,28 +79,80 @@ def _entry_relu_in(b, i):
     return not (b == 2 and i == 1)
 
 
+# ---- the merged tensors: how the checkpoint's tensors sit inside the ones the layers and the backwards use ---------------------
+
+_B0, _B1 = 'large_sep_feature/Branch_0/', 'large_sep_feature/Branch_1/'
+# the one relation that is no concatenation: the merged (1,15) conv's bias is b_b = b0 + b1, so both addends get d_bb
+LARGE_SEP_BIAS_SUM = ('b_b', (_B0 + 'conv2d_1/bias', _B1 + 'conv2d_1/bias'))
+
+
+def merged_shapes(group, **sizes):
+    """{variable: its shape in the checkpoint} of a group merged_layout knows, in the group's variable order, from the same sizes"""
+    if group == 'large_sep_feature':
+        cin, mid, co = (int(sizes[k]) for k in ('cin', 'mid', 'co'))
+        return {br + k: shape for br in (_B0, _B1) for k, shape in (('conv2d/kernel', (15, 1, cin, mid)), ('conv2d/bias', (mid,)),
+                                                                  ('conv2d_1/kernel', (1, 15, mid, co)), ('conv2d_1/bias', (co,)))}
+    if group == 'rpn_head':
+        A, cin, hid = (int(sizes[k]) for k in ('A', 'cin', 'hid'))
+        shapes = ((3, 3, cin, hid), (hid,), (1, 1, hid, 2 * A), (2 * A,), (1, 1, hid, 4 * A), (4 * A,))
+        return dict(zip(RPN_HEAD_VARIABLES, shapes))
+    if group == 'final_head':
+        nc, co, fcw = (int(sizes[k]) for k in ('nc', 'co', 'fcw'))
+        return dict(zip(HEAD_VARIABLES, ((co, fcw), (fcw,), (fcw, nc), (nc,), (fcw, 4), (4,))))
+    raise InvalidArgumentError(-1, "merged_layout: group must be 'large_sep_feature', 'rpn_head' or 'final_head', got %r" % (group,))
+
+
+def merged_layout(group, **sizes):
+    """THE statement of the merges (net/xception_body.py:381-400, 450-475, 536-557): the merged tensors of a group as a list of
+    (key, outer, [(variable, width), ...]) -- the vocabulary of host_concat / host_split / concat_device / split_device:
+    merged[o, off_p : off_p + width_p] = variable_p read as [outer, width_p].
+      'large_sep_feature' (cin, mid, co): K_a = Branch_0 | Branch_1 side by side along the (15,1) convs' outputs, b_a their
+        biases, K_b = the (1,15) kernels stacked along the inputs (per tap); with LARGE_SEP_BIAS_SUM that is all eight tensors
+      'rpn_head' (A, cin, hid): K_0, b_0 = the 3x3 conv alone; K_1, b_1 = conv2d_1 | conv2d_2 (2A | 4A)
+      'final_head' (nc, co, fcw): K_0, b_0 = subnet_fc alone; K_1, b_1 = fc_cls | fc_loc (nc | 4)
+    A slot of one part is that variable itself, reshaped.  Every width follows from merged_shapes and the slot's outer."""
+    shapes = merged_shapes(group, **sizes)
+    names = list(shapes)
+    if group == 'large_sep_feature':
+        cin = int(sizes['cin'])
+        slots = [('K_a', 15 * cin, (names[0], names[4])), ('b_a', 1, (names[1], names[5])), ('K_b', 15, (names[2], names[6]))]
+    else:                                              # a layer alone, then two side by side: kernels at outer = their inputs
+        k0, k1 = shapes[names[0]], shapes[names[2]]
+        slots = [('K_0', math.prod(k0[:-1]), names[0:1]), ('b_0', 1, names[1:2]),
+                 ('K_1', math.prod(k1[:-1]), (names[2], names[4])), ('b_1', 1, (names[3], names[5]))]
+    return [(key, outer, [(n, math.prod(shapes[n]) // outer) for n in parts]) for key, outer, parts in slots]
+
+
+def _merge(layout, tensors):
+    """{key: merged [outer, W] array} of a layout from {variable: array}: host_concat per slot"""
+    return {key: train_ops.host_concat([tensors[n] for n, _ in parts], outer) for key, outer, parts in layout}
+
+
+def _unmerge(layout, shapes, merged):
+    """_merge's inverse and adjoint: {variable: array in its checkpoint shape} from {key: merged array}, host_split per slot"""
+    return {n: a.reshape(shapes[n]) for key, outer, parts in layout
+            for (n, _), a in zip(parts, train_ops.host_split(merged[key], outer, [w for _, w in parts]))}
+
+
 def merge_large_sep(weights, dtype=np.float32):
     """The large-separable block's two branches as one conv pair (net/xception_body.py:450-475; the same fusion as the
     native net's, without the BN fold): both (15,1) convs read the same input -> one kernel [15,1,cin,2*mid] with the
     branches side by side along the outputs and the bias [2*mid]; branch_0b + branch_1b -> one (1,15) kernel [1,15,2*mid,co]
     with the branches stacked along the inputs and the bias b0 + b1.  -> (K_a, b_a, K_b, b_b)"""
-    g = lambda br, name: np.asarray(weights['large_sep_feature/%s/%s' % (br, name)], dtype)
-    ka = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d/kernel'), g('Branch_1', 'conv2d/kernel')], axis=3))
-    ba = np.concatenate([g('Branch_0', 'conv2d/bias'), g('Branch_1', 'conv2d/bias')])
-    kb = np.ascontiguousarray(np.concatenate([g('Branch_0', 'conv2d_1/kernel'), g('Branch_1', 'conv2d_1/kernel')], axis=2))
-    return ka, ba, kb, g('Branch_0', 'conv2d_1/bias') + g('Branch_1', 'conv2d_1/bias')
+    w = {k: np.asarray(weights[k], dtype) for k in LARGE_SEP_VARIABLES[:8]}
+    (_, _, cin, mid), co = w[_B0 + 'conv2d/kernel'].shape, w[_B0 + 'conv2d_1/kernel'].shape[3]
+    m = _merge(merged_layout('large_sep_feature', cin=cin, mid=mid, co=co), w)
+    b0, b1 = LARGE_SEP_BIAS_SUM[1]
+    return m['K_a'].reshape(15, 1, cin, -1), m['b_a'].reshape(-1), m['K_b'].reshape(1, 15, -1, co), w[b0] + w[b1]
 
 
 def split_large_sep_grads(d_ka, d_ba, d_kb, d_bb, mid):
     """merge_large_sep's adjoint: the gradients of the merged tensors -> the eight conv gradients under the checkpoint's names
     and in its shapes.  Both conv2d_1 biases enter the block as b0 + b1, so both get d_bb."""
-    out = {}
-    for i, br in enumerate(('Branch_0', 'Branch_1')):
-        p, sl = 'large_sep_feature/%s/' % br, slice(i * mid, (i + 1) * mid)
-        out[p + 'conv2d/kernel'] = np.ascontiguousarray(d_ka[..., sl])
-        out[p + 'conv2d/bias'] = np.ascontiguousarray(d_ba[sl])
-        out[p + 'conv2d_1/kernel'] = np.ascontiguousarray(d_kb[:, :, sl, :])
-        out[p + 'conv2d_1/bias'] = np.array(d_bb)
+    sizes = dict(cin=d_ka.shape[2], mid=mid, co=d_kb.shape[3])
+    out = _unmerge(merged_layout('large_sep_feature', **sizes), merged_shapes('large_sep_feature', **sizes),
+                   {'K_a': d_ka, 'b_a': d_ba, 'K_b': d_kb})
+    out.update({n: np.array(d_bb) for n in LARGE_SEP_BIAS_SUM[1]})
     return out
 
 
@@ -563,31 +615,75 @@ def new_body(d):
 
 # ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
 
-def _head_operands(d):
-    """the w operands of the head's two dense backwards, made once per detector: subnet_fc's kernel and fc_cls | fc_loc side by
-    side as [K,1,1,J] dense device tensors (MomentumOptimizer(reach='all') rebuilds them in place after a step)"""
-    if not hasattr(d, '_head_kernels_dev'):
-        k0 = d._head_kernels['final_head/subnet_fc/kernel']
-        k1 = np.concatenate([d._head_kernels['final_head/fc_cls/kernel'], d._head_kernels['final_head/fc_loc/kernel']], axis=1)
-        d._head_kernels_dev = []
-        for k in (k0, np.ascontiguousarray(k1)):
+def _kernels(weights):
+    return [k for k in weights if k.endswith('/kernel')]
+
+
+def _group_sizes(d, group):
+    """merged_layout's sizes of a group, from the detector's own tensors"""
+    if group == 'rpn_head':
+        _, _, cin, hid = d._rpn_weights['rpn_head/conv2d/kernel'].shape
+        return dict(A=d.cfg.num_anchors, cin=cin, hid=hid)
+    if group == 'final_head':
+        co, fcw = d._head_weights['final_head/subnet_fc/kernel'].shape
+        return dict(nc=d.cfg.num_classes, co=co, fcw=fcw)
+    s = d._lsep
+    return dict(cin=s.K_a.shape[2], mid=s.mid, co=s.K_b.shape[3])
+
+
+def _operands(d, group):
+    """the w operands of the two backwards of a head ('rpn_head', 'final_head'), made once per detector from merged_layout's K
+    slots: the first layer's kernel (the RPN's 3x3 conv keeps its shape) and the two layers behind it side by side, as [K,1,1,J]
+    dense device tensors (MomentumOptimizer(reach='all') rebuilds them in place after a step)"""
+    attr = '_%s_operands' % group
+    if not hasattr(d, attr):
+        weights = d._rpn_weights if group == 'rpn_head' else d._head_weights
+        layout = [slot for slot in merged_layout(group, **_group_sizes(d, group)) if slot[0][0] == 'K']
+        out = []
+        for (_, outer, parts), k in zip(layout, _merge(layout, weights).values()):
+            one = weights[parts[0][0]].shape if len(parts) == 1 else ()
             b = to_device(k)
-            d._head_kernels_dev.append(DeviceTensor(b.ptr, (k.shape[0], 1, 1, k.shape[1]), k.shape[1], owner=b))
-    return d._head_kernels_dev
+            out.append(DeviceTensor(b.ptr, one if len(one) == 4 else (outer, 1, 1, k.shape[1]), k.shape[1], owner=b))
+        setattr(d, attr, tuple(out))
+    return getattr(d, attr)
 
 
-def _rpn_operands(d):
-    """the w operands of the RPN head's backward, made once per detector: the 3x3 kernel, and conv2d_1 | conv2d_2 side by side
-    as a [512,1,1,6A] dense device tensor (MomentumOptimizer(reach='all') rebuilds them in place after a step)"""
-    if not hasattr(d, '_rpn_kernels_dev'):
-        A = d.cfg.num_anchors
-        k0 = d._rpn_kernels['rpn_head/conv2d/kernel']
-        k1 = np.ascontiguousarray(np.concatenate([d._rpn_kernels['rpn_head/conv2d_1/kernel'].reshape(-1, 2 * A),
-                                                  d._rpn_kernels['rpn_head/conv2d_2/kernel'].reshape(-1, 4 * A)], axis=1))
-        b0, b1 = to_device(k0), to_device(k1)
-        d._rpn_kernels_dev = (DeviceTensor(b0.ptr, k0.shape, k0.shape[3], owner=b0),
-                              DeviceTensor(b1.ptr, (k1.shape[0], 1, 1, k1.shape[1]), k1.shape[1], owner=b1))
-    return d._rpn_kernels_dev
+class _WeightGrads(object):
+    """The tail head_backward, rpn_backward and large_sep_backward share: the gradients of a group's merged tensors -> the
+    gradients of its variables under the checkpoint's names and in its shapes, by merged_layout.  Made AHEAD of the launches
+    (weight_grads='device': the per-variable tensors are allocated here); split(merged) behind them and ahead of the sync, with
+    merged = {key: the DeviceBuffer a backward op left} ('device': the one split_device table, 'host': no launch); collect()
+    behind the sync -> {variable: dense DeviceTensor | NumPy array}.  A slot of one part is its variable: no copy."""
+
+    def __init__(self, d, group, weight_grads):
+        sizes = _group_sizes(d, group)
+        self.layout, self.shapes = merged_layout(group, **sizes), merged_shapes(group, **sizes)
+        self.sums = (LARGE_SEP_BIAS_SUM,) if group == 'large_sep_feature' else ()
+        self.dev = None
+        if weight_grads == 'device':
+            split = [n for _, _, parts in self.layout if len(parts) > 1 for n, _ in parts] + [n for _, names in self.sums for n in names]
+            self.dev = _new_grads({n: self.shapes[n] for n in split})
+
+    def split(self, merged, stream):
+        self.merged = merged
+        if self.dev is not None:
+            self.table = [(merged[key], outer, [(self.dev[n], w) for n, w in parts]) for key, outer, parts in self.layout if len(parts) > 1] + \
+                         [(merged[key], 1, [(self.dev[n], math.prod(self.shapes[n]))]) for key, names in self.sums for n in names]
+            train_ops.split_device(self.table, stream=stream)
+
+    def collect(self):
+        merged, ones = self.merged, [(key, parts[0][0]) for key, _, parts in self.layout if len(parts) == 1]
+        if self.dev is not None:
+            out = dict(self.dev)
+            out.update({n: _as_grad(merged[key], self.shapes[n]) for key, n in ones})
+            self.table[0][0]._keep = None                 # (split_device's keep-alive chain: the stream has run)
+            return out
+        host = {key: to_host(merged[key].ptr, (outer, sum(w for _, w in parts))) for key, outer, parts in self.layout}
+        out = _unmerge(self.layout, self.shapes, host)
+        for key, names in self.sums:
+            d_sum = to_host(merged[key].ptr, self.shapes[names[0]])
+            out.update({n: np.array(d_sum) for n in names})
+        return out
 
 
 def head_backward(loss_func, to_feat=False, weight_grads='host'):
@@ -619,36 +715,24 @@ def head_backward(loss_func, to_feat=False, weight_grads='host'):
     if (g.shape[1], g.shape[3]) != (d.R, nc + 4) or n > d.max_batch:
         raise InvalidArgumentError(-1, 'head_backward: gradient of shape %r but the detector has %d ROIs per image, %d classes, '
                                        'max_batch %d' % (g.shape, d.R, nc, d.max_batch))
-    if len(d._head_kernels) != 3:
+    if len(_kernels(d._head_weights)) != 3:
         raise InvalidArgumentError(-1, 'head_backward: the detector was built without the final_head kernels')
     _check_step(d, 'head_backward', loss_func, '_head_step')
-    w0, w1 = _head_operands(d)
+    w0, w1 = _operands(d, 'final_head')
     fc, pooled = d.buffer('fc', n), d.buffer('pooled', n)
     K0, K1 = w0.shape[0], w1.shape[0]
     d_feat = None
     if to_feat:                                    # (allocated ahead of the launches, not between the last two)
         fb = d.buffer('feat', n)
         d_feat = DeviceTensor.empty(fb.shape, ld=fb.ld)
-    p, dev = 'final_head/', None
-    if weight_grads == 'device':
-        dev = _new_grads({p + 'fc_cls/kernel': (K1, nc), p + 'fc_cls/bias': (nc,), p + 'fc_loc/kernel': (K1, 4), p + 'fc_loc/bias': (4,)})
+    wg = _WeightGrads(d, 'final_head', weight_grads)
     dx1, dw1, db1 = train_ops.dense_backward_device(fc, w1, g, None, stream=d.stream)
     dx0, dw0, db0 = train_ops.dense_backward_device(pooled, w0, dx1, fc, stream=d.stream)
     if to_feat:
         check(lib().xdet_net_head_pool_backward(d.handle, n, dx0.ptr, dx0.ld, d_feat.ptr, d.stream.handle))
-    if dev is not None:
-        train_ops.split_device([(dw1, K1, [(dev[p + 'fc_cls/kernel'], nc), (dev[p + 'fc_loc/kernel'], 4)]),
-                                (db1, 1, [(dev[p + 'fc_cls/bias'], nc), (dev[p + 'fc_loc/bias'], 4)])], stream=d.stream)
+    wg.split({'K_0': dw0, 'b_0': db0, 'K_1': dw1, 'b_1': db1}, d.stream)
     _sync(d)
-    if dev is not None:
-        out = dict(dev)
-        out[p + 'subnet_fc/kernel'], out[p + 'subnet_fc/bias'] = _as_grad(dw0, (K0, K1)), _as_grad(db0, (K1,))
-        dw1._keep = None
-    else:
-        kw1, kb1 = to_host(dw1.ptr, (K1, nc + 4)), to_host(db1.ptr, (nc + 4,))
-        out = {'final_head/subnet_fc/kernel': to_host(dw0.ptr, (K0, K1)), 'final_head/subnet_fc/bias': to_host(db0.ptr, (K1,)),
-               'final_head/fc_cls/kernel': np.ascontiguousarray(kw1[:, :nc]), 'final_head/fc_cls/bias': kb1[:nc].copy(),
-               'final_head/fc_loc/kernel': np.ascontiguousarray(kw1[:, nc:]), 'final_head/fc_loc/bias': kb1[nc:].copy()}
+    out = wg.collect()
     out.update({'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
                 'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)})
     if to_feat:
@@ -679,7 +763,7 @@ def rpn_backward(rpn_loss_result, weight_grads='host'):
     if g is None:
         raise InvalidArgumentError(-1, 'rpn_backward: the loss left no gradient on the device (call losses.rpn_loss(..., '
                                        'keep_device=True) on the tensors get_rpn returned)')
-    if len(d._rpn_kernels) != 3:
+    if len(_kernels(d._rpn_weights)) != 3:
         raise InvalidArgumentError(-1, 'rpn_backward: the detector was built without the rpn_head kernels')
     n, A = g.shape[0], d.cfg.num_anchors
     out_view = d.buffer('rpn_out', min(max(n, 1), d.max_batch))
@@ -687,30 +771,15 @@ def rpn_backward(rpn_loss_result, weight_grads='host'):
         raise InvalidArgumentError(-1, 'rpn_backward: gradient of shape %r (ld %d) but the detector\'s rpn_out is %r (ld %d), '
                                        'max_batch %d' % (g.shape, g.ld, tuple(out_view.shape[1:]), out_view.ld, d.max_batch))
     _check_step(d, 'rpn_backward', rpn_loss_result, '_rpn_step')
-    w0, w1 = _rpn_operands(d)
+    w0, w1 = _operands(d, 'rpn_head')
     hid, mid_x = d.buffer('rpn_hidden', n), d.buffer('mid_x', n)
-    J, p, dev = w0.shape[3], 'rpn_head/', None
-    if weight_grads == 'device':
-        dev = _new_grads({p + 'conv2d_1/kernel': (1, 1, J, 2 * A), p + 'conv2d_1/bias': (2 * A,),
-                          p + 'conv2d_2/kernel': (1, 1, J, 4 * A), p + 'conv2d_2/bias': (4 * A,)})
+    wg = _WeightGrads(d, 'rpn_head', weight_grads)
     dx1, dw1, db1 = train_ops.dense_backward_device(hid, w1, g, None, stream=d.stream)
     d_hid = DeviceTensor(dx1.ptr, hid.shape, dx1.ld, owner=dx1)
     dx0, dw0, db0 = train_ops.conv_backward_device(mid_x, w0, d_hid, hid, relu_in=True, stream=d.stream)
-    if dev is not None:
-        train_ops.split_device([(dw1, J, [(dev[p + 'conv2d_1/kernel'], 2 * A), (dev[p + 'conv2d_2/kernel'], 4 * A)]),
-                                (db1, 1, [(dev[p + 'conv2d_1/bias'], 2 * A), (dev[p + 'conv2d_2/bias'], 4 * A)])], stream=d.stream)
+    wg.split({'K_0': dw0, 'b_0': db0, 'K_1': dw1, 'b_1': db1}, d.stream)
     _sync(d)
-    if dev is not None:
-        out = dict(dev)
-        out[p + 'conv2d/kernel'], out[p + 'conv2d/bias'] = _as_grad(dw0, w0.shape), _as_grad(db0, (J,))
-        dw1._keep = None
-    else:
-        kw1, kb1 = to_host(dw1.ptr, (J, 6 * A)), to_host(db1.ptr, (6 * A,))
-        out = {'rpn_head/conv2d/kernel': to_host(dw0.ptr, w0.shape), 'rpn_head/conv2d/bias': to_host(db0.ptr, (J,)),
-               'rpn_head/conv2d_1/kernel': np.ascontiguousarray(kw1[:, :2 * A]).reshape(1, 1, J, 2 * A),
-               'rpn_head/conv2d_1/bias': kb1[:2 * A].copy(),
-               'rpn_head/conv2d_2/kernel': np.ascontiguousarray(kw1[:, 2 * A:]).reshape(1, 1, J, 4 * A),
-               'rpn_head/conv2d_2/bias': kb1[2 * A:].copy()}
+    out = wg.collect()
     out.update({'mid': dx0, 'rpn_hidden': d_hid})
     return out
 
@@ -737,28 +806,15 @@ def large_sep_backward(d_feat, weight_grads='host'):
     s, n = _stage(d, LARGE_SEP, 'large_sep_backward', 'large_sep_kernel(..., is_training=True)')
     feat, out = d.buffer('feat', n), d.buffer('out', n)
     _check_grad('large_sep_backward', 'd_feat', d_feat, feat)
-    co, mid2, mid, cin = s.K_b.shape[3], s.K_a.shape[3], s.mid, s.K_a.shape[2]
-    b0, b1, dev = 'large_sep_feature/Branch_0/', 'large_sep_feature/Branch_1/', None
-    if weight_grads == 'device':
-        dev = _new_grads({br + k: shape for br in (b0, b1) for k, shape in (('conv2d/kernel', (15, 1, cin, mid)), ('conv2d/bias', (mid,)),
-                                                                           ('conv2d_1/kernel', (1, 15, mid, co)), ('conv2d_1/bias', (co,)))})
+    co = s.K_b.shape[3]
+    wg = _WeightGrads(d, 'large_sep_feature', weight_grads)
     dz, dgamma, dbeta = s.bn.backward(d, _first(s.z, n), feat, d_feat)
     dt, dkb, dbb = train_ops.conv_backward_device(_first(s.t, n), s.K_b, dz, None, stream=d.stream)
     d_out, dka, dba = train_ops.conv_backward_device(out, s.K_a, dt, None, stream=d.stream)
-    if dev is not None:
-        train_ops.split_device([(dka, 15 * cin, [(dev[b0 + 'conv2d/kernel'], mid), (dev[b1 + 'conv2d/kernel'], mid)]),
-                                (dba, 1, [(dev[b0 + 'conv2d/bias'], mid), (dev[b1 + 'conv2d/bias'], mid)]),
-                                (dkb, 15, [(dev[b0 + 'conv2d_1/kernel'], mid * co), (dev[b1 + 'conv2d_1/kernel'], mid * co)]),
-                                (dbb, 1, [(dev[b0 + 'conv2d_1/bias'], co)]), (dbb, 1, [(dev[b1 + 'conv2d_1/bias'], co)])], stream=d.stream)
+    wg.split({'K_a': dka, 'b_a': dba, 'K_b': dkb, 'b_b': dbb}, d.stream)
     _sync(d)
-    if dev is not None:
-        grads = dict(dev)
-        grads[s.bn.name + '/gamma'], grads[s.bn.name + '/beta'] = _as_grad(dgamma, (co,)), _as_grad(dbeta, (co,))
-        dka._keep = None
-    else:
-        grads = split_large_sep_grads(to_host(dka.ptr, s.K_a.shape), to_host(dba.ptr, (mid2,)), to_host(dkb.ptr, s.K_b.shape),
-                                      to_host(dbb.ptr, (co,)), s.mid)
-        _download({s.bn.name + '/gamma': (dgamma, (co,)), s.bn.name + '/beta': (dbeta, (co,))}, grads)
+    grads = wg.collect()
+    _deliver({s.bn.name + '/gamma': (dgamma, (co,)), s.bn.name + '/beta': (dbeta, (co,))}, grads, weight_grads)
     grads['out'], grads['z'], grads['t'] = d_out, dz, dt
     return grads
 
@@ -1172,19 +1228,15 @@ class MomentumOptimizer(object):
             m[v] = DeviceTensor(b.ptr, a.shape, a.shape[-1], owner=b)
             masters[v] = (m[v], a.shape)
         masters[s.bn.name + '/gamma'], masters[s.bn.name + '/beta'] = (s.bn.gamma, (s.bn.co,)), (s.bn.beta, (s.bn.co,))
-        cin, mid2, co, mid = s.K_a.shape[2], s.K_a.shape[3], s.K_b.shape[3], s.mid
+        mid2, co = s.K_a.shape[3], s.K_b.shape[3]
         s.b_a, s.b_b = DeviceBuffer(4 * mid2), DeviceBuffer(4 * co)
-        (r0, r1), (h0, h1) = _rpn_operands(d), _head_operands(d)
-        A, nc, J, K0, K1 = d.cfg.num_anchors, d.cfg.num_classes, r0.shape[3], h0.shape[0], h1.shape[0]
-        b0, b1 = 'large_sep_feature/Branch_0/', 'large_sep_feature/Branch_1/'
-        self._bias_sum = (m[b0 + 'conv2d_1/bias'], m[b1 + 'conv2d_1/bias'], s.b_b, co)
-        self._concat = [(s.K_a, 15 * cin, [(m[b0 + 'conv2d/kernel'], mid), (m[b1 + 'conv2d/kernel'], mid)]),
-                        (s.K_b, 15, [(m[b0 + 'conv2d_1/kernel'], mid * co), (m[b1 + 'conv2d_1/kernel'], mid * co)]),
-                        (s.b_a, 1, [(m[b0 + 'conv2d/bias'], mid), (m[b1 + 'conv2d/bias'], mid)]),
-                        (r0, 9 * r0.shape[2], [(m['rpn_head/conv2d/kernel'], J)]),
-                        (r1, J, [(m['rpn_head/conv2d_1/kernel'], 2 * A), (m['rpn_head/conv2d_2/kernel'], 4 * A)]),
-                        (h0, K0, [(m['final_head/subnet_fc/kernel'], K1)]),
-                        (h1, K1, [(m['final_head/fc_cls/kernel'], nc), (m['final_head/fc_loc/kernel'], 4)])]
+        (r0, r1), (h0, h1) = _operands(d, 'rpn_head'), _operands(d, 'final_head')
+        self._bias_sum = tuple(m[v] for v in LARGE_SEP_BIAS_SUM[1]) + (s.b_b, co)
+        # merged_layout's slots that have a merged tensor here (the heads' biases are merged by the net itself, refresh_heads)
+        merged = {'large_sep_feature': {'K_a': s.K_a, 'b_a': s.b_a, 'K_b': s.K_b}, 'rpn_head': {'K_0': r0, 'K_1': r1},
+                  'final_head': {'K_0': h0, 'K_1': h1}}
+        self._concat = [(to[key], outer, [(m[v], w) for v, w in parts]) for group, to in merged.items()
+                        for key, outer, parts in merged_layout(group, **_group_sizes(d, group)) if key in to]
         table, _ = train_ops._pack_table(self._concat, 'tensors_concat')
         self._concat_ws = DeviceBuffer(lib().xdet_tensors_concat_workspace_bytes(table, len(table)))
         self._head_names = RPN_HEAD_VARIABLES + HEAD_VARIABLES

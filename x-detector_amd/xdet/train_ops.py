@@ -699,19 +699,18 @@ def host_momentum_step(var, grad, accum, lr, momentum=0.9, weight_decay=0.0, dec
     return var - dtype(lr) * accum, accum
 
 
-def _momentum_array(a, n, what):
-    """one of a slot's three arrays: a DeviceBuffer of at least n floats or a dense DeviceTensor of n elements -> pointer"""
+def _device_array(a, n, who, what, null=True):
+    """one array of a table door named `who`: a dense DeviceTensor of n elements or a DeviceBuffer of at least n floats -> pointer
+    (null=False: the door itself names a NULL pointer)"""
     if isinstance(a, DeviceTensor):
         if a.ld != a.shape[-1] or math.prod(a.shape) != n:
-            raise InvalidArgumentError(-1, 'momentum_step: %s must be dense and hold %d elements, got shape %r with ld %d'
-                                       % (what, n, a.shape, a.ld))
+            raise InvalidArgumentError(-1, '%s: %s must be dense and hold %d elements, got shape %r with ld %d' % (who, what, n, a.shape, a.ld))
     elif not isinstance(a, DeviceBuffer):
-        raise InvalidArgumentError(-1, 'momentum_step: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
-                                   % (what, type(a).__name__))
+        raise InvalidArgumentError(-1, '%s: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s' % (who, what, type(a).__name__))
     elif a.nbytes < 4 * n:
-        raise InvalidArgumentError(-1, 'momentum_step: %s holds %d bytes, %d elements need %d' % (what, a.nbytes, n, 4 * n))
-    if not a.ptr:
-        raise InvalidArgumentError(-1, 'momentum_step: %s is a NULL pointer' % what)
+        raise InvalidArgumentError(-1, '%s: %s holds %d bytes, %d elements need %d' % (who, what, a.nbytes, n, 4 * n))
+    if null and not a.ptr:
+        raise InvalidArgumentError(-1, '%s: %s is a NULL pointer' % (who, what))
     return a.ptr
 
 
@@ -731,7 +730,7 @@ def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, st
         var, grad, accum, n, decay = slot
         n = int(n)
         _check_sizes((n,), (1,), 'momentum_step: slot %d holds n = %d elements (positive, below 2^31)', (i, n), widest=None)
-        ptrs = [_momentum_array(a, n, 'slot %d\'s %s' % (i, what)) for a, what in ((var, 'var'), (grad, 'grad'), (accum, 'accum'))]
+        ptrs = [_device_array(a, n, 'momentum_step', 'slot %d\'s %s' % (i, what)) for a, what in ((var, 'var'), (grad, 'grad'), (accum, 'accum'))]
         table[i] = MomentumSlot(ptrs[0], ptrs[1], ptrs[2], n, 1 if decay else 0)
     need = lib().xdet_momentum_step_workspace_bytes(table, len(slots))
     if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
@@ -777,20 +776,6 @@ def bn_fold_device(gamma, beta, moving_mean, moving_variance, eps, bias=None, C=
     return sc, sh
 
 
-def _refresh_array(a, n, what):
-    """a slot's kernel, scale or shift: a dense DeviceTensor of n elements or a DeviceBuffer of at least n floats -> pointer"""
-    if isinstance(a, DeviceTensor):
-        if a.ld != a.shape[-1] or math.prod(a.shape) != n:
-            raise InvalidArgumentError(-1, 'refresh_layers: %s must be dense and hold %d elements, got shape %r with ld %d'
-                                       % (what, n, a.shape, a.ld))
-    elif not isinstance(a, DeviceBuffer):
-        raise InvalidArgumentError(-1, 'refresh_layers: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
-                                   % (what, type(a).__name__))
-    elif a.nbytes < 4 * n:
-        raise InvalidArgumentError(-1, 'refresh_layers: %s holds %d bytes, %d elements need %d' % (what, a.nbytes, n, 4 * n))
-    return a.ptr
-
-
 def refresh_layers_table(slots):
     """the argument checks of refresh_layers_device, without touching the GPU -> (the xdet_layer_refresh table, the objects it
     points to): what a caller sizes a workspace from (xdet_layers_refresh_workspace_bytes) ahead of the calls"""
@@ -814,7 +799,7 @@ def refresh_layers_table(slots):
         else:
             raise InvalidArgumentError(-1, 'refresh_layers: slot %d\'s layer must be a Conv2D or a DepthwiseConv2D (a layer object of xdet.ops), got %s'
                                        % (i, type(layer).__name__))
-        ptrs = [_refresh_array(a, m, 'slot %d\'s %s' % (i, what)) if a is not None else None
+        ptrs = [_device_array(a, m, 'refresh_layers', 'slot %d\'s %s' % (i, what), null=False) if a is not None else None
                 for a, m, what in ((kernel, n, 'kernel'), (scale, co, 'scale'), (shift, co, 'shift'))]
         if not ptrs[0]:
             raise InvalidArgumentError(-1, 'refresh_layers: slot %d has no kernel' % i)
@@ -870,20 +855,6 @@ def host_split(merged, outer, widths):
     return [np.ascontiguousarray(m[:, a:b]) for a, b in zip(offs[:-1], offs[1:])]
 
 
-def _pack_array(a, n, who, what):
-    """one tensor of a pack slot: a dense DeviceTensor of n elements or a DeviceBuffer of at least n floats -> pointer"""
-    if isinstance(a, DeviceTensor):
-        if a.ld != a.shape[-1] or math.prod(a.shape) != n:
-            raise InvalidArgumentError(-1, '%s: %s must be dense and hold %d elements, got shape %r with ld %d' % (who, what, n, a.shape, a.ld))
-    elif not isinstance(a, DeviceBuffer):
-        raise InvalidArgumentError(-1, '%s: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s' % (who, what, type(a).__name__))
-    elif a.nbytes < 4 * n:
-        raise InvalidArgumentError(-1, '%s: %s holds %d bytes, %d elements need %d' % (who, what, a.nbytes, n, 4 * n))
-    if not a.ptr:
-        raise InvalidArgumentError(-1, '%s: %s is a NULL pointer' % (who, what))
-    return a.ptr
-
-
 def _pack_table(slots, who):
     """the argument checks of concat_device / split_device, without touching the GPU -> (the xdet_pack_slot table, the arrays it
     points to)"""
@@ -905,9 +876,9 @@ def _pack_table(slots, who):
             raise InvalidArgumentError(-1, '%s: slot %d has widths %r at outer = %d (positive, outer * their sum below 2^31)'
                                        % (who, i, widths, outer))
         s = PackSlot()
-        s.merged, s.outer, s.n_parts = _pack_array(merged, int(outer) * sum(widths), who, 'slot %d\'s merged tensor' % i), int(outer), len(parts)
+        s.merged, s.outer, s.n_parts = _device_array(merged, int(outer) * sum(widths), who, 'slot %d\'s merged tensor' % i), int(outer), len(parts)
         for p, (a, w) in enumerate(parts):
-            s.part[p], s.width[p] = _pack_array(a, int(outer) * int(w), who, 'slot %d\'s part %d' % (i, p)), int(w)
+            s.part[p], s.width[p] = _device_array(a, int(outer) * int(w), who, 'slot %d\'s part %d' % (i, p)), int(w)
         table[i] = s
         arrays += [merged] + [a for a, _ in parts]
     return table, arrays
