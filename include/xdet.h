@@ -277,6 +277,14 @@ int xdet_spectral_conv_forward(void* layer, const float* in, int N, int ld_in, v
  * hold ceil(N*Ho*Ho / 16) * 16 * 32 halves each; pixels past N*Ho*Ho of the last group are not written. */
 int xdet_stem_conv3x3s2_forward(const float* in_nchw, const float* w27x32, const float* scale, const float* shift,
                                 uint16_t* out_hi, uint16_t* out_lo, int N, int S, void* stream);
+/* block1_conv1 in training mode (csrc/stem_train.hip): the same geometry from the same NCHW input, but the raw f32 conv output
+ * z [N][Ho][Ho][ld_z] (channels 32 .. ld_z - 1 of a pixel are not written) that the training-mode batch norm takes its
+ * statistics from -- no BN, no ReLU, no split.  w (device): [3][3][3][32], the checkpoint's own layout, read in place: an
+ * optimizer's master needs no repack.  Arithmetic: per output element one f32 accumulator from 0, the 27 products added by
+ * fmaf in (ky, kx, ci) order, which is xdet_stem_conv3x3s2_forward's accumulation in front of its scale and shift.  With an
+ * even S the image's last row and column lie under no window and are never read.  An image's result does not depend on the
+ * batch it arrives in.  XDET_ERR_INVALID_ARG ahead of any launch: a NULL argument, N < 1, S < 3, ld_z < 32, N * S * S >= 2^31. */
+int xdet_stem_conv3x3s2_train_forward(const float* in_nchw, const float* w, int N, int S, float* z, int ld_z, void* stream);
 /* conv2d_fixed_padding(7 x 7, 64 filters, stride 2) of the ResNet v2 stem (net/resnet_v2.py:311-320) from the NCHW input
  * [N][3][S][S] with the input patch staged in LDS (csrc/resnet_stem.hip).  `layer`: xdet_conv_create(7, 7, 3, 64, stride 2,
  * pad_mode 2, pad 3 / 3) in mode 1 (f16x3); its scale / shift are applied, its relu_out must be 0.  out: NHWC f32
@@ -1190,6 +1198,19 @@ int xdet_net_refresh_weights(void* net, const xdet_net_weight_dev* table_host, i
  * built, and a large_sep_feature group on a net whose block is in the spectral form (build it with the option
  * large_sep=direct): a spectral layer keeps its kernel as DFT-domain block matrices. */
 int xdet_net_refresh_heads(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
+/* The same for the stem, the last layers outside the two doors above: the same table, two groups, each taken whole only --
+ *   block1_conv1: block1_conv1/kernel [3,3,3,32] and block1_conv1_bn/{gamma, beta, moving_mean, moving_variance};
+ *   block1_conv2: block1_conv2/kernel [3,3,32,64] and the four arrays of block1_conv2_bn.
+ * block1_conv2 -- and block1_conv1 in a net built in f32 mode, where it is a conv layer -- goes xdet_net_refresh_weights' way:
+ * xdet_bn_fold (eps 1e-4) into scratch the net owns (one block at the first call; xdet_net_memory reports it), a slot of one
+ * xdet_layers_refresh_device table, one synchronisation, the layer's host copy of the epilogue scale read back.  In the
+ * split-precision modes block1_conv1 is the kernel of xdet_stem_conv3x3s2_forward and no layer: its kernel is copied device to
+ * device into the net's own array (the same layout), and the fold's scale and shift replace the net's host copies at exponent
+ * 0 and are uploaded again times 2^-e, e the current exponent of the plane "block1_conv1 [stem]".  Exponents,
+ * xdet_net_plane_scales and captured graphs stay; a replayed graph computes with the new weights.
+ * Errors -> XDET_ERR_INVALID_ARG, by name, before any GPU work and with the net unchanged: a name outside the two groups, a
+ * group given in part, a name given twice, a NULL pointer, an empty table, a net that is not built. */
+int xdet_net_refresh_stem(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
 /* Device memory of the net's workspace and weights in bytes (everything the plan allocated), and how many bytes of
  * tensors were placed into blocks recycled from dead tensors (option "workspace" = "reuse", the default: a builder hands a
  * tensor's block back once its last consumer is planned and a later tensor takes it over -- a planes tensor only a block

@@ -675,6 +675,10 @@ int xdet_net_refresh_heads(void* net, const xdet_net_weight_dev* table, int n, v
   XDET_LIGHTHEAD(nt, net, "net_refresh_heads");
   return nt->refresh_heads(table, n, S(stream));
 }
+int xdet_net_refresh_stem(void* net, const xdet_net_weight_dev* table, int n, void* stream) {
+  XDET_LIGHTHEAD(nt, net, "net_refresh_stem");
+  return nt->refresh_stem(table, n, S(stream));
+}
 int xdet_net_get_rpn(void* net, int N, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_get_rpn");
   XDET_TRY(n->check(N));

@@ -159,6 +159,14 @@ struct LightHeadNet : Plan {
   BodyRefreshScratch rf;                            // one block for the whole reach, allocated at the first refresh; the folds
   std::vector<size_t> rf_off;                       // of a record's channels at rf.scale / rf.shift + rf_off[record]
   int scale_read_back(ConvLayer* L);
+  // xdet_net_refresh_stem: block1_conv1 and block1_conv2 from trained weights in device memory.  The direct-form stem keeps
+  // no layer: the net holds its kernel's device copy, its folded batch norm at exponent 0 and the plane the exponent belongs to
+  int refresh_stem(const xdet_net_weight_dev* table, int n, hipStream_t s);
+  BodyRefreshScratch rf_stem;                       // one block, allocated at the first call: conv1's channels, then conv2's
+  Pow2Scaled stem_sc, stem_sh;
+  float* stem_w = nullptr;
+  int stem_pidx = -1;
+  static constexpr float stem_eps = 1e-4f;          // net/xception_body.py:20
   // xdet_net_refresh_heads: the layers the plan owns -- the RPN head's two, the head's two dense layers and (direct form) the
   // large-separable block's two -- from the checkpoint's tensors in device memory.  hd_*: the layers, set by the builders
   // (hd_lsep stays NULL in the spectral form); hs, hs_k: the merges' scratch, allocated at the first call (that names the block)

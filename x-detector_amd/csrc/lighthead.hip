@@ -25,10 +25,12 @@ int LightHeadNet::build_body() {
     x.H = x.W = (S - 3) / 2 + 1; x.C = 32; x.ld = 32; x.no_f32 = true;
     XDET_TRY(new_planes(&x));
     pscales[x.pidx].name = "block1_conv1 [stem]";
-    const Pow2Scaled bn_sc{sc, d_sc}, bn_sh{sh, d_sh};
-    pscales[x.pidx].apply.push_back([=](int e) {     // relu(x*sc + sh) * 2^-e = relu(x*(sc 2^-e) + sh 2^-e), exactly
-      XDET_TRY(bn_sc.upload(-e));
-      return bn_sh.upload(-e);
+    // (members: xdet_net_refresh_stem replaces the host vectors behind them and uploads again at the plane's exponent)
+    stem_sc = Pow2Scaled{sc, d_sc}; stem_sh = Pow2Scaled{sh, d_sh};
+    stem_w = d_w; stem_pidx = x.pidx;
+    pscales[x.pidx].apply.push_back([this](int e) {  // relu(x*sc + sh) * 2^-e = relu(x*(sc 2^-e) + sh 2^-e), exactly
+      XDET_TRY(stem_sc.upload(-e));
+      return stem_sh.upload(-e);
     });
     const Buf o = x;
     stem_direct = true;
@@ -473,6 +475,67 @@ int LightHeadNet::refresh_weights(const xdet_net_weight_dev* table, int n, hipSt
       XDET_TRY(download(g[role], hw->second.v.size()));
       hw->second.v = k;
     }
+  }
+  return XDET_OK;
+}
+
+// The stem from trained weights (include/xdet.h): block1_conv2 -- and block1_conv1 where conv_bn built it, in f32 mode -- takes
+// refresh_weights' own path: the fold, a slot of one table repack, scale_read_back.  block1_conv1 in the direct form keeps no
+// layer: its kernel is copied into d_w (the checkpoint's layout), and the fold's scale and shift replace the host vectors
+// behind the two Pow2Scaleds, uploaded again at the plane's current exponent.
+int LightHeadNet::refresh_stem(const xdet_net_weight_dev* table, int n, hipStream_t s) {
+  XDET_REQUIRE(built, "net_refresh_stem: the net is not built");
+  XDET_REQUIRE(table && n > 0, "net_refresh_stem: an empty table");
+  enum { R_KERNEL, R_GAMMA, R_BETA, R_MEAN, R_VAR };
+  const char* const convs[2] = {"block1_conv1", "block1_conv2"};
+  const int cout[2] = {32, 64};
+  std::vector<NameGroup> groups;
+  const LayerRec* rec[2] = {nullptr, nullptr};
+  for (int g = 0; g < 2; ++g) {
+    const std::string p = convs[g], bn = p + "_bn";
+    groups.push_back({p, {p + "/kernel", bn + "/gamma", bn + "/beta", bn + "/moving_mean", bn + "/moving_variance"}});
+    for (const LayerRec& r : layer_recs)
+      if (r.prefix == p) rec[g] = &r;
+  }
+  std::vector<std::vector<const float*>> given;
+  XDET_TRY(parse_weight_table("net_refresh_stem", "the kernels and batch norms of block1_conv1 and block1_conv2; the body's blocks 2-14 are "
+                              "xdet_net_refresh_weights'", groups, table, n, &given));
+  XDET_REQUIRE(rec[1] && (rec[0] || (stem_direct && stem_w && stem_pidx >= 0)), "net_refresh_stem: the plan holds no such layers");
+  const float* some = table[0].data;                         // (measuring reads no kernel)
+  if (!rf_stem.ws) {
+    std::vector<xdet_layer_refresh> all;
+    for (int g = 0; g < 2; ++g)
+      if (rec[g]) all.push_back({rec[g]->conv, some, nullptr, nullptr});
+    const size_t bytes = xdet_layers_refresh_workspace_bytes(all.data(), (int)all.size());
+    XDET_REQUIRE(bytes > 0, "net_refresh_stem: the plan holds a layer the table door refuses");
+    void* block = nullptr;
+    XDET_TRY(alloc_bytes(ws_measure(256, body_refresh_layout, bytes, (size_t)(cout[0] + cout[1])), &block, false));
+    rf_stem = ws_carve(block, 256, body_refresh_layout, bytes, (size_t)(cout[0] + cout[1]));
+  }
+  float* const sc[2] = {rf_stem.scale, rf_stem.scale + cout[0]};
+  float* const sh[2] = {rf_stem.shift, rf_stem.shift + cout[0]};
+  std::vector<xdet_layer_refresh> slots;
+  for (int g = 0; g < 2; ++g)
+    if (!given[g].empty() && rec[g]) slots.push_back({rec[g]->conv, given[g][R_KERNEL], sc[g], sh[g]});
+  // the table door's refusals are met here, ahead of the first launch: no layer is touched by a refused call
+  XDET_REQUIRE(slots.empty() || xdet_layers_refresh_workspace_bytes(slots.data(), (int)slots.size()) > 0,
+               "net_refresh_stem: the plan holds a layer the table door refuses");
+  for (int g = 0; g < 2; ++g) {
+    const std::vector<const float*>& t = given[g];
+    if (t.empty()) continue;
+    XDET_TRY(xdet_bn_fold(t[R_GAMMA], t[R_BETA], t[R_MEAN], t[R_VAR], nullptr, rec[g] ? rec[g]->eps : stem_eps, cout[g], sc[g], sh[g], s));
+  }
+  const bool direct = !given[0].empty() && !rec[0];
+  if (direct) XDET_HIP(hipMemcpyAsync(stem_w, given[0][R_KERNEL], (size_t)27 * 32 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (!slots.empty()) XDET_TRY(xdet_layers_refresh_device(slots.data(), (int)slots.size(), rf_stem.ws, s));
+  XDET_HIP(hipStreamSynchronize(s));
+  for (const xdet_layer_refresh& l : slots) XDET_TRY(scale_read_back(static_cast<ConvLayer*>(l.layer)));
+  if (direct) {
+    XDET_HIP(hipMemcpy(stem_sc.host.data(), sc[0], (size_t)cout[0] * sizeof(float), hipMemcpyDeviceToHost));
+    XDET_HIP(hipMemcpy(stem_sh.host.data(), sh[0], (size_t)cout[0] * sizeof(float), hipMemcpyDeviceToHost));
+    const int e = pscales[stem_pidx].exp;
+    XDET_TRY(stem_sc.upload(-e));
+    XDET_TRY(stem_sh.upload(-e));
   }
   return XDET_OK;
 }

@@ -63,6 +63,11 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- nothing in the reference (its trainer is one session; xdet_v5_resnet_train.py:144 only
                              anticipates replicate_model_fn): data-parallel training, every rank's gradients become the
                              rank-ordered f32 mean, the same bits on every rank, ahead of the step
+  stem_train, stem_backward, host_stem_train, host_stem_backward, STEM_VARIABLES, STEM_MOVING, STEM_STAGE, check_stem
+  (xdet.model; LightHeadDetector(stem_train=True), detector.stem_saved(), LightHeadDetector.refresh_stem)
+                          <- the two stem convs (net/xception_body.py:243-258) with batch statistics and their backward,
+                             block1_conv1 from the NCHW image by a kernel of its own (xdet_stem_conv3x3s2_train_forward); with
+                             it MomentumOptimizer steps the whole network, 176 variables, and refreshes the eval net's stem
   jpeg_info, host_jpeg_coefficients, host_decode_jpeg, decode_jpegs_device, decode_jpegs (xdet.jpeg);
   LightHeadDetector.detect_jpegs (xdet.model)
                           <- tf.image.decode_image in front of the eval and training pipelines (dataset/dataset_common.py:542)

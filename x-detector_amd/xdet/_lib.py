@@ -136,6 +136,7 @@ SIGNATURES = {
     'xdet_spectral_conv_workspace_bytes': (c_size_t, [c_void_p, c_int]),
     'xdet_spectral_conv_forward': (c_int, [c_void_p, PF, c_int, c_int, c_void_p, PF, c_int, c_void_p]),
     'xdet_stem_conv3x3s2_forward': (c_int, [PF, PF, PF, PF, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'xdet_stem_conv3x3s2_train_forward': (c_int, [PF, PF, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_resnet_stem7x7_forward': (c_int, [c_void_p, PF, c_int, c_int, PF, c_void_p]),
     'xdet_maxpool3x3s2_bn_planes': (c_int, [PF, PF, PF, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                             c_void_p, c_void_p, c_int, c_float, c_void_p]),
@@ -229,6 +230,7 @@ SIGNATURES = {
     'xdet_net_mid_refresh': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_refresh_weights': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
     'xdet_net_refresh_heads': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
+    'xdet_net_refresh_stem': (c_int, [c_void_p, ctypes.POINTER(NetWeightDev), c_int, c_void_p]),
     'xdet_net_large_sep': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_rpn_decode': (c_int, [c_void_p, c_int, c_void_p]),
     'xdet_net_get_proposals': (c_int, [c_void_p, c_int, c_void_p]),

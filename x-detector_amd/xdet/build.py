@@ -34,6 +34,7 @@ SOURCES = [
     ('batchnorm.hip', ['-ffp-contract=off']),
     ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('pool_backward.hip', ['-ffp-contract=off']),
+    ('stem_train.hip', ['-ffp-contract=off']),
     ('optimizer.hip', ['-ffp-contract=off']),
     ('conv_repack.hip', ['-ffp-contract=off']),
     ('weight_pack.hip', ['-ffp-contract=off']),

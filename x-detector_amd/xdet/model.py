@@ -26,7 +26,7 @@ class LightHeadDetector(object):
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
                  pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
-                 entry_flow_train=False):
+                 entry_flow_train=False, stem_train=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -64,9 +64,17 @@ class LightHeadDetector(object):
         both units and the block's output), the workspaces and the gradient tensors the backward writes, all sized for
         max_batch: model.entry_flow_train() recomputes `entry_x` from `stem_out` with batch statistics,
         model.entry_flow_backward takes the gradient from `entry_x` down to `stem_out`.  The default detector allocates and runs
-        none of this."""
+        none of this.
+        stem_train=True (needs entry_flow_train=True: the training-mode `stem_out` it writes is consumed by the training-mode
+        entry flow): the six variables of the two stem convs (STEM_VARIABLES) and the moving statistics of their two batch
+        norms are kept unfolded on the device, with block1_conv2 as a conv layer of its own, the image as NHWC4 rows, the
+        tensors a training forward saves (z1, a1, z2), the three gradient tensors of the backward and the workspaces, all sized
+        for max_batch: model.stem_train() recomputes `stem_out` from the images with batch statistics, model.stem_backward
+        takes the gradient from `stem_out` down to both kernels.  With it MomentumOptimizer steps the whole network.  The
+        default detector allocates and runs none of this."""
         stages = (large_sep_train, exit_flow_train, middle_flow_train, entry_flow_train)
         _train.check_stages(stages, weights)
+        _train.check_stem(stem_train, entry_flow_train, weights)
         if device is not None:
             check(lib().xdet_set_device(int(device)))
         self.cfg = LightHeadConfig(image_size=image_size, max_batch=max_batch, num_classes=num_classes,
@@ -122,6 +130,9 @@ class LightHeadDetector(object):
         self._det_boxes = DeviceBuffer(B * nc * k * 16)
         self._N = 0
         _train.build_stages(self, stages, weights)       # self.large_sep_train ... self.entry_flow_train and their states
+        self.stem_train = bool(stem_train)               # the fifth stage, next to the table (train.STEM_STAGE)
+        if stem_train:
+            self._stem = _train.StemState(self, weights)
 
     def large_sep_saved(self):
         """what the last large_sep_kernel(..., is_training=True) left on the device, as DeviceTensors: 't' [n,h,w,2*mid] =
@@ -155,6 +166,14 @@ class LightHeadDetector(object):
         '<bn>/save_mean', '/save_invstd' (the batch statistics), '/moving_mean', '/moving_variance' (after their update), each
         [1,1,1,C]"""
         return _train.saved(self, _train.ENTRY)
+
+    def stem_saved(self):
+        """what the last model.stem_train() left on the device, as DeviceTensors of the n images it ran on: 'x1' (the images as
+        NHWC rows of 4 floats, what block1_conv1's dW reads), 'block1_conv1/z' (the first conv's output, its batch norm's
+        input), 'a1' (that batch norm's ReLU output), 'block1_conv2/z', 'x2' (the net's `stem_out`); and per batch norm
+        '<bn>/save_mean', '/save_invstd' (the batch statistics), '/moving_mean', '/moving_variance' (after their update), each
+        [1,1,1,C]"""
+        return _train.saved(self, _train.STEM)
 
     # ---- plumbing -------------------------------------------------------------------
     def buffer(self, name, n=None):
@@ -264,6 +283,34 @@ class LightHeadDetector(object):
         for i, (name, t) in enumerate(tensors.items()):
             table[i] = NetWeightDev(name.encode(), t.ptr)
         check(lib().xdet_net_refresh_heads(self.handle, table, len(tensors), self.stream.handle))
+
+    def refresh_stem(self, tensors):
+        """Refresh the eval net's stem from weights on the device (xdet_net_refresh_stem): tensors is {checkpoint name: dense f32
+        DeviceTensor or DeviceBuffer in the checkpoint's shape} over whole groups -- 'block1_conv1' and 'block1_conv2', each
+        <conv>/kernel and the four arrays of <conv>_bn (train.STEM_VARIABLES + STEM_MOVING).  The batch norms are folded on the
+        device; block1_conv2 is repacked by the table door, block1_conv1's kernel copied into the net's array and its folded
+        scale and shift uploaded again at the plane's current exponent; the stream is synchronised and the host state a
+        calibration works from brought back in line; exponents, plane_scales() and the captured graphs stay.
+        Refused ahead of any GPU work, by name: a host array, a name outside the two groups, a group given in part."""
+        from ._lib import NetWeightDev
+        for name, t in tensors.items():
+            if not isinstance(t, (DeviceTensor, DeviceBuffer)) or not t.ptr:
+                raise InvalidArgumentError(-1, 'refresh_stem: %s must be a DeviceTensor or a DeviceBuffer (device memory), got %s'
+                                           % (name, type(t).__name__))
+        groups = {c: [c + '/kernel'] + ['%s_bn/%s' % (c, k) for k in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
+                  for c in _train.STEM_CONVS}
+        for name in tensors:
+            if not any(name in want for want in groups.values()):
+                raise InvalidArgumentError(-1, 'refresh_stem: %s is outside the reach (the kernels and batch norms of block1_conv1 '
+                                               'and block1_conv2)' % name)
+        for c, want in groups.items():
+            miss = [n for n in want if n not in tensors]
+            if miss and len(miss) != len(want):
+                raise InvalidArgumentError(-1, 'refresh_stem: the group of %s is given in part: %s is missing' % (c, ', '.join(miss)))
+        table = (NetWeightDev * max(len(tensors), 1))()
+        for i, (name, t) in enumerate(tensors.items()):
+            table[i] = NetWeightDev(name.encode(), t.ptr)
+        check(lib().xdet_net_refresh_stem(self.handle, table, len(tensors), self.stream.handle))
 
     def x8_planes(self):
         """tensors in the x8 form (cross='fp8', after calibrate()): xdet_net_x8_planes"""

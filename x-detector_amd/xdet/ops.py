@@ -486,6 +486,22 @@ def stem_conv3x3s2(images_nchw, kernel_hwio, scale, shift, out=None, stream=None
     return hi, lo
 
 
+def stem_conv3x3s2_train(images_nchw, kernel_hwio, ld=32, out=None, stream=None):
+    """block1_conv1 in training mode (xdet_stem_conv3x3s2_train_forward): images f32 [N,3,S,S], kernel [3,3,3,32] -> the raw f32
+    conv output as a DeviceTensor [N,Ho,Ho,32] with pixel stride ld, Ho = (S-3)//2 + 1 -- no BN, no ReLU, no split; channels
+    32 .. ld - 1 of a pixel are not written.  out: a DeviceTensor [N,Ho,Ho,32] to write into (with its ld)."""
+    x = np.ascontiguousarray(images_nchw, np.float32)
+    N, C, S, S2 = x.shape
+    assert C == 3 and S == S2 and tuple(np.shape(kernel_hwio)) == (3, 3, 3, 32)
+    Ho = (S - 3) // 2 + 1
+    d_x, d_w = to_device(x), to_device(np.ascontiguousarray(kernel_hwio, np.float32))
+    z = out if out is not None else DeviceTensor.empty((N, Ho, Ho, 32), ld=ld)
+    assert tuple(z.shape) == (N, Ho, Ho, 32), z.shape
+    check(lib().xdet_stem_conv3x3s2_train_forward(d_x.ptr, d_w.ptr, N, S, z.ptr, z.ld, stream.handle if stream else None))
+    synchronize(stream)
+    return z
+
+
 def resnet_stem7x7(conv, images_nchw, stream=None):
     """conv2d_fixed_padding(7, 64, stride 2) of the ResNet v2 stem on its own kernel (xdet_resnet_stem7x7_forward): `conv` a
     Conv2D(7x7x3x64, stride 2, 'EXPLICIT', explicit_pad=3) created in the f16x3 mode, images f32 [N,3,S,S] -> DeviceTensor

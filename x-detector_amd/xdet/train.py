@@ -4,7 +4,8 @@ Four stages can be rebuilt in training mode (batch statistics, moving-average up
 above it writes: the large-separable block <- the exit flow <- the middle flow <- blocks 2-4 of the entry flow (`STAGES`).  A
 detector built with a stage's flag keeps one state object for it (`LargeSepState`, `ExitFlowState`, `MiddleFlowState`,
 `EntryFlowState`), made of `BatchNorm`, `SepUnit` and `Projection`; the module-level functions run a stage of the detector
-that is current (`with det.scope():`).  The head's and the RPN head's backward (`head_backward`, `rpn_backward`) and the NumPy
+that is current (`with det.scope():`).  The stem -- the two convs in front of block 2 -- is a fifth stage that stands next to
+the table (`STEM_STAGE`, `StemState`): it feeds all four.  The head's and the RPN head's backward (`head_backward`, `rpn_backward`) and the NumPy
 statements of the middle and the entry flow (`host_*`) live here too, and the optimizer step over the three flows' variables
 and, at reach='all', the large-separable block's and both heads' (`MomentumOptimizer`, `piecewise_learning_rate`).
 """
@@ -26,7 +27,8 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEA
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
            'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'optimizer_variables',
-           'MomentumOptimizer']
+           'MomentumOptimizer', 'STEM_CONVS', 'STEM_VARIABLES', 'STEM_MOVING', 'STEM_EPS', 'STEM_MOMENTUM', 'STEM_STAGE', 'STEM', 'StemState',
+           'check_stem', 'stem_train', 'stem_backward', 'host_stem_train', 'host_stem_backward']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
                             for conv in ('conv2d', 'conv2d_1') for v in ('kernel', 'bias')) + \
@@ -73,6 +75,13 @@ ENTRY_FLOW_MOVING = tuple('%s/%s' % (bn, v) for b in ENTRY_FLOW_BLOCKS
                           for bn in ('batch_normalization_%d' % (b - 1), 'block%d_sepconv1_bn' % b, 'block%d_sepconv2_bn' % b)
                           for v in ('moving_mean', 'moving_variance'))
 ENTRY_FLOW_EPS, ENTRY_FLOW_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
+
+# the stem (net/xception_body.py:243-258): conv 3x3 / stride 2 / 'VALID' 3 -> 32 from the image, conv 3x3 / 'VALID' 32 -> 64,
+# each with a batch norm and a ReLU behind it; the second ReLU's output is the entry flow's input, the net's `stem_out`
+STEM_CONVS = ('block1_conv1', 'block1_conv2')
+STEM_VARIABLES = tuple(c + v for c in STEM_CONVS for v in ('/kernel', '_bn/gamma', '_bn/beta'))
+STEM_MOVING = tuple(c + v for c in STEM_CONVS for v in ('_bn/moving_mean', '_bn/moving_variance'))
+STEM_EPS, STEM_MOMENTUM = EXIT_FLOW_EPS, EXIT_FLOW_MOMENTUM
 
 
 def _entry_relu_in(b, i):
@@ -533,6 +542,48 @@ class EntryFlowState(object):
         return out
 
 
+class StemState(object):
+    """the stem: the two kernels as the checkpoint stores them (K1 is what the training-mode conv reads, K2 the backward's
+    operand: both the optimizer's masters), both batch norms, block1_conv2 as a conv layer (split precision, f32 out, 3x3
+    'VALID'), the image as NHWC rows of 4 floats (block1_conv1's dW reads it), the kept z1, a1 and z2, the three gradient
+    tensors of the backward, and one BN and one conv-backward workspace for every batch size up to max_batch"""
+
+    def __init__(self, d, weights):
+        k1 = np.ascontiguousarray(weights['block1_conv1/kernel'], np.float32)
+        k2 = np.ascontiguousarray(weights['block1_conv2/kernel'], np.float32)
+        B, S = d.max_batch, d.image_size
+        c1, c2 = k1.shape[3], k2.shape[3]
+        H1 = (S - 3) // 2 + 1
+        H2 = H1 - 2
+        so = d.buffer('stem_out', 1)
+        if tuple(k1.shape) != (3, 3, 3, 32) or tuple(k2.shape[:3]) != (3, 3, 32) or tuple(so.shape[1:]) != (H2, H2, c2):
+            raise InvalidArgumentError(-1, 'stem_train: block1_conv2 gives %r but the net\'s stem_out is %r (kernels %r and %r)'
+                                       % ((H2, H2, c2), tuple(so.shape[1:]), tuple(k1.shape), tuple(k2.shape)))
+        self.n, self.S, self.H1, self.H2 = 0, S, H1, H2
+        self.K1, self.K2 = _dense(k1), _dense(k2)
+        self.bn1 = BatchNorm(weights, 'block1_conv1_bn', STEM_EPS, STEM_MOMENTUM)
+        self.bn2 = BatchNorm(weights, 'block1_conv2_bn', STEM_EPS, STEM_MOMENTUM)
+        with _f16x3():
+            self.conv2 = ops.Conv2D(k2, padding='VALID')
+        self.image = DeviceTensor.empty((B, S, S, 3), ld=4)
+        self.z1, self.a1, self.z2 = (DeviceTensor.empty(s) for s in ((B, H1, H1, c1), (B, H1, H1, c1), (B, H2, H2, c2)))
+        self.dz2, self.da1, self.dz1 = (DeviceTensor.empty(s) for s in ((B, H2, H2, c2), (B, H1, H1, c1), (B, H1, H1, c1)))
+        self.db = DeviceBuffer(4 * max(c1, c2))          # the bias gradient xdet_conv_backward_strided insists on: dropped
+        l = lib()
+        self.ws_bn = _max_over_batches(B, lambda n: max(l.xdet_batch_norm_workspace_bytes(n * H1 * H1, c1),
+                                                        l.xdet_batch_norm_workspace_bytes(n * H2 * H2, c2)))
+        self.ws_conv = _max_over_batches(B, lambda n: max(l.xdet_conv_backward_strided_workspace_bytes(n, H1, H1, c1, c2, 3, 3, 1, 0),
+                                                          l.xdet_conv_backward_strided_workspace_bytes(n, S, S, 3, c1, 3, 3, 2, 0)))
+
+    def saved(self, d):
+        n = self.n
+        out = {'x1': _first(self.image, n), 'block1_conv1/z': _first(self.z1, n), 'a1': _first(self.a1, n),
+               'block1_conv2/z': _first(self.z2, n), 'x2': d.buffer('stem_out', n)}
+        self.bn1.views(out)
+        self.bn2.views(out)
+        return out
+
+
 # The stages in the order the data flows backward through them, each consuming what the next one writes in training mode:
 # (the constructor flag and detector attribute, where the detector keeps the state, its class, the weights it needs, the
 # forward its *_saved() names, and why it cannot do without the stage above it in this table)
@@ -547,6 +598,29 @@ STAGES = (
     Stage('entry_flow_train', '_entry', EntryFlowState, ENTRY_FLOW_VARIABLES + ENTRY_FLOW_MOVING, 'model.entry_flow_train()',
           'the training-mode `entry_x` it writes is consumed by the middle flow in training mode'))
 LARGE_SEP, EXIT, MIDDLE, ENTRY = range(4)
+# The stem stands next to the table, not in it: it is upstream of every stage of STAGES -- its training forward drops what all
+# four had saved, and no training forward of theirs drops what it saved -- and the shared bookkeeping reads its flag as
+# getattr(d, 'stem_train', False), so whatever carries exactly the table's four flags behaves as it did.
+STEM_STAGE = Stage('stem_train', '_stem', StemState, STEM_VARIABLES + STEM_MOVING, 'model.stem_train()',
+                   'the training-mode `stem_out` it writes is consumed by the entry flow in training mode')
+STEM = 4
+
+
+def _stage_of(k):
+    return STEM_STAGE if k == STEM else STAGES[k]
+
+
+def check_stem(stem_on, entry_on, weights):
+    """check_stages' two refusals for the stem, ahead of the native net: it needs the entry flow's stage, then its own variables
+    and moving statistics"""
+    s = STEM_STAGE
+    if not stem_on:
+        return
+    if not entry_on:
+        raise InvalidArgumentError(-1, '%s=True needs %s=True (%s)' % (s.flag, STAGES[ENTRY].flag, s.needs))
+    miss = [v for v in s.names if v not in weights]
+    if miss:
+        raise InvalidArgumentError(-1, '%s: the weights lack %s' % (s.flag, ', '.join(miss)))
 
 
 def check_stages(on, weights):
@@ -573,9 +647,10 @@ def build_stages(d, on, weights):
 
 
 def saved(d, k):
-    """detector.<stage>_saved(): what stage k's last training forward left on the device, as DeviceTensors of its n images"""
-    s = STAGES[k]
-    state = getattr(d, s.attr) if getattr(d, s.flag) else None
+    """detector.<stage>_saved(): what stage k's last training forward left on the device, as DeviceTensors of its n images
+    (k: an index of STAGES, or STEM)"""
+    s = _stage_of(k)
+    state = getattr(d, s.attr) if getattr(d, s.flag, False) else None
     if state is None or not state.n:
         raise InvalidArgumentError(-1, '%s: no %s has run on this detector' % (s.flag.replace('_train', '_saved'), s.forward))
     return state.saved(d)
@@ -583,9 +658,10 @@ def saved(d, k):
 
 def _stage(d, k, fn, first=None, keeps=''):
     """the two refusals an entry point opens with -> (stage k's state, the images to run on).  A backward names the training
-    forward it follows (`first`) and runs on that one's images; a training forward follows the eval body and runs on its"""
-    s = STAGES[k]
-    if not getattr(d, s.flag):
+    forward it follows (`first`) and runs on that one's images; a training forward follows the eval body and runs on its
+    (k: an index of STAGES, or STEM)"""
+    s = _stage_of(k)
+    if not getattr(d, s.flag, False):
         why = '' if first else ' (the default detector folds the moving statistics into the conv weights%s)' % keeps
         raise InvalidArgumentError(-1, '%s: needs a detector built with %s=True%s' % (fn, s.flag, why))
     state = getattr(d, s.attr)
@@ -603,14 +679,25 @@ def _ran(d, k, n):
     getattr(d, STAGES[k].attr).n = n
 
 
+def _stem_ran(d, n):
+    """the stem's training forward has run on n images: it feeds every stage of STAGES, so what all four had saved belongs to
+    another `stem_out`"""
+    for s in STAGES:
+        if getattr(d, s.flag):
+            getattr(d, s.attr).n = 0
+    getattr(d, STEM_STAGE.attr).n = n
+
+
 def new_body(d):
     """the eval body is about to run on new images (set_images, a caller-owned image pointer, the uint8 ingest): `stem_out`,
     `entry_x`, `mid_x` and `out` will hold their eval tensors, so what every stage had saved belongs to tensors that are gone.
     Each *_backward and *_saved() refuses until its stage's training forward has run again.  A detector built without
-    training flags pays the four attribute reads"""
+    training flags pays the four attribute reads, and one more for the stem's flag"""
     for s in STAGES:
         if getattr(d, s.flag):
             getattr(d, s.attr).n = 0
+    if getattr(d, STEM_STAGE.flag, False):
+        getattr(d, STEM_STAGE.attr).n = 0
 
 
 # ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
@@ -1090,6 +1177,98 @@ def entry_flow_backward(d_entry, intermediates=False, weight_grads='host'):
     return grads
 
 
+def stem_train(images=None):
+    """The stem in training mode (net/xception_body.py:243-258), called after XceptionBody(..., is_training=False) on a detector
+    built with stem_train=True: both stem convs are computed again from the images with batch statistics --
+
+        x1 = nhwc4(images)           (xdet_nchw_to_nhwc4: what block1_conv1's dW reads in the backward)
+        z1 = conv3x3s2_valid(images, K1)     (xdet_stem_conv3x3s2_train_forward: f32, straight from NCHW and from the master K1)
+        a1 = relu(BN(z1))            z2 = conv3x3_valid(a1, K2)   (xdet_conv_forward, split precision, f32 out)
+        stem_out = relu(BN(z2))
+
+    -- the batch norms by xdet_batch_norm_forward in training mode (eps 1e-4, momentum 0.99, the moving statistics updated on
+    their device copies); the second one writes straight into the net's `stem_out` buffer (with its ld), so entry_flow_train()
+    and everything behind it go on unchanged.  Five calls on the detector's stream with no host round trip.  images=None: the
+    detector's own image buffer, what set_images, XceptionBody and the ingest doors (detect_images, detect_jpegs) filled, and
+    the body's image count; images=: a dense f32 DeviceTensor [n,3,S,S] (NCHW, ld S) from a caller that ran the body on its own
+    pointer (forward_device(images_ptr=...)).  The saved state of all four stages of STAGES is dropped: their backwards refuse
+    until their training forwards have run on the new tensors.  What stem_backward needs stays on the device
+    (detector.stem_saved()) until the next eval body or optimizer step; no other stage's training forward drops it.
+    -> `stem_out` [N,h,w,64]."""
+    d = _det()
+    if images is None or not getattr(d, STEM_STAGE.flag, False):
+        s, n = _stage(d, STEM, 'stem_train', keeps=' and keeps no unfolded stem')
+        src = d._images.ptr
+    else:                                                # (the caller's own body: the detector counted no images for it)
+        s = getattr(d, STEM_STAGE.attr)
+        S = s.S
+        if not isinstance(images, DeviceTensor) or len(images.shape) != 4 or tuple(images.shape[1:]) != (3, S, S) \
+                or images.ld != S or not 1 <= images.shape[0] <= d.max_batch:
+            raise InvalidArgumentError(-1, 'stem_train: images must be a dense f32 DeviceTensor [n,3,%d,%d] (NCHW, ld %d) of 1 to %d '
+                                           'images, got %r (ld %r)' % (S, S, S, d.max_batch, getattr(images, 'shape', None),
+                                                                      getattr(images, 'ld', None)))
+        n, src = images.shape[0], images.ptr
+    h, l = d.stream.handle, lib()
+    S, H1, H2 = s.S, s.H1, s.H2
+    out = d.buffer('stem_out', n)
+    check(l.xdet_nchw_to_nhwc4(src, s.image.ptr, n, 3, S, S, h))
+    check(l.xdet_stem_conv3x3s2_train_forward(src, s.K1.ptr, n, S, s.z1.ptr, s.z1.ld, h))
+    s.bn1.forward(d, s.z1, True, s.a1, n * H1 * H1, s.ws_bn)
+    check(l.xdet_conv_forward(s.conv2.handle, s.a1.ptr, n, H1, H1, s.a1.ld, s.z2.ptr, s.z2.ld, None, 0, h))
+    s.bn2.forward(d, s.z2, True, out, n * H2 * H2, s.ws_bn)
+    _stem_ran(d, n)                                  # (what every other stage saved belongs to another stem_out)
+    _sync(d)
+    return out
+
+
+def stem_backward(d_stem, intermediates=False, weight_grads='host'):
+    """The backward of the stem in training mode, called after stem_train() on a detector built with stem_train=True:
+    d_stem = entry_flow_backward(...)['stem'] (d loss / d stem_out, with `stem_out`'s shape and ld).
+
+        dz2 = BN_backward(bn2, d_stem)   (masked by the net's `stem_out`)      da1, dK2 = conv_backward(a1, K2, dz2)
+        dz1 = BN_backward(bn1, da1)      (masked by the kept a1)               dK1 = conv_backward(x1, K1, dz1)    (no dx)
+
+    -- xdet_batch_norm_backward and xdet_conv_backward_strided (stride 1 and stride 2, 'VALID'; x1 = the NHWC4 image; the bias
+    gradients it insists on are computed and dropped): four calls on the detector's stream with no host round trip and no
+    float atomics, on tensors, workspaces and results that all exist before the first launch.  There is no image gradient.
+    -> a dict with the six gradients under the checkpoint's variable names and in its shapes (STEM_VARIABLES, NumPy).
+    intermediates=True: also 'z/block1_conv2' (dz2), 'a/block1_conv1' (da1) and 'z/block1_conv1' (dz1), each in a tensor of
+    its own.  Refused once a new eval body (set_images, forward, calibrate, detect_images) or an optimizer step has run since
+    stem_train(): the kept tensors belong to other images or weights.
+    weight_grads='device': the six variables come back as dense DeviceTensors in the checkpoint's shapes instead and nothing is
+    downloaded (what MomentumOptimizer.step takes); everything else the call returns is unchanged."""
+    d = _det()
+    _check_weight_grads('stem_backward', weight_grads)
+    s, n = _stage(d, STEM, 'stem_backward', 'stem_train()')
+    out = d.buffer('stem_out', n)
+    _check_grad('stem_backward', 'd_stem', d_stem, out)
+    S, H1, H2 = s.S, s.H1, s.H2
+    c1, c2 = s.K1.shape[3], s.K2.shape[3]
+    # everything the call returns on the device, allocated ahead of the launches
+    grads = {}
+    if intermediates:
+        dz2, da1, dz1 = (DeviceTensor.empty((n,) + tuple(t.shape[1:]), ld=t.ld) for t in (s.dz2, s.da1, s.dz1))
+        grads.update({'z/block1_conv2': dz2, 'a/block1_conv1': da1, 'z/block1_conv1': dz1})
+    else:
+        dz2, da1, dz1 = _first(s.dz2, n), _first(s.da1, n), _first(s.dz1, n)
+    shapes = dict(zip(STEM_VARIABLES, (tuple(s.K1.shape), (c1,), (c1,), tuple(s.K2.shape), (c2,), (c2,))))
+    dev = {v: (DeviceBuffer(max(4 * math.prod(shape), 16)), shape) for v, shape in shapes.items()}
+    (dk1, _), (dg1, _), (db1, _), (dk2, _), (dg2, _), (db2, _) = (dev[v] for v in STEM_VARIABLES)
+    x1, z1, a1, z2 = s.image, s.z1, s.a1, s.z2
+    h, l = d.stream.handle, lib()
+    check(l.xdet_batch_norm_backward(z2.ptr, z2.ld, out.ptr, out.ld, d_stem.ptr, d_stem.ld, n * H2 * H2, c2, s.bn2.gamma.ptr,
+                                     s.bn2.save_mean.ptr, s.bn2.save_invstd.ptr, 1, dz2.ptr, dz2.ld, dg2.ptr, db2.ptr, s.ws_bn.ptr, h))
+    check(l.xdet_conv_backward_strided(a1.ptr, a1.ld, s.K2.ptr, None, 0, dz2.ptr, dz2.ld, n, H1, H1, c1, c2, 3, 3, 1, 0, 0,
+                                       da1.ptr, da1.ld, dk2.ptr, s.db.ptr, s.ws_conv.ptr, h))
+    check(l.xdet_batch_norm_backward(z1.ptr, z1.ld, a1.ptr, a1.ld, da1.ptr, da1.ld, n * H1 * H1, c1, s.bn1.gamma.ptr,
+                                     s.bn1.save_mean.ptr, s.bn1.save_invstd.ptr, 1, dz1.ptr, dz1.ld, dg1.ptr, db1.ptr, s.ws_bn.ptr, h))
+    check(l.xdet_conv_backward_strided(x1.ptr, x1.ld, s.K1.ptr, None, 0, dz1.ptr, dz1.ld, n, S, S, 3, c1, 3, 3, 2, 0, 0,
+                                       None, x1.ld, dk1.ptr, s.db.ptr, s.ws_conv.ptr, h))
+    _sync(d)
+    _deliver(dev, grads, weight_grads)
+    return grads
+
+
 # ---- the optimizer step: the reference's schedule and tf.train.MomentumOptimizer over the three flows' variables ---------------
 
 def piecewise_learning_rate(step, base=1e-3, boundaries=(60000, 80000), factors=(1, 0.8, 0.1), end=1e-4):
@@ -1111,13 +1290,15 @@ def decayed(name):
     return 'batch_normalization' not in name and '_bn' not in name
 
 
-def optimizer_variables(on, reach='flows'):
+def optimizer_variables(on, reach='flows', stem=False):
     """MomentumOptimizer.variables for a detector whose stages are `on` (one flag per stage, in STAGES' order): the entry, the
     middle and the exit flow's variables of the stages that are on, in that order -- and with reach='all' LARGE_SEP_VARIABLES,
-    RPN_HEAD_VARIABLES and HEAD_VARIABLES behind them (170 with all stages on).  This is also the order of the gradient exchange."""
+    RPN_HEAD_VARIABLES and HEAD_VARIABLES behind them (170 with all stages on).  stem=True (a detector built with
+    stem_train=True): STEM_VARIABLES in front of them all -- 154 and 176, the whole network.  This is also the order of the
+    gradient exchange."""
     names = tuple(v for k, vs in ((ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES))
                   if on[k] for v in vs)
-    return names + (LARGE_SEP_VARIABLES + RPN_HEAD_VARIABLES + HEAD_VARIABLES if reach == 'all' else ())
+    return (STEM_VARIABLES if stem else ()) + names + (LARGE_SEP_VARIABLES + RPN_HEAD_VARIABLES + HEAD_VARIABLES if reach == 'all' else ())
 
 
 def eval_net_groups(names):
@@ -1155,7 +1336,7 @@ class MomentumOptimizer(object):
     three, 15 + 48 + 9 = 72 of them kernels in the L2 set).  The masters are the buffers the stages already hold -- SepUnit.K_dw,
     SepUnit.K_pw, Projection.K, BatchNorm.gamma, BatchNorm.beta -- updated in place; the optimizer allocates the momentum slots
     (zero) and the step's workspace and holds a second copy of nothing.
-    Out of its reach (reach='flows', the default): the large-separable block, the head, the RPN head and the stem keep their weights.  The NATIVE EVAL NET
+    Out of its reach (reach='flows', the default): the large-separable block, the head and the RPN head keep their weights (and the stem, on a detector built without stem_train).  The NATIVE EVAL NET
     keeps the weights it last folded -- XceptionBody(..., is_training=False), forward, detect_images and evaluate compute with
     them -- until refresh_eval_net() refolds the body's blocks 2-14 from the masters and the training stages' moving statistics
     on the device (xdet_net_refresh_weights: no host round trip of the weights, no second net, the captured graphs stay).
@@ -1163,9 +1344,14 @@ class MomentumOptimizer(object):
     weights): `variables` is the flows' list as above, then LARGE_SEP_VARIABLES, RPN_HEAD_VARIABLES and HEAD_VARIABLES -- 170
     with all stages on, the 10 conv / dense kernels and their 10 biases of the three new groups in the L2 set (`decayed`; the
     block's gamma and beta are not).  The masters of those 20 tensors are new device copies in the checkpoint's shapes, gamma
-    and beta the buffers LargeSepState.bn holds.  Only the two stem convs then stay at the checkpoint's values."""
+    and beta the buffers LargeSepState.bn holds.
+    A detector built with stem_train=True: STEM_VARIABLES come first -- 154 variables at reach='flows', 176 at reach='all', the
+    whole network: nothing stays at the checkpoint's values.  Their masters are StemState's K1 and K2 (two more kernels in the
+    L2 set) and the two batch norms' gamma and beta; block1_conv1's training forward reads K1 in place, block1_conv2's layer
+    is one more slot of the refresh table, and refresh_eval_net() hands the eval net's stem over too (xdet_net_refresh_stem)."""
 
     reach = 'flows'
+    _stem = None                                           # StemState of a detector built with stem_train=True
 
     def __init__(self, det, momentum=0.9, weight_decay=2e-4, reach='flows'):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
@@ -1191,11 +1377,14 @@ class MomentumOptimizer(object):
             masters[u.name + '/depthwise_kernel'], masters[u.name + '/pointwise_kernel'] = (u.K_dw, u.K_dw.shape), (u.K_pw, u.K_pw.shape)
         for p in self._projections():
             masters[p.name + '/kernel'] = (p.K, p.K.shape)
-        for bn in self._batch_norms():
+        self._stem = getattr(det, STEM_STAGE.attr) if getattr(det, STEM_STAGE.flag, False) else None
+        if self._stem is not None:
+            masters['block1_conv1/kernel'], masters['block1_conv2/kernel'] = (self._stem.K1, self._stem.K1.shape), (self._stem.K2, self._stem.K2.shape)
+        for bn in self._batch_norms() + self._stem_batch_norms():
             masters[bn.name + '/gamma'], masters[bn.name + '/beta'] = (bn.gamma, (bn.co,)), (bn.beta, (bn.co,))
         on_flags = [getattr(det, s.flag, False) for s in STAGES]
         self._flow_variables = optimizer_variables(on_flags)
-        self.variables = optimizer_variables(on_flags, reach)
+        self.variables = optimizer_variables(on_flags, reach, stem=self._stem is not None)
         if reach == 'all':
             self._reach_all(masters)
         self._master = {v: masters[v] for v in self.variables}            # name -> (device array, shape)
@@ -1254,6 +1443,9 @@ class MomentumOptimizer(object):
     def _batch_norms(self):
         return [u.bn for u in self._units()] + [p.bn for p in self._projections()]
 
+    def _stem_batch_norms(self):
+        return [self._stem.bn1, self._stem.bn2] if self._stem is not None else []
+
     def step(self, grads, lr, comm=None):
         """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
         backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
@@ -1261,7 +1453,8 @@ class MomentumOptimizer(object):
         depthwise layer and every projection's conv, as the units hold them at this moment) from the updated masters by one
         xdet_layers_refresh_device table; and the drop of every stage's saved state, as a new eval
         body drops it: the kept tensors belong to the old weights, so each *_backward refuses until its training forward has run
-        again (the eval body need not: `stem_out` does not depend on these variables).
+        again (the eval body need not: `stem_out` does not depend on these variables -- unless the stem is stepped too, and
+        then stem_train() writes the new one).
         -> {'step': the number of steps taken, 'lr': lr, 'l2': sum over the L2 set of sum v^2 / 2 before the update, a float}.
         Refused ahead of any launch: a missing gradient (by name), a host array, a wrong shape.
         comm (an xdet.dist.Communicator; data-parallel training, every rank calls step with its own batch's gradients): after
@@ -1317,6 +1510,8 @@ class MomentumOptimizer(object):
     def _refresh_slots(self):
         """the training forward layers and their masters, as the units hold them at this moment: refresh_layers_device's table"""
         slots = [s for u in self._units() for s in ((u.pw, u.K_pw), (u.dw, u.K_dw))] + [(p.conv, p.K) for p in self._projections()]
+        if self._stem is not None:                         # (block1_conv1 reads its master in place: nothing to refresh)
+            slots.append((self._stem.conv2, self._stem.K2))
         if self.reach == 'all':                            # the large-separable block's two merged convs, with their biases
             s = self.det._lsep
             slots += [(s.conv_a, s.K_a, None, s.b_a), (s.conv_b, s.K_b, None, s.b_b)]
@@ -1338,6 +1533,18 @@ class MomentumOptimizer(object):
         out[bn.name + '/moving_mean'], out[bn.name + '/moving_variance'] = bn.moving_mean, bn.moving_variance
         return out
 
+    def eval_net_stem_tensors(self):
+        """a detector built with stem_train=True: {name: device array} of the two groups refresh_eval_net hands to
+        xdet_net_refresh_stem -- both kernels' masters and the four arrays of both batch norms"""
+        s = self._stem
+        if s is None:
+            raise InvalidArgumentError(-1, 'eval_net_stem_tensors: needs a detector built with stem_train=True')
+        out = {'block1_conv1/kernel': s.K1, 'block1_conv2/kernel': s.K2}
+        for bn in self._stem_batch_norms():
+            for k in ('gamma', 'beta', 'moving_mean', 'moving_variance'):
+                out['%s/%s' % (bn.name, k)] = getattr(bn, k)
+        return out
+
     def refresh_eval_net(self):
         """Refold the native eval net's layers of the stages that are on from the masters and the training stages' moving statistics
         as the device holds them (LightHeadDetector.refresh_weights: xdet_net_refresh_weights) -> the number of layers refreshed
@@ -1347,13 +1554,18 @@ class MomentumOptimizer(object):
         xdet_net_refresh_heads first (LightHeadDetector.refresh_heads: merged, folded with eps 1e-5 and the bias b0 + b1, the two
         direct-form layers repacked) -> 74.  A net whose block is in the spectral form refuses that group by name (build the
         detector with large_sep='direct'), ahead of any launch of this call.  The RPN head and the head need nothing here: the
-        eval net and the training forward share those layers, and step has refreshed them."""
+        eval net and the training forward share those layers, and step has refreshed them.
+        A detector built with stem_train=True: both stem convs go through xdet_net_refresh_stem as well
+        (LightHeadDetector.refresh_stem) -> 74 at reach='flows', 76 at reach='all'."""
         if not hasattr(self.det, 'refresh_weights'):
             raise InvalidArgumentError(-1, 'refresh_eval_net: a PipelinedDetector is out of scope: its two nets would each need the call')
         tensors, extra = self.eval_net_tensors(), 0
         if self.reach == 'all':
             self.det.refresh_heads(self.eval_net_large_sep_tensors())
             extra = 2
+        if self._stem is not None:
+            self.det.refresh_stem(self.eval_net_stem_tensors())
+            extra += 2
         self.det.refresh_weights(tensors)
         return len(eval_net_groups(tensors)) + sum(1 for n in tensors if n.endswith('/depthwise_kernel')) + extra
 
@@ -1376,7 +1588,7 @@ class MomentumOptimizer(object):
             master, shape = self._master[v]
             out[v] = to_host(master.ptr, shape)
         lsep = STAGES[LARGE_SEP]                           # (its training forward moves its statistics too)
-        for bn in self._batch_norms() + ([getattr(self.det, lsep.attr).bn] if getattr(self.det, lsep.flag, False) else []):
+        for bn in self._stem_batch_norms() + self._batch_norms() + ([getattr(self.det, lsep.attr).bn] if getattr(self.det, lsep.flag, False) else []):
             for k in ('moving_mean', 'moving_variance'):
                 out['%s/%s' % (bn.name, k)] = to_host(getattr(bn, k).ptr, (bn.co,))
         return out
@@ -1521,4 +1733,50 @@ def host_entry_flow_backward(saved, weights, d_entry, dtype=np.float64, blocks=E
                                                                    _entry_relu_in(b, i), dtype, out)
         g = train_ops.host_add_upsample2(dy, dxs, dtype)
         out['stem' if b == blocks[0] else 'x%d' % b] = g
+    return out
+
+
+def _host_valid_conv(x, k, stride, dtype):
+    """conv(x [N,H,W,C], k [kh,kw,C,J]) at `stride`, 'VALID': one matrix product per tap, the taps added in storage order"""
+    x, k = np.asarray(x, dtype), np.asarray(k, dtype)
+    kh, kw = k.shape[:2]
+    Ho, Wo = (x.shape[1] - kh) // stride + 1, (x.shape[2] - kw) // stride + 1
+    out = np.zeros((x.shape[0], Ho, Wo, k.shape[3]), dtype)
+    for a in range(kh):
+        for b in range(kw):
+            out += np.matmul(x[:, a:a + (Ho - 1) * stride + 1:stride, b:b + (Wo - 1) * stride + 1:stride], k[a, b])
+    return out
+
+
+def host_stem_train(images_nchw, weights, dtype=np.float64):
+    """The NumPy statement of stem_train: images [N,3,S,S] and the stem's variables and moving statistics under the checkpoint's
+    names (the channel counts come from the weights) -> (stem_out, saved): relu(BN(conv(relu(BN(conv(images)))))) and a dict
+    with detector.stem_saved()'s keys -- 'x1' (the images as NHWC), 'block1_conv1/z', 'a1', 'block1_conv2/z', 'x2' (stem_out)
+    and per batch norm '/save_mean', '/save_invstd', '/moving_mean', '/moving_variance' [C] (the moving ones after
+    TensorFlow's update as train_ops.host_batch_norm_forward states it)."""
+    saved = {'x1': np.ascontiguousarray(np.transpose(np.asarray(images_nchw, dtype), (0, 2, 3, 1)))}
+    x = saved['x1']
+    for conv, stride, z, y in (('block1_conv1', 2, 'block1_conv1/z', 'a1'), ('block1_conv2', 1, 'block1_conv2/z', 'x2')):
+        saved[z] = _host_valid_conv(x, weights[conv + '/kernel'], stride, dtype)
+        x = saved[y] = np.maximum(_host_bn_forward(saved[z], weights, conv + '_bn', STEM_EPS, STEM_MOMENTUM, dtype, saved), dtype(0))
+    return x, saved
+
+
+def host_stem_backward(saved, weights, d_stem, dtype=np.float64):
+    """The NumPy statement of stem_backward(d_stem, intermediates=True): saved = what host_stem_train (or detector.stem_saved(),
+    as NumPy arrays) left, d_stem = d loss / d stem_out -> a dict with the six gradients under the checkpoint's names and in
+    its shapes, 'z/block1_conv2', 'a/block1_conv1' and 'z/block1_conv1'.  Composed of train_ops.host_batch_norm_backward and
+    train_ops.host_conv_backward_strided ('VALID'; stride 1, then stride 2 without dx): there is no image gradient."""
+    vec = lambda a: np.asarray(a, dtype).reshape(-1)
+    g, out = np.asarray(d_stem, dtype), {}
+    for conv, stride, z, y, x, dx in (('block1_conv2', 1, 'block1_conv2/z', 'x2', 'a1', 'a/block1_conv1'),
+                                      ('block1_conv1', 2, 'block1_conv1/z', 'a1', 'x1', None)):
+        bn = conv + '_bn'
+        dz, out[bn + '/gamma'], out[bn + '/beta'] = train_ops.host_batch_norm_backward(
+            saved[z], saved[y], g, weights[bn + '/gamma'], vec(saved[bn + '/save_mean']), vec(saved[bn + '/save_invstd']), True, dtype)
+        g, out[conv + '/kernel'], _ = train_ops.host_conv_backward_strided(saved[x], weights[conv + '/kernel'], dz, dtype=dtype,
+                                                                          with_dx=dx is not None, stride=stride, padding='VALID')
+        out['z/' + conv] = dz
+        if dx is not None:
+            out[dx] = g
     return out
