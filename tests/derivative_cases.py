@@ -1,5 +1,6 @@
 """The derivative check's instrument (tests/test_derivative_math.py proves it on the host statements, where the derivative is
-known; tests/test_gpu_train_derivative.py turns it on the training chain of xdet/train.py): masks, directions, the difference
+known; tests/test_gpu_train_derivative.py and tests/test_gpu_train_derivative_ends.py turn it on the training chain of
+xdet/train.py): masks, directions, the difference
 quotient, the two metrics and the list of directions.  NumPy only.
 
 For a loss L of tensors x = {name: array}, a gradient dict g claimed to be dL/dx and a mask, the direction is the masked copy
@@ -32,7 +33,8 @@ import collections
 
 import numpy as np
 
-from xdet.train import ENTRY_FLOW_VARIABLES, MIDDLE_FLOW_VARIABLES, EXIT_FLOW_VARIABLES, LARGE_SEP_VARIABLES
+from xdet.train import ENTRY_FLOW_VARIABLES, MIDDLE_FLOW_VARIABLES, EXIT_FLOW_VARIABLES, LARGE_SEP_VARIABLES, STEM_VARIABLES, \
+    RPN_HEAD_VARIABLES, HEAD_VARIABLES
 
 f64 = np.float64
 INPUT = 'stem_out'
@@ -40,8 +42,8 @@ INPUT_MASKS = ('whole', 'image 0', 'image 1', 'even pixels', 'odd pixels', 'bord
 
 Measured = collections.namedtuple('Measured', 'eta h p q q2 rho r dL L')
 # name: what the tests print; kind: 'input', 'kernels', 'gamma/beta' or 'biases' (one eta per kind); stage: 'input', 'entry',
-# 'middle', 'exit' or 'large_sep'; variables: the checkpoint names perturbed at once ((INPUT,) for an input direction); mask:
-# one of INPUT_MASKS or None
+# 'middle', 'exit' or 'large_sep' (END_DIRECTIONS: 'stem', 'rpn_head' or 'final_head'); variables: the checkpoint names
+# perturbed at once ((INPUT,) for an input direction); mask: one of INPUT_MASKS or None
 Direction = collections.namedtuple('Direction', 'name kind stage variables mask')
 
 
@@ -69,7 +71,16 @@ def variable_kinds(stage, variables):
     """one stage's variables by kind, in the order the directions are listed -> [(what, kind, names)]; every variable falls
     into exactly one"""
     ends = lambda s: tuple(v for v in variables if v.endswith(s))
-    if stage == 'large_sep':
+    if stage == 'stem':
+        # one direction per kernel: K1 goes forward through the NCHW stem kernel and backward through the stride-2 geometry on
+        # the NHWC4 image, K2 forward through an f16x3 conv layer and backward through the stride-1 'VALID' one
+        table = [(v, 'kernels', (v,)) for v in variables if v.endswith('/kernel')]
+    elif stage in ('rpn_head', 'final_head'):
+        # the layer alone, the two layers behind it that the net and the backward run as one merged layer, the three biases
+        kernels, layer = ends('/kernel'), lambda v: v.split('/')[1]
+        table = [(layer(kernels[0]) + '/kernel', 'kernels', kernels[:1]),
+                 (' + '.join(layer(k) for k in kernels[1:]) + ' kernels', 'kernels', kernels[1:]), ('biases', 'biases', ends('/bias'))]
+    elif stage == 'large_sep':
         table = [('conv2d kernels', 'kernels', ends('/conv2d/kernel')), ('conv2d_1 kernels', 'kernels', ends('/conv2d_1/kernel')),
                  ('conv2d biases', 'biases', ends('/conv2d/bias')), ('conv2d_1 biases', 'biases', ends('/conv2d_1/bias'))]
     else:
@@ -77,7 +88,8 @@ def variable_kinds(stage, variables):
         table = [('depthwise kernels', 'kernels', ends('/depthwise_kernel')), ('pointwise kernels', 'kernels', ends('/pointwise_kernel'))]
         if proj:
             table.append(('projection kernels' if len(proj) > 1 else proj[0], 'kernels', proj))
-    table += [('gamma', 'gamma/beta', ends('/gamma')), ('beta', 'gamma/beta', ends('/beta'))]
+    if stage not in ('rpn_head', 'final_head'):
+        table += [('gamma', 'gamma/beta', ends('/gamma')), ('beta', 'gamma/beta', ends('/beta'))]
     listed = [v for _, _, names in table for v in names]
     assert sorted(listed) == sorted(variables) and all(names for _, _, names in table), (stage, sorted(set(variables) ^ set(listed)))
     return table
@@ -88,6 +100,13 @@ STAGE_VARIABLES = (('entry', ENTRY_FLOW_VARIABLES), ('middle', MIDDLE_FLOW_VARIA
 DIRECTIONS = tuple(Direction('input, ' + m, 'input', 'input', (INPUT,), m) for m in INPUT_MASKS) + \
     tuple(Direction('%s, %s' % (stage, what), kind, stage, names, None)
           for stage, variables in STAGE_VARIABLES for what, kind, names in variable_kinds(stage, variables))
+
+
+# The two ends of the network, beside the list above (tests/test_gpu_train_derivative_ends.py): the stem's six variables and
+# the twelve of the two heads.  No input direction: the stem's backward returns no image gradient.
+END_STAGE_VARIABLES = (('stem', STEM_VARIABLES), ('rpn_head', RPN_HEAD_VARIABLES), ('final_head', HEAD_VARIABLES))
+END_DIRECTIONS = tuple(Direction('%s, %s' % (stage, what), kind, stage, names, None)
+                       for stage, variables in END_STAGE_VARIABLES for what, kind, names in variable_kinds(stage, variables))
 
 
 def direction(g, names, mask=None):

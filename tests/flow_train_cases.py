@@ -1,8 +1,8 @@
 """What the training-flow GPU tests share (tests/test_gpu_exit_flow_backward.py, test_gpu_middle_flow_backward.py,
-test_gpu_entry_flow_backward.py, test_gpu_train_partial_batch.py, test_gpu_train_derivative.py): the sizes of their one pass, its
-ROIs, labels, targets and anchor encodings, the chain behind the exit flow that all run, the whole training forward down to the
-scalar loss (the derivative check's instrument), and the float64 statements and metrics the forward steps are judged with.  The
-bars stay in the test files."""
+test_gpu_entry_flow_backward.py, test_gpu_train_partial_batch.py, test_gpu_train_derivative.py,
+test_gpu_train_derivative_ends.py): the sizes of their one pass, its ROIs, labels, targets and anchor encodings, the chain behind
+the exit flow that all run, the whole training forward down to the scalar loss (the derivative check's instrument), and the
+float64 statements and metrics the forward steps are judged with.  The bars stay in the test files."""
 import numpy as np
 
 import batch_norm_cases as BC
@@ -82,21 +82,24 @@ def head_and_rpn_inputs(n=2):
     return rois, labels, targets, a_l, a_t
 
 
-def downstream(out_t, mid, inputs):
+def downstream(out_t, mid, inputs, head=None, weight_grads='host'):
     """the chain behind the exit flow, on the current detector: from the training-mode `out` through the training
     large-separable block, the head loss and its backward down to d loss / d out, and from `mid` (the tensor get_rpn accepts)
     through the RPN, its loss and its backward down to the RPN's share of d loss / d mid_x
-    -> (large_sep_backward's dict, rpn_backward's dict)"""
+    -> (large_sep_backward's dict, rpn_backward's dict).  head: a dict that gains what head_backward returned (its six weight
+    gradients are kept nowhere else); weight_grads: what the three backwards are called with"""
     from xdet import model as M, losses as L
     rois, labels, targets, a_l, a_t = inputs
     feat = M.large_sep_kernel(out_t, MID, CO, True, 'channels_first', 'large_sep_feature')
     loss_func = L.HeadLoss(labels, targets, 0.25)
     M.get_head(feat, None, 7, 7, loss_func, rois, NC, True, True, 32, 'channels_first', 'final_head')
-    head = M.head_backward(loss_func, to_feat=True)
-    lsep = M.large_sep_backward(head['feat'])
+    got = M.head_backward(loss_func, to_feat=True, weight_grads=weight_grads)
+    if head is not None:
+        head.update(got)
+    lsep = M.large_sep_backward(got['feat'], weight_grads=weight_grads)
     cls, box = M.get_rpn(mid, A, False, 'channels_first', 'rpn_head')
     res = L.rpn_loss(cls, box, a_l, a_t, 256, 0.25, seed=5, keep_device=True)
-    return lsep, M.rpn_backward(res)
+    return lsep, M.rpn_backward(res, weight_grads=weight_grads)
 
 
 def forward_losses(inputs):

@@ -12,7 +12,7 @@ The sizes are the flow tests': S = 256, two images (synthetic_images(2, S, seed=
 of tests/test_gpu_entry_flow_backward.py, f16x3, head_and_rpn_inputs().  The base pass is test_gpu_train_partial_batch.one_pass;
 it gives the 158 weight gradients of the four stages and d loss / d stem_out.  26 directions (derivative_cases.DIRECTIONS), each
 four forward passes (+-h, +-2h) at a perturbed point; no backward runs there and the backward's dense copies are not touched.
-The head's and the RPN head's own twelve weight gradients are not perturbed (they live in the native net).
+The head's and the RPN head's own twelve weights and the stem's six are tests/test_gpu_train_derivative_ends.py's.
 
 How eta and BAR were fixed (measured once on an MI355X; the ladder script is not kept).  Along v = g / |g| the slope of a ReLU
 network is largest at the base point itself -- every active unit's own term of g pushes that unit further from its kink on one
