@@ -72,7 +72,8 @@ int xdet_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* syncs on
  *   feat   f32 [N,C,H,W] (feat_layout 0) or [N,H,W,ldc] (feat_layout 1, first C channels used)
  *   rois   f32 [N,R,4] (cy,cx,h,w) -- or corner boxes when rois_are_corners != 0, in which case
  *          _point2center (net/xception_body.py:215-218) is applied on the fly
- *   pooled f32 [N,R,out_ld] (first C = gh*gw*bank entries per ROI, = [N,R,gh*gw,bank] when out_ld == C)
+ *   pooled f32 [N,R,out_ld] (first C = gh*gw*bank entries per ROI, = [N,R,gh*gw,bank] when out_ld == C; the entries
+ *          [C, out_ld) of every row are set to 0, in `index` too: a consumer that reads whole rows finds no stale bytes)
  *   index  i32 same shape, may be NULL.  Degenerate ROI: pooled 0 and index 0.
  * Errors: same argument checks as PSROIAlignOp::Compute (:209-226) -> XDET_ERR_INVALID_ARG. */
 int xdet_psroialign_fwd(const float* feat, const float* rois, float* pooled, int32_t* index, int N, int C, int H,

@@ -3,9 +3,9 @@
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from oracle_compare import TOL, rel_err, match_detections, explain_proposal_mismatch
 
-TOL = 1e-3
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope='module', params=['f32', 'f16x3', 'f16x3+spectral'])
@@ -28,10 +28,6 @@ def run(request, oracle, lh_weights):
     trace = {}
     ref = oracle.lighthead_forward(imgs, lh_weights, rpn_post_nms_top_n=300, trace=trace)
     return det, got, ref, trace, imgs
-
-
-def rel_err(a, b):
-    return float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max()))
 
 
 def test_dense_stages(run):
@@ -90,28 +86,6 @@ def test_predictions_dict(run, oracle):
             top2 = np.sort(prob[i, j], -1)[..., -2:]
             assert np.all((top2[..., 1] - top2[..., 0])[diff] < TOL), 'arg-max class differs without a tie'
     assert (pred['classes'] > 0).sum() > 0     # some ROI is not background
-
-
-def match_detections(got, ref, tol=TOL):
-    """set matching per class: every oracle detection needs a distinct GPU detection whose score
-    and box agree within tol (two detections whose scores differ by float noise may legitimately
-    swap places in the score-ordered output)."""
-    total = matched = extra = 0
-    for c in ref:
-        gs, gb = got[c]
-        rs, rb = ref[c]
-        kg, kr = int((gs > 0).sum()), int((rs > 0).sum())
-        assert np.all(gs[kg:] == 0) and np.all(gb[kg:] == 0)            # zero padding
-        used = np.zeros(kg, bool)
-        for j in range(kr):
-            d = np.maximum(np.abs(gs[:kg] - rs[j]), np.abs(gb[:kg] - rb[j]).max(1)) if kg else np.array([])
-            d = np.where(used, np.inf, d)
-            if kg and d.min() < tol:
-                used[int(d.argmin())] = True
-                matched += 1
-        total += kr
-        extra += kg - int(used.sum())
-    return total, matched, extra
 
 
 def iou(a, b):
@@ -267,22 +241,6 @@ def test_other_baseline_configs(size, R, lsep, oracle, lh_weights):
         assert matched == total and extra == 0, (matched, total, extra)
     else:       # one flipped keep/suppress decision changes a handful of head inputs
         assert matched >= total - max(2, total // 50) and extra <= max(2, total // 50)
-
-
-def explain_proposal_mismatch(oracle, tr, gpu_props):
-    """A proposal set may differ from the oracle's ONLY through an NMS decision that sits on the 0.7 threshold:
-    a GPU-only box must have, among the oracle's proposals, a partner whose IoU with it is within 1e-5 of the
-    threshold (the suppressor that won on one side and lost on the other).  Anything else is a real bug."""
-    ref = tr['proposals'][0]
-    d = np.abs(gpu_props[:, None, :] - ref[None, :, :]).max(-1)
-    only_gpu = gpu_props[d.min(1) >= TOL]
-    assert 0 < len(only_gpu) <= 3, len(only_gpu)
-    for b in only_gpu:
-        both = np.concatenate([b[None], ref])
-        ious = np.array([oracle.iou_tf(both, 0, j) for j in range(1, len(both))])
-        near = np.abs(ious - 0.7).min()
-        print('  GPU-only proposal %s: closest oracle-side IoU to the 0.7 threshold: |IoU - 0.7| = %.2e' % (b, near))
-        assert near < 1e-5, near
 
 
 def test_net_misuse_is_reported_not_executed(lh_weights):

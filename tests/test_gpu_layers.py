@@ -1,5 +1,7 @@
 """Dense / window kernels on the GPU vs the oracle's restatement of the tf.layers semantics.
 Tolerance: exact-f32 MFMA differs from BLAS only by summation order -> 2e-5 of the output scale."""
+import zlib
+
 import numpy as np
 import pytest
 
@@ -40,7 +42,7 @@ def test_conv_matches_oracle(case, oracle, precision):
     from xdet.ops import Conv2D
     from xdet.runtime import DeviceTensor
     N, H, W, cin, cout, kh, kw, stride, padding, dil = case
-    rng = np.random.default_rng(hash(case) % (2 ** 31))
+    rng = np.random.default_rng(zlib.crc32(repr(case).encode()))
     x = rng.standard_normal((N, H, W, cin)).astype(np.float32)
     k = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)
@@ -414,7 +416,7 @@ def test_ksplit_modes_are_bit_identical_and_match_the_plain_kernel(case, prec, o
     from xdet.ops import Conv2D
     from xdet.runtime import DeviceTensor, set_precision
     N, H, W, cin, cout, kh, kw, stride, padding = case
-    rng = np.random.default_rng(abs(hash(case)) % (2 ** 31))
+    rng = np.random.default_rng(zlib.crc32(repr(case).encode()))
     x = rng.standard_normal((N, H, W, cin)).astype(np.float32)
     k = (rng.standard_normal((kh, kw, cin, cout)) / np.sqrt(kh * kw * cin)).astype(np.float32)
     scale = rng.uniform(0.5, 1.5, cout).astype(np.float32)

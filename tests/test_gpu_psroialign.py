@@ -107,6 +107,32 @@ def test_nhwc_bank10_form_bit_exact(method, shape, corners, oracle):
     assert np.array_equal(to_host(d_pool2.ptr, (n, r, gh * gw, 10), np.float32), po)
 
 
+@pytest.mark.parametrize('method', ['max', 'mean'])
+@pytest.mark.parametrize('r', [9, 2100])
+def test_padded_output_rows_get_their_pad_written(method, r, oracle):
+    """The net's `pooled` tensor: 490 channels at a row stride of 512, in a workspace block that held another tensor
+    before.  The dense layer behind reads all 512 entries of a row (the last 22 against zero weights), so the op must
+    write them: rows [C, out_ld) of both outputs are 0 over NaN bits, next to bit-exact values -- for ordinary and for
+    degenerate ROIs (random_rois has two), with one ROI per workgroup (18 ROIs) and with four (more than 2048)."""
+    from xdet._lib import lib, check
+    from xdet.runtime import to_device, to_host
+    n, h, w, g = 2, 4, 4, 7
+    c, ld = 10 * g * g, 512
+    rng = np.random.default_rng(r)
+    feat = rng.standard_normal((n, c, h, w)).astype(np.float32)
+    rois = random_rois(rng, n, r)
+    po, io = oracle.ps_roi_align(feat, rois, g, g, method)
+    nhwc = np.zeros((n, h, w, ld), np.float32)
+    nhwc[..., :c] = np.transpose(feat, (0, 2, 3, 1))
+    nan = np.full((n, r, ld), np.nan, np.float32)
+    d_in, d_roi, d_pool, d_idx = to_device(nhwc), to_device(rois), to_device(nan), to_device(nan.view(np.int32))
+    check(lib().xdet_psroialign_fwd(d_in.ptr, d_roi.ptr, d_pool.ptr, d_idx.ptr, n, c, h, w, r, g, g,
+                                    1 if method == 'max' else 0, 1, ld, ld, 0, None))
+    p, i = to_host(d_pool.ptr, (n, r, ld), np.float32), to_host(d_idx.ptr, (n, r, ld), np.int32)
+    assert np.array_equal(p[..., :c].reshape(po.shape), po) and np.array_equal(i[..., :c].reshape(io.shape), io)
+    assert np.all(p[..., c:] == 0) and np.all(i[..., c:] == 0), int(np.isnan(p[..., c:]).sum())
+
+
 def test_empty_and_errors():
     import xdet
     feat = np.zeros((1, 8, 4, 4), np.float32)

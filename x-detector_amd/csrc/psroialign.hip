@@ -149,6 +149,12 @@ __global__ __launch_bounds__(256, 4) void psroialign_fwd_kernel(const float* __r
   }
   float* prow = pooled + nr * out_ld;
   int32_t* irow = index ? index + nr * out_ld : nullptr;
+  // A row with a padded channel stride gets its pad from its producer, like every NHWC tensor of a plan: the dense layer
+  // behind reads all out_ld entries (against zero weights), and a recycled workspace block holds another tensor's bytes.
+  for (int e = C + e_first; e < out_ld; e += e_step) {
+    prow[e] = 0.f;
+    if (irow) irow[e] = 0;
+  }
 
   if (r2 < FLT_MIN || r3 < FLT_MIN) {   // degenerate ROI: zero (reference leaves the index unwritten)
     for (int e = e_first; e < C; e += e_step) {

@@ -26,7 +26,7 @@ class LightHeadDetector(object):
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
                  pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
-                 entry_flow_train=False, stem_train=False):
+                 entry_flow_train=False, stem_train=False, keep=()):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -71,7 +71,9 @@ class LightHeadDetector(object):
         tensors a training forward saves (z1, a1, z2), the three gradient tensors of the backward and the workspaces, all sized
         for max_batch: model.stem_train() recomputes `stem_out` from the images with batch statistics, model.stem_backward
         takes the gradient from `stem_out` down to both kernels.  With it MomentumOptimizer steps the whole network.  The
-        default detector allocates and runs none of this."""
+        default detector allocates and runs none of this.
+        keep=('stem_out', 'entry_x'): the eval body keeps these tensors as named buffers (the options the training stages
+        set for themselves) without any training state -- for looking at the entry flow stage by stage."""
         stages = (large_sep_train, exit_flow_train, middle_flow_train, entry_flow_train)
         _train.check_stages(stages, weights)
         _train.check_stem(stem_train, entry_flow_train, weights)
@@ -112,9 +114,11 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'pool_index', b'keep'))
         if rpn_hidden:
             check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
-        if middle_flow_train:
+        if set(keep) - {'stem_out', 'entry_x'}:
+            raise InvalidArgumentError(-1, 'keep: %r is not one of stem_out, entry_x' % (sorted(set(keep) - {'stem_out', 'entry_x'}),))
+        if middle_flow_train or 'entry_x' in keep:
             check(lib().xdet_net_set_option(self.handle, b'entry_x', b'keep'))
-        if entry_flow_train:
+        if entry_flow_train or 'stem_out' in keep:
             check(lib().xdet_net_set_option(self.handle, b'stem_out', b'keep'))
         self.pool_index, self.rpn_hidden = bool(pool_index), bool(rpn_hidden)
         check(lib().xdet_net_build(self.handle))
