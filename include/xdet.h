@@ -915,6 +915,24 @@ int xdet_momentum_step(const xdet_momentum_slot* slots_host, int n_slots, float 
  * vouches for kh * kw * cin * cout floats.  Afterwards the layer's host copy of the scale is stale: a later activation
  * exponent (a plan's calibration) is refused for this layer. */
 int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const float* shift_dev, void* stream);
+/* The same for a spectral conv layer (xdet_spectral_conv_create, or the two a net owns): every operand buffer of its per-bin
+ * GEMM layer from a dense f32 [taps][cin][cout] kernel in device memory, in place.  The layer keeps its kernel as the real block
+ * matrices [L/2][2 round_up(cin,32)][2 round_up(cout,32)] of the DFT domain; an element of them is one function of the dense
+ * kernel and a table of L/2 x taps cosines and sines (csrc/spectral_weights.h: a double accumulator over the taps in ascending
+ * order, every product and sum rounded on its own, one conversion to f32), which the host evaluates at creation and the two
+ * repack passes of csrc/conv_repack.hip evaluate per element here, from the layer's device copy of the table.  So each buffer
+ * holds exactly what xdet_spectral_conv_create would have made from the same values -- padding rows and columns +0, the sign of
+ * a zero included -- and no array of the block matrices' size is allocated: the call needs the layer's own buffers only.
+ * An activation exponent e the GEMM layer carries (a net's calibration) is honoured as by xdet_layers_refresh_device: the
+ * epilogue scale ends as 2^-shift of the row times 2^e, exact.  scale_dev / shift_dev (f32 [cout] in device memory; NULL: kept)
+ * replace the scale and shift of the inverse transform's epilogue, out = relu?(y * scale + shift); channels past cout stay +0.
+ * Two passes over the bins on `stream` (and one small launch for scale / shift), no synchronisation, nothing read on the host.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work and with the layer unchanged: a NULL layer, a NULL kernel, a handle that
+ * is not a spectral conv layer.  The shape is the layer's: the caller vouches for taps * cin * cout floats.  Afterwards the
+ * GEMM layer's host copy of the epilogue scale is stale, as after xdet_conv_set_kernel_device (a net brings it back in line in
+ * xdet_net_refresh_heads). */
+int xdet_spectral_conv_set_kernel_device(void* layer, const float* kernel_dev, const float* scale_dev, const float* shift_dev,
+                                         void* stream);
 /* The same for a depthwise layer (xdet_depthwise_create): its taps [9][round_up(C,32)] from a dense f32 [3,3,C,1] kernel in
  * device memory, padding channels +0.  Errors: a NULL kernel, a layer whose taps carry an activation pre-scale. */
 int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream);
@@ -1058,6 +1076,9 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   domain of the convolved axis (one GEMM per frequency bin, ~5x fewer MFMA FLOPs; needs a split-precision
  *   mode and a 16/30/50 feature map); auto = spectral whenever those hold, else direct.
  *   The choice is per net, never per call: results do not depend on the batch an image arrives in.
+ *   "spectral_refresh" = "off" | "on": a net whose block is in the spectral form keeps pointers to its two spectral layers, and
+ *   xdet_net_refresh_heads takes the large_sep_feature group through xdet_spectral_conv_set_kernel_device (on), or refuses
+ *   that group on such a net (off, the default).  No effect on a net in the direct form, and none on any forward.
  *   "sepconv" = "fused" | "split": entry-flow separable blocks as one kernel (default) or depthwise + pointwise.
  *   "rpn_stream" = "side" | "main": the RPN / proposal branch forks onto a side stream under the large-separable
  *   convs (default) or stays on the caller's stream (per-kernel profiles without cross-stream sharing).
@@ -1188,16 +1209,20 @@ int xdet_net_refresh_weights(void* net, const xdet_net_weight_dev* table_host, i
  *   large_sep_feature: the eight conv tensors of Branch_0 and Branch_1 and batch_normalization/{gamma, beta, moving_mean,
  *                      moving_variance}: the branches merged as the plan merges them when it is built (K_a, b_a, K_b), the
  *                      bias b0 + b1 (xdet_add_rows on one row), xdet_bn_fold with eps 1e-5 and that bias, then the two
- *                      direct-form layers.
+ *                      direct-form layers -- or, on a net in the spectral form built with the option spectral_refresh=on, the
+ *                      same merges, sum and fold into the same scratch, then xdet_spectral_conv_set_kernel_device on the
+ *                      (15,1) layer with K_a and shift b_a and on the (1,15) layer with K_b and the folded scale and shift,
+ *                      each at its GEMM layer's own activation exponent.
  * The merges are one xdet_tensors_concat table into scratch the net owns (one block at the first call: the two table doors'
  * workspaces and every merged tensor but the large-separable kernels, which are a second block at the first call that names
  * that group; xdet_net_memory reports both), then one xdet_layers_refresh_device table over the touched layers on `stream`,
  * one synchronisation, and the host bookkeeping of xdet_net_refresh_weights: every touched layer's host copy of the epilogue
- * scale is read back and the layers accept an activation exponent again.  Exponents and captured graphs stay.
+ * scale is read back (of a spectral layer's GEMM layer: every bin's rows) and the layers accept an activation exponent again.
+ * Exponents and captured graphs stay.
  * Errors -> XDET_ERR_INVALID_ARG, by name, before any GPU work and with no layer touched: a name outside the three groups (the
  * body's variables among them), a group given in part, a name given twice, a NULL pointer, an empty table, a net that is not
- * built, and a large_sep_feature group on a net whose block is in the spectral form (build it with the option
- * large_sep=direct): a spectral layer keeps its kernel as DFT-domain block matrices. */
+ * built, and a large_sep_feature group on a net whose block is in the spectral form and that was built without the option
+ * spectral_refresh=on (build it with that option, or with large_sep=direct). */
 int xdet_net_refresh_heads(void* net, const xdet_net_weight_dev* table_host, int n, void* stream);
 /* The same for the stem, the last layers outside the two doors above: the same table, two groups, each taken whole only --
  *   block1_conv1: block1_conv1/kernel [3,3,3,32] and block1_conv1_bn/{gamma, beta, moving_mean, moving_variance};

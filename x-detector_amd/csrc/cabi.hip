@@ -528,6 +528,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->large_sep_mode = v == "auto" ? 0 : v == "direct" ? 1 : 2;
     return XDET_OK;
   }
+  if (k == "spectral_refresh") {
+    XDET_REQUIRE(v == "on" || v == "off", "spectral_refresh must be on | off");
+    n->spectral_refresh = v == "on";
+    return XDET_OK;
+  }
   if (k == "rpn_stream") {
     XDET_REQUIRE(v == "side" || v == "main", "rpn_stream must be side | main");
     n->rpn_side_stream = v == "side";

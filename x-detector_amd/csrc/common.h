@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/xdet.h"   // XDET_OK / XDET_ERR_* codes
 #include "conv_params.h"   // struct ConvParams: what every MFMA conv kernel is launched with
+#include "spectral_weights.h"   // the spectral convs' transform length, host tables and block-matrix element
 #include "workspace.h"     // WsWalk, ws_measure / ws_carve: how a caller-owned workspace is sized and handed out
 #include <atomic>
 #include <cstdint>
@@ -114,14 +115,8 @@ int launch_depthwise3x3_split(const float* in, const float* w9c, unsigned short*
                               int H, int W, int C, int ld, int dil, int relu_in, hipStream_t s, int x8 = 0, int x8_exp = 0);
 
 // ---- spectral large-separable conv: DFT passes around the grouped GEMM (spectral.hip) ----
+// (spectral_weights.h: the transform length spectral_points(F), the host tables and the block matrices' element function)
 bool spectral_supported(int F);
-// Transform length of an F-long axis: the smallest even L >= F + 7 (spectral.hip's header has the argument), sized for
-// the longest kernel SpectralConv::init admits.  The host tables, the block matrices and the kernels' instantiations
-// all take it from here.
-constexpr int kSpectralMaxTaps = 15;
-constexpr int spectral_points(int F) { return (F + kSpectralMaxTaps / 2 + 1) / 2 * 2; }
-void spectral_tables(int F, std::vector<float>* fwd, std::vector<float>* inv);
-void spectral_weights(const float* w, int T, int cin, int cout, int cin_ld, int cout_ld, int F, std::vector<float>* out);
 int launch_dft_fwd(const float* in, int F, int ld, int axis, int N, int m_pad, const float* tab, unsigned short* hi,
                    unsigned short* lo, hipStream_t s);
 int launch_dft_inv(const float* Y, int F, int ldn, int C_ld, int N, int m_pad, const float* tab, const float* scale,

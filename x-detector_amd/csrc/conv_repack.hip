@@ -6,6 +6,8 @@
 // DepthwiseLayer::init's padded host copy, restated in five lines.  The table door, xdet_layers_refresh_device, runs the same
 // per-tile device code over any number of layers in a fixed number of launches (a tile -> slot table in the workspace), and
 // xdet_bn_fold makes a net-owned layer's epilogue scale and shift from the four arrays of its batch norm on the device.
+// xdet_spectral_conv_set_kernel_device refreshes the grouped layer of a spectral conv by the same two passes, their source the
+// block matrices' element function (spectral_weights.h) instead of a load: the tile code takes its source as a template argument.
 //
 // The repack makes two passes over the kernel [kh*kw][cin][cout] (a row of the transposed matrix, kh*kw*cin_p values of one
 // output channel strided by cout, does not fit in LDS for the 15x1 convs): the largest |w| per output channel (an integer
@@ -39,20 +41,36 @@ struct ConvRepack {
   int first_tile, tiles_x;              // the slot's tiles are first_tile + by * tiles_x + bx
 };
 
-// the value of row co, column k of group g's padded [cout_pad][kp] matrix: k = tap * cin_p + ci
-__device__ __forceinline__ float repack_source(const ConvRepack& a, int g, int co, int k) {
-  const int tap = k / a.cin_p, ci = k - tap * a.cin_p;
-  return (tap < a.taps && ci < a.cin && co < a.cout) ? a.w[(((size_t)g * a.taps + tap) * a.cin + ci) * a.cout + co] : 0.f;
-}
+// Where a tile's values come from: the value of row co, column k of group g's padded [cout_pad][kp] matrix.  The tile code
+// below takes the source as a template argument and shares every line behind the fetch.
+// A conv layer: a load from the dense kernel, k = tap * cin_p + ci
+struct DenseSource {
+  __device__ __forceinline__ float operator()(const ConvRepack& a, int g, int co, int k) const {
+    const int tap = k / a.cin_p, ci = k - tap * a.cin_p;
+    return (tap < a.taps && ci < a.cin && co < a.cout) ? a.w[(((size_t)g * a.taps + tap) * a.cin + ci) * a.cout + co] : 0.f;
+  }
+};
+// The grouped layer of a spectral conv: group g is frequency bin g, and the value is spectral_weight_element of the dense
+// [T][cin][cout] kernel and the layer's twiddle table (doubles; a bin's 2 T coefficients are uniform over a workgroup).  A
+// tile's 64 threads of one k read 64 neighbouring output channels of each tap: along cout, as the dense source does.
+struct SpectralSource {
+  const float* w;                       // [T][cin][cout] dense
+  const double *cr, *ci;                // [NB][T] each
+  int T, cin, cout, cin_ld, cout_ld;
+  __device__ __forceinline__ float operator()(const ConvRepack&, int g, int co, int k) const {
+    return spectral_weight_element(w, cr, ci, T, cin, cout, cin_ld, cout_ld, g, k, co);
+  }
+};
 
-__device__ __forceinline__ void repack_max_tile(const ConvRepack& a, int bx, int by, int g) {
+template <class Source>
+__device__ __forceinline__ void repack_max_tile(const ConvRepack& a, const Source& source, int bx, int by, int g) {
   const int co = bx * RP_CO + (threadIdx.x & (RP_CO - 1));
   const int k0 = by * RP_K + (threadIdx.x / RP_CO) * (RP_K / 4);
   if (co >= a.cout) return;
   float m = 0.f;
 #pragma unroll
   for (int i = 0; i < RP_K / 4; ++i) {
-    const float f = fabsf(repack_source(a, g, co, k0 + i));
+    const float f = fabsf(source(a, g, co, k0 + i));
     m = m < f ? f : m;                  // (std::max's own comparison: a NaN never becomes the maximum)
   }
   if (m > 0.f) atomicMax(a.mx + (size_t)g * a.cout_pad + co, __float_as_uint(m));
@@ -67,13 +85,15 @@ __device__ __forceinline__ float repack_scale0(const ConvRepack& a, float* keep,
   return s;
 }
 
-__device__ __forceinline__ void repack_tile(const ConvRepack& a, int precision, int bx, int kb, int g, float (*tile)[RP_CO + 1]) {
+template <class Source>
+__device__ __forceinline__ void repack_tile(const ConvRepack& a, const Source& source, int precision, int bx, int kb, int g,
+                                            float (*tile)[RP_CO + 1]) {
   const int tid = threadIdx.x;
   const int co0 = bx * RP_CO;
   {
     const int c = tid & (RP_CO - 1), kq = tid / RP_CO;
 #pragma unroll
-    for (int i = 0; i < RP_K / 4; ++i) tile[kq * (RP_K / 4) + i][c] = repack_source(a, g, co0 + c, kb * RP_K + kq * (RP_K / 4) + i);
+    for (int i = 0; i < RP_K / 4; ++i) tile[kq * (RP_K / 4) + i][c] = source(a, g, co0 + c, kb * RP_K + kq * (RP_K / 4) + i);
   }
   __syncthreads();
   const int c = tid >> 2, q = tid & 3;                      // output row co0 + c, columns kb * 32 + q * 8 .. + 7
@@ -133,11 +153,32 @@ __device__ __forceinline__ void repack_tile(const ConvRepack& a, int precision, 
 }
 
 // one layer per launch: ConvLayer::init and xdet_conv_set_kernel_device
-__global__ __launch_bounds__(RP_T) void conv_repack_max_kernel(ConvRepack a) { repack_max_tile(a, blockIdx.x, blockIdx.y, blockIdx.z); }
+__global__ __launch_bounds__(RP_T) void conv_repack_max_kernel(ConvRepack a) {
+  repack_max_tile(a, DenseSource(), blockIdx.x, blockIdx.y, blockIdx.z);
+}
 
 __global__ __launch_bounds__(RP_T) void conv_repack_kernel(ConvRepack a, int precision) {
   __shared__ float tile[RP_K][RP_CO + 1];
-  repack_tile(a, precision, blockIdx.x, blockIdx.y, blockIdx.z, tile);
+  repack_tile(a, DenseSource(), precision, blockIdx.x, blockIdx.y, blockIdx.z, tile);
+}
+
+// the grouped layer of a spectral conv, one bin per blockIdx.z (SpectralConv::set_kernel_device)
+__global__ __launch_bounds__(RP_T) void spectral_repack_max_kernel(ConvRepack a, SpectralSource src) {
+  repack_max_tile(a, src, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+__global__ __launch_bounds__(RP_T) void spectral_repack_kernel(ConvRepack a, SpectralSource src, int precision) {
+  __shared__ float tile[RP_K][RP_CO + 1];
+  repack_tile(a, src, precision, blockIdx.x, blockIdx.y, blockIdx.z, tile);
+}
+
+// the inverse pass's arrays [cout_ld] from dense [cout] ones (NULL: kept); channels past cout stay +0
+__global__ __launch_bounds__(256) void spectral_epilogue_kernel(const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                int cout, float* __restrict__ d_scale, float* __restrict__ d_shift) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cout) return;
+  if (scale) d_scale[c] = scale[c];
+  if (shift) d_shift[c] = shift[c];
 }
 
 // a table of layers per launch (xdet_layers_refresh_device): workgroup b works on tile b - first_tile of slot tile_slot[b]
@@ -145,14 +186,14 @@ __global__ __launch_bounds__(RP_T) void conv_repack_max_table_kernel(const ConvR
   const ConvRepack a = slots[tile_slot[blockIdx.x]];
   if (a.precision == PREC_F32) return;
   const int t = (int)blockIdx.x - a.first_tile;
-  repack_max_tile(a, t % a.tiles_x, t / a.tiles_x, 0);
+  repack_max_tile(a, DenseSource(), t % a.tiles_x, t / a.tiles_x, 0);
 }
 
 __global__ __launch_bounds__(RP_T) void conv_repack_table_kernel(const ConvRepack* __restrict__ slots, const int* __restrict__ tile_slot) {
   __shared__ float tile[RP_K][RP_CO + 1];
   const ConvRepack a = slots[tile_slot[blockIdx.x]];
   const int t = (int)blockIdx.x - a.first_tile;
-  repack_tile(a, a.precision, t % a.tiles_x, t / a.tiles_x, 0, tile);
+  repack_tile(a, DenseSource(), a.precision, t % a.tiles_x, t / a.tiles_x, 0, tile);
 }
 
 // every operand buffer of L from the dense kernel w (device memory); shift NULL: d_shift stays as it is
@@ -246,6 +287,32 @@ int ConvLayer::set_kernel_device(const float* k_hwio, const float* shift, hipStr
                "net-owned layer): its scale arrays are not the ones it was created with");
   host_stale = true;
   return launch_conv_repack(*this, k_hwio, shift, s);
+}
+
+// The refresh of a spectral conv (layers.h): G's row maxima, then exponent, split and scatter, both passes fed by
+// spectral_weight_element instead of a dense matrix -- no buffer of the block matrices' size exists at any time.  What the call
+// reads beyond the layer's operand buffers: the dense kernel, the twiddle table, and the row-maxima scratch G owns.
+int SpectralConv::set_kernel_device(const float* w, const float* scale, const float* shift, hipStream_t s) {
+  XDET_REQUIRE(w, "spectral_conv_set_kernel_device: kernel is NULL");
+  XDET_REQUIRE(G.groups == NB && G.precision != PREC_F32 && G.cout_pad == 2 * cout_ld && G.kp == 2 * cin_ld && G.cout_pad % RP_CO == 0 &&
+                   G.kp % RP_K == 0 && d_tw,
+               "spectral_conv_set_kernel_device: unexpected padding");
+  ConvRepack a = conv_repack_args(G, nullptr, nullptr);
+  a.in_exp = G.in_exp;
+  const SpectralSource src = {w, d_tw.get(), d_tw.get() + (size_t)NB * T, T, cin, cout, cin_ld, cout_ld};
+  const dim3 grid((unsigned)(a.cout_pad / RP_CO), (unsigned)(a.kp / RP_K), (unsigned)NB);
+  G.host_stale = true;
+  XDET_HIP(hipMemsetAsync(a.mx, 0, (size_t)NB * a.cout_pad * sizeof(unsigned), s));
+  hipLaunchKernelGGL(spectral_repack_max_kernel, grid, dim3(RP_T), 0, s, a, src);
+  XDET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(spectral_repack_kernel, grid, dim3(RP_T), 0, s, a, src, G.precision);
+  XDET_LAUNCH_CHECK();
+  if (scale || shift) {
+    hipLaunchKernelGGL(spectral_epilogue_kernel, dim3((unsigned)cdiv(cout, 256)), dim3(256), 0, s, scale, shift, cout, d_scale.get(),
+                       d_shift.get());
+    XDET_LAUNCH_CHECK();
+  }
+  return XDET_OK;
 }
 
 // tap i of the padded [9][ld] taps from the dense [3,3,C,1] kernel; e: the layer's activation exponent (set_out_exp: taps 2^-e)
@@ -362,6 +429,14 @@ int xdet_conv_set_kernel_device(void* layer, const float* kernel_hwio_dev, const
   XDET_REQUIRE(b->kind == 1, "conv_set_kernel_device: a spectral layer keeps its kernel as DFT-domain block matrices");
   DeviceGuard guard(b->device);
   return static_cast<ConvLayer*>(b)->set_kernel_device(kernel_hwio_dev, shift_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+int xdet_spectral_conv_set_kernel_device(void* layer, const float* kernel_dev, const float* scale_dev, const float* shift_dev,
+                                         void* stream) {
+  LayerBase* b = static_cast<LayerBase*>(layer);
+  XDET_REQUIRE(b && b->kind == 3, "spectral_conv_set_kernel_device: not a spectral conv layer");
+  DeviceGuard guard(b->device);
+  return static_cast<SpectralConv*>(b)->set_kernel_device(kernel_dev, scale_dev, shift_dev, reinterpret_cast<hipStream_t>(stream));
 }
 
 int xdet_depthwise_set_kernel_device(void* layer, const float* k33c1_dev, void* stream) {

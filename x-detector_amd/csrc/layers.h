@@ -281,8 +281,9 @@ struct ConvLayer : LayerBase {
 // caller: split planes x_hi / x_lo of planes_halves(N) halves each and the f32 products y of y_floats(N) floats
 // (+ 512 bytes of slack each).  The three passes are separate members so that a plan can time them as three ops.
 struct SpectralConv : LayerBase {
-  int F = 0, NB = 0, axis = 0, cin = 0, cin_ld = 0, cout = 0, cout_ld = 0, relu = 0;
+  int F = 0, NB = 0, T = 0, axis = 0, cin = 0, cin_ld = 0, cout = 0, cout_ld = 0, relu = 0;
   ConvLayer G;                           // [NB] groups of [2 cin_ld x 2 cout_ld] real block matrices
+  DevMem<double> d_tw;                   // the twiddle table of spectral_weights.h: cr [NB][T], then ci [NB][T]
   Pow2Scaled tab_fwd;                    // the forward table carries the operand planes' activation pre-scale 2^-e
   DevMem<float> d_tf, d_ti, d_scale, d_shift;
   // rows per bin at a batch of N: whole 256-row GEMM tiles; a single image or two (N*F <= 128) get the 128-row tile instead
@@ -291,13 +292,13 @@ struct SpectralConv : LayerBase {
   size_t planes_halves(int N) const { return (size_t)NB * m_pad(N) * 2 * cin_ld; }
   size_t y_floats(int N) const { return (size_t)NB * m_pad(N) * 2 * cout_ld; }
   // w: [T][cin][cout] (the taps along `axis`: 0 = y, 1 = x); scale / shift: [cout] or NULL (ones / zeros)
-  int init(const float* w, int T, int cin_, int cout_, int axis_, int F_, const float* scale, const float* shift, int relu_) {
-    XDET_REQUIRE(w && T > 0 && T % 2 == 1 && T <= kSpectralMaxTaps && cin_ > 0 && cout_ > 0 && (axis_ == 0 || axis_ == 1),
+  int init(const float* w, int T_, int cin_, int cout_, int axis_, int F_, const float* scale, const float* shift, int relu_) {
+    XDET_REQUIRE(w && T_ > 0 && T_ % 2 == 1 && T_ <= kSpectralMaxTaps && cin_ > 0 && cout_ > 0 && (axis_ == 0 || axis_ == 1),
                  "spectral conv: an odd number of taps (<= 15) along axis 0 | 1");
     XDET_REQUIRE(spectral_supported(F_), "spectral conv: the feature-map side must be 16, 30 or 50");
     XDET_REQUIRE(g_default_precision != PREC_F32, "spectral conv: needs a split-precision mode");
     kind = 3;
-    F = F_; NB = spectral_points(F) / 2; axis = axis_; relu = relu_;
+    F = F_; NB = spectral_points(F) / 2; T = T_; axis = axis_; relu = relu_;
     cin = cin_; cin_ld = round_up(cin, 32); cout = cout_; cout_ld = round_up(cout, 32);
     {
       std::vector<float> wb;
@@ -305,6 +306,12 @@ struct SpectralConv : LayerBase {
       XDET_TRY(G.init(1, 1, 2 * cin_ld, 2 * cout_ld, 1, 1, 0, 0, 0, wb.data(), nullptr, nullptr, 0, NB));
     }
     device = G.device;
+    {
+      std::vector<double> cr, ci;        // what set_kernel_device evaluates the block matrices from, on the device
+      spectral_twiddles(T, F, &cr, &ci);
+      cr.insert(cr.end(), ci.begin(), ci.end());
+      XDET_TRY(d_tw.upload(cr.data(), cr.size()));
+    }
     std::vector<float> ti, sc(cout_ld, 0.f), sh(cout_ld, 0.f);
     spectral_tables(F, &tab_fwd.host, &ti);
     for (int c = 0; c < cout; ++c) { sc[c] = scale ? scale[c] : 1.f; sh[c] = shift ? shift[c] : 0.f; }
@@ -315,6 +322,11 @@ struct SpectralConv : LayerBase {
     tab_fwd.dev = d_tf;
     return XDET_OK;
   }
+  // Every operand buffer of G from a dense [T][cin][cout] kernel in device memory, in place (conv_repack.hip): the two passes
+  // of the conv repack with spectral_weight_element as their source, at G's own activation exponent -- G then holds what
+  // init() followed by set_in_exp(G.in_exp) would have made of the same values.  scale / shift: dense [cout] device arrays
+  // that replace the inverse pass's d_scale / d_shift (NULL: kept).  No synchronisation; G.in_scale.host is stale afterwards.
+  int set_kernel_device(const float* w, const float* scale, const float* shift, hipStream_t s);
   // the forward transform is linear: 2^-e rides in its table and 2^e in the per-bin GEMM's epilogue scale
   int set_in_exp(int e) {
     XDET_TRY(tab_fwd.upload(-e));

@@ -32,6 +32,7 @@ struct LightHeadNet : Plan {
   int fmap = 0, n_anchor = 0;
   int large_sep_mode = 0;               // 0 = auto, 1 = direct (15,1)/(1,15) convs, 2 = spectral (DFT-domain GEMMs)
   bool large_sep_spectral = false;      // decided at build
+  bool spectral_refresh = false;        // option "spectral_refresh" = "off" | "on": refresh_heads takes the large_sep_feature group on a spectral block
   bool rpn_side_stream = true;          // option "rpn_stream" = "side" | "main"
   bool check_range = false;             // option "check_range" = "off" | "on": validate every activation against the f16 range
   bool latency_ksplit = true;           // option "ksplit" = "on" | "off" | "all": fixed split-K for the narrow head GEMM (on),
@@ -169,9 +170,11 @@ struct LightHeadNet : Plan {
   static constexpr float stem_eps = 1e-4f;          // net/xception_body.py:20
   // xdet_net_refresh_heads: the layers the plan owns -- the RPN head's two, the head's two dense layers and (direct form) the
   // large-separable block's two -- from the checkpoint's tensors in device memory.  hd_*: the layers, set by the builders
-  // (hd_lsep stays NULL in the spectral form); hs, hs_k: the merges' scratch, allocated at the first call (that names the block)
+  // (hd_lsep stays NULL in the spectral form; hd_spec: that form's two layers, kept with option "spectral_refresh" = "on" only);
+  // hs, hs_k: the merges' scratch, allocated at the first call (that names the block)
   int refresh_heads(const xdet_net_weight_dev* table, int n, hipStream_t s);
   ConvLayer *hd_rpn[2] = {nullptr, nullptr}, *hd_head[2] = {nullptr, nullptr}, *hd_lsep[2] = {nullptr, nullptr};
+  SpectralConv* hd_spec[2] = {nullptr, nullptr};
   HeadsRefreshScratch hs;
   LargeSepKernelScratch hs_k;
   int calibrate(const float* images, int N, hipStream_t s, int* n_scaled);

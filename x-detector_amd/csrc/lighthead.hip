@@ -214,6 +214,7 @@ int LightHeadNet::build_large_sep_spectral() {
   XDET_TRY(SA->init(ka.data(), 15, cin, mid2, 0, F, nullptr, ba.data(), 0));
   XDET_TRY(SB->init(kb.data(), 15, mid2, co, 1, F, sc.data(), sh.data(), 1));
   XDET_REQUIRE(SA->cin_ld == out.ld && SA->cout_ld == mid2, "plan: the spectral convs' channel strides");
+  if (spectral_refresh) { hd_spec[0] = SA; hd_spec[1] = SB; }
   const int NB = SA->NB, cin_ld = SA->cin_ld, co_ld = SB->cout_ld;
   // workspace, sized for max_batch: rows of every bin are padded to a whole number of 256-row GEMM tiles
   const size_t mp_max = (size_t)round_up(max_batch * F, 256), rows = (size_t)NB * mp_max;
@@ -543,7 +544,7 @@ int LightHeadNet::refresh_stem(const xdet_net_weight_dev* table, int n, hipStrea
 // behind a table repack and its synchronisation: the layer's host copy of the epilogue scale at exponent 0 (d_scale carries
 // 2^in_exp, exactly), so that a calibration may apply an activation exponent to it again
 int LightHeadNet::scale_read_back(ConvLayer* L) {
-  std::vector<float> k((size_t)L->cout_pad);
+  std::vector<float> k((size_t)L->groups * L->cout_pad);      // (a grouped layer: every group's rows)
   XDET_HIP(hipMemcpy(k.data(), L->d_scale, k.size() * sizeof(float), hipMemcpyDeviceToHost));
   for (float& v : k) v = ldexpf(v, -L->in_exp);
   L->in_scale.host = k;
@@ -564,11 +565,14 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
                               "xdet_net_refresh_weights'", groups, table, n, &given));
   bool on[MG_N];
   for (int g = 0; g < MG_N; ++g) on[g] = !given[g].empty();
-  XDET_REQUIRE(!on[MG_LSEP] || !large_sep_spectral,
+  XDET_REQUIRE(!on[MG_LSEP] || !large_sep_spectral || spectral_refresh,
                "net_refresh_heads: the large_sep_feature group needs a net whose block is in the direct form (option large_sep=direct): "
-               "this net's is in the spectral form, which keeps the kernels as DFT-domain block matrices");
+               "this net's is in the spectral form, which keeps the kernels as DFT-domain block matrices (option spectral_refresh=on, "
+               "set before the build, lets such a net evaluate them on the device)");
+  const bool spec = on[MG_LSEP] && large_sep_spectral;          // the block's two layers are SpectralConvs, behind their own door
   ConvLayer* const* hd[MG_N] = {hd_rpn, hd_head, hd_lsep};
-  for (int g = 0; g < MG_N; ++g) XDET_REQUIRE(!on[g] || (hd[g][0] && hd[g][1]), "net_refresh_heads: the plan holds no such layers");
+  for (int g = 0; g < MG_N; ++g)
+    XDET_REQUIRE(!on[g] || (g == MG_LSEP && spec ? hd_spec[0] && hd_spec[1] : hd[g][0] && hd[g][1]), "net_refresh_heads: the plan holds no such layers");
   const MergedSizes z = merged_sizes();
   float* some = reinterpret_cast<float*>(this);              // (measuring reads no tensor)
   // a group's xdet_pack_slots by merged_layers.h: from the table's arrays into the scratch (measuring: `some` for both)
@@ -589,7 +593,7 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
     // first call that names them
     std::vector<xdet_pack_slot> slots;
     for (int g = 0; g < MG_N; ++g)
-      if (g != MG_LSEP || !large_sep_spectral) pack_slots(g, true, &slots);
+      if (g != MG_LSEP || !large_sep_spectral || spectral_refresh) pack_slots(g, true, &slots);
     const size_t pack_bytes = xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size());
     std::vector<xdet_layer_refresh> all;
     for (ConvLayer* L : {hd_rpn[0], hd_rpn[1], hd_head[0], hd_head[1], hd_lsep[0], hd_lsep[1]})
@@ -617,13 +621,14 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
     layers.push_back({hd_head[0], given[MG_HEAD][HEAD_K0], nullptr, given[MG_HEAD][HEAD_B0]});
     layers.push_back({hd_head[1], hs.head[SLOT_K], nullptr, hs.head[SLOT_B]});
   }
-  if (on[MG_LSEP]) {
+  if (on[MG_LSEP] && !spec) {
     layers.push_back({hd_lsep[0], hs_k.k_a, nullptr, hs.b_a});
     layers.push_back({hd_lsep[1], hs_k.k_b, hs.scale, hs.shift});
   }
   // every refusal the two table doors have is met here, ahead of the first launch: no layer is touched by a refused call
+  // (a call that names the spectral block alone has no table of layers)
   XDET_REQUIRE(xdet_tensors_concat_workspace_bytes(slots.data(), (int)slots.size()) > 0 &&
-               xdet_layers_refresh_workspace_bytes(layers.data(), (int)layers.size()) > 0,
+               (layers.empty() || xdet_layers_refresh_workspace_bytes(layers.data(), (int)layers.size()) > 0),
                "net_refresh_heads: the plan holds a layer the table door refuses");
   XDET_TRY(xdet_tensors_concat(slots.data(), (int)slots.size(), hs.pack_ws, s));
   if (on[MG_LSEP]) {
@@ -632,9 +637,17 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
     XDET_TRY(xdet_add_rows(g[LSEP_B0], co, g[LSEP_B1], co, hs.b_sum, co, 1, co, s));
     XDET_TRY(xdet_bn_fold(g[LSEP_GAMMA], g[LSEP_BETA], g[LSEP_MEAN], g[LSEP_VAR], hs.b_sum, 1e-5f, co, hs.scale, hs.shift, s));
   }
-  XDET_TRY(xdet_layers_refresh_device(layers.data(), (int)layers.size(), hs.repack_ws, s));
+  if (!layers.empty()) XDET_TRY(xdet_layers_refresh_device(layers.data(), (int)layers.size(), hs.repack_ws, s));
+  if (spec) {
+    // the spectral form of the two slots above: (15,1) + b_a, then (1,15) + the fold, each layer's block matrices evaluated
+    // from the merged kernel on the device (SpectralConv::set_kernel_device) at the grouped layer's own exponent
+    XDET_TRY(hd_spec[0]->set_kernel_device(hs_k.k_a, nullptr, hs.b_a, s));
+    XDET_TRY(hd_spec[1]->set_kernel_device(hs_k.k_b, hs.scale, hs.shift, s));
+  }
   XDET_HIP(hipStreamSynchronize(s));
   for (const xdet_layer_refresh& l : layers) XDET_TRY(scale_read_back(static_cast<ConvLayer*>(l.layer)));
+  if (spec)
+    for (SpectralConv* S : hd_spec) XDET_TRY(scale_read_back(&S->G));
   return XDET_OK;
 }
 

@@ -157,78 +157,7 @@ __global__ __launch_bounds__(256) void dft_inv_kernel(const float* __restrict__ 
 
 bool spectral_supported(int F) { return F == 16 || F == 30 || F == 50; }
 
-// host: the DFT tables of one axis length.  fwd/inv: [L/2][2][F] as the kernels read them.
-void spectral_tables(int F, std::vector<float>* fwd, std::vector<float>* inv) {
-  const int L = spectral_points(F), NB = L / 2;
-  fwd->assign((size_t)NB * 2 * F, 0.f);
-  inv->assign((size_t)NB * 2 * F, 0.f);
-  const double w = 2.0 * M_PI / L;
-  for (int i = 0; i < F; ++i) {
-    // bin 0: re slot = DC, im slot = Nyquist (both real)
-    (*fwd)[(size_t)0 * 2 * F + i] = 1.f;
-    (*fwd)[(size_t)0 * 2 * F + F + i] = (i & 1) ? -1.f : 1.f;
-    (*inv)[(size_t)0 * 2 * F + i] = (float)(1.0 / L);
-    (*inv)[(size_t)0 * 2 * F + F + i] = (float)(((i & 1) ? -1.0 : 1.0) / L);
-    for (int b = 1; b < NB; ++b) {
-      const double th = w * (double)(((long long)b * i) % L);
-      (*fwd)[((size_t)b * 2) * F + i] = (float)std::cos(th);          // X[b] = sum x[i] e^{-i th}
-      (*fwd)[((size_t)b * 2 + 1) * F + i] = (float)(-std::sin(th));
-      (*inv)[((size_t)b * 2) * F + i] = (float)(2.0 * std::cos(th) / L);   // x[i] = 1/L sum_b' Y[b'] e^{+i th}
-      (*inv)[((size_t)b * 2 + 1) * F + i] = (float)(-2.0 * std::sin(th) / L);
-    }
-  }
-}
-
-// host: the per-bin real block matrices of a T-tap kernel w[T][cin][cout] (pad = T/2 leading taps, TF SAME),
-// laid out as a grouped 1x1 weight [L/2][2*cin_ld][2*cout_ld] (rows: re | im of the input, cols: re | im of the output)
-void spectral_weights(const float* w, int T, int cin, int cout, int cin_ld, int cout_ld, int F, std::vector<float>* out) {
-  const int L = spectral_points(F), NB = L / 2, pad = T / 2;
-  const size_t K2 = 2 * (size_t)cin_ld, N2 = 2 * (size_t)cout_ld;
-  out->assign((size_t)NB * K2 * N2, 0.f);
-  const double om = 2.0 * M_PI / L;
-  std::vector<double> cr(T), ci(T);
-  std::vector<double> gr(cout), gi(cout);
-  for (int b = 0; b < NB; ++b) {
-    float* B = out->data() + (size_t)b * K2 * N2;
-    if (b == 0) {
-      // DC: G[0] = sum_t w[t]; Nyquist: G[L/2] = sum_t w[t] (-1)^{(pad - t) mod L}
-      for (int k = 0; k < cin; ++k) {
-        for (int n = 0; n < cout; ++n) { gr[n] = 0; gi[n] = 0; }
-        for (int t = 0; t < T; ++t) {
-          const int j = ((pad - t) % L + L) % L;
-          const double sgn = (j & 1) ? -1.0 : 1.0;
-          const float* src = w + ((size_t)t * cin + k) * cout;
-          for (int n = 0; n < cout; ++n) { gr[n] += src[n]; gi[n] += sgn * src[n]; }
-        }
-        float* r0 = B + (size_t)k * N2;                  // DC input row -> DC output columns
-        float* r1 = B + ((size_t)cin_ld + k) * N2;       // Nyquist input row -> Nyquist output columns
-        for (int n = 0; n < cout; ++n) { r0[n] = (float)gr[n]; r1[cout_ld + n] = (float)gi[n]; }
-      }
-      continue;
-    }
-    for (int t = 0; t < T; ++t) {
-      const int j = ((pad - t) % L + L) % L;
-      const double th = om * (double)(((long long)b * j) % L);
-      cr[t] = std::cos(th);
-      ci[t] = -std::sin(th);
-    }
-    for (int k = 0; k < cin; ++k) {
-      for (int n = 0; n < cout; ++n) { gr[n] = 0; gi[n] = 0; }
-      for (int t = 0; t < T; ++t) {
-        const float* src = w + ((size_t)t * cin + k) * cout;
-        const double a = cr[t], bb = ci[t];
-        for (int n = 0; n < cout; ++n) { gr[n] += a * src[n]; gi[n] += bb * src[n]; }
-      }
-      // [Xr Xi] x [[Gr, Gi], [-Gi, Gr]] = [Xr Gr - Xi Gi, Xr Gi + Xi Gr]
-      float* r0 = B + (size_t)k * N2;
-      float* r1 = B + ((size_t)cin_ld + k) * N2;
-      for (int n = 0; n < cout; ++n) {
-        r0[n] = (float)gr[n]; r0[cout_ld + n] = (float)gi[n];
-        r1[n] = (float)(-gi[n]); r1[cout_ld + n] = (float)gr[n];
-      }
-    }
-  }
-}
+// (the host tables, the twiddle table and the per-bin block matrices: spectral_weights.h)
 
 template <int F>
 static int launch_fwd_t(const float* in, int ld, int axis, int N, int m_pad, const float* tab, u16* hi, u16* lo, hipStream_t s) {

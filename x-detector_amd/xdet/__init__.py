@@ -58,6 +58,9 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the same optimizer over the large-separable block, the RPN head and the head as well (170
                              variables): the merges the forward layers are built from, and the split of their gradients, as
                              one table-driven copy on the device
+  SpectralConv.set_kernel_device (xdet.ops); LightHeadDetector(spectral_refresh=True)
+                          <- nothing in the reference: the DFT-domain block matrices of the spectral large-separable convs
+                             evaluated from trained kernels on the device, so refresh_eval_net() covers the default form
   host_average_gradients, grad_pack_device, grad_reduce_ranks_device, grad_flat_offsets (xdet.ops);
   Communicator.average_gradients (xdet.dist); MomentumOptimizer.step(grads, lr, comm=...)
                           <- nothing in the reference (its trainer is one session; xdet_v5_resnet_train.py:144 only

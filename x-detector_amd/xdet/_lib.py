@@ -210,6 +210,7 @@ SIGNATURES = {
     'xdet_grad_pack': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_void_p, c_void_p]),
     'xdet_grad_reduce_ranks': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_int, c_void_p, c_void_p]),
     'xdet_conv_set_kernel_device': (c_int, [c_void_p, PF, PF, c_void_p]),
+    'xdet_spectral_conv_set_kernel_device': (c_int, [c_void_p, PF, PF, PF, c_void_p]),
     'xdet_depthwise_set_kernel_device': (c_int, [c_void_p, PF, c_void_p]),
     'xdet_bn_fold': (c_int, [PF, PF, PF, PF, PF, c_float, c_int, PF, PF, c_void_p]),
     'xdet_layers_refresh_workspace_bytes': (c_size_t, [ctypes.POINTER(LayerRefresh), c_int]),

@@ -26,7 +26,7 @@ class LightHeadDetector(object):
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
                  pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
-                 entry_flow_train=False, stem_train=False, keep=()):
+                 entry_flow_train=False, stem_train=False, keep=(), spectral_refresh=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -73,7 +73,11 @@ class LightHeadDetector(object):
         takes the gradient from `stem_out` down to both kernels.  With it MomentumOptimizer steps the whole network.  The
         default detector allocates and runs none of this.
         keep=('stem_out', 'entry_x'): the eval body keeps these tensors as named buffers (the options the training stages
-        set for themselves) without any training state -- for looking at the entry flow stage by stage."""
+        set for themselves) without any training state -- for looking at the entry flow stage by stage.
+        spectral_refresh=True: a detector whose large-separable block is in the spectral form (large_sep='spectral', or 'auto'
+        where that resolves to it) lets refresh_heads take the large_sep_feature group: the block matrices of its two spectral
+        layers are evaluated from the merged kernels on the device (option "spectral_refresh", include/xdet.h).  The default
+        refuses that group on such a detector; the forward is the same either way."""
         stages = (large_sep_train, exit_flow_train, middle_flow_train, entry_flow_train)
         _train.check_stages(stages, weights)
         _train.check_stem(stem_train, entry_flow_train, weights)
@@ -99,6 +103,8 @@ class LightHeadDetector(object):
             dims = (ctypes.c_int64 * a.ndim)(*a.shape)
             check(lib().xdet_net_set_weight(self.handle, name.encode(), _host(a), a.ndim, dims))
         check(lib().xdet_net_set_option(self.handle, b'large_sep', large_sep.encode()))
+        if spectral_refresh:
+            check(lib().xdet_net_set_option(self.handle, b'spectral_refresh', b'on'))
         check(lib().xdet_net_set_option(self.handle, b'sepconv', sepconv.encode()))
         check(lib().xdet_net_set_option(self.handle, b'rpn_stream', rpn_stream.encode()))
         check(lib().xdet_net_set_option(self.handle, b'conv3x3', conv3x3.encode()))
@@ -274,10 +280,12 @@ class LightHeadDetector(object):
         """Refresh the layers the net's plan owns from weights on the device (xdet_net_refresh_heads): tensors is {checkpoint name:
         dense f32 DeviceTensor or DeviceBuffer in the checkpoint's shape} over whole groups -- 'rpn_head' (train.RPN_HEAD_VARIABLES),
         'final_head' (train.HEAD_VARIABLES), 'large_sep_feature' (train.LARGE_SEP_VARIABLES + LARGE_SEP_MOVING; a net whose block
-        is in the direct form only: large_sep='direct').  The merges run on the device into scratch the net owns, the touched
-        layers are repacked by one table, the stream is synchronised and the host state a calibration works from brought back in
-        line; exponents, plane_scales() and the captured graphs stay.  Refused ahead of any GPU work, by name: a host array, a name
-        outside the three groups, a group given in part, a duplicate, the large_sep_feature group on a spectral block."""
+        is in the direct form, large_sep='direct', or a spectral one built with spectral_refresh=True, whose two layers then
+        evaluate their DFT-domain block matrices from the merged kernels on the device).  The merges run on the device into
+        scratch the net owns, the touched layers are repacked by one table (the spectral layers by their own door), the stream is
+        synchronised and the host state a calibration works from brought back in line; exponents, plane_scales() and the
+        captured graphs stay.  Refused ahead of any GPU work, by name: a host array, a name outside the three groups, a group
+        given in part, a duplicate, the large_sep_feature group on a spectral block built without spectral_refresh=True."""
         from ._lib import NetWeightDev
         for name, t in tensors.items():
             if not isinstance(t, (DeviceTensor, DeviceBuffer)) or not t.ptr:

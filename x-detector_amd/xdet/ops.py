@@ -449,6 +449,25 @@ class SpectralConv(object):
     def workspace_bytes(self, N):
         return int(lib().xdet_spectral_conv_workspace_bytes(self.handle, int(N)))
 
+    def set_kernel_device(self, kernel, scale=None, shift=None, stream=None):
+        """Rewrite the layer's DFT-domain block matrices from a kernel in device memory (xdet_spectral_conv_set_kernel_device):
+        kernel is a dense DeviceTensor [T, cin, cout] (ld cout), scale / shift DeviceBuffers / DeviceTensors of cout floats or
+        None (kept).  The layer then holds what SpectralConv(kernel's values, ...) would hold, bit for bit; nothing is
+        synchronised or read on the host.  Refused by name: a host array, a wrong shape."""
+        want = (self.taps, self.cin, self.cout)
+        if not isinstance(kernel, DeviceTensor) or tuple(kernel.shape) != want or kernel.ld != self.cout:
+            raise InvalidArgumentError(-1, 'SpectralConv.set_kernel_device: kernel must be a dense DeviceTensor of shape %r (device '
+                                       'memory), got %s %r (ld %r)' % (want, type(kernel).__name__, getattr(kernel, 'shape', None),
+                                                                       getattr(kernel, 'ld', None)))
+        for name, a in (('scale', scale), ('shift', shift)):
+            if a is not None and (not isinstance(a, (DeviceBuffer, DeviceTensor))
+                                  or (isinstance(a, DeviceBuffer) and a.nbytes < 4 * self.cout)):
+                raise InvalidArgumentError(-1, 'SpectralConv.set_kernel_device: %s must be a device array of %d floats, got %s'
+                                           % (name, self.cout, type(a).__name__))
+        check(lib().xdet_spectral_conv_set_kernel_device(self.handle, kernel.ptr, scale.ptr if scale is not None else None,
+                                                         shift.ptr if shift is not None else None,
+                                                         stream.handle if stream else None))
+
     def __call__(self, x, out=None, workspace=None, stream=None):
         """x: DeviceTensor [N,F,F,cin]; out (optional): a DeviceTensor to write into (its ld may exceed round_up(cout,32));
         workspace (optional): a DeviceBuffer of workspace_bytes(N) bytes, any contents"""

@@ -1552,8 +1552,11 @@ class MomentumOptimizer(object):
         export_weights(...) computes, bit for bit.  Under data-parallel training each rank folds its own moving statistics.
         reach='all': the large_sep_feature group -- the ten masters and the training stage's moving statistics -- goes through
         xdet_net_refresh_heads first (LightHeadDetector.refresh_heads: merged, folded with eps 1e-5 and the bias b0 + b1, the two
-        direct-form layers repacked) -> 74.  A net whose block is in the spectral form refuses that group by name (build the
-        detector with large_sep='direct'), ahead of any launch of this call.  The RPN head and the head need nothing here: the
+        direct-form layers repacked) -> 74.  A net whose block is in the spectral form takes the same merges and fold through its
+        two spectral layers (xdet_spectral_conv_set_kernel_device: the DFT-domain block matrices evaluated from the merged
+        kernels on the device, no host copy and no array of their size) when the detector was built with spectral_refresh=True
+        -> 74 as well; built without it, it refuses that group by name (large_sep='direct' or spectral_refresh=True), ahead of
+        any launch of this call.  The RPN head and the head need nothing here: the
         eval net and the training forward share those layers, and step has refreshed them.
         A detector built with stem_train=True: both stem convs go through xdet_net_refresh_stem as well
         (LightHeadDetector.refresh_stem) -> 74 at reach='flows', 76 at reach='all'."""
