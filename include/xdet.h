@@ -1114,7 +1114,21 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   (net/xception_body.py:260), f32 in every plan -- stays a named buffer [max_batch, h, w, 64] (xdet_net_buffer "stem_out")
  *   instead of going back to the workspace pool when block 2 has read it: what a training-mode entry flow starts from.  off
  *   (default): the plan, the kernels and their arguments are the same as ever and the name is refused.  keep: every tensor of
- *   the forward has the same bits; only addresses inside the workspace move. */
+ *   the forward has the same bits; only addresses inside the workspace move.
+ *   "head_rois" = "off" | "<P>", a whole number in 1..rpn_post_nms_top_n (anything else: XDET_ERR_INVALID_ARG, naming the
+ *   option): the head stage of a TRAINING net.  The reference proposes rpn_post_nms_top_n ROIs per image, samples P of them
+ *   and runs PsRoiAlign, the head and its backward on those (light_head_rfcn_train.py:86-112, net/xception_body.py:446-448,
+ *   502-533).  With P the head stage -- "pooled", "fc", "cls_reg" and, with "pool_index" = "keep", "pool_index" -- is planned
+ *   on P rows per image instead of rpn_post_nms_top_n, with the same layers and constants: the plan a net created with
+ *   rpn_post_nms_top_n = P has.  The proposal stage keeps rpn_post_nms_top_n ("proposals", xdet_net_get_proposals and its
+ *   workspace).  The sampled ROIs live in a new buffer, xdet_net_buffer "head_rois": f32 [max_batch, P, 4] corner boxes in
+ *   the layout of "proposals", written by the caller (a device-to-device copy of what xdet_encode_rois left); xdet_net_get_head
+ *   and xdet_net_head_pool_backward read it in place of "proposals".  Such a net has no eval tail: xdet_net_forward,
+ *   xdet_net_forward_u8, xdet_net_calibrate (which runs whole forwards), xdet_net_head_decode and xdet_net_bboxes_eval return
+ *   XDET_ERR_STATE with a sentence that names head_rois, ahead of any launch and of a graph capture.  The refresh doors
+ *   (xdet_net_refresh_weights / _heads / _stem) do not depend on the row count and work as ever.  off (default): the net as
+ *   ever, byte for byte, and the buffer name is refused.  No kernel belongs to the option: PsRoiAlign, its ordered gradient
+ *   and the dense layers take the row count as an argument. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
@@ -1122,7 +1136,9 @@ int xdet_net_destroy(void* net);
  * "rpn_boxes","proposals","pooled","fc","cls_reg","head_boxes","prop_counts"; "pool_index" (i32, dims / ld of "pooled")
  * with option "pool_index" = "keep" only, "rpn_hidden" (f32 [max_batch,h,w,512]) with option "rpn_hidden" = "keep" only,
  * "entry_x" (f32 [max_batch,h,w,728]) with option "entry_x" = "keep" only, "stem_out" (f32 [max_batch,h,w,64]) with option
- * "stem_out" = "keep" only, otherwise XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU */
+ * "stem_out" = "keep" only, "head_rois" (f32 [max_batch,P,1,4], ld 4) with option "head_rois" = "<P>" only, otherwise
+ * XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU.  With "head_rois" = "<P>" the buffers "pooled", "fc", "cls_reg"
+ * and "pool_index" have P rows per image, "proposals" and "head_boxes" rpn_post_nms_top_n */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */
@@ -1138,9 +1154,11 @@ int xdet_net_rpn_decode(void* net, int N, void* stream);                        
 int xdet_net_get_proposals(void* net, int N, void* stream);                            /* :402 -> "proposals" */
 int xdet_net_get_head(void* net, int N, void* stream);                                 /* :477 -> "cls_reg" */
 int xdet_net_head_decode(void* net, int N, void* stream);                              /* -> "head_boxes" */
-/* The head's pooling backward: d loss / d pooled (device, [N*R, ld], first C = grid*grid*bank entries of a row) ->
- * d loss / d feat, by xdet_psroialign_grad_ordered on the net's own "proposals" (corner boxes), the "pool_index" the last
- * xdet_net_get_head kept, cfg.grid and 'max'.  d_feat: [N, feat.H, feat.W, feat.ld], the layout of the "feat" buffer,
+/* (xdet_net_get_head reads "proposals", rpn_post_nms_top_n rows per image -- or, on a net built with "head_rois" = "<P>",
+ * the "head_rois" buffer with P rows; xdet_net_head_decode and xdet_net_bboxes_eval are XDET_ERR_STATE on such a net.) */
+/* The head's pooling backward: d loss / d pooled (device, [N*R, ld], first C = grid*grid*bank entries of a row; R = P on a
+ * net built with "head_rois" = "<P>") -> d loss / d feat, by xdet_psroialign_grad_ordered on the net's own "proposals"
+ * ("head_rois" on such a net; corner boxes), the "pool_index" the last xdet_net_get_head kept, cfg.grid and 'max'.  d_feat: [N, feat.H, feat.W, feat.ld], the layout of the "feat" buffer,
  * every element written (padding channels zero).  XDET_ERR_STATE for a net built with "pool_index" = "off". */
 int xdet_net_head_pool_backward(void* net, int N, const float* d_pooled, int ld, float* d_feat, void* stream);
 int xdet_net_bboxes_eval(void* net, int N, const int* image_shapes, const float* bbox_img, float* det_scores,

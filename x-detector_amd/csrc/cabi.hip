@@ -588,6 +588,17 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->keep_pool_index = v == "keep";
     return XDET_OK;
   }
+  if (k == "head_rois") {
+    // "off", or the sampled ROIs per image the head stage is planned on: a whole number in 1..rpn_post_nms_top_n
+    if (v == "off") { n->head_rois_n = 0; return XDET_OK; }
+    char* end = nullptr;
+    const long p = v.empty() ? 0 : strtol(v.c_str(), &end, 10);
+    XDET_REQUIRE(!v.empty() && end && *end == '\0' && p >= 1 && p <= (long)n->cfg.rpn_post_nms_top_n,
+                 "head_rois must be off or a whole number in 1..rpn_post_nms_top_n (" + std::to_string(n->cfg.rpn_post_nms_top_n) +
+                     "), got " + v);
+    n->head_rois_n = (int)p;
+    return XDET_OK;
+  }
   if (k == "rpn_hidden") {
     XDET_REQUIRE(v == "keep" || v == "off", "rpn_hidden must be keep | off");
     n->keep_rpn_hidden = v == "keep";
@@ -651,6 +662,10 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
   else if (s == "objectness") { *dptr = n->objectness; dims[0] = B; dims[1] = n->n_anchor; dims[2] = 1; dims[3] = 1; *ld = 1; }
   else if (s == "rpn_boxes") { *dptr = n->rpn_boxes; dims[0] = B; dims[1] = n->n_anchor; dims[2] = 1; dims[3] = 4; *ld = 4; }
   else if (s == "proposals") { *dptr = n->proposals; dims[0] = B; dims[1] = R; dims[2] = 1; dims[3] = 4; *ld = 4; }
+  else if (s == "head_rois") {
+    XDET_REQUIRE(n->head_rois != nullptr, "net_buffer: head_rois needs a net built with the option head_rois=<P>");
+    *dptr = n->head_rois; dims[0] = B; dims[1] = n->head_rois_n; dims[2] = 1; dims[3] = 4; *ld = 4;
+  }
   else if (s == "head_boxes") { *dptr = n->head_boxes; dims[0] = B; dims[1] = R; dims[2] = 1; dims[3] = 4; *ld = 4; }
   else if (s == "prop_counts") { *dptr = n->prop_ws.counts; dims[0] = B; dims[1] = 4; dims[2] = 1; dims[3] = 1; *ld = 1; }
   else if (s == "sorted_boxes") { *dptr = n->prop_ws.sboxes; dims[0] = B; dims[1] = n->cfg.rpn_pre_nms_top_n; dims[2] = 1; dims[3] = 4; *ld = 4; }
@@ -725,6 +740,7 @@ int xdet_net_forward(void* net, const float* images, int N, const int* image_sha
                      float* det_scores, float* det_boxes, int use_graph, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_forward");
   XDET_REQUIRE(n && images && det_scores && det_boxes, "forward: NULL argument");
+  XDET_TRY(n->eval_refused("net_forward"));      // (ahead of a graph capture)
   XDET_TRY(n->check(N));
   hipStream_t s = S(stream);
   if (!use_graph) return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s);
@@ -742,6 +758,7 @@ int xdet_net_forward_u8(void* net, const uint8_t* packed, int64_t packed_bytes, 
   XDET_LIGHTHEAD(n, net, "net_forward_u8");
   XDET_REQUIRE(n && packed && offsets && image_shapes && images && bbox_img && det_scores && det_boxes,
                "forward_u8: NULL argument");
+  XDET_TRY(n->eval_refused("net_forward_u8"));   // (ahead of the ingest and of a graph capture)
   XDET_TRY(n->check(N));
   XDET_REQUIRE(resize >= XDET_RESIZE_NONE && resize <= XDET_RESIZE_WARP, "forward_u8: unknown resize mode");
   XDET_REQUIRE(packed_bytes >= 0, "forward_u8: packed_bytes < 0");

@@ -16,6 +16,11 @@ struct LightHeadNet : Plan {
   float *objectness = nullptr, *rpn_boxes = nullptr, *proposals = nullptr, *head_boxes = nullptr;
   int32_t* pool_index = nullptr;  // [B * R][pooled.ld] argmax sample ids of the head's PsRoiAlign (option "pool_index" = "keep")
   bool keep_pool_index = false;
+  // option "head_rois" = "<P>": the head stage is planned on P sampled rows per image (pooled, fc, cls_reg, pool_index) and
+  // reads its ROIs from `head_rois` [max_batch, P, 4], corner boxes in the layout of `proposals`; the proposal stage keeps
+  // cfg.rpn_post_nms_top_n rows.  0 = off: the head runs on `proposals`.  Such a net has no eval tail (eval_refused)
+  int head_rois_n = 0;
+  float* head_rois = nullptr;
   Buf rpn_hidden;                 // relu(rpn_head/conv2d) as f32 [B,h,w,512] (option "rpn_hidden" = "keep"; p stays NULL without)
   bool keep_rpn_hidden = false;
   Buf entry_x;                    // block 4's sum, the middle flow's input, f32 [B,h,w,728] (option "entry_x" = "keep"; p stays NULL without)
@@ -81,6 +86,16 @@ struct LightHeadNet : Plan {
 
   int build();
 
+  int head_rows() const { return head_rois_n ? head_rois_n : cfg.rpn_post_nms_top_n; }
+  const float* head_boxes_in() const { return head_rois_n ? head_rois : proposals; }
+  // the eval entries of a net whose head runs on sampled rows: refused ahead of any launch and of a graph capture
+  int eval_refused(const char* what) const {
+    if (!head_rois_n) return XDET_OK;
+    set_last_error(std::string(what) + ": this net was built with the option head_rois=" + std::to_string(head_rois_n) +
+                   " (its head runs on the sampled ROIs of the head_rois buffer, a training net): it has no eval forward and no "
+                   "detection tail; build a net without head_rois for those");
+    return XDET_ERR_STATE;
+  }
   int check(int N) const {
     if (!built) {
       set_last_error("net not built");
@@ -113,12 +128,12 @@ struct LightHeadNet : Plan {
   int get_head(int N, hipStream_t s) {
     XDET_TRY(check(N));
     const int C = cfg.bank * cfg.grid * cfg.grid;
-    XDET_TRY(launch_psroialign(feat.p, proposals, pooled.p, pool_index, N, C, feat.H, feat.W, cfg.rpn_post_nms_top_n,
+    XDET_TRY(launch_psroialign(feat.p, head_boxes_in(), pooled.p, pool_index, N, C, feat.H, feat.W, head_rows(),
                                cfg.grid, cfg.grid, 1, 1, feat.ld, pooled.ld, /*corners=*/1, s));
     return run_stage(ST_HEAD, N, s);
   }
   // d loss / d pooled -> d loss / d feat in the layout of `feat`: the order-exact PsRoiAlign gradient on the net's own
-  // corner proposals and the argmax the last get_head kept
+  // corner proposals (the sampled ROIs of `head_rois` with that option) and the argmax the last get_head kept
   int head_pool_backward(int N, const float* d_pooled, int ld, float* d_feat, hipStream_t s) {
     XDET_TRY(check(N));
     if (!pool_index) {
@@ -127,10 +142,11 @@ struct LightHeadNet : Plan {
     }
     XDET_REQUIRE(d_pooled && d_feat, "net_head_pool_backward: NULL argument");
     const int C = cfg.bank * cfg.grid * cfg.grid;
-    return launch_psroialign_grad_ordered(proposals, d_pooled, ld, pool_index, pooled.ld, d_feat, N, C, feat.H, feat.W,
-                                          cfg.rpn_post_nms_top_n, cfg.grid, cfg.grid, 1, 1, feat.ld, /*corners=*/1, s);
+    return launch_psroialign_grad_ordered(head_boxes_in(), d_pooled, ld, pool_index, pooled.ld, d_feat, N, C, feat.H, feat.W,
+                                          head_rows(), cfg.grid, cfg.grid, 1, 1, feat.ld, /*corners=*/1, s);
   }
   int head_decode(int N, hipStream_t s) {
+    XDET_TRY(eval_refused("net_head_decode"));
     XDET_TRY(check(N));
     return launch_ext_decode_rois(proposals, cls_reg.p + cfg.num_classes, cls_reg.ld,
                                   (int64_t)N * cfg.rpn_post_nms_top_n, head_boxes, s);
@@ -149,6 +165,7 @@ struct LightHeadNet : Plan {
   }
   // the stage entry points (xdet_net_head_decode / xdet_net_bboxes_eval): each complete on its own, from "cls_reg" / "head_boxes"
   int bboxes_eval(int N, const int* shapes, const float* bbox, float* ds, float* db, hipStream_t s) {
+    XDET_TRY(eval_refused("net_bboxes_eval"));
     XDET_TRY(check(N));
     return launch_bboxes_eval(cls_reg.p, cls_reg.ld, head_boxes, N, cfg.rpn_post_nms_top_n, cfg.num_classes,
                               shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,

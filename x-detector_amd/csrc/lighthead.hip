@@ -279,7 +279,9 @@ int LightHeadNet::build_large_sep_spectral() {
 
 int LightHeadNet::build_head() {
   const MergedSizes z = merged_sizes();
-  const int R = cfg.rpn_post_nms_top_n, C = z.co, nc = z.nc, fw = z.fcw;
+  // (the rows of the head stage: the sampled ROIs per image with the option head_rois, else the proposals -- the same
+  //  layers and ConvEmit constants either way, so head_rois = P plans what a net built with rpn_post_nms_top_n = P plans)
+  const int R = head_rows(), C = z.co, nc = z.nc, fw = z.fcw;
   std::vector<const float*> t;
   XDET_TRY(need_group(MG_HEAD, {{C, fw}, {fw}, {fw, nc}, {nc}, {fw, 4}, {4}}, &t));
   // ROI rows are the GEMM M dimension: treat [N*R, C] as an NHWC tensor with H = R, W = 1
@@ -302,6 +304,8 @@ int LightHeadNet::build_head() {
 int LightHeadNet::build() {
   XDET_REQUIRE(!built, "net already built");
   XDET_REQUIRE(cfg.max_batch > 0 && cfg.image_size >= 64, "bad max_batch / image_size");
+  XDET_REQUIRE(head_rois_n == 0 || (head_rois_n >= 1 && head_rois_n <= cfg.rpn_post_nms_top_n),
+               "head_rois must be off or in 1..rpn_post_nms_top_n");
   XDET_REQUIRE(cfg.num_anchors == 22, "anchor table is the reference's 22-anchor set (1 extra + 7 scales x 3 ratios)");
   max_batch = cfg.max_batch;
   net_precision = g_default_precision;
@@ -337,6 +341,7 @@ int LightHeadNet::build() {
   XDET_TRY(alloc_bytes((size_t)B * n_anchor * 4, reinterpret_cast<void**>(&objectness)));
   XDET_TRY(alloc_bytes((size_t)B * n_anchor * 16, reinterpret_cast<void**>(&rpn_boxes)));
   XDET_TRY(alloc_bytes((size_t)B * R * 16, reinterpret_cast<void**>(&proposals)));
+  if (head_rois_n) XDET_TRY(alloc_bytes((size_t)B * head_rois_n * 16, reinterpret_cast<void**>(&head_rois)));
   XDET_TRY(alloc_bytes((size_t)B * R * 16, reinterpret_cast<void**>(&head_boxes)));
   XDET_TRY(alloc_bytes((size_t)B * cfg.num_classes * R * 4, reinterpret_cast<void**>(&class_probs)));
   XDET_TRY(alloc_bytes((size_t)B * mid_x.per_image() * 4, reinterpret_cast<void**>(&mid_relu)));
@@ -652,6 +657,7 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
 }
 
 int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_scaled) {
+  XDET_TRY(eval_refused("net_calibrate"));             // (it measures the planes of whole forwards)
   XDET_TRY(check(N));
   XDET_REQUIRE(images != nullptr, "calibrate: images is NULL");
   if (n_scaled) *n_scaled = 0;
@@ -666,6 +672,7 @@ int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_sc
 
 int LightHeadNet::forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                   hipStream_t s) {
+  XDET_TRY(eval_refused("net_forward"));
   XDET_TRY(entry_and_middle_flow(images, N, s));
   // fork: the RPN branch (3x3 conv, 1x1 heads, decode, top-k, NMS -- a long conv and then small latency-bound
   // launches) needs mid_outputs only (net/xception_body.py:339,381-400): it runs on a side stream under the exit flow

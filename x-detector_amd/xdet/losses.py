@@ -296,7 +296,8 @@ def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=
 
 class HeadLoss(object):
     """The `loss_func` of model.get_head(..., is_training=True): the sampled ROIs' labels [N,P] and targets [N,P,4]
-    (what the encode_fn of get_proposals returned) and fg_ratio, as the reference's lambda closes over them
+    (what the encode_fn of get_proposals returned: NumPy, or the device arrays of ext_encode_rois(..., keep_device=True), labels
+    i32, read in place) and fg_ratio, as the reference's lambda closes over them
     (light_head_rfcn_train.py:407).  Calling it with the head's outputs gives the HeadLossResult; get_head leaves the last
     one in `.result` (losses, per_roi, select and the gradients) and returns the scalar; `.grad_device` is d loss / d cls_reg
     on the GPU, in the `cls_reg` buffer's layout (model.head_backward reads it)."""
@@ -309,6 +310,11 @@ class HeadLoss(object):
     def __call__(self, cls_score, bboxes_reg=None, ohem_k=0, num_classes=None, stream=None):
         labels = self.labels if hasattr(self.labels, 'ptr') else np.asarray(self.labels).astype(np.int32)
         kept = []
+        for t in (labels, self.targets):                 # what encode_rois(..., keep_device=True) left unsynchronised on
+            made_on = getattr(t, 'made_on', stream)       # another stream is waited for; anything else is read as it is
+            if made_on is not stream:
+                from .runtime import synchronize
+                synchronize(made_on)
         self.result = head_loss(cls_score, bboxes_reg, labels, self.targets, self.fg_ratio, ohem_k, self.sigma, num_classes,
                                 stream=stream, device_grad=kept)
         self.grad_device = kept[0] if kept else None

@@ -26,7 +26,7 @@ class LightHeadDetector(object):
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
                  pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
-                 entry_flow_train=False, stem_train=False, keep=(), spectral_refresh=False):
+                 entry_flow_train=False, stem_train=False, keep=(), spectral_refresh=False, head_rois=None):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -77,7 +77,15 @@ class LightHeadDetector(object):
         spectral_refresh=True: a detector whose large-separable block is in the spectral form (large_sep='spectral', or 'auto'
         where that resolves to it) lets refresh_heads take the large_sep_feature group: the block matrices of its two spectral
         layers are evaluated from the merged kernels on the device (option "spectral_refresh", include/xdet.h).  The default
-        refuses that group on such a detector; the forward is the same either way."""
+        refuses that group on such a detector; the forward is the same either way.
+        head_rois=P (1 <= P <= rpn_post_nms_top_n; option "head_rois", include/xdet.h): the head stage -- `pooled`, `fc`,
+        `cls_reg`, `pool_index` -- is planned on P rows per image, the ROIs a training step samples from the proposals, and
+        reads them from the buffer 'head_rois' [max_batch, P, 1, 4]; the proposal stage keeps rpn_post_nms_top_n.  `head_R` is
+        P then (else rpn_post_nms_top_n): get_head(..., is_training=True) takes P ROIs per image, a DeviceTensor of them by a
+        device-to-device copy, and head_backward, MomentumOptimizer and refresh_eval_net work on this one detector.  Such a
+        detector has no eval forward: forward, calibrate, detect_images, detect_jpegs, evaluate* and
+        get_head(..., is_training=False) refuse by naming the option.  The default (None) is the detector as ever."""
+        self.head_rois = _train.check_head_rois(head_rois, rpn_post_nms_top_n)
         stages = (large_sep_train, exit_flow_train, middle_flow_train, entry_flow_train)
         _train.check_stages(stages, weights)
         _train.check_stem(stem_train, entry_flow_train, weights)
@@ -120,6 +128,8 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'pool_index', b'keep'))
         if rpn_hidden:
             check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
+        if self.head_rois is not None:
+            check(lib().xdet_net_set_option(self.handle, b'head_rois', str(self.head_rois).encode()))
         if set(keep) - {'stem_out', 'entry_x'}:
             raise InvalidArgumentError(-1, 'keep: %r is not one of stem_out, entry_x' % (sorted(set(keep) - {'stem_out', 'entry_x'}),))
         if middle_flow_train or 'entry_x' in keep:
@@ -132,6 +142,7 @@ class LightHeadDetector(object):
         self.image_size = image_size
         self.num_classes = num_classes
         self.R = rpn_post_nms_top_n
+        self.head_R = self.head_rois if self.head_rois is not None else self.R      # rows of the head stage
         self.nms_topk = nms_topk
         self.stream = Stream()
         B, nc, k = max_batch, num_classes - 1, nms_topk
@@ -206,7 +217,7 @@ class LightHeadDetector(object):
         """overwrite a workspace buffer from the host (tests: feed one stage the oracle's tensors)."""
         t = self.buffer(name, n=array.shape[0])
         a = np.asarray(array, np.float32)
-        if name in ('objectness', 'rpn_boxes', 'proposals', 'head_boxes'):
+        if name in ('objectness', 'rpn_boxes', 'proposals', 'head_boxes', 'head_rois'):
             flat = np.ascontiguousarray(a)
         else:
             n, h, w, c = a.shape
@@ -496,7 +507,7 @@ class LightHeadDetector(object):
         """the `predictions` dict of the EstimatorSpec (light_head_rfcn_eval.py:429-433)."""
         n = n or self._N
         nc = self.num_classes
-        cr = self.buffer('cls_reg', n).numpy().reshape(n, self.R, -1)
+        cr = self.buffer('cls_reg', n).numpy().reshape(n, self.head_R, -1)
         logits = cr[..., :nc]
         e = np.exp(logits - logits.max(-1, keepdims=True))
         prob = e / e.sum(-1, keepdims=True)
@@ -673,8 +684,13 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
     on the net's `cls_reg` buffer in place (OHEM keeps the ohem_roi_one_image hardest ROIs per image; the reference's second
     run of the dense layers on the gathered rows has the same weights, so the selected rows' logits are the gathered ones)
     -> the scalar head loss; losses, per-ROI values, the selection and d loss / d cls_reg are in loss_func.result.  The head's
-    row count is fixed when the detector is built: proposals_bboxes.shape[1] must equal its rpn_post_nms_top_n (a head detector
-    built with rpn_post_nms_top_n = the ROIs sampled per image).  `pooling_op` is accepted for signature parity; the fused HIP
+    row count is fixed when the detector is built: proposals_bboxes.shape[1] must equal its head_R -- head_rois on a detector
+    built with that option, which then holds the proposal stage at rpn_post_nms_top_n and the head on the sampled set, else
+    rpn_post_nms_top_n (a head detector built with rpn_post_nms_top_n = the ROIs sampled per image).  On a head_rois detector
+    the ROIs go into the net's `head_rois` buffer: a DeviceTensor [N,P,(1,)4] (what ext_encode_rois(..., keep_device=True)
+    returns) by one device-to-device copy on the detector's stream -- none when it is that buffer -- and a host array by an
+    upload; is_training=False is refused there, the eval head and its tail need a detector without the option.
+    `pooling_op` is accepted for signature parity; the fused HIP
     PsRoiAlign is always used.  head_backward(loss_func) takes the gradient from there through the two dense layers."""
     d = _det()
     if (grid_width, grid_height) != (d.cfg.grid, d.cfg.grid) or num_classes != d.cfg.num_classes:
@@ -685,20 +701,32 @@ def get_head(net_input, pooling_op, grid_width, grid_height, loss_func, proposal
         from .losses import HeadLoss
         if not isinstance(loss_func, HeadLoss):
             raise InvalidArgumentError(-1, 'get_head: is_training=True needs a losses.HeadLoss as loss_func')
-        if proposals_bboxes.shape[1] != d.R:
-            raise InvalidArgumentError(-1, 'get_head: %d ROIs per image but the detector was built with rpn_post_nms_top_n = %d'
-                                       % (proposals_bboxes.shape[1], d.R))
+        if proposals_bboxes.shape[1] != d.head_R:
+            raise InvalidArgumentError(-1, 'get_head: %d ROIs per image but the detector was built with %s = %d'
+                                       % (proposals_bboxes.shape[1], 'head_rois' if d.head_rois is not None else 'rpn_post_nms_top_n',
+                                          d.head_R))
+    elif d.head_rois is not None:
+        raise InvalidArgumentError(-1, 'get_head: is_training=False on a detector built with head_rois=%d: its head runs on the '
+                                       'sampled ROIs only; the eval head needs a detector built without head_rois' % d.head_rois)
     elif using_ohem:
         raise InvalidArgumentError(-1, 'get_head: OHEM belongs to the training branch (is_training=True)')
+    if n > d.max_batch:
+        raise InvalidArgumentError(-1, 'get_head: ROIs of %d images but the detector was built with max_batch = %d' % (n, d.max_batch))
     view = d.buffer('feat', n)
     if not _same(net_input, view):
         d.write('feat', net_input.numpy() if isinstance(net_input, DeviceTensor) else net_input)
-    d.write('proposals', np.asarray(proposals_bboxes, np.float32))
+    if d.head_rois is None:
+        d.write('proposals', proposals_bboxes.numpy() if isinstance(proposals_bboxes, DeviceTensor) else
+                np.asarray(proposals_bboxes, np.float32))
+    elif isinstance(proposals_bboxes, DeviceTensor):
+        _train.rois_to_head(d, proposals_bboxes, n)
+    else:
+        d.write('head_rois', np.asarray(proposals_bboxes, np.float32).reshape(n, d.head_R, 4))
     check(lib().xdet_net_get_head(d.handle, n, d.stream.handle))
     _train.heads_ran(d, '_head_step')
     _sync(d)
     if is_training:
         res = loss_func(d.buffer('cls_reg', n), None, int(ohem_roi_one_image) if using_ohem else 0, num_classes)
         return float(res.losses[0])
-    cr = d.buffer('cls_reg', n).numpy().reshape(n, d.R, -1)
+    cr = d.buffer('cls_reg', n).numpy().reshape(n, d.head_R, -1)
     return cr[..., :num_classes], cr[..., num_classes:num_classes + 4]

@@ -300,10 +300,15 @@ def encode_anchors(anchor, labels, bboxes, n_gt=None, allowed_border=0., high_th
 
 def encode_rois(rois, labels, bboxes, n_gt=None, allowed_border=0.1, fg_thr=0.5, bg_high_thr=0.5, bg_low_thr=0.,
                 prior_scaling=(1., 1., 1., 1.), rois_per_image=256, fg_fraction=0.25, seed=0, image_ids=None,
-                return_all=False, stream=None):
+                return_all=False, stream=None, keep_device=False):
     """host_encode_rois on the GPU (xdet_encode_rois), same results in the same order.  rois: NumPy [N,R,4], or a
     DeviceTensor / DeviceBuffer holding N * R * 4 floats (then `rois` is not copied; give R through its shape [N,R,1,4] or
-    [N,R,4]) -- e.g. the `proposals` buffer of a LightHeadDetector."""
+    [N,R,4]) -- e.g. the `proposals` buffer of a LightHeadDetector.
+    keep_device=True: the results stay where the kernel wrote them and the call does not synchronise -- out_rois and
+    out_targets as f32 DeviceTensors [N,P,1,4] (ld 4), out_labels (i32), out_scores and out_index (i32) [N,P,1,1], counts
+    (i32) [N,1,1,4] (with return_all the three unsampled arrays likewise), each carrying the stream it was made on
+    (`made_on`): model.get_head on a head_rois detector copies the ROIs device to device, losses.HeadLoss reads labels and
+    targets in place.  DeviceTensor.numpy() reads f32: download an i32 one with runtime.to_host(t.ptr, shape, np.int32)."""
     from ._lib import lib, check, InvalidArgumentError
     from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
     gl, gb, ng = ground_truth(labels, bboxes, n_gt)
@@ -343,6 +348,18 @@ def encode_rois(rois, labels, bboxes, n_gt=None, allowed_border=0.1, fg_thr=0.5,
                                  int(seed) & 0xFFFFFFFF, d_ids.ptr if d_ids is not None else None, ws.ptr, o_r.ptr, o_t.ptr,
                                  o_l.ptr, o_s.ptr, o_i.ptr, o_c.ptr, a_l.ptr if a_l else None, a_t.ptr if a_t else None,
                                  a_s.ptr if a_s else None, _h(stream)))
+    if keep_device:
+        # (nothing waits here: the inputs and the workspace stay referenced by the first result until it goes)
+        held = (d_r, d_gl, d_gb, d_ng, d_ids, ws)
+        outs = [(o_r, (N, P, 1, 4)), (o_t, (N, P, 1, 4)), (o_l, (N, P, 1, 1)), (o_s, (N, P, 1, 1)), (o_i, (N, P, 1, 1)), (o_c, (N, 1, 1, 4))]
+        if return_all:
+            outs += [(a_l, (N, M, 1, 1)), (a_t, (N, M, 1, 4)), (a_s, (N, M, 1, 1))]
+        res = []
+        for buf, shp in outs:
+            t = DeviceTensor(buf.ptr, shp, shp[-1], owner=buf)
+            t.made_on, t._inputs = stream, held
+            res.append(t)
+        return tuple(res)
     synchronize(stream)
     out = (to_host(o_r.ptr, (N, P, 4), f32), to_host(o_t.ptr, (N, P, 4), f32), to_host(o_l.ptr, (N, P), np.int32),
            to_host(o_s.ptr, (N, P), f32), to_host(o_i.ptr, (N, P), np.int32), to_host(o_c.ptr, (N, 4), np.int32))
@@ -399,12 +416,16 @@ class AnchorEncoder(object):
         return out_l, out_t, out_s, out_b, len(self._anchors)
 
     def ext_encode_rois(self, all_rois, all_labels, all_bboxes, rois_per_image, fg_fraction, allowed_border,
-                        head_prior_scaling=[1., 1., 1., 1.], seed=0, n_gt=None, image_ids=None, stream=None):
+                        head_prior_scaling=[1., 1., 1., 1.], seed=0, n_gt=None, image_ids=None, stream=None, keep_device=False):
         """-> (rois f32 [N,P,4], targets f32 [N,P,4], labels int64 [N,P], scores f32 [N,P]).  all_rois: NumPy [N,R,4] or a
-        DeviceTensor (no host copy then); the shuffle is the defined one (module docstring), chosen by `seed`."""
+        DeviceTensor (no host copy then); the shuffle is the defined one (module docstring), chosen by `seed`.
+        keep_device=True: the four come back as encode_rois(..., keep_device=True) leaves them, DeviceTensors (labels i32) with
+        no synchronisation: model.get_head on a head_rois detector and losses.HeadLoss take them as they are."""
         r, t, l, s = encode_rois(all_rois, all_labels, all_bboxes, n_gt, allowed_border, self._rpn_fg_thres,
                                  self._rpn_bg_high_thres, self._rpn_bg_low_thres, head_prior_scaling, rois_per_image,
-                                 fg_fraction, seed, image_ids, False, stream)[:4]
+                                 fg_fraction, seed, image_ids, False, stream, keep_device)[:4]
+        if keep_device:
+            return r, t, l, s
         return r, t, l.astype(np.int64), s
 
     def decode_all_anchors(self, pred_location, squeeze_inner=False):

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import train_ops, ops
 from ._lib import lib, check, XdetError, InvalidArgumentError, MomentumSlot
-from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, _det, _sync
+from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, synchronize, _det, _sync
 
 __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEAD_VARIABLES', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
            'EXIT_FLOW_UNITS', 'EXIT_FLOW_BNS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
@@ -700,6 +700,38 @@ def new_body(d):
         getattr(d, STEM_STAGE.attr).n = 0
 
 
+# ---- the sampled-ROI head (LightHeadDetector(head_rois=P), option "head_rois") -----------------------------------------------
+
+def check_head_rois(head_rois, rpn_post_nms_top_n):
+    """the constructor's argument -> None (off) or P; refused by name ahead of the native net: anything but a whole number in
+    1..rpn_post_nms_top_n (the C side states the same bound for its option)"""
+    if head_rois is None:
+        return None
+    ok = isinstance(head_rois, (int, np.integer)) and not isinstance(head_rois, bool)
+    if not ok or not 1 <= int(head_rois) <= int(rpn_post_nms_top_n):
+        raise InvalidArgumentError(-1, 'head_rois must be None (off) or a whole number in 1..rpn_post_nms_top_n (%d), got %r'
+                                       % (rpn_post_nms_top_n, head_rois))
+    return int(head_rois)
+
+
+def rois_to_head(d, rois, n):
+    """get_head on a head_rois detector, handed its ROIs as a DeviceTensor [n,P,(1,)4] of dense corner boxes: one
+    device-to-device copy into the net's `head_rois` buffer on the detector's stream; none when it is that buffer.  A tensor
+    that ext_encode_rois(..., keep_device=True) made on another stream carries that stream: it is waited for first"""
+    view = d.buffer('head_rois', n)
+    shp = tuple(rois.shape)
+    if rois.ld != 4 or shp[-1] != 4 or shp[0] != n or int(np.prod(shp[1:-1])) != d.head_R:
+        raise InvalidArgumentError(-1, 'get_head: device ROIs must be dense corner boxes [N,%d,(1,)4] (ld 4), got %r (ld %d)'
+                                       % (d.head_R, shp, rois.ld))
+    if rois.ptr == view.ptr:
+        return
+    made_on = getattr(rois, 'made_on', d.stream)
+    if made_on is not d.stream:
+        synchronize(made_on)
+    check(lib().xdet_memcpy_d2d(view.ptr, rois.ptr, n * d.head_R * 16, d.stream.handle))
+    d._head_rois_src = rois                              # (alive until the next hand-over: the copy may still be in flight)
+
+
 # ---- the head's and the RPN head's backward -----------------------------------------------------------------------------------
 
 def _kernels(weights):
@@ -799,9 +831,9 @@ def head_backward(loss_func, to_feat=False, weight_grads='host'):
         raise InvalidArgumentError(-1, 'head_backward: the losses ran without a gradient (call get_head(..., is_training=True, '
                                        '...) with this loss_func first)')
     n, nc = g.shape[0], d.cfg.num_classes
-    if (g.shape[1], g.shape[3]) != (d.R, nc + 4) or n > d.max_batch:
+    if (g.shape[1], g.shape[3]) != (d.head_R, nc + 4) or n > d.max_batch:
         raise InvalidArgumentError(-1, 'head_backward: gradient of shape %r but the detector has %d ROIs per image, %d classes, '
-                                       'max_batch %d' % (g.shape, d.R, nc, d.max_batch))
+                                       'max_batch %d' % (g.shape, d.head_R, nc, d.max_batch))
     if len(_kernels(d._head_weights)) != 3:
         raise InvalidArgumentError(-1, 'head_backward: the detector was built without the final_head kernels')
     _check_step(d, 'head_backward', loss_func, '_head_step')
@@ -820,8 +852,8 @@ def head_backward(loss_func, to_feat=False, weight_grads='host'):
     wg.split({'K_0': dw0, 'b_0': db0, 'K_1': dw1, 'b_1': db1}, d.stream)
     _sync(d)
     out = wg.collect()
-    out.update({'pooled': DeviceTensor(dx0.ptr, (n, d.R, 1, K0), K0, owner=dx0),
-                'fc': DeviceTensor(dx1.ptr, (n, d.R, 1, K1), K1, owner=dx1)})
+    out.update({'pooled': DeviceTensor(dx0.ptr, (n, d.head_R, 1, K0), K0, owner=dx0),
+                'fc': DeviceTensor(dx1.ptr, (n, d.head_R, 1, K1), K1, owner=dx1)})
     if to_feat:
         out['feat'] = d_feat
     return out
