@@ -902,6 +902,32 @@ typedef struct {
 size_t xdet_momentum_step_workspace_bytes(const xdet_momentum_slot* slots_host, int n_slots);
 int xdet_momentum_step(const xdet_momentum_slot* slots_host, int n_slots, float lr, float momentum, float weight_decay, float* l2,
                        void* workspace, void* stream);
+/* The guard of the step: whether the gradients of a slot table may be applied, decided on the device.
+ * xdet_grad_stats reads `grad` of every slot (var and accum are not looked at and may be anything) in the chunks of
+ * xdet_momentum_step -- 4096 consecutive elements of one slot, one workgroup each, 128-bit accesses in a slot whose grad is
+ * 16-byte aligned -- and writes ONE 16-byte record to stats_dev (device memory, 4-byte aligned):
+ *     float   grad_sq         sum over all slots of sum grad^2, f32, in the fixed order of l2 above (vector, thread, the 256
+ *                             threads of a chunk pairwise, the C chunk partials pairwise; not halved).  NaN or +inf when a
+ *                             gradient is not finite or the sum overflows
+ *     int32_t nonfinite       the number of elements that are NaN, +inf or -inf (it stays at INT32_MAX, never wraps)
+ *     int32_t first_bad_slot  the lowest table index of a slot that holds one, -1 if none does
+ *     int32_t 0
+ * An element beyond a slot's end is absent: it adds +0 and is never counted, whatever lies there.  Two launches, the chunks'
+ * partials (sum, count, INT32_MAX-or-slot) and one workgroup that folds them (sum, sum, min) in the order the C partials of
+ * l2 fold; no float atomic, no fence, no workgroup that waits for another: the same call gives the same bits.
+ * xdet_momentum_step_guarded is xdet_momentum_step with one more argument.  skip_dev (an int32 in device memory, or NULL):
+ * every workgroup reads *skip_dev once; non-zero: nothing is stored to any var or accum -- their bytes stay -- while l2 is
+ * still written (it is computed from the values before the update either way).  NULL or zero: xdet_momentum_step, the same
+ * launches and the same bits.  The intended skip_dev is the address of the record's `nonfinite`, stats_dev + 4, after
+ * xdet_grad_stats on the same stream: the host decides nothing and waits for nothing.
+ * workspace of xdet_grad_stats: xdet_grad_stats_workspace_bytes(slots, n_slots) bytes (0 for a table the call refuses), under
+ * the rules of the step's; the two calls may not share one workspace unless the caller orders them on one stream.
+ * Errors and limits as xdet_momentum_step's, with these differences: xdet_grad_stats refuses a slot with a NULL grad (only)
+ * and a NULL or misaligned stats_dev. */
+size_t xdet_grad_stats_workspace_bytes(const xdet_momentum_slot* slots_host, int n_slots);
+int xdet_grad_stats(const xdet_momentum_slot* slots_host, int n_slots, void* stats_dev, void* workspace, void* stream);
+int xdet_momentum_step_guarded(const xdet_momentum_slot* slots_host, int n_slots, float lr, float momentum, float weight_decay,
+                               float* l2, const int32_t* skip_dev, void* workspace, void* stream);
 /* Rewrite, on the device and in place, every operand buffer a conv layer (xdet_conv_create) owns from a dense f32
  * [kh,kw,cin,cout] kernel in device memory: the transposed matrix of the f32 mode, or the per-row power-of-two pre-scale, the
  * f16 hi / lo split, the K-blocked copies, the fp8 x8 copy of a pointwise f16x3 layer and the epilogue scale (the scale the

@@ -71,6 +71,12 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the two stem convs (net/xception_body.py:243-258) with batch statistics and their backward,
                              block1_conv1 from the NCHW image by a kernel of its own (xdet_stem_conv3x3s2_train_forward); with
                              it MomentumOptimizer steps the whole network, 176 variables, and refreshes the eval net's stem
+  host_grad_stats, grad_stats_device, momentum_step_device(..., skip=) (xdet.ops); MomentumOptimizer.step(..., guard=, sync=),
+  StepPending, TrainStep, StepResult (xdet.model); encode_all_anchors(..., keep_device=True), losses.rpn_loss / HeadLoss
+  (..., device_result=True, buffers=)
+                          <- the reference's train_op as one call (light_head_rfcn_train.py:420-436, logged scalars
+                             :510-516), with nothing in the reference behind the guard: a pass over the gradients that
+                             decides on the device whether the momentum step stores anything
   jpeg_info, host_jpeg_coefficients, host_decode_jpeg, decode_jpegs_device, decode_jpegs (xdet.jpeg);
   LightHeadDetector.detect_jpegs (xdet.model)
                           <- tf.image.decode_image in front of the eval and training pipelines (dataset/dataset_common.py:542)

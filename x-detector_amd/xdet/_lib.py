@@ -206,6 +206,10 @@ SIGNATURES = {
     'xdet_add_upsample2': (c_int, [PF, c_int, PF, c_int, c_int, c_int, c_int, c_int, PF, c_int, c_void_p]),
     'xdet_momentum_step_workspace_bytes': (c_size_t, [ctypes.POINTER(MomentumSlot), c_int]),
     'xdet_momentum_step': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_void_p]),
+    'xdet_grad_stats_workspace_bytes': (c_size_t, [ctypes.POINTER(MomentumSlot), c_int]),
+    'xdet_grad_stats': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_void_p, c_void_p, c_void_p]),
+    'xdet_momentum_step_guarded': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_void_p,
+                                           c_void_p]),
     'xdet_grad_average_workspace_bytes': (c_size_t, [ctypes.POINTER(GradSlot), c_int, c_int, c_int64]),
     'xdet_grad_pack': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_void_p, c_void_p]),
     'xdet_grad_reduce_ranks': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_int, c_void_p, c_void_p]),

@@ -35,7 +35,9 @@ MAX_CLASSES = 128         # C
 
 class RpnLossResult(collections.namedtuple('RpnLossResult', 'losses sel_index counts grad_cls grad_loc')):
     """The five fields unpack as ever; `grad_device` (an attribute, not a field) is d loss / d rpn_out left on the GPU by
-    rpn_loss(..., keep_device=True): a DeviceTensor [N,h,w,6A] with the rpn_out buffer's ld, else None."""
+    rpn_loss(..., keep_device=True): a DeviceTensor [N,h,w,6A] with the rpn_out buffer's ld, else None.
+    From rpn_loss(..., device_result=True): losses, sel_index and counts are the DeviceBuffers the kernel wrote (f32 [3],
+    i32 [S], i32 [4]), grad_cls and grad_loc None, and nothing was synchronised."""
     grad_device = None
 
 
@@ -167,8 +169,15 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
+def _check_buffers(who, buffers):
+    if buffers is not None and not isinstance(buffers, dict):
+        from ._lib import InvalidArgumentError
+        raise InvalidArgumentError(-1, '%s: buffers must be a dict the caller keeps (filled on the first call), got %s'
+                                       % (who, type(buffers).__name__))
+
+
 def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio, seed=0, sigma=1., with_grad=True, stream=None,
-             keep_device=False):
+             keep_device=False, device_result=False, buffers=None):
     """host_rpn_loss on the GPU (xdet_rpn_loss), the same results.  cls_score / bbox_pred: NumPy [N,Hh,Ww,2A] / [N,Hh,Ww,4A]
     (or [N,n,2A] / [N,n,4A]), or the two DeviceTensor views model.get_rpn returns -- then the detector's rpn_out buffer is
     read in place, nothing is copied.  labels [N,n_a] / targets [N,n_a,4]: NumPy or device buffers (DeviceBuffer /
@@ -176,7 +185,11 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
     grad_cls [N,...,2A], grad_loc [N,...,4A] (None without with_grad).
     keep_device=True (the two views of get_rpn, cls_score [N,h,w,2A] followed by bbox_pred, and with_grad): the result's
     `grad_device` also carries the gradient as the GPU wrote it, a DeviceTensor [N,h,w,6A] with rpn_out's ld -- what
-    model.rpn_backward reads."""
+    model.rpn_backward reads.
+    device_result=True (default off; goes with keep_device=True and device labels and targets): losses, selection, counts and
+    gradient stay on the device -- the result's losses, sel_index and counts are DeviceBuffers -- and the call neither
+    downloads nor synchronises.  buffers (a dict the caller keeps, default None): workspace, results and gradient live in
+    it from the first call on, so a driver allocates them once; a later call overwrites what the earlier one returned."""
     from ._lib import lib, check, InvalidArgumentError
     from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
     if isinstance(cls_score, DeviceTensor) != isinstance(bbox_pred, DeviceTensor):
@@ -199,6 +212,9 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
     if keep_device and not (on_device and with_grad and len(shp) == 4 and cls_off == 0 and box_off == 2 * A):
         raise InvalidArgumentError(-1, 'rpn_loss: keep_device=True needs with_grad and the two DeviceTensor views model.get_rpn '
                                        'returns ([N,h,w,2A] and, right behind it, [N,h,w,4A])')
+    if device_result and not (keep_device and hasattr(labels, 'ptr') and hasattr(targets, 'ptr')):
+        raise InvalidArgumentError(-1, 'rpn_loss: device_result=True needs keep_device=True and labels and targets in device memory')
+    _check_buffers('rpn_loss', buffers)
     N, hw = int(shp[0]), int(np.prod(shp[1:-1]))
     S = N * int(anchors_per_image)
     fgr, sg = float(fg_ratio), float(sigma)
@@ -219,12 +235,20 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
         d_in = to_device(packed)
         in_ptr = d_in.ptr
     d_lab, d_tg = _device(labels, np.int32), _device(targets, f32)
-    ws = DeviceBuffer(lib().xdet_losses_workspace_bytes(N, int(anchors_per_image)))
-    d_sel, d_cnt, d_loss = DeviceBuffer(S * 4), DeviceBuffer(16), DeviceBuffer(16)
-    d_grad = DeviceBuffer(N * hw * ld * 4) if with_grad else None
+    _b = T._buffer
+    ws = _b(buffers, 'ws', lib().xdet_losses_workspace_bytes(N, int(anchors_per_image)))
+    d_sel, d_cnt, d_loss = _b(buffers, 'select', S * 4), _b(buffers, 'counts', 16), _b(buffers, 'losses', 16)
+    d_grad = _b(buffers, 'grad', N * hw * ld * 4) if with_grad else None
     check(lib().xdet_rpn_loss(in_ptr, ld, cls_off, box_off, N, hw, 1, A, d_lab.ptr, d_tg.ptr, int(anchors_per_image), fgr,
                               int(seed) & 0xFFFFFFFF, sg, ws.ptr, d_sel.ptr, d_cnt.ptr, d_loss.ptr, d_grad.ptr if d_grad else None,
                               _h(stream)))
+    if device_result:
+        res = RpnLossResult(d_loss, d_sel, d_cnt, None, None)
+        res.grad_device = DeviceTensor(d_grad.ptr, tuple(shp[:3]) + (6 * A,), ld, owner=d_grad)
+        res._inputs = (d_lab, d_tg, ws)                  # (alive with the result: the launch may still be in flight)
+        from .train import forward_step
+        res.forward_step = forward_step(cls_score, '_rpn_step')
+        return res
     synchronize(stream)
     g_cls = g_loc = None
     if with_grad:
@@ -241,11 +265,15 @@ def rpn_loss(cls_score, bbox_pred, labels, targets, anchors_per_image, fg_ratio,
 
 
 def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=1., num_classes=None, with_grad=True, stream=None,
-              device_grad=None):
+              device_grad=None, device_result=False, buffers=None):
     """host_head_loss on the GPU (xdet_head_loss), the same results.  cls_score [N,P,C] / bboxes_reg [N,P,4] as NumPy arrays;
     or cls_score = the detector's `cls_reg` DeviceTensor ([N,P,1,C+4]: C class logits, then the 4 regression outputs) with
     bboxes_reg None -- read in place.  labels [N,P] / targets [N,P,4]: NumPy or device buffers (as xdet_encode_rois wrote
-    them)."""
+    them).
+    device_result=True (default off; a device cls_reg tensor, device labels and targets, with_grad): losses, per_roi and
+    select of the result are the DeviceBuffers the kernel wrote (f32 [3], f32 [N,P], i32 [N,K]), grad_cls and grad_reg None,
+    the gradient is device_grad's one entry, and the call neither downloads nor synchronises.  buffers (a dict the caller
+    keeps, default None): workspace, results and gradient live in it from the first call on."""
     from ._lib import lib, check, InvalidArgumentError
     from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
     if isinstance(cls_score, DeviceTensor):
@@ -271,6 +299,10 @@ def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=
                                    % (N, P, MAX_ROIS, C, MAX_CLASSES, ld, k, fg_ratio, sigma))
     if n_lab is not None and n_lab != N * P:
         raise InvalidArgumentError(-1, 'head_loss: %d labels for %d ROIs' % (n_lab, N * P))
+    if device_result and not (isinstance(cls_score, DeviceTensor) and with_grad and hasattr(labels, 'ptr') and hasattr(targets, 'ptr')):
+        raise InvalidArgumentError(-1, 'head_loss: device_result=True needs the cls_reg DeviceTensor, with_grad and labels and targets '
+                                       'in device memory')
+    _check_buffers('head_loss', buffers)
     if not isinstance(cls_score, DeviceTensor):
         packed = np.zeros((N, P, ld), f32)
         packed[..., :C], packed[..., C:C + 4] = c, r
@@ -278,11 +310,18 @@ def head_loss(cls_score, bboxes_reg, labels, targets, fg_ratio, ohem_k=0, sigma=
         in_ptr = d_in.ptr
     K = min(k, P) if k > 0 else P
     d_lab, d_tg = _device(labels, np.int32), _device(targets, f32)
-    ws = DeviceBuffer(lib().xdet_losses_workspace_bytes(N, 0))
-    d_loss, d_per, d_sel = DeviceBuffer(16), DeviceBuffer(N * P * 4), DeviceBuffer(N * K * 4)
-    d_grad = DeviceBuffer(N * P * ld * 4) if with_grad else None
+    _b = T._buffer
+    ws = _b(buffers, 'ws', lib().xdet_losses_workspace_bytes(N, 0))
+    d_loss, d_per, d_sel = _b(buffers, 'losses', 16), _b(buffers, 'per_roi', N * P * 4), _b(buffers, 'select', N * K * 4)
+    d_grad = _b(buffers, 'grad', N * P * ld * 4) if with_grad else None
     check(lib().xdet_head_loss(in_ptr, ld, 0, C, N, P, C, d_lab.ptr, d_tg.ptr, fgr, k, sg, ws.ptr, d_loss.ptr, d_per.ptr, d_sel.ptr,
                                d_grad.ptr if d_grad else None, _h(stream)))
+    if device_result:
+        g = DeviceTensor(d_grad.ptr, (N, P, 1, C + 4), ld, owner=d_grad)
+        g._inputs = (d_lab, d_tg, ws)                    # (alive with the gradient: the launch may still be in flight)
+        if device_grad is not None:
+            device_grad.append(g)
+        return HeadLossResult(d_loss, d_per, d_sel, None, None)
     synchronize(stream)
     g_cls = g_reg = None
     if with_grad:
@@ -300,10 +339,13 @@ class HeadLoss(object):
     i32, read in place) and fg_ratio, as the reference's lambda closes over them
     (light_head_rfcn_train.py:407).  Calling it with the head's outputs gives the HeadLossResult; get_head leaves the last
     one in `.result` (losses, per_roi, select and the gradients) and returns the scalar; `.grad_device` is d loss / d cls_reg
-    on the GPU, in the `cls_reg` buffer's layout (model.head_backward reads it)."""
+    on the GPU, in the `cls_reg` buffer's layout (model.head_backward reads it).  device_result=True / buffers=: head_loss's
+    mode that leaves losses, per-ROI values and selection on the device and synchronises nothing (the result's three fields are
+    DeviceBuffers then), and the dict its buffers live in."""
 
-    def __init__(self, labels, targets, fg_ratio, sigma=1.):
+    def __init__(self, labels, targets, fg_ratio, sigma=1., device_result=False, buffers=None):
         self.labels, self.targets, self.fg_ratio, self.sigma = labels, targets, fg_ratio, sigma
+        self.device_result, self.buffers = device_result, buffers    # (head_loss's two arguments of these names; default off)
         self.result = None
         self.grad_device = None
 
@@ -316,7 +358,7 @@ class HeadLoss(object):
                 from .runtime import synchronize
                 synchronize(made_on)
         self.result = head_loss(cls_score, bboxes_reg, labels, self.targets, self.fg_ratio, ohem_k, self.sigma, num_classes,
-                                stream=stream, device_grad=kept)
+                                stream=stream, device_grad=kept, device_result=self.device_result, buffers=self.buffers)
         self.grad_device = kept[0] if kept else None
         from .train import forward_step
         self.forward_step = forward_step(cls_score, '_head_step')    # (which weights the forward ran with: head_backward's guard)

@@ -2,6 +2,7 @@
 
 Plain ctypes over libxdet_hip.so / libamdhip64 -- no PyTorch in the product path.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -89,6 +90,22 @@ def synchronize(stream=None):
     check(lib().xdet_stream_sync(stream.handle if stream else None))
 
 
+# A driver that runs a whole chain of calls on one stream and reads back once (train.TrainStep) defers the waits its stages end
+# with: inside `with deferred(stream):` a stage's closing _sync of a detector on that stream returns at once, and a buffer that
+# is zeroed on creation is zeroed by a memset on that stream, in order with the launches that follow, instead of a memset the
+# host waits for.  Nothing else changes: the same calls in the same order on the same stream.
+_deferred = []
+
+
+@contextlib.contextmanager
+def deferred(stream):
+    _deferred.append(stream)
+    try:
+        yield stream
+    finally:
+        _deferred.pop()
+
+
 class DeviceBuffer(object):
     """An owned hipMalloc allocation."""
     def __init__(self, nbytes, zero=False):
@@ -96,7 +113,9 @@ class DeviceBuffer(object):
         check(lib().xdet_malloc(ctypes.byref(p), nbytes))
         self.ptr = p.value
         self.nbytes = nbytes
-        if zero:
+        if zero and _deferred:
+            check(lib().xdet_memset(self.ptr, 0, nbytes, _deferred[-1].handle))
+        elif zero:
             check(lib().xdet_memset(self.ptr, 0, nbytes, None))
             synchronize()
 
@@ -193,4 +212,5 @@ def _det():
 
 
 def _sync(d):
-    d.stream.synchronize()
+    if not (_deferred and _deferred[-1] is d.stream):
+        d.stream.synchronize()

@@ -263,13 +263,30 @@ def _h(stream):
     return stream.handle if stream is not None else None
 
 
+def _buffer(buffers, key, nbytes, fill=None):
+    """a DeviceBuffer of at least nbytes: a new one (buffers None), or the caller's dict entry `key`, made on first use and
+    kept there, so a driver that passes the same dict every step allocates once.  fill: a host array uploaded into a new one"""
+    from .runtime import DeviceBuffer, to_device
+    b = buffers.get(key) if buffers is not None else None
+    if b is None or b.nbytes < nbytes:
+        b = to_device(fill) if fill is not None else DeviceBuffer(max(nbytes, 16))
+        if buffers is not None:
+            buffers[key] = b
+    return b
+
+
 def encode_anchors(anchor, labels, bboxes, n_gt=None, allowed_border=0., high_thr=0.7, low_thr=0.3,
-                   prior_scaling=(1., 1., 1., 1.), stream=None):
+                   prior_scaling=(1., 1., 1., 1.), stream=None, keep_device=False, buffers=None):
     """host_encode_anchors on the GPU (xdet_encode_anchors) -> (labels i32 [N,HWA], targets f32 [N,HWA,4], scores f32 [N,HWA]).
     labels / bboxes / n_gt may be the DeviceTensors of augment.preprocess_train ([N,1,1,G] i32, [N,G,1,4] f32, [1,1,1,N]
-    i32): they are read where they are, nothing is copied to the host."""
+    i32): they are read where they are, nothing is copied to the host.
+    keep_device=True (default off): the three stay where the kernel wrote them -- DeviceTensors [N,HWA,1,1] (labels i32),
+    [N,HWA,1,4] and [N,HWA,1,1], each carrying the stream it was made on (`made_on`) -- and the call does not synchronise;
+    losses.rpn_loss reads labels and targets in place.  buffers (a dict the caller keeps, default None): the anchors' device
+    copy, the workspace and the three results live in it from the first call on, so later calls allocate and upload nothing
+    -- and overwrite what the earlier call returned."""
     from ._lib import lib, check
-    from .runtime import to_device, to_host, DeviceBuffer, synchronize
+    from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
     on_device = _device_ground_truth(labels, bboxes, n_gt)
     if on_device:
         N, G = labels.shape[0], labels.shape[3]
@@ -287,20 +304,30 @@ def encode_anchors(anchor, labels, bboxes, n_gt=None, allowed_border=0., high_th
         check(lib().xdet_encode_anchors(None, None, Hh, Ww, A, args[0], None, None, None, N, G, thr[0], thr[1], sc4, None, None,
                                         None, None, None))
     n_a = Hh * Ww * A
-    yx = to_device(np.stack([yref.reshape(-1), xref.reshape(-1)], 1).astype(f32))
-    hw = to_device(np.stack([href.reshape(-1), wref.reshape(-1)], 1).astype(f32))
+    if buffers is not None and 'yx' in buffers:          # (the anchors of an encoder do not change)
+        yx, hw = buffers['yx'], buffers['hw']
+    else:
+        yx = _buffer(buffers, 'yx', 0, np.stack([yref.reshape(-1), xref.reshape(-1)], 1).astype(f32))
+        hw = _buffer(buffers, 'hw', 0, np.stack([href.reshape(-1), wref.reshape(-1)], 1).astype(f32))
     d_gl, d_gb, d_ng = (labels, bboxes, n_gt) if on_device else (to_device(gl), to_device(gb), to_device(ng))
-    ws = DeviceBuffer(max(lib().xdet_targets_workspace_bytes(N, 0, G), 16))
-    d_l, d_t, d_s = DeviceBuffer(N * n_a * 4), DeviceBuffer(N * n_a * 16), DeviceBuffer(N * n_a * 4)
+    ws = _buffer(buffers, 'ws', lib().xdet_targets_workspace_bytes(N, 0, G))
+    d_l, d_t, d_s = _buffer(buffers, 'labels', N * n_a * 4), _buffer(buffers, 'targets', N * n_a * 16), _buffer(buffers, 'scores', N * n_a * 4)
     check(lib().xdet_encode_anchors(yx.ptr, hw.ptr, Hh, Ww, A, args[0], d_gl.ptr, d_gb.ptr, d_ng.ptr, N, G, thr[0], thr[1], sc4,
                                     ws.ptr, d_l.ptr, d_t.ptr, d_s.ptr, _h(stream)))
+    if keep_device:
+        res = []
+        for buf, w in ((d_l, 1), (d_t, 4), (d_s, 1)):
+            t = DeviceTensor(buf.ptr, (N, n_a, 1, w), w, owner=buf)
+            t.made_on, t._inputs = stream, (yx, hw, d_gl, d_gb, d_ng, ws)
+            res.append(t)
+        return tuple(res)
     synchronize(stream)
     return (to_host(d_l.ptr, (N, n_a), np.int32), to_host(d_t.ptr, (N, n_a, 4), f32), to_host(d_s.ptr, (N, n_a), f32))
 
 
 def encode_rois(rois, labels, bboxes, n_gt=None, allowed_border=0.1, fg_thr=0.5, bg_high_thr=0.5, bg_low_thr=0.,
                 prior_scaling=(1., 1., 1., 1.), rois_per_image=256, fg_fraction=0.25, seed=0, image_ids=None,
-                return_all=False, stream=None, keep_device=False):
+                return_all=False, stream=None, keep_device=False, buffers=None):
     """host_encode_rois on the GPU (xdet_encode_rois), same results in the same order.  rois: NumPy [N,R,4], or a
     DeviceTensor / DeviceBuffer holding N * R * 4 floats (then `rois` is not copied; give R through its shape [N,R,1,4] or
     [N,R,4]) -- e.g. the `proposals` buffer of a LightHeadDetector.
@@ -308,11 +335,18 @@ def encode_rois(rois, labels, bboxes, n_gt=None, allowed_border=0.1, fg_thr=0.5,
     out_targets as f32 DeviceTensors [N,P,1,4] (ld 4), out_labels (i32), out_scores and out_index (i32) [N,P,1,1], counts
     (i32) [N,1,1,4] (with return_all the three unsampled arrays likewise), each carrying the stream it was made on
     (`made_on`): model.get_head on a head_rois detector copies the ROIs device to device, losses.HeadLoss reads labels and
-    targets in place.  DeviceTensor.numpy() reads f32: download an i32 one with runtime.to_host(t.ptr, shape, np.int32)."""
+    targets in place.  DeviceTensor.numpy() reads f32: download an i32 one with runtime.to_host(t.ptr, shape, np.int32).
+    labels / bboxes / n_gt may be the DeviceTensors of augment.preprocess_train, read where they are (as encode_anchors takes
+    them).  buffers (a dict the caller keeps, default None): the workspace and every result live in it from the first call on
+    -- later calls allocate nothing and overwrite what the earlier call returned."""
     from ._lib import lib, check, InvalidArgumentError
     from .runtime import to_device, to_host, DeviceBuffer, DeviceTensor, synchronize
-    gl, gb, ng = ground_truth(labels, bboxes, n_gt)
-    N, G = gl.shape
+    gt_on_device = _device_ground_truth(labels, bboxes, n_gt)
+    if gt_on_device:
+        N, G = labels.shape[0], labels.shape[3]
+    else:
+        gl, gb, ng = ground_truth(labels, bboxes, n_gt)
+        N, G = gl.shape
     if isinstance(rois, DeviceTensor):
         shp = tuple(rois.shape)
         if shp[0] != N or shp[-1] != 4 or rois.ld != 4:
@@ -335,12 +369,13 @@ def encode_rois(rois, labels, bboxes, n_gt=None, allowed_border=0.1, fg_thr=0.5,
                                      None, None, None, None, None, None, None, None, None, None))
     if d_r is None:
         d_r = to_device(r)
-    d_gl, d_gb, d_ng = to_device(gl), to_device(gb), to_device(ng)
+    d_gl, d_gb, d_ng = (labels, bboxes, n_gt) if gt_on_device else (to_device(gl), to_device(gb), to_device(ng))
     d_ids = to_device(np.ascontiguousarray(image_ids, np.int32).reshape(N)) if image_ids is not None else None
     M = R + G
-    ws = DeviceBuffer(lib().xdet_targets_workspace_bytes(N, M, G))
-    o_r, o_t = DeviceBuffer(N * P * 16), DeviceBuffer(N * P * 16)
-    o_l, o_s, o_i, o_c = DeviceBuffer(N * P * 4), DeviceBuffer(N * P * 4), DeviceBuffer(N * P * 4), DeviceBuffer(N * 16)
+    ws = _buffer(buffers, 'ws', lib().xdet_targets_workspace_bytes(N, M, G))
+    o_r, o_t = _buffer(buffers, 'rois', N * P * 16), _buffer(buffers, 'targets', N * P * 16)
+    o_l, o_s, o_i, o_c = (_buffer(buffers, 'labels', N * P * 4), _buffer(buffers, 'scores', N * P * 4), _buffer(buffers, 'index', N * P * 4),
+                          _buffer(buffers, 'counts', N * 16))
     a_l = a_t = a_s = None
     if return_all:
         a_l, a_t, a_s = DeviceBuffer(N * M * 4), DeviceBuffer(N * M * 16), DeviceBuffer(N * M * 4)
@@ -393,10 +428,13 @@ class AnchorEncoder(object):
         height, width = (ymax - ymin), (xmax - xmin)
         return ymin + height / f32(2.), xmin + width / f32(2.), height, width
 
-    def encode_all_anchors(self, labels, bboxes, n_gt=None, stream=None):
+    def encode_all_anchors(self, labels, bboxes, n_gt=None, stream=None, keep_device=False):
         """labels / bboxes: one image ([g] / [g,4], as in the reference's input pipeline), a list of per-image arrays, or
         padded [N,G] / [N,G,4] with n_gt -> (labels, targets, scores, anchor_boxes, n_layers), lists per layer; labels int64.
-        A single image gives arrays without the batch axis."""
+        A single image gives arrays without the batch axis.
+        keep_device=True (default off): labels (i32), targets and scores stay as xdet_encode_anchors wrote them, DeviceTensors
+        per layer with the batch axis (encode_anchors(..., keep_device=True)); nothing is downloaded or synchronised, and from
+        the second call on nothing is allocated: the encoder keeps the buffers, so a call overwrites what the last returned."""
         if _device_ground_truth(labels, bboxes, n_gt):      # augment.preprocess_train's outputs, as they are
             single, (gl, gb, ng) = False, (labels, bboxes, n_gt)
         else:
@@ -406,6 +444,15 @@ class AnchorEncoder(object):
             gl, gb, ng = ground_truth(labels, bboxes, n_gt)
         out_l, out_t, out_s, out_b = [], [], [], []
         for layer, anchor in enumerate(self._anchors):
+            if keep_device:
+                kept = self.__dict__.setdefault('_device_buffers', {}).setdefault(layer, {})
+                l, t, s = encode_anchors(anchor, gl, gb, ng, self._allowed_borders[layer], self._positive_threshold,
+                                         self._ignore_threshold, self._prior_scaling, stream, True, kept)
+                out_l.append(l)
+                out_t.append(t)
+                out_s.append(s)
+                out_b.append(anchor_boxes(anchor)[0])
+                continue
             l, t, s = encode_anchors(anchor, gl, gb, ng, self._allowed_borders[layer], self._positive_threshold,
                                      self._ignore_threshold, self._prior_scaling, stream)
             l = l.astype(np.int64)
@@ -416,14 +463,15 @@ class AnchorEncoder(object):
         return out_l, out_t, out_s, out_b, len(self._anchors)
 
     def ext_encode_rois(self, all_rois, all_labels, all_bboxes, rois_per_image, fg_fraction, allowed_border,
-                        head_prior_scaling=[1., 1., 1., 1.], seed=0, n_gt=None, image_ids=None, stream=None, keep_device=False):
+                        head_prior_scaling=[1., 1., 1., 1.], seed=0, n_gt=None, image_ids=None, stream=None, keep_device=False,
+                        buffers=None):
         """-> (rois f32 [N,P,4], targets f32 [N,P,4], labels int64 [N,P], scores f32 [N,P]).  all_rois: NumPy [N,R,4] or a
         DeviceTensor (no host copy then); the shuffle is the defined one (module docstring), chosen by `seed`.
         keep_device=True: the four come back as encode_rois(..., keep_device=True) leaves them, DeviceTensors (labels i32) with
         no synchronisation: model.get_head on a head_rois detector and losses.HeadLoss take them as they are."""
         r, t, l, s = encode_rois(all_rois, all_labels, all_bboxes, n_gt, allowed_border, self._rpn_fg_thres,
                                  self._rpn_bg_high_thres, self._rpn_bg_low_thres, head_prior_scaling, rois_per_image,
-                                 fg_fraction, seed, image_ids, False, stream, keep_device)[:4]
+                                 fg_fraction, seed, image_ids, False, stream, keep_device, buffers)[:4]
         if keep_device:
             return r, t, l, s
         return r, t, l.astype(np.int64), s

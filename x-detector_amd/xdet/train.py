@@ -27,7 +27,7 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEA
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
            'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'optimizer_variables',
-           'MomentumOptimizer', 'STEM_CONVS', 'STEM_VARIABLES', 'STEM_MOVING', 'STEM_EPS', 'STEM_MOMENTUM', 'STEM_STAGE', 'STEM', 'StemState',
+           'MomentumOptimizer', 'StepPending', 'TrainStep', 'StepResult', 'LOGGED_SCALARS', 'STEM_CONVS', 'STEM_VARIABLES', 'STEM_MOVING', 'STEM_EPS', 'STEM_MOMENTUM', 'STEM_STAGE', 'STEM', 'StemState',
            'check_stem', 'stem_train', 'stem_backward', 'host_stem_train', 'host_stem_backward']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
@@ -1361,13 +1361,47 @@ def eval_net_groups(names):
     return groups
 
 
+class StepPending(object):
+    """What MomentumOptimizer.step(..., sync=False) returns: the step's scalars are still on the device.  read() -> the dict
+    step returns with sync=True, after ONE synchronisation of the detector's stream (a second read() returns the same dict
+    and touches nothing); it is also what releases the optimizer for its next step."""
+
+    def __init__(self, opt, lr, guard):
+        self.opt, self.lr, self.guard, self.result, self._alive = opt, lr, guard, None, None
+        self.l2 = self.stats = None                        # the device buffers the scalars lie in (set by step)
+
+    def read(self):
+        if self.result is not None:
+            return self.result
+        opt = self.opt
+        _sync(opt.det)
+        if opt.reach == 'all':
+            opt._concat[0][0]._keep = None                 # (concat_device's keep-alive chain: the stream has run)
+        self.l2._keep = self._alive = None
+        out = {'step': None, 'lr': self.lr, 'l2': float(to_host(self.l2.ptr, (1,))[0])}
+        if self.guard:
+            self.stats._keep = None
+            rec = to_host(self.stats.ptr, (1,), train_ops.GRAD_STATS_DTYPE)[0]
+            skipped = int(rec['nonfinite']) != 0
+            if not skipped:
+                opt.steps += 1
+            with np.errstate(invalid='ignore'):
+                out['grad_norm'] = float(np.sqrt(np.float64(rec['grad_sq'])))
+            out['skipped'] = skipped
+            out['first_bad'] = opt.variables[int(rec['first_bad_slot'])] if skipped else None
+        out['step'] = opt.steps
+        opt._pending, self.result = None, out
+        return out
+
+
 class MomentumOptimizer(object):
     """tf.train.MomentumOptimizer(lr, momentum) over the loss the reference minimises, loss + weight_decay * sum l2_loss(v) over
     the variables `decayed` names (light_head_rfcn_train.py:420,435), for the flow stages `det` was built with: the variables
     of ENTRY_FLOW_VARIABLES + MIDDLE_FLOW_VARIABLES + EXIT_FLOW_VARIABLES whose stage is on, in that order (148 with all
     three, 15 + 48 + 9 = 72 of them kernels in the L2 set).  The masters are the buffers the stages already hold -- SepUnit.K_dw,
     SepUnit.K_pw, Projection.K, BatchNorm.gamma, BatchNorm.beta -- updated in place; the optimizer allocates the momentum slots
-    (zero) and the step's workspace and holds a second copy of nothing.
+    (zero) and the step's workspace and holds a second copy of nothing -- what protects the masters from a gradient that is
+    not finite is step(..., guard=True), which decides on the device and stores nothing to them when one is.
     Out of its reach (reach='flows', the default): the large-separable block, the head and the RPN head keep their weights (and the stem, on a detector built without stem_train).  The NATIVE EVAL NET
     keeps the weights it last folded -- XceptionBody(..., is_training=False), forward, detect_images and evaluate compute with
     them -- until refresh_eval_net() refolds the body's blocks 2-14 from the masters and the training stages' moving statistics
@@ -1384,6 +1418,7 @@ class MomentumOptimizer(object):
 
     reach = 'flows'
     _stem = None                                           # StemState of a detector built with stem_train=True
+    _pending = None                                        # the StepPending of a step(..., sync=False) that has not been read
 
     def __init__(self, det, momentum=0.9, weight_decay=2e-4, reach='flows'):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
@@ -1426,6 +1461,9 @@ class MomentumOptimizer(object):
         for i, v in enumerate(self.variables):                            # (sizes only: the workspace depends on nothing else)
             table[i] = MomentumSlot(1, 1, 1, int(np.prod(self._master[v][1])), 0)
         self._ws = DeviceBuffer(lib().xdet_momentum_step_workspace_bytes(table, len(self.variables)))
+        # the guard's workspace, its 16-byte record and the step's l2: allocated once, so a step allocates nothing
+        self._stats_ws = DeviceBuffer(lib().xdet_grad_stats_workspace_bytes(table, len(self.variables)))
+        self._stats, self._l2, self._pending = DeviceBuffer(16), DeviceBuffer(16), None
         self._refresh_ws = None                            # (an optimizer over no layers has none, and step refreshes nothing)
         if self._refresh_slots():
             rtable, _ = train_ops.refresh_layers_table(self._refresh_slots())
@@ -1478,7 +1516,7 @@ class MomentumOptimizer(object):
     def _stem_batch_norms(self):
         return [self._stem.bn1, self._stem.bn2] if self._stem is not None else []
 
-    def step(self, grads, lr, comm=None):
+    def step(self, grads, lr, comm=None, guard=False, sync=True):
         """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
         backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
         stream: one xdet_momentum_step over all variables; the refresh of the forward layers (every unit's pointwise and
@@ -1505,7 +1543,22 @@ class MomentumOptimizer(object):
         conv_b join the xdet_layers_refresh_device table with their biases; and xdet_net_refresh_heads refreshes the net's own RPN
         and head layers, which the eval net and the training forward share.  What get_rpn, get_head and the losses left is stale:
         rpn_backward and head_backward refuse a loss result from before the step until the forward has run again.  The number
-        of launches does not depend on the number of variables."""
+        of launches does not depend on the number of variables.
+        guard=True: behind the rank average and ahead of the step, xdet_grad_stats runs over the gradients of `self.variables`
+        (after the average every rank decides on the same bits) and the step is xdet_momentum_step_guarded on the record's
+        count of non-finite elements: where one gradient element is NaN or +-inf no master and no momentum byte changes --
+        the host decides nothing and waits for nothing.  Everything behind the step runs either way: the refresh rebuilds the
+        same operands from the unchanged masters, and the saved state is dropped all the same (the batch that made it is
+        spent).  The result gains 'grad_norm' (the square root of the record's grad_sq, NaN or inf on a skipped step),
+        'skipped' and 'first_bad' (the name of the first variable, in `self.variables`' order, whose gradient holds such an
+        element, else None); `self.steps`, and the result's 'step', advance only when the step was taken.
+        sync=False: nothing is read back and nothing is synchronised; -> a StepPending whose read() synchronises the
+        detector's stream once, reads l2 (and the record) and returns the dict above; the keep-alive references the
+        synchronisation bounds live until then, and so does `self.steps` under guard=True.  The buffers the scalars lie in are
+        the optimizer's own, so the next step is refused until read() has been called."""
+        if self._pending is not None:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the result of the last step(..., sync=False) has not been read: '
+                                           'call its read() first (the next step writes the same l2 and guard record)')
         miss = [v for v in self.variables if v not in grads]
         if miss:
             raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradients lack %s' % ', '.join(miss))
@@ -1520,7 +1573,11 @@ class MomentumOptimizer(object):
         if comm is not None:
             comm.average_gradients([grads[v] for v in self.variables], d.stream)
             comm.wait()
-        l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws)
+        stats = train_ops.grad_stats_device(slots, stream=d.stream, workspace=self._stats_ws, out=self._stats) if guard else None
+        more = {'skip': stats} if guard else {}            # (the default path makes the call it always made)
+        if getattr(self, '_l2', None) is not None:
+            more['l2_out'] = self._l2
+        l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws, **more)
         if self.reach == 'all':                            # the merged tensors the layers and the backwards read, from the masters
             train_ops.concat_device(self._concat, stream=d.stream, workspace=self._concat_ws)
             b0, b1, bb, co = self._bias_sum
@@ -1532,12 +1589,11 @@ class MomentumOptimizer(object):
             d.refresh_heads({v: self._master[v][0] for v in self._head_names})
             d._heads_step = getattr(d, '_heads_step', 0) + 1
         new_body(d)
-        _sync(d)
-        if self.reach == 'all':
-            self._concat[0][0]._keep = None                # (concat_device's keep-alive chain: the stream has run)
-        l2._keep = None
-        self.steps += 1
-        return {'step': self.steps, 'lr': float(lr), 'l2': float(to_host(l2.ptr, (1,))[0])}
+        if not guard:                                      # (a guarded step counts once its record has been read)
+            self.steps += 1
+        self._pending = StepPending(self, float(lr), guard)
+        self._pending.l2, self._pending.stats = l2, stats
+        return self._pending.read() if sync else self._pending
 
     def _refresh_slots(self):
         """the training forward layers and their masters, as the units hold them at this moment: refresh_layers_device's table"""
@@ -1627,6 +1683,187 @@ class MomentumOptimizer(object):
             for k in ('moving_mean', 'moving_variance'):
                 out['%s/%s' % (bn.name, k)] = to_host(getattr(bn, k).ptr, (bn.co,))
         return out
+
+
+# ---- the single-call driver: one training step from a batch ------------------------------------------------------------------
+
+LOGGED_SCALARS = ('rpn_ce_loss', 'rpn_loc_loss', 'rpn_loss', 'head_loss', 'head_ce_loss', 'head_loc_loss', 'total_loss')
+
+
+class StepResult(object):
+    """What TrainStep.step returns: every scalar of the step is still on the device.  read() -> a dict, after ONE
+    synchronisation of the detector's stream (the optimizer's StepPending.read(); a second read() returns the same dict):
+    the reference's seven logged scalars under the names of light_head_rfcn_train.py:510-516 -- rpn_ce_loss, rpn_loc_loss,
+    rpn_loss, head_loss, head_ce_loss, head_loc_loss (f32 as the loss kernels wrote them) and total_loss =
+    ((rpn_ce_loss + rpn_loc_loss) + head_loss) + weight_decay * l2 in f32, the order of line 420 -- and l2, grad_norm, skipped,
+    first_bad, step and lr as MomentumOptimizer.step(..., guard=True) returns them (grad_norm, skipped and first_bad only
+    from a guarded step)."""
+
+    def __init__(self, pending, rpn_losses, head_losses, weight_decay):
+        self.pending, self._rpn, self._head, self._wd, self.result = pending, rpn_losses, head_losses, weight_decay, None
+
+    def read(self):
+        if self.result is None:
+            info = self.pending.read()                     # (the one synchronisation; the downloads below wait for nothing)
+            rpn, head = to_host(self._rpn.ptr, (3,)), to_host(self._head.ptr, (3,))
+            f = np.float32
+            with np.errstate(invalid='ignore', over='ignore'):
+                total = ((rpn[0] + rpn[1]) + head[0]) + f(self._wd) * f(info['l2'])
+            out = dict(zip(LOGGED_SCALARS, (rpn[0], rpn[1], rpn[2], head[0], head[1], head[2], f(total))))
+            out.update(info)
+            self.result, self._rpn, self._head = out, None, None
+        return self.result
+
+
+class TrainStep(object):
+    """One training step in one call: step(images, glabels, gboxes, n_gt, lr, seed) -> StepResult.  The stages are the chain the
+    tests make by hand, on ONE detector and in this order, all on the detector's stream: the anchors' labels and targets
+    (encoder.encode_all_anchors(..., keep_device=True)); the eval body (xdet_net_xception_body); stem_train on a detector
+    built with it, entry_flow_train, middle_flow_train, exit_flow_train; get_rpn, rpn_decode and get_proposals on the net's own
+    buffers (the three C calls, no download and upload of objectness and boxes in between); the sampled ROIs
+    (encoder.ext_encode_rois(proposals, ..., keep_device=True)); large_sep_kernel in training mode; get_head on the sampled
+    ROIs and the head loss with OHEM (losses.HeadLoss(..., device_result=True)); head_backward(to_feat=True), large_sep_backward,
+    losses.rpn_loss(..., device_result=True), rpn_backward, exit_flow_backward (with the RPN's share of d mid),
+    middle_flow_backward, entry_flow_backward and, with the stem, stem_backward, all with weight_grads='device'; and
+    opt.step(grads, lr, guard=guard, sync=False).  Between the first launch and StepResult.read() the host waits for nothing
+    and reads nothing back (runtime.deferred: the stages' closing waits are skipped, buffers that start zeroed are zeroed on
+    the stream): the same kernels on the same operands as the chain made by hand, so the same bits.
+    The inputs are what augment.preprocess_train leaves on the device: images f32 NCHW [N,3,S,S], glabels i32 [N,1,1,G],
+    gboxes f32 [N,G,1,4], n_gt i32 [1,1,1,N], N at most max_batch; host arrays (images [N,3,S,S]; labels and boxes as
+    targets.ground_truth takes them, n_gt or None) are uploaded first, which waits for the copies.  step_images(images_u8,
+    labels, bboxes, lr, seed) runs augment.preprocess_train(..., seed) in front.
+    The sampling seeds are functions of `seed` alone (TrainStep.seeds): the RPN's anchor sampling draws with 2 * seed, the ROI
+    sampling with 2 * seed + 1, both modulo 2^32; step_images hands `seed` itself to the augmentation.
+    guard=True: a gradient that is not finite skips the update on the device (MomentumOptimizer.step).  The loss buffers, the
+    anchor and ROI targets and the guard record are allocated on the first step and reused.
+    Refused ahead of any launch, in one sentence that lists everything missing: a detector built without head_rois,
+    pool_index, rpn_hidden, large_sep_train or one of the three flow stages, an optimizer of another detector or without
+    reach='all', and arguments that differ from what the detector was built with."""
+
+    def __init__(self, det, opt, encoder, *, rpn_anchors_per_image=256, rpn_fg_ratio, roi_one_image, fg_ratio, ohem_roi_one_image,
+                 nms_threshold, rpn_min_size, guard=True, allowed_border=0.1):
+        lack = [what for what, have in (('head_rois=%r' % (roi_one_image,), getattr(det, 'head_rois', None) is not None),
+                                        ('pool_index=True', getattr(det, 'pool_index', False)),
+                                        ('rpn_hidden=True', getattr(det, 'rpn_hidden', False)),
+                                        ('large_sep_train=True', getattr(det, 'large_sep_train', False)),
+                                        ('exit_flow_train=True', getattr(det, 'exit_flow_train', False)),
+                                        ('middle_flow_train=True', getattr(det, 'middle_flow_train', False)),
+                                        ('entry_flow_train=True', getattr(det, 'entry_flow_train', False))) if not have]
+        needs = ['a detector built with ' + ', '.join(lack)] if lack else []
+        if getattr(opt, 'det', None) is not det or getattr(opt, 'reach', None) != 'all':
+            needs.append("a MomentumOptimizer(det, reach='all') of this detector")
+        if needs:
+            raise InvalidArgumentError(-1, 'TrainStep: the step needs ' + ' and '.join(needs))
+        cfg = det.cfg
+        differ = [what for what, ok in (('roi_one_image = %r (head_rois = %r)' % (roi_one_image, det.head_rois), roi_one_image == det.head_rois),
+                                        ('nms_threshold = %r (%r)' % (nms_threshold, cfg.rpn_nms_thres),
+                                         np.float32(nms_threshold) == np.float32(cfg.rpn_nms_thres)),
+                                        ('rpn_min_size = %r (%r)' % (rpn_min_size, cfg.rpn_min_size),
+                                         np.float32(rpn_min_size) == np.float32(cfg.rpn_min_size)),
+                                        ('ohem_roi_one_image = %r (1 .. roi_one_image)' % (ohem_roi_one_image,),
+                                         isinstance(ohem_roi_one_image, (int, np.integer)) and 1 <= ohem_roi_one_image <= det.head_rois),
+                                        ('rpn_anchors_per_image = %r (positive)' % (rpn_anchors_per_image,),
+                                         isinstance(rpn_anchors_per_image, (int, np.integer)) and rpn_anchors_per_image > 0),
+                                        ('an encoder of %d anchor layers (1)' % len(getattr(encoder, '_anchors', ())),
+                                         len(getattr(encoder, '_anchors', ())) == 1)) if not ok]
+        if differ:
+            raise InvalidArgumentError(-1, 'TrainStep: arguments that differ from what the detector was built with: ' + ', '.join(differ))
+        self.det, self.opt, self.encoder, self.guard = det, opt, encoder, bool(guard)
+        self.rpn_anchors_per_image, self.rpn_fg_ratio = int(rpn_anchors_per_image), float(rpn_fg_ratio)
+        self.roi_one_image, self.fg_ratio, self.ohem_roi_one_image = int(roi_one_image), float(fg_ratio), int(ohem_roi_one_image)
+        self.allowed_border = float(allowed_border)
+        self._variables = set(opt.variables)
+        self._rpn_buffers, self._head_buffers, self._roi_buffers = {}, {}, {}
+
+    @staticmethod
+    def seeds(seed):
+        """-> (the seed of the RPN's anchor sampling, the seed of the ROI sampling): 2 * seed and 2 * seed + 1 modulo 2^32"""
+        return (2 * int(seed)) & 0xFFFFFFFF, (2 * int(seed) + 1) & 0xFFFFFFFF
+
+    def upload(self, images, glabels, gboxes, n_gt=None):
+        """-> the four inputs of step as DeviceTensors in preprocess_train's layout: device tensors pass, host arrays are
+        uploaded (each upload waits for its copy); a wrong shape is refused"""
+        from . import targets as T
+        d, S = self.det, self.det.image_size
+        if not isinstance(images, DeviceTensor):
+            a = np.ascontiguousarray(images, np.float32)
+            if a.ndim == 4 and a.shape[1:] == (3, S, S):
+                b = to_device(a)
+                images = DeviceTensor(b.ptr, a.shape, S, owner=b)
+        if (not isinstance(images, DeviceTensor) or len(images.shape) != 4 or tuple(images.shape[1:]) != (3, S, S) or images.ld != S
+                or not 1 <= images.shape[0] <= d.max_batch):
+            raise InvalidArgumentError(-1, 'TrainStep.step: images must be f32 [n,3,%d,%d] (NCHW, dense) of 1 to %d images, got %r'
+                                           % (S, S, d.max_batch, getattr(images, 'shape', None)))
+        if not T._device_ground_truth(glabels, gboxes, n_gt):
+            gl, gb, ng = T.ground_truth(glabels, gboxes, n_gt)
+            if gl.shape[1] == 0:
+                gl, gb = np.zeros((gl.shape[0], 1), np.int32), np.zeros((gl.shape[0], 1, 4), np.float32)
+            N, G = gl.shape
+            bl, bb, bn = to_device(gl.astype(np.int32)), to_device(gb.astype(np.float32)), to_device(ng.astype(np.int32))
+            glabels, gboxes, n_gt = (DeviceTensor(bl.ptr, (N, 1, 1, G), G, owner=bl), DeviceTensor(bb.ptr, (N, G, 1, 4), 4, owner=bb),
+                                     DeviceTensor(bn.ptr, (1, 1, 1, N), N, owner=bn))
+        if glabels.shape[0] != images.shape[0]:
+            raise InvalidArgumentError(-1, 'TrainStep.step: ground truth of %d images for %d images' % (glabels.shape[0], images.shape[0]))
+        return images, glabels, gboxes, n_gt
+
+    def step(self, images, glabels, gboxes, n_gt, lr, seed):
+        from . import losses as L
+        from .runtime import deferred
+        d, opt, enc = self.det, self.opt, self.encoder
+        if opt._pending is not None:
+            raise InvalidArgumentError(-1, 'TrainStep.step: the result of the last step has not been read: call its read() first')
+        images, glabels, gboxes, n_gt = self.upload(images, glabels, gboxes, n_gt)
+        rpn_seed, roi_seed = self.seeds(seed)
+        n, S, A, nc = images.shape[0], d.image_size, d.cfg.num_anchors, d.cfg.num_classes
+        h, l = d.stream.handle, lib()
+        stem = getattr(d, STEM_STAGE.flag, False)
+        with d.scope(), deferred(d.stream):
+            new_body(d)                                    # (as set_images: the stages' saved state belongs to the images that go)
+            check(l.xdet_memcpy_d2d(d._images.ptr, images.ptr, n * 3 * S * S * 4, h))
+            d._N = n
+            a_l, a_t, _, _, _ = enc.encode_all_anchors(glabels, gboxes, n_gt, stream=d.stream, keep_device=True)
+            check(l.xdet_net_xception_body(d.handle, d._images.ptr, n, h))
+            if stem:
+                stem_train()
+            entry_flow_train()
+            middle_flow_train()
+            exit_flow_train()
+            check(l.xdet_net_get_rpn(d.handle, n, h))
+            heads_ran(d, '_rpn_step')
+            rpn_out = d.buffer('rpn_out', n)
+            cls, box = rpn_out.channels(0, 2 * A), rpn_out.channels(2 * A, 6 * A)
+            check(l.xdet_net_rpn_decode(d.handle, n, h))
+            check(l.xdet_net_get_proposals(d.handle, n, h))
+            rois, r_t, r_l, _ = enc.ext_encode_rois(d.buffer('proposals', n), glabels, gboxes, self.roi_one_image, self.fg_ratio,
+                                                    self.allowed_border, seed=roi_seed, n_gt=n_gt, stream=d.stream, keep_device=True,
+                                                    buffers=self._roi_buffers)
+            d._lsep.forward(d, d.buffer('out', n), n)
+            loss_func = L.HeadLoss(r_l, r_t, self.fg_ratio, device_result=True, buffers=self._head_buffers)
+            rois_to_head(d, rois, n)
+            check(l.xdet_net_get_head(d.handle, n, h))
+            heads_ran(d, '_head_step')
+            head_res = loss_func(d.buffer('cls_reg', n), None, self.ohem_roi_one_image, nc, stream=d.stream)
+            sections = [head_backward(loss_func, to_feat=True, weight_grads='device')]
+            sections.append(large_sep_backward(sections[0]['feat'], weight_grads='device'))
+            rpn_res = L.rpn_loss(cls, box, a_l[0], a_t[0], self.rpn_anchors_per_image, self.rpn_fg_ratio, seed=rpn_seed, stream=d.stream,
+                                 keep_device=True, device_result=True, buffers=self._rpn_buffers)
+            sections.append(rpn_backward(rpn_res, weight_grads='device'))
+            sections.append(exit_flow_backward(sections[1]['out'], sections[2]['mid'], weight_grads='device'))
+            sections.append(middle_flow_backward(sections[3]['mid'], weight_grads='device'))
+            sections.append(entry_flow_backward(sections[4]['entry'], weight_grads='device'))
+            if stem:
+                sections.append(stem_backward(sections[5]['stem'], weight_grads='device'))
+            grads = {k: v for sec in sections for k, v in sec.items() if k in self._variables}
+            pending = opt.step(grads, lr, guard=self.guard, sync=False)
+            pending._alive = (sections, images, glabels, gboxes, n_gt, loss_func, rpn_res)   # (until read(): the stream may still run)
+        return StepResult(pending, rpn_res.losses, head_res.losses, opt.weight_decay)
+
+    def step_images(self, images_u8, labels, bboxes, lr, seed):
+        """augment.preprocess_train(images_u8, labels, bboxes, the detector's image size, seed) on the detector's stream, then
+        step on what it left on the device"""
+        from . import augment
+        d = self.det
+        return self.step(*augment.preprocess_train(images_u8, labels, bboxes, d.image_size, seed, stream=d.stream), lr, seed)
 
 
 # ---- the flows' host statements: NumPy, any channel counts and map sizes (the weights and the input decide), float64 as the

@@ -17,6 +17,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
            'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
+           'host_grad_stats', 'grad_stats_device',
            'host_bn_fold', 'bn_fold_device', 'refresh_layers_table', 'refresh_layers_device',
            'host_concat', 'host_split', 'concat_device', 'split_device',
            'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
@@ -714,33 +715,90 @@ def _device_array(a, n, who, what, null=True):
     return a.ptr
 
 
-def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, stream=None, workspace=None):
-    """host_momentum_step over a table of variables in one launch (xdet_momentum_step): slots is a sequence of (var, grad, accum,
-    n, decay) with var, grad, accum dense DeviceTensors of n elements or DeviceBuffers of at least n floats; var and accum are
-    updated in place.  l2=True: -> a DeviceBuffer holding one float, sum over the decayed slots of sum var^2 / 2 on the values
-    before the update, summed in the fixed order include/xdet.h documents (None otherwise).  workspace: a DeviceBuffer of at
-    least xdet_momentum_step_workspace_bytes bytes (default: allocated here).  Nothing is synchronised."""
+def _momentum_table(slots, who):
+    """the xdet_momentum_slot table of a sequence of (var, grad, accum, n, decay) -> (table, the slots as a list)"""
     slots = list(slots)
     if not slots:
-        raise InvalidArgumentError(-1, 'momentum_step: an empty slot table')
+        raise InvalidArgumentError(-1, '%s: an empty slot table' % who)
     table = (MomentumSlot * len(slots))()
     for i, slot in enumerate(slots):
         if len(slot) != 5:
-            raise InvalidArgumentError(-1, 'momentum_step: slot %d must be (var, grad, accum, n, decay)' % i)
+            raise InvalidArgumentError(-1, '%s: slot %d must be (var, grad, accum, n, decay)' % (who, i))
         var, grad, accum, n, decay = slot
         n = int(n)
-        _check_sizes((n,), (1,), 'momentum_step: slot %d holds n = %d elements (positive, below 2^31)', (i, n), widest=None)
-        ptrs = [_device_array(a, n, 'momentum_step', 'slot %d\'s %s' % (i, what)) for a, what in ((var, 'var'), (grad, 'grad'), (accum, 'accum'))]
+        _check_sizes((n,), (1,), who + ': slot %d holds n = %d elements (positive, below 2^31)', (i, n), widest=None)
+        ptrs = [_device_array(a, n, who, 'slot %d\'s %s' % (i, what)) for a, what in ((var, 'var'), (grad, 'grad'), (accum, 'accum'))]
         table[i] = MomentumSlot(ptrs[0], ptrs[1], ptrs[2], n, 1 if decay else 0)
-    need = lib().xdet_momentum_step_workspace_bytes(table, len(slots))
+    return table, slots
+
+
+def _table_workspace(workspace, need, who):
     if workspace is not None and (not isinstance(workspace, DeviceBuffer) or workspace.nbytes < need):
-        raise InvalidArgumentError(-1, 'momentum_step: workspace must be a DeviceBuffer of at least %d bytes' % need)
-    ws = workspace if workspace is not None else DeviceBuffer(need)
-    d_l2 = DeviceBuffer(16) if l2 else None
-    check(lib().xdet_momentum_step(table, len(slots), float(lr), float(momentum), float(weight_decay),
-                                   d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
-    _keep_alive((d_l2,), (ws,) + tuple(a for s in slots for a in s[:3]))
+        raise InvalidArgumentError(-1, '%s: workspace must be a DeviceBuffer of at least %d bytes' % (who, need))
+    return workspace if workspace is not None else DeviceBuffer(need)
+
+
+def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, stream=None, workspace=None, skip=None, l2_out=None):
+    """host_momentum_step over a table of variables in one launch (xdet_momentum_step): slots is a sequence of (var, grad, accum,
+    n, decay) with var, grad, accum dense DeviceTensors of n elements or DeviceBuffers of at least n floats; var and accum are
+    updated in place.  l2=True: -> a DeviceBuffer holding one float, sum over the decayed slots of sum var^2 / 2 on the values
+    before the update, summed in the fixed order include/xdet.h documents (None otherwise); l2_out: the caller's buffer for it,
+    at least 4 bytes.  workspace: a DeviceBuffer of at least xdet_momentum_step_workspace_bytes bytes (default: allocated
+    here).  skip (the record grad_stats_device left, a DeviceBuffer of at least 8 bytes; default None: the plain call): the
+    guarded step, xdet_momentum_step_guarded on the record's `nonfinite` word -- where that word is not zero no var and no
+    accum byte changes, and l2 is written all the same.  Nothing is synchronised."""
+    table, slots = _momentum_table(slots, 'momentum_step')
+    if skip is not None and (not isinstance(skip, DeviceBuffer) or skip.nbytes < 8 or not skip.ptr):
+        raise InvalidArgumentError(-1, 'momentum_step: skip must be the record of grad_stats_device, a DeviceBuffer of at least 8 bytes')
+    if l2_out is not None and (not l2 or not isinstance(l2_out, DeviceBuffer) or l2_out.nbytes < 4 or not l2_out.ptr):
+        raise InvalidArgumentError(-1, 'momentum_step: l2_out goes with l2=True and must be a DeviceBuffer of at least 4 bytes')
+    ws = _table_workspace(workspace, lib().xdet_momentum_step_workspace_bytes(table, len(slots)), 'momentum_step')
+    d_l2 = (l2_out if l2_out is not None else DeviceBuffer(16)) if l2 else None
+    if skip is None:
+        check(lib().xdet_momentum_step(table, len(slots), float(lr), float(momentum), float(weight_decay),
+                                       d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
+    else:
+        check(lib().xdet_momentum_step_guarded(table, len(slots), float(lr), float(momentum), float(weight_decay),
+                                               d_l2.ptr if l2 else None, skip.ptr + 4, ws.ptr, _handle(stream)))
+    _keep_alive((d_l2,), (ws, skip) + tuple(a for s in slots for a in s[:3]))
     return d_l2
+
+
+# ---- the guard of the step: sum of squares and non-finite count of a table's gradients (xdet_grad_stats, csrc/optimizer.hip) --
+
+def host_grad_stats(grads):
+    """The NumPy statement of xdet_grad_stats (include/xdet.h) over a sequence of gradient arrays, one per slot -> (grad_sq,
+    nonfinite, first_bad): the float64 sum of squares of every element (the yardstick of the record's f32 grad_sq: NaN or inf
+    where the record's is), the number of elements that are NaN, +inf or -inf, and the lowest index of an array that holds
+    one, -1 if none does."""
+    grad_sq, nonfinite, first_bad = np.float64(0), 0, -1
+    for i, g in enumerate(grads):
+        g = np.asarray(g, np.float64).ravel()
+        with np.errstate(over='ignore', invalid='ignore'):
+            grad_sq = grad_sq + np.square(g).sum()
+        bad = int(np.count_nonzero(~np.isfinite(g)))
+        nonfinite += bad
+        if bad and first_bad < 0:
+            first_bad = i
+    return float(grad_sq), nonfinite, first_bad
+
+
+GRAD_STATS_DTYPE = np.dtype([('grad_sq', np.float32), ('nonfinite', np.int32), ('first_bad_slot', np.int32), ('zero', np.int32)])
+
+
+def grad_stats_device(slots, stream=None, workspace=None, out=None):
+    """xdet_grad_stats over the gradients of a momentum_step_device table (the same 5-tuples; var and accum are checked as
+    there and not read) -> a DeviceBuffer that holds the 16-byte record {f32 grad_sq, i32 nonfinite, i32 first_bad_slot, i32 0}
+    (GRAD_STATS_DTYPE; what momentum_step_device takes as skip=).  out: the caller's DeviceBuffer of at least 16 bytes;
+    workspace: one of at least xdet_grad_stats_workspace_bytes bytes (defaults: allocated here).  Nothing is synchronised."""
+    table, slots = _momentum_table(slots, 'grad_stats')
+    if out is not None and (not isinstance(out, DeviceBuffer) or out.nbytes < 16 or not out.ptr):
+        raise InvalidArgumentError(-1, 'grad_stats: out must be a DeviceBuffer of at least 16 bytes')
+    ws = _table_workspace(workspace, lib().xdet_grad_stats_workspace_bytes(table, len(slots)), 'grad_stats')
+    rec = out if out is not None else DeviceBuffer(16)
+    check(lib().xdet_grad_stats(table, len(slots), rec.ptr, ws.ptr, _handle(stream)))
+    _keep_alive((rec,), (ws,) + tuple(s[1] for s in slots))
+    return rec
 
 
 # ---- the refresh of forward layers from weights on the device (xdet_bn_fold, xdet_layers_refresh_device, csrc/conv_repack.hip) --
