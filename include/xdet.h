@@ -506,12 +506,27 @@ int xdet_bboxes_eval(const float* cls, int ld_cls, const float* boxes, int N, in
  *   boxes not 16-byte aligned, form outside {0, 1}.
  * xdet_bboxes_eval_probs: xdet_bboxes_eval from those probabilities instead of the logits; bad_per_image (may be NULL):
  *   i32 [N], an image with a non-zero entry gets NaN in slot 0 of every class.  Same limits as xdet_bboxes_eval
- *   (R <= 1024, 1 <= nms_topk <= 256, num_classes >= 2, nms_thr >= 0). */
+ *   (R <= 1024, 1 <= nms_topk <= 256, num_classes >= 2, nms_thr >= 0).
+ * xdet_bboxes_eval_probs_wide: the same arguments, outputs and bits for 1 <= R <= 6144 ROIs per image -- 6144 is the proposal
+ *   stage's own ceiling for rpn_post_nms_top_n; a training net proposes 1800.  R <= 1024 launches xdet_bboxes_eval_probs'
+ *   kernel; above that bboxes_eval_wide_kernel, one workgroup per (image, class) as well: the keys of all R ROIs in LDS
+ *   (8 bytes each, R rounded up to 2048 / 4096 / 8192 slots), the same order (descending score, ties to the lower ROI index),
+ *   and the boxes of the at most min(2 * nms_topk, 512) winners computed again from `boxes`.  XDET_ERR_INVALID_ARG, nothing
+ *   launched: everything xdet_bboxes_eval_probs refuses, and R > 6144 by a sentence that names the bound.
+ * xdet_bboxes_eval_probs_wide_only: the wide kernel at any 1 <= R <= 6144 (a door for tests: the two kernels on the same
+ *   input give the same bits); otherwise as xdet_bboxes_eval_probs_wide. */
 int xdet_head_decode_probs(const float* rois, const float* cls_reg, int ld, int num_classes, int R, int64_t n, int form,
                            float* boxes, float* probs, int32_t* bad, void* stream);
 int xdet_bboxes_eval_probs(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
                            const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
                            const int32_t* bad_per_image /* may be NULL */, float* det_scores, float* det_boxes, void* stream);
+int xdet_bboxes_eval_probs_wide(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
+                                const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
+                                const int32_t* bad_per_image /* may be NULL */, float* det_scores, float* det_boxes, void* stream);
+int xdet_bboxes_eval_probs_wide_only(const float* probs, const float* boxes, int N, int R, int num_classes,
+                                     const int* image_shapes, const float* bbox_img, int net_h, int net_w, float select_thr,
+                                     float nms_thr, int nms_topk, const int32_t* bad_per_image /* may be NULL */,
+                                     float* det_scores, float* det_boxes, void* stream);
 
 /* ---- bboxes_eval, scoring part: eval_helper.bboxes_matching_batch (utility/eval_helper.py:700-830) -----------------
  * The TP / FP flags of every detection slot against the image's ground truth, per (image, class), as the greedy walk of
@@ -1154,7 +1169,19 @@ int xdet_net_set_weight(void* net, const char* name, const float* data_host, int
  *   XDET_ERR_STATE with a sentence that names head_rois, ahead of any launch and of a graph capture.  The refresh doors
  *   (xdet_net_refresh_weights / _heads / _stem) do not depend on the row count and work as ever.  off (default): the net as
  *   ever, byte for byte, and the buffer name is refused.  No kernel belongs to the option: PsRoiAlign, its ordered gradient
- *   and the dense layers take the row count as an argument. */
+ *   and the dense layers take the row count as an argument.
+ *   "eval_head" = "off" | "on" (on needs "head_rois" = "<P>": without it xdet_net_build returns XDET_ERR_INVALID_ARG with one
+ *   sentence): a second head stage on such a training net, so that the net that trains also evaluates.  It is built on the
+ *   SAME two dense layers as the sampled-row stage (what xdet_net_refresh_heads refreshes, it refreshes for both) over its
+ *   own buffers "pooled_eval", "fc_eval", "cls_reg_eval" with rpn_post_nms_top_n rows per image: the head plan of a net built
+ *   with rpn_post_nms_top_n = R and no head_rois, and the same bits.  xdet_net_forward and xdet_net_forward_u8 (eager and
+ *   captured) then run on it: PsRoiAlign from "proposals" into "pooled_eval" (no pool_index), the eval stage, the decode from
+ *   "cls_reg_eval" and bboxes_eval (the wide form when rpn_post_nms_top_n > 1024).  They overwrite the body's and the RPN's
+ *   buffers and "proposals", and leave "pooled", "fc", "cls_reg", "pool_index" and "head_rois" alone.  The stage entries
+ *   xdet_net_head_decode and xdet_net_bboxes_eval (the logits form) stay XDET_ERR_STATE, and so does xdet_net_calibrate, by a
+ *   sentence that says why: the training stages and the refresh doors of such a net are built at exponent 0, and a second
+ *   input plane on a shared layer has no pre-scale hook.  off (default): the head_rois net as described above, byte for
+ *   byte, and the three buffer names are refused. */
 int xdet_net_set_option(void* net, const char* key, const char* value);
 int xdet_net_build(void* net);     /* folds BN, transposes/pads weights, allocates the workspace */
 int xdet_net_destroy(void* net);
@@ -1164,7 +1191,9 @@ int xdet_net_destroy(void* net);
  * "entry_x" (f32 [max_batch,h,w,728]) with option "entry_x" = "keep" only, "stem_out" (f32 [max_batch,h,w,64]) with option
  * "stem_out" = "keep" only, "head_rois" (f32 [max_batch,P,1,4], ld 4) with option "head_rois" = "<P>" only, otherwise
  * XDET_ERR_INVALID_ARG; "mid_x" is "mid" in front of its ReLU.  With "head_rois" = "<P>" the buffers "pooled", "fc", "cls_reg"
- * and "pool_index" have P rows per image, "proposals" and "head_boxes" rpn_post_nms_top_n */
+ * and "pool_index" have P rows per image, "proposals" and "head_boxes" rpn_post_nms_top_n; "pooled_eval", "fc_eval" and
+ * "cls_reg_eval" (rpn_post_nms_top_n rows per image, the dims / ld a net without head_rois has for "pooled", "fc", "cls_reg")
+ * with option "eval_head" = "on" only, otherwise XDET_ERR_INVALID_ARG */
 int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], int* ld);
 /* stage entry points = the reference's graph-builder functions (net/xception_body.py) */
 int xdet_net_xception_body(void* net, const float* images_nchw, int N, void* stream);  /* :236 -> "mid","out" */
@@ -1196,7 +1225,10 @@ int xdet_net_bboxes_eval(void* net, int N, const int* image_shapes, const float*
  * new tuple captures (and runs) a new graph, later calls with the same tuple replay it; at most 8
  * graphs are kept per net (oldest evicted).  The CONTENTS of the buffers may change between replays,
  * the buffers themselves must stay allocated while their graph is cached.
- * xdet_net_graph_count: number of graphs currently cached (tests). */
+ * xdet_net_graph_count: number of graphs currently cached (tests).
+ * rpn_post_nms_top_n up to 6144: above 1024 ROIs per image the tail is bboxes_eval's wide form (xdet_bboxes_eval_probs_wide);
+ * up to 1024 no launch and no argument differs.  On a net built with "head_rois" = "<P>" the forward needs "eval_head" = "on"
+ * and runs that stage (XDET_ERR_STATE without). */
 int xdet_net_forward(void* net, const float* images_nchw, int N, const int* image_shapes, const float* bbox_img,
                      float* det_scores, float* det_boxes, int use_graph, void* stream);
 /* uint8 ingest + whole forward: xdet_preprocess_eval_batch (out_size = the net's S) into images_nchw / bbox_img, then

@@ -477,6 +477,23 @@ int xdet_bboxes_eval_probs(const float* probs, const float* boxes, int N, int R,
   return launch_bboxes_eval_probs(probs, boxes, N, R, num_classes, image_shapes, bbox_img, net_h, net_w, select_thr, nms_thr,
                                   nms_topk, det_scores, det_boxes, S(stream), bad_per_image);
 }
+// 1 <= R <= 6144: the kernel above up to 1024 ROIs per image, the wide one beyond (what a net with more proposals runs)
+int xdet_bboxes_eval_probs_wide(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
+                                const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
+                                const int32_t* bad_per_image, float* det_scores, float* det_boxes, void* stream) {
+  XDET_REQUIRE(probs && boxes && image_shapes && bbox_img && det_scores && det_boxes, "bboxes_eval_probs_wide: NULL argument");
+  return launch_bboxes_eval_probs_wide(probs, boxes, N, R, num_classes, image_shapes, bbox_img, net_h, net_w, select_thr, nms_thr,
+                                       nms_topk, det_scores, det_boxes, S(stream), bad_per_image, false);
+}
+// the wide kernel at any R (tests: the two kernels on the same input)
+int xdet_bboxes_eval_probs_wide_only(const float* probs, const float* boxes, int N, int R, int num_classes,
+                                     const int* image_shapes, const float* bbox_img, int net_h, int net_w, float select_thr,
+                                     float nms_thr, int nms_topk, const int32_t* bad_per_image, float* det_scores,
+                                     float* det_boxes, void* stream) {
+  XDET_REQUIRE(probs && boxes && image_shapes && bbox_img && det_scores && det_boxes, "bboxes_eval_probs_wide_only: NULL argument");
+  return launch_bboxes_eval_probs_wide(probs, boxes, N, R, num_classes, image_shapes, bbox_img, net_h, net_w, select_thr, nms_thr,
+                                       nms_topk, det_scores, det_boxes, S(stream), bad_per_image, true);
+}
 
 // A handle is a void*: both plan types start with their Plan base, whose kind tag says what the pointer really is
 // (handing a resnet handle to a light-head entry point used to be undefined behaviour).
@@ -599,6 +616,11 @@ int xdet_net_set_option(void* net, const char* key, const char* value) {
     n->head_rois_n = (int)p;
     return XDET_OK;
   }
+  if (k == "eval_head") {
+    XDET_REQUIRE(v == "on" || v == "off", "eval_head must be on | off");
+    n->eval_head = v == "on";
+    return XDET_OK;
+  }
   if (k == "rpn_hidden") {
     XDET_REQUIRE(v == "keep" || v == "off", "rpn_hidden must be keep | off");
     n->keep_rpn_hidden = v == "keep";
@@ -665,6 +687,10 @@ int xdet_net_buffer(void* net, const char* name, void** dptr, int64_t dims[4], i
   else if (s == "head_rois") {
     XDET_REQUIRE(n->head_rois != nullptr, "net_buffer: head_rois needs a net built with the option head_rois=<P>");
     *dptr = n->head_rois; dims[0] = B; dims[1] = n->head_rois_n; dims[2] = 1; dims[3] = 4; *ld = 4;
+  }
+  else if (s == "pooled_eval" || s == "fc_eval" || s == "cls_reg_eval") {
+    XDET_REQUIRE(n->pooled_eval.p != nullptr, "net_buffer: " + s + " needs a net built with the options head_rois=<P> and eval_head=on");
+    from_buf(s == "pooled_eval" ? n->pooled_eval : s == "fc_eval" ? n->fc_eval : n->cls_reg_eval);
   }
   else if (s == "head_boxes") { *dptr = n->head_boxes; dims[0] = B; dims[1] = R; dims[2] = 1; dims[3] = 4; *ld = 4; }
   else if (s == "prop_counts") { *dptr = n->prop_ws.counts; dims[0] = B; dims[1] = 4; dims[2] = 1; dims[3] = 1; *ld = 1; }
@@ -740,7 +766,7 @@ int xdet_net_forward(void* net, const float* images, int N, const int* image_sha
                      float* det_scores, float* det_boxes, int use_graph, void* stream) {
   XDET_LIGHTHEAD(n, net, "net_forward");
   XDET_REQUIRE(n && images && det_scores && det_boxes, "forward: NULL argument");
-  XDET_TRY(n->eval_refused("net_forward"));      // (ahead of a graph capture)
+  XDET_TRY(n->eval_refused("net_forward", /*whole_forward=*/true));      // (ahead of a graph capture)
   XDET_TRY(n->check(N));
   hipStream_t s = S(stream);
   if (!use_graph) return n->forward_eager(images, N, image_shapes, bbox_img, det_scores, det_boxes, s);
@@ -758,7 +784,7 @@ int xdet_net_forward_u8(void* net, const uint8_t* packed, int64_t packed_bytes, 
   XDET_LIGHTHEAD(n, net, "net_forward_u8");
   XDET_REQUIRE(n && packed && offsets && image_shapes && images && bbox_img && det_scores && det_boxes,
                "forward_u8: NULL argument");
-  XDET_TRY(n->eval_refused("net_forward_u8"));   // (ahead of the ingest and of a graph capture)
+  XDET_TRY(n->eval_refused("net_forward_u8", /*whole_forward=*/true));   // (ahead of the ingest and of a graph capture)
   XDET_TRY(n->check(N));
   XDET_REQUIRE(resize >= XDET_RESIZE_NONE && resize <= XDET_RESIZE_WARP, "forward_u8: unknown resize mode");
   XDET_REQUIRE(packed_bytes >= 0, "forward_u8: packed_bytes < 0");
@@ -820,7 +846,7 @@ int xdet_net_memory(void* net, size_t* allocated_bytes, size_t* recycled_bytes) 
 int xdet_net_flops_per_image(void* net, double* backbone, double* rpn, double* large_sep, double* head) {
   XDET_LIGHTHEAD(n, net, "net_flops_per_image");
   XDET_REQUIRE(n && n->built, "net not built");
-  double f[5] = {0, 0, 0, 0, 0};
+  double f[ST_N] = {};                           // (ST_HEAD_EVAL, the second plan of the same head, is counted nowhere)
   for (const Op& op : n->ops) f[op.stage] += std::max(op.flops, 0.0);
   if (backbone) *backbone = f[ST_BODY] + f[ST_EXIT];
   if (rpn) *rpn = f[ST_RPN];

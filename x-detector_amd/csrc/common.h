@@ -236,5 +236,11 @@ int launch_head_decode_probs(const float* rois, const float* cls_reg, int ld, in
 int launch_bboxes_eval_probs(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
                              const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
                              float* det_scores, float* det_boxes, hipStream_t s, const int* bad_per_image = nullptr);
+// the same for 1 <= R <= 6144: the kernel above up to 1024 ROIs per image, bboxes_eval_wide_kernel (keys of all R in LDS, the
+// winners' boxes computed again from `boxes`) beyond; force_wide: the wide kernel at any R
+int launch_bboxes_eval_probs_wide(const float* probs, const float* boxes, int N, int R, int num_classes, const int* image_shapes,
+                                  const float* bbox_img, int net_h, int net_w, float select_thr, float nms_thr, int nms_topk,
+                                  float* det_scores, float* det_boxes, hipStream_t s, const int* bad_per_image = nullptr,
+                                  bool force_wide = false);
 
 }  // namespace xdet

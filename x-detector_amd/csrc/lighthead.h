@@ -7,7 +7,8 @@ namespace xdet {
 
 // ST_EXIT: the exit flow (conv2d_4, blocks 13-14, net/xception_body.py:340-376) -- part of the backbone, its own stage so that
 // the RPN branch, which only needs mid_outputs (:339), can fork in front of it
-enum { ST_BODY = 0, ST_RPN = 1, ST_LSEP = 2, ST_HEAD = 3, ST_EXIT = 4 };
+// ST_HEAD_EVAL: the head on all rpn_post_nms_top_n proposals of a net whose ST_HEAD runs on sampled rows (option "eval_head")
+enum { ST_BODY = 0, ST_RPN = 1, ST_LSEP = 2, ST_HEAD = 3, ST_EXIT = 4, ST_HEAD_EVAL = 5, ST_N = 6 };
 
 struct LightHeadNet : Plan {
   xdet_lighthead_config cfg;
@@ -19,8 +20,14 @@ struct LightHeadNet : Plan {
   // option "head_rois" = "<P>": the head stage is planned on P sampled rows per image (pooled, fc, cls_reg, pool_index) and
   // reads its ROIs from `head_rois` [max_batch, P, 4], corner boxes in the layout of `proposals`; the proposal stage keeps
   // cfg.rpn_post_nms_top_n rows.  0 = off: the head runs on `proposals`.  Such a net has no eval tail (eval_refused)
+  // unless it is built with eval_head as well
   int head_rois_n = 0;
   float* head_rois = nullptr;
+  // option "eval_head" = "on" (needs head_rois): a second head stage, ST_HEAD_EVAL, on the SAME two layers (hd_head) over its own
+  // buffers with cfg.rpn_post_nms_top_n rows per image -- the head plan of a net built without head_rois -- which the whole
+  // forward runs on `proposals`; the sampled-row buffers (pooled, fc, cls_reg, pool_index, head_rois) are not touched by it
+  bool eval_head = false;
+  Buf pooled_eval, fc_eval, cls_reg_eval;
   Buf rpn_hidden;                 // relu(rpn_head/conv2d) as f32 [B,h,w,512] (option "rpn_hidden" = "keep"; p stays NULL without)
   bool keep_rpn_hidden = false;
   Buf entry_x;                    // block 4's sum, the middle flow's input, f32 [B,h,w,728] (option "entry_x" = "keep"; p stays NULL without)
@@ -89,8 +96,16 @@ struct LightHeadNet : Plan {
   int head_rows() const { return head_rois_n ? head_rois_n : cfg.rpn_post_nms_top_n; }
   const float* head_boxes_in() const { return head_rois_n ? head_rois : proposals; }
   // the eval entries of a net whose head runs on sampled rows: refused ahead of any launch and of a graph capture
-  int eval_refused(const char* what) const {
-    if (!head_rois_n) return XDET_OK;
+  // (whole_forward: xdet_net_forward / _forward_u8, which a net with the option eval_head runs on its second head stage)
+  int eval_refused(const char* what, bool whole_forward = false) const {
+    if (!head_rois_n || (eval_head && whole_forward)) return XDET_OK;
+    if (eval_head) {
+      set_last_error(std::string(what) + ": this net was built with the options head_rois=" + std::to_string(head_rois_n) +
+                     " and eval_head=on: its eval head runs inside xdet_net_forward / xdet_net_forward_u8 on the buffer "
+                     "cls_reg_eval, and this stage entry of the logits form reads cls_reg, which holds the sampled rows; build a "
+                     "net without head_rois for the stage entries");
+      return XDET_ERR_STATE;
+    }
     set_last_error(std::string(what) + ": this net was built with the option head_rois=" + std::to_string(head_rois_n) +
                    " (its head runs on the sampled ROIs of the head_rois buffer, a training net): it has no eval forward and no "
                    "detection tail; build a net without head_rois for those");
@@ -151,14 +166,29 @@ struct LightHeadNet : Plan {
     return launch_ext_decode_rois(proposals, cls_reg.p + cfg.num_classes, cls_reg.ld,
                                   (int64_t)N * cfg.rpn_post_nms_top_n, head_boxes, s);
   }
+  // the whole forward's head on a head_rois net (option "eval_head"): all proposals into pooled_eval, no argmax kept
+  int get_head_eval(int N, hipStream_t s) {
+    XDET_TRY(check(N));
+    XDET_REQUIRE(head_rois_n && eval_head && pooled_eval.p, "get_head_eval: the net has no eval head stage");
+    const int C = cfg.bank * cfg.grid * cfg.grid;
+    XDET_TRY(launch_psroialign(feat.p, proposals, pooled_eval.p, nullptr, N, C, feat.H, feat.W, cfg.rpn_post_nms_top_n,
+                               cfg.grid, cfg.grid, 1, 1, feat.ld, pooled_eval.ld, /*corners=*/1, s));
+    return run_stage(ST_HEAD_EVAL, N, s);
+  }
   // the whole forward: A11 and the softmax A12 starts from in one pass over the ROIs, then A12 from the probabilities
   int head_decode_probs(int N, hipStream_t s) {
     XDET_TRY(check(N));
+    const Buf& cls_reg = head_rois_n ? cls_reg_eval : this->cls_reg;       // (rpn_post_nms_top_n rows either way)
     return launch_head_decode_probs(proposals, cls_reg.p, cls_reg.ld, cfg.num_classes, cfg.rpn_post_nms_top_n,
                                     (int64_t)N * cfg.rpn_post_nms_top_n, head_boxes, class_probs, prop_ws.bad, s);
   }
   int bboxes_eval_probs(int N, const int* shapes, const float* bbox, float* ds, float* db, hipStream_t s) {
     XDET_TRY(check(N));
+    // more than 1024 ROIs per image (a training net's 1800): the wide form; up to 1024 the launch it always was
+    if (cfg.rpn_post_nms_top_n > 1024)
+      return launch_bboxes_eval_probs_wide(class_probs, head_boxes, N, cfg.rpn_post_nms_top_n, cfg.num_classes,
+                                           shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
+                                           cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);
     return launch_bboxes_eval_probs(class_probs, head_boxes, N, cfg.rpn_post_nms_top_n, cfg.num_classes,
                                     shapes ? shapes : def_shapes, bbox ? bbox : def_bbox, cfg.image_size, cfg.image_size,
                                     cfg.select_threshold, cfg.nms_threshold, cfg.nms_topk, ds, db, s, prop_ws.bad);

@@ -282,6 +282,11 @@ int LightHeadNet::build_head() {
   // (the rows of the head stage: the sampled ROIs per image with the option head_rois, else the proposals -- the same
   //  layers and ConvEmit constants either way, so head_rois = P plans what a net built with rpn_post_nms_top_n = P plans)
   const int R = head_rows(), C = z.co, nc = z.nc, fw = z.fcw;
+  // With the option eval_head the sampled-row stage's tensors get blocks of their own instead of ones the body has handed back:
+  // a training step's pooled, fc and cls_reg then survive an eval forward, whose body would otherwise write through them
+  // (1 MiB at 64 rows and 256 pixels).  Without the option the plan is the one it always was.
+  struct ReuseGuard { bool& r; bool old; ~ReuseGuard() { r = old; } } reuse_guard{reuse_workspace, reuse_workspace};
+  if (eval_head) reuse_workspace = false;
   std::vector<const float*> t;
   XDET_TRY(need_group(MG_HEAD, {{C, fw}, {fw}, {fw, nc}, {nc}, {fw, 4}, {4}}, &t));
   // ROI rows are the GEMM M dimension: treat [N*R, C] as an NHWC tensor with H = R, W = 1
@@ -298,6 +303,24 @@ int LightHeadNet::build_head() {
   cls_emit.ksplit = latency_ksplit;     // 300 rows x 25 outputs: 3 tiles against 64 K steps
   XDET_TRY(add_conv("final_head/fc_cls+fc_loc", ST_HEAD, fc, L1, nullptr, 0, &cls_reg, cls_emit));
   hd_head[0] = L0; hd_head[1] = L1;
+  if (!eval_head) return XDET_OK;
+  reuse_workspace = reuse_guard.old;      // (the eval stage takes recycled blocks as the head of a net without head_rois does)
+  // The eval stage of a head_rois net: the same two layers, names and ConvEmit constants over buffers of
+  // cfg.rpn_post_nms_top_n rows -- what the lines above plan on a net without head_rois.  A layer's split-K form is a constant
+  // of the layer, and maybe_ksplit takes it from the buffer's extent: the two extents must come to the same form, or the
+  // shared layer would compute one of the two stages on another summation tree than the net it stands for.
+  struct KsForm { int ksplit; bool narrow; int64_t tiles; int mode; };
+  auto form_of = [](const ConvLayer* L) { return KsForm{L->ksplit, L->ks_narrow, L->ks_tiles, L->ks_mode}; };
+  auto same = [](const KsForm& a, const KsForm& b) { return a.ksplit == b.ksplit && a.narrow == b.narrow && a.tiles == b.tiles && a.mode == b.mode; };
+  const KsForm f0 = form_of(L0), f1 = form_of(L1);
+  const size_t n_ks = ks_layers.size();
+  XDET_TRY(new_buf(cfg.rpn_post_nms_top_n, 1, C, &pooled_eval));
+  XDET_TRY(add_conv("final_head/subnet_fc [eval]", ST_HEAD_EVAL, pooled_eval, L0, nullptr, 0, &fc_eval, ConvEmit{1}));
+  XDET_TRY(add_conv("final_head/fc_cls+fc_loc [eval]", ST_HEAD_EVAL, fc_eval, L1, nullptr, 0, &cls_reg_eval, cls_emit));
+  ks_layers.resize(n_ks);                 // (the layers are listed once: finish_ksplit binds a layer's slab, not a stage's)
+  XDET_REQUIRE(same(f0, form_of(L0)) && same(f1, form_of(L1)),
+               "eval_head: the head's dense layers come to another split-K form on rpn_post_nms_top_n rows than on head_rois rows; "
+               "the two stages cannot share their layers at these sizes");
   return XDET_OK;
 }
 
@@ -306,6 +329,8 @@ int LightHeadNet::build() {
   XDET_REQUIRE(cfg.max_batch > 0 && cfg.image_size >= 64, "bad max_batch / image_size");
   XDET_REQUIRE(head_rois_n == 0 || (head_rois_n >= 1 && head_rois_n <= cfg.rpn_post_nms_top_n),
                "head_rois must be off or in 1..rpn_post_nms_top_n");
+  XDET_REQUIRE(!eval_head || head_rois_n, "eval_head=on needs the option head_rois=<P>: a net without head_rois runs its one head "
+                                          "stage on all proposals already");
   XDET_REQUIRE(cfg.num_anchors == 22, "anchor table is the reference's 22-anchor set (1 extra + 7 scales x 3 ratios)");
   max_batch = cfg.max_batch;
   net_precision = g_default_precision;
@@ -657,6 +682,12 @@ int LightHeadNet::refresh_heads(const xdet_net_weight_dev* table, int n, hipStre
 }
 
 int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_scaled) {
+  if (head_rois_n && eval_head) {
+    set_last_error("net_calibrate: this net was built with the options head_rois=" + std::to_string(head_rois_n) +
+                   " and eval_head=on: its training stages and refresh doors are built and tested at exponent 0, and the eval head's "
+                   "input plane on the shared dense layers has no pre-scale hook of its own; calibrate a net without head_rois");
+    return XDET_ERR_STATE;
+  }
   XDET_TRY(eval_refused("net_calibrate"));             // (it measures the planes of whole forwards)
   XDET_TRY(check(N));
   XDET_REQUIRE(images != nullptr, "calibrate: images is NULL");
@@ -672,7 +703,7 @@ int LightHeadNet::calibrate(const float* images, int N, hipStream_t s, int* n_sc
 
 int LightHeadNet::forward_eager(const float* images, int N, const int* shapes, const float* bbox, float* ds, float* db,
                   hipStream_t s) {
-  XDET_TRY(eval_refused("net_forward"));
+  XDET_TRY(eval_refused("net_forward", /*whole_forward=*/true));
   XDET_TRY(entry_and_middle_flow(images, N, s));
   // fork: the RPN branch (3x3 conv, 1x1 heads, decode, top-k, NMS -- a long conv and then small latency-bound
   // launches) needs mid_outputs only (net/xception_body.py:339,381-400): it runs on a side stream under the exit flow
@@ -706,7 +737,7 @@ int LightHeadNet::forward_eager(const float* images, int N, const int* shapes, c
     XDET_HIP(hipEventRecord(ev_join, aux));
     XDET_HIP(hipStreamWaitEvent(s, ev_join, 0));   // join before the head consumes the proposals
   }
-  XDET_TRY(get_head(N, s));
+  XDET_TRY(head_rois_n ? get_head_eval(N, s) : get_head(N, s));
   XDET_TRY(head_decode_probs(N, s));
   if (check_range && net_precision != PREC_F32) {
     for (const auto& b : f32_bufs) {

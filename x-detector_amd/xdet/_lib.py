@@ -166,6 +166,10 @@ SIGNATURES = {
     'xdet_head_decode_probs': (c_int, [PF, PF, c_int, c_int, c_int, c_int64, c_int, PF, PF, PI, c_void_p]),
     'xdet_bboxes_eval_probs': (c_int, [PF, PF, c_int, c_int, c_int, PI, PF, c_int, c_int, c_float, c_float, c_int, PI,
                                        PF, PF, c_void_p]),
+    'xdet_bboxes_eval_probs_wide': (c_int, [PF, PF, c_int, c_int, c_int, PI, PF, c_int, c_int, c_float, c_float, c_int, PI,
+                                            PF, PF, c_void_p]),
+    'xdet_bboxes_eval_probs_wide_only': (c_int, [PF, PF, c_int, c_int, c_int, PI, PF, c_int, c_int, c_float, c_float, c_int, PI,
+                                                 PF, PF, c_void_p]),
     'xdet_bboxes_matching': (c_int, [PF, PF, c_int, c_int, c_int, PI, PF, c_void_p, PI, c_int, c_float, c_void_p, c_void_p, PI,
                                      c_void_p]),
     'xdet_tpfp_create': (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),

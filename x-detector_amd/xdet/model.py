@@ -26,7 +26,7 @@ class LightHeadDetector(object):
                  nms_threshold=0.3, nms_topk=200, device=None, large_sep='auto', sepconv='fused', rpn_stream='side',
                  conv3x3='patch', pool='split', check_range=False, ksplit=True, cross='f16', workspace=None, pool_sub=None,
                  pool_index=False, rpn_hidden=False, large_sep_train=False, exit_flow_train=False, middle_flow_train=False,
-                 entry_flow_train=False, stem_train=False, keep=(), spectral_refresh=False, head_rois=None):
+                 entry_flow_train=False, stem_train=False, keep=(), spectral_refresh=False, head_rois=None, eval_head=False):
         """check_range=True: every activation tensor is validated against the f16 range of the split-precision convs
         after each forward (|x| <= 65504, no NaN); a violation raises in detections() / forward().  For validating a
         new checkpoint once: the pass re-reads every activation (~+30 % time).
@@ -84,8 +84,16 @@ class LightHeadDetector(object):
         P then (else rpn_post_nms_top_n): get_head(..., is_training=True) takes P ROIs per image, a DeviceTensor of them by a
         device-to-device copy, and head_backward, MomentumOptimizer and refresh_eval_net work on this one detector.  Such a
         detector has no eval forward: forward, calibrate, detect_images, detect_jpegs, evaluate* and
-        get_head(..., is_training=False) refuse by naming the option.  The default (None) is the detector as ever."""
+        get_head(..., is_training=False) refuse by naming the option.  The default (None) is the detector as ever.
+        eval_head=True (needs head_rois=P; option "eval_head", include/xdet.h): the training detector also evaluates.  A
+        second head stage on the same two dense layers runs on all rpn_post_nms_top_n proposals over its own buffers
+        ('pooled_eval', 'fc_eval', 'cls_reg_eval'), and forward, detect_images, detect_jpegs and evaluate* work as on a
+        detector built without head_rois from the same weights, bit for bit -- after MomentumOptimizer.refresh_eval_net()
+        from the trained ones.  An eval forward is a new body: the training stages' saved state is dropped, and the
+        sampled-row buffers keep what they held.  calibrate and get_head(..., is_training=False) still refuse.
+        rpn_post_nms_top_n may be up to 6144: above 1024 ROIs per image the detection tail is bboxes_eval's wide form."""
         self.head_rois = _train.check_head_rois(head_rois, rpn_post_nms_top_n)
+        self.eval_head = _train.check_eval_head(eval_head, self.head_rois)
         stages = (large_sep_train, exit_flow_train, middle_flow_train, entry_flow_train)
         _train.check_stages(stages, weights)
         _train.check_stem(stem_train, entry_flow_train, weights)
@@ -130,6 +138,8 @@ class LightHeadDetector(object):
             check(lib().xdet_net_set_option(self.handle, b'rpn_hidden', b'keep'))
         if self.head_rois is not None:
             check(lib().xdet_net_set_option(self.handle, b'head_rois', str(self.head_rois).encode()))
+        if self.eval_head:
+            check(lib().xdet_net_set_option(self.handle, b'eval_head', b'on'))
         if set(keep) - {'stem_out', 'entry_x'}:
             raise InvalidArgumentError(-1, 'keep: %r is not one of stem_out, entry_x' % (sorted(set(keep) - {'stem_out', 'entry_x'}),))
         if middle_flow_train or 'entry_x' in keep:

@@ -701,10 +701,18 @@ def head_decode_probs(rois, cls_reg, num_classes, R, form=0, stream=None):
 
 
 def bboxes_eval_from_probs(probs, bboxes_pred, image_shape=(480, 480), bbox_img=(0., 0., 1., 1.), select_threshold=0.01,
-                           nms_threshold=0.3, nms_topk=200, train_image_size=480, bad=None, stream=None):
+                           nms_threshold=0.3, nms_topk=200, train_image_size=480, bad=None, stream=None, wide=False):
     """xdet_bboxes_eval_probs: bboxes_eval from head_decode_probs' outputs, as the whole forward runs it.
     probs [N,num_classes,R] (or [num_classes,R]), bboxes_pred [N*R,4] in any shape, bad: i32 [N] or None
-    -> what bboxes_eval returns."""
+    -> what bboxes_eval returns.
+    wide=False: R <= 1024 (the door as ever).  wide=True: xdet_bboxes_eval_probs_wide, R <= 6144 -- the same kernel up to 1024
+    ROIs per image, the wide one (keys of all R in LDS, the winners' boxes computed again) beyond, what a net with more than
+    1024 proposals runs.  wide='force': xdet_bboxes_eval_probs_wide_only, the wide kernel at any R <= 6144 (tests: the two
+    kernels on the same input)."""
+    if not any(wide is v for v in (False, True)) and wide != 'force':
+        raise InvalidArgumentError(-1, "bboxes_eval_from_probs: wide must be False, True or 'force', got %r" % (wide,))
+    door = (lib().xdet_bboxes_eval_probs_wide_only if wide == 'force' else
+            lib().xdet_bboxes_eval_probs_wide if wide else lib().xdet_bboxes_eval_probs)
     p = np.ascontiguousarray(probs, np.float32)
     single = p.ndim == 2
     if single:
@@ -718,9 +726,8 @@ def bboxes_eval_from_probs(probs, bboxes_pred, image_shape=(480, 480), bbox_img=
     d_bad = None if bad is None else to_device(np.ascontiguousarray(bad, np.int32).reshape(N))
     n_out = max(N * (nc - 1) * nms_topk, 1)
     d_os, d_ob = DeviceBuffer(max(n_out * 4, 16)), DeviceBuffer(max(n_out * 16, 16))
-    check(lib().xdet_bboxes_eval_probs(d_p.ptr, d_b.ptr, N, R, nc, d_s.ptr, d_i.ptr, train_image_size, train_image_size,
-                                       select_threshold, nms_threshold, nms_topk, d_bad.ptr if d_bad else None, d_os.ptr,
-                                       d_ob.ptr, stream.handle if stream else None))
+    check(door(d_p.ptr, d_b.ptr, N, R, nc, d_s.ptr, d_i.ptr, train_image_size, train_image_size, select_threshold, nms_threshold,
+               nms_topk, d_bad.ptr if d_bad else None, d_os.ptr, d_ob.ptr, stream.handle if stream else None))
     sc = to_host(d_os.ptr, (N, nc - 1, nms_topk), np.float32, stream)
     bx = to_host(d_ob.ptr, (N, nc - 1, nms_topk, 4), np.float32, stream)
     out = [{k + 1: (sc[n, k], bx[n, k]) for k in range(nc - 1)} for n in range(N)]

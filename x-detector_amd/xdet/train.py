@@ -714,6 +714,17 @@ def check_head_rois(head_rois, rpn_post_nms_top_n):
     return int(head_rois)
 
 
+def check_eval_head(eval_head, head_rois):
+    """the detector's eval_head argument -> bool; refused ahead of any GPU work: on a detector without head_rois (its one
+    head stage runs on all proposals already), anything but a bool"""
+    if not isinstance(eval_head, (bool, np.bool_)):
+        raise InvalidArgumentError(-1, 'eval_head must be True or False, got %r' % (eval_head,))
+    if eval_head and head_rois is None:
+        raise InvalidArgumentError(-1, 'eval_head=True needs head_rois=P: a detector without head_rois runs its one head stage on '
+                                       'all proposals already and evaluates as it is')
+    return bool(eval_head)
+
+
 def rois_to_head(d, rois, n):
     """get_head on a head_rois detector, handed its ROIs as a DeviceTensor [n,P,(1,)4] of dense corner boxes: one
     device-to-device copy into the net's `head_rois` buffer on the detector's stream; none when it is that buffer.  A tensor
