@@ -943,6 +943,29 @@ size_t xdet_grad_stats_workspace_bytes(const xdet_momentum_slot* slots_host, int
 int xdet_grad_stats(const xdet_momentum_slot* slots_host, int n_slots, void* stats_dev, void* workspace, void* stream);
 int xdet_momentum_step_guarded(const xdet_momentum_slot* slots_host, int n_slots, float lr, float momentum, float weight_decay,
                                float* l2, const int32_t* skip_dev, void* workspace, void* stream);
+/* The clipped step: xdet_momentum_step on gradients scaled to a global norm of at most clip_norm, decided on the device.
+ * stats_dev is the 16-byte record xdet_grad_stats left on the same stream (device memory, 4-byte aligned).  Every workgroup
+ * reads its grad_sq once -- and, with guard != 0, its nonfinite, as the guarded form reads *skip_dev -- and computes
+ *     norm  = sqrt(grad_sq)                     f32, correctly rounded (the IEEE square root, no fast form)
+ *     scale = clip_norm / max(norm, clip_norm)  f32, correctly rounded; max(a, b) = b where a <= b, else a: a NaN norm stays
+ * The norm is the guard's `grad_norm`: over the loss gradients of ALL slots, without the L2 term.  Per element
+ *     g = grad * scale;  g += weight_decay * var where the slot's decay is set
+ * and the rest is xdet_momentum_step operation for operation and rounding for rounding (one more rounding per element, the
+ * product; l2 as there, from the values before the update).  It follows that
+ *   - norm <= clip_norm gives scale == 1.0f exactly (x / x is 1), grad * 1.0f is grad, and the call stores the bits of
+ *     xdet_momentum_step;
+ *   - guard != 0 and nonfinite != 0: nothing is stored to any var or accum -- their bytes stay -- while l2 is still written;
+ *   - guard == 0 decides nothing: a NaN grad_sq gives a NaN scale and with it NaN in EVERY var and accum; a grad_sq of +inf
+ *     (an infinite element, or a sum that overflowed) gives scale 0, so a finite gradient counts as zero and an infinite one
+ *     gives NaN in its element.  That is the caller's choice; the guard is what prevents it.
+ * scale_out (a device float, or NULL): workgroup 0 writes the scale it used, by one plain vector store, skipped step or not.
+ * The launches are xdet_momentum_step's (the chunks, then the fold of l2), the workspace is xdet_momentum_step_workspace_bytes;
+ * no float atomic, no fence, no workgroup that waits for another: the same call gives the same bits.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a clip_norm that is not finite or <= 0, a NULL or misaligned
+ *   stats_dev, and everything xdet_momentum_step refuses. */
+int xdet_momentum_step_clipped(const xdet_momentum_slot* slots_host, int n_slots, float lr, float momentum, float weight_decay,
+                               float* l2, const void* stats_dev, float clip_norm, int guard, float* scale_out, void* workspace,
+                               void* stream);
 /* Rewrite, on the device and in place, every operand buffer a conv layer (xdet_conv_create) owns from a dense f32
  * [kh,kw,cin,cout] kernel in device memory: the transposed matrix of the f32 mode, or the per-row power-of-two pre-scale, the
  * f16 hi / lo split, the K-blocked copies, the fp8 x8 copy of a pointwise f16x3 layer and the epilogue scale (the scale the

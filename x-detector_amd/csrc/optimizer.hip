@@ -15,6 +15,7 @@
 // down the tree the step uses for v^2; the count of non-finite elements is an integer and needs no order.  Nothing here
 // uses a float atomic, a fence or a workgroup that waits for another: the second launch is the barrier.
 #include <climits>
+#include <cmath>
 
 #include "layers.h"
 
@@ -34,13 +35,31 @@ struct MomentumSlotDev {                // a slot as the kernel reads it
   int vec, pad;                         // vec: all three pointers are 16-byte aligned
 };
 
-// partial[chunk] = the chunk's share of sum v^2 (0 for a slot without decay), by the fixed tree of include/xdet.h
+// the 16-byte record xdet_grad_stats writes (include/xdet.h)
+struct GradStatsRecord {
+  float grad_sq;
+  int nonfinite, first_bad_slot, zero;
+};
+
+// partial[chunk] = the chunk's share of sum v^2 (0 for a slot without decay), by the fixed tree of include/xdet.h.
+// CLIP: the clipped form -- the gradients are scaled by clip_norm / max(sqrt(stats->grad_sq), clip_norm), both operations
+// correctly rounded (sqrtf and `/` are the IEEE ones here: the file is built with -fhip-fp32-correctly-rounded-divide-sqrt),
+// and `skip` is the record's count where the caller asked for the guard; workgroup 0 leaves the scale in *scale_out.
+// !CLIP is the kernel as it was: stats, clip_norm and scale_out are not looked at.
+template <bool CLIP>
 __global__ __launch_bounds__(MS_T) void momentum_step_kernel(const MomentumSlotDev* __restrict__ slots, const int* __restrict__ chunk_slot,
                                                              float lr, float momentum, float weight_decay, float* __restrict__ partial,
-                                                             const int* __restrict__ skip) {
+                                                             const int* __restrict__ skip, const GradStatsRecord* __restrict__ stats,
+                                                             float clip_norm, float* __restrict__ scale_out) {
   __shared__ float red[MS_T];
   const int tid = threadIdx.x;
   const bool hold = skip != nullptr && *skip != 0;          // (one word, the same for every thread of the grid)
+  float scale = 1.f;
+  if (CLIP) {
+    const float norm = sqrtf(stats->grad_sq);               // (one word again; a NaN norm fails the comparison and stays)
+    scale = clip_norm / (norm <= clip_norm ? clip_norm : norm);
+    if (scale_out != nullptr && blockIdx.x == 0 && tid == 0) *scale_out = scale;
+  }
   const MomentumSlotDev s = slots[chunk_slot[blockIdx.x]];
   const long long start = (long long)((int)blockIdx.x - s.first_chunk) * MS_CHUNK;
   const long long left = s.n - start;                       // > 0 by construction of the chunk table
@@ -73,7 +92,8 @@ __global__ __launch_bounds__(MS_T) void momentum_step_kernel(const MomentumSlotD
     t[i] = (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float gg = s.decay ? g[i][c] + weight_decay * v[i][c] : g[i][c];
+      const float gs = CLIP ? g[i][c] * scale : g[i][c];
+      const float gg = s.decay ? gs + weight_decay * v[i][c] : gs;
       a[i][c] = momentum * a[i][c] + gg;
       v[i][c] = v[i][c] - lr * a[i][c];
     }
@@ -116,12 +136,6 @@ __global__ __launch_bounds__(1024) void momentum_l2_kernel(float* partial, int n
   }
   if (threadIdx.x == 0) *l2 = 0.5f * partial[0];
 }
-
-// the 16-byte record xdet_grad_stats writes (include/xdet.h)
-struct GradStatsRecord {
-  float grad_sq;
-  int nonfinite, first_bad_slot, zero;
-};
 
 __device__ __forceinline__ int non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u ? 1 : 0; }
 // (a count is at most 2^34: it stays at INT_MAX rather than wrap to a value that could read as zero)
@@ -259,6 +273,15 @@ static int upload_tables(const char* who, const xdet_momentum_slot* slots, int n
   return XDET_OK;
 }
 
+// the second launch of a step that computes l2: one workgroup over the chunk partials
+static int launch_l2_fold(float* d_partial, int64_t chunks, float* l2, hipStream_t s) {
+  int P = 1;
+  while (P < chunks) P <<= 1;
+  hipLaunchKernelGGL(momentum_l2_kernel, dim3(1), dim3(1024), 0, s, d_partial, (int)chunks, P, l2);
+  XDET_LAUNCH_CHECK();
+  return XDET_OK;
+}
+
 }  // namespace xdet
 
 using namespace xdet;
@@ -279,15 +302,31 @@ int xdet_momentum_step_guarded(const xdet_momentum_slot* slots, int n_slots, flo
   int64_t chunks;
   XDET_TRY(upload_tables("momentum_step", slots, n_slots, false, workspace, s, &d_slots, &d_chunk, &behind, &chunks));
   float* d_partial = reinterpret_cast<float*>(behind);
-  hipLaunchKernelGGL(momentum_step_kernel, dim3((unsigned)chunks), dim3(MS_T), 0, s, d_slots, d_chunk, lr, momentum, weight_decay,
-                     l2 ? d_partial : nullptr, skip_dev);
+  hipLaunchKernelGGL(momentum_step_kernel<false>, dim3((unsigned)chunks), dim3(MS_T), 0, s, d_slots, d_chunk, lr, momentum, weight_decay,
+                     l2 ? d_partial : nullptr, skip_dev, (const GradStatsRecord*)nullptr, 0.f, (float*)nullptr);
   XDET_LAUNCH_CHECK();
-  if (l2) {
-    int P = 1;
-    while (P < chunks) P <<= 1;
-    hipLaunchKernelGGL(momentum_l2_kernel, dim3(1), dim3(1024), 0, s, d_partial, (int)chunks, P, l2);
-    XDET_LAUNCH_CHECK();
-  }
+  if (l2) XDET_TRY(launch_l2_fold(d_partial, chunks, l2, s));
+  return XDET_OK;
+}
+
+int xdet_momentum_step_clipped(const xdet_momentum_slot* slots, int n_slots, float lr, float momentum, float weight_decay, float* l2,
+                               const void* stats_dev, float clip_norm, int guard, float* scale_out, void* workspace, void* stream) {
+  XDET_REQUIRE(std::isfinite(clip_norm) && clip_norm > 0.f, "momentum_step_clipped: clip_norm must be finite and positive");
+  XDET_REQUIRE(stats_dev, "momentum_step_clipped: stats_dev is NULL");
+  XDET_REQUIRE((reinterpret_cast<uintptr_t>(stats_dev) & 3) == 0, "momentum_step_clipped: stats_dev must be 4-byte aligned");
+  XDET_REQUIRE((reinterpret_cast<uintptr_t>(scale_out) & 3) == 0, "momentum_step_clipped: scale_out must be 4-byte aligned");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  MomentumSlotDev* d_slots;
+  int* d_chunk;
+  char* behind;
+  int64_t chunks;
+  XDET_TRY(upload_tables("momentum_step", slots, n_slots, false, workspace, s, &d_slots, &d_chunk, &behind, &chunks));
+  float* d_partial = reinterpret_cast<float*>(behind);
+  const GradStatsRecord* rec = static_cast<const GradStatsRecord*>(stats_dev);
+  hipLaunchKernelGGL(momentum_step_kernel<true>, dim3((unsigned)chunks), dim3(MS_T), 0, s, d_slots, d_chunk, lr, momentum, weight_decay,
+                     l2 ? d_partial : nullptr, guard ? &rec->nonfinite : (const int*)nullptr, rec, clip_norm, scale_out);
+  XDET_LAUNCH_CHECK();
+  if (l2) XDET_TRY(launch_l2_fold(d_partial, chunks, l2, s));
   return XDET_OK;
 }
 

@@ -77,6 +77,12 @@ The names below mirror the interfaces of HiKapok/X-Detector's eval path:
                           <- the reference's train_op as one call (light_head_rfcn_train.py:420-436, logged scalars
                              :510-516), with nothing in the reference behind the guard: a pass over the gradients that
                              decides on the device whether the momentum step stores anything
+  host_clip_scale, host_grad_sq, host_momentum_step(..., scale=), momentum_step_device(..., clip=, scale_out=) (xdet.ops);
+  MomentumOptimizer.step(..., clip_norm=), TrainStep(..., comm=, clip_norm=) (xdet.model)
+                          <- nothing in the reference (its trainer neither clips nor runs on more than one device): the
+                             gradients scaled to a global norm inside the momentum step, from the guard's record, and the
+                             one-call step on `world` ranks -- gradients, moving statistics and logged scalars averaged
+                             on the streams, the host waiting only in read()
   jpeg_info, host_jpeg_coefficients, host_decode_jpeg, decode_jpegs_device, decode_jpegs (xdet.jpeg);
   LightHeadDetector.detect_jpegs (xdet.model)
                           <- tf.image.decode_image in front of the eval and training pipelines (dataset/dataset_common.py:542)

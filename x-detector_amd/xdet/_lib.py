@@ -214,6 +214,8 @@ SIGNATURES = {
     'xdet_grad_stats': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_void_p, c_void_p, c_void_p]),
     'xdet_momentum_step_guarded': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_void_p,
                                            c_void_p]),
+    'xdet_momentum_step_clipped': (c_int, [ctypes.POINTER(MomentumSlot), c_int, c_float, c_float, c_float, PF, c_void_p, c_float,
+                                           c_int, c_void_p, c_void_p, c_void_p]),
     'xdet_grad_average_workspace_bytes': (c_size_t, [ctypes.POINTER(GradSlot), c_int, c_int, c_int64]),
     'xdet_grad_pack': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_void_p, c_void_p]),
     'xdet_grad_reduce_ranks': (c_int, [ctypes.POINTER(GradSlot), c_int, c_int64, c_int64, PF, c_int, c_void_p, c_void_p]),

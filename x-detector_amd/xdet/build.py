@@ -35,7 +35,7 @@ SOURCES = [
     ('depthwise_backward.hip', ['-ffp-contract=off']),
     ('pool_backward.hip', ['-ffp-contract=off']),
     ('stem_train.hip', ['-ffp-contract=off']),
-    ('optimizer.hip', ['-ffp-contract=off']),
+    ('optimizer.hip', ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt']),   # (the clip's sqrt and divide: IEEE)
     ('conv_repack.hip', ['-ffp-contract=off']),
     ('weight_pack.hip', ['-ffp-contract=off']),
     ('grad_average.hip', ['-ffp-contract=off']),

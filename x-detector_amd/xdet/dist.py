@@ -166,6 +166,9 @@ class Communicator(object):
         allgather_bytes: a mismatch raises InvalidArgumentError on every rank before any gradient moves, where the collective
         would hang or scramble the data.  The table is remembered: later calls with it synchronise nothing on the host.
         workspace: a DeviceBuffer of at least xdet_grad_average_workspace_bytes bytes (default: kept by the communicator).
+        The communicator keeps the tensors and the workspace of the last TWO exchanges alive (train.TrainStep enqueues two per
+        step before its read() waits); a caller with more in flight keeps its own.  wait() covers them all: the stream runs
+        in order and the event it waits for is recorded behind the last one.
         world == 1: nothing is launched, the gradients keep their bits."""
         import struct
         import zlib
@@ -196,7 +199,9 @@ class Communicator(object):
                 self._grad_ws = DeviceBuffer(need)
             ws = self._grad_ws
         check(lib().xdet_comm_average_gradients(self.handle, table, len(sizes), int(chunk_elems), ws.ptr, stream.handle))
-        self._grad_keep = (tensors, ws)
+        # the tensors and workspaces of the exchanges that may still be in flight: the one-call step enqueues two (the
+        # gradients, then the statistics and scalars) before its read() waits, so the last two stay
+        self._grad_keep = ((self._grad_keep or ())[-1:]) + ((tensors, ws),)
 
     def max_over_ranks(self, value):
         from ._lib import lib, check

@@ -1375,31 +1375,41 @@ def eval_net_groups(names):
 class StepPending(object):
     """What MomentumOptimizer.step(..., sync=False) returns: the step's scalars are still on the device.  read() -> the dict
     step returns with sync=True, after ONE synchronisation of the detector's stream (a second read() returns the same dict
-    and touches nothing); it is also what releases the optimizer for its next step."""
+    and touches nothing); it is also what releases the optimizer for its next step.
+    A step of data-parallel training with sync=False carries its communicator (`comm`): read() first waits for it with
+    comm.wait(), the host wait under the watchdog -- it covers every exchange enqueued so far, so a dead peer is the
+    watchdog's error -- and only then synchronises the detector's stream, which by then waits for no peer."""
 
-    def __init__(self, opt, lr, guard):
-        self.opt, self.lr, self.guard, self.result, self._alive = opt, lr, guard, None, None
-        self.l2 = self.stats = None                        # the device buffers the scalars lie in (set by step)
+    def __init__(self, opt, lr, guard, clip=False, comm=None):
+        self.opt, self.lr, self.guard, self.clip, self.comm, self.result, self._alive = opt, lr, guard, clip, comm, None, None
+        self.l2 = self.stats = self.scale = None           # the device buffers the scalars lie in (set by step)
 
     def read(self):
         if self.result is not None:
             return self.result
         opt = self.opt
+        if self.comm is not None:
+            self.comm.wait()
+            self.comm = None
         _sync(opt.det)
         if opt.reach == 'all':
             opt._concat[0][0]._keep = None                 # (concat_device's keep-alive chain: the stream has run)
         self.l2._keep = self._alive = None
         out = {'step': None, 'lr': self.lr, 'l2': float(to_host(self.l2.ptr, (1,))[0])}
-        if self.guard:
+        if self.guard or self.clip:
             self.stats._keep = None
             rec = to_host(self.stats.ptr, (1,), train_ops.GRAD_STATS_DTYPE)[0]
+            with np.errstate(invalid='ignore'):
+                out['grad_norm'] = float(np.sqrt(np.float64(rec['grad_sq'])))
+        if self.guard:
             skipped = int(rec['nonfinite']) != 0
             if not skipped:
                 opt.steps += 1
-            with np.errstate(invalid='ignore'):
-                out['grad_norm'] = float(np.sqrt(np.float64(rec['grad_sq'])))
             out['skipped'] = skipped
             out['first_bad'] = opt.variables[int(rec['first_bad_slot'])] if skipped else None
+        if self.clip:
+            self.scale._keep = None
+            out['clip_scale'] = float(to_host(self.scale.ptr, (1,))[0])
         out['step'] = opt.steps
         opt._pending, self.result = None, out
         return out
@@ -1430,6 +1440,7 @@ class MomentumOptimizer(object):
     reach = 'flows'
     _stem = None                                           # StemState of a detector built with stem_train=True
     _pending = None                                        # the StepPending of a step(..., sync=False) that has not been read
+    _scale = None                                          # the clipped step's scale on the device (allocated by the first one)
 
     def __init__(self, det, momentum=0.9, weight_decay=2e-4, reach='flows'):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
@@ -1527,7 +1538,13 @@ class MomentumOptimizer(object):
     def _stem_batch_norms(self):
         return [self._stem.bn1, self._stem.bn2] if self._stem is not None else []
 
-    def step(self, grads, lr, comm=None, guard=False, sync=True):
+    def _moving_batch_norms(self):
+        """every batch norm whose moving statistics a training forward of this detector moves: the stem's, the flows' and the
+        large-separable block's (its training forward moves its statistics too)"""
+        lsep = STAGES[LARGE_SEP]
+        return self._stem_batch_norms() + self._batch_norms() + ([getattr(self.det, lsep.attr).bn] if getattr(self.det, lsep.flag, False) else [])
+
+    def step(self, grads, lr, comm=None, guard=False, sync=True, clip_norm=None):
         """One update of every variable from `grads`, {name: dense DeviceTensor in the checkpoint's shape} -- the dicts the flows'
         backwards return with weight_grads='device', merged; other keys are ignored -- at learning rate `lr`, on the detector's
         stream: one xdet_momentum_step over all variables; the refresh of the forward layers (every unit's pointwise and
@@ -1545,7 +1562,8 @@ class MomentumOptimizer(object):
         for the exchange with comm.wait() before the step's launches -- a dead peer is then the watchdog's error, not a hang
         in the step's own synchronisation.  The ranks' variables and momentum slots stay bit-equal as long as they started
         bit-equal.  What is NOT averaged: each rank's batch-norm moving statistics stay its own (export_weights of any rank
-        gives the same variables, but that rank's statistics), and so do the loss scalars.  The result dict is the same, and
+        gives the same variables, but that rank's statistics), and so do the loss scalars -- TrainStep(comm=) averages both
+        behind this call.  The result dict is the same, and
         `l2` is unchanged.  comm=None: a single process, no communicator is touched.
         reach='all': `grads` also carries what head_backward, rpn_backward and large_sep_backward return with
         weight_grads='device'.  Behind the one xdet_momentum_step, in this order: one concat_device table rebuilds from the masters
@@ -1566,10 +1584,22 @@ class MomentumOptimizer(object):
         sync=False: nothing is read back and nothing is synchronised; -> a StepPending whose read() synchronises the
         detector's stream once, reads l2 (and the record) and returns the dict above; the keep-alive references the
         synchronisation bounds live until then, and so does `self.steps` under guard=True.  The buffers the scalars lie in are
-        the optimizer's own, so the next step is refused until read() has been called."""
+        the optimizer's own, so the next step is refused until read() has been called.
+        With comm and sync=False the host wait for the exchange moves out of the step as well: the StepPending carries the
+        communicator and its read() calls comm.wait() (under the watchdog) ahead of the one synchronisation; with sync=True
+        the order stays comm.wait(), then the step's launches.
+        clip_norm=c (finite, positive; default None: exactly the calls above): xdet_grad_stats runs whether or not guard is
+        set, and the step is xdet_momentum_step_clipped on its record -- every gradient times c / max(grad_norm, c), the scale
+        computed on the device in f32 (xdet.ops.host_clip_scale) from the norm over ALL variables' loss gradients, without
+        the L2 term, behind the rank average; guard=True holds the same step on the same record.  The result gains
+        'clip_scale' (1.0 where nothing was clipped) and, guarded or not, 'grad_norm'.  Without the guard a gradient that is
+        not finite reaches the weights as NaN (include/xdet.h)."""
         if self._pending is not None:
             raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the result of the last step(..., sync=False) has not been read: '
                                            'call its read() first (the next step writes the same l2 and guard record)')
+        if clip_norm is not None and not (isinstance(clip_norm, (int, float, np.floating, np.integer)) and not isinstance(clip_norm, bool)
+                                          and np.isfinite(np.float32(clip_norm)) and np.float32(clip_norm) > 0):
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.step: clip_norm must be None or a finite positive number, got %r' % (clip_norm,))
         miss = [v for v in self.variables if v not in grads]
         if miss:
             raise InvalidArgumentError(-1, 'MomentumOptimizer.step: the gradients lack %s' % ', '.join(miss))
@@ -1581,11 +1611,17 @@ class MomentumOptimizer(object):
                                            % (v, tuple(shape), type(g).__name__, getattr(g, 'shape', None)))
         slots = [(self._master[v][0], grads[v], self._slot[v], math.prod(self._master[v][1]), self._decayed[v]) for v in self.variables]
         d = self.det
+        clip = clip_norm is not None
         if comm is not None:
             comm.average_gradients([grads[v] for v in self.variables], d.stream)
-            comm.wait()
-        stats = train_ops.grad_stats_device(slots, stream=d.stream, workspace=self._stats_ws, out=self._stats) if guard else None
+            if sync:
+                comm.wait()
+        stats = train_ops.grad_stats_device(slots, stream=d.stream, workspace=self._stats_ws, out=self._stats) if guard or clip else None
         more = {'skip': stats} if guard else {}            # (the default path makes the call it always made)
+        if clip:
+            if self._scale is None:
+                self._scale = DeviceBuffer(16)
+            more.update(clip=(stats, clip_norm), scale_out=self._scale)
         if getattr(self, '_l2', None) is not None:
             more['l2_out'] = self._l2
         l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws, **more)
@@ -1602,8 +1638,8 @@ class MomentumOptimizer(object):
         new_body(d)
         if not guard:                                      # (a guarded step counts once its record has been read)
             self.steps += 1
-        self._pending = StepPending(self, float(lr), guard)
-        self._pending.l2, self._pending.stats = l2, stats
+        self._pending = StepPending(self, float(lr), guard, clip, comm if not sync else None)
+        self._pending.l2, self._pending.stats, self._pending.scale = l2, stats, self._scale if clip else None
         return self._pending.read() if sync else self._pending
 
     def _refresh_slots(self):
@@ -1689,8 +1725,7 @@ class MomentumOptimizer(object):
         for v in self.variables:
             master, shape = self._master[v]
             out[v] = to_host(master.ptr, shape)
-        lsep = STAGES[LARGE_SEP]                           # (its training forward moves its statistics too)
-        for bn in self._stem_batch_norms() + self._batch_norms() + ([getattr(self.det, lsep.attr).bn] if getattr(self.det, lsep.flag, False) else []):
+        for bn in self._moving_batch_norms():
             for k in ('moving_mean', 'moving_variance'):
                 out['%s/%s' % (bn.name, k)] = to_host(getattr(bn, k).ptr, (bn.co,))
         return out
@@ -1708,7 +1743,8 @@ class StepResult(object):
     rpn_loss, head_loss, head_ce_loss, head_loc_loss (f32 as the loss kernels wrote them) and total_loss =
     ((rpn_ce_loss + rpn_loc_loss) + head_loss) + weight_decay * l2 in f32, the order of line 420 -- and l2, grad_norm, skipped,
     first_bad, step and lr as MomentumOptimizer.step(..., guard=True) returns them (grad_norm, skipped and first_bad only
-    from a guarded step)."""
+    from a guarded step), and clip_scale from a clipped one.  Under TrainStep(comm=) on more than one rank the six loss
+    scalars are their means over the ranks (averaged on the device behind the step) and total_loss is formed from those."""
 
     def __init__(self, pending, rpn_losses, head_losses, weight_decay):
         self.pending, self._rpn, self._head, self._wd, self.result = pending, rpn_losses, head_losses, weight_decay, None
@@ -1747,12 +1783,19 @@ class TrainStep(object):
     sampling with 2 * seed + 1, both modulo 2^32; step_images hands `seed` itself to the augmentation.
     guard=True: a gradient that is not finite skips the update on the device (MomentumOptimizer.step).  The loss buffers, the
     anchor and ROI targets and the guard record are allocated on the first step and reused.
+    clip_norm=c and comm (an xdet.dist.Communicator) are handed to opt.step(..., sync=False): the gradients are averaged over
+    the ranks and clipped to a global norm of c inside the step, and no host wait happens before StepResult.read(), which
+    waits for the communicator under its watchdog first.  With comm on more than one rank a second exchange follows the
+    optimizer step on the detector's stream: the moving statistics of every batch norm (stem, flows, large-separable block)
+    and the six scalars the loss kernels wrote are replaced in place by their mean over the ranks, so export_weights of any
+    rank is one dict and read() returns the rank means (total_loss from them and l2, which is rank-equal already).  A
+    communicator of one rank launches nothing extra and keeps the bits of comm=None.
     Refused ahead of any launch, in one sentence that lists everything missing: a detector built without head_rois,
     pool_index, rpn_hidden, large_sep_train or one of the three flow stages, an optimizer of another detector or without
     reach='all', and arguments that differ from what the detector was built with."""
 
     def __init__(self, det, opt, encoder, *, rpn_anchors_per_image=256, rpn_fg_ratio, roi_one_image, fg_ratio, ohem_roi_one_image,
-                 nms_threshold, rpn_min_size, guard=True, allowed_border=0.1):
+                 nms_threshold, rpn_min_size, guard=True, allowed_border=0.1, comm=None, clip_norm=None):
         lack = [what for what, have in (('head_rois=%r' % (roi_one_image,), getattr(det, 'head_rois', None) is not None),
                                         ('pool_index=True', getattr(det, 'pool_index', False)),
                                         ('rpn_hidden=True', getattr(det, 'rpn_hidden', False)),
@@ -1783,6 +1826,13 @@ class TrainStep(object):
         self.rpn_anchors_per_image, self.rpn_fg_ratio = int(rpn_anchors_per_image), float(rpn_fg_ratio)
         self.roi_one_image, self.fg_ratio, self.ohem_roi_one_image = int(roi_one_image), float(fg_ratio), int(ohem_roi_one_image)
         self.allowed_border = float(allowed_border)
+        if comm is not None and not (hasattr(comm, 'average_gradients') and hasattr(comm, 'world')):
+            raise InvalidArgumentError(-1, 'TrainStep: comm must be an xdet.dist.Communicator, got %s' % type(comm).__name__)
+        if clip_norm is not None and not (isinstance(clip_norm, (int, float, np.floating, np.integer)) and not isinstance(clip_norm, bool)
+                                          and np.isfinite(np.float32(clip_norm)) and np.float32(clip_norm) > 0):
+            raise InvalidArgumentError(-1, 'TrainStep: clip_norm must be None or a finite positive number, got %r' % (clip_norm,))
+        self.comm, self.clip_norm = comm, clip_norm
+        self._rank_ws = None                               # the workspace of the second exchange (allocated by the first step)
         self._variables = set(opt.variables)
         self._rpn_buffers, self._head_buffers, self._roi_buffers = {}, {}, {}
 
@@ -1865,9 +1915,31 @@ class TrainStep(object):
             if stem:
                 sections.append(stem_backward(sections[5]['stem'], weight_grads='device'))
             grads = {k: v for sec in sections for k, v in sec.items() if k in self._variables}
-            pending = opt.step(grads, lr, guard=self.guard, sync=False)
+            more = {}                                      # (the defaults make the call the driver always made)
+            if self.comm is not None:
+                more['comm'] = self.comm
+            if self.clip_norm is not None:
+                more['clip_norm'] = self.clip_norm
+            pending = opt.step(grads, lr, guard=self.guard, sync=False, **more)
             pending._alive = (sections, images, glabels, gboxes, n_gt, loss_func, rpn_res)   # (until read(): the stream may still run)
+            if self.comm is not None and self.comm.world > 1:
+                self._average_over_ranks(rpn_res.losses, head_res.losses)
         return StepResult(pending, rpn_res.losses, head_res.losses, opt.weight_decay)
+
+    def _average_over_ranks(self, rpn_losses, head_losses):
+        """The second exchange of a data-parallel step, behind the optimizer step on the detector's stream: what stays per
+        rank under MomentumOptimizer.step(comm=) -- the moving_mean and moving_variance of every batch norm a training forward
+        moves, and the two loss kernels' three scalars each -- becomes its mean over the ranks, in place
+        (Communicator.average_gradients on a table of its own: one handshake, on the first step).  l2 is not in the table:
+        it is computed from the masters, which are the same bits on every rank, and total_loss follows from the means."""
+        tensors = [DeviceTensor(b.ptr, (bn.co,), bn.co, owner=b) for bn in self.opt._moving_batch_norms()
+                   for b in (bn.moving_mean, bn.moving_variance)]
+        tensors += [DeviceTensor(b.ptr, (3,), 3, owner=b) for b in (rpn_losses, head_losses)]
+        chunk = 1 << 20
+        if self._rank_ws is None:
+            _, table, sizes, _ = train_ops._grad_table(tensors, chunk)
+            self._rank_ws = DeviceBuffer(lib().xdet_grad_average_workspace_bytes(table, len(sizes), self.comm.world, chunk))
+        self.comm.average_gradients(tensors, self.det.stream, chunk_elems=chunk, workspace=self._rank_ws)
 
     def step_images(self, images_u8, labels, bboxes, lr, seed):
         """augment.preprocess_train(images_u8, labels, bboxes, the detector's image size, seed) on the detector's stream, then

@@ -17,7 +17,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'host_depthwise_backward', 'depthwise_backward_device', 'depthwise_backward', 'add_rows_device',
            'host_max_pool_backward', 'host_subsample2', 'host_add_upsample2', 'max_pool_backward_device', 'max_pool_backward',
            'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
-           'host_grad_stats', 'grad_stats_device',
+           'host_grad_stats', 'grad_stats_device', 'host_clip_scale', 'host_grad_sq',
            'host_bn_fold', 'bn_fold_device', 'refresh_layers_table', 'refresh_layers_device',
            'host_concat', 'host_split', 'concat_device', 'split_device',
            'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
@@ -685,7 +685,7 @@ def add_upsample2_device(a, b, out=None, stream=None):
 
 # ---- the optimizer step: tf.train.MomentumOptimizer with the reference's L2 term (xdet_momentum_step, csrc/optimizer.hip) --
 
-def host_momentum_step(var, grad, accum, lr, momentum=0.9, weight_decay=0.0, decay=True, dtype=np.float32):
+def host_momentum_step(var, grad, accum, lr, momentum=0.9, weight_decay=0.0, decay=True, dtype=np.float32, scale=np.float32(1)):
     """The NumPy statement of xdet_momentum_step (include/xdet.h) for one variable: var, grad, accum of one shape ->
     (new var, new accum),
 
@@ -693,11 +693,67 @@ def host_momentum_step(var, grad, accum, lr, momentum=0.9, weight_decay=0.0, dec
         accum = momentum * accum + g
         var = var - lr * accum
 
-    every operation rounded on its own in `dtype`: float32 is the op's result bit for bit; float64 the yardstick."""
+    every operation rounded on its own in `dtype`: float32 is the op's result bit for bit; float64 the yardstick.
+    scale (host_clip_scale's result): xdet_momentum_step_clipped, grad * scale in grad's place, one more rounding.  The
+    default 1 is exact -- x * 1 is x -- so the call without it keeps the bits of the statement above."""
     var, grad, accum = np.asarray(var, dtype), np.asarray(grad, dtype), np.asarray(accum, dtype)
+    with np.errstate(invalid='ignore', over='ignore'):
+        grad = grad * dtype(scale)
     g = grad + dtype(weight_decay) * var if decay else grad
     accum = dtype(momentum) * accum + g
     return var - dtype(lr) * accum, accum
+
+
+def host_clip_scale(grad_sq, clip_norm):
+    """The NumPy statement of the clipped step's scale (xdet_momentum_step_clipped, include/xdet.h) from the record's f32
+    grad_sq -> an f32 scalar,
+
+        norm  = sqrt(grad_sq)
+        scale = clip_norm / max(norm, clip_norm)
+
+    two operations, each correctly rounded in f32: exactly 1 wherever norm <= clip_norm, norm == clip_norm included.  A NaN
+    grad_sq gives NaN (the maximum keeps a NaN norm), +inf gives 0."""
+    f = np.float32
+    clip = f(clip_norm)
+    if not np.isfinite(clip) or clip <= 0:
+        raise InvalidArgumentError(-1, 'clip_scale: clip_norm must be finite and positive, got %r' % (clip_norm,))
+    with np.errstate(invalid='ignore'):
+        norm = np.sqrt(f(grad_sq))
+        return f(clip / (clip if norm <= clip else norm))
+
+
+def host_grad_sq(grads):
+    """The record's grad_sq bit for bit: the f32 sum of squares of a sequence of gradient arrays, one per slot, in the fixed
+    order of include/xdet.h -- a vector's (g0^2 + g1^2) + (g2^2 + g3^2), a thread's (t0 + t1) + (t2 + t3) over its four
+    vectors, the 256 threads of a chunk of 4096 elements pairwise, the chunk partials of all slots pairwise under the power
+    of two at or above their count; an element beyond a slot's end is +0.  (host_grad_stats is its float64 yardstick.)"""
+    f = np.float32
+    partials = []
+    with np.errstate(invalid='ignore', over='ignore'):
+        for g in grads:
+            g = np.asarray(g, f).ravel()
+            chunks = -(-g.size // 4096)
+            x = np.zeros(chunks * 4096, f)
+            x[:g.size] = g
+            x = x.reshape(chunks, 4, 256, 4)                # element j of a chunk: vector q = j / 4 = i * 256 + thread
+            x = x * x
+            v = (x[..., 0] + x[..., 1]) + (x[..., 2] + x[..., 3])
+            s = (v[:, 0] + v[:, 1]) + (v[:, 2] + v[:, 3])
+            w = 128
+            while w >= 1:
+                s = s[:, :w] + s[:, w:2 * w]
+                w >>= 1
+            partials.append(s[:, 0])
+        p = np.concatenate(partials)
+        n, P = p.size, 1
+        while P < n:
+            P <<= 1
+        w = P >> 1
+        while w >= 1:
+            m = max(0, min(w, n - w))                       # i < w with i + w < n
+            p[:m] = p[:m] + p[w:w + m]
+            w >>= 1
+    return f(p[0])
 
 
 def _device_array(a, n, who, what, null=True):
@@ -738,7 +794,8 @@ def _table_workspace(workspace, need, who):
     return workspace if workspace is not None else DeviceBuffer(need)
 
 
-def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, stream=None, workspace=None, skip=None, l2_out=None):
+def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, stream=None, workspace=None, skip=None, l2_out=None,
+                         clip=None, scale_out=None):
     """host_momentum_step over a table of variables in one launch (xdet_momentum_step): slots is a sequence of (var, grad, accum,
     n, decay) with var, grad, accum dense DeviceTensors of n elements or DeviceBuffers of at least n floats; var and accum are
     updated in place.  l2=True: -> a DeviceBuffer holding one float, sum over the decayed slots of sum var^2 / 2 on the values
@@ -746,14 +803,36 @@ def momentum_step_device(slots, lr, momentum=0.9, weight_decay=0.0, l2=False, st
     at least 4 bytes.  workspace: a DeviceBuffer of at least xdet_momentum_step_workspace_bytes bytes (default: allocated
     here).  skip (the record grad_stats_device left, a DeviceBuffer of at least 8 bytes; default None: the plain call): the
     guarded step, xdet_momentum_step_guarded on the record's `nonfinite` word -- where that word is not zero no var and no
-    accum byte changes, and l2 is written all the same.  Nothing is synchronised."""
+    accum byte changes, and l2 is written all the same.
+    clip=(stats, clip_norm) (stats: the record grad_stats_device left on the same stream, a DeviceBuffer of at least 16 bytes;
+    default None: the calls above): the clipped step, xdet_momentum_step_clipped -- every gradient times host_clip_scale(the
+    record's grad_sq, clip_norm), host_momentum_step(..., scale=); guarded by the same record where skip is given (skip must
+    then be `stats` itself).  scale_out: the caller's DeviceBuffer of at least 4 bytes that receives the scale (goes with
+    clip).  Without the guard a grad_sq that is not finite gives NaN weights (include/xdet.h says which).
+    Nothing is synchronised."""
     table, slots = _momentum_table(slots, 'momentum_step')
     if skip is not None and (not isinstance(skip, DeviceBuffer) or skip.nbytes < 8 or not skip.ptr):
         raise InvalidArgumentError(-1, 'momentum_step: skip must be the record of grad_stats_device, a DeviceBuffer of at least 8 bytes')
     if l2_out is not None and (not l2 or not isinstance(l2_out, DeviceBuffer) or l2_out.nbytes < 4 or not l2_out.ptr):
         raise InvalidArgumentError(-1, 'momentum_step: l2_out goes with l2=True and must be a DeviceBuffer of at least 4 bytes')
+    if scale_out is not None and (clip is None or not isinstance(scale_out, DeviceBuffer) or scale_out.nbytes < 4 or not scale_out.ptr):
+        raise InvalidArgumentError(-1, 'momentum_step: scale_out goes with clip= and must be a DeviceBuffer of at least 4 bytes')
+    if clip is not None:
+        if not isinstance(clip, (tuple, list)) or len(clip) != 2 or not isinstance(clip[0], DeviceBuffer) or clip[0].nbytes < 16:
+            raise InvalidArgumentError(-1, 'momentum_step: clip must be (the record of grad_stats_device, a DeviceBuffer of at least '
+                                           '16 bytes, clip_norm)')
+        if skip is not None and skip is not clip[0]:
+            raise InvalidArgumentError(-1, 'momentum_step: with clip=, skip must be the same record (one record decides both)')
     ws = _table_workspace(workspace, lib().xdet_momentum_step_workspace_bytes(table, len(slots)), 'momentum_step')
     d_l2 = (l2_out if l2_out is not None else DeviceBuffer(16)) if l2 else None
+    if clip is not None:
+        stats, clip_norm = clip
+        # (a NULL stats_dev and a clip_norm that is not finite or <= 0 are the C door's refusals, ahead of any launch)
+        check(lib().xdet_momentum_step_clipped(table, len(slots), float(lr), float(momentum), float(weight_decay),
+                                               d_l2.ptr if l2 else None, stats.ptr or None, float(clip_norm), 1 if skip is not None else 0,
+                                               scale_out.ptr if scale_out is not None else None, ws.ptr, _handle(stream)))
+        _keep_alive((d_l2 if l2 else scale_out,), (ws, stats, scale_out) + tuple(a for s in slots for a in s[:3]))
+        return d_l2
     if skip is None:
         check(lib().xdet_momentum_step(table, len(slots), float(lr), float(momentum), float(weight_decay),
                                        d_l2.ptr if l2 else None, ws.ptr, _handle(stream)))
