@@ -56,6 +56,12 @@ int xdet_memset(void* dptr, int value, size_t bytes, void* stream);
 int xdet_memcpy_h2d(void* dst, const void* src_host, size_t bytes, void* stream);
 int xdet_memcpy_d2h(void* dst_host, const void* src, size_t bytes, void* stream);
 int xdet_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream);
+/* xdet_memcpy_d2h synchronises `stream` before it returns; xdet_memcpy_d2h_async only enqueues the copy and returns (dst_host
+ * should be pinned, xdet_malloc_host: into pageable memory the runtime may wait all the same); the bytes are there once an
+ * event recorded behind it has been waited for (xdet_event_sync). */
+int xdet_memcpy_d2h_async(void* dst_host, const void* src, size_t bytes, void* stream);
+int xdet_malloc_host(void** hptr, size_t bytes);  /* page-locked host memory (hipHostMalloc), at least 16 bytes */
+int xdet_free_host(void* hptr);                    /* NULL: nothing */
 int xdet_stream_create(void** stream);
 int xdet_stream_destroy(void* stream);
 int xdet_stream_sync(void* stream);
@@ -64,6 +70,7 @@ int xdet_event_create(void** ev);
 int xdet_event_destroy(void* ev);
 int xdet_event_record(void* ev, void* stream);
 int xdet_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* syncs on ev_stop */
+int xdet_event_sync(void* ev);                     /* the host waits until everything enqueued ahead of the record has run */
 
 /* ---- A9: PsRoiAlign forward --------------------------------------------------------------
  * Replaces op_module.ps_roi_align(inputs, rois, grid_dim_width, grid_dim_height, pool_method)
@@ -1068,6 +1075,35 @@ size_t xdet_tensors_concat_workspace_bytes(const xdet_pack_slot* slots_host, int
 size_t xdet_tensors_split_workspace_bytes(const xdet_pack_slot* slots_host, int n_slots);
 int xdet_tensors_concat(const xdet_pack_slot* slots_host, int n_slots, void* workspace, void* stream);
 int xdet_tensors_split(const xdet_pack_slot* slots_host, int n_slots, void* workspace, void* stream);
+
+/* ---- the checkpoint op (csrc/crc32c.hip): checksum, and optionally copy, a table of device buffers in one pass --------------
+ * For every slot i, crc_out_dev[i] = the CRC-32C of src[0 .. bytes): Castagnoli, reflected polynomial 0x82f63b78, initial
+ * register and final xor 0xffffffff, UNMASKED -- exactly what xdet.tf_checkpoint.crc32c(bytes) returns (the NumPy statement;
+ * a TensorFlow bundle stores mask_crc of it).  bytes == 0 gives 0 and touches neither src nor dst.
+ * Where dst is not NULL, dst[0 .. bytes) receives the same bytes in the same pass: every source byte is read once, no bit is
+ * changed (NaN payloads, -0 and denormals arrive as they left), and no byte outside [dst, dst + bytes) is written (a byte
+ * tail is stored as bytes).  Slots with and without dst may share a table; src and dst of a slot must not overlap.
+ * Pointers must be 4-byte aligned; any length is allowed.  A slot whose src and dst (where given) are both 16-byte aligned
+ * moves in 16-byte accesses, every other one in dwords.
+ * Two launches serve the whole table, whatever the number of slots: a slot is cut into chunks of xdet_crc32c_chunk_bytes() =
+ * 32768 bytes (256 lanes x 128 bytes; a slot's last chunk is short, chunks never cross a slot), one workgroup per chunk
+ * writes the chunk's raw register into the workspace, combining its lanes through the CRC's linearity; then one workgroup per
+ * slot folds the slot's registers as a tree with powers x^(8n) mod P that are computed here on the host and uploaded with the
+ * slot table, as xdet_momentum_step uploads its tables.  Integer arithmetic only: no atomics, no fence, no workgroup waits
+ * for another, and the call does not synchronise.
+ * workspace: xdet_crc32c_workspace_bytes(slots, n_slots) bytes of device memory (0 for a table the call refuses); it needs no
+ *   initialisation and may be larger; a call behind a call on the same stream may reuse it.
+ * Limits: at most 65536 slots and 2^22 chunks (128 GiB) per table.
+ * Errors -> XDET_ERR_INVALID_ARG before any GPU work: a NULL or empty table, a NULL src with bytes > 0, a src or dst that is
+ *   not 4-byte aligned, a NULL (or misaligned) crc_out_dev, a NULL workspace, a table beyond the limits. */
+typedef struct {
+  const void* src;
+  void* dst;
+  size_t bytes;
+} xdet_crc_slot;
+size_t xdet_crc32c_chunk_bytes(void);
+size_t xdet_crc32c_workspace_bytes(const xdet_crc_slot* slots_host, int n_slots);
+int xdet_crc32c(const xdet_crc_slot* slots_host, int n_slots, uint32_t* crc_out_dev, void* workspace, void* stream);
 
 /* ---- the gradient average of data-parallel training (csrc/grad_average.hip; the exchange itself is
  * xdet_comm_average_gradients in csrc/comm.hip): every rank's gradients become the rank-ordered mean, ahead of the step ------

@@ -51,6 +51,9 @@ int xdet_free(void* dptr) { if (dptr) XDET_HIP(hipFree(dptr)); return XDET_OK; }
 int xdet_memset(void* dptr, int value, size_t bytes, void* stream) { XDET_HIP(hipMemsetAsync(dptr, value, bytes, S(stream))); return XDET_OK; }
 int xdet_memcpy_h2d(void* dst, const void* src, size_t bytes, void* stream) { XDET_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, S(stream))); return XDET_OK; }
 int xdet_memcpy_d2h(void* dst, const void* src, size_t bytes, void* stream) { XDET_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, S(stream))); XDET_HIP(hipStreamSynchronize(S(stream))); return XDET_OK; }
+int xdet_memcpy_d2h_async(void* dst, const void* src, size_t bytes, void* stream) { XDET_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, S(stream))); return XDET_OK; }
+int xdet_malloc_host(void** hptr, size_t bytes) { XDET_REQUIRE(hptr, "hptr is NULL"); XDET_HIP(hipHostMalloc(hptr, std::max<size_t>(bytes, 16), hipHostMallocDefault)); return XDET_OK; }
+int xdet_free_host(void* hptr) { if (hptr) XDET_HIP(hipHostFree(hptr)); return XDET_OK; }
 int xdet_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) { XDET_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, S(stream))); return XDET_OK; }
 int xdet_stream_create(void** stream) { hipStream_t s; XDET_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); *stream = s; return XDET_OK; }
 int xdet_stream_destroy(void* stream) { XDET_HIP(hipStreamDestroy(S(stream))); return XDET_OK; }
@@ -58,6 +61,7 @@ int xdet_stream_sync(void* stream) { XDET_HIP(hipStreamSynchronize(S(stream))); 
 int xdet_event_create(void** ev) { hipEvent_t e; XDET_HIP(hipEventCreate(&e)); *ev = e; return XDET_OK; }
 int xdet_event_destroy(void* ev) { XDET_HIP(hipEventDestroy(reinterpret_cast<hipEvent_t>(ev))); return XDET_OK; }
 int xdet_event_record(void* ev, void* stream) { XDET_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(ev), S(stream))); return XDET_OK; }
+int xdet_event_sync(void* ev) { XDET_HIP(hipEventSynchronize(reinterpret_cast<hipEvent_t>(ev))); return XDET_OK; }
 int xdet_event_elapsed_ms(void* a, void* b, float* ms) {
   XDET_HIP(hipEventSynchronize(reinterpret_cast<hipEvent_t>(b)));
   XDET_HIP(hipEventElapsedTime(ms, reinterpret_cast<hipEvent_t>(a), reinterpret_cast<hipEvent_t>(b)));

@@ -70,6 +70,11 @@ class PackSlot(ctypes.Structure):
     _fields_ = [('merged', c_void_p), ('outer', c_int), ('n_parts', c_int), ('part', c_void_p * 4), ('width', c_int * 4)]
 
 
+class CrcSlot(ctypes.Structure):
+    """xdet_crc_slot: one buffer of xdet_crc32c -- its device pointer, where to copy it (NULL: checksum only), its bytes"""
+    _fields_ = [('src', c_void_p), ('dst', c_void_p), ('bytes', c_size_t)]
+
+
 class NetWeightDev(ctypes.Structure):
     """xdet_net_weight_dev: one array of xdet_net_refresh_weights -- the checkpoint's name and the dense f32 data on the device"""
     _fields_ = [('name', ctypes.c_char_p), ('data', c_void_p)]
@@ -100,6 +105,9 @@ SIGNATURES = {
     'xdet_memset': (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     'xdet_memcpy_h2d': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'xdet_memcpy_d2h': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'xdet_memcpy_d2h_async': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    'xdet_malloc_host': (c_int, [ctypes.POINTER(c_void_p), c_size_t]),
+    'xdet_free_host': (c_int, [c_void_p]),
     'xdet_memcpy_d2d': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     'xdet_stream_create': (c_int, [ctypes.POINTER(c_void_p)]),
     'xdet_stream_destroy': (c_int, [c_void_p]),
@@ -107,6 +115,7 @@ SIGNATURES = {
     'xdet_event_create': (c_int, [ctypes.POINTER(c_void_p)]),
     'xdet_event_destroy': (c_int, [c_void_p]),
     'xdet_event_record': (c_int, [c_void_p, c_void_p]),
+    'xdet_event_sync': (c_int, [c_void_p]),
     'xdet_event_elapsed_ms': (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_float)]),
     'xdet_psroialign_fwd': (c_int, [PF, PF, PF, PI] + [c_int] * 12 + [c_void_p]),
     'xdet_psroialign_grad': (c_int, [PF, PF, PI, PF] + [c_int] * 10 + [c_void_p]),
@@ -229,6 +238,9 @@ SIGNATURES = {
     'xdet_tensors_split_workspace_bytes': (c_size_t, [ctypes.POINTER(PackSlot), c_int]),
     'xdet_tensors_concat': (c_int, [ctypes.POINTER(PackSlot), c_int, c_void_p, c_void_p]),
     'xdet_tensors_split': (c_int, [ctypes.POINTER(PackSlot), c_int, c_void_p, c_void_p]),
+    'xdet_crc32c_chunk_bytes': (c_size_t, []),
+    'xdet_crc32c_workspace_bytes': (c_size_t, [ctypes.POINTER(CrcSlot), c_int]),
+    'xdet_crc32c': (c_int, [ctypes.POINTER(CrcSlot), c_int, c_void_p, c_void_p, c_void_p]),
     'xdet_net_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(LightHeadConfig)]),
     'xdet_net_set_weight': (c_int, [c_void_p, ctypes.c_char_p, PF, c_int, ctypes.POINTER(c_int64)]),
     'xdet_net_set_option': (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_char_p]),

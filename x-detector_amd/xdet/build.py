@@ -39,6 +39,7 @@ SOURCES = [
     ('conv_repack.hip', ['-ffp-contract=off']),
     ('weight_pack.hip', ['-ffp-contract=off']),
     ('grad_average.hip', ['-ffp-contract=off']),
+    ('crc32c.hip', []),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('augment.hip', ['-ffp-contract=off']),
     ('jpeg.hip', ['-ffp-contract=off']),

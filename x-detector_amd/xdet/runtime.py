@@ -74,6 +74,10 @@ class Event(object):
     def record(self, stream=None):
         check(lib().xdet_event_record(self.handle, stream.handle if stream else None))
 
+    def synchronize(self):
+        """the host waits until everything enqueued ahead of the last record() has run (xdet_event_sync)"""
+        check(lib().xdet_event_sync(self.handle))
+
     def elapsed_ms(self, stop):
         ms = ctypes.c_float()
         check(lib().xdet_event_elapsed_ms(self.handle, stop.handle, ctypes.byref(ms)))
@@ -122,6 +126,36 @@ class DeviceBuffer(object):
     def free(self):
         if self.ptr:
             lib().xdet_free(c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PinnedBuffer(object):
+    """An owned page-locked host allocation (xdet_malloc_host): the target of a device-to-host copy the host does not wait for.
+    view(offset, shape, dtype) -> a NumPy array over its bytes, valid while the buffer lives."""
+    def __init__(self, nbytes):
+        p = c_void_p()
+        check(lib().xdet_malloc_host(ctypes.byref(p), nbytes))
+        self.ptr = p.value
+        self.nbytes = nbytes
+        self._bytes = (ctypes.c_ubyte * max(nbytes, 1)).from_address(self.ptr)
+
+    def view(self, offset, shape, dtype=np.float32):
+        dtype = np.dtype(dtype)
+        n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
+        if offset < 0 or offset + n * dtype.itemsize > self.nbytes:
+            raise ValueError('PinnedBuffer.view: %d bytes at %d are outside %d' % (n * dtype.itemsize, offset, self.nbytes))
+        return np.frombuffer(self._bytes, dtype, n, offset).reshape(shape)
+
+    def free(self):
+        if self.ptr:
+            self._bytes = None
+            lib().xdet_free_host(c_void_p(self.ptr))
             self.ptr = None
 
     def __del__(self):

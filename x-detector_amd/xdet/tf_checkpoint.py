@@ -380,10 +380,15 @@ def _build_block(items, restart_interval=16):
     return bytes(out)
 
 
-def write_checkpoint(prefix, tensors, block_entries=24):
+def write_checkpoint(prefix, tensors, block_entries=24, crcs=None):
     """{name: ndarray} -> <prefix>.index + <prefix>.data-00000-of-00001 (one shard, no compression), byte layout
-    as tensorflow/core/util/tensor_bundle writes it (entries sorted by name, CRC32C per tensor and per block)."""
+    as tensorflow/core/util/tensor_bundle writes it (entries sorted by name, CRC32C per tensor and per block).
+    crcs: {name: the UNMASKED CRC-32C of that tensor's bytes}, e.g. computed on the device where the tensor lay
+    (xdet.ops.crc32c_device); a name present there is not checksummed again -- its value is written as given, and its bytes
+    go to the data shard without a copy -- every other name is checksummed here.  Without it every byte written is the same."""
     names = sorted(tensors)
+    if crcs:
+        return _write_checkpoint_streamed(prefix, tensors, names, block_entries, crcs)
     data = bytearray()
     items = [(b'', _pb_varint_field(1, 1) + _pb_varint_field(2, 0) +
               _pb_bytes_field(3, _pb_varint_field(1, 1)))]           # num_shards 1, little endian, version {producer 1}
@@ -400,6 +405,31 @@ def write_checkpoint(prefix, tensors, block_entries=24):
         data += raw
     with open(prefix + '.data-00000-of-00001', 'wb') as f:
         f.write(bytes(data))
+    return _write_index(prefix, items, block_entries)
+
+
+def _write_checkpoint_streamed(prefix, tensors, names, block_entries, crcs):
+    """write_checkpoint with supplied checksums: the same two files, the data shard written tensor by tensor"""
+    items = [(b'', _pb_varint_field(1, 1) + _pb_varint_field(2, 0) + _pb_bytes_field(3, _pb_varint_field(1, 1)))]
+    offset = 0
+    with open(prefix + '.data-00000-of-00001', 'wb') as f:
+        for n in names:
+            a = np.asarray(tensors[n], order='C')
+            if a.dtype not in _DT_OF:
+                raise CheckpointError('%s: dtype %s not supported' % (n, a.dtype))
+            a = a.astype(a.dtype.newbyteorder('<'), copy=False)
+            crc = int(crcs[n]) & 0xffffffff if n in crcs else crc32c(a.tobytes())
+            shape = b''.join(_pb_bytes_field(2, _pb_varint_field(1, int(d))) for d in a.shape)
+            entry = (_pb_varint_field(1, _DT_OF[a.dtype]) + _pb_bytes_field(2, shape) +
+                     (_pb_varint_field(4, offset) if offset else b'') + _pb_varint_field(5, a.nbytes) +
+                     _put_varint((6 << 3) | 5) + struct.pack('<I', mask_crc(crc)))
+            items.append((n.encode('utf-8'), entry))
+            f.write(a.data if a.ndim else a.tobytes())
+            offset += a.nbytes
+    return _write_index(prefix, items, block_entries)
+
+
+def _write_index(prefix, items, block_entries):
     table = bytearray()
     index_items = []
 

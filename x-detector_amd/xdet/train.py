@@ -17,7 +17,7 @@ import numpy as np
 
 from . import train_ops, ops
 from ._lib import lib, check, XdetError, InvalidArgumentError, MomentumSlot
-from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, get_precision, set_precision, synchronize, _det, _sync
+from .runtime import DeviceBuffer, DeviceTensor, PinnedBuffer, Event, to_device, to_host, get_precision, set_precision, synchronize, _det, _sync
 
 __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEAD_VARIABLES', 'LARGE_SEP_EPS', 'LARGE_SEP_MOMENTUM',
            'EXIT_FLOW_UNITS', 'EXIT_FLOW_BNS', 'EXIT_FLOW_VARIABLES', 'EXIT_FLOW_MOVING', 'EXIT_FLOW_EPS', 'EXIT_FLOW_MOMENTUM',
@@ -27,7 +27,7 @@ __all__ = ['LARGE_SEP_VARIABLES', 'LARGE_SEP_MOVING', 'RPN_HEAD_VARIABLES', 'HEA
            'large_sep_backward', 'exit_flow_train', 'exit_flow_backward', 'middle_flow_train', 'middle_flow_backward',
            'entry_flow_train', 'entry_flow_backward', 'host_middle_flow_train', 'host_middle_flow_backward',
            'host_entry_flow_train', 'host_entry_flow_backward', 'piecewise_learning_rate', 'decayed', 'eval_net_groups', 'optimizer_variables',
-           'MomentumOptimizer', 'StepPending', 'TrainStep', 'StepResult', 'LOGGED_SCALARS', 'STEM_CONVS', 'STEM_VARIABLES', 'STEM_MOVING', 'STEM_EPS', 'STEM_MOMENTUM', 'STEM_STAGE', 'STEM', 'StemState',
+           'MomentumOptimizer', 'StepPending', 'Snapshot', 'checkpoint_names', 'TrainStep', 'StepResult', 'LOGGED_SCALARS', 'STEM_CONVS', 'STEM_VARIABLES', 'STEM_MOVING', 'STEM_EPS', 'STEM_MOMENTUM', 'STEM_STAGE', 'STEM', 'StemState',
            'check_stem', 'stem_train', 'stem_backward', 'host_stem_train', 'host_stem_backward']
 
 LARGE_SEP_VARIABLES = tuple('large_sep_feature/%s/%s/%s' % (br, conv, v) for br in ('Branch_0', 'Branch_1')
@@ -1415,6 +1415,71 @@ class StepPending(object):
         return out
 
 
+def checkpoint_names(variables, batch_norms=(), model_scope='xception_lighthead'):
+    """The reference's checkpoint names of a training state, in the order MomentumOptimizer.snapshot() lays it out: every
+    variable as '<scope>/<variable>', then every momentum slot as '<scope>/<variable>/Momentum' (tf.train.MomentumOptimizer's
+    slot name), then '<scope>/<bn>/moving_mean' and '<scope>/<bn>/moving_variance' of every batch norm name given, and
+    'global_step' (outside the scope: tf.train.get_or_create_global_step, light_head_rfcn_train.py:283) last.
+    model_scope '' or None: no prefix."""
+    pre = model_scope + '/' if model_scope else ''
+    return ([pre + v for v in variables] + [pre + v + '/Momentum' for v in variables] +
+            ['%s%s/%s' % (pre, bn, k) for bn in batch_norms for k in ('moving_mean', 'moving_variance')] + ['global_step'])
+
+
+class Snapshot(object):
+    """What MomentumOptimizer.snapshot() returns: the training state at the point of the call in stream order -- masters,
+    momentum slots, moving statistics and their CRC-32Cs -- on its way into the optimizer's pinned staging.  Nothing has been
+    waited for.  write(prefix) / tensors() wait for the snapshot's event (not for the stream: steps enqueued behind the snapshot
+    go on); release() hands the staging back without writing.  The optimizer holds one snapshot at a time."""
+
+    def __init__(self, opt, step, layout, total, event):
+        self.opt, self.step, self._layout, self._total, self._event, self._done = opt, int(step), layout, total, event, False
+
+    def _arrays(self):
+        """-> ({name without scope: a view of the staging}, {the same name: its unmasked CRC-32C as the device computed it})"""
+        if self._done:
+            raise InvalidArgumentError(-1, 'Snapshot: already written or released (its staging may hold a later snapshot)')
+        self._event.synchronize()
+        st = self.opt._snap_host
+        crcs = st.view(self._total, (len(self._layout),), np.uint32)
+        return ({name: st.view(off, shape) for name, off, shape in self._layout},
+                {name: int(c) for (name, _, _), c in zip(self._layout, crcs)})
+
+    def _named(self, arrays, base, model_scope):
+        pre = model_scope + '/' if model_scope else ''
+        out = {pre + k: np.asarray(v, np.float32) for k, v in (base or {}).items() if k not in arrays}
+        out.update((pre + k, v) for k, v in arrays.items())
+        out['global_step'] = np.asarray(self.step, np.int64)
+        return out
+
+    def tensors(self, base=None, model_scope='xception_lighthead'):
+        """-> {checkpoint name: host array}, what write() writes (copies: they outlive the snapshot)"""
+        arrays, _ = self._arrays()
+        return {k: np.array(v) for k, v in self._named(arrays, base, model_scope).items()}
+
+    def write(self, prefix, base=None, model_scope='xception_lighthead'):
+        """Wait for the snapshot's event and write a TensorFlow V2 bundle (tf_checkpoint.write_checkpoint) under the reference's
+        names (checkpoint_names): '<scope>/<variable>', '<scope>/<variable>/Momentum', the moving statistics and global_step
+        (int64, the optimizer's `steps` at the snapshot).  The CRCs of the snapshot's tensors are the ones the device computed
+        beside the copy (write_checkpoint(crcs=)): the host does no per-byte work on them.  base: a weights dict that supplies
+        the variables outside the optimizer's reach (reach='flows'), checksummed on the host.  Releases the snapshot.
+        -> prefix"""
+        from .tf_checkpoint import write_checkpoint
+        arrays, crcs = self._arrays()
+        pre = model_scope + '/' if model_scope else ''
+        write_checkpoint(prefix, self._named(arrays, base, model_scope), crcs={pre + k: c for k, c in crcs.items()})
+        self.release()
+        return prefix
+
+    def release(self):
+        """hand the staging back to the optimizer: its next snapshot() or restore() may overwrite it"""
+        if not self._done:
+            self._event.synchronize()                      # (the copy into the staging must not outlive its owner's claim)
+            self._done = True
+            if self.opt._snapshot is self:
+                self.opt._snapshot = None
+
+
 class MomentumOptimizer(object):
     """tf.train.MomentumOptimizer(lr, momentum) over the loss the reference minimises, loss + weight_decay * sum l2_loss(v) over
     the variables `decayed` names (light_head_rfcn_train.py:420,435), for the flow stages `det` was built with: the variables
@@ -1441,6 +1506,8 @@ class MomentumOptimizer(object):
     _stem = None                                           # StemState of a detector built with stem_train=True
     _pending = None                                        # the StepPending of a step(..., sync=False) that has not been read
     _scale = None                                          # the clipped step's scale on the device (allocated by the first one)
+    _snapshot = None                                       # the Snapshot that has been neither written nor released
+    _snap_dev = _snap_host = _snap_ws = _snap_event = None  # the snapshot buffer, its pinned staging, the table workspace
 
     def __init__(self, det, momentum=0.9, weight_decay=2e-4, reach='flows'):
         flows = [(ENTRY, ENTRY_FLOW_VARIABLES), (MIDDLE, MIDDLE_FLOW_VARIABLES), (EXIT, EXIT_FLOW_VARIABLES)]
@@ -1625,6 +1692,18 @@ class MomentumOptimizer(object):
         if getattr(self, '_l2', None) is not None:
             more['l2_out'] = self._l2
         l2 = train_ops.momentum_step_device(slots, lr, self.momentum, self.weight_decay, l2=True, stream=d.stream, workspace=self._ws, **more)
+        self._refresh_from_masters()
+        if not guard:                                      # (a guarded step counts once its record has been read)
+            self.steps += 1
+        self._pending = StepPending(self, float(lr), guard, clip, comm if not sync else None)
+        self._pending.l2, self._pending.stats, self._pending.scale = l2, stats, self._scale if clip else None
+        return self._pending.read() if sync else self._pending
+
+    def _refresh_from_masters(self):
+        """Everything step enqueues behind the momentum step, in its order, so the forward layers and the backwards' operands
+        hold what the masters hold: (reach='all') one concat_device table and the b0 + b1 row; the refresh_layers_device table;
+        (reach='all') xdet_net_refresh_heads; and the drop of every stage's saved state.  restore() ends with the same calls."""
+        d = self.det
         if self.reach == 'all':                            # the merged tensors the layers and the backwards read, from the masters
             train_ops.concat_device(self._concat, stream=d.stream, workspace=self._concat_ws)
             b0, b1, bb, co = self._bias_sum
@@ -1636,11 +1715,6 @@ class MomentumOptimizer(object):
             d.refresh_heads({v: self._master[v][0] for v in self._head_names})
             d._heads_step = getattr(d, '_heads_step', 0) + 1
         new_body(d)
-        if not guard:                                      # (a guarded step counts once its record has been read)
-            self.steps += 1
-        self._pending = StepPending(self, float(lr), guard, clip, comm if not sync else None)
-        self._pending.l2, self._pending.stats, self._pending.scale = l2, stats, self._scale if clip else None
-        return self._pending.read() if sync else self._pending
 
     def _refresh_slots(self):
         """the training forward layers and their masters, as the units hold them at this moment: refresh_layers_device's table"""
@@ -1729,6 +1803,137 @@ class MomentumOptimizer(object):
             for k in ('moving_mean', 'moving_variance'):
                 out['%s/%s' % (bn.name, k)] = to_host(getattr(bn, k).ptr, (bn.co,))
         return out
+
+    # ---- checkpoints: a device snapshot with CRC-32C, and the way back in ------------------------------------------------
+
+    def _state_layout(self):
+        """the training state as snapshot() lays it out: [(name, live device pointer, shape, offset in the snapshot buffer)] of
+        every master, every momentum slot (name + '/Momentum') and the moving statistics of every batch norm a training
+        forward moves, each on a 16-byte boundary; -> (the list, the buffer's bytes in front of the CRC words)"""
+        items = [(v, self._master[v][0].ptr, tuple(self._master[v][1])) for v in self.variables]
+        items += [(v + '/Momentum', self._slot[v].ptr, tuple(self._master[v][1])) for v in self.variables]
+        for bn in self._moving_batch_norms():
+            items += [('%s/%s' % (bn.name, k), getattr(bn, k).ptr, (bn.co,)) for k in ('moving_mean', 'moving_variance')]
+        out, off = [], 0
+        for name, ptr, shape in items:
+            out.append((name, ptr, shape, off))
+            off += (4 * math.prod(shape) + 15) // 16 * 16
+        return out, off
+
+    def _snapshot_buffers(self, layout, total):
+        """the snapshot buffer [state | one CRC word per tensor | a second row of CRC words], its pinned staging, the table's
+        workspace and the event: allocated at the first snapshot() or restore()"""
+        if self._snap_dev is None:
+            n = len(layout)
+            table, _ = train_ops.crc32c_table([(1 << 4, 4 * math.prod(shape)) for _, _, shape, _ in layout])   # (sizes only)
+            self._snap_ws = DeviceBuffer(lib().xdet_crc32c_workspace_bytes(table, n))
+            self._snap_dev = DeviceBuffer(total + 8 * n)
+            self._snap_host = PinnedBuffer(total + 4 * n)
+            self._snap_event = Event()
+
+    def snapshot(self):
+        """The training state of this moment, put aside without a wait -> a train.Snapshot.  On the detector's stream: ONE
+        xdet_crc32c table copies every master of `self.variables`, every momentum slot and the moving_mean / moving_variance of
+        every batch norm of _moving_batch_norms() into one device buffer the optimizer owns (allocated at the first snapshot)
+        and writes their CRC-32Cs behind them; one asynchronous device-to-host copy carries buffer and CRCs into pinned
+        staging; an event is recorded.  The snapshot holds the state at the point of the call in stream order: steps enqueued
+        later do not reach it, and the host returns at once.  Snapshot.write(prefix) writes the bundle.
+        Refused ahead of any launch: the result of the last step has not been read (under the guard the step count is not
+        known until read()); a previous snapshot has been neither written nor released (there is one staging buffer)."""
+        if self._pending is not None:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.snapshot: the result of the last step(..., sync=False) has not been read: '
+                                           'call its read() first (the step count of a guarded step is not known until then)')
+        if self._snapshot is not None:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.snapshot: the previous snapshot has been neither written nor released '
+                                           '(Snapshot.write / Snapshot.release): its staging is still in use')
+        layout, total = self._state_layout()
+        self._snapshot_buffers(layout, total)
+        d, dev = self.det, self._snap_dev
+        table, _ = train_ops.crc32c_table([(ptr, 4 * math.prod(shape)) for _, ptr, shape, _ in layout],
+                                          copy_to=[dev.ptr + off for _, _, _, off in layout], who='snapshot')
+        train_ops.crc32c_launch(table, dev.ptr + total, stream=d.stream, workspace=self._snap_ws)
+        check(lib().xdet_memcpy_d2h_async(self._snap_host.ptr, dev.ptr, total + 4 * len(layout), d.stream.handle))
+        self._snap_event.record(d.stream)
+        self._snapshot = Snapshot(self, self.steps, [(name, off, shape) for name, _, shape, off in layout], total, self._snap_event)
+        return self._snapshot
+
+    def restore(self, prefix, model_scope='xception_lighthead', slots='require'):
+        """Take masters, momentum slots, moving statistics and the step count from the TensorFlow V2 bundle `prefix` (what
+        Snapshot.write wrote, or the reference's own model.ckpt-N) back onto the device -> {'step': global_step, 'tensors':
+        the checkpoint names restored}.  Everything a step needs is checked ahead of any copy -- every variable, its
+        '/Momentum', every moving statistic, and global_step, each float32 (global_step int64) in the variable's shape and
+        inside its data shard; a refusal (CheckpointError) names what is missing or mis-shaped -- and an unread pending step or
+        a live snapshot is refused (InvalidArgumentError).
+        Then the tensors' bytes go from the file into the pinned staging and up into the snapshot buffer; ONE xdet_crc32c
+        without destinations checksums them THERE, and the host compares the words with the index's CRCs: the bytes are
+        checked as they arrived in device memory.  A mismatch raises CheckpointError naming the tensor, and no master, slot
+        or statistic has changed.  Only then does one more table copy the buffer into the live tensors, followed by exactly
+        the launches step makes behind the momentum step (_refresh_from_masters), so forward layers and backward operands
+        match the masters; `steps` = global_step.  refresh_eval_net() afterwards works as after a step.
+        slots='zero': a weights-only checkpoint is accepted -- the momentum slots are zeroed whatever the file holds, and the
+        step is 0 where global_step is absent.
+        Data-parallel: every rank restores the same file and ends bit-equal."""
+        from .tf_checkpoint import CheckpointReader, CheckpointError, DT_FLOAT, DT_INT64, mask_crc
+        if slots not in ('require', 'zero'):
+            raise InvalidArgumentError(-1, "MomentumOptimizer.restore: slots must be 'require' or 'zero', got %r" % (slots,))
+        if self._pending is not None:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.restore: the result of the last step(..., sync=False) has not been read: '
+                                           'call its read() first')
+        if self._snapshot is not None:
+            raise InvalidArgumentError(-1, 'MomentumOptimizer.restore: a snapshot has been neither written nor released: its staging '
+                                           'is still in use')
+        layout, total = self._state_layout()
+        pre = model_scope + '/' if model_scope else ''
+        rd = CheckpointReader(prefix)
+        bad, plan = [], []                                  # plan: (name, entry or None for zeros, live pointer, shape, offset)
+        for name, ptr, shape, off in layout:
+            zero = slots == 'zero' and name.endswith('/Momentum')
+            e = None if zero else rd.entries.get(pre + name)
+            if zero:
+                pass
+            elif e is None:
+                bad.append('%s is missing' % (pre + name))
+            elif e['sliced'] or e['dtype'] != DT_FLOAT:
+                bad.append('%s is not a dense float32 tensor' % (pre + name))
+            elif tuple(e['shape']) != tuple(shape) or e['size'] != 4 * math.prod(shape):
+                bad.append('%s has shape %r (%d bytes), the variable %r' % (pre + name, tuple(e['shape']), e['size'], tuple(shape)))
+            elif e['offset'] + e['size'] > rd._shard(e['shard_id']).size:
+                bad.append('%s lies outside its data shard (truncated)' % (pre + name))
+            plan.append((name, e, ptr, shape, off))
+        g = rd.entries.get('global_step')
+        if g is None and slots == 'require':
+            bad.append('global_step is missing')
+        elif g is not None and (g['dtype'] != DT_INT64 or tuple(g['shape']) != ()):
+            bad.append('global_step is not an int64 scalar')
+        if bad:
+            raise CheckpointError('MomentumOptimizer.restore: %s: %s%s' % (prefix, '; '.join(bad[:8]),
+                                                                           ' (and %d more)' % (len(bad) - 8) if len(bad) > 8 else ''))
+        step = int(rd.get_tensor('global_step', verify_crc=True)) if g is not None else 0
+        if step < 0:
+            raise CheckpointError('MomentumOptimizer.restore: %s: global_step is %d' % (prefix, step))
+        self._snapshot_buffers(layout, total)
+        d, dev, host = self.det, self._snap_dev, self._snap_host
+        for name, e, _, shape, off in plan:                 # file -> staging: a copy, no arithmetic and no checksum on the host
+            view = host.view(off, (4 * math.prod(shape),), np.uint8)
+            if e is None:
+                view[:] = 0
+            else:
+                view[:] = rd._shard(e['shard_id'])[e['offset']:e['offset'] + e['size']]
+        n = len(plan)
+        check(lib().xdet_memcpy_h2d(dev.ptr, host.ptr, total, d.stream.handle))
+        spans = [(dev.ptr + off, 4 * math.prod(shape)) for _, _, _, shape, off in plan]
+        table, _ = train_ops.crc32c_table(spans, who='restore')
+        train_ops.crc32c_launch(table, dev.ptr + total, stream=d.stream, workspace=self._snap_ws)
+        got = to_host(dev.ptr + total, (n,), np.uint32, d.stream)          # (the one wait of a restore)
+        for (name, e, _, _, _), c in zip(plan, got):
+            if e is not None and e['crc32c'] is not None and mask_crc(int(c)) != e['crc32c']:
+                raise CheckpointError('MomentumOptimizer.restore: %s: %s: tensor checksum mismatch (as it arrived in device memory); '
+                                      'nothing was restored' % (prefix, pre + name))
+        table, _ = train_ops.crc32c_table(spans, copy_to=[ptr for _, _, ptr, _, _ in plan], who='restore')
+        train_ops.crc32c_launch(table, dev.ptr + total + 4 * n, stream=d.stream, workspace=self._snap_ws)
+        self._refresh_from_masters()
+        self.steps = step
+        return {'step': step, 'tensors': [pre + name for name, e, _, _, _ in plan if e is not None] + (['global_step'] if g is not None else [])}
 
 
 # ---- the single-call driver: one training step from a batch ------------------------------------------------------------------

@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot, LayerRefresh, PackSlot
+from ._lib import lib, check, InvalidArgumentError, MomentumSlot, GradSlot, LayerRefresh, PackSlot, CrcSlot
 from .runtime import DeviceBuffer, DeviceTensor, to_device, to_host, synchronize
 
 __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
@@ -19,7 +19,7 @@ __all__ = ['host_dense_backward', 'dense_backward_device', 'dense_backward',
            'subsample2_device', 'add_upsample2_device', 'host_momentum_step', 'momentum_step_device',
            'host_grad_stats', 'grad_stats_device', 'host_clip_scale', 'host_grad_sq',
            'host_bn_fold', 'bn_fold_device', 'refresh_layers_table', 'refresh_layers_device',
-           'host_concat', 'host_split', 'concat_device', 'split_device',
+           'host_concat', 'host_split', 'concat_device', 'split_device', 'crc32c_table', 'crc32c_launch', 'crc32c_device',
            'host_average_gradients', 'grad_flat_offsets', 'grad_pack_device', 'grad_reduce_ranks_device']
 
 
@@ -1045,6 +1045,93 @@ def split_device(slots, stream=None, workspace=None):
     part_p[o, :] = merged[o, off_p : off_p + width_p].  Two slots may read one merged tensor."""
     l = lib()
     _pack_device(slots, 'tensors_split', l.xdet_tensors_split_workspace_bytes, l.xdet_tensors_split, stream, workspace)
+
+
+# ---- the checkpoint op (xdet_crc32c, csrc/crc32c.hip): checksum, and optionally copy, a table of device buffers ---------------
+
+def _crc_span(a, who, what):
+    """one buffer of the crc32c doors -> (pointer, bytes, the object to keep alive): a DeviceBuffer (all of it), a dense
+    DeviceTensor (its elements), or (pointer-like, bytes) -- an integer address, a DeviceBuffer or a DeviceTensor and the bytes
+    to take from there"""
+    if isinstance(a, DeviceBuffer):
+        return a.ptr or 0, int(a.nbytes), a
+    if isinstance(a, DeviceTensor):
+        if a.ld != a.shape[-1]:
+            raise InvalidArgumentError(-1, '%s: %s must be dense, got shape %r with ld %d' % (who, what, a.shape, a.ld))
+        return a.ptr, 4 * math.prod(a.shape), a
+    if isinstance(a, (tuple, list)) and len(a) == 2:
+        at, n = a
+        ptr = at.ptr if isinstance(at, (DeviceBuffer, DeviceTensor)) else at
+        if ptr is not None and (isinstance(ptr, bool) or not isinstance(ptr, (int, np.integer))):
+            raise InvalidArgumentError(-1, '%s: %s has a pointer of type %s' % (who, what, type(ptr).__name__))
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise InvalidArgumentError(-1, '%s: %s has bytes = %r (a non-negative integer)' % (who, what, n))
+        return int(ptr or 0), int(n), at
+    raise InvalidArgumentError(-1, '%s: %s must be a DeviceBuffer, a dense DeviceTensor or (pointer, bytes), got %s'
+                               % (who, what, type(a).__name__))
+
+
+def crc32c_table(buffers, copy_to=None, who='crc32c'):
+    """the argument checks of the crc32c doors, without touching the GPU -> (the xdet_crc_slot table, the objects it points to).
+    buffers: a sequence of DeviceBuffer / dense DeviceTensor / (pointer, bytes); copy_to: None, or one destination per buffer
+    -- None (checksum only), a pointer, a DeviceBuffer or a DeviceTensor that holds at least the buffer's bytes."""
+    buffers = list(buffers)
+    if not buffers:
+        raise InvalidArgumentError(-1, '%s: an empty slot table' % who)
+    if len(buffers) > 65536:
+        raise InvalidArgumentError(-1, '%s: at most 65536 slots, got %d' % (who, len(buffers)))
+    dsts = list(copy_to) if copy_to is not None else [None] * len(buffers)
+    if len(dsts) != len(buffers):
+        raise InvalidArgumentError(-1, '%s: copy_to names %d destinations for %d buffers' % (who, len(dsts), len(buffers)))
+    table, keep = (CrcSlot * len(buffers))(), []
+    for i, (a, d) in enumerate(zip(buffers, dsts)):
+        ptr, n, obj = _crc_span(a, who, 'buffer %d' % i)
+        if n and not ptr:
+            raise InvalidArgumentError(-1, '%s: buffer %d is a NULL pointer with %d bytes' % (who, i, n))
+        dptr = 0
+        if d is not None:
+            if isinstance(d, DeviceBuffer):
+                dptr, room = d.ptr or 0, d.nbytes
+            elif isinstance(d, DeviceTensor):
+                dptr, room = d.ptr, 4 * math.prod(d.shape[:-1]) * d.ld
+            else:
+                dptr, room = int(d), n
+            if room < n:
+                raise InvalidArgumentError(-1, '%s: destination %d holds %d bytes, the buffer %d' % (who, i, room, n))
+        if (ptr | dptr) & 3:
+            raise InvalidArgumentError(-1, '%s: slot %d: src and dst must be 4-byte aligned' % (who, i))
+        table[i] = CrcSlot(ptr or None, dptr or None, n)
+        keep += [obj, d]
+    return table, keep
+
+
+def crc32c_launch(table, out, stream=None, workspace=None, keep=()):
+    """xdet_crc32c over a table of crc32c_table: the CRCs go to `out`, a DeviceBuffer of at least 4 bytes per slot (or a device
+    address); workspace: a DeviceBuffer of at least xdet_crc32c_workspace_bytes bytes (default: allocated here).  Two launches
+    whatever the table; nothing is synchronised.  -> the workspace used"""
+    need = lib().xdet_crc32c_workspace_bytes(table, len(table))
+    if not need:
+        raise InvalidArgumentError(-1, 'crc32c: the table is beyond the limits (65536 slots, 2^22 chunks of 32 KiB)')
+    if isinstance(out, DeviceBuffer) and out.nbytes < 4 * len(table):
+        raise InvalidArgumentError(-1, 'crc32c: out holds %d bytes, %d slots need %d' % (out.nbytes, len(table), 4 * len(table)))
+    ws = _table_workspace(workspace, need, 'crc32c')
+    check(lib().xdet_crc32c(table, len(table), out.ptr if isinstance(out, DeviceBuffer) else int(out), ws.ptr, _handle(stream)))
+    if isinstance(out, DeviceBuffer):
+        out._keep = (ws,) + tuple(keep)
+    return ws
+
+
+def crc32c_device(buffers, copy_to=None, stream=None):
+    """The CRC-32C of every buffer of a table of device buffers, computed where they lie (xdet_crc32c) -> np.uint32[n], each
+    equal to xdet.tf_checkpoint.crc32c of the buffer's bytes (unmasked; an empty buffer gives 0).  copy_to: one destination
+    per buffer (None: none) that receives the buffer's bytes in the same pass, bit for bit.  The call reads the n words back,
+    so it synchronises `stream`; crc32c_table / crc32c_launch are the halves that do not."""
+    table, keep = crc32c_table(buffers, copy_to)
+    out = DeviceBuffer(4 * len(table))
+    crc32c_launch(table, out, stream=stream, keep=keep)
+    got = to_host(out.ptr, (len(table),), np.uint32, stream)
+    out._keep = None
+    return got
 
 
 # ---- the gradient average of data-parallel training (xdet_grad_pack / xdet_grad_reduce_ranks, csrc/grad_average.hip; the

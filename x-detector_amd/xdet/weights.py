@@ -274,3 +274,74 @@ def save_weights_tf_checkpoint(prefix, weights, model_scope='xception_lighthead'
 
 def save_weights_npz(path, weights, model_scope='xception_lighthead'):
     np.savez(path, **{'%s/%s:0' % (model_scope, k): v for k, v in weights.items()})
+
+
+WARM_START_EXCLUDE_SCOPES = ('xception_lighthead/rpn_head', 'xception_lighthead/large_sep_feature', 'xception_lighthead/final_head')
+
+
+def is_trainable(name):
+    """whether a variable of the weights dict is in the reference's TRAINABLE_VARIABLES: every kernel, bias, gamma and beta; a
+    batch norm's moving statistics are not"""
+    return name.rsplit('/', 1)[-1] not in ('moving_mean', 'moving_variance')
+
+
+def warm_start(base, prefix, model_scope='xception_lighthead', checkpoint_model_scope='', exclude_scopes=WARM_START_EXCLUDE_SCOPES,
+               ignore_missing_vars=True):
+    """The reference's fine-tuning start, get_init_fn_for_scaffold (utility/train_helper.py:5-72), stated over a weights dict:
+    -> (weights, report), `weights` a copy of `base` with every restored variable replaced by the checkpoint's tensor.
+      * TRAINABLE variables only (train_helper.py:17): kernels, biases, gamma and beta.  The moving statistics are not in
+        TRAINABLE_VARIABLES, so they are NOT restored and keep `base`'s values -- the reference starts a fine-tuning run from an
+        ImageNet backbone with freshly initialised moving_mean / moving_variance, a quirk kept here because the statement is
+        the reference's.
+      * exclusion is by prefix of the FULL name, '<model_scope>/<variable>' (train_helper.py:20-23); the default is the
+        reference's --checkpoint_exclude_scopes (light_head_rfcn_train.py:158), given as a sequence or its comma-separated
+        string.
+      * the name in the checkpoint (train_helper.py:26-30): checkpoint_model_scope None -> the full name; a scope that is
+        empty after strip() -> the full name with every '<model_scope>/' replaced by checkpoint_model_scope as given;
+        otherwise every '<model_scope>' replaced by checkpoint_model_scope.
+      * an empty restore set raises ValueError('variables_to_restore cannot be empty') (train_helper.py:49-50).
+      * ignore_missing_vars=True: a variable the checkpoint lacks is listed in report['missing'] and keeps base's value;
+        False: it raises CheckpointError naming it (tf.train.Saver's NotFoundError).
+      * a shape (or dtype) mismatch is an error, ValueError naming the variable: the Saver is built with reshape=False.
+    report: {'restored': [variable names], 'missing': [...], 'excluded': [...], 'not_trainable': [...], 'checkpoint_names':
+    {variable: its name in the checkpoint}}, each list in base's order."""
+    from .tf_checkpoint import CheckpointReader, CheckpointError
+    if isinstance(exclude_scopes, str):
+        exclude_scopes = exclude_scopes.split(',')
+    exclusions = [s.strip() for s in (exclude_scopes or ())]
+    report = {'restored': [], 'missing': [], 'excluded': [], 'not_trainable': [], 'checkpoint_names': {}}
+    to_restore = {}
+    for name in base:
+        if not is_trainable(name):
+            report['not_trainable'].append(name)
+            continue
+        full = '%s/%s' % (model_scope, name)
+        if any(full.startswith(e) for e in exclusions):
+            report['excluded'].append(name)
+            continue
+        if checkpoint_model_scope is None:
+            ckpt = full
+        elif checkpoint_model_scope.strip() == '':
+            ckpt = full.replace(model_scope + '/', checkpoint_model_scope)
+        else:
+            ckpt = full.replace(model_scope, checkpoint_model_scope)
+        to_restore[name] = ckpt
+    if not to_restore:
+        raise ValueError('variables_to_restore cannot be empty')
+    rd = CheckpointReader(prefix)
+    out = dict(base)
+    for name, ckpt in to_restore.items():
+        report['checkpoint_names'][name] = ckpt
+        if not rd.has_tensor(ckpt):
+            if not ignore_missing_vars:
+                raise CheckpointError('warm_start: %s (variable %s) is missing in checkpoint %s' % (ckpt, name, prefix))
+            report['missing'].append(name)
+            continue
+        a = rd.get_tensor(ckpt)
+        want = np.asarray(base[name])
+        if tuple(a.shape) != tuple(want.shape) or a.dtype != np.float32:
+            raise ValueError('warm_start: %s has shape %s %s in the checkpoint, the variable %s has %s (reshape=False)'
+                             % (ckpt, a.dtype, tuple(a.shape), name, tuple(want.shape)))
+        out[name] = a
+        report['restored'].append(name)
+    return out, report
